@@ -12,6 +12,12 @@ automatic beta ladder, return per-chain best configurations and energies, and
 
 Weak scaling: every rank runs its own 1024 chains (global replica ids
 rank*1024 ...); value = all ranks' flip attempts / max-over-ranks wall time.
+`ms_per_step` is the wall time of one timed step.
+
+    --dump-outputs DIR  after the timed steps, write what the last step returned (rank 0's
+                        chains) as DIR/<name>.npy: see dump_outputs().
+    --full              also run the secondary measurements below (minutes); a plain run sets up,
+                        warms up, times the steps and prints the line.
 
 The JSON line also carries
   roofline      for the sweep kernel, against the resource that binds it — VALU
@@ -24,7 +30,10 @@ The JSON line also carries
                 off).  Every case of the PMC summary carries the fingerprint of the sources
                 its kernel is built from (kernel file, plan builder, headers, flags) as
                 measured: a case whose sources have changed since is dropped — its `frac`
-                is null and `frac_null_reason` / `stale_counter_cases` say so;
+                is null and `frac_null_reason` / `stale_counter_cases` say so.  The rate
+                with every proposal evaluated takes runs of its own: --full only;
+
+and, with --full (N = 1):
   shuffled_order  the same clusters, chains and sweeps with the reference annealer's
                 visiting order (a fresh random permutation every sweep,
                 asp_sa_anneal_shuffled), and the reference's default call (64 chains x
@@ -59,22 +68,65 @@ CLOCK_GHZ = 2.4         # peak engine clock: the VALU-issue peak is NUM_SIMDS * 
 F64_VALU_PEAK_TFLOPS = 78.6  # vector f64 (MI355X_MICROARCH.md: half the 157.3 TF f32 vector peak)
 CLUSTER_SIZES = (10000, 30000, 100000)
 CLUSTER_SEED = 783494  # experiments/sampled_connected_components.py:621
+DUMP_CHAINS = 64              # chains per cluster whose configurations --dump-outputs writes
+DUMP_SPIN_BYTES = 48 << 20    # cap on those configurations (float32), all clusters together
 
 
 def parse_args():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=5)
-    p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--steps", type=int, default=5, help="timed steps")
+    p.add_argument("--warmup", type=int, default=1, help="untimed steps before them")
+    p.add_argument("--full", action="store_true",
+                   help="also the secondary measurements (CPU baseline, coupling build, other workloads, "
+                        "shuffled order, rate without skipping): minutes")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's results as DIR/<name>.npy")
     p.add_argument("--replicas", type=int, default=1024, help="chains per GPU")
     p.add_argument("--sweeps", type=int, default=128, help="sweeps per step")
     p.add_argument("--sizes", type=str, default=",".join(str(k) for k in CLUSTER_SIZES))
     p.add_argument("--group", type=int, default=0, help="replicas per workgroup (0 = auto)")
     p.add_argument("--threads", type=int, default=0, help="threads per workgroup (0 = auto)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-build", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
+    p.add_argument("--no-build", action="store_true",
+                   help="(--full) leave out the build, default-call, batched, large- and real-cluster legs "
+                        "and the rate without skipping")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
+
+
+def dump_outputs(directory, clusters, replicas):
+    """--dump-outputs: what the last timed step returned to its caller, per cluster of K spins
+    (rank 0's chains):
+
+      energies_K<K>.npy  float64 [replicas]: every chain's best energy;
+      spins_K<K>.npy     float32 [64, K]: the best configurations (bit values 0 / 1, bit j of word
+                         j // 64) of a fixed, seeded sample of 64 chains — beyond 48 MB over all
+                         clusters, of a fixed, seeded sample of the spins as well.
+
+    The inputs are fixed by the arguments (CLUSTER_SEED, seed 12345), so two builds can be
+    compared file by file."""
+    os.makedirs(directory, exist_ok=True)
+    total_spins = sum(c["J"].shape[0] for c in clusters)
+    chains_kept = min(replicas, DUMP_CHAINS)
+    for c in clusters:
+        k = c["J"].shape[0]
+        xs, es = c["last"]
+        xs = np.asarray(xs).view(np.uint64)
+        rng = np.random.default_rng([CLUSTER_SEED, k])
+        chains = np.sort(rng.choice(replicas, chains_kept, replace=False))
+        words = np.ascontiguousarray(xs[chains])
+        bits = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :k]
+        spins_kept = int(DUMP_SPIN_BYTES * k / total_spins) // (4 * chains_kept)
+        if spins_kept < k:
+            bits = bits[:, np.sort(rng.choice(k, max(1, spins_kept), replace=False))]
+        np.save(os.path.join(directory, "energies_K%d.npy" % k), np.asarray(es, dtype=np.float64))
+        np.save(os.path.join(directory, "spins_K%d.npy" % k), bits.astype(np.float32))
 
 
 def _load_profile(name):
@@ -755,8 +807,8 @@ def main():
                 dist.all_gather(parts, mine)
                 torch.stack(parts).cpu()  # every rank ends up with all ranks' best chains
                 # and, as at N = 1, with all of its own chains on the host (same work per rank)
-                c["xs_t"].cpu()
-                c["es_t"].cpu()
+                xs = c["xs_t"].cpu().numpy()
+                es = c["es_t"].cpu().numpy()
             else:
                 xs, es = sa.anneal_raw(c["ham"], 12345, c["betas"], replicas, offset)
                 if use_dist:
@@ -765,6 +817,7 @@ def main():
                     payload = np.concatenate([xs[best].view(np.int64).reshape(1, words),
                                               np.array([[es[best]]]).view(np.int64)], axis=1)
                     asp_dist.all_gather_rows(payload, [1] * world)
+            c["last"] = (xs, es)  # (for --dump-outputs)
             if record:
                 sweep_ms.append((c, lib.asp_sa_last_sweep_ms(c["ham"].plan())))
 
@@ -790,6 +843,8 @@ def main():
     flips_per_step = sum(c["J"].shape[0] for c in clusters) * replicas * args.sweeps
     value = world * flips_per_step * args.steps / elapsed
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, clusters, replicas)
     if rank == 0:
         launch = []
         for c in clusters:
@@ -806,10 +861,10 @@ def main():
 
         counters, traffic, stale = profiled_counters(asp_build.built_source_set_fingerprints())
         # every proposal evaluated: field cache and inert-block skipping off (results identical).
-        # Left out under --no-build, the form the rocprofv3 passes use, so that their per-launch
-        # averages cover the timed workload only.
+        # --full only, and left out under --no-build, the form the rocprofv3 passes use, so that
+        # their per-launch averages cover the timed workload only.
         kernel_flips_no_skip = None
-        if not args.no_build:
+        if args.full and not args.no_build:
             no_skip_ms = 0.0
             for c in clusters:
                 _lib.check(lib.asp_sa_set_field_cache(c["ham"].plan(), 0))
@@ -956,11 +1011,11 @@ def main():
             "value_no_skip": (value * kernel_flips_no_skip / kernel_flips
                               if kernel_flips_no_skip else None),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cores = usable_cores()
             out["cpu_baseline"] = cpu_baseline(clusters[0]["J"], clusters[0]["field"], cores,
                                                args.cpu_seconds)
-        if world == 1 and not args.no_build:
+        if args.full and world == 1 and not args.no_build:
             out["build"] = bench_build(clusters[-1]["J"], 1)
             out["reference_default_call"] = bench_default_call()
             out["batched_small_clusters"] = bench_batched_clusters()
@@ -977,7 +1032,7 @@ def main():
                     "real_kagome_36", counters, out["real_kagome_36_clusters"]["kernel_flips_per_s"])
             except Exception as error:  # a secondary leg never costs the headline line
                 out["real_kagome_36_clusters"] = {"error": "%s: %s" % (type(error).__name__, error)}
-        if world == 1:
+        if args.full and world == 1:
             # (also under --no-build: it is part of what the rocprofv3 passes of the bench see)
             out["shuffled_order"] = bench_shuffled_order(clusters, replicas, args.sweeps, offset, counters)
         print(json.dumps(out))

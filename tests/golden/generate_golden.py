@@ -162,6 +162,25 @@ def export_build_vectors():
                         signs=oracle.ref_extract_signs(psi))
 
 
+REFERENCE_RANDOM_CASES = 12
+
+
+def export_reference_random_cases():
+    """What the reference binary returns for the random cases of
+    tests/test_oracle_build.py::test_oracle_matches_reference_binary_random (inputs regenerated by
+    tests/helpers.py, stored as their digest) as `<seed>_<name>` -> build_matrix_reference_random.npz."""
+    from helpers import BUILD_INPUTS, case_digest, reference_random_case
+
+    out = {}
+    for seed in range(REFERENCE_RANDOM_CASES):
+        case = reference_random_case(seed)
+        nnz, row, col, elements, field = oracle.ref_build_matrix(*[case[k] for k in BUILD_INPUTS])
+        result = dict(inputs_sha256=np.array(case_digest(case)), nnz=nnz, row=row, col=col,
+                      elements=elements, field=field, signs=oracle.ref_extract_signs(case["psi"]))
+        out.update({"%d_%s" % (seed, k): v for k, v in result.items()})
+    np.savez_compressed(os.path.join(HERE, "build_matrix_reference_random.npz"), **out)
+
+
 # ---------------------------------------------------------------------------
 # vectors from the reference's common.py
 # ---------------------------------------------------------------------------
@@ -252,6 +271,7 @@ if __name__ == "__main__":
         raise SystemExit("reference checkout not present; golden vectors are committed")
     models = export_models()
     export_build_vectors()
+    export_reference_random_cases()
     export_common_vectors(load_reference_common(), models)
     for f in sorted(os.listdir(HERE)):
         print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -31,6 +31,29 @@ def random_build_case(rng, num_spins, mean_other, multiword, miss_rate, repeat_c
                 other_psi=rng.normal(size=m))
 
 
+BUILD_INPUTS = ["spins", "counts", "psi", "other_spins", "other_coeffs", "other_counts", "other_psi"]
+
+
+def reference_random_case(seed):
+    """Case `seed` of tests/test_oracle_build.py::test_oracle_matches_reference_binary_random (the
+    reference binary's outputs for it are stored in build_matrix_reference_random.npz)."""
+    rng = np.random.default_rng(1000 + seed)
+    return random_build_case(rng, int(rng.integers(1, 600)), float(rng.uniform(0.5, 20)),
+                             bool(seed % 3 == 0), float(rng.uniform(0, 1)), bool(seed % 2))
+
+
+def case_digest(case):
+    """sha256 of a build case's inputs (dtype, shape and bytes of each), hex."""
+    import hashlib
+
+    h = hashlib.sha256()
+    for k in BUILD_INPUTS:
+        a = np.ascontiguousarray(case[k])
+        h.update(("%s %s %s;" % (k, a.dtype.str, a.shape)).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
 def random_operator(seed, kind, number_spins=14, num_bonds=20, num_keys=700):
     """A random two-site operator, a sorted cluster of random states and unit-norm amplitudes.
 

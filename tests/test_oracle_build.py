@@ -1,14 +1,12 @@
-"""CPU: pin the oracle's coupling-build restatement against the REFERENCE —
-oracle/_ref (cbits/build_matrix.c compiled in place, present in the build
-container) and the committed golden vectors that binary produced."""
+"""CPU: pin the oracle's coupling-build restatement against the REFERENCE — the
+committed golden vectors its cbits/build_matrix.c (compiled in place into
+oracle/_ref by tests/golden/generate_golden.py) produced."""
 import numpy as np
 import pytest
 
 import oracle
 from conftest import golden
-from helpers import random_build_case
-
-INPUTS = ["spins", "counts", "psi", "other_spins", "other_coeffs", "other_counts", "other_psi"]
+from helpers import BUILD_INPUTS as INPUTS, case_digest, reference_random_case
 
 
 def _bits(a):
@@ -40,19 +38,19 @@ def test_extract_signs_golden_and_edge_values():
     assert oracle.extract_signs(psi)[0] == 0b10100001  # only strictly positive values
 
 
-@pytest.mark.skipif(oracle.ref_lib() is None, reason="reference checkout/_ref build not present")
 @pytest.mark.parametrize("seed", range(12))
 def test_oracle_matches_reference_binary_random(seed):
-    rng = np.random.default_rng(1000 + seed)
-    case = random_build_case(rng, int(rng.integers(1, 600)), float(rng.uniform(0.5, 20)),
-                             bool(seed % 3 == 0), float(rng.uniform(0, 1)), bool(seed % 2))
-    args = [case[k] for k in INPUTS]
-    a = oracle.build_matrix(*args)
-    b = oracle.ref_build_matrix(*args)
-    assert a[0] == b[0]
+    """Twelve random cases against what the reference binary (oracle/_ref) returned for them,
+    stored by tests/golden/generate_golden.py: build_matrix_reference_random.npz."""
+    case = reference_random_case(seed)
+    g = golden("build_matrix_reference_random.npz")
+    assert str(g["%d_inputs_sha256" % seed]) == case_digest(case), "the stored outputs are of other inputs"
+    a = oracle.build_matrix(*[case[k] for k in INPUTS])
+    b = [g["%d_%s" % (seed, k)] for k in ("nnz", "row", "col", "elements", "field")]
+    assert a[0] == int(b[0])
     for x, y in zip(a[1:], b[1:]):
         assert _bits(x) == _bits(y)
-    assert np.array_equal(oracle.extract_signs(case["psi"]), oracle.ref_extract_signs(case["psi"]))
+    assert np.array_equal(oracle.extract_signs(case["psi"]), g["%d_signs" % seed])
 
 
 def test_key_order_is_word0_major():

@@ -6,11 +6,11 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-build > $OUT/bench_trace.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-build > $OUT/bench_trace.log 2>&1 || exit 1
 hipcc --offload-arch=gfx950 -O3 tools/fetch_calibrate.hip -o /tmp/fetch_calibrate > $OUT/calib_build.log 2>&1 || exit 6
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_calib -- /tmp/fetch_calibrate > $OUT/pmc_calib.log 2>&1 || exit 7
 # the SAME command as the bench line (rank 0, N=1), minus the CPU legs
-ARGS="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-build"
+ARGS="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-build"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python $ARGS > $OUT/pmc_fetch.log 2>&1 || exit 2
 rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/pmc_l2 -- python $ARGS > $OUT/pmc_l2.log 2>&1 || exit 3
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS --output-format csv -d $OUT/pmc_sq1 -- python $ARGS > $OUT/pmc_sq1.log 2>&1 || exit 4
