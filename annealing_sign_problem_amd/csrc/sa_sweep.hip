@@ -6,9 +6,9 @@
 // Mapping to the machine
 //   * one workgroup = one GROUP of M replicas (M in {1,2,4,8}); the whole anneal
 //     (all sweeps) is ONE launch, the spins never leave LDS;
-//   * LDS: one byte per (padded) spin position, bit m = sign bit of replica m
-//     (1 means s = -1), so one ds_read_u8 serves all M replicas of a neighbour
-//     (kBytes); a 32-bit word per position for M = 4 on small clusters, where
+//   * LDS: one byte per (padded) spin position, bit 2m (M <= 4) or bit m (M = 8)
+//     = sign bit of replica m (1 means s = -1), so one ds_read_u8 serves all M
+//     replicas of a neighbour (kBytes); a 32-bit word per position for M = 4 on small clusters, where
 //     the sign of a term is one SDWA instruction (kWide); beyond the capacity of
 //     bytes one BIT per position and one replica per workgroup, flips applied
 //     by a wavefront ballot (kBits), and beyond 1.3e6 spins the same bit words
@@ -22,8 +22,9 @@
 //     colour means no couplings inside the block, so the 64 x M proposals of a
 //     block are independent and are decided at once;
 //   * couplings stream from the quad-interleaved sliced ELL: per four terms a
-//     lane issues three 16-byte loads (every wavefront instruction covers 1 KiB
-//     of contiguous memory), shared by M replicas, one quad prefetched ahead;
+//     lane issues three 16-byte buffer loads (every wavefront instruction covers
+//     1 KiB of contiguous memory; the quad is a scalar offset), shared by M
+//     replicas, one quad prefetched ahead;
 //   * dE is an f64 sum in fixed row order (bit-exact against the oracle), the
 //     acceptance uses a counter-based Philox4x32-10 word per (spin, sweep,
 //     replica) and a fixed-sequence exp reached through a hardware-exp filter,
@@ -97,6 +98,122 @@ __device__ __forceinline__ void store_word(uint64_t *p, uint64_t v) {
   }
 }
 
+// kBytes with M <= 4 keeps replica m at bit 2m of the spin byte (the odd bits stay 0); M = 8
+// fills the byte and keeps bit m.  With the even bits the high word of the term's +-1.0 is
+//   (byte << (31 - 2m)) | 0x3FF00000   (one v_lshl_or_b32)
+// for every m: bit 2m lands on bit 31, the higher replica bits leave the word, the lower ones
+// land on bits 29, 27 or 25 (already 1 in 0x3FF00000) and bit 30 receives an odd bit, always 0.
+// With bit m = replica m that shift drags replica m - 1 into bit 30.  Replica MASKS (flip, the
+// dirty and inert bytes, snapshot's `mask`) stay indexed by replica; encode_replicas() turns
+// one into spin-byte bits where it meets the byte.
+template <int M, int LAYOUT>
+constexpr bool kEvenBits = LAYOUT == kBytes && M <= 4;
+
+template <int M, int LAYOUT>
+__device__ __forceinline__ constexpr int replica_bit(int m) {
+  return kEvenBits<M, LAYOUT> ? 2 * m : m;
+}
+
+template <int M, int LAYOUT>
+__device__ __forceinline__ uint32_t encode_replicas(uint32_t mask) {
+  if constexpr (kEvenBits<M, LAYOUT>) {
+    return (mask & 1u) | ((mask & 2u) << 1) | ((mask & 4u) << 2) | ((mask & 8u) << 3);
+  } else {
+    return mask;
+  }
+}
+
+__device__ __forceinline__ double even_spin_factor(uint32_t spin_byte, int m) {
+  return __hiloint2double(static_cast<int>((spin_byte << (31 - 2 * m)) | 0x3FF00000u), 0);
+}
+
+// The ELL stream of one block through BUFFER loads: the resource's base is the block's first
+// quad (scalar, set up once per visit), the quad is a scalar offset (quad * 1024 B of columns,
+// quad * 2048 B of values) and the lane part a vector offset fixed for the whole kernel, so a
+// quad costs no vector address arithmetic.  Offsets are relative to the block, so any plan size
+// fits the 32-bit offsets.
+using BufferRsrc = __amdgpu_buffer_rsrc_t;
+__device__ __forceinline__ BufferRsrc block_rsrc(const void *base) {
+  // raw buffer, 4 GiB range, gfx9 DATA_FORMAT word
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0xFFFFFFFF, 0x00020000);
+}
+struct BlockStream {
+  BufferRsrc col, val;
+  uint32_t lane16;  // lane * 16
+  const uint4 *cptr;      // (the ablation builds of load_quad only)
+  const double2 *vptr;
+};
+
+__device__ __forceinline__ void load_quad(Quad &q, const BlockStream &s, uint32_t quad) {
+#if ASP_ABL_NO_GLOAD || ASP_ABL_HALF_BYTES
+  load_quad(q, s.cptr, s.vptr, quad);
+#else
+  q.c = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(s.col, s.lane16, quad * 1024u, 0));
+  q.v01 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(s.val, s.lane16, quad * 2048u, 0));
+  q.v23 = __builtin_bit_cast(double2,
+                             __builtin_amdgcn_raw_buffer_load_b128(s.val, s.lane16 + 1024u, quad * 2048u, 0));
+#endif
+}
+
+// kWide: wide_factor's SDWA rewrites the top byte of a multiplier held as a whole f64 whose low
+// word stays 0 for the whole anneal (rebuilt from `hi` and a literal 0, as wide_factor returns
+// it, the pair was re-assembled and low words re-zeroed inside the k-loop).
+__device__ __forceinline__ double wide_factor_held(uint32_t word, int m, double &mult) {
+  uint32_t hi = static_cast<uint32_t>(__double2hiint(mult));
+  wide_factor(word, m, hi);
+  mult = __hiloint2double(static_cast<int>(hi), __double2loint(mult));
+  return mult;
+}
+
+// The row sums of one quad.  The even-bit byte layout gathers its four bytes and takes each
+// sign with one v_lshl_or_b32 that the compiler schedules (plain C++: no inline asm, so no
+// hazard padding); kWide takes its SDWA sign into a held multiplier.  Both neighbour-major (each
+// acc[m] still receives its terms in ascending k).  The other layouts go through
+// sa_device.hpp's accumulate_quad.
+template <int M, int LAYOUT>
+__device__ __forceinline__ void accumulate(const Quad &q, const uint8_t *spins, double (&acc)[M],
+                                           uint32_t (&one_hi)[4], double (&mult)[4]) {
+  if constexpr (kEvenBits<M, LAYOUT> || LAYOUT == kWide) {
+    const uint32_t cs[4] = {q.c.x, q.c.y, q.c.z, q.c.w};
+    const double vs[4] = {q.v01.x, q.v01.y, q.v23.x, q.v23.y};
+    uint32_t s[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#if ASP_ABL_NO_LDS
+      s[j] = cs[j] & 15u;
+#else
+      if constexpr (LAYOUT == kWide) {
+        s[j] = *reinterpret_cast<LdsWord *>(static_cast<uintptr_t>(cs[j]));
+      } else {
+#if ASP_ABS_LDS
+        s[j] = *reinterpret_cast<LdsByte *>(static_cast<uintptr_t>(cs[j]));
+#else
+        s[j] = spins[cs[j]];
+#endif
+      }
+#endif
+    }
+#if ASP_ABL_NO_FMA
+    asm volatile("" ::"v"(s[0]), "v"(s[1]), "v"(s[2]), "v"(s[3]), "v"(vs[0]), "v"(vs[1]),
+                 "v"(vs[2]), "v"(vs[3]));
+    return;
+#endif
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        if constexpr (LAYOUT == kWide) {
+          acc[m] = __builtin_fma(vs[j], wide_factor_held(s[j], m, mult[m & 3]), acc[m]);
+        } else {
+          acc[m] = __builtin_fma(vs[j], even_spin_factor(s[j], m), acc[m]);
+        }
+      }
+    }
+  } else {
+    accumulate_quad<M, LAYOUT>(q, spins, acc, one_hi);
+  }
+}
+
 // (`Args` is SweepArgs, or SweepArgs in the constant address space: see k_sa_sweep_batch)
 template <int M, int LAYOUT, typename Args>
 __device__ __forceinline__ void snapshot(const uint8_t *spins, const Args &a, uint32_t group,
@@ -153,11 +270,12 @@ __device__ __forceinline__ void snapshot(const uint8_t *spins, const Args &a, ui
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       if (!((mask >> m) & 1u)) continue;
+      const int bit = replica_bit<M, LAYOUT>(m);
       uint64_t word = 0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const uint32_t nib = gather_bit4(q[j].x, m) | (gather_bit4(q[j].y, m) << 4) |
-                             (gather_bit4(q[j].z, m) << 8) | (gather_bit4(q[j].w, m) << 12);
+        const uint32_t nib = gather_bit4(q[j].x, bit) | (gather_bit4(q[j].y, bit) << 4) |
+                             (gather_bit4(q[j].z, bit) << 8) | (gather_bit4(q[j].w, bit) << 12);
         word |= static_cast<uint64_t>(nib) << (16 * j);
       }
       a.best_perm[(static_cast<uint64_t>(group) * M + m) * a.num_blocks + w] = word;
@@ -226,7 +344,8 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     uint32_t byte = 0;
     if (spin != kDummySpin) {
       if (a.x0_perm != nullptr) {
-        byte = ((a.x0_perm[p >> 6] >> (p & 63u)) & 1ull) ? ((1u << M) - 1u) : 0u;  // replica mask
+        byte = ((a.x0_perm[p >> 6] >> (p & 63u)) & 1ull) ? encode_replicas<M, LAYOUT>((1u << M) - 1u)
+                                                         : 0u;  // every replica
       } else {
         Philox4 rnd{};
         uint32_t have = 0xFFFFFFFFu;
@@ -238,7 +357,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
             rnd = philox4x32_10(spin, 0xFFFFFFFFu, have, 0u, key0, key1);
           }
           const uint32_t up = pick_word(rnd, r & 3u) & 1u;  // 1 -> s = +1 -> sign bit 0
-          byte |= (up ^ 1u) << m;
+          byte |= (up ^ 1u) << replica_bit<M, LAYOUT>(m);
         }
       }
     }
@@ -274,6 +393,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     a.trace[(static_cast<uint64_t>(group) * M + tid) * (a.num_sweeps + 1ull)] = 0;
   }
   uint32_t one_hi[4] = {0x3FF00000u, 0x3FF00000u, 0x3FF00000u, 0x3FF00000u};
+  double mult[4] = {1.0, 1.0, 1.0, 1.0};  // kWide's multipliers (low words stay 0)
   for (uint32_t t = 0; t < a.num_sweeps; ++t) {
     const double beta = a.betas[t];
     // wave-uniform: cached fields are in use during this sweep
@@ -328,6 +448,9 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
         const uint4 *cptr = reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u + lane;
         const double2 *vptr =
             reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u + lane;
+        const BlockStream stream{block_rsrc(reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u),
+                                 block_rsrc(reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u),
+                                 lane * 16u, cptr, vptr};
         // issued now, consumed after the row sum: their latency hides under the k-loop
         const uint32_t spin = a.spin_of_pos[p];
         const double h = a.field_pos[p];
@@ -359,19 +482,19 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
           // even quad count the last load reads one quad past the block — the next block's
           // first slabs or the tail padding the plan appends — and is never consumed.
           Quad qa, qb;
-          load_quad(qa, cptr, vptr, 0);
+          load_quad(qa, stream, 0);
           uint32_t i = 0;
           for (; i + 2 <= quads_run; i += 2) {
-            load_quad(qb, cptr, vptr, i + 1);
+            load_quad(qb, stream, i + 1);
             __builtin_amdgcn_sched_barrier(0);
-            accumulate_quad<M, LAYOUT>(qa, spins, acc, one_hi);
+            accumulate<M, LAYOUT>(qa, spins, acc, one_hi, mult);
             __builtin_amdgcn_sched_barrier(0);
-            load_quad(qa, cptr, vptr, i + 2);
+            load_quad(qa, stream, i + 2);
             __builtin_amdgcn_sched_barrier(0);
-            accumulate_quad<M, LAYOUT>(qb, spins, acc, one_hi);
+            accumulate<M, LAYOUT>(qb, spins, acc, one_hi, mult);
             __builtin_amdgcn_sched_barrier(0);
           }
-          if (i < quads_run) accumulate_quad<M, LAYOUT>(qa, spins, acc, one_hi);
+          if (i < quads_run) accumulate<M, LAYOUT>(qa, spins, acc, one_hi, mult);
           if (cached) {
 #pragma unroll
             for (int m = 0; m < M; ++m) cache_row[m * 64] = acc[m];
@@ -397,7 +520,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
 #pragma unroll
         for (int m = 0; m < M; ++m) {
           const double g = __dadd_rn(acc[m], h);
-          const bool negative = (own >> (WIDE ? 8 * m + 7 : m)) & 1u;  // s = -1
+          const bool negative = (own >> (WIDE ? 8 * m + 7 : replica_bit<M, LAYOUT>(m))) & 1u;  // s = -1
           de[m] = __dmul_rn(negative ? 2.0 : -2.0, g);
           if constexpr (DESCENT) {
             open = open || (valid && de[m] < 0.0);
@@ -499,7 +622,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
           // instruction: an LDS atomic on the word (eight positions) instead of a byte store
           if (flip) atomicXor(reinterpret_cast<uint32_t *>(spins) + (p >> 3), flip << ((p & 7u) << 2));
         } else {
-          if (flip) spins[p] = static_cast<uint8_t>(own ^ flip);
+          if (flip) spins[p] = static_cast<uint8_t>(own ^ encode_replicas<M, LAYOUT>(flip));
         }
 #if ASP_INERT_SKIP
         if (cached) {
