@@ -55,43 +55,22 @@ namespace {
 
 using asp::DeviceBuffer;
 
-// Timing-only ablations of k_search_flat (results are WRONG when set; never set in the product
-// build): 1 no probe, 2 probe without the verifying load, 3 every trip re-reads the chunk's first
-// 4 KiB (no HBM stream), 4 no pass through LDS (a lane takes the first piece it loaded for its
-// key), 5 one 16-byte load per probe instead of the bucket's four, 6 no result stores
-#ifndef ASP_BUILD_ABL
-#define ASP_BUILD_ABL 0
-#endif
-
 constexpr int kThreads = 256;
 constexpr int kRowLanes = 32;                         // lanes cooperating on one row (k_emit_rows)
 constexpr int kRowsPerBlock = kThreads / kRowLanes;   // 8
 constexpr uint32_t kGroup = 64;                       // needles a wavefront resolves per trip
 constexpr uint32_t kSearchWaves = kThreads / 64;      // 4
-#ifndef ASP_BUILD_SLOTS_PER_KEY
-#define ASP_BUILD_SLOTS_PER_KEY 2
-#endif
-constexpr uint64_t kSlotsPerKey = ASP_BUILD_SLOTS_PER_KEY;  // the hash's load factor is at most its inverse
-#ifndef ASP_BUILD_TRIPS
-#define ASP_BUILD_TRIPS 8
-#endif
-constexpr uint32_t kTrips = ASP_BUILD_TRIPS;          // trips of a wavefront of k_search_flat (4 / 8 / 16: the same)
+constexpr uint64_t kSlotsPerKey = 2;                  // the hash's load factor is at most its inverse
+constexpr uint32_t kTrips = 8;                        // trips of a wavefront of k_search_flat (4 / 8 / 16: the same)
 constexpr uint32_t kGroupsPerChunk = kSearchWaves * kTrips;  // 32: a chunk = a workgroup = 2048 needles
 constexpr uint32_t kChunk = kGroupsPerChunk * kGroup;
 constexpr uint32_t kChunksPerSuper = 64;              // 131072 needles
 static_assert(kGroupsPerChunk <= 64 && kChunksPerSuper <= 64, "one wavefront sums a level");
 constexpr uint32_t kStagePlaces = kGroup * 5;         // 16-byte places of a wavefront's LDS staging area
-// (slots of a bucket: 8, 4 or 2.  Measured at K = 1e5, search / insert in us: eight 70.4 / 12.5,
-// four — half the bytes per probe, ~8 % of the look-ups in a second bucket — 66.8 / 15.1, two
-// 67.8 / 13.6, two at a load factor <= 1/4 66.5 / 9.4: 126-128 us per build whichever.  The
-// timing-only ablations above say where the search's 70 us are: 22 without any probe (the keys
-// alone, largely from the 256 MB last-level cache on repeated runs), 56 with one 16-byte load per
-// probe and the chain cut there, 59 without the verifying load, 68 without the stores, 42 with
-// the keys re-read from L2 — the dependent look-up, not the bytes.)
-#ifndef ASP_BUILD_BUCKET
-#define ASP_BUILD_BUCKET 8
-#endif
-constexpr uint32_t kBucket = ASP_BUILD_BUCKET;        // hash slots a probe reads
+// (slots of a bucket: buckets of 4 or 2 slots, or 2 at a load factor <= 1/4, measured 126-128 us
+// per build like 8.  The search's 70 us at K = 1e5 are the dependent look-up, not the bytes:
+// DESIGN.md §3 records the per-variant and ablation timings.)
+constexpr uint32_t kBucket = 8;                       // hash slots a probe reads
 
 // One hash slot: {fingerprint: the hash's high word | index + 1}, 0 = empty.  Eight bytes, so that
 // the whole hash (load factor <= 1/2: 2 MiB at K = 1e5) and the first words it is verified against
@@ -139,39 +118,16 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // compiler's own waits run.
 // The slots of one bucket, two to a 16-byte load:
 __device__ __forceinline__ void load_bucket(const Slot *bucket, u32x4 (&s)[kBucket / 2]) {
-  static_assert(kBucket == 8 || kBucket == 4 || kBucket == 2, "the loads are spelled out");
-#if ASP_BUILD_ABL == 5
-  {
-    asm volatile("global_load_dwordx4 %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=&v"(s[0]) : "v"(bucket) : "memory");
-    for (uint32_t j = 1; j < kBucket / 2; ++j) s[j] = u32x4{0u, 0u, 0u, 0u};
-  }
-#elif ASP_BUILD_BUCKET == 8
-  {
-    asm volatile(
-        "global_load_dwordx4 %0, %4, off\n\t"
-        "global_load_dwordx4 %1, %4, off offset:16\n\t"
-        "global_load_dwordx4 %2, %4, off offset:32\n\t"
-        "global_load_dwordx4 %3, %4, off offset:48\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3])
-        : "v"(bucket)
-        : "memory");
-  }
-#elif ASP_BUILD_BUCKET == 2
-  {
-    asm volatile("global_load_dwordx4 %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=&v"(s[0]) : "v"(bucket) : "memory");
-  }
-#else
-  {
-    asm volatile(
-        "global_load_dwordx4 %0, %2, off\n\t"
-        "global_load_dwordx4 %1, %2, off offset:16\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(s[0]), "=&v"(s[1])
-        : "v"(bucket)
-        : "memory");
-  }
-#endif
+  static_assert(kBucket == 8, "the loads are spelled out");
+  asm volatile(
+      "global_load_dwordx4 %0, %4, off\n\t"
+      "global_load_dwordx4 %1, %4, off offset:16\n\t"
+      "global_load_dwordx4 %2, %4, off offset:32\n\t"
+      "global_load_dwordx4 %3, %4, off offset:48\n\t"
+      "s_waitcnt vmcnt(0)"
+      : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3])
+      : "v"(bucket)
+      : "memory");
 }
 
 // Index in the table of the needle with hash h, or -1 (`verify(index)`: the needle IS
@@ -234,8 +190,7 @@ __device__ __forceinline__ void search_flat_body(
   // piece: under a branch hipcc would wait for every load where it is issued)
   uint4 buf[4];
   auto request = [&](uint32_t k) {
-    const uint32_t slice = ASP_BUILD_ABL == 3 ? 0u : k;
-    const uint64_t piece0 = (chunk_first + static_cast<uint64_t>(slice * kSearchWaves + wave) * kGroup) * 4u + lane;
+    const uint64_t piece0 = (chunk_first + static_cast<uint64_t>(k * kSearchWaves + wave) * kGroup) * 4u + lane;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const uint64_t piece = piece0 + static_cast<uint64_t>(i) * kGroup;
@@ -252,13 +207,13 @@ __device__ __forceinline__ void search_flat_body(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const uint32_t piece = i * kGroup + lane;  // piece & 3 of key piece >> 2
-      if (ASP_BUILD_ABL != 4) mine[piece + (piece >> 2)] = buf[i];
+      mine[piece + (piece >> 2)] = buf[i];
     }
     __builtin_amdgcn_wave_barrier();  // same wavefront: LDS ops are in order, keep them so
     uint64_t key[8];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const uint4 q = ASP_BUILD_ABL == 4 ? buf[0] : mine[lane * 5 + j];
+      const uint4 q = mine[lane * 5 + j];
       key[2 * j] = (static_cast<uint64_t>(q.y) << 32) | q.x;
       key[2 * j + 1] = (static_cast<uint64_t>(q.w) << 32) | q.z;
     }
@@ -277,7 +232,6 @@ __device__ __forceinline__ void search_flat_body(
     const bool wanted = e < num_needles && (HAS_TAILS || needle_tail == 0);
     const uint64_t h = mix64(key[0]);
     auto verify = [&](uint32_t at) {
-      if (ASP_BUILD_ABL == 2) return true;
       if (table0[at] != key[0]) return false;  // (an L2 hit: 8 K bytes in all)
       if (!HAS_TAILS) return true;
       // word 0 matches: the full 512-bit keys must agree (cbits/build_matrix.c:11-18)
@@ -289,10 +243,10 @@ __device__ __forceinline__ void search_flat_body(
     // (tried: four lanes per bucket, 16 bytes each, the hash by shuffle and the verdict through LDS —
     // a quarter of the lines per load instruction, and slower: 100 against 71 us)
     int32_t idx = -1;
-    if (ASP_BUILD_ABL != 1 && wanted) idx = find_key(slots, bucket_mask, h, verify);
-    if (e < num_needles && (ASP_BUILD_ABL != 6 || idx == 12345)) found[e] = idx;
+    if (wanted) idx = find_key(slots, bucket_mask, h, verify);
+    if (e < num_needles) found[e] = idx;
     const uint32_t hcount = static_cast<uint32_t>(__popcll(__ballot(idx >= 0)));
-    if (lane == 0 && (ASP_BUILD_ABL != 6 || hcount == 99)) group_hits[group] = hcount;
+    if (lane == 0) group_hits[group] = hcount;
     hits += hcount;
   }
   // hits of the chunk: to its own total and, atomically, to the total of its super-chunk

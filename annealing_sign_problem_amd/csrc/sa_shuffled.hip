@@ -49,6 +49,14 @@ using asp::DeviceBuffer;
 using asp::kDummySpin;
 using namespace asp::dev;
 
+// Development aid (-DASP_SHUF_TIMING=1): every wavefront of workgroup 0 adds up the shader-clock
+// cycles it spends in the row sums, the request, the accept phase, the level barriers and the
+// per-sweep bookkeeping, wavefront 0 of the order kernel those of its phases; the totals land
+// behind the status words (tools/time_shuffled.py --timing).
+#ifndef ASP_SHUF_TIMING
+#define ASP_SHUF_TIMING 0
+#endif
+
 constexpr uint32_t kPriorityCounter = 0xFFFFFFFEu;  // counter word 2 of the priority draw
 constexpr uint32_t kOrderThreads = 1024;            // threads of an order workgroup (large K)
 constexpr uint32_t kClassCap = 63;                  // rows of >= 63 quads share the last class
@@ -279,10 +287,7 @@ struct PeelArrays {
 
 // (`Args` is OrderArgs, or OrderArgs in the constant address space: the batched kernel reads its
 // problem's descriptor from a table, like k_sa_sweep_batch does; `s` = sweep of the chunk)
-#ifndef ASP_SHUF_PEEL_ROWS
-#define ASP_SHUF_PEEL_ROWS 4
-#endif
-constexpr int kPeelRows = ASP_SHUF_PEEL_ROWS;  // rows in flight per group of lanes (kPeelLdsCounters)
+constexpr int kPeelRows = 4;  // rows in flight per group of lanes (kPeelLdsCounters)
 
 template <int MODE, typename Args>
 __device__ __forceinline__ void shuffled_orders_impl(const Args &a, const uint32_t s) {
@@ -1130,7 +1135,7 @@ __device__ __forceinline__ void gather_quad(const HeldQuad &q, uint32_t (&s)[4],
   }
 }
 
-// high word of +-1.0 from byte m of a wide spin word, in place (see wide_factor)
+// high word of +-1.0 from byte m of a wide spin word, in place (as sa_sweep.hip's wide_factor)
 #define ASP_SDWA_SIGN(sel)                                                                         \
   asm volatile("v_or_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD " \
                "src1_sel:" sel : "+v"(hi) : "v"(0x3Fu), "v"(word))
@@ -1182,22 +1187,6 @@ __device__ __forceinline__ void apply_quad(const HeldQuad &q, const uint32_t (&s
   }
 }
 
-// Timing-only ablations (results are WRONG when set; never set in the product build):
-// 1 no row sums, 2 no accept phase, 3 no coupling loads, 4 no level barriers, 5 a cheap hash for
-// Philox, 6 a cheap compare for the exp filter
-#ifndef ASP_SHUF_ABL
-#define ASP_SHUF_ABL 0
-#endif
-
-// Development aid (-DASP_SHUF_TIMING=1): every wavefront of workgroup 0 adds up the shader-clock
-// cycles it spends in the row sums, the request, the accept phase, the level barriers and the
-// per-sweep bookkeeping; the totals land behind the status words (tools/time_shuffled.py --timing).
-#ifndef ASP_SHUF_TIMING
-#define ASP_SHUF_TIMING 0
-#endif
-#ifndef ASP_SHUF_ABLATE_ENV
-#define ASP_SHUF_ABLATE_ENV 0  // 1: honour $ASP_SHUFFLED_ABLATE (timing-only launches that skip work: WRONG results)
-#endif
 #if ASP_SHUF_TIMING
 #define ASP_TICK(slot)                                  \
   do {                                                  \
@@ -1210,21 +1199,16 @@ __device__ __forceinline__ void apply_quad(const HeldQuad &q, const uint32_t (&s
 #endif
 
 constexpr uint32_t kNoBlock = 0xFFFFFFFFu;
-#ifndef ASP_SHUF_HELD_QUADS
-#define ASP_SHUF_HELD_QUADS 12
-#endif
 // quads of a block kept in registers (wider blocks stream the rest).  Scanned in round 4 on the
-// production batch and on K = 1e4 x 1024 chains (-DASP_SHUF_HELD_QUADS=6/8/10/12): fewer held quads
+// production batch and on K = 1e4 x 1024 chains (6/8/10/12): fewer held quads
 // free registers (10: the order kernel fits beside two sweep wavefronts per SIMD; 6: three sweep
 // wavefronts per SIMD) but every step down lengthens a visit, 22.3 / 25.1 / 27.8 / 31.6 ms for
 // 12 / 10 / 8 / 6 on the single cluster.
-constexpr int kHeldQuads = ASP_SHUF_HELD_QUADS;
-#ifndef ASP_SHUF_FIRST_QUADS
-#define ASP_SHUF_FIRST_QUADS 6
-#endif
+constexpr int kHeldQuads = 12;
 // quads of the next block requested BEFORE the accept phase (the rest after it: what is requested
 // late must land during the level barrier, so as much as the miss queue takes goes out early)
-constexpr int kFirstQuads = ASP_SHUF_FIRST_QUADS < kHeldQuads ? ASP_SHUF_FIRST_QUADS : kHeldQuads;
+constexpr int kFirstQuads = 6;
+static_assert(kFirstQuads <= kHeldQuads, "the first request is part of the held quads");
 
 // The loads of a block do not depend on the spins, so a wavefront fetches its NEXT block — of this
 // level or of the next one — while it finishes the current one: the quads of the next block are
@@ -1267,11 +1251,10 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
   constexpr uint32_t CH = PK ? 64u : 8u;  // chains of a workgroup the bookkeeping arrays hold
   extern __shared__ __align__(16) uint8_t lds[];
   if (a.status[kStatBad] != 0u) return;  // an order kernel ran out of room: the host repeats the call
-#if ASP_ABS_LDS
+  // gather_quad addresses the spins absolutely: the dynamic LDS block must be the first
   if (reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t *)lds) != 0) {
     __builtin_trap();
   }
-#endif
   const uint32_t K = a.num_spins;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   // The problem's own wavefronts: in a shared launch (k_sa_sweep_shuffled_batch) the workgroups have
@@ -1304,17 +1287,6 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
   const uint32_t waves = a.waves;
   const uint32_t team = TEAMS == 1 ? 0u : __builtin_amdgcn_readfirstlane(tid >> 6) / waves;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6) - team * waves;
-#ifdef ASP_SHUF_PRIO
-  // experiment: the wavefront with the widest blocks of every level (wave 0: the levels are sorted
-  // by row length) issues first where it shares a SIMD with another workgroup's wavefront
-  if (wave == 0) {
-    __builtin_amdgcn_s_setprio(3);
-  } else if (wave == 1) {
-    __builtin_amdgcn_s_setprio(2);
-  } else if (wave == 2) {
-    __builtin_amdgcn_s_setprio(1);
-  }
-#endif
   const uint32_t r0 = a.replica_first + group * MT;  // first chain of the (lane's) group
   const uint32_t c0 = team * M;                      // first chain of this wavefront's team
   // this team's chains inside a spin's LDS word (byte per chain) or byte (bit per chain)
@@ -1438,7 +1410,7 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
     auto request_quads = [&](int lo, int hi) {
 #pragma unroll
       for (int j = lo; j < hi; ++j) {
-        if (ASP_SHUF_ABL != 3 && static_cast<uint32_t>(j) < held_quads) {
+        if (static_cast<uint32_t>(j) < held_quads) {
           load_quad_at(hq[j], static_cast<uint32_t>(j));
         } else {
           hq[j].c = __builtin_nondeterministic_value(hq[j].c);
@@ -1492,7 +1464,7 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
         double acc[M];
 #pragma unroll
         for (int m = 0; m < M; ++m) acc[m] = 0.0;
-        if (busy && ASP_SHUF_ABL != 1) {
+        if (busy) {
           const uint32_t quads = held_quads;
           // the row sums in the order k = 0, 1, 2, ... of the row (= ascending column: the
           // oracle's); the LDS gather of quad j + 1 is issued before the FMAs of quad j (past the
@@ -1538,7 +1510,7 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
         request_first(nb);
         __builtin_amdgcn_sched_barrier(0);
         ASP_TICK(1);
-        if (busy && ASP_SHUF_ABL != 2) {
+        if (busy) {
           // (this team's chains only: the partner team owns the other half of the word / byte)
           const uint32_t own = PK ? wide[(gbase >> 2) + me] : read_spin<LAYOUT>(spins, me) >> team_shift;
           bool need = false;  // some proposal of this lane needs a random number
@@ -1560,19 +1532,10 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
               const uint32_t r = r0 + c0 + m;
               if (m == 0 || (r >> 2) != have) {
                 have = r >> 2;
-#if ASP_SHUF_ABL == 5
-                rnd = Philox4{{spin * 2654435761u ^ t, spin ^ (t * 40503u), spin + have, t ^ key0}};
-#else
                 rnd = philox4x32_10(spin, t, have, 0u, key0, key1);
-#endif
               }
-#if ASP_SHUF_ABL == 6
-              const bool accept = valid && (de[m] <= 0.0 || pick_word(rnd, r & 3u) <
-                                                                static_cast<uint32_t>(__dmul_rn(beta, de[m])));
-#else
               const bool accept = valid && (de[m] <= 0.0 || metropolis_accept_word(pick_word(rnd, r & 3u),
                                                                                    __dmul_rn(beta, de[m])));
-#endif
               flip |= (accept ? 1u : 0u) << m;
             }
           } else {
@@ -1620,11 +1583,9 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
         if (!same_level) break;
         b = nb;
       }
-#if ASP_SHUF_ABL != 4
       // (spins in HBM: the flips must have arrived before another wavefront gathers them)
       if constexpr (GLOBAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-#endif
       ASP_TICK(3);
       lb_begin = lb_end;
       lb_end = lb_after;
@@ -1903,7 +1864,6 @@ struct ShuffledRun {
   uint64_t padded = 0;
   int m = 1, teams = 1, attempt = 0;
   int forced_m = 0;      // chains per workgroup chosen by the batched driver (0: by this run)
-  uint32_t order_threads_cap = 0;  // set by the batched driver: threads of an order workgroup at most
   bool batch_saturates = false;    // set by the batched driver: the batch has more workgroups than the chip holds
   bool batched = false;  // launched by the batched driver: no timing events of its own
   bool trivial = false;  // nothing to launch (no spins or no chains)
@@ -1913,12 +1873,9 @@ struct ShuffledRun {
   // the sweep kernel of a third: an order workgroup is a chain of dependent global accesses (23 ms
   // for a sweep of 1e5 spins), so their THROUGHPUT is workgroups in flight / that latency, and a
   // 128-sweep call has only 32 sweeps per chunk to offer.
-  // (round 4, -DASP_SHUF_LANES=2/3/4/6: no difference on the kagome_36 pipeline — 23.6 / 23.7 / 23.1 s —
+  // (round 4, 2/3/4/6 lanes: no difference on the kagome_36 pipeline — 23.6 / 23.7 / 23.1 s —
   // nor on the synthetic batches, and every lane is one more buffer set to allocate)
-#ifndef ASP_SHUF_LANES
-#define ASP_SHUF_LANES 2
-#endif
-  static constexpr int kLanes = ASP_SHUF_LANES, kSets = kLanes + 1;
+  static constexpr int kLanes = 2, kSets = kLanes + 1;
   asp::ScopedStream order_stream[kLanes];
   hipEvent_t ordered[kSets] = {}, swept[kSets] = {};
   DeviceBuffer<double> d_betas, d_partial, d_e;
@@ -2000,8 +1957,7 @@ struct ShuffledRun {
     // widest (K = 12 870 alone on the chip: +6 %) — but not in a batch that oversubscribes the chip,
     // where a wavefront mostly waiting at level barriers holds 256 registers of a SIMD that another
     // problem's workgroup could run in (128-problem production batch, sweeps alone: 1.69 -> 1.56 s)
-    uint32_t waves_extra = batch_saturates ? 0u : 1u;
-    if (const char *env = std::getenv("ASP_SHUFFLED_WAVES_EXTRA")) waves_extra = static_cast<uint32_t>(std::atoi(env));
+    const uint32_t waves_extra = batch_saturates ? 0u : 1u;
     if (!waves) {
       // a wavefront per block of an average level, and one more: the first blocks of a level are
       // its widest (K = 12 870: 4 blocks per level, 4 -> 8 wavefronts +6 %)
@@ -2053,8 +2009,7 @@ struct ShuffledRun {
       // largest clusters, the same for 64 .. 112 problems; profiles/r04_shuffled_batch_trace.txt).
       // A call that does not fill the chip keeps blocks of 64 where a level has them: lane packing
       // costs an add per gather and per-lane chain ids (K = 3000 x 64 chains: 43.7 against 49.5 ms).
-      double s_factor = batch_saturates ? 0.25 : 0.75;
-      if (const char *env = std::getenv("ASP_SHUFFLED_S_FACTOR")) s_factor = std::atof(env);
+      const double s_factor = batch_saturates ? 0.25 : 0.75;
       uint32_t want = std::max(4u, std::min(64u, next_pow2(static_cast<uint32_t>(std::ceil(s_factor * mean_level)))));
       if (const char *env = std::getenv("ASP_SHUFFLED_LOG_S")) {
         want = 1u << std::max(2l, std::min(6l, std::strtol(env, nullptr, 10)));
@@ -2075,12 +2030,8 @@ struct ShuffledRun {
     wgs = (groups + (64u >> log_s) - 1) / (64u >> log_s);
     quad_cap = 0;  // 0: derive from level_cap
     order_threads = K >= 4096 ? kOrderThreads : (K >= 512 ? 256u : 64u);
-    if (order_threads_cap) order_threads = std::min(order_threads, order_threads_cap);
     lanes_per_row = std::min(64u, std::min(order_threads, next_pow2(std::max(
         1u, static_cast<uint32_t>(std::ceil(mean_degree / 4.0))))));
-    if (const char *env = std::getenv("ASP_SHUFFLED_LANES_PER_ROW")) {  // measurements
-      lanes_per_row = std::min(64u, next_pow2(std::max(1u, static_cast<uint32_t>(std::atoi(env)))));
-    }
     if (const char *env = std::getenv("ASP_SHUFFLED_BYTES")) budget = std::strtoull(env, nullptr, 10);
 
     // (the run's own order streams and events: made by enqueue(), which the batched driver — with
@@ -2618,17 +2569,15 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(order_lds_wide)));
     }
     std::vector<std::unique_ptr<Class>> classes;
-    int lds_buckets = 2;  // (scanned on the kagome_36 pipeline: 8.1 / 7.4 / 9.3 s per round with 1 / 2 / 3)
-    if (const char *env = std::getenv("ASP_SHUFFLED_LDS_BUCKETS")) lds_buckets = std::atoi(env);
     for (uint32_t i = 0; i < P; ++i) {
       ShuffledRun *r = runs[i];
       Class *c = nullptr;
       // (a launch has ONE LDS size, the largest of its members: a 2 000-spin model in the launch of a
       // 200 000-spin one would hold a whole compute unit's LDS — three LDS sizes per kernel, so
       // four, two or one workgroup per compute unit)
-      int lds_bucket = r->lds <= 40 * 1024 ? 0 : (r->lds <= 80 * 1024 ? 1 : 2);
-      if (lds_buckets == 2) lds_bucket = r->lds <= 80 * 1024 ? 0 : 1;  // (one workgroup per compute unit, or more)
-      if (lds_buckets <= 1) lds_bucket = 0;
+      // two LDS sizes: one workgroup per compute unit, or more (scanned on the kagome_36 pipeline:
+      // 8.1 / 7.4 / 9.3 s per round with one / two / three sizes)
+      const int lds_bucket = r->lds <= 80 * 1024 ? 0 : 1;
       for (auto &k : classes) {
         if (k->layout == r->layout && k->m == r->m && k->packed_lanes == r->packed_lanes &&
             k->lds_bucket == lds_bucket) {
@@ -2736,14 +2685,6 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
                             &sargs[static_cast<size_t>(turn) * P + i]);
       }
     }
-    // Timing-only ablations (results are WRONG; tools/time_shuffled_batch_only.py): 1 = orders of
-    // the first buffer sets only, every later chunk sweeps through stale ones (the cost of the
-    // sweep kernels alone); 2 = no sweep launches after the first chunk (the order kernels alone)
-    // (only in a build with -DASP_SHUF_ABLATE_ENV=1: the product ignores the variable)
-    int ablate = 0;
-#if ASP_SHUF_ABLATE_ENV
-    if (const char *env = std::getenv("ASP_SHUFFLED_ABLATE")) ablate = std::atoi(env);
-#endif
     // (the wide kernels read a table of the wide problems only: their grids are workgroups per
     // (problem, sweep), and two thirds of a pipeline round are small models of the fused path)
     const uint32_t Pw = static_cast<uint32_t>(wide_members.size());
@@ -2771,7 +2712,7 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
       const uint32_t now = num_sweeps > done ? std::min(chunk, num_sweeps - done) : 0u;
       const uint32_t which = turn % nsets;
       hipStream_t os = order_stream[turn % nlanes].stream;
-      if (now && !(ablate == 1 && turn >= nsets)) {
+      if (now) {
         if (turn >= nsets) {
           for (auto &c : classes) ASP_HIP_TRY(hipStreamWaitEvent(os, c->swept[which], 0));
         }
@@ -2792,7 +2733,6 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
 
       }
       for (auto &c : classes) {
-        if (ablate == 2 && turn > 0) continue;
         hipStream_t cs = c->stream.stream;
         if (now) ASP_HIP_TRY(hipStreamWaitEvent(cs, ordered[which], 0));
         ShuffledBatchKernel kernel = shuffled_batch_kernel_for(c->m, c->layout, c->packed_lanes);
@@ -2863,15 +2803,7 @@ int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uin
       }
     }
   }
-  if (const char *env = std::getenv("ASP_SHUFFLED_BATCH_M")) {  // (development: scan the chains per group of a batch)
-    const int forced = std::atoi(env);
-    if (forced == 1 || forced == 2 || forced == 4) m = forced;
-  }
-  int big_m = 8;  // chains per workgroup of the clusters beyond the word layout, in a batch that fills the chip
-  if (const char *env = std::getenv("ASP_SHUFFLED_BATCH_BIG_M")) {
-    const int forced = std::atoi(env);
-    if (forced == 1 || forced == 2 || forced == 4 || forced == 8) big_m = forced;
-  }
+  const int big_m = 8;  // chains per workgroup of the clusters beyond the word layout, in a batch that fills the chip
   for (uint32_t k = 0; k < count; ++k) {
     const asp_sa_batch_item &it = items[which[k]];
     runs.emplace_back(new ShuffledRun());
@@ -2896,9 +2828,6 @@ int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uin
       if (saturates && it.plan->host.num_spins * 4ull > it.plan->max_lds * 15 / 16) r.forced_m = big_m;
     }
     r.batch_saturates = saturates;
-    if (const char *env = std::getenv("ASP_SHUFFLED_ORDER_THREADS")) {  // (development: scanned 128 .. 1024, no effect)
-      r.order_threads_cap = static_cast<uint32_t>(std::max(64l, std::min(1024l, std::strtol(env, nullptr, 10) / 64 * 64)));
-    }
     ASP_TRY(r.setup());
   }
   phase("setup");

@@ -53,7 +53,10 @@ namespace {
 using asp::DeviceBuffer;
 using asp::kDummySpin;
 using asp::upload_vector;
-using namespace asp::dev;  // Philox, expneg, the accept filters, coupling quads (sa_device.hpp)
+using namespace asp::dev;  // Philox, the accept filter, the spin layouts (sa_device.hpp)
+
+constexpr int kMaxThreads = 1024;  // launch bound of the sweep kernel (VGPR budget = 512 / waves per SIMD)
+constexpr int kTeamSleep = 4;  // s_sleep argument between two polls of the team barrier (0/1/4/16/64 scanned)
 
 struct SweepArgs {
   const uint32_t *color_block_start;  // num_colors + 1
@@ -98,6 +101,32 @@ __device__ __forceinline__ void store_word(uint64_t *p, uint64_t v) {
   }
 }
 
+// v with its sign flipped when bit 0 of `neg` is set (energy kernel, not hot).
+__device__ __forceinline__ double signed_coupling(double v, uint32_t neg, int m) {
+  const unsigned long long flip = static_cast<unsigned long long>((neg >> m) & 1u) << 63;
+  return __longlong_as_double(__double_as_longlong(v) ^ static_cast<long long>(flip));
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+#pragma unroll
+  for (int step = 1; step < 64; step <<= 1) v += __shfl_xor(v, step, 64);
+  return v;
+}
+
+// Butterfly sum over the 64 lanes; every lane ends with the balanced-tree total
+// ((v0+v1)+(v2+v3))+... (f64 addition commutes, so all lanes agree bitwise).
+__device__ __forceinline__ double wave_tree_sum_f64(double v) {
+#pragma unroll
+  for (int step = 1; step < 64; step <<= 1) v = __dadd_rn(v, __shfl_xor(v, step, 64));
+  return v;
+}
+
+// Collect bit m of each of the four bytes of d into a nibble (byte 0 -> bit 0).
+__device__ __forceinline__ uint32_t gather_bit4(uint32_t d, int m) {
+  const uint32_t t = (d >> m) & 0x01010101u;
+  return ((t * 0x00204081u) >> 21) & 0xFu;
+}
+
 // kBytes with M <= 4 keeps replica m at bit 2m of the spin byte (the odd bits stay 0); M = 8
 // fills the byte and keeps bit m.  With the even bits the high word of the term's +-1.0 is
 //   (byte << (31 - 2m)) | 0x3FF00000   (one v_lshl_or_b32)
@@ -123,39 +152,56 @@ __device__ __forceinline__ uint32_t encode_replicas(uint32_t mask) {
   }
 }
 
-__device__ __forceinline__ double even_spin_factor(uint32_t spin_byte, int m) {
-  return __hiloint2double(static_cast<int>((spin_byte << (31 - 2 * m)) | 0x3FF00000u), 0);
+// +-1.0 with the sign taken from replica m's bit of a neighbour's spin byte (1 -> -1.0).
+// acc = fma(v, +-1.0, acc) is bit-identical to acc + (+-v): the product is exact, so the only
+// rounding is the add's; the low dword of the multiplier is a constant zero.
+//   even-bit bytes: one v_lshl_or_b32 (above) that the compiler schedules (plain C++: no inline
+//     asm, so no hazard padding);
+//   bit m (bytes at M = 8, nibbles, bits): replica m's bit to bit 0 with a RIGHT shift — a plain
+//     VOP2, 2.5 SIMD cycles per wave64 on this chip, where every left shift and every VOP3 costs
+//     4.3-4.4 (profiles/r02_issue_rate_probe.txt) — then the m = 0 instruction.
+template <int M, int LAYOUT>
+__device__ __forceinline__ double spin_factor(uint32_t spin_byte, int m) {
+  uint32_t hi;
+  if constexpr (kEvenBits<M, LAYOUT>) {
+    hi = (spin_byte << (31 - 2 * m)) | 0x3FF00000u;
+  } else if (m == 0) {
+    hi = (spin_byte << 31) | 0x3FF00000u;  // v_lshl_or_b32: nothing but bit 0 survives the shift
+  } else {
+    const uint32_t down = spin_byte >> m;
+    asm("v_lshl_or_b32 %0, %1, 31, %2" : "=v"(hi) : "v"(down), "s"(0x3FF00000u));
+  }
+  return __hiloint2double(static_cast<int>(hi), 0);
 }
 
-// The ELL stream of one block through BUFFER loads: the resource's base is the block's first
-// quad (scalar, set up once per visit), the quad is a scalar offset (quad * 1024 B of columns,
-// quad * 2048 B of values) and the lane part a vector offset fixed for the whole kernel, so a
-// quad costs no vector address arithmetic.  Offsets are relative to the block, so any plan size
-// fits the 32-bit offsets.
-using BufferRsrc = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ BufferRsrc block_rsrc(const void *base) {
-  // raw buffer, 4 GiB range, gfx9 DATA_FORMAT word
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0xFFFFFFFF, 0x00020000);
+// kWide: byte m of `word` (0x00 / 0x80) OR 0x3F becomes byte 3 of `hi`, whose lower three bytes
+// keep 0xF00000 — i.e. hi = high word of +1.0 or -1.0 — in one v_or_b32_sdwa (byte select on
+// the source, byte-3 write with the rest preserved).  Two VALU ops per (term, replica)
+// instead of three.
+__device__ __forceinline__ double wide_factor(uint32_t word, int m, uint32_t &hi) {
+  const uint32_t top = 0x3Fu;
+  switch (m) {
+    case 0:
+      asm("v_or_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD "
+          "src1_sel:BYTE_0" : "+v"(hi) : "v"(top), "v"(word));
+      break;
+    case 1:
+      asm("v_or_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD "
+          "src1_sel:BYTE_1" : "+v"(hi) : "v"(top), "v"(word));
+      break;
+    case 2:
+      asm("v_or_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD "
+          "src1_sel:BYTE_2" : "+v"(hi) : "v"(top), "v"(word));
+      break;
+    default:
+      asm("v_or_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD "
+          "src1_sel:BYTE_3" : "+v"(hi) : "v"(top), "v"(word));
+      break;
+  }
+  return __hiloint2double(static_cast<int>(hi), 0);
 }
-struct BlockStream {
-  BufferRsrc col, val;
-  uint32_t lane16;  // lane * 16
-  const uint4 *cptr;      // (the ablation builds of load_quad only)
-  const double2 *vptr;
-};
 
-__device__ __forceinline__ void load_quad(Quad &q, const BlockStream &s, uint32_t quad) {
-#if ASP_ABL_NO_GLOAD || ASP_ABL_HALF_BYTES
-  load_quad(q, s.cptr, s.vptr, quad);
-#else
-  q.c = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(s.col, s.lane16, quad * 1024u, 0));
-  q.v01 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(s.val, s.lane16, quad * 2048u, 0));
-  q.v23 = __builtin_bit_cast(double2,
-                             __builtin_amdgcn_raw_buffer_load_b128(s.val, s.lane16 + 1024u, quad * 2048u, 0));
-#endif
-}
-
-// kWide: wide_factor's SDWA rewrites the top byte of a multiplier held as a whole f64 whose low
+// The SDWA of wide_factor rewrites the top byte of a multiplier held as a whole f64 whose low
 // word stays 0 for the whole anneal (rebuilt from `hi` and a literal 0, as wide_factor returns
 // it, the pair was re-assembled and low words re-zeroed inside the k-loop).
 __device__ __forceinline__ double wide_factor_held(uint32_t word, int m, double &mult) {
@@ -165,52 +211,91 @@ __device__ __forceinline__ double wide_factor_held(uint32_t word, int m, double 
   return mult;
 }
 
-// The row sums of one quad.  The even-bit byte layout gathers its four bytes and takes each
-// sign with one v_lshl_or_b32 that the compiler schedules (plain C++: no inline asm, so no
-// hazard padding); kWide takes its SDWA sign into a held multiplier.  Both neighbour-major (each
-// acc[m] still receives its terms in ascending k).  The other layouts go through
-// sa_device.hpp's accumulate_quad.
+// Four consecutive ELL entries of one lane (one row), k = 4q .. 4q+3.
+struct Quad {
+  uint4 c;
+  double2 v01, v23;
+};
+
+// Three 16-byte loads per lane through pointers (the team kernel); quad index `quad` is relative
+// to the block's first quad.
+__device__ __forceinline__ void load_quad(Quad &q, const uint4 *__restrict__ cptr,
+                                          const double2 *__restrict__ vptr, uint32_t quad) {
+  q.c = cptr[quad * 64u];
+  q.v01 = vptr[quad * 128u];
+  q.v23 = vptr[quad * 128u + 64u];
+}
+
+// The ELL stream of one block through BUFFER loads: the resource's base is the block's first
+// quad (scalar, set up once per visit), the quad is a scalar offset (quad * 1024 B of columns,
+// quad * 2048 B of values) and the lane part a vector offset fixed for the whole kernel, so a
+// quad costs no vector address arithmetic.  Offsets are relative to the block, so any plan size
+// fits the 32-bit offsets.  `cptr`: the lane's columns through a plain pointer, for the dirty
+// marking that re-reads them after a flip.
+using BufferRsrc = __amdgpu_buffer_rsrc_t;
+__device__ __forceinline__ BufferRsrc block_rsrc(const void *base) {
+  // raw buffer, 4 GiB range, gfx9 DATA_FORMAT word
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0xFFFFFFFF, 0x00020000);
+}
+struct BlockStream {
+  const uint4 *cptr;
+  BufferRsrc col, val;
+  uint32_t lane16;  // lane * 16
+};
+
+__device__ __forceinline__ void load_quad(Quad &q, const BlockStream &s, uint32_t quad) {
+  q.c = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(s.col, s.lane16, quad * 1024u, 0));
+  q.v01 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(s.val, s.lane16, quad * 2048u, 0));
+  q.v23 = __builtin_bit_cast(double2,
+                             __builtin_amdgcn_raw_buffer_load_b128(s.val, s.lane16 + 1024u, quad * 2048u, 0));
+}
+
+// The row sums of one quad: the four neighbours' spins are gathered, then neighbour-major FMAs
+// (consecutive FMAs go to different accumulators; each acc[m] still receives its terms in
+// ascending k).  `mult`: kWide's held multipliers (wide_factor_held), untouched by the others.
 template <int M, int LAYOUT>
 __device__ __forceinline__ void accumulate(const Quad &q, const uint8_t *spins, double (&acc)[M],
-                                           uint32_t (&one_hi)[4], double (&mult)[4]) {
-  if constexpr (kEvenBits<M, LAYOUT> || LAYOUT == kWide) {
-    const uint32_t cs[4] = {q.c.x, q.c.y, q.c.z, q.c.w};
-    const double vs[4] = {q.v01.x, q.v01.y, q.v23.x, q.v23.y};
-    uint32_t s[4];
+                                           double (&mult)[4]) {
+  const uint32_t cs[4] = {q.c.x, q.c.y, q.c.z, q.c.w};
+  const double vs[4] = {q.v01.x, q.v01.y, q.v23.x, q.v23.y};
+  uint32_t s[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#if ASP_ABL_NO_LDS
-      s[j] = cs[j] & 15u;
-#else
+  for (int j = 0; j < 4; ++j) {
+    if constexpr (LAYOUT == kBytes) {
+      // even-bit bytes and bytes at M = 8: the spin bytes start at LDS address 0 (checked in the
+      // kernel prologue), so a position IS its LDS address — no base add in front of every
+      // ds_read_u8
+      s[j] = *reinterpret_cast<LdsByte *>(static_cast<uintptr_t>(cs[j]));
+    } else if constexpr (LAYOUT == kWide) {
+      // columns of the wide plan are LDS byte addresses (position * 4)
+      s[j] = *reinterpret_cast<LdsWord *>(static_cast<uintptr_t>(cs[j]));
+    } else if constexpr (LAYOUT == kNibbles) {
+      // position c: byte c / 2, nibble c % 2; the bits above replica m's are ignored by spin_factor
+      const uint32_t byte = *reinterpret_cast<LdsByte *>(static_cast<uintptr_t>(cs[j] >> 1));
+      s[j] = byte >> ((cs[j] & 1u) << 2);
+    } else if constexpr (LAYOUT == kBits) {
+      const uint32_t *words = reinterpret_cast<const uint32_t *>(spins);
+      s[j] = (words[cs[j] >> 5] >> (cs[j] & 31u)) & 1u;
+    } else {
+      static_assert(LAYOUT == kGlobal, "spins are LDS bytes, words, nibbles or bits, or bits in HBM");
+      // words written by other wavefronts of the workgroup during earlier colour steps: read at
+      // device scope (past the CU's vector L1)
+      const uint32_t *words = reinterpret_cast<const uint32_t *>(spins);
+      const uint32_t w = __hip_atomic_load(words + (cs[j] >> 5), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+      s[j] = (w >> (cs[j] & 31u)) & 1u;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
       if constexpr (LAYOUT == kWide) {
-        s[j] = *reinterpret_cast<LdsWord *>(static_cast<uintptr_t>(cs[j]));
+        acc[m] = __builtin_fma(vs[j], wide_factor_held(s[j], m, mult[m & 3]), acc[m]);
       } else {
-#if ASP_ABS_LDS
-        s[j] = *reinterpret_cast<LdsByte *>(static_cast<uintptr_t>(cs[j]));
-#else
-        s[j] = spins[cs[j]];
-#endif
-      }
-#endif
-    }
-#if ASP_ABL_NO_FMA
-    asm volatile("" ::"v"(s[0]), "v"(s[1]), "v"(s[2]), "v"(s[3]), "v"(vs[0]), "v"(vs[1]),
-                 "v"(vs[2]), "v"(vs[3]));
-    return;
-#endif
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int m = 0; m < M; ++m) {
-        if constexpr (LAYOUT == kWide) {
-          acc[m] = __builtin_fma(vs[j], wide_factor_held(s[j], m, mult[m & 3]), acc[m]);
-        } else {
-          acc[m] = __builtin_fma(vs[j], even_spin_factor(s[j], m), acc[m]);
-        }
+        acc[m] = __builtin_fma(vs[j], spin_factor<M, LAYOUT>(s[j], m), acc[m]);
       }
     }
-  } else {
-    accumulate_quad<M, LAYOUT>(q, spins, acc, one_hi);
   }
 }
 
@@ -322,13 +407,11 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
   uint8_t *inert = dirty + ((a.num_blocks + 15u) & ~15u);
   const bool cache_available = !PACKED && a.field_cache != nullptr;
 
-#if ASP_ABS_LDS
-  // accumulate_quad addresses the spin bytes absolutely: the dynamic LDS block must be the
-  // first (this kernel declares no static LDS)
+  // accumulate addresses the spin bytes absolutely: the dynamic LDS block must be the first
+  // (this kernel declares no static LDS)
   if (reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t *)lds) != 0) {
     __builtin_trap();
   }
-#endif
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
   const uint32_t wave = tid >> 6;
@@ -392,7 +475,6 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
   if (a.trace != nullptr && tid < M) {
     a.trace[(static_cast<uint64_t>(group) * M + tid) * (a.num_sweeps + 1ull)] = 0;
   }
-  uint32_t one_hi[4] = {0x3FF00000u, 0x3FF00000u, 0x3FF00000u, 0x3FF00000u};
   double mult[4] = {1.0, 1.0, 1.0, 1.0};  // kWide's multipliers (low words stay 0)
   for (uint32_t t = 0; t < a.num_sweeps; ++t) {
     const double beta = a.betas[t];
@@ -414,29 +496,16 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     for (uint32_t c = 0; c < a.num_colors; ++c) {
       const uint32_t b_begin = a.color_block_start[c];
       const uint32_t b_end = a.color_block_start[c + 1];
-#if ASP_SERPENTINE
-      // Serpentine assignment: blocks of a colour are sorted by descending width, so a plain
-      // round-robin would always hand wave 0 the widest block of every round.  Any assignment
-      // gives the same bits (blocks of one colour are independent).
-      for (uint32_t round = 0;; ++round) {
-        const uint32_t slot = (round & 1u) ? (waves - 1u - wave) : wave;
-        const uint32_t b = b_begin + round * waves + slot;
-        if (round * waves >= b_end - b_begin) break;
-        if (b >= b_end) continue;
-#else
       for (uint32_t b = b_begin + wave; b < b_end; b += waves) {
-#endif
         const uint32_t p = b * 64u + lane;
         bool reuse = false;
         if (cached) {
           reuse = (__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(dirty[b])) &
                    ((1u << M) - 1u)) == 0u;
-#if ASP_INERT_SKIP
           // fields unchanged and every proposal certain to be rejected again: nothing to do
           if (reuse && __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(inert[b])) != 0u) {
             continue;
           }
-#endif
         }
         // {first slab, width}: one broadcast LDS read (two scalar loads when bit-packed)
         const uint2 info =
@@ -445,12 +514,9 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
         const uint32_t quads = __builtin_amdgcn_readfirstlane(info.y) >> 2;
         // info.x = first slab of the block (a multiple of 4): quad index = slab / 4
         const uint64_t first_quad = __builtin_amdgcn_readfirstlane(info.x) >> 2;
-        const uint4 *cptr = reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u + lane;
-        const double2 *vptr =
-            reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u + lane;
-        const BlockStream stream{block_rsrc(reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u),
-                                 block_rsrc(reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u),
-                                 lane * 16u, cptr, vptr};
+        const uint4 *col = reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u;
+        const double2 *val = reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u;
+        const BlockStream stream{col + lane, block_rsrc(col), block_rsrc(val), lane * 16u};
         // issued now, consumed after the row sum: their latency hides under the k-loop
         const uint32_t spin = a.spin_of_pos[p];
         const double h = a.field_pos[p];
@@ -469,11 +535,6 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
         } else {
 #pragma unroll
           for (int m = 0; m < M; ++m) acc[m] = 0.0;
-#if ASP_ABL_NO_KLOOP
-          const uint32_t quads_run = 0;
-#else
-          const uint32_t quads_run = quads;
-#endif
           // k-loop, prefetch distance one: the next quad's three 16-byte loads are in flight
           // while the current quad is gathered from LDS and accumulated, in the oracle's order
           // k = 0, 1, 2, ...  Loop control is scalar and the body has no conditional loads
@@ -484,17 +545,17 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
           Quad qa, qb;
           load_quad(qa, stream, 0);
           uint32_t i = 0;
-          for (; i + 2 <= quads_run; i += 2) {
+          for (; i + 2 <= quads; i += 2) {
             load_quad(qb, stream, i + 1);
             __builtin_amdgcn_sched_barrier(0);
-            accumulate<M, LAYOUT>(qa, spins, acc, one_hi, mult);
+            accumulate<M, LAYOUT>(qa, spins, acc, mult);
             __builtin_amdgcn_sched_barrier(0);
             load_quad(qa, stream, i + 2);
             __builtin_amdgcn_sched_barrier(0);
-            accumulate<M, LAYOUT>(qb, spins, acc, one_hi, mult);
+            accumulate<M, LAYOUT>(qb, spins, acc, mult);
             __builtin_amdgcn_sched_barrier(0);
           }
-          if (i < quads_run) accumulate<M, LAYOUT>(qa, spins, acc, one_hi, mult);
+          if (i < quads) accumulate<M, LAYOUT>(qa, spins, acc, mult);
           if (cached) {
 #pragma unroll
             for (int m = 0; m < M; ++m) cache_row[m * 64] = acc[m];
@@ -527,22 +588,14 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
           } else {
             const bool maybe = valid && !(__dmul_rn(beta, de[m]) >= 23.0);  // not a certain rejection
             open = open || maybe;
-#if ASP_EXPERIMENT_GLAUBER
-            need = need || maybe;
-#else
             need = need || (maybe && !(de[m] <= 0.0));
-#endif
           }
         }
         // Random numbers only when some proposal of the block is undecided without one
         // (dE <= 0 is accepted, beta * dE >= 23 rejected, whatever the draw): a wave-uniform
         // branch around the 10 Philox rounds and the exp filter.  Counter-based RNG: skipping
         // a draw changes nothing downstream.
-#if ASP_PHILOX_SKIP
         const bool draw = !DESCENT && __ballot(need) != 0ull;
-#else
-        const bool draw = !DESCENT;
-#endif
         uint32_t accept_mask = 0;
         if (draw) {
           Philox4 rnd{};
@@ -552,44 +605,18 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
             const uint32_t r = r0 + m;
             if (m == 0 || (r >> 2) != have) {
               have = r >> 2;
-#if ASP_ABL_NO_PHILOX
-              rnd = Philox4{{spin * 2654435761u ^ t, spin ^ (t * 40503u), spin + have, t ^ key0}};
-#else
               rnd = philox4x32_10(spin, t, have, 0u, key0, key1);
-#endif
             }
             const uint32_t word = pick_word(rnd, r & 3u);
-            bool accept;
-#if ASP_ABL_NO_ACCEPT
-            asm volatile("" ::"v"(de[m]), "v"(word));
-            accept = false;
-#elif ASP_ABL_NO_EXP
-            accept = valid && (de[m] <= 0.0 || word < static_cast<uint32_t>(__dmul_rn(beta, de[m])));
-#elif ASP_EXPERIMENT_GLAUBER
-            {
-              const double x = __dmul_rn(beta, de[m]);
-              const double uu = (static_cast<double>(word) + 0.5) * 0x1p-32;
-              accept = valid && x < 23.0 && uu < 1.0 / (1.0 + exp(x));
-            }
-#elif ASP_EXP_FILTER == 2
-            accept = valid && (de[m] <= 0.0 || metropolis_accept_word(word, __dmul_rn(beta, de[m])));
-#else
-            const double u = __dmul_rn(__dadd_rn(static_cast<double>(word), 0.5), 0x1p-32);
-#if ASP_EXP_FILTER
-            accept = valid && (de[m] <= 0.0 || metropolis_accept(u, __dmul_rn(beta, de[m])));
-#else
-            accept = valid && (de[m] <= 0.0 || u < expneg(__dmul_rn(beta, de[m])));
-#endif
-#endif
+            const bool accept =
+                valid && (de[m] <= 0.0 || metropolis_accept_word(word, __dmul_rn(beta, de[m])));
             accept_mask |= (accept ? 1u : 0u) << m;
           }
         } else {
 #pragma unroll
           for (int m = 0; m < M; ++m) {
-            // (no draw needed: DESCENT, or every proposal decided; with the heat-bath experiment a
-            // skipped draw means every proposal was a certain rejection)
-            const bool accept = valid && (DESCENT ? de[m] < 0.0
-                                                  : (ASP_EXPERIMENT_GLAUBER ? false : de[m] <= 0.0));
+            // (no draw needed: DESCENT, or every proposal decided)
+            const bool accept = valid && (DESCENT ? de[m] < 0.0 : de[m] <= 0.0);
             accept_mask |= (accept ? 1u : 0u) << m;
           }
         }
@@ -599,12 +626,8 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
             flip |= 1u << m;
             // rint(dE * 2^S) as int64: |dE * 2^S| < 2^51 by the plan's choice of S, so adding
             // 1.5 * 2^52 leaves the rounded integer in the mantissa (ties to even, = rint)
-#if ASP_MAGIC_RINT
             q_acc[m] += __double_as_longlong(__dadd_rn(__dmul_rn(de[m], a.scale), 0x1.8p52)) -
                         0x4338000000000000ll;
-#else
-            q_acc[m] += static_cast<long long>(__builtin_rint(__dmul_rn(de[m], a.scale)));
-#endif
             n_acc[m] += 1;
           }
         }
@@ -624,19 +647,17 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
         } else {
           if (flip) spins[p] = static_cast<uint8_t>(own ^ encode_replicas<M, LAYOUT>(flip));
         }
-#if ASP_INERT_SKIP
         if (cached) {
           const bool none_open = __ballot(open) == 0ull;
           if (lane == 0) inert[b] = none_open ? 1 : 0;
         }
-#endif
         if (cached && __ballot(flip != 0) != 0ull) {
           // Every neighbour of a flipped spin sits in a block of ANOTHER colour: mark those
           // blocks stale for the replicas that flipped.  The row's columns are streamed again
           // (columns only); in cached mode flips are rare by construction.
           uint32_t *dirty_words = reinterpret_cast<uint32_t *>(dirty);
           for (uint32_t q = 0; q < quads; ++q) {
-            const uint4 c4 = cptr[q * 64u];
+            const uint4 c4 = stream.cptr[q * 64u];
             if (flip) {
               const uint32_t cols[4] = {c4.x, c4.y, c4.z, c4.w};
 #pragma unroll
@@ -650,9 +671,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
           }
         }
       }
-#if !ASP_ABL_NO_BARRIER
       __syncthreads();
-#endif
     }
 
     // ---- exact (integer) reduction of the sweep's energy change ----
@@ -712,7 +731,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
 }
 
 template <int M, bool DESCENT, int LAYOUT>
-__global__ __launch_bounds__(ASP_MAX_THREADS) void k_sa_sweep(SweepArgs a) {
+__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep(SweepArgs a) {
   sa_sweep_body<M, DESCENT, LAYOUT>(a, blockIdx.x);
 }
 
@@ -734,7 +753,7 @@ struct BatchArgs {
 };
 
 template <int M, int LAYOUT>
-__global__ __launch_bounds__(ASP_MAX_THREADS) void k_sa_sweep_batch(BatchArgs b) {
+__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_batch(BatchArgs b) {
   const BatchSlot slot = b.slots[(blockIdx.x & 7u) * b.slots_per_xcd + (blockIdx.x >> 3)];
   const uint32_t problem = __builtin_amdgcn_readfirstlane(slot.problem);
   if (problem == 0xFFFFFFFFu) return;
@@ -800,7 +819,7 @@ __device__ __forceinline__ void team_barrier(const TeamArgs &ta, unsigned long l
         __hip_atomic_store(ta.abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         break;
       }
-      __builtin_amdgcn_s_sleep(ASP_TEAM_SLEEP);
+      __builtin_amdgcn_s_sleep(kTeamSleep);
     }
   }
   __syncthreads();
@@ -863,7 +882,7 @@ __global__ __launch_bounds__(1024) void k_sa_sweep_team(TeamArgs ta) {
     }
   }
 
-  uint32_t one_hi[4] = {0x3FF00000u, 0x3FF00000u, 0x3FF00000u, 0x3FF00000u};
+  double mult[4] = {1.0, 1.0, 1.0, 1.0};  // (accumulate's kWide multipliers: unused by kBits)
   for (uint32_t t = 0; t < a.num_sweeps; ++t) {
     const double beta = a.betas[t];
     const bool tracking = __builtin_amdgcn_readfirstlane(ctl[0]) != 0;
@@ -901,14 +920,14 @@ __global__ __launch_bounds__(1024) void k_sa_sweep_team(TeamArgs ta) {
         for (; i + 2 <= quads; i += 2) {
           load_quad(qb, cptr, vptr, i + 1);
           __builtin_amdgcn_sched_barrier(0);
-          accumulate_quad<1, kBits>(qa, lds, acc, one_hi);
+          accumulate<1, kBits>(qa, lds, acc, mult);
           __builtin_amdgcn_sched_barrier(0);
           load_quad(qa, cptr, vptr, i + 2);
           __builtin_amdgcn_sched_barrier(0);
-          accumulate_quad<1, kBits>(qb, lds, acc, one_hi);
+          accumulate<1, kBits>(qb, lds, acc, mult);
           __builtin_amdgcn_sched_barrier(0);
         }
-        if (i < quads) accumulate_quad<1, kBits>(qa, lds, acc, one_hi);
+        if (i < quads) accumulate<1, kBits>(qa, lds, acc, mult);
         const bool valid = spin != kDummySpin;
         const bool negative = (words[b] >> lane) & 1ull;
         const double g = __dadd_rn(acc[0], h);
@@ -1709,8 +1728,7 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
       args.field_cache = p->w_field_cache.ptr;
       // a flip stales ~degree blocks: cached mode pays while that is a fraction of all blocks
       const double degree = std::max(1.0, static_cast<double>(L.a_col.size()) / static_cast<double>(K));
-      double factor = 0.7;
-      if (const char *env = std::getenv("ASP_CACHE_FACTOR")) factor = std::atof(env);  // tuning aid
+      const double factor = 0.7;
       args.cache_enter_flips =
           static_cast<uint32_t>(std::max(1.0, factor * static_cast<double>(L.num_blocks) / degree));
     } else {
@@ -2073,21 +2091,17 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
     // Layout and wavefronts per workgroup in a shared launch.  Small problems — several
     // workgroups fit a CU — take the word layout (one-instruction signs) and 4 wavefronts: small
     // workgroups interleave better than the 16 a lone problem wants (cap 16 / 8 / 4 on clusters of
-    // 1e2..1e4 spins, 128 problems: 109 / 133 / 152 G flips/s, 512: 152 / 200 / 213;
-    // tools/tune_batch.py).  Larger ones keep a byte per spin — the word layout would leave them
+    // 1e2..1e4 spins, 128 problems: 109 / 133 / 152 G flips/s, 512: 152 / 200 / 213).  Larger ones keep a byte per spin — the word layout would leave them
     // one workgroup per CU — and take 16 wavefronts (the sampled-cluster pipeline's order-2 models,
     // 1e4..2e5 spins, cap 4 / 8 / 16: 150 / 234 / 279 G flips/s; profiles/r03_batch_tune_real.txt).
-    uint64_t wide_max = 10000, small_max = 10000;
-    if (const char *env = std::getenv("ASP_BATCH_WIDE_MAX")) wide_max = std::strtoull(env, nullptr, 10);    // tuning aids
-    if (const char *env = std::getenv("ASP_BATCH_SMALL_MAX")) small_max = std::strtoull(env, nullptr, 10);
+    const uint64_t wide_max = 10000, small_max = 10000;
     e.layout = !bytes_fit ? (nibbles_fit ? kNibbles : kBits)
                           : (p->allow_wide && p->ell_col4.ptr && L.num_spins <= wide_max &&
                                      sweep_lds_bytes(L, kWide) <= p->max_lds
                                  ? kWide
                                  : kBytes);
-    uint32_t cap = L.num_spins <= small_max ? 4u : 16u;
-    if (const char *env = std::getenv("ASP_BATCH_WAVES")) cap = static_cast<uint32_t>(std::atoi(env));  // tuning aid
-    e.waves = std::min<uint32_t>(widest, std::max(1u, std::min(16u, cap)));
+    const uint32_t cap = L.num_spins <= small_max ? 4u : 16u;
+    e.waves = std::min<uint32_t>(widest, cap);
     e.work = static_cast<double>(it.num_sweeps) * static_cast<double>(L.ell_off.back() + L.num_blocks);
     entries.push_back(e);
   }
@@ -2129,7 +2143,7 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
   auto waves_of_class = [&](int c) { return kWaves[c / 4]; };
   auto layout_of_class = [&](int c) { return kLayouts[c % 4]; };
   // ---- replicas per workgroup, per class ----
-  // Measured on the production mix (tools/tune_batch.py, K log-uniform in [1e2, 1e4], 64 chains x
+  // Measured on the production mix (K log-uniform in [1e2, 1e4], 64 chains x
   // 5120 sweeps): four replicas per workgroup — the word layout with its one-instruction signs —
   // is fastest from 64 problems (86 G flips/s against 73 with two) over 128 (127 against 101
   // with eight, 95 with two, 62 with one) to 512 (161, the same as eight); fewer replicas per
@@ -2153,14 +2167,6 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
     // (fewer replicas per workgroup for the classes of the largest problems, to shorten the
     // batch's longest workgroup, was measured and LOSES: 123 -> 97 G flips/s at 128 problems,
     // 157 -> 120 at 512; the word layout's efficiency outweighs the shorter tail)
-    if (const char *env = std::getenv("ASP_BATCH_BIG_M")) {  // tuning aid
-      const int forced = std::atoi(env);
-      if (forced == 1 || forced == 2 || forced == 4 || forced == 8) {
-        for (int c = 0; c < kNumClasses; ++c) {
-          if (waves_of_class(c) >= 8) m_of_class[c] = forced;
-        }
-      }
-    }
     if (const char *env = std::getenv("ASP_BATCH_M")) {  // tuning aid
       const int forced = std::atoi(env);
       if (forced == 1 || forced == 2 || forced == 4 || forced == 8) {

@@ -1,8 +1,7 @@
 #!/bin/bash
 # One annealing round of the kagome_36 pipeline (32 clusters, shuffled order) per argument, each argument a
-# list of environment settings — library variants (ASP_LIB_TAG=...), launch-shape knobs, or, with a
-# -DASP_SHUF_ABLATE_ENV=1 build, ASP_SHUFFLED_ABLATE=1|2 (sweeps / orders alone; wrong results).  GPU box.
-#   tools/pipeline_round_variants.sh "ASP_LIB_TAG=" "ASP_LIB_TAG=abl ASP_SHUFFLED_ABLATE=1"
+# list of environment settings — library variants (ASP_LIB_TAG=...) or launch-shape knobs.  GPU box.
+#   tools/pipeline_round_variants.sh "ASP_LIB_TAG=" "ASP_LIB_TAG=old"
 export ASP_NO_REBUILD=1
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 D=/tmp/k36; mkdir -p $D
