@@ -75,21 +75,31 @@ def test_full_space_coupling_build_and_energy_identity(models, name):
     assert abs(e_signs - e_oracle) <= 1e-12 * abs(e_signs)
 
 
-def _chains_vs_oracle(h, seed, sweeps, reps, threads):
+def _chains_vs_oracle(h, seed, sweeps, reps, threads, shuffled_reps=None):
+    """The colour-ordered chains, then (``shuffled_reps`` of them, default ``reps``) the
+    shuffled ones -- the default order of every entry point -- against the oracle: configurations,
+    energies, tracked energies and accepted flips.  Returns the colour leg's (xs, es)."""
     from annealing_sign_problem_amd import _lib
     from annealing_sign_problem_amd import annealer as sa
 
     info = h.info()
     betas = sa.make_schedule(info.beta0_auto, info.beta1_auto, sweeps)
-    xs, es = sa.anneal_raw(h, seed, betas, reps)
-    tracked = np.zeros(reps, np.int64)
-    accepted = np.zeros(reps, np.uint64)
-    _lib.check(_lib.load().asp_sa_last_stats(h.plan(), reps, _lib.ptr(tracked), _lib.ptr(accepted)))
-    oxs, oes, otracked, oaccepted = oracle.sa_anneal(h.exchange, h.field, seed, betas, reps, 0, None,
-                                                    info.energy_scale_exp, num_threads=threads)
-    assert np.array_equal(accepted, oaccepted) and np.array_equal(tracked, otracked)
-    assert np.array_equal(xs, oxs) and es.tobytes() == oes.tobytes()
-    return xs, es
+    out = None
+    for shuffled, count in ((False, reps), (True, reps if shuffled_reps is None else shuffled_reps)):
+        xs, es = sa.anneal_raw(h, seed, betas, count, shuffled=shuffled)
+        tracked = np.zeros(count, np.int64)
+        accepted = np.zeros(count, np.uint64)
+        _lib.check(_lib.load().asp_sa_last_stats(h.plan(), count, _lib.ptr(tracked),
+                                                 _lib.ptr(accepted)))
+        run = oracle.sa_anneal_shuffled if shuffled else oracle.sa_anneal
+        oxs, oes, otracked, oaccepted = run(h.exchange, h.field, seed, betas, count, 0, None,
+                                            info.energy_scale_exp, num_threads=threads)
+        assert np.array_equal(accepted, oaccepted) and np.array_equal(tracked, otracked), \
+            "shuffled" if shuffled else "colour"
+        assert np.array_equal(xs, oxs) and es.tobytes() == oes.tobytes(), \
+            "shuffled" if shuffled else "colour"
+        out = out or (xs, es)
+    return out
 
 
 def test_config1_j1j2_full_space_one_and_few_replicas(models):

@@ -119,7 +119,7 @@ def test_sweep_with_field_nonsymmetric_J_and_x0():
     J.data = rng.normal(size=J.data.shape)          # not symmetric, has a diagonal
     J = (J + scipy.sparse.diags(rng.normal(size=n))).tocsr()
     field = rng.normal(size=n) * 0.3
-    x0 = rng.integers(0, 2**63, size=(n + 63) // 64, dtype=np.uint64)
+    x0 = rng.integers(0, 2**64, size=(n + 63) // 64, dtype=np.uint64)
     _compare(J, field, 7, np.geomspace(0.2, 50.0, 35), 9, x0=x0, m=2, threads=128)
 
 
@@ -149,7 +149,7 @@ def test_energy_matches_oracle_and_numpy():
     h = np.random.default_rng(1).normal(size=5000) * 1e-3
     ham = sa.Hamiltonian(J, h)
     rng = np.random.default_rng(2)
-    xs = rng.integers(0, 2**63, size=(7, (5000 + 63) // 64), dtype=np.uint64)
+    xs = rng.integers(0, 2**64, size=(7, (5000 + 63) // 64), dtype=np.uint64)
     xs[:, -1] &= np.uint64((1 << (5000 % 64)) - 1)
     got = ham.energies(xs)
     assert got.tobytes() == oracle.sa_energy(J, h, xs).tobytes()
@@ -284,7 +284,7 @@ def test_bit_packed_layout_bit_exact(threads, where):
                                            ham.info().energy_scale_exp, num_threads=8)
     assert np.array_equal(accepted, oacc) and np.array_equal(tracked, otr)
     assert np.array_equal(xs, oxs) and es.tobytes() == oes.tobytes()
-    x0 = np.random.default_rng(6).integers(0, 2**63, size=(1500 + 63) // 64, dtype=np.uint64)
+    x0 = np.random.default_rng(6).integers(0, 2**64, size=(1500 + 63) // 64, dtype=np.uint64)
     xs, es = sa.anneal_raw(ham, 1, betas[:10], 2, 0, x0)
     oxs, oes, _, _ = oracle.sa_anneal(J, field, 1, betas[:10], 2, 0, x0, ham.info().energy_scale_exp)
     assert np.array_equal(xs, oxs) and es.tobytes() == oes.tobytes()
@@ -1134,12 +1134,14 @@ def test_shuffled_batch_with_a_cluster_beyond_a_byte_per_spin():
     cases = [_shuffled_case(k, d, 6, seed=k) for k, d in ((500, 5.0), (170000, 5.0), (2000, 8.0), (60000, 6.0))]
     hams = [c[2] for c in cases]
     batch = sa.anneal_batch_raw(hams, [3, 4, 5, 6], [c[4] for c in cases], [4, 4, 4, 4], shuffled=True)
+    tr, acc = _stats(hams[1], 4)
     for (J, h, ham, info, betas), seed, (bx, be) in zip(cases, (3, 4, 5, 6), batch):
         sx, se = sa.anneal_raw(ham, seed, betas, 4, 0, None, shuffled=True)
         assert np.array_equal(bx, sx) and be.tobytes() == se.tobytes()
     J, h, ham, info, betas = cases[1]
-    ox, oe, _, _ = oracle.sa_anneal_shuffled(J, h, 4, betas, 4, 0, None, info.energy_scale_exp, num_threads=8)
+    ox, oe, otr, oacc = oracle.sa_anneal_shuffled(J, h, 4, betas, 4, 0, None, info.energy_scale_exp, num_threads=8)
     assert np.array_equal(batch[1][0], ox) and batch[1][1].tobytes() == oe.tobytes()
+    assert np.array_equal(tr, otr) and np.array_equal(acc, oacc)
     # many chains: four per workgroup for the whole batch, four bits per spin for the large one
     big = sa.anneal_batch_raw(hams[:2], [1, 2], [c[4] for c in cases[:2]], [600, 600], shuffled=True)
     for (J, h, ham, info, betas), seed, (bx, be) in zip(cases[:2], (1, 2), big):
@@ -1164,12 +1166,15 @@ def test_shuffled_batch_equals_the_single_calls():
     reps = [6, 3, 9, 2, 5]
     offsets = [0, 4, 1, 0, 2]
     batch = sa.anneal_batch_raw(hams, seeds, [p[4] for p in problems], reps, offsets, shuffled=True)
-    for (J, h, ham, info, betas), seed, r, off, (bx, be) in zip(problems, seeds, reps, offsets, batch):
+    stats = [_stats(ham, r) for ham, r in zip(hams, reps)]
+    for (J, h, ham, info, betas), seed, r, off, (bx, be), (tr, acc) in zip(problems, seeds, reps, offsets,
+                                                                         batch, stats):
         sx, se = sa.anneal_raw(ham, seed, betas, r, off, None, shuffled=True)
         assert np.array_equal(bx, sx) and be.tobytes() == se.tobytes()
-        ox, oe, _, _ = oracle.sa_anneal_shuffled(J, h, seed, betas, r, off, None, info.energy_scale_exp,
-                                                 num_threads=4)
+        ox, oe, otr, oacc = oracle.sa_anneal_shuffled(J, h, seed, betas, r, off, None, info.energy_scale_exp,
+                                                      num_threads=4)
         assert np.array_equal(bx, ox) and be.tobytes() == oe.tobytes()
+        assert np.array_equal(tr, otr) and np.array_equal(acc, oacc)
     # many chains per problem: the batch packs four chains into a workgroup (the single call one)
     big = sa.anneal_batch_raw(hams[:3], [1, 2, 3], [p[4] for p in problems[:3]], [300, 300, 300], shuffled=True)
     for (J, h, ham, info, betas), seed, (bx, be) in zip(problems[:3], (1, 2, 3), big):
@@ -1280,9 +1285,11 @@ def test_shuffled_lane_packing_over_many_chunks_and_in_a_batch():
     sizes = [_shuffled_blocks(c[2])[0] for c in batch]
     assert len(set(sizes)) >= 3 and max(sizes) == 64
     for (J, h, ham, info, betas), seed, reps, (bx, be) in zip(batch, (3, 4, 5, 6), (64, 64, 17, 64), results):
-        oxs, oes, _, _ = oracle.sa_anneal_shuffled(J, h, seed, betas, reps, 0, None, info.energy_scale_exp,
-                                                   num_threads=16)
+        tr, acc = _stats(ham, reps)
+        oxs, oes, otr, oacc = oracle.sa_anneal_shuffled(J, h, seed, betas, reps, 0, None, info.energy_scale_exp,
+                                                        num_threads=16)
         assert np.array_equal(bx, oxs) and be.tobytes() == oes.tobytes()
+        assert np.array_equal(tr, otr) and np.array_equal(acc, oacc)
 
 
 _LEVEL_LAUNCHES = {"ASP_SHUFFLED_ORDER_IN_HBM": "1", "ASP_SHUFFLED_COUNTERS_IN_HBM": "1"}
@@ -1337,9 +1344,14 @@ def test_shuffled_wide_orders_hand_over_to_the_sweep_workgroup(monkeypatch, wide
     other = _shuffled_case(400, 8.0, 60, seed=18)
     results = sa.anneal_batch_raw([ham, other[2]], [5, 6], [betas, other[4]], [4, 4], shuffled=True)
     assert np.array_equal(results[0][0], oxs) and results[0][1].tobytes() == oes.tobytes()
-    o2, e2, _, _ = oracle.sa_anneal_shuffled(other[0], other[1], 6, other[4], 4, 0, None, other[3].energy_scale_exp,
-                                             num_threads=4)
+    o2, e2, otr2, oacc2 = oracle.sa_anneal_shuffled(other[0], other[1], 6, other[4], 4, 0, None,
+                                                    other[3].energy_scale_exp, num_threads=4)
     assert np.array_equal(results[1][0], o2) and results[1][1].tobytes() == e2.tobytes()
+    _, _, otr, oacc = oracle.sa_anneal_shuffled(J, h, 5, betas, 4, 0, None, info.energy_scale_exp,
+                                                num_threads=4)
+    for hm, want_tr, want_acc in ((ham, otr, oacc), (other[2], otr2, oacc2)):
+        tr, acc = _stats(hm, 4)
+        assert np.array_equal(tr, want_tr) and np.array_equal(acc, want_acc)
 
 
 def test_shuffled_batch_mixes_the_order_build_paths():
@@ -1355,9 +1367,11 @@ def test_shuffled_batch_mixes_the_order_build_paths():
     results = sa.anneal_batch_raw([c[2] for c in cases], list(seeds), [c[4] for c in cases], list(reps_of),
                                   shuffled=True)
     for (J, h, ham, info, betas), seed, reps, (bx, be) in zip(cases, seeds, reps_of, results):
-        oxs, oes, _, _ = oracle.sa_anneal_shuffled(J, h, seed, betas, reps, 0, None, info.energy_scale_exp,
-                                                   num_threads=4)
+        tr, acc = _stats(ham, reps)
+        oxs, oes, otr, oacc = oracle.sa_anneal_shuffled(J, h, seed, betas, reps, 0, None, info.energy_scale_exp,
+                                                        num_threads=4)
         assert np.array_equal(bx, oxs) and be.tobytes() == oes.tobytes()
+        assert np.array_equal(tr, otr) and np.array_equal(acc, oacc)
 
 
 def test_shuffled_fill_statistics():
@@ -1402,3 +1416,118 @@ def test_shuffled_sweep_with_the_spins_in_hbm(monkeypatch):
     # the public entry point in its default order
     x, e = sa.anneal(ham, seed=3, number_sweeps=4, repetitions=1)
     assert x.shape == ((n + 63) // 64,) and np.isfinite(e)
+
+
+# ---------------------------------------------------------------------------------------------
+# Edges of the seed and replica-id ranges; the default order under random configurations
+# ---------------------------------------------------------------------------------------------
+
+def test_top_of_the_replica_id_range():
+    """Chains at offset 2^32 - 9 - R (the last R replica ids the entry points accept: ids plus
+    the 8 of a padded group stay below 2^32 - 1) equal the oracle's in the colour order, the
+    shuffled order and a batch of both; one replica more is refused by each entry point."""
+    from annealing_sign_problem_amd import _lib
+    from annealing_sign_problem_amd import annealer as sa
+
+    reps = 13
+    top = 2**32 - 9 - reps
+    J, h, ham, info, betas = _shuffled_case(700, 8.0, 20, seed=41)
+    other = _shuffled_case(300, 5.0, 20, seed=42)
+    S = info.energy_scale_exp
+    seed = 2**33 + 5
+    for shuffled, run in ((False, oracle.sa_anneal), (True, oracle.sa_anneal_shuffled)):
+        label = "shuffled" if shuffled else "colour"
+        xs, es = sa.anneal_raw(ham, seed, betas, reps, top, None, shuffled=shuffled)
+        tracked, accepted = _stats(ham, reps)
+        oxs, oes, otr, oacc = run(J, h, seed, betas, reps, top, None, S, num_threads=8)
+        assert np.array_equal(xs, oxs) and es.tobytes() == oes.tobytes(), label
+        assert np.array_equal(tracked, otr) and np.array_equal(accepted, oacc), label
+        batch = sa.anneal_batch_raw([ham, other[2]], [seed, 3], [betas, other[4]], [reps, 4],
+                                    [top, 0], shuffled=shuffled)
+        assert np.array_equal(batch[0][0], oxs) and batch[0][1].tobytes() == oes.tobytes(), label
+        tracked, accepted = _stats(ham, reps)
+        assert np.array_equal(tracked, otr) and np.array_equal(accepted, oacc), label
+        with pytest.raises(_lib.AspError):
+            sa.anneal_raw(ham, seed, betas, reps + 1, top, None, shuffled=shuffled)
+        with pytest.raises(_lib.AspError):
+            sa.anneal_batch_raw([ham, other[2]], [seed, 3], [betas, other[4]], [reps + 1, 4],
+                                [top, 0], shuffled=shuffled)
+    with pytest.raises(_lib.AspError):
+        sa.anneal_raw(ham, seed, betas, 1, top + reps, None, shuffled=True)
+
+
+def test_shuffled_seeds_beyond_32_bits_at_production_size():
+    """Seeds >= 2^32 put both Philox key words to use in the order build and the acceptance
+    phase: a K = 6000 cluster alone and a batch of three against the oracle, bit for bit,
+    tracked energies and accepted flips included."""
+    from annealing_sign_problem_amd import annealer as sa
+
+    seeds = [2**32, 2**63 + 2**40 + 7, 0xFFFFFFFF_00000001]
+    cases = [_shuffled_case(6000, 20.0, 24, seed=51), _shuffled_case(1500, 12.0, 24, seed=52),
+             _shuffled_case(5000, 23.0, 24, seed=53)]
+    J, h, ham, info, betas = cases[0]
+    xs, es = sa.anneal_raw(ham, seeds[1], betas, 16, 0, None, shuffled=True)
+    tracked, accepted = _stats(ham, 16)
+    oxs, oes, otr, oacc = oracle.sa_anneal_shuffled(J, h, seeds[1], betas, 16, 0, None,
+                                                    info.energy_scale_exp, num_threads=16)
+    assert np.array_equal(xs, oxs) and es.tobytes() == oes.tobytes()
+    assert np.array_equal(tracked, otr) and np.array_equal(accepted, oacc)
+    reps = [8, 12, 5]
+    results = sa.anneal_batch_raw([c[2] for c in cases], seeds, [c[4] for c in cases], reps,
+                                  [0, 3, 1], shuffled=True)
+    for (J, h, ham, info, betas), seed, r, off, (bx, be) in zip(cases, seeds, reps, (0, 3, 1),
+                                                                results):
+        tracked, accepted = _stats(ham, r)
+        oxs, oes, otr, oacc = oracle.sa_anneal_shuffled(J, h, seed, betas, r, off, None,
+                                                        info.energy_scale_exp, num_threads=12)
+        assert np.array_equal(bx, oxs) and be.tobytes() == oes.tobytes(), seed
+        assert np.array_equal(tracked, otr) and np.array_equal(accepted, oacc), seed
+
+
+def test_randomised_shuffled_configurations_match_oracle():
+    """The default (shuffled) order's counterpart of test_randomised_configurations_match_oracle:
+    a hundred random small problems with random ladders (some with a beta = 0 sweep), offsets,
+    starts, seeds (half of them >= 2^32) and launch geometries (chains per workgroup, wavefronts,
+    teams): every chain, tracked energy and flip count equals the oracle's."""
+    from annealing_sign_problem_amd import _lib, synthetic
+    from annealing_sign_problem_amd import annealer as sa
+
+    lib = _lib.load()
+    rng = np.random.default_rng(20261016)
+    for case in range(100):
+        n = int(rng.choice([1, 2, 63, 64, 65, 128, 500, 1024, 1500, 2500]))
+        degree = float(rng.choice([0.0, 1.0, 3.0, 9.0, 24.0]))
+        if degree == 0.0 or n < 4:
+            J = scipy.sparse.diags(rng.normal(size=n)).tocsr()
+            h = rng.normal(size=n)
+        else:
+            J, h, _ = synthetic.planted_cluster(n, seed=int(rng.integers(1 << 30)),
+                                                mean_degree=min(degree, n / 3),
+                                                frustrated_fraction=float(rng.random() * 0.5))
+            h = h + rng.normal(size=n) * float(rng.choice([0.0, 1e-3, 1.0]))
+        sweeps = int(rng.choice([0, 1, 7, 30]))
+        betas = np.geomspace(0.2, float(rng.choice([5.0, 1e4, 1e12])), sweeps) if sweeps else np.zeros(0)
+        if sweeps > 3 and rng.random() < 0.3:
+            betas[sweeps // 2] = 0.0          # an infinite-temperature sweep in the middle
+        reps = int(rng.choice([1, 3, 8, 17]))
+        offset = int(rng.choice([0, 1, 5, 1000]))
+        seed = int(rng.integers(0, 2**32)) + (int(rng.integers(1, 2**32)) << 32 if case % 2 else 0)
+        x0 = None
+        if rng.random() < 0.4:
+            x0 = sa.signs_to_bits(np.where(rng.random(n) < 0.5, 1.0, -1.0))
+        ham = sa.Hamiltonian(J, h)
+        m = int(rng.choice([0, 1, 2, 4, 8]))
+        waves = int(rng.choice([0, 1, 3, 8]))
+        teams = int(rng.choice([0, 1, 2]))
+        _lib.check(lib.asp_sa_set_shuffled_launch(ham.plan(), m, waves))
+        _lib.check(lib.asp_sa_set_shuffled_teams(ham.plan(), teams))
+        label = "case %d: n=%d degree=%s sweeps=%d reps=%d seed=%d m=%d waves=%d teams=%d" % (
+            case, n, degree, sweeps, reps, seed, m, waves, teams)
+        xs, es = sa.anneal_raw(ham, seed, betas, reps, offset, x0, shuffled=True)
+        tracked, accepted = _stats(ham, reps)
+        S = ham.info().energy_scale_exp
+        oxs, oes, otr, oacc = oracle.sa_anneal_shuffled(J, h, seed, betas, reps, offset, x0, S,
+                                                        num_threads=4)
+        assert np.array_equal(xs, oxs), label
+        assert es.tobytes() == oes.tobytes(), label
+        assert np.array_equal(tracked, otr) and np.array_equal(accepted, oacc), label

@@ -52,7 +52,7 @@ def test_energy_equals_numpy(symmetric):
     J, h = _random_problem(777, 0.02, 5, symmetric)
     rng = np.random.default_rng(6)
     words = (777 + 63) // 64
-    xs = rng.integers(0, 2**63, size=(5, words), dtype=np.uint64)
+    xs = rng.integers(0, 2**64, size=(5, words), dtype=np.uint64)
     es = oracle.sa_energy(J, h, xs)
     for x, e in zip(xs, es):
         s = 2.0 * ((x[np.arange(777) // 64] >> (np.arange(777) % 64).astype(np.uint64)) & np.uint64(1)) - 1.0
