@@ -70,6 +70,19 @@ class SaBatchItem(ctypes.Structure):
     ]
 
 
+class SaGreedyItem(ctypes.Structure):
+    """Mirror of ``asp_sa_greedy_item`` (include/asp.h)."""
+
+    _fields_ = [
+        ("plan", c_void_p),
+        ("max_sweeps", c_u32),
+        ("flags", c_u32),
+        ("out_x", c_void_p),
+        ("out_e", c_void_p),
+        ("out_sweeps", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/asp.h declares
 SIGNATURES = {
     "asp_last_error": (ctypes.c_char_p, []),
@@ -151,6 +164,8 @@ SIGNATURES = {
     "asp_sa_anneal_batch": (c_int, [ctypes.POINTER(SaBatchItem), c_u32]),
     "asp_sa_batch_last_ms": (c_float, []),
     "asp_sa_greedy": (c_int, [c_void_p, c_u32, c_void_p, c_void_p, ctypes.POINTER(c_u32)]),
+    "asp_sa_greedy_batch": (c_int, [ctypes.POINTER(SaGreedyItem), c_u32]),
+    "asp_sa_greedy_batch_last_ms": (c_int, [ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
     "asp_sa_greedy_tree_host": (c_int, [c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "asp_sa_last_sweep_ms": (c_float, [c_void_p]),
     "asp_sa_last_total_ms": (c_float, [c_void_p]),

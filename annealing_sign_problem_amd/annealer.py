@@ -35,6 +35,7 @@ __all__ = [
     "anneal",
     "anneal_batch",
     "greedy_solve",
+    "greedy_solve_batch",
     "signs_to_bits",
     "bits_to_signs",
     "make_schedule",
@@ -440,3 +441,16 @@ def greedy_solve(hamiltonian: Hamiltonian):
     from .greedy import greedy_solve as _greedy
 
     return _greedy(hamiltonian)
+
+
+def greedy_solve_batch(hamiltonians, max_sweeps=None, return_sweeps: bool = False):
+    """``[greedy_solve(h) for h in hamiltonians]`` in one device call (``asp_sa_greedy_batch``):
+    identical results, the descents of all problems in shared launches."""
+    from . import greedy as _greedy
+
+    hamiltonians = list(hamiltonians)
+    for h in hamiltonians:
+        if not isinstance(h, Hamiltonian):
+            raise TypeError("'hamiltonians' must hold Hamiltonian objects")
+    return _greedy.greedy_solve_batch(
+        hamiltonians, _greedy.MAX_RELAXATION_SWEEPS if max_sweeps is None else max_sweeps, return_sweeps)

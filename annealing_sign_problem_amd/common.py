@@ -301,13 +301,20 @@ def _project_on_frozen(model: IsingModel, x: np.ndarray, frozen_spins) -> np.nda
 
 
 def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_sweeps: int = 5120,
-                       repetitions: int = 64, sweep_order: Optional[str] = None):
-    """``[solve_ising_model(m, "sa", f, seed, number_sweeps, repetitions) for m, f in
+                       repetitions: int = 64, sweep_order: Optional[str] = None, mode: str = "sa"):
+    """``[solve_ising_model(m, mode, f, seed, number_sweeps, repetitions) for m, f in
     zip(models, frozen_spins)]`` with all annealing chains of all models in ONE device call
     (``sa.anneal_batch``): the same result for every model, at the throughput of a full chip
-    instead of one small launch per model."""
+    instead of one small launch per model.  ``mode="greedy"``: the greedy solves of all models in
+    one call (``sa.greedy_solve_batch``), with the same projection on the frozen spins."""
     models = list(models)
     frozen = [None] * len(models) if frozen_spins is None else list(frozen_spins)
+    if mode == "greedy":
+        solved = sa.greedy_solve_batch([m.ising_hamiltonian for m in models])
+        return [_project_on_frozen(m, x, f) for m, (x, _), f in zip(models, solved, frozen)]
+    if mode != "sa":
+        raise ValueError(
+            "invalid mode specified: '{}'; expected either 'sa' or 'greedy'".format(mode))
     best = sa.anneal_batch([m.ising_hamiltonian for m in models], seed=seed,
                            number_sweeps=number_sweeps, repetitions=repetitions, only_best=True,
                            sweep_order=sweep_order)

@@ -5,12 +5,16 @@
 // whose three cases (both spins new / one new / two clusters) are followed here with a
 // union-find that carries the sign of every spin relative to its cluster root.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <numeric>
+#include <system_error>
+#include <thread>
 #include <vector>
 
 #include "asp_common.hpp"
+#include "greedy.hpp"
 #include "sa_plan.hpp"
 
 namespace asp {
@@ -173,6 +177,37 @@ int greedy_tree_signs(const SaHostLayout &L, uint64_t *x) {
     if (!down[v]) x[v / 64] |= 1ull << (v % 64);
   }
   return ASP_OK;
+}
+
+// greedy_tree_signs for many problems on a small pool of threads (asp_sa_greedy_batch: a caller
+// that batches has no thread per cluster left to hide the trees behind).  Thread safety:
+// greedy_tree_signs is a pure function of the layout it is given — it reads the const
+// SaHostLayout, keeps all its working state in locals, touches no global, no error state and no
+// device, and cannot fail — and problem i writes only x[i], ceil(K_i / 64) words that no other
+// problem shares.  The workers take problem indices from one atomic counter, so the result does
+// not depend on which thread ran which problem, nor on how many threads there are.
+void greedy_tree_signs_many(const SaHostLayout *const *layouts, uint64_t *const *x, size_t count) {
+  constexpr size_t kMaxTreeThreads = 8;
+  size_t workers = std::min(count, kMaxTreeThreads);
+  const unsigned cores = std::thread::hardware_concurrency();
+  if (cores != 0) workers = std::min<size_t>(workers, cores);
+  std::atomic<size_t> next{0};
+  auto work = [&]() {
+    for (size_t i = next.fetch_add(1, std::memory_order_relaxed); i < count;
+         i = next.fetch_add(1, std::memory_order_relaxed)) {
+      (void)greedy_tree_signs(*layouts[i], x[i]);
+    }
+  };
+  std::vector<std::thread> pool;
+  for (size_t w = 1; w < workers; ++w) {
+    try {
+      pool.emplace_back(work);
+    } catch (const std::system_error &) {
+      break;  // no more threads to be had: the ones running (this one at least) do the work
+    }
+  }
+  work();
+  for (std::thread &t : pool) t.join();
 }
 
 }  // namespace asp

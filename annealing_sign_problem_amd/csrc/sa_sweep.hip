@@ -33,10 +33,13 @@
 //     (integer adds commute, so the parallel reduction is deterministic); the
 //     best configuration is snapshotted to HBM at sweep granularity;
 //   * DESCENT instantiation: strict-descent sweeps without random numbers (the
-//     greedy solver's relaxation).
+//     greedy solver's relaxation); k_sa_descent_batch runs the descents of many
+//     problems in one launch, each workgroup stopping after its first sweep
+//     without a flip.
 // f64-VALU- and vector-memory-bound integer+f64 work: no MFMA.
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <initializer_list>
@@ -44,6 +47,7 @@
 #include <vector>
 
 #include "asp_common.hpp"
+#include "greedy.hpp"
 #include "sa_device.hpp"
 #include "sa_internal.hpp"
 #include "sa_plan.hpp"
@@ -368,12 +372,27 @@ __device__ __forceinline__ void snapshot(const uint8_t *spins, const Args &a, ui
   }
 }
 
-// DESCENT = true: strict-descent sweeps (accept iff dE < 0, no random numbers), used by the
-// greedy solver's relaxation; the final configuration is snapshotted after every sweep.
+// How a descent ends (DESCENT only).  NoEarlyStop: all num_sweeps sweeps run (the annealer; the
+// chunks of asp_sa_greedy, whose host looks at the flip count between chunks).  StopWhenStill:
+// the workgroup leaves after the first sweep that flipped nothing and reports the number of
+// sweeps it performed (k_sa_descent_batch).
+struct NoEarlyStop {
+  static constexpr bool kEnabled = false;
+};
+struct StopWhenStill {
+  static constexpr bool kEnabled = true;
+  uint32_t *sweeps_done;  // this problem's word
+};
+
+// DESCENT = true: strict-descent sweeps (accept iff dE < 0, no random numbers, no beta: a.betas is
+// never read), used by the greedy solver's relaxation; the final configuration is snapshotted
+// after every sweep.
 // The whole anneal of one group of M replicas by one workgroup; `group` = index of the group
 // inside its problem (k_sa_sweep: the workgroup id; k_sa_sweep_batch: looked up in a table).
-template <int M, bool DESCENT, int LAYOUT, typename Args>
-__device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t group) {
+template <int M, bool DESCENT, int LAYOUT, typename Args, typename Stop = NoEarlyStop>
+__device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t group,
+                                              const Stop stop = Stop{}) {
+  static_assert(DESCENT || !Stop::kEnabled, "only a descent can stop early");
   constexpr bool GLOBAL = LAYOUT == kGlobal;
   constexpr bool PACKED = LAYOUT == kBits || GLOBAL;  // one bit per position
   constexpr bool WIDE = LAYOUT == kWide;
@@ -476,14 +495,24 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     a.trace[(static_cast<uint64_t>(group) * M + tid) * (a.num_sweeps + 1ull)] = 0;
   }
   double mult[4] = {1.0, 1.0, 1.0, 1.0};  // kWide's multipliers (low words stay 0)
+  // StopWhenStill: sweeps performed, and the chain's accepted flips before the running sweep
+  [[maybe_unused]] uint32_t sweeps_done = a.num_sweeps;
+  [[maybe_unused]] long long flips_before = 0;
   for (uint32_t t = 0; t < a.num_sweeps; ++t) {
-    const double beta = a.betas[t];
+    double beta;
+    if constexpr (DESCENT) {
+      beta = 0.0;  // unused by the descent rule: a certain rejection there is dE >= 0 at any beta
+    } else {
+      beta = a.betas[t];
+    }
     // wave-uniform: cached fields are in use during this sweep
     const bool cached = cache_available && __builtin_amdgcn_readfirstlane(cache_ctl[1]) != 0;
-    if (cached && t > 0 && beta < a.betas[t - 1]) {
-      // certain rejections are only certain for non-decreasing beta (workgroup-uniform branch)
-      for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) inert[b] = 0;
-      __syncthreads();
+    if constexpr (!DESCENT) {
+      if (cached && t > 0 && beta < a.betas[t - 1]) {
+        // certain rejections are only certain for non-decreasing beta (workgroup-uniform branch)
+        for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) inert[b] = 0;
+        __syncthreads();
+      }
     }
     long long q_acc[M];
     uint32_t n_acc[M];  // accepted flips of this lane in this sweep (< 2^32 blocks per sweep)
@@ -711,6 +740,18 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
       }
     }
     __syncthreads();
+    if constexpr (DESCENT && Stop::kEnabled) {
+      // book[16]: flips of the chain so far — complete since the barrier after the reduction, next
+      // written in the following sweep's reduction (colour barriers away).  Workgroup-uniform.
+      // A sweep without a flip left the configuration as the last snapshot holds it.
+      static_assert(M == 1, "one chain decides when the workgroup stops");
+      const long long flips = book[16];
+      if (flips == flips_before) {
+        sweeps_done = t + 1u;
+        break;
+      }
+      flips_before = flips;
+    }
     const uint32_t improved = DESCENT ? ((1u << M) - 1u) : *improved_flag;
     if (improved) snapshot<M, LAYOUT>(spins, a, group, improved);
     if (cache_available && cache_ctl[2] != 0) {
@@ -727,6 +768,9 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     a.tracked[static_cast<uint64_t>(group) * M + tid] = book[8 + tid];
     a.accepted[static_cast<uint64_t>(group) * M + tid] =
         static_cast<unsigned long long>(book[16 + tid]);
+  }
+  if constexpr (DESCENT && Stop::kEnabled) {
+    if (tid == 0) *stop.sweeps_done = sweeps_done;
   }
 }
 
@@ -764,6 +808,36 @@ __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_batch(BatchArgs b) {
   using ConstArgs = const SweepArgs __attribute__((address_space(4)));
   ConstArgs *a = reinterpret_cast<ConstArgs *>(reinterpret_cast<uintptr_t>(b.problems + problem));
   sa_sweep_body<M, false, LAYOUT>(*a, __builtin_amdgcn_readfirstlane(slot.group));
+}
+
+// Many DESCENTS in one launch (asp_sa_greedy_batch): workgroup -> problem through the slot table
+// of k_sa_sweep_batch (every problem is one chain, so its group is always 0).  Each problem starts
+// from its own configuration (s.x0_perm), runs strict-descent sweeps until one flips nothing or
+// s.num_sweeps (the caller's max_sweeps) are done — decided here, by the workgroup that owns the
+// whole chain, with no host round trip — and leaves the number of sweeps in its own word.  What
+// the descent needs beyond SweepArgs lives in this wrapper, so that SweepArgs — shared by every
+// annealing kernel, whose register assignment follows its layout — stays as it is.
+struct DescentProblem {
+  SweepArgs s;            // betas: nullptr (never read); num_sweeps: the cap; trace: nullptr
+  const uint64_t *x0;     // the tree's configuration, packed in original order (bit = +1)
+  uint64_t *x0_perm;      // = s.x0_perm, written by k_permute_bits_problems
+  uint32_t *sweeps_done;  // sweeps performed
+};
+struct DescentBatchArgs {
+  const DescentProblem *problems;
+  const BatchSlot *slots;  // [8][slots_per_xcd]
+  uint32_t slots_per_xcd;
+};
+
+template <int LAYOUT>
+__global__ __launch_bounds__(kMaxThreads) void k_sa_descent_batch(DescentBatchArgs b) {
+  const BatchSlot slot = b.slots[(blockIdx.x & 7u) * b.slots_per_xcd + (blockIdx.x >> 3)];
+  const uint32_t problem = __builtin_amdgcn_readfirstlane(slot.problem);
+  if (problem == 0xFFFFFFFFu) return;
+  // (the constant address space: see k_sa_sweep_batch)
+  using ConstProblem = const DescentProblem __attribute__((address_space(4)));
+  ConstProblem *d = reinterpret_cast<ConstProblem *>(reinterpret_cast<uintptr_t>(b.problems + problem));
+  sa_sweep_body<1, true, LAYOUT>(d->s, 0u, StopWhenStill{d->sweeps_done});
 }
 
 // ---------------------------------------------------------------------------
@@ -1285,6 +1359,21 @@ __global__ __launch_bounds__(256) void k_unpermute_bits(const uint64_t *__restri
   }
 }
 
+// k_permute_bits for the initial configurations of a batch of descents: a workgroup per problem.
+__global__ __launch_bounds__(256) void k_permute_bits_problems(const DescentProblem *problems) {
+  const DescentProblem &d = problems[blockIdx.x];
+  for (uint32_t b = threadIdx.x; b < d.s.num_blocks; b += blockDim.x) {
+    uint64_t word = 0;
+    for (uint32_t l = 0; l < 64; ++l) {
+      const uint32_t spin = d.s.spin_of_pos[b * 64u + l];
+      if (spin == kDummySpin) continue;
+      const uint64_t up = (d.x0[spin >> 6] >> (spin & 63u)) & 1ull;
+      word |= (up ^ 1ull) << l;
+    }
+    d.x0_perm[b] = word;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_unpermute_bits_batch(const PostProblem *problems,
                                                              const BatchSlot *chains) {
   const BatchSlot c = chains[blockIdx.x];
@@ -1578,6 +1667,9 @@ int asp_sa_set_packed(asp_sa_plan *p, int packed) {
 }  // extern "C"
 
 namespace {
+
+int greedy_relax(asp_sa_plan *p, uint32_t max_sweeps, std::vector<uint64_t> &x, uint64_t *out_x,
+                 double *out_e, uint32_t *out_sweeps, bool exact_sweeps);
 
 // All chains of one call; descent = strict-descent sweeps (greedy relaxation).
 int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_sweeps,
@@ -1906,6 +1998,22 @@ int asp_sa_greedy(asp_sa_plan *p, uint32_t max_sweeps, uint64_t *out_x, double *
   // 1. strongest-coupling-first cluster merging on the host (O(E log E))
   std::vector<uint64_t> x(words, 0);
   ASP_TRY(asp::greedy_tree_signs(L, x.data()));
+  return greedy_relax(p, max_sweeps, x, out_x, out_e, out_sweeps, false);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The device half of asp_sa_greedy for a plan with K > 0; x: the tree's configuration (consumed).
+// exact_sweeps (asp_sa_greedy_batch's items that run alone): *out_sweeps is t, the index of the
+// first sweep that flipped nothing (or max_sweeps), as the shared launches report it, instead of
+// the whole chunks performed.  The chunks only tell which one flipped last; that chunk is then
+// replayed from its start one sweep at a time until the final configuration appears — a fixed
+// point of the deterministic sweep, so the first sweep after it is the one that flips nothing.
+int greedy_relax(asp_sa_plan *p, uint32_t max_sweeps, std::vector<uint64_t> &x, uint64_t *out_x,
+                 double *out_e, uint32_t *out_sweeps, bool exact_sweeps) {
+  const uint32_t words = static_cast<uint32_t>(x.size());
   // 2. strict-descent relaxation on the device, in chunks, until a chunk flips nothing
   constexpr uint32_t kChunk = 8;
   std::vector<double> zeros(kChunk, 0.0);
@@ -1915,18 +2023,46 @@ int asp_sa_greedy(asp_sa_plan *p, uint32_t max_sweeps, uint64_t *out_x, double *
   if (max_sweeps == 0) {
     ASP_TRY(asp_sa_energy(p, 1, x.data(), &energy));
   }
+  const bool replay = exact_sweeps && out_sweeps != nullptr;
+  std::vector<uint64_t> flipped_from;  // start of the last chunk that flipped something
+  uint32_t flipped_at = 0, flipped_len = 0;
   while (done < max_sweeps) {
     const uint32_t chunk = std::min(kChunk, max_sweeps - done);
     ASP_TRY(run_chains(p, 0, zeros.data(), chunk, 1, 0, x.data(), true, next.data(), &energy));
+    const bool still = p->last_accepted.empty() || p->last_accepted[0] == 0;
+    if (replay && !still) {
+      flipped_from = x;
+      flipped_at = done;
+      flipped_len = chunk;
+    }
     done += chunk;
     x.swap(next);
-    if (p->last_accepted.empty() || p->last_accepted[0] == 0) break;
+    if (still) break;
   }
   std::copy(x.begin(), x.end(), out_x);
   *out_e = energy;
   if (out_sweeps) *out_sweeps = done;
+  if (replay && max_sweeps != 0) {
+    uint32_t t = 1;  // no chunk flipped: the tree's configuration is a local minimum
+    if (!flipped_from.empty()) {
+      uint32_t u = 0;
+      double unused = 0.0;
+      while (u < flipped_len) {
+        ASP_TRY(run_chains(p, 0, zeros.data(), 1, 1, 0, flipped_from.data(), true, next.data(), &unused));
+        ++u;
+        if (next == x) break;
+        flipped_from.swap(next);
+      }
+      t = std::min(max_sweeps, flipped_at + u + 1u);
+    }
+    *out_sweeps = t;
+  }
   return ASP_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int asp_sa_last_stats(asp_sa_plan const *p, uint32_t count, int64_t *tracked, uint64_t *accepted) {
   if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
@@ -2434,6 +2570,352 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
     p->last_threads = static_cast<int>(64u * waves_of_class(c));
     p->last_groups = static_cast<int>(off[k].groups);
     p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_batch_last_ms
+  }
+  return ASP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Batched greedy solve: many problems' descents in shared launches
+// ---------------------------------------------------------------------------
+// The reference's production job solves tens of thousands of sampled clusters, three models each,
+// with sa.greedy_solve (Makefile:115-127, experiments/sampled_connected_components.py:696-751).
+// asp_sa_greedy spends one workgroup, ~25 launches and a host round trip every 8 sweeps on each.
+// Here the host trees of all items run on a small thread pool, their signs go up in ONE copy and
+// are permuted by ONE launch, every problem is a workgroup of a few shared k_sa_descent_batch
+// launches (one per wavefront count) that decides on the device when it has converged, and the
+// energies, configurations and sweep counts come back in one copy each.
+
+namespace {
+
+thread_local float g_greedy_tree_ms = 0.0f, g_greedy_descent_ms = 0.0f;
+
+}  // namespace
+
+extern "C" {
+
+int asp_sa_greedy_batch_last_ms(float *tree_ms, float *descent_ms) {
+  if (tree_ms) *tree_ms = g_greedy_tree_ms;
+  if (descent_ms) *descent_ms = g_greedy_descent_ms;
+  return ASP_OK;
+}
+
+int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
+  asp_clear_error();
+  g_greedy_tree_ms = g_greedy_descent_ms = 0.0f;
+  if (count == 0) return ASP_OK;
+  if (!items) return asp::set_error(ASP_ERR_INVALID, "null items");
+  // ---- validation: every item before anything runs or is written ----
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_greedy_item &it = items[i];
+    if (!it.plan) return asp::set_error(ASP_ERR_INVALID, "item %u: null plan", i);
+    if (!it.out_x || !it.out_e) return asp::set_error(ASP_ERR_INVALID, "item %u: null output", i);
+    if (it.flags != 0) return asp::set_error(ASP_ERR_INVALID, "item %u: unknown flags 0x%x", i, it.flags);
+  }
+  {
+    std::vector<std::pair<const asp_sa_plan *, uint32_t>> plans(count);
+    for (uint32_t i = 0; i < count; ++i) plans[i] = {items[i].plan, i};
+    std::sort(plans.begin(), plans.end());
+    for (uint32_t i = 1; i < count; ++i) {
+      if (plans[i].first == plans[i - 1].first) {
+        return asp::set_error(ASP_ERR_INVALID, "items %u and %u share a plan", plans[i - 1].second,
+                              plans[i].second);
+      }
+    }
+  }
+  ASP_TRY(asp::bind_device());
+  // ---- which items go into the shared launches ----
+  // A byte per position must fit the LDS (up to ~1.3e5 spins); problems beyond that, plans with a
+  // forced launch geometry, layout or team size, and a batch of one take asp_sa_greedy's device
+  // half (team sweep included).  Results never depend on the path.
+  std::vector<uint32_t> live, shared, alone;  // live: K > 0, in item order
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_greedy_item &it = items[i];
+    const asp_sa_plan *p = it.plan;
+    if (it.out_sweeps) *it.out_sweeps = 0;
+    if (p->host.num_spins == 0) {
+      *it.out_e = 0.0;
+      continue;
+    }
+    live.push_back(i);
+    const bool forced = p->force_m || p->force_threads || p->force_packed || p->team_mode >= 2;
+    if (forced || sweep_lds_bytes(p->host, kBytes) > p->max_lds) {
+      alone.push_back(i);
+    } else {
+      shared.push_back(i);
+    }
+  }
+  if (shared.size() == 1) {
+    alone.push_back(shared[0]);
+    shared.clear();
+  }
+  if (live.empty()) return ASP_OK;
+  // ---- the host trees of ALL live items, on the pool (greedy.cpp) ----
+  std::vector<uint64_t> tree_at(count, 0);  // offset of item i's words in h_x0
+  uint64_t n_words = 0;
+  for (uint32_t i : live) {
+    tree_at[i] = n_words;
+    n_words += (items[i].plan->host.num_spins + 63) / 64;
+  }
+  std::vector<uint64_t> h_x0(n_words, 0);
+  {
+    std::vector<const asp::SaHostLayout *> layouts(live.size());
+    std::vector<uint64_t *> outs(live.size());
+    for (size_t k = 0; k < live.size(); ++k) {
+      layouts[k] = &items[live[k]].plan->host;
+      outs[k] = h_x0.data() + tree_at[live[k]];
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    asp::greedy_tree_signs_many(layouts.data(), outs.data(), live.size());
+    g_greedy_tree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  for (uint32_t i : alone) {
+    const asp_sa_greedy_item &it = items[i];
+    const uint64_t words = (it.plan->host.num_spins + 63) / 64;
+    std::vector<uint64_t> x(h_x0.begin() + tree_at[i], h_x0.begin() + tree_at[i] + words);
+    ASP_TRY(greedy_relax(it.plan, it.max_sweeps, x, it.out_x, it.out_e, it.out_sweeps, true));
+    g_greedy_descent_ms += it.plan->last_sweep_ms;  // (the last chunk's; see asp_sa_greedy_batch_last_ms)
+  }
+  if (shared.empty()) return ASP_OK;
+
+  // ---- launch classes: workgroups of one launch have one wavefront count ----
+  static const uint32_t kWaves[] = {1, 2, 3, 4, 6, 8, 12, 16};
+  constexpr int kNumClasses = sizeof kWaves / sizeof kWaves[0];
+  const size_t n = shared.size();
+  struct Offsets {
+    uint64_t blocks, cache, x;  // best / x0_perm / partial rows; field cache; packed words
+  };
+  std::vector<Offsets> off(n);
+  std::vector<int> class_of(n);
+  std::vector<double> work(n);
+  uint64_t n_blocks = 0, n_cache = 0, n_x = 0;
+  size_t energy_lds = 0;
+  bool use_cache = true;
+  for (size_t k = 0; k < n; ++k) {
+    const asp_sa_plan *p = items[shared[k]].plan;
+    const asp::SaHostLayout &L = p->host;
+    off[k] = Offsets{n_blocks, n_cache, n_x};
+    n_blocks += L.num_blocks;
+    n_cache += static_cast<uint64_t>(L.num_blocks) * 64ull;
+    n_x += (L.num_spins + 63) / 64;
+    // one wavefront per block of the widest colour class, at most 16: the single path's choice
+    const uint32_t waves = std::min<uint32_t>(widest_color(L), 16u);
+    int c = kNumClasses - 1;
+    for (int j = 0; j < kNumClasses; ++j) {
+      if (waves <= kWaves[j]) {
+        c = j;
+        break;
+      }
+    }
+    class_of[k] = c;
+    work[k] = static_cast<double>(L.ell_off.back() + L.num_blocks);
+    energy_lds = std::max(energy_lds, static_cast<size_t>(L.num_blocks) * sizeof(uint64_t));
+    use_cache = use_cache && p->use_field_cache;
+  }
+  if (n_cache * sizeof(double) > (32ull << 30)) use_cache = false;
+  const size_t max_lds = items[shared[0]].plan->max_lds;
+
+  // (host arrays of the asynchronous uploads first, so that they outlive the stream's work)
+  std::vector<uint64_t> h_x0_shared(n_x);
+  std::vector<DescentProblem> h_problems(n);
+  std::vector<PostProblem> h_post(n);
+  std::vector<BatchSlot> h_chains(n), h_slots;
+  std::vector<uint64_t> h_x(n_x);
+  std::vector<double> h_e(n);
+  std::vector<uint32_t> h_sweeps(n);
+  asp::ScopedStream main_stream;
+  ASP_TRY(main_stream.acquire());
+  hipStream_t s = main_stream.stream;
+  asp::ScopedStream class_stream[kNumClasses];
+  DeviceBuffer<uint64_t> d_x0, d_x0_perm, d_best, d_x;
+  DeviceBuffer<double> d_partial, d_e, d_cache;
+  DeviceBuffer<long long> d_tracked;
+  DeviceBuffer<unsigned long long> d_accepted;
+  DeviceBuffer<uint32_t> d_sweeps;
+  DeviceBuffer<DescentProblem> d_problems;
+  DeviceBuffer<PostProblem> d_post;
+  DeviceBuffer<BatchSlot> d_slots, d_chains;
+  asp::StreamFence fence(s);
+  ASP_TRY(d_x0.alloc(n_x));
+  ASP_TRY(d_x0_perm.alloc(n_blocks));
+  ASP_TRY(d_best.alloc(n_blocks));
+  ASP_TRY(d_x.alloc(n_x));
+  ASP_TRY(d_partial.alloc(n_blocks));
+  ASP_TRY(d_e.alloc(n));
+  ASP_TRY(d_tracked.alloc(n));
+  ASP_TRY(d_accepted.alloc(n));
+  ASP_TRY(d_sweeps.alloc(n));
+  if (use_cache && d_cache.alloc(n_cache) != ASP_OK) {
+    asp_clear_error();  // the cache is an optimisation: run without it
+    use_cache = false;
+  }
+  // ---- descriptors ----
+  for (size_t k = 0; k < n; ++k) {
+    const asp_sa_greedy_item &it = items[shared[k]];
+    const asp_sa_plan *p = it.plan;
+    const asp::SaHostLayout &L = p->host;
+    const uint64_t words = (L.num_spins + 63) / 64;
+    std::copy(h_x0.begin() + tree_at[shared[k]], h_x0.begin() + tree_at[shared[k]] + words,
+              h_x0_shared.begin() + off[k].x);
+    DescentProblem d{};
+    SweepArgs &a = d.s;
+    a.color_block_start = p->color_block_start.ptr;
+    a.block_width = p->block_width.ptr;
+    a.ell_off = p->ell_off.ptr;
+    a.ell_col = p->ell_col.ptr;
+    a.ell_val = p->ell_val.ptr;
+    a.spin_of_pos = p->spin_of_pos.ptr;
+    a.field_pos = p->field_pos.ptr;
+    a.betas = nullptr;  // the descent reads none
+    a.x0_perm = d_x0_perm.ptr + off[k].blocks;
+    a.best_perm = d_best.ptr + off[k].blocks;
+    a.tracked = d_tracked.ptr + k;
+    a.accepted = d_accepted.ptr + k;
+    a.seed = 0;
+    a.scale = std::ldexp(1.0, L.energy_scale_exp);
+    a.num_colors = L.num_colors;
+    a.num_blocks = L.num_blocks;
+    a.num_sweeps = it.max_sweeps;
+    a.replica_first = 0;
+    // the field cache and its inert blocks as in the single path: late sweeps flip little
+    a.field_cache = use_cache ? d_cache.ptr + off[k].cache : nullptr;
+    const double degree =
+        std::max(1.0, static_cast<double>(L.a_col.size()) / static_cast<double>(L.num_spins));
+    a.cache_enter_flips =
+        static_cast<uint32_t>(std::max(1.0, 0.7 * static_cast<double>(L.num_blocks) / degree));
+    a.spin_words = nullptr;
+    a.trace = nullptr;
+    d.x0 = d_x0.ptr + off[k].x;
+    d.x0_perm = d_x0_perm.ptr + off[k].blocks;
+    d.sweeps_done = d_sweeps.ptr + k;
+    h_problems[k] = d;
+    PostProblem pp{};
+    pp.e = EnergyArgs{p->block_width.ptr, p->ell_off.ptr, p->ell_col.ptr, p->ell_val.ptr,
+                      p->field_pos.ptr, d_best.ptr + off[k].blocks, d_partial.ptr + off[k].blocks,
+                      L.num_blocks};
+    pp.pos_of_spin = p->pos_of_spin.ptr;
+    pp.num_spins = L.num_spins;
+    pp.words = static_cast<uint32_t>(words);
+    pp.diag_sum = L.diag_sum;
+    pp.out_e = d_e.ptr + k;
+    pp.out_x = d_x.ptr + off[k].x;
+    h_post[k] = pp;
+    h_chains[k] = BatchSlot{static_cast<uint32_t>(k), 0u};
+  }
+  // ---- slot tables: per class, problems longest first, dealt round-robin to the 8 XCDs ----
+  struct ClassLaunch {
+    uint64_t slot_at = 0;
+    uint32_t slots_per_xcd = 0;
+    size_t lds = 0;
+    bool used = false;
+  };
+  ClassLaunch launches[kNumClasses];
+  for (int c = 0; c < kNumClasses; ++c) {
+    std::vector<size_t> members;
+    for (size_t k = 0; k < n; ++k) {
+      if (class_of[k] == c) members.push_back(k);
+    }
+    if (members.empty()) continue;
+    std::stable_sort(members.begin(), members.end(), [&](size_t a, size_t b) { return work[a] > work[b]; });
+    std::vector<BatchSlot> per_xcd[8];
+    for (size_t j = 0; j < members.size(); ++j) {
+      per_xcd[j % 8].push_back(BatchSlot{static_cast<uint32_t>(members[j]), 0u});
+      launches[c].lds =
+          std::max(launches[c].lds, sweep_lds_bytes(items[shared[members[j]]].plan->host, kBytes));
+    }
+    const uint32_t most = static_cast<uint32_t>(per_xcd[0].size());  // XCD 0 is dealt to first
+    launches[c].used = true;
+    launches[c].slot_at = h_slots.size();
+    launches[c].slots_per_xcd = most;
+    for (int x = 0; x < 8; ++x) {
+      per_xcd[x].resize(most, BatchSlot{0xFFFFFFFFu, 0});
+      h_slots.insert(h_slots.end(), per_xcd[x].begin(), per_xcd[x].end());
+    }
+  }
+  ASP_TRY(d_problems.alloc(n));
+  ASP_TRY(d_post.alloc(n));
+  ASP_TRY(d_slots.alloc(h_slots.size()));
+  ASP_TRY(d_chains.alloc(n));
+  ASP_TRY(d_x0.upload(h_x0_shared.data(), n_x, s));
+  ASP_TRY(d_problems.upload(h_problems.data(), n, s));
+  ASP_TRY(d_post.upload(h_post.data(), n, s));
+  ASP_TRY(d_slots.upload(h_slots.data(), h_slots.size(), s));
+  ASP_TRY(d_chains.upload(h_chains.data(), n, s));
+  hipEvent_t ev[2 + kNumClasses] = {};
+  struct EventGuard {
+    hipEvent_t *ev;
+    int n;
+    ~EventGuard() {
+      for (int i = 0; i < n; ++i) {
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+      }
+    }
+  } event_guard{ev, 2 + kNumClasses};
+  for (auto &e : ev) ASP_HIP_TRY(hipEventCreate(&e));
+  // every problem's tree signs into block order: one launch
+  hipLaunchKernelGGL(k_permute_bits_problems, dim3(static_cast<unsigned>(n)), dim3(256), 0, s,
+                     d_problems.ptr);
+  ASP_HIP_TRY(hipGetLastError());
+  ASP_HIP_TRY(hipEventRecord(ev[0], s));
+  // ---- one descent launch per class, each on its own stream so that they share the chip ----
+  for (int c = 0; c < kNumClasses; ++c) {
+    if (!launches[c].used) continue;
+    ASP_TRY(class_stream[c].acquire());
+    hipStream_t cs = class_stream[c].stream;
+    ASP_HIP_TRY(hipStreamWaitEvent(cs, ev[0], 0));
+    DescentBatchArgs b{d_problems.ptr, d_slots.ptr + launches[c].slot_at, launches[c].slots_per_xcd};
+    if (launches[c].lds > 64 * 1024) {
+      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sa_descent_batch<kBytes>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      static_cast<int>(launches[c].lds)));
+    }
+    hipLaunchKernelGGL(k_sa_descent_batch<kBytes>, dim3(8u * launches[c].slots_per_xcd),
+                       dim3(64u * kWaves[c]), launches[c].lds, cs, b);
+    ASP_HIP_TRY(hipGetLastError());
+    ASP_HIP_TRY(hipEventRecord(ev[2 + c], cs));
+    ASP_HIP_TRY(hipStreamWaitEvent(s, ev[2 + c], 0));
+  }
+  ASP_HIP_TRY(hipEventRecord(ev[1], s));
+  // ---- energies (the kernels and so the reduction order of energies_of_perm) and
+  // original-order bits of every problem's final configuration ----
+  const unsigned chains = static_cast<unsigned>(n);
+  if (energy_lds > max_lds) {
+    hipLaunchKernelGGL(k_sa_energy_blocks_batch<false>, dim3(chains), dim3(512), 0, s, d_post.ptr,
+                       d_chains.ptr);
+  } else {
+    if (energy_lds > 64 * 1024) {
+      ASP_HIP_TRY(hipFuncSetAttribute(
+          reinterpret_cast<const void *>(k_sa_energy_blocks_batch<true>),
+          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(energy_lds)));
+    }
+    hipLaunchKernelGGL(k_sa_energy_blocks_batch<true>, dim3(chains), dim3(512), energy_lds, s,
+                       d_post.ptr, d_chains.ptr);
+  }
+  hipLaunchKernelGGL(k_sa_energy_fold_batch, dim3(chains), dim3(64), 0, s, d_post.ptr, d_chains.ptr);
+  hipLaunchKernelGGL(k_unpermute_bits_batch, dim3(chains), dim3(256), 0, s, d_post.ptr, d_chains.ptr);
+  ASP_HIP_TRY(hipGetLastError());
+  ASP_TRY(d_x.download(h_x.data(), n_x, s));
+  ASP_TRY(d_e.download(h_e.data(), n, s));
+  ASP_TRY(d_sweeps.download(h_sweeps.data(), n, s));
+  ASP_HIP_TRY(hipStreamSynchronize(s));
+  float ms = 0.0f;
+  ASP_HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  g_greedy_descent_ms += ms;
+  for (size_t k = 0; k < n; ++k) {
+    const asp_sa_greedy_item &it = items[shared[k]];
+    asp_sa_plan *p = it.plan;
+    const uint64_t words = (p->host.num_spins + 63) / 64;
+    std::copy(h_x.begin() + off[k].x, h_x.begin() + off[k].x + words, it.out_x);
+    *it.out_e = h_e[k];
+    if (it.out_sweeps) *it.out_sweeps = h_sweeps[k];
+    p->last_tracked.clear();  // (the shared launches bring no per-chain statistics back)
+    p->last_accepted.clear();
+    p->last_m = 1;
+    p->last_layout = kBytes;
+    p->last_threads = static_cast<int>(64u * kWaves[class_of[k]]);
+    p->last_groups = 1;
+    p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_greedy_batch_last_ms
   }
   return ASP_OK;
 }

@@ -215,12 +215,15 @@ def process_cluster(cluster, hamiltonian, ground_state, noisy_ground_state, nois
 
 
 def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, noisy_ground_state,
-                   noisy_log_coeff_fn, order: int, global_cutoff: float, jobs: int = 1):
+                   noisy_log_coeff_fn, order: int, global_cutoff: float, jobs: int = 1,
+                   greedy_batch: bool = False):
     """First half of :func:`process_clusters_batched`: the models of every order of every cluster,
     each with its greedy result — a list of ``(cluster index, model, exact_signs, weights, result
     so far)`` in cluster order.  The models of a cluster do not depend on its solutions (the
     extension of order i grows from the model of order i-1, common.py:516), so they can all be
-    built before anything is annealed."""
+    built before anything is annealed.  ``greedy_batch``: the models are built first (on the
+    ``jobs`` threads) and ALL of them are then solved by one ``greedy_solve_batch`` call instead
+    of one ``greedy_solve`` each; the results are the same."""
     basis = hamiltonian.basis
 
     def stage(item):
@@ -235,11 +238,24 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
             else:
                 h = common.make_hamiltonian_extension(h, noisy_log_coeff_fn)
                 h = common.sparsify_using_global_cutoff(h, global_cutoff, cluster)
-            r = solve_and_test_model(h, cluster, exact_signs, weights, annealing=False)
+            if greedy_batch:  # (the greedy columns are filled in below)
+                r = OptimizationResult(h.size, float("nan"), float("nan"), float("nan"), float("nan"),
+                                       float("nan"))
+            else:
+                r = solve_and_test_model(h, cluster, exact_signs, weights, annealing=False)
             r.amplitude_overlap = amplitude_overlap(h.spins, ground_state, noisy_ground_state, basis,
                                                     h.basis_index)
             out.append((index, h, exact_signs, weights, r))
         return out
+
+    def solved(staged):
+        if greedy_batch and staged:
+            solutions = common.solve_ising_models([m for _, m, _, _, _ in staged],
+                                                  [clusters[c] for c, _, _, _, _ in staged], mode="greedy")
+            for (_, _, exact_signs, weights, r), x in zip(staged, solutions):
+                r.greedy_accuracy, r.greedy_overlap = common.compute_accuracy_and_overlap(x, exact_signs,
+                                                                                          weights)
+        return staged
 
     # the builds of different clusters are independent and their C calls release the GIL: --jobs
     # host threads keep several in flight on the GPU (own streams); order of the list = cluster
@@ -248,8 +264,8 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
         from concurrent.futures import ThreadPoolExecutor
 
         with ThreadPoolExecutor(max_workers=jobs) as pool:
-            return [entry for part in pool.map(stage, enumerate(clusters)) for entry in part]
-    return [entry for item in enumerate(clusters) for entry in stage(item)]
+            return solved([entry for part in pool.map(stage, enumerate(clusters)) for entry in part])
+    return solved([entry for item in enumerate(clusters) for entry in stage(item)])
 
 
 def anneal_staged(staged, clusters: Sequence[np.ndarray], annealing: bool,
@@ -280,12 +296,13 @@ def anneal_staged(staged, clusters: Sequence[np.ndarray], annealing: bool,
 def process_clusters_batched(clusters: Sequence[np.ndarray], hamiltonian, ground_state,
                              noisy_ground_state, noisy_log_coeff_fn, order: int,
                              global_cutoff: float, annealing: bool, jobs: int = 1,
-                             sweep_order: Optional[str] = None) -> List[List[OptimizationResult]]:
+                             sweep_order: Optional[str] = None,
+                             greedy_batch: bool = False) -> List[List[OptimizationResult]]:
     """``[process_cluster(c, ...) for c in clusters]`` with the annealing of ALL models — every
     cluster at every order — in one batched device call (:func:`stage_clusters`, then
     :func:`anneal_staged`); the results are identical to the per-cluster loop."""
     staged = stage_clusters(clusters, hamiltonian, ground_state, noisy_ground_state, noisy_log_coeff_fn,
-                            order, global_cutoff, jobs)
+                            order, global_cutoff, jobs, **({"greedy_batch": True} if greedy_batch else {}))
     return anneal_staged(staged, clusters, annealing, sweep_order)
 
 
@@ -327,6 +344,10 @@ def parse_command_line(argv=None):
                              "node.  On ONE GPU it does not pay (the device multiplexes processes at "
                              "a higher cost than the interpreter lock: profiles/r03_pipeline_workers.txt)."
                              "  The output does not depend on it")
+    parser.add_argument("--greedy-batch", default=False, action="store_true",
+                        help="solve the greedy models of a round of --batch clusters with ONE batched "
+                             "call (greedy_solve_batch) instead of one greedy_solve per model; the "
+                             "output is the same")
     parser.add_argument("--jobs", type=int, default=1,
                         help="host threads building / solving clusters concurrently (independent "
                              "plans and HIP streams on one GPU; the output does not depend on it)")
@@ -498,10 +519,11 @@ def _worker_chunk(indices):
     else:
         report = lambda lines: lines  # noqa: E731
     some = [w["clusters"][c] for c in indices]
-    if args.batch > 1 and args.annealing:
+    if args.batch > 1 and (args.annealing or args.greedy_batch):
         chunk = process_clusters_batched(some, w["hamiltonian"], w["ground_state"], w["noisy_ground_state"],
                                          w["log_coeff_fn"], args.order, args.global_cutoff, args.annealing,
-                                         jobs=args.jobs, sweep_order=args.sweep_order)
+                                         jobs=args.jobs, sweep_order=args.sweep_order,
+                                         **({"greedy_batch": True} if args.greedy_batch else {}))
         return report([",".join(r.to_csv_str() for r in columns) for columns in chunk])
 
     def work(cluster):
@@ -676,9 +698,12 @@ def _main_in_group(args, asp_dist, created_group, phase):
                                noisy_log_coeff_fn, args.order, args.global_cutoff, args.annealing,
                                args.sweep_order)
 
+    # (the keyword is passed only with --greedy-batch: without it every call is the one it was)
+    greedy_batch = {"greedy_batch": True} if args.greedy_batch else {}
+
     def work_many(some):
         """CSV lines of a list of clusters, their annealing batched --batch clusters at a time."""
-        if args.batch <= 1 or not args.annealing:
+        if args.batch <= 1 or not (args.annealing or args.greedy_batch):
             if args.jobs > 1 and len(some) > 1:
                 from concurrent.futures import ThreadPoolExecutor
 
@@ -690,7 +715,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
             chunk = process_clusters_batched(some[start:start + args.batch], hamiltonian,
                                              ground_state, noisy_ground_state, noisy_log_coeff_fn,
                                              args.order, args.global_cutoff, args.annealing,
-                                             jobs=args.jobs, sweep_order=args.sweep_order)
+                                             jobs=args.jobs, sweep_order=args.sweep_order, **greedy_batch)
             lines += [",".join(r.to_csv_str() for r in columns) for columns in chunk]
         return lines
 
@@ -720,7 +745,8 @@ def _main_in_group(args, asp_dist, created_group, phase):
 
             def stage(some):
                 return stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
-                                      noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs)
+                                      noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
+                                      **greedy_batch)
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(stage, my_share(0)) if rounds else None
@@ -744,7 +770,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
     # With --jobs > 1 several clusters are in flight on one GPU at once — the C calls release
     # the GIL and every Hamiltonian owns its stream.  All randomness was consumed above, so the
     # lines written are identical for any --jobs and any --batch.
-    if args.jobs > 1 and (args.batch <= 1 or not args.annealing):
+    if args.jobs > 1 and (args.batch <= 1 or not (args.annealing or args.greedy_batch)):
         from concurrent.futures import ThreadPoolExecutor
 
         import collections
@@ -768,12 +794,13 @@ def _main_in_group(args, asp_dist, created_group, phase):
         step = max(args.batch, 1)
         lines_of = lambda columns_of_clusters: [",".join(r.to_csv_str() for r in columns)  # noqa: E731
                                                 for columns in columns_of_clusters]
-        if step > 1 and args.annealing:
+        if step > 1 and (args.annealing or args.greedy_batch):
             def next_round():
                 """(clusters, their staged models) of the next round; only this thread pulls clusters."""
                 some = list(itertools.islice(clusters, step))
                 return some, stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
-                                            noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs)
+                                            noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
+                                            **greedy_batch)
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(next_round)

@@ -501,6 +501,41 @@ float asp_sa_batch_last_ms(void);
 int asp_sa_greedy(asp_sa_plan *p, uint32_t max_sweeps, uint64_t *out_x, double *out_e,
                   uint32_t *out_sweeps);
 
+/* Many asp_sa_greedy calls in ONE: the host trees of all items run on a small
+ * thread pool inside the call (at most 8 threads), their signs are uploaded and permuted together,
+ * every problem is one workgroup of a few shared launches (k_sa_descent_batch, one launch per
+ * wavefront count) that leaves its sweep loop ON THE DEVICE after the first sweep that flipped
+ * nothing, and configurations, energies and sweep counts come back in one copy each.
+ *  - Item i's out_x and out_e are exactly what asp_sa_greedy(plan, max_sweeps, ...) returns: the
+ *    same words and the same double, for any composition and order of the batch.
+ *  - out_sweeps (may be NULL) is the EXACT number of sweeps performed, t: the index (from 1) of the
+ *    first sweep that flipped nothing, or max_sweeps if none did.  asp_sa_greedy reports whole
+ *    chunks of 8 instead: min(max_sweeps, 8 * (ceil((t - 1) / 8) + 1)) for the same problem (a
+ *    fixed point of the deterministic sweep stays fixed).  max_sweeps = 0 returns the tree's
+ *    configuration and its energy.
+ *  - All items are validated before anything runs or any output is written: a null plan, a null
+ *    out_x or out_e, flags other than 0 and two items sharing a plan are ASP_ERR_INVALID, with the
+ *    item's index in the message.  count = 0 is fine (no device needed), and so are plans with
+ *    K = 0 (energy 0, no sweeps, out_x untouched).
+ *  - Items that do not fit the shared launches — more spins than a byte per position holds in the
+ *    LDS (~1.3e5), a plan with a forced launch geometry, layout or team size, a batch of one —
+ *    take asp_sa_greedy's path inside the call, team sweeps included.  Results, out_sweeps among
+ *    them, never depend on which path ran.
+ * A plan is used by one thread at a time, as everywhere. */
+typedef struct asp_sa_greedy_item {
+  asp_sa_plan *plan;
+  uint32_t max_sweeps;
+  uint32_t flags;        /* 0; anything else is ASP_ERR_INVALID */
+  uint64_t *out_x;       /* ceil(K/64) words */
+  double *out_e;         /* 1 */
+  uint32_t *out_sweeps;  /* may be NULL */
+} asp_sa_greedy_item;
+int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count);
+/* Of this thread's last asp_sa_greedy_batch call, in ms (either pointer may be NULL): wall time of
+ * the host trees on the pool, and device time of the descent launches (HIP events around the
+ * shared launches, plus the last chunk's of every item that ran alone). */
+int asp_sa_greedy_batch_last_ms(float *tree_ms, float *descent_ms);
+
 /* Host-only: the cluster-merging half of asp_sa_greedy (no relaxation, no device). */
 int asp_sa_greedy_tree_host(uint64_t num_spins, int64_t const *indptr, int32_t const *indices,
                             double const *data, double const *field, uint64_t *out_x);
