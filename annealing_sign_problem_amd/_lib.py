@@ -155,6 +155,8 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p]),
     "asp_sa_anneal_shuffled": (c_int, [c_void_p, c_u64, c_void_p, c_u32, c_u32, c_u32, c_void_p, c_void_p,
                                        c_void_p]),
+    "asp_sa_anneal_shuffled_trace": (c_int, [c_void_p, c_u64, c_void_p, c_u32, c_u32, c_u32, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
     "asp_sa_set_shuffled_launch": (c_int, [c_void_p, c_int, c_int]),
     "asp_sa_set_shuffled_teams": (c_int, [c_void_p, c_int]),
     "asp_sa_last_shuffled": (c_int, [c_void_p, ctypes.POINTER(c_u32), ctypes.POINTER(c_float)]),

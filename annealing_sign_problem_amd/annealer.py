@@ -34,6 +34,7 @@ __all__ = [
     "Hamiltonian",
     "anneal",
     "anneal_batch",
+    "anneal_traces",
     "greedy_solve",
     "greedy_solve_batch",
     "signs_to_bits",
@@ -392,9 +393,11 @@ def anneal_batch(hamiltonians, seed=None, number_sweeps: int = 5120, repetitions
 
 
 def anneal_trace_raw(hamiltonian: Hamiltonian, seed: int, betas: np.ndarray, repetitions: int,
-                     replica_offset: int = 0, x0=None):
+                     replica_offset: int = 0, x0=None, shuffled: bool = False):
     """``anneal_raw`` plus ``trace int64[R, T+1]``: tracked energy of every chain after each
-    sweep in units of ``2**-energy_scale_exp``, relative to its initial configuration."""
+    sweep in units of ``2**-energy_scale_exp``, relative to its initial configuration.
+    ``shuffled``: a fresh visiting order every sweep (``asp_sa_anneal_shuffled_trace``) instead of
+    the colour order (``asp_sa_anneal_trace``), as in ``anneal_raw``."""
     lib = _lib.load()
     plan = hamiltonian.plan()
     words = (hamiltonian.size + 63) // 64
@@ -406,34 +409,68 @@ def anneal_trace_raw(hamiltonian: Hamiltonian, seed: int, betas: np.ndarray, rep
         x0 = np.ascontiguousarray(x0, dtype=np.uint64).reshape(-1)
         if x0.shape[0] != words:
             raise ValueError("'x0' must have {} words".format(words))
-    _lib.check(lib.asp_sa_anneal_trace(plan, ctypes.c_uint64(seed), _lib.ptr(betas),
-                                       ctypes.c_uint32(betas.shape[0]),
-                                       ctypes.c_uint32(repetitions),
-                                       ctypes.c_uint32(replica_offset), _lib.ptr(x0),
-                                       _lib.ptr(xs), _lib.ptr(es), _lib.ptr(trace)))
+    entry = lib.asp_sa_anneal_shuffled_trace if shuffled else lib.asp_sa_anneal_trace
+    _lib.check(entry(plan, ctypes.c_uint64(seed), _lib.ptr(betas),
+                     ctypes.c_uint32(betas.shape[0]), ctypes.c_uint32(repetitions),
+                     ctypes.c_uint32(replica_offset), _lib.ptr(x0),
+                     _lib.ptr(xs), _lib.ptr(es), _lib.ptr(trace)))
     return xs[:, :words], es, trace
 
 
+def anneal_traces(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: int = 5120,
+                  beta0: Optional[float] = None, beta1: Optional[float] = None, repetitions: int = 1,
+                  sweep_order: Optional[str] = None):
+    """``anneal(..., only_best=False)`` with the energy of every chain after every sweep:
+    ``(xs[R, words], es[R], e_current[R, T+1], e_best[R, T+1])`` in energy units.  Column 0 is the
+    initial configuration, ``e_best`` the running minimum of ``e_current``, ``e_best[r, -1] ==
+    es[r]``.
+
+    Every chain is anchored the way ``anneal_with_traces`` anchors its one chain: the traces are
+    the kernel's exact integer bookkeeping of the accepted ``dE``, shifted so that the chain's best
+    value is ``es[r]``, the returned configuration's energy recomputed in full precision.
+
+    ``sweep_order`` as in ``anneal``: ``None`` (default) is ``$ASP_SWEEP_ORDER`` if set, else
+    ``"shuffled"`` — the chains ``anneal`` runs with the same seed.  Chains stay on this rank."""
+    shuffled = resolve_sweep_order(sweep_order) == "shuffled"  # (first: a bad order fails without a GPU)
+    if not isinstance(hamiltonian, Hamiltonian):
+        raise TypeError("'hamiltonian' must be a Hamiltonian")
+    repetitions = int(repetitions)
+    if repetitions < 1:
+        raise ValueError("'repetitions' must be positive")
+    info = hamiltonian.info()
+    beta0 = info.beta0_auto if beta0 is None else beta0
+    beta1 = info.beta1_auto if beta1 is None else beta1
+    betas = make_schedule(float(beta0), float(beta1), number_sweeps)
+    xs, es, trace = anneal_trace_raw(hamiltonian, _resolve_seed(seed), betas, repetitions, 0, x0,
+                                     shuffled=shuffled)
+    unit = 2.0 ** -info.energy_scale_exp
+    best = np.minimum.accumulate(trace, axis=1)
+    floor = best[:, -1:]
+    e_best = es[:, None] + (best - floor).astype(np.float64) * unit
+    e_current = es[:, None] + (trace - floor).astype(np.float64) * unit
+    return xs, es, e_current, e_best
+
+
 def anneal_with_traces(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: int = 5120,
-                       beta0: Optional[float] = None, beta1: Optional[float] = None):
+                       beta0: Optional[float] = None, beta1: Optional[float] = None,
+                       sweep_order: Optional[str] = "colour"):
     """The older annealer API (annealing_sign_problem/train.py:238-245, square_deep.py:181-183):
     one chain, ``(x, e_current, e_best)`` with the energy after every sweep and the best energy
     so far (``e_best[0]`` before the first sweep, ``e_best[-1]`` the returned configuration's).
 
     The traces come from the kernel's exact integer bookkeeping of the accepted ``dE`` and are
-    anchored at the returned configuration's energy, which is recomputed in full precision."""
+    anchored at the returned configuration's energy, which is recomputed in full precision.
+
+    ``sweep_order="colour"`` (the default, what this function has always run) traces the fixed
+    colour order — NOT the chain ``anneal(h, seed=seed)`` runs.  ``sweep_order=None`` gives the
+    chain ``anneal()`` runs: ``$ASP_SWEEP_ORDER`` if set, else ``"shuffled"``, the reference
+    annealer's order.  ``sweep_order="shuffled"`` asks for that order by name."""
+    sweep_order = resolve_sweep_order(sweep_order)  # (first: a bad order fails without a GPU)
     if not isinstance(hamiltonian, Hamiltonian):
         raise TypeError("'hamiltonian' must be a Hamiltonian")
-    info = hamiltonian.info()
-    beta0 = info.beta0_auto if beta0 is None else beta0
-    beta1 = info.beta1_auto if beta1 is None else beta1
-    betas = make_schedule(float(beta0), float(beta1), number_sweeps)
-    xs, es, trace = anneal_trace_raw(hamiltonian, _resolve_seed(seed), betas, 1, 0, x0)
-    unit = 2.0 ** -info.energy_scale_exp
-    best = np.minimum.accumulate(trace[0])
-    e_best = es[0] + (best - best[-1]).astype(np.float64) * unit
-    e_current = es[0] + (trace[0] - best[-1]).astype(np.float64) * unit
-    return xs[0].copy(), e_current, e_best
+    xs, _, e_current, e_best = anneal_traces(hamiltonian, x0, seed, number_sweeps, beta0, beta1, 1,
+                                             sweep_order)
+    return xs[0].copy(), e_current[0], e_best[0]
 
 
 def greedy_solve(hamiltonian: Hamiltonian):

@@ -36,6 +36,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "asp_common.hpp"
@@ -976,6 +977,16 @@ struct ShuffledArgs {
   uint32_t waves;  // wavefronts (per team) of this problem's workgroups
 };
 
+// The arguments of the kernels with TRACE = true (asp_sa_anneal_shuffled_trace): per-sweep energy
+// traces, trace[c][t + 1] = tracked energy of chain c of the call after sweep t of the call, rows of
+// trace_stride = sweeps of the call + 1 values for the trace_chains real chains of the call (the
+// chains padding the last group have no row).  A struct of their own: ShuffledArgs — the descriptor
+// the batched kernels read from a table — keeps its size.
+struct ShuffledTraceArgs : ShuffledArgs {
+  long long *trace;
+  uint32_t trace_chains, trace_stride;
+};
+
 // Spins stay in LDS in ORIGINAL order, in one of four layouts: a 32-bit word per spin (kWide: byte
 // m = 0x80 * chain m is -1; up to four chains), a byte per spin (kBytes: bit m; up to eight), and —
 // for clusters beyond the capacity of bytes — four bits per spin (kNibbles: up to four chains,
@@ -1231,7 +1242,10 @@ static_assert(kFirstQuads <= kHeldQuads, "the first request is part of the held 
 // column + base of the lane's group (one VALU add per gather), the energy bookkeeping is
 // reduced over the S lanes of a group.  Everything else — arithmetic, random words, the order
 // of the terms — is the lane = spin kernel's; every chain is bit for bit the same.
-template <int M, int LAYOUT, int TEAMS, bool PK, typename Args>
+// TRACE = true: the same sweep that also stores every chain's tracked energy once per sweep (a.trace).
+// A template parameter and not a branch: the kernels use every scalar register they can get, and the
+// untraced instantiations stay instruction for instruction what they were.
+template <int M, int LAYOUT, int TEAMS, bool PK, bool TRACE, typename Args>
 __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_t wg) {
   constexpr bool WIDE = LAYOUT == kWide;
   constexpr int MT = M * TEAMS;  // chains of a group
@@ -1619,6 +1633,10 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
         book[CH + tid] = e;
         atomicOr(improved_flag + (tid >> 5), 1u << (tid & 31u));
       }
+      if constexpr (TRACE) {  // one 8-byte store per chain and sweep, by the lane that owns book[tid]
+        const uint64_t at = first_chain + tid;
+        if (at < a.trace_chains) a.trace[at * a.trace_stride + t + 1u] = e;
+      }
     }
     __syncthreads();
     const uint64_t improved = static_cast<uint64_t>(improved_flag[0]) | (static_cast<uint64_t>(improved_flag[1]) << 32);
@@ -1658,11 +1676,16 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
   }
 }
 
-using ShuffledKernel = void (*)(ShuffledArgs);
+template <bool TRACE>
+using ShuffledArgsOf = std::conditional_t<TRACE, ShuffledTraceArgs, ShuffledArgs>;
+template <bool TRACE>
+using ShuffledKernelOf = void (*)(ShuffledArgsOf<TRACE>);
+using ShuffledKernel = ShuffledKernelOf<false>;
+using ShuffledTraceKernel = ShuffledKernelOf<true>;
 
-template <int M, int LAYOUT, int TEAMS, bool PK = false>
-__global__ __launch_bounds__(512) void k_sa_sweep_shuffled(ShuffledArgs a) {
-  shuffled_sweep_body<M, LAYOUT, TEAMS, PK>(a, blockIdx.x);
+template <int M, int LAYOUT, int TEAMS, bool PK = false, bool TRACE = false>
+__global__ __launch_bounds__(512) void k_sa_sweep_shuffled(ShuffledArgsOf<TRACE> a) {
+  shuffled_sweep_body<M, LAYOUT, TEAMS, PK, TRACE>(a, blockIdx.x);
 }
 
 // Many problems in one launch: workgroup -> (problem, workgroup of the problem) through a slot
@@ -1678,61 +1701,70 @@ __global__ __launch_bounds__(512) void k_sa_sweep_shuffled_batch(const ShuffledA
   if (slot.problem == 0xFFFFFFFFu) return;  // (padding of the XCD-aware slot table)
   ConstArgs *a = reinterpret_cast<ConstArgs *>(
       reinterpret_cast<uintptr_t>(problems + __builtin_amdgcn_readfirstlane(slot.problem)));
-  shuffled_sweep_body<M, LAYOUT, 1, PK>(*a, __builtin_amdgcn_readfirstlane(slot.group));
+  shuffled_sweep_body<M, LAYOUT, 1, PK, false>(*a, __builtin_amdgcn_readfirstlane(slot.group));
 }
 
 // m = chains per group; teams = 2: two teams of m / 2 chains (wide: m = 4 or 2; bytes: m = 8 or 4);
 // packed_lanes: blocks of fewer than 64 spins, several groups per wavefront (wide layout, one team)
-ShuffledKernel shuffled_kernel_for(int m, int layout, int teams = 1, bool packed_lanes = false) {
+template <bool TRACE>
+ShuffledKernelOf<TRACE> shuffled_kernel_of(int m, int layout, int teams, bool packed_lanes) {
   if (packed_lanes) {
     if (layout != kWide || teams != 1) return nullptr;
     switch (m) {
-      case 1: return k_sa_sweep_shuffled<1, kWide, 1, true>;
-      case 2: return k_sa_sweep_shuffled<2, kWide, 1, true>;
-      case 4: return k_sa_sweep_shuffled<4, kWide, 1, true>;
+      case 1: return k_sa_sweep_shuffled<1, kWide, 1, true, TRACE>;
+      case 2: return k_sa_sweep_shuffled<2, kWide, 1, true, TRACE>;
+      case 4: return k_sa_sweep_shuffled<4, kWide, 1, true, TRACE>;
       default: return nullptr;
     }
   }
   if (teams == 2) {
     if (layout == kWide) {
       switch (m) {
-        case 2: return k_sa_sweep_shuffled<1, kWide, 2>;
-        case 4: return k_sa_sweep_shuffled<2, kWide, 2>;
+        case 2: return k_sa_sweep_shuffled<1, kWide, 2, false, TRACE>;
+        case 4: return k_sa_sweep_shuffled<2, kWide, 2, false, TRACE>;
         default: return nullptr;
       }
     }
     if (layout != kBytes) return nullptr;
     switch (m) {
-      case 4: return k_sa_sweep_shuffled<2, kBytes, 2>;
-      case 8: return k_sa_sweep_shuffled<4, kBytes, 2>;
+      case 4: return k_sa_sweep_shuffled<2, kBytes, 2, false, TRACE>;
+      case 8: return k_sa_sweep_shuffled<4, kBytes, 2, false, TRACE>;
       default: return nullptr;
     }
   }
   if (layout == kWide) {
     switch (m) {
-      case 1: return k_sa_sweep_shuffled<1, kWide, 1>;
-      case 2: return k_sa_sweep_shuffled<2, kWide, 1>;
-      case 4: return k_sa_sweep_shuffled<4, kWide, 1>;
+      case 1: return k_sa_sweep_shuffled<1, kWide, 1, false, TRACE>;
+      case 2: return k_sa_sweep_shuffled<2, kWide, 1, false, TRACE>;
+      case 4: return k_sa_sweep_shuffled<4, kWide, 1, false, TRACE>;
       default: return nullptr;
     }
   }
   if (layout == kNibbles) {
     switch (m) {
-      case 1: return k_sa_sweep_shuffled<1, kNibbles, 1>;
-      case 2: return k_sa_sweep_shuffled<2, kNibbles, 1>;
-      case 4: return k_sa_sweep_shuffled<4, kNibbles, 1>;
+      case 1: return k_sa_sweep_shuffled<1, kNibbles, 1, false, TRACE>;
+      case 2: return k_sa_sweep_shuffled<2, kNibbles, 1, false, TRACE>;
+      case 4: return k_sa_sweep_shuffled<4, kNibbles, 1, false, TRACE>;
       default: return nullptr;
     }
   }
-  if (layout == kBits) return m == 1 ? k_sa_sweep_shuffled<1, kBits, 1> : nullptr;
-  if (layout == kGlobal) return m == 1 ? k_sa_sweep_shuffled<1, kGlobal, 1> : nullptr;
+  if (layout == kBits) return m == 1 ? k_sa_sweep_shuffled<1, kBits, 1, false, TRACE> : nullptr;
+  if (layout == kGlobal) return m == 1 ? k_sa_sweep_shuffled<1, kGlobal, 1, false, TRACE> : nullptr;
   switch (m) {
-    case 1: return k_sa_sweep_shuffled<1, kBytes, 1>;
-    case 2: return k_sa_sweep_shuffled<2, kBytes, 1>;
-    case 4: return k_sa_sweep_shuffled<4, kBytes, 1>;
-    case 8: return k_sa_sweep_shuffled<8, kBytes, 1>;
+    case 1: return k_sa_sweep_shuffled<1, kBytes, 1, false, TRACE>;
+    case 2: return k_sa_sweep_shuffled<2, kBytes, 1, false, TRACE>;
+    case 4: return k_sa_sweep_shuffled<4, kBytes, 1, false, TRACE>;
+    case 8: return k_sa_sweep_shuffled<8, kBytes, 1, false, TRACE>;
     default: return nullptr;
   }
+}
+ShuffledKernel shuffled_kernel_for(int m, int layout, int teams = 1, bool packed_lanes = false) {
+  return shuffled_kernel_of<false>(m, layout, teams, packed_lanes);
+}
+// The instantiation that also writes ShuffledTraceArgs::trace — the same forms, one for one, so that a
+// traced call runs the layout, chains per group, packing and teams of the untraced one.
+ShuffledTraceKernel shuffled_trace_kernel_for(int m, int layout, int teams, bool packed_lanes) {
+  return shuffled_kernel_of<true>(m, layout, teams, packed_lanes);
 }
 
 // spins (of `groups` groups: lane packing) | delta[CH] book[3 CH] | flags (16 B) | meta[block_cap] |
@@ -1853,6 +1885,7 @@ struct ShuffledRun {
   const uint64_t *x0 = nullptr;
   uint64_t *out_x = nullptr;
   double *out_e = nullptr;
+  int64_t *out_trace = nullptr;  // HOST [repetitions][num_sweeps + 1] or nullptr (asp_sa_anneal_shuffled_trace)
   uint64_t budget = 3ull << 30;  // bytes of visiting orders per buffer set
 
   uint64_t K = 0;
@@ -1923,6 +1956,7 @@ struct ShuffledRun {
     p->last_sweep_ms = p->last_total_ms = p->last_order_ms = 0.0f;
     if (K == 0) {
       for (uint32_t r = 0; r < repetitions; ++r) out_e[r] = 0.0;  // (host pointers: nothing ran)
+      if (out_trace) std::fill_n(out_trace, trace_elems(), int64_t{0});  // (no spins: the energy stays 0)
       trivial = true;
       return ASP_OK;
     }
@@ -2037,6 +2071,13 @@ struct ShuffledRun {
     // (the run's own order streams and events: made by enqueue(), which the batched driver — with
     // its shared streams — never calls; 128 problems x (2 streams, 6 events) were 0.1 s of a batch)
     hipStream_t s = p->stream;
+    if (out_trace) {
+      // Rows of the real chains only, zeroed once: entry 0 of a row is never written by a kernel and
+      // every other entry by every attempt.  (First of the allocations: a trace that does not fit
+      // fails the call before anything is queued.)
+      ASP_TRY(p->w_trace.ensure(trace_elems()));
+      ASP_HIP_TRY(hipMemsetAsync(p->w_trace.ptr, 0, trace_elems() * sizeof(long long), s));
+    }
     ASP_TRY(d_betas.alloc(num_sweeps));
     // (a byte per spin and group between chunks — or, beyond every LDS layout, the chains' spin words)
     const bool spins_in_hbm = shuffled_layout_for(K, m, level_cap, words + level_cap, p->max_lds) == kGlobal;
@@ -2056,6 +2097,8 @@ struct ShuffledRun {
     }
     return ASP_OK;
   }
+
+  uint64_t trace_elems() const { return static_cast<uint64_t>(repetitions) * (static_cast<uint64_t>(num_sweeps) + 1); }
 
   // ---- one attempt: plan (capacities -> kernels, buffers, argument templates), then launches ----
   uint32_t block_cap = 0, stream_kib = 0, chunk = 0;
@@ -2089,6 +2132,7 @@ struct ShuffledRun {
     return w;
   }
   ShuffledKernel kernel = nullptr;
+  ShuffledTraceKernel trace_kernel = nullptr;  // the traced instantiation of `kernel` (out_trace)
   int nsets = 1, nlanes = 1;
   OrderArgs oa{};
   ShuffledArgs sa{};
@@ -2287,8 +2331,11 @@ struct ShuffledRun {
       teams = 1;
       kernel = shuffled_kernel_for(m, layout, 1, packed_lanes);
     }
+    // (a traced call: the traced instantiation of the form just chosen)
+    trace_kernel = out_trace ? shuffled_trace_kernel_for(m, layout, teams, packed_lanes) : nullptr;
     if (lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+      ASP_HIP_TRY(hipFuncSetAttribute(out_trace ? reinterpret_cast<const void *>(trace_kernel)
+                                                : reinterpret_cast<const void *>(kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     }
     if (order_lds > 64 * 1024) {
@@ -2346,7 +2393,16 @@ struct ShuffledRun {
 
         ASP_HIP_TRY(hipStreamWaitEvent(s, ordered[which], 0));
       }
-      hipLaunchKernelGGL(kernel, dim3(wgs), dim3(waves * teams * 64), lds, s, s_args);
+      if (out_trace) {
+        ShuffledTraceArgs t_args{};
+        static_cast<ShuffledArgs &>(t_args) = s_args;
+        t_args.trace = p->w_trace.ptr;
+        t_args.trace_chains = repetitions;
+        t_args.trace_stride = num_sweeps + 1u;
+        hipLaunchKernelGGL(trace_kernel, dim3(wgs), dim3(waves * teams * 64), lds, s, t_args);
+      } else {
+        hipLaunchKernelGGL(kernel, dim3(wgs), dim3(waves * teams * 64), lds, s, s_args);
+      }
       ASP_HIP_TRY(hipGetLastError());
       ASP_HIP_TRY(hipEventRecord(swept[which], s));
       first_launch = false;
@@ -2424,6 +2480,9 @@ struct ShuffledRun {
                                hipMemcpyDeviceToHost, s));
     ASP_HIP_TRY(hipMemcpyAsync(p->last_accepted.data(), d_accepted.ptr, repetitions * sizeof(uint64_t),
                                hipMemcpyDeviceToHost, s));
+    if (out_trace) {  // one copy at the end: the rows of the call's chains are contiguous
+      ASP_HIP_TRY(hipMemcpyAsync(out_trace, p->w_trace.ptr, trace_elems() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    }
     return ASP_OK;
   }
 
@@ -2870,6 +2929,36 @@ int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uin
 
 }  // namespace asp
 
+namespace {
+
+// One single-problem call, with (asp_sa_anneal_shuffled_trace) or without per-sweep traces.
+int run_shuffled(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_sweeps, uint32_t repetitions,
+                 uint32_t replica_offset, uint64_t const *x0, uint64_t *out_x, double *out_e, int64_t *out_trace) {
+  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
+  ASP_TRY(asp::bind_device());
+  ShuffledRun run;
+  run.p = p;
+  run.seed = seed;
+  run.betas = betas;
+  run.num_sweeps = num_sweeps;
+  run.repetitions = repetitions;
+  run.replica_offset = replica_offset;
+  run.x0 = x0;
+  run.out_x = out_x;
+  run.out_e = out_e;
+  run.out_trace = out_trace;
+  ASP_TRY(run.setup());
+  bool again = true;
+  while (again) {
+    ASP_TRY(run.enqueue());
+    ASP_TRY(run.collect(&again));
+  }
+  ASP_TRY(run.finish_enqueue());
+  return run.finish_wait();
+}
+
+}  // namespace
+
 extern "C" {
 
 int asp_sa_set_shuffled_launch(asp_sa_plan *p, int chains_per_group, int wavefronts) {
@@ -2920,26 +3009,15 @@ int asp_sa_anneal_shuffled(asp_sa_plan *p, uint64_t seed, double const *betas, u
                            uint32_t repetitions, uint32_t replica_offset, uint64_t const *x0,
                            uint64_t *out_x, double *out_e) {
   asp_clear_error();
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  ASP_TRY(asp::bind_device());
-  ShuffledRun run;
-  run.p = p;
-  run.seed = seed;
-  run.betas = betas;
-  run.num_sweeps = num_sweeps;
-  run.repetitions = repetitions;
-  run.replica_offset = replica_offset;
-  run.x0 = x0;
-  run.out_x = out_x;
-  run.out_e = out_e;
-  ASP_TRY(run.setup());
-  bool again = true;
-  while (again) {
-    ASP_TRY(run.enqueue());
-    ASP_TRY(run.collect(&again));
-  }
-  ASP_TRY(run.finish_enqueue());
-  return run.finish_wait();
+  return run_shuffled(p, seed, betas, num_sweeps, repetitions, replica_offset, x0, out_x, out_e, nullptr);
+}
+
+int asp_sa_anneal_shuffled_trace(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_sweeps,
+                                 uint32_t repetitions, uint32_t replica_offset, uint64_t const *x0,
+                                 uint64_t *out_x, double *out_e, int64_t *out_trace) {
+  asp_clear_error();
+  if (!out_trace) return asp::set_error(ASP_ERR_INVALID, "null trace pointer");
+  return run_shuffled(p, seed, betas, num_sweeps, repetitions, replica_offset, x0, out_x, out_e, out_trace);
 }
 
 }  // extern "C"

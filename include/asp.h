@@ -439,6 +439,26 @@ int asp_sa_anneal_trace(asp_sa_plan *p, uint64_t seed, double const *betas, uint
 int asp_sa_anneal_shuffled(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_sweeps,
                            uint32_t repetitions, uint32_t replica_offset, uint64_t const *x0,
                            uint64_t *out_x, double *out_e);
+/* asp_sa_anneal_shuffled that also returns every chain's energy after each sweep: the per-sweep
+ * traces of asp_sa_anneal_trace for the visiting order the Python entry points use by default.
+ * out_trace (HOST, [repetitions][num_sweeps + 1]) has the meaning and units given there:
+ * out_trace[r * (num_sweeps + 1) + t] = tracked energy of chain r of the call (global replica
+ * replica_offset + r) after t sweeps in units of 2^-energy_scale_exp, relative to its initial
+ * configuration (entry 0 is 0); the best-so-far trace is its running minimum, and its last value is
+ * what asp_sa_last_stats reports as the tracked energy.  The value is stored where the sweep kernel
+ * folds the sweep's exact integer energy change into the chain's tracked energy, after the last
+ * level of the sweep: one 8-byte store per chain and sweep, gathered in a device buffer of the plan
+ * and copied out once at the end.  Everything else — out_x, out_e, asp_sa_last_stats,
+ * asp_sa_last_layout (5), asp_sa_last_shuffled* and the kernel form the launcher picks (spin layout,
+ * chains per group, lane packing, teams) — is exactly that of asp_sa_anneal_shuffled with the same
+ * arguments.  out_trace == NULL is ASP_ERR_INVALID, checked before any device work; a trace buffer
+ * that cannot be allocated is ASP_ERR_ALLOC and no output is written.  num_sweeps == 0 writes the
+ * single 0 of every chain, a plan without spins rows of zeros.  The batched launches
+ * (ASP_SA_BATCH_SHUFFLED) have no trace form. */
+int asp_sa_anneal_shuffled_trace(asp_sa_plan *p, uint64_t seed, double const *betas,
+                                 uint32_t num_sweeps, uint32_t repetitions,
+                                 uint32_t replica_offset, uint64_t const *x0, uint64_t *out_x,
+                                 double *out_e, int64_t *out_trace);
 /* Launch geometry of the shuffled sweep (0 = automatic): chains per workgroup in {1,2,4,8} and
  * wavefronts per workgroup in 1..8.  Results never depend on it. */
 int asp_sa_set_shuffled_launch(asp_sa_plan *p, int chains_per_group, int wavefronts);
