@@ -9,3 +9,4 @@ __version__ = "0.4.0"  # = asp_version() of libasp_hip.so
 
 from .common import *  # noqa: F401,F403
 from . import annealer  # noqa: F401
+from .annealer import Chains, anneal_until  # noqa: F401  (resumable chains)

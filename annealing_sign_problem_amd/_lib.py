@@ -83,6 +83,19 @@ class SaGreedyItem(ctypes.Structure):
     ]
 
 
+class SaChainsSnapshot(ctypes.Structure):
+    """Mirror of ``asp_sa_chains_snapshot`` (include/asp.h)."""
+
+    _fields_ = [
+        ("sweeps_done", c_u32),
+        ("x_current", c_void_p),
+        ("x_best", c_void_p),
+        ("tracked_current", c_void_p),
+        ("tracked_best", c_void_p),
+        ("accepted", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/asp.h declares
 SIGNATURES = {
     "asp_last_error": (ctypes.c_char_p, []),
@@ -163,6 +176,12 @@ SIGNATURES = {
     "asp_sa_team_watchdog_trips": (c_int, [c_void_p, ctypes.POINTER(c_u32), ctypes.POINTER(c_u64)]),
     "asp_sa_last_shuffled_blocks": (c_int, [c_void_p, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
     "asp_sa_last_shuffled_fill": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "asp_sa_chains_create": (c_int, [c_void_p, c_u64, c_u32, c_u32, c_void_p, c_u64, ctypes.POINTER(c_void_p)]),
+    "asp_sa_chains_destroy": (None, [c_void_p]),
+    "asp_sa_chains_advance": (c_int, [c_void_p, c_void_p, c_u32, c_u32, c_void_p]),
+    "asp_sa_chains_result": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "asp_sa_chains_export": (c_int, [c_void_p, ctypes.POINTER(SaChainsSnapshot)]),
+    "asp_sa_chains_import": (c_int, [c_void_p, ctypes.POINTER(SaChainsSnapshot)]),
     "asp_sa_anneal_batch": (c_int, [ctypes.POINTER(SaBatchItem), c_u32]),
     "asp_sa_batch_last_ms": (c_float, []),
     "asp_sa_greedy": (c_int, [c_void_p, c_u32, c_void_p, c_void_p, ctypes.POINTER(c_u32)]),

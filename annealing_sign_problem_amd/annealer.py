@@ -35,6 +35,8 @@ __all__ = [
     "anneal",
     "anneal_batch",
     "anneal_traces",
+    "anneal_until",
+    "Chains",
     "greedy_solve",
     "greedy_solve_batch",
     "signs_to_bits",
@@ -449,6 +451,197 @@ def anneal_traces(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: i
     e_best = es[:, None] + (best - floor).astype(np.float64) * unit
     e_current = es[:, None] + (trace - floor).astype(np.float64) * unit
     return xs, es, e_current, e_best
+
+
+class Chains:
+    """Resumable annealing chains of ``hamiltonian`` on the device (``asp_sa_chains``, DESIGN.md
+    §4.10): ``repetitions`` chains that are advanced a segment of sweeps at a time, looked at,
+    checkpointed and continued.  Any split of a schedule into ``advance`` calls gives exactly the
+    chains of the closed call (``anneal_raw`` with the same seed, ``x0`` and ``replica_offset``).
+
+    ``x0``: ``None`` (the random start of ``anneal``), one packed configuration ``[words]`` shared
+    by every chain, or ``[repetitions, words]`` with a start of its own for every chain."""
+
+    _ORDERS = {"colour": 0, "shuffled": 1}
+
+    def __init__(self, hamiltonian: Hamiltonian, seed=None, repetitions: int = 1, x0=None,
+                 replica_offset: int = 0):
+        if not isinstance(hamiltonian, Hamiltonian):
+            raise TypeError("'hamiltonian' must be a Hamiltonian")
+        repetitions = int(repetitions)
+        if repetitions < 1:
+            raise ValueError("'repetitions' must be positive")
+        self._handle = None
+        self.hamiltonian = hamiltonian
+        self.repetitions = repetitions
+        self.replica_offset = int(replica_offset)
+        self.seed = _resolve_seed(seed)
+        self.words = (hamiltonian.size + 63) // 64
+        stride = 0
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.uint64)
+            if x0.ndim == 1:
+                if x0.shape[0] != self.words:
+                    raise ValueError("a shared 'x0' must have {} words".format(self.words))
+            elif x0.ndim == 2:
+                if x0.shape != (repetitions, self.words):
+                    raise ValueError("a per-chain 'x0' must have shape ({}, {})".format(repetitions, self.words))
+                stride = self.words
+                if self.words == 0:
+                    x0 = None
+            else:
+                raise ValueError("'x0' must be a packed configuration [words] or one per chain [repetitions, words]")
+        lib = _lib.load()
+        self._plan = hamiltonian.plan()
+        handle = ctypes.c_void_p()
+        _lib.check(lib.asp_sa_chains_create(self._plan, ctypes.c_uint64(self.seed), ctypes.c_uint32(repetitions),
+                                            ctypes.c_uint32(self.replica_offset), _lib.ptr(x0),
+                                            ctypes.c_uint64(stride), ctypes.byref(handle)))
+        self._handle = handle
+        _lib.track(self)
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("these chains are closed")
+        if self.hamiltonian._plan is None or self.hamiltonian._plan.value != self._plan.value:
+            raise ValueError("the Hamiltonian's device plan was released or rebuilt: these chains are gone with it")
+        return self._handle
+
+    @property
+    def sweeps_done(self) -> int:
+        return int(self._export([])["sweeps_done"])  # (no arrays: the counter only, no device work)
+
+    def advance(self, betas, sweep_order: Optional[str] = None, trace: bool = False):
+        """Run ``len(betas)`` more sweeps, sweep ``k`` at inverse temperature ``betas[k]``.
+        ``sweep_order`` as in ``anneal`` (``None``: ``$ASP_SWEEP_ORDER``, else ``"shuffled"``); it may
+        differ from segment to segment.  ``trace=True`` returns ``int64[R, len(betas) + 1]``: the
+        tracked energy before the segment and after each of its sweeps, in units of
+        ``2**-energy_scale_exp`` relative to the chain's very first configuration; else ``None``."""
+        order = self._ORDERS[resolve_sweep_order(sweep_order)]
+        handle = self._live()
+        betas = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        rows = np.zeros((self.repetitions, betas.shape[0] + 1), dtype=np.int64) if trace else None
+        _lib.check(_lib.load().asp_sa_chains_advance(handle, _lib.ptr(betas), ctypes.c_uint32(betas.shape[0]),
+                                                     ctypes.c_uint32(order), _lib.ptr(rows)))
+        return rows
+
+    def result(self, only_best: bool = False):
+        """The best configuration so far of every chain and its energy, ``(xs[R, words], es[R])`` —
+        what ``anneal(..., only_best=False)`` returns; ``only_best=True``: the best of them."""
+        xs = np.zeros((self.repetitions, max(self.words, 1)), dtype=np.uint64)
+        es = np.zeros(self.repetitions, dtype=np.float64)
+        _lib.check(_lib.load().asp_sa_chains_result(self._live(), _lib.ptr(xs), _lib.ptr(es)))
+        xs = xs[:, :self.words]
+        if only_best:
+            best = int(np.argmin(es))  # first minimum, as anneal()
+            return xs[best].copy(), float(es[best])
+        return xs, es
+
+    def _export(self, names) -> dict:
+        shapes = {"x_current": (self.repetitions, self.words), "x_best": (self.repetitions, self.words),
+                  "tracked_current": (self.repetitions,), "tracked_best": (self.repetitions,),
+                  "accepted": (self.repetitions,)}
+        out = {name: np.zeros(shapes[name], dtype=np.int64 if name.startswith("tracked") else np.uint64)
+               for name in names}
+        snap = _lib.SaChainsSnapshot()
+        for name, array in out.items():
+            if array.size:
+                setattr(snap, name, array.ctypes.data)
+        _lib.check(_lib.load().asp_sa_chains_export(self._live(), ctypes.byref(snap)))
+        out["sweeps_done"] = np.uint32(snap.sweeps_done)
+        return out
+
+    def state(self) -> dict:
+        """Everything a continuation needs, as numpy arrays (``np.savez(path, **chains.state())``):
+        ``x_current`` / ``x_best`` ``uint64[R, words]``, ``tracked_current`` / ``tracked_best``
+        ``int64[R]`` (units of ``2**-energy_scale_exp``, relative to the chain's first
+        configuration), ``accepted`` ``uint64[R]`` and ``sweeps_done``."""
+        return self._export(["x_current", "x_best", "tracked_current", "tracked_best", "accepted"])
+
+    def load_state(self, state) -> None:
+        """Continue from ``state`` (a ``state()`` dict or the ``np.load`` of one) — chains of the same
+        Hamiltonian, seed, repetitions and replica_offset."""
+        shapes = {"x_current": (self.repetitions, self.words), "x_best": (self.repetitions, self.words),
+                  "tracked_current": (self.repetitions,), "tracked_best": (self.repetitions,),
+                  "accepted": (self.repetitions,)}
+        snap = _lib.SaChainsSnapshot()
+        keep = []
+        for name, shape in shapes.items():
+            dtype = np.int64 if name.startswith("tracked") else np.uint64
+            array = np.ascontiguousarray(state[name], dtype=dtype)
+            if array.shape != shape:
+                raise ValueError("state[{!r}] must have shape {}".format(name, shape))
+            if array.size == 0:
+                array = np.zeros(1, dtype=dtype)  # (never read; a snapshot array must not be NULL)
+            keep.append(array)
+            setattr(snap, name, array.ctypes.data)
+        sweeps_done = int(state["sweeps_done"])
+        if not 0 <= sweeps_done < 2**32:
+            raise ValueError("state['sweeps_done'] must fit 32 bits")
+        snap.sweeps_done = sweeps_done
+        _lib.check(_lib.load().asp_sa_chains_import(self._live(), ctypes.byref(snap)))
+
+    def close(self) -> None:
+        """Destroy the device handle now."""
+        if self._handle is not None:
+            try:
+                _lib.load().asp_sa_chains_destroy(self._handle)
+            finally:
+                self._handle = None
+
+    release = close  # (what _lib.shutdown calls on every live owner of a handle)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        if getattr(self, "_handle", None) is None or _lib.closed():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def anneal_until(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: int = 5120,
+                 beta0: Optional[float] = None, beta1: Optional[float] = None, repetitions: int = 1,
+                 only_best: bool = True, sweep_order: Optional[str] = None, check_every: int = 512,
+                 patience: Optional[int] = None):
+    """``anneal`` that may stop early: the usual geometric ladder of ``number_sweeps`` sweeps is run
+    in segments of ``check_every`` sweeps (``Chains``), and the run ends once NO chain's best energy
+    has improved for ``patience`` consecutive segments.  Returns ``(x, e, sweeps_run)`` with
+    ``(x, e)`` as ``anneal`` returns them.  ``patience=None`` never stops early and returns exactly
+    ``anneal(...)``'s result (the continuation law).  Chains stay on this rank."""
+    order = resolve_sweep_order(sweep_order)  # (first: a bad order fails without a GPU)
+    check_every = int(check_every)
+    if check_every < 1:
+        raise ValueError("'check_every' must be positive")
+    if patience is not None and int(patience) < 1:
+        raise ValueError("'patience' must be positive or None")
+    if not isinstance(hamiltonian, Hamiltonian):
+        raise TypeError("'hamiltonian' must be a Hamiltonian")
+    if beta0 is None or beta1 is None:
+        info = hamiltonian.info()
+        beta0 = info.beta0_auto if beta0 is None else beta0
+        beta1 = info.beta1_auto if beta1 is None else beta1
+    betas = make_schedule(float(beta0), float(beta1), number_sweeps)
+    with Chains(hamiltonian, seed=seed, repetitions=repetitions, x0=x0) as chains:
+        best = chains._export(["tracked_best"])["tracked_best"]
+        still = 0
+        done = 0
+        while done < betas.shape[0]:
+            chains.advance(betas[done:done + check_every], sweep_order=order)
+            done = min(done + check_every, betas.shape[0])
+            now = chains._export(["tracked_best"])["tracked_best"]
+            still = 0 if np.any(now < best) else still + 1
+            best = now
+            if patience is not None and still >= int(patience):
+                break
+        x, e = chains.result(only_best=only_best)
+    return x, e, done
 
 
 def anneal_with_traces(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: int = 5120,

@@ -37,6 +37,7 @@ SOURCES = [
     "greedy.cpp",
     "sa_sweep.hip",
     "sa_shuffled.hip",
+    "sa_chains.hip",
 ]
 
 # -ffp-contract=off: the parity contract needs every multiply/add rounded on its

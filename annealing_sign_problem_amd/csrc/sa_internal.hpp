@@ -36,6 +36,8 @@ struct asp_sa_plan {
   asp::DeviceBuffer<double> w_field_cache;  // [groups][blocks][M][64], see SweepArgs::field_cache
   asp::DeviceBuffer<uint64_t> w_spins;      // [groups][blocks] sign words of the HBM-resident layout
   asp::DeviceBuffer<long long> w_trace;     // [groups * M][sweeps + 1] tracked energies (asp_sa_anneal_trace)
+  asp::DeviceBuffer<uint64_t> w_cur_perm;   // [groups * M][blocks] sign words of a handle's chains (Resume::cur_perm)
+  asp::DeviceBuffer<long long> w_e_cur;     // [groups * M] their current tracked energies (Resume::e_cur)
   // team sweep exchange area, FINE-GRAINED device memory (coherent across XCDs without cache
   // maintenance): arrivals u64[teams] | sums i64[teams][6] | abort u32 (+pad) | flips u64[teams][blocks]
   void *team_area = nullptr;
@@ -65,6 +67,20 @@ struct asp_sa_plan {
 };
 
 
+// The chains behind asp_sa_chains_create: everything a continuation needs, on the
+// device and independent of the sweep order and of every launch choice — configurations packed in
+// ORIGINAL spin order (bit = +1) and three integers per chain.  Sized once, at create.
+struct asp_sa_chains {
+  asp_sa_plan *plan = nullptr;
+  uint64_t seed = 0;
+  uint32_t repetitions = 0, replica_offset = 0, words = 0;
+  uint32_t sweeps_done = 0;
+  asp::DeviceBuffer<uint64_t> x_cur, x_best;        // [repetitions][words]
+  asp::DeviceBuffer<long long> e_cur, e_best;       // [repetitions] tracked energies (fixed point)
+  asp::DeviceBuffer<unsigned long long> accepted;   // [repetitions]
+  std::vector<int64_t> h_e_cur;                     // host copy of e_cur (entry 0 of a segment's trace)
+};
+
 namespace asp {
 
 template <typename T>
@@ -85,5 +101,12 @@ int sa_energies_of_perm(asp_sa_plan *p, const uint64_t *perm, uint32_t count, do
 // asp_sa_anneal_batch's items with ASP_SA_BATCH_SHUFFLED set (csrc/sa_shuffled.hip): items[which[k]],
 // k < count; adds the device time of their sweeps to *sweep_ms.
 int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uint32_t count, float *sweep_ms);
+
+// One segment of asp_sa_chains_advance (arguments validated, num_sweeps > 0, a plan with spins):
+// sweeps c->sweeps_done .. + num_sweeps - 1 from and into the handle's state; c->sweeps_done is the
+// caller's to advance.  trace: nullptr or HOST [repetitions][num_sweeps + 1], entries 1.. written here.
+// Colour order (csrc/sa_sweep.hip) and shuffled order (csrc/sa_shuffled.hip).
+int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace);
+int sa_chains_advance_shuffled(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace);
 
 }  // namespace asp

@@ -1704,6 +1704,58 @@ __global__ __launch_bounds__(512) void k_sa_sweep_shuffled_batch(const ShuffledA
   shuffled_sweep_body<M, LAYOUT, 1, PK, false>(*a, __builtin_amdgcn_readfirstlane(slot.group));
 }
 
+// The chains of an asp_sa_chains handle into and out of the form the sweep kernels
+// carry a chain in between two chunks: ShuffledArgs::state, [groups][K] with bit j of entry i = spin i
+// of chain g * m + j is -1 — a byte per spin, or kGlobal's 32-bit word (T).  The handle keeps every
+// chain packed in original order (bit = +1), whatever m and layout the launcher picks per segment.
+// in: a workgroup column per group, threads over the spins; the chains padding the last group start
+// with every spin up.
+template <typename T>
+__global__ __launch_bounds__(256) void k_chains_state_in(const uint64_t *__restrict__ x, uint32_t words,
+                                                        uint32_t num_spins, uint32_t chains, uint32_t m,
+                                                        T *__restrict__ state) {
+  const uint32_t g = blockIdx.x;
+  for (uint32_t i = blockIdx.y * blockDim.x + threadIdx.x; i < num_spins; i += gridDim.y * blockDim.x) {
+    uint32_t mask = 0;
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint64_t r = static_cast<uint64_t>(g) * m + j;
+      if (r >= chains) break;
+      mask |= (static_cast<uint32_t>((x[r * words + (i >> 6)] >> (i & 63u)) & 1ull) ^ 1u) << j;
+    }
+    state[static_cast<uint64_t>(g) * num_spins + i] = static_cast<T>(mask);
+  }
+}
+// out: a wavefront per word of a chain (lane j owns spin 64 w + j), the word is one ballot.
+template <typename T>
+__global__ __launch_bounds__(256) void k_chains_state_out(const T *__restrict__ state, uint32_t num_spins,
+                                                         uint32_t words, uint32_t m, uint64_t *__restrict__ x) {
+  const uint32_t r = blockIdx.x, lane = threadIdx.x & 63u;
+  const T *state_g = state + static_cast<uint64_t>(r / m) * num_spins;
+  for (uint32_t w = blockIdx.y * (blockDim.x >> 6) + (threadIdx.x >> 6); w < words; w += gridDim.y * (blockDim.x >> 6)) {
+    const uint32_t i = w * 64u + lane;  // (w is uniform over the wavefront)
+    bool up = false;
+    if (i < num_spins) up = ((static_cast<uint32_t>(state_g[i]) >> (r % m)) & 1u) == 0u;
+    const uint64_t word = __ballot(up);
+    if (lane == 0) x[static_cast<uint64_t>(r) * words + w] = word;
+  }
+}
+
+// The value p - 8 t0, for the segments of a handle.  The sweep kernels index the call's betas and trace
+// rows with the GLOBAL sweep index t (the one of the random words): a.betas[t], a.trace[.. + t + 1].  In
+// a closed call t starts at 0; in a segment it starts at t0, so the kernel is handed a base that lies
+// 8 t0 bytes BEFORE the segment's array (up to 32 GiB before it) and its own "+ 8 t" lands inside the
+// array again: every address that is dereferenced belongs to the array.  The base itself does not —
+// it is formed here with unsigned integer arithmetic, but the kernel's indexing from it is pointer
+// arithmetic from outside the object, which the language does not define; it holds on this target
+// because a global address is a flat 64-bit integer and the add wraps.  The price of leaving every
+// existing sweep kernel instruction for instruction what it was; a sweep-index base of its own in
+// ShuffledArgs is the clean form, for a change that re-measures those kernels.
+template <typename T>
+T *rebased(T *p, uint32_t t0) {
+  static_assert(sizeof(T) == 8, "arrays of 8-byte entries");
+  return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) - 8ull * t0);
+}
+
 // m = chains per group; teams = 2: two teams of m / 2 chains (wide: m = 4 or 2; bytes: m = 8 or 4);
 // packed_lanes: blocks of fewer than 64 spins, several groups per wavefront (wide layout, one team)
 template <bool TRACE>
@@ -1887,6 +1939,12 @@ struct ShuffledRun {
   double *out_e = nullptr;
   int64_t *out_trace = nullptr;  // HOST [repetitions][num_sweeps + 1] or nullptr (asp_sa_anneal_shuffled_trace)
   uint64_t budget = 3ull << 30;  // bytes of visiting orders per buffer set
+  // A segment of a handle (asp_sa_chains_advance, order 1) instead of a closed call: the chains start
+  // from and end in `resume`'s state, sweep k of the call is global sweep t0 + k — in the order build
+  // (OrderArgs::first_sweep) and in the sweep kernel (ShuffledArgs::first_sweep: random words; betas
+  // and trace through rebased()) —, no launch initialises, and nothing is reported but the state.
+  asp_sa_chains *resume = nullptr;
+  uint32_t t0 = 0;
 
   uint64_t K = 0;
   uint32_t words = 0, groups = 0, waves = 1, level_cap = 0, quad_cap = 0, order_threads = 64, lanes_per_row = 1;
@@ -1942,7 +2000,7 @@ struct ShuffledRun {
       trivial = true;
       return ASP_OK;
     }
-    if (!out_x || !out_e || (num_sweeps && !betas)) return asp::set_error(ASP_ERR_INVALID, "null argument");
+    if ((!resume && (!out_x || !out_e)) || (num_sweeps && !betas)) return asp::set_error(ASP_ERR_INVALID, "null argument");
     if (num_sweeps >= 0xFFFFFFFEu) return asp::set_error(ASP_ERR_INVALID, "num_sweeps too large");
     if (static_cast<uint64_t>(replica_offset) + repetitions + 8 > 0xFFFFFFFFull) {
       return asp::set_error(ASP_ERR_INVALID, "replica ids exceed 32 bits");
@@ -2261,7 +2319,7 @@ struct ShuffledRun {
     ASP_TRY(d_state.ensure(static_cast<uint64_t>(groups) * K * (layout == kGlobal ? 4 : 1)));
     sa = ShuffledArgs{};
     sa.status = d_status.ptr;
-    sa.betas = d_betas.ptr;
+    sa.betas = rebased(d_betas.ptr, t0);
     sa.x0 = x0 ? d_x0.ptr : nullptr;
     sa.state = d_state.ptr;
     sa.best = d_best.ptr;
@@ -2295,7 +2353,7 @@ struct ShuffledRun {
     x.peel_ctl = d_peel_ctl[lane].ptr;
     x.level_start_g = d_level_start[lane].ptr;
     x.later = d_later[lane].ptr;
-    x.first_sweep = done;
+    x.first_sweep = t0 + done;
     x.count = now;
     x.level_block = o.level_block.ptr;
     x.num_levels = o.num_levels.ptr;
@@ -2308,9 +2366,9 @@ struct ShuffledRun {
     y.num_levels = o.num_levels.ptr;
     y.block_meta = o.block_meta.ptr;
     y.stream = o.stream.ptr;
-    y.first_sweep = done;
+    y.first_sweep = t0 + done;
     y.chunk_sweeps = now;
-    y.initialise = first_launch ? 1u : 0u;
+    y.initialise = first_launch && !resume ? 1u : 0u;
     *s_out = y;
   }
 
@@ -2368,6 +2426,7 @@ struct ShuffledRun {
     for (int i = 0; i < nlanes; ++i) {
       ASP_HIP_TRY(hipStreamWaitEvent(order_stream[i].stream, p->ev[0], 0));  // status zeroed, buffers ours
     }
+    if (resume) ASP_TRY(load_resume());
     bool first_launch = true;
     uint32_t turn = 0;
     for (uint32_t done = 0; done < num_sweeps || first_launch; done += chunk, ++turn) {
@@ -2396,7 +2455,7 @@ struct ShuffledRun {
       if (out_trace) {
         ShuffledTraceArgs t_args{};
         static_cast<ShuffledArgs &>(t_args) = s_args;
-        t_args.trace = p->w_trace.ptr;
+        t_args.trace = rebased(p->w_trace.ptr, t0);
         t_args.trace_chains = repetitions;
         t_args.trace_stride = num_sweeps + 1u;
         hipLaunchKernelGGL(trace_kernel, dim3(wgs), dim3(waves * teams * 64), lds, s, t_args);
@@ -2441,11 +2500,65 @@ struct ShuffledRun {
     return ASP_OK;
   }
 
+  // The handle's chains into the attempt's buffers, in the form of a chain between two chunks (queued
+  // on the plan's stream ahead of the first sweep launch; every attempt reloads them).
+  int load_resume() {
+    hipStream_t s = p->stream;
+    const uint64_t R = repetitions;
+    if (padded > R) {  // (the chains padding the last group: integers 0; never read back)
+      ASP_HIP_TRY(hipMemsetAsync(d_ecur.ptr + R, 0, (padded - R) * 8, s));
+      ASP_HIP_TRY(hipMemsetAsync(d_ebest.ptr + R, 0, (padded - R) * 8, s));
+      ASP_HIP_TRY(hipMemsetAsync(d_accepted.ptr + R, 0, (padded - R) * 8, s));
+    }
+    ASP_HIP_TRY(hipMemcpyAsync(d_ecur.ptr, resume->e_cur.ptr, R * 8, hipMemcpyDeviceToDevice, s));
+    ASP_HIP_TRY(hipMemcpyAsync(d_ebest.ptr, resume->e_best.ptr, R * 8, hipMemcpyDeviceToDevice, s));
+    ASP_HIP_TRY(hipMemcpyAsync(d_accepted.ptr, resume->accepted.ptr, R * 8, hipMemcpyDeviceToDevice, s));
+    ASP_HIP_TRY(hipMemcpyAsync(d_best.ptr, resume->x_best.ptr, R * words * 8, hipMemcpyDeviceToDevice, s));
+    const dim3 grid(groups, static_cast<uint32_t>(std::min<uint64_t>((K + 255) / 256, 1024)));
+    if (layout == kGlobal) {
+      hipLaunchKernelGGL(k_chains_state_in<uint32_t>, grid, dim3(256), 0, s, resume->x_cur.ptr, words,
+                         static_cast<uint32_t>(K), repetitions, static_cast<uint32_t>(m),
+                         reinterpret_cast<uint32_t *>(d_state.ptr));
+    } else {
+      hipLaunchKernelGGL(k_chains_state_in<uint8_t>, grid, dim3(256), 0, s, resume->x_cur.ptr, words,
+                         static_cast<uint32_t>(K), repetitions, static_cast<uint32_t>(m), d_state.ptr);
+    }
+    ASP_HIP_TRY(hipGetLastError());
+    return ASP_OK;
+  }
+
+  // The end of a segment: the chains back into the handle (queued).
+  int finish_resume() {
+    hipStream_t s = p->stream;
+    const uint64_t R = repetitions;
+    const dim3 grid(repetitions, std::min(words / 4u + 1u, 1024u));
+    if (layout == kGlobal) {
+      hipLaunchKernelGGL(k_chains_state_out<uint32_t>, grid, dim3(256), 0, s,
+                         reinterpret_cast<const uint32_t *>(d_state.ptr), static_cast<uint32_t>(K), words,
+                         static_cast<uint32_t>(m), resume->x_cur.ptr);
+    } else {
+      hipLaunchKernelGGL(k_chains_state_out<uint8_t>, grid, dim3(256), 0, s, d_state.ptr,
+                         static_cast<uint32_t>(K), words, static_cast<uint32_t>(m), resume->x_cur.ptr);
+    }
+    ASP_HIP_TRY(hipGetLastError());
+    ASP_HIP_TRY(hipMemcpyAsync(resume->x_best.ptr, d_best.ptr, R * words * 8, hipMemcpyDeviceToDevice, s));
+    ASP_HIP_TRY(hipMemcpyAsync(resume->e_cur.ptr, d_ecur.ptr, R * 8, hipMemcpyDeviceToDevice, s));
+    ASP_HIP_TRY(hipMemcpyAsync(resume->e_best.ptr, d_ebest.ptr, R * 8, hipMemcpyDeviceToDevice, s));
+    ASP_HIP_TRY(hipMemcpyAsync(resume->accepted.ptr, d_accepted.ptr, R * 8, hipMemcpyDeviceToDevice, s));
+    ASP_HIP_TRY(hipEventRecord(p->ev[3], s));
+    ASP_HIP_TRY(hipMemcpyAsync(resume->h_e_cur.data(), d_ecur.ptr, R * 8, hipMemcpyDeviceToHost, s));
+    if (out_trace) {
+      ASP_HIP_TRY(hipMemcpyAsync(out_trace, p->w_trace.ptr, trace_elems() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    }
+    return ASP_OK;
+  }
+
   // Energies of §4.6 from the packed best configurations and the copies to the caller (queued).
   int finish_enqueue() {
     if (trivial) return ASP_OK;
     hipStream_t s = p->stream;
     p->last_shuffled_levels = static_cast<int>(status[kStatLevels]);
+    if (resume) return finish_resume();
 #if ASP_SHUF_TIMING
     {
       unsigned long long host_ticks[kTimingSlots * kTimingWaves + kOrderTimingSlots];
@@ -2958,6 +3071,34 @@ int run_shuffled(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t nu
 }
 
 }  // namespace
+
+namespace asp {
+
+// One segment of a handle in the shuffled order: a ShuffledRun in its resume form — the launcher's
+// every choice (chains per group, spin layout, lane packing, teams of a workgroup, chunk size, the
+// retry with larger capacities) is the closed call's.
+int sa_chains_advance_shuffled(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace) {
+  ShuffledRun run;
+  run.p = c->plan;
+  run.seed = c->seed;
+  run.betas = betas;
+  run.num_sweeps = num_sweeps;
+  run.repetitions = c->repetitions;
+  run.replica_offset = c->replica_offset;
+  run.out_trace = trace;
+  run.resume = c;
+  run.t0 = c->sweeps_done;
+  ASP_TRY(run.setup());
+  bool again = true;
+  while (again) {
+    ASP_TRY(run.enqueue());
+    ASP_TRY(run.collect(&again));
+  }
+  ASP_TRY(run.finish_enqueue());
+  return run.finish_wait();
+}
+
+}  // namespace asp
 
 extern "C" {
 

@@ -384,15 +384,35 @@ struct StopWhenStill {
   uint32_t *sweeps_done;  // this problem's word
 };
 
+// How a launch starts and ends.  NoResume: the closed calls — a fresh chain (one shared x0 or the
+// counter RNG, tracked energy 0, sweep index 0) whose final state is dropped.  Resume: one segment of
+// an asp_sa_chains handle — every chain starts from its OWN sign words, the
+// tracked energy, the best threshold and the flip count start from carried values (a.tracked and
+// a.accepted are read before they are written), sweep t of the launch draws with sweep index t0 + t,
+// and the final configuration and tracked energy are stored beside the best ones.  All of it at the
+// head and the tail of the launch; a template parameter, so the closed calls' instantiations stay
+// what they were.
+struct NoResume {
+  static constexpr bool kEnabled = false;
+};
+struct Resume {
+  static constexpr bool kEnabled = true;
+  uint64_t *cur_perm;  // [groups * M][num_blocks] sign-bit words: start of every chain in, final state out
+  long long *e_cur;    // [groups * M] current tracked energy, in and out
+  uint32_t t0;         // sweeps the chains have behind them
+};
+
 // DESCENT = true: strict-descent sweeps (accept iff dE < 0, no random numbers, no beta: a.betas is
 // never read), used by the greedy solver's relaxation; the final configuration is snapshotted
 // after every sweep.
 // The whole anneal of one group of M replicas by one workgroup; `group` = index of the group
 // inside its problem (k_sa_sweep: the workgroup id; k_sa_sweep_batch: looked up in a table).
-template <int M, bool DESCENT, int LAYOUT, typename Args, typename Stop = NoEarlyStop>
+template <int M, bool DESCENT, int LAYOUT, typename Args, typename Stop = NoEarlyStop,
+          typename Res = NoResume>
 __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t group,
-                                              const Stop stop = Stop{}) {
+                                              const Stop stop = Stop{}, const Res res = Res{}) {
   static_assert(DESCENT || !Stop::kEnabled, "only a descent can stop early");
+  static_assert(!DESCENT || !Res::kEnabled, "a descent is never resumed");
   constexpr bool GLOBAL = LAYOUT == kGlobal;
   constexpr bool PACKED = LAYOUT == kBits || GLOBAL;  // one bit per position
   constexpr bool WIDE = LAYOUT == kWide;
@@ -444,7 +464,16 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     const uint32_t p = b0 * 64u + (tid & 63u);
     const uint32_t spin = a.spin_of_pos[p];
     uint32_t byte = 0;
-    if (spin != kDummySpin) {
+    if constexpr (Res::kEnabled) {
+      // every chain's own words (a padding lane's bit is whatever the words hold: never read back)
+      if (spin != kDummySpin) {
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+          const uint64_t word = res.cur_perm[(static_cast<uint64_t>(group) * M + m) * a.num_blocks + b0];
+          byte |= static_cast<uint32_t>((word >> (tid & 63u)) & 1ull) << replica_bit<M, LAYOUT>(m);
+        }
+      }
+    } else if (spin != kDummySpin) {
       if (a.x0_perm != nullptr) {
         byte = ((a.x0_perm[p >> 6] >> (p & 63u)) & 1ull) ? encode_replicas<M, LAYOUT>((1u << M) - 1u)
                                                          : 0u;  // every replica
@@ -480,25 +509,50 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
       meta[b] = make_uint2(static_cast<uint32_t>(a.ell_off[b]), a.block_width[b]);
     }
   }
-  if (tid < 32) delta[tid] = 0;  // delta[8] + book[24]
+  if constexpr (Res::kEnabled) {
+    // delta[8] | book[24]: every entry is written once, by one lane — 0, or for book[] of a live
+    // chain the carried value (current tracked energy, best, accepted flips)
+    if (tid < 32) {
+      const uint32_t which = tid >> 3, m = tid & 7u;
+      long long v = 0;
+      if (which >= 1u && m < static_cast<uint32_t>(M)) {
+        const uint64_t chain = static_cast<uint64_t>(group) * M + m;
+        v = which == 1u ? res.e_cur[chain]
+                        : (which == 2u ? a.tracked[chain] : static_cast<long long>(a.accepted[chain]));
+      }
+      delta[tid] = v;
+    }
+  } else {
+    if (tid < 32) delta[tid] = 0;  // delta[8] + book[24]
+  }
   if (tid == 0) {
     *improved_flag = 0;
     cache_ctl[0] = 0;
     cache_ctl[1] = 0;
     cache_ctl[2] = 0;
   }
-  __syncthreads();
-  snapshot<M, LAYOUT>(spins, a, group, (1u << M) - 1u);
-  __syncthreads();
+  if constexpr (Res::kEnabled) {
+    // (the best configuration so far is in a.best_perm already and stays unless the segment
+    // improves on it: no initial snapshot)
+    __syncthreads();
+  } else {
+    __syncthreads();
+    snapshot<M, LAYOUT>(spins, a, group, (1u << M) - 1u);
+    __syncthreads();
+  }
 
   if (a.trace != nullptr && tid < M) {
-    a.trace[(static_cast<uint64_t>(group) * M + tid) * (a.num_sweeps + 1ull)] = 0;
+    long long start = 0;
+    if constexpr (Res::kEnabled) start = book[tid];  // (not reset: relative to the chain's very first state)
+    a.trace[(static_cast<uint64_t>(group) * M + tid) * (a.num_sweeps + 1ull)] = start;
   }
   double mult[4] = {1.0, 1.0, 1.0, 1.0};  // kWide's multipliers (low words stay 0)
   // StopWhenStill: sweeps performed, and the chain's accepted flips before the running sweep
   [[maybe_unused]] uint32_t sweeps_done = a.num_sweeps;
   [[maybe_unused]] long long flips_before = 0;
   for (uint32_t t = 0; t < a.num_sweeps; ++t) {
+    uint32_t t_draw = t;  // the sweep index of the random words: global over the segments of a handle
+    if constexpr (Res::kEnabled) t_draw += res.t0;
     double beta;
     if constexpr (DESCENT) {
       beta = 0.0;  // unused by the descent rule: a certain rejection there is dE >= 0 at any beta
@@ -634,7 +688,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
             const uint32_t r = r0 + m;
             if (m == 0 || (r >> 2) != have) {
               have = r >> 2;
-              rnd = philox4x32_10(spin, t, have, 0u, key0, key1);
+              rnd = philox4x32_10(spin, t_draw, have, 0u, key0, key1);
             }
             const uint32_t word = pick_word(rnd, r & 3u);
             const bool accept =
@@ -772,11 +826,24 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
   if constexpr (DESCENT && Stop::kEnabled) {
     if (tid == 0) *stop.sweeps_done = sweeps_done;
   }
+  if constexpr (Res::kEnabled) {
+    // the state the next segment starts from (the spins were last written before the final barriers)
+    if (tid < M) res.e_cur[static_cast<uint64_t>(group) * M + tid] = book[tid];
+    SweepArgs fin = a;
+    fin.best_perm = res.cur_perm;
+    snapshot<M, LAYOUT>(spins, fin, group, (1u << M) - 1u);
+  }
 }
 
 template <int M, bool DESCENT, int LAYOUT>
 __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep(SweepArgs a) {
   sa_sweep_body<M, DESCENT, LAYOUT>(a, blockIdx.x);
+}
+
+// One segment of an asp_sa_chains handle in the colour order (asp_sa_chains_advance, order 0).
+template <int M, int LAYOUT>
+__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_resume(SweepArgs a, Resume r) {
+  sa_sweep_body<M, false, LAYOUT, SweepArgs, NoEarlyStop, Resume>(a, blockIdx.x, NoEarlyStop{}, r);
 }
 
 // Many PROBLEMS in one launch (asp_sa_anneal_batch): workgroup -> (problem, group of M replicas)
@@ -1418,6 +1485,23 @@ SweepKernel sweep_kernel_for(int m, bool descent, int layout) {
   }
 }
 
+using ResumeKernel = void (*)(SweepArgs, Resume);
+
+// The forms of a handle's segment: every spin layout and group size of the closed call, no teams.
+ResumeKernel resume_kernel_for(int m, int layout) {
+  if (layout == kBits) return k_sa_sweep_resume<1, kBits>;
+  if (layout == kGlobal) return k_sa_sweep_resume<1, kGlobal>;
+  if (layout == kWide) return m == 4 ? k_sa_sweep_resume<4, kWide> : nullptr;
+  if (layout == kNibbles) return m == 4 ? k_sa_sweep_resume<4, kNibbles> : nullptr;
+  switch (m) {
+    case 1: return k_sa_sweep_resume<1, kBytes>;
+    case 2: return k_sa_sweep_resume<2, kBytes>;
+    case 4: return k_sa_sweep_resume<4, kBytes>;
+    case 8: return k_sa_sweep_resume<8, kBytes>;
+    default: return nullptr;
+  }
+}
+
 size_t sweep_lds_bytes(const asp::SaHostLayout &L, int layout) {
   // spins | delta[8] book[24] | flag (16 B) | meta[num_blocks]
   // ... | cache_ctl[4] | dirty[num_blocks] | inert[num_blocks] (each rounded up to 16 B)
@@ -1474,6 +1558,81 @@ void choose_launch(const asp_sa_plan *p, uint32_t repetitions, int *m_out, int *
   }
   *m_out = m;
   *threads_out = threads;
+}
+
+// Chains per group, threads and spin layout of a launch with one workgroup per group of chains —
+// shared by the closed calls (run_chains, which may then spread a chain over a team instead) and by
+// the segments of a handle (sa_chains_advance_colour), so that both take the same form.
+struct ColourLaunch {
+  int m = 1, threads = 64, layout = kBytes;
+  bool packed = false, nibbles = false, global = false, wide = false;
+};
+ColourLaunch choose_colour_launch(const asp_sa_plan *p, uint32_t repetitions, bool descent, bool traced) {
+  const asp::SaHostLayout &L = p->host;
+  ColourLaunch c;
+  choose_launch(p, repetitions, &c.m, &c.threads);
+  if (descent) c.m = 1;
+  // One byte per position when that fits the LDS; otherwise one BIT per position, one replica
+  // per workgroup (flips applied by wavefront ballot) — 8x the capacity.
+  c.packed = p->force_packed != 0;
+  if (!c.packed && sweep_lds_bytes(L, kBytes) > p->max_lds) {
+    // ... or, with chains enough for four per workgroup, four bits per position: twice the
+    // capacity of bytes and still four replicas sharing every coupling load
+    if (!descent && !traced && c.m >= 4 && sweep_lds_bytes(L, kNibbles) <= p->max_lds) {
+      c.nibbles = true;
+      c.m = 4;
+    } else {
+      c.packed = true;
+    }
+  }
+  // not even a bit per position fits the LDS: keep the words in HBM (no size limit, slow)
+  c.global = p->force_packed == 2 || (c.packed && sweep_lds_bytes(L, kBits) > p->max_lds);
+  if (c.packed) c.m = 1;
+  // A word per position (SDWA sign trick, DESIGN.md §5.2) when four replicas share the
+  // workgroup and the words fit; results do not depend on the layout.
+  // (measured: +2..12 % with four replicas per workgroup, nothing with two)
+  c.wide = !c.packed && !c.nibbles && !descent && p->allow_wide && c.m == 4 && p->ell_col4.ptr != nullptr &&
+           sweep_lds_bytes(L, kWide) <= p->max_lds;
+  c.layout = c.global ? kGlobal : (c.packed ? kBits : (c.nibbles ? kNibbles : (c.wide ? kWide : kBytes)));
+  return c;
+}
+
+// The plan's part of the sweep arguments (the same for every launch of the plan in the form `c`); the
+// caller adds betas, the start, the outputs, the seed and the sweep / replica counts.
+SweepArgs plan_sweep_args(const asp_sa_plan *p, const ColourLaunch &c) {
+  const asp::SaHostLayout &L = p->host;
+  SweepArgs plan_args{};
+  plan_args.color_block_start = p->color_block_start.ptr;
+  plan_args.block_width = p->block_width.ptr;
+  plan_args.ell_off = p->ell_off.ptr;
+  plan_args.ell_col = c.wide ? p->ell_col4.ptr : p->ell_col.ptr;
+  plan_args.ell_val = p->ell_val.ptr;
+  plan_args.spin_of_pos = p->spin_of_pos.ptr;
+  plan_args.field_pos = p->field_pos.ptr;
+  plan_args.scale = std::ldexp(1.0, L.energy_scale_exp);
+  plan_args.num_colors = L.num_colors;
+  plan_args.num_blocks = L.num_blocks;
+  plan_args.spin_words = c.global ? p->w_spins.ptr : nullptr;
+  return plan_args;
+}
+
+// Switch the field cache on after a sweep with fewer flips than this: a flip stales ~degree blocks,
+// and cached mode pays while that is a fraction of all blocks.
+uint32_t cache_enter_flips_of(const asp::SaHostLayout &L) {
+  const double degree = std::max(1.0, static_cast<double>(L.a_col.size()) / static_cast<double>(L.num_spins));
+  return static_cast<uint32_t>(std::max(1.0, 0.7 * static_cast<double>(L.num_blocks) / degree));
+}
+
+// The field cache of `padded` chains (512 B per block and replica), when it fits comfortably in HBM.
+void attach_field_cache(asp_sa_plan *p, uint64_t padded, SweepArgs *args) {
+  const asp::SaHostLayout &L = p->host;
+  const uint64_t cache_elems = padded * L.num_blocks * 64ull;
+  if (cache_elems * sizeof(double) <= (32ull << 30) && p->w_field_cache.ensure(cache_elems) == ASP_OK) {
+    args->field_cache = p->w_field_cache.ptr;
+    args->cache_enter_flips = cache_enter_flips_of(L);
+  } else {
+    asp_clear_error();  // the cache is an optimisation: run without it
+  }
 }
 
 int energies_of_perm(asp_sa_plan *p, const uint64_t *perm_words, uint32_t count, double *partial,
@@ -1698,31 +1857,9 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
     for (uint32_t r = 0; r < repetitions; ++r) out_e[r] = 0.0;
     return ASP_OK;
   }
-  int m = 1, threads = 64;
-  choose_launch(p, repetitions, &m, &threads);
-  if (descent) m = 1;
-  // One byte per position when that fits the LDS; otherwise one BIT per position, one replica
-  // per workgroup (flips applied by wavefront ballot) — 8x the capacity.
-  bool packed = p->force_packed != 0;
-  bool nibbles = false;
-  if (!packed && sweep_lds_bytes(L, kBytes) > p->max_lds) {
-    // ... or, with chains enough for four per workgroup, four bits per position: twice the
-    // capacity of bytes and still four replicas sharing every coupling load
-    if (!descent && !out_trace && m >= 4 && sweep_lds_bytes(L, kNibbles) <= p->max_lds) {
-      nibbles = true;
-      m = 4;
-    } else {
-      packed = true;
-    }
-  }
-  // not even a bit per position fits the LDS: keep the words in HBM (no size limit, slow)
-  const bool global = p->force_packed == 2 || (packed && sweep_lds_bytes(L, kBits) > p->max_lds);
-  if (packed) m = 1;
-  // A word per position (SDWA sign trick, DESIGN.md §5.2) when four replicas share the
-  // workgroup and the words fit; results do not depend on the layout.
-  // (measured: +2..12 % with four replicas per workgroup, nothing with two)
-  const bool wide = !packed && !nibbles && !descent && p->allow_wide && m == 4 &&
-                    p->ell_col4.ptr != nullptr && sweep_lds_bytes(L, kWide) <= p->max_lds;
+  const ColourLaunch chosen = choose_colour_launch(p, repetitions, descent, out_trace != nullptr);
+  int m = chosen.m, threads = chosen.threads;
+  const bool packed = chosen.packed, nibbles = chosen.nibbles, global = chosen.global;
   // Few chains on a large cluster: spread each chain over a team of workgroups (k_sa_sweep_team).
   uint32_t team = 0;
   {
@@ -1747,9 +1884,7 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
     if (team * repetitions > static_cast<uint32_t>(p->num_cus)) team = 0;  // must be co-resident
   }
   if (team >= 2) m = 1;
-  const int layout = team >= 2 ? kBits
-                               : (global ? kGlobal
-                                         : (packed ? kBits : (nibbles ? kNibbles : (wide ? kWide : kBytes))));
+  const int layout = team >= 2 ? kBits : chosen.layout;
   const size_t lds = team >= 2 ? team_lds_bytes(L) : sweep_lds_bytes(L, layout);
   if (lds > p->max_lds) {
     return asp::set_error(ASP_ERR_TOO_LARGE, "%zu B of LDS needed, %zu B available", lds,
@@ -1785,47 +1920,22 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
                        words, p->spin_of_pos.ptr, L.num_blocks, 1u, d_x0_perm.ptr);
   }
 
-  SweepArgs args{};
-  args.color_block_start = p->color_block_start.ptr;
-  args.block_width = p->block_width.ptr;
-  args.ell_off = p->ell_off.ptr;
-  args.ell_col = wide ? p->ell_col4.ptr : p->ell_col.ptr;
-  args.ell_val = p->ell_val.ptr;
-  args.spin_of_pos = p->spin_of_pos.ptr;
-  args.field_pos = p->field_pos.ptr;
+  SweepArgs args = plan_sweep_args(p, chosen);
   args.betas = d_betas.ptr;
   args.x0_perm = x0 ? d_x0_perm.ptr : nullptr;
   args.best_perm = d_best.ptr;
   args.tracked = d_tracked.ptr;
   args.accepted = d_accepted.ptr;
   args.seed = seed;
-  args.scale = std::ldexp(1.0, L.energy_scale_exp);
-  args.num_colors = L.num_colors;
-  args.num_blocks = L.num_blocks;
   args.num_sweeps = num_sweeps;
   args.replica_first = replica_offset;
-  args.field_cache = nullptr;
-  args.cache_enter_flips = 0;
-  args.spin_words = global ? p->w_spins.ptr : nullptr;
-  args.trace = nullptr;
   const uint64_t trace_elems = padded * (static_cast<uint64_t>(num_sweeps) + 1);
   if (out_trace) {
     ASP_TRY(p->w_trace.ensure(trace_elems));
     args.trace = p->w_trace.ptr;
   }
   if (p->use_field_cache && !packed && team < 2) {  // (both the byte and the wide layout)
-    // 512 B per block and replica; skipped when it would not fit comfortably in HBM
-    const uint64_t cache_elems = padded * L.num_blocks * 64ull;
-    if (cache_elems * sizeof(double) <= (32ull << 30) && p->w_field_cache.ensure(cache_elems) == ASP_OK) {
-      args.field_cache = p->w_field_cache.ptr;
-      // a flip stales ~degree blocks: cached mode pays while that is a fraction of all blocks
-      const double degree = std::max(1.0, static_cast<double>(L.a_col.size()) / static_cast<double>(K));
-      const double factor = 0.7;
-      args.cache_enter_flips =
-          static_cast<uint32_t>(std::max(1.0, factor * static_cast<double>(L.num_blocks) / degree));
-    } else {
-      asp_clear_error();  // the cache is an optimisation: run without it
-    }
+    attach_field_cache(p, padded, &args);
   }
 
   p->team_abort_host = 0;
@@ -1843,9 +1953,7 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
     threads = static_cast<int>(std::min<uint32_t>(16u, (widest + team - 1) / team)) * 64;
     if (p->use_field_cache) {
       // the team's "tracking" of untouched blocks uses the field cache's switch-over threshold
-      const double degree = std::max(1.0, static_cast<double>(L.a_col.size()) / static_cast<double>(K));
-      args.cache_enter_flips =
-          static_cast<uint32_t>(std::max(1.0, 0.7 * static_cast<double>(L.num_blocks) / degree));
+      args.cache_enter_flips = cache_enter_flips_of(L);
     }
     TeamArgs ta{};
     ta.s = args;
@@ -1962,6 +2070,106 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
 }
 
 }  // namespace
+
+namespace asp {
+
+// One segment of a handle in the colour order: the handle's original-order configurations are
+// permuted into the plan's block order (current and best, every chain its own), k_sa_sweep_resume
+// runs the sweeps from the carried integers with sweep index base c->sweeps_done, and both
+// configurations go back.  The launch is run_chains' minus teams: the same choice of chains per
+// group and spin layout, honouring asp_sa_set_launch / _set_packed / _set_wide; asp_sa_set_team
+// is ignored (a handle runs one workgroup per group of chains).
+int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace) {
+  asp_sa_plan *p = c->plan;
+  const SaHostLayout &L = p->host;
+  const uint64_t K = L.num_spins;
+  const uint32_t words = c->words, repetitions = c->repetitions;
+  const ColourLaunch chosen = choose_colour_launch(p, repetitions, false, trace != nullptr);
+  const int m = chosen.m, threads = chosen.threads, layout = chosen.layout;
+  const size_t lds = sweep_lds_bytes(L, layout);
+  if (lds > p->max_lds) {
+    return set_error(ASP_ERR_TOO_LARGE, "%zu B of LDS needed, %zu B available", lds, p->max_lds);
+  }
+  ResumeKernel kernel = resume_kernel_for(m, layout);
+  if (!kernel) return set_error(ASP_ERR_INVALID, "no resumable sweep for %d chains per group", m);
+  const uint32_t groups = (repetitions + m - 1) / m;
+  const uint64_t padded = static_cast<uint64_t>(groups) * m;
+  hipStream_t s = p->stream;
+  StreamFence fence(s);
+  if (chosen.global) ASP_TRY(p->w_spins.ensure(static_cast<uint64_t>(groups) * L.num_blocks));
+  ASP_TRY(p->w_betas.ensure(num_sweeps));
+  ASP_TRY(p->w_best.ensure(padded * L.num_blocks));
+  ASP_TRY(p->w_cur_perm.ensure(padded * L.num_blocks));
+  ASP_TRY(p->w_tracked.ensure(padded));
+  ASP_TRY(p->w_accepted.ensure(padded));
+  ASP_TRY(p->w_e_cur.ensure(padded));
+  ASP_TRY(p->w_betas.upload(betas, num_sweeps, s));
+  // (the chains padding the last group: all spins up, integers 0; their results are never read)
+  if (padded > repetitions) {
+    const uint64_t tail = (padded - repetitions) * L.num_blocks * sizeof(uint64_t);
+    ASP_HIP_TRY(hipMemsetAsync(p->w_best.ptr + static_cast<uint64_t>(repetitions) * L.num_blocks, 0, tail, s));
+    ASP_HIP_TRY(hipMemsetAsync(p->w_cur_perm.ptr + static_cast<uint64_t>(repetitions) * L.num_blocks, 0, tail, s));
+    ASP_HIP_TRY(hipMemsetAsync(p->w_tracked.ptr + repetitions, 0, (padded - repetitions) * 8, s));
+    ASP_HIP_TRY(hipMemsetAsync(p->w_accepted.ptr + repetitions, 0, (padded - repetitions) * 8, s));
+    ASP_HIP_TRY(hipMemsetAsync(p->w_e_cur.ptr + repetitions, 0, (padded - repetitions) * 8, s));
+  }
+  ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
+  ASP_HIP_TRY(hipMemcpyAsync(p->w_e_cur.ptr, c->e_cur.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
+  ASP_HIP_TRY(hipMemcpyAsync(p->w_tracked.ptr, c->e_best.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
+  ASP_HIP_TRY(hipMemcpyAsync(p->w_accepted.ptr, c->accepted.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
+  ASP_TRY(sa_permute_bits(p, c->x_cur.ptr, repetitions, p->w_cur_perm.ptr));
+  ASP_TRY(sa_permute_bits(p, c->x_best.ptr, repetitions, p->w_best.ptr));
+
+  SweepArgs args = plan_sweep_args(p, chosen);
+  args.betas = p->w_betas.ptr;
+  args.x0_perm = nullptr;
+  args.best_perm = p->w_best.ptr;
+  args.tracked = p->w_tracked.ptr;
+  args.accepted = p->w_accepted.ptr;
+  args.seed = c->seed;
+  args.num_sweeps = num_sweeps;
+  args.replica_first = c->replica_offset;
+  if (trace) {
+    ASP_TRY(p->w_trace.ensure(padded * (static_cast<uint64_t>(num_sweeps) + 1)));
+    args.trace = p->w_trace.ptr;
+  }
+  if (p->use_field_cache && !chosen.packed) attach_field_cache(p, padded, &args);
+  Resume res{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done};
+  if (lds > 64 * 1024) {
+    ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+  }
+  ASP_HIP_TRY(hipEventRecord(p->ev[1], s));
+  hipLaunchKernelGGL(kernel, dim3(groups), dim3(threads), lds, s, args, res);
+  ASP_HIP_TRY(hipGetLastError());
+  ASP_HIP_TRY(hipEventRecord(p->ev[2], s));
+  const dim3 grid((words + 3) / 4, (repetitions + kUnpermuteChains - 1) / kUnpermuteChains);
+  hipLaunchKernelGGL(k_unpermute_bits, grid, dim3(256), 0, s, p->w_cur_perm.ptr, L.num_blocks,
+                     p->pos_of_spin.ptr, K, words, repetitions, c->x_cur.ptr);
+  hipLaunchKernelGGL(k_unpermute_bits, grid, dim3(256), 0, s, p->w_best.ptr, L.num_blocks,
+                     p->pos_of_spin.ptr, K, words, repetitions, c->x_best.ptr);
+  ASP_HIP_TRY(hipGetLastError());
+  ASP_HIP_TRY(hipMemcpyAsync(c->e_cur.ptr, p->w_e_cur.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
+  ASP_HIP_TRY(hipMemcpyAsync(c->e_best.ptr, p->w_tracked.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
+  ASP_HIP_TRY(hipMemcpyAsync(c->accepted.ptr, p->w_accepted.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
+  ASP_HIP_TRY(hipEventRecord(p->ev[3], s));
+  ASP_HIP_TRY(hipMemcpyAsync(c->h_e_cur.data(), p->w_e_cur.ptr, repetitions * 8ull, hipMemcpyDeviceToHost, s));
+  if (trace) {  // rows of the real chains come first
+    ASP_HIP_TRY(hipMemcpyAsync(trace, p->w_trace.ptr,
+                               static_cast<uint64_t>(repetitions) * (num_sweeps + 1ull) * sizeof(int64_t),
+                               hipMemcpyDeviceToHost, s));
+  }
+  ASP_HIP_TRY(hipStreamSynchronize(s));
+  p->last_m = m;
+  p->last_layout = layout;
+  p->last_threads = threads;
+  p->last_groups = static_cast<int>(groups);
+  ASP_HIP_TRY(hipEventElapsedTime(&p->last_sweep_ms, p->ev[1], p->ev[2]));
+  ASP_HIP_TRY(hipEventElapsedTime(&p->last_total_ms, p->ev[0], p->ev[3]));
+  return ASP_OK;
+}
+
+}  // namespace asp
 
 extern "C" {
 

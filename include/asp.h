@@ -482,6 +482,75 @@ int asp_sa_last_shuffled_blocks(asp_sa_plan const *p, uint32_t *spins_per_block,
  * and a padding coupling execute like real ones. */
 int asp_sa_last_shuffled_fill(asp_sa_plan const *p, double *lane_fill, double *row_fill);
 
+/* RESUMABLE chains: a device-resident set of chains of one plan that is advanced a
+ * segment of sweeps at a time, inspected, checkpointed and continued — per-chain start
+ * configurations (annealing_sign_problem/train.py:238-245,297 anneals from a caller's x0), early
+ * stopping, re-heating, a change of visiting order in mid-run, a killed job that resumes.
+ *
+ * The continuation law: for any split n_1 + ... + n_k = N of a schedule betas[0..N) (segments of 0
+ * sweeps included), create(p, seed, R, off, x0, 0), advance(betas + n_1 + .. + n_{i-1}, n_i, order) for
+ * every i and result() return the words and doubles of asp_sa_anneal (order 0) / asp_sa_anneal_shuffled
+ * (order 1) called with (p, seed, betas, N, R, off, x0); the traces, concatenated without each later
+ * segment's entry 0, are those of the _trace calls, and the final tracked_best / accepted are that
+ * call's asp_sa_last_stats.  Sweep k of a segment is sweep t = sweeps_done + k of the chain: in the
+ * Philox counter of its random words and in the priorities of its shuffled visiting order (the order
+ * build starts its chunks at any t); "best" carries across segments with the closed call's tie-break
+ * (replaced on a strict improvement over the carried tracked_best only).
+ *
+ * Between calls a handle holds, per chain, two configurations in original spin order and three
+ * integers — nothing that depends on the visiting order or on a launch choice —, so segments may
+ * change `order`, and export -> import into another handle of the same plan continues the same chains.
+ * Buffers are sized once, at create.  Launch forms: a segment in the shuffled order runs every form
+ * of asp_sa_anneal_shuffled (spin layouts, chains per group, lane packing, asp_sa_set_shuffled_launch
+ * / _teams); a segment in the colour order runs every spin layout and group size of asp_sa_anneal
+ * (asp_sa_set_launch, _set_packed, _set_wide and _set_field_cache are honoured) but NO team launches:
+ * asp_sa_set_team is ignored and few chains on a large cluster run one workgroup per chain.  Results
+ * never depend on any of it.  A handle is used by one thread at a time, with its plan, and must be
+ * destroyed before the plan is.
+ *
+ * Every argument is checked before any device work and before any output is written; ASP_ERR_INVALID:
+ * a null plan / handle / out pointer, null betas with num_sweeps > 0, a negative or NaN beta, an order
+ * other than 0 or 1, an x0_stride of 1 .. ceil(K/64) - 1, sweeps_done + num_sweeps > 2^32 - 2 (t = 2^32 - 1
+ * is the random start's counter), a snapshot to import that lacks one of its five arrays.
+ * repetitions = 0 and plans without spins behave as in the closed calls (nothing runs, energies 0). */
+typedef struct asp_sa_chains asp_sa_chains;
+
+/* x0 == NULL: the random start of asp_sa_anneal (the t = 2^32 - 1 draw).  x0_stride == 0: every chain
+ * starts from the ceil(K/64) words at x0.  x0_stride >= ceil(K/64): chain r starts from
+ * x0 + r * x0_stride — chain r is then the one chain of a handle created with repetitions = 1,
+ * replica_offset + r and the shared start x0 + r * x0_stride.  Host pointers. */
+int asp_sa_chains_create(asp_sa_plan *p, uint64_t seed, uint32_t repetitions, uint32_t replica_offset,
+                         uint64_t const *x0, uint64_t x0_stride, asp_sa_chains **out);
+void asp_sa_chains_destroy(asp_sa_chains *c);
+
+/* Run sweeps t0 .. t0 + num_sweeps - 1 (t0 = sweeps done so far) at betas[0..num_sweeps).
+ * order: 0 = colour (asp_sa_anneal's chain), 1 = shuffled (asp_sa_anneal_shuffled's).
+ * out_trace: NULL, or HOST [repetitions][num_sweeps + 1]: the tracked energy at the start of the
+ * segment (entry 0, NOT reset to 0) and after each of its sweeps, in the units of asp_sa_anneal_trace,
+ * relative to the chain's very first configuration.  asp_sa_last_sweep_ms / _total_ms / _last_launch /
+ * _last_layout of the plan describe the segment. */
+int asp_sa_chains_advance(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, uint32_t order,
+                          int64_t *out_trace);
+
+/* The best configuration so far of every chain and its energy — what the closed call returns:
+ * out_x[repetitions * ceil(K/64)], out_e[repetitions] (host or device pointers). */
+int asp_sa_chains_result(asp_sa_chains *c, uint64_t *out_x, double *out_e);
+
+/* Everything a continuation needs, as plain host arrays the caller allocates (any pointer may be NULL
+ * on export; sweeps_done is always written): checkpoint to disk, inspect, or load into another handle
+ * of the same plan with the same seed, repetitions and replica_offset (those three are the handle's,
+ * not the snapshot's). */
+typedef struct asp_sa_chains_snapshot {
+  uint32_t sweeps_done;
+  uint64_t *x_current;       /* [repetitions][ceil(K/64)], original spin order, bit set = +1 */
+  uint64_t *x_best;          /* same shape */
+  int64_t *tracked_current;  /* [repetitions], units of 2^-energy_scale_exp, relative to the chain's first state */
+  int64_t *tracked_best;
+  uint64_t *accepted;        /* accepted flips so far */
+} asp_sa_chains_snapshot;
+int asp_sa_chains_export(asp_sa_chains *c, asp_sa_chains_snapshot *s);
+int asp_sa_chains_import(asp_sa_chains *c, asp_sa_chains_snapshot const *s);  /* all five arrays required */
+
 /* MANY independent problems in one call — the shape of the reference's production job: tens of
  * thousands of sampled clusters, each solved with 64 repetitions x 5120 sweeps
  * (Makefile:9,115-127; experiments/sampled_connected_components.py:764-767; common.py:236-239).
