@@ -43,6 +43,9 @@ using asp::DeviceBuffer;
 using asp::SymmetryArgs;
 
 constexpr int kThreads = 256;
+// A launch may hold fewer than 2^32 threads in all: with one workgroup per value of the high bits
+// the 24 to 28 high bits of 44 to 48 sites were refused ("invalid configuration argument").
+constexpr uint32_t kMaxGenerateBlocks = 1u << 22;
 
 unsigned grid_for(uint64_t items, uint64_t per_block) {
   return static_cast<unsigned>((items + per_block - 1) / per_block);
@@ -99,26 +102,28 @@ __device__ __forceinline__ void append(bool keep, uint64_t x, uint64_t *__restri
   }
 }
 
-// First pass: workgroup = one value of the high bits; its candidates are that value joined with
+// First pass: a workgroup takes one value of the high bits at a time (the grid is capped, see
+// kMaxGenerateBlocks, and strides over the values); its candidates are that value joined with
 // every low word of the matching population count (all low words when weight < 0).
 __global__ __launch_bounds__(kThreads) void k_sector_generate(
     SymmetryArgs g, uint32_t e_end, const uint32_t *__restrict__ low_words,
-    const uint32_t *__restrict__ low_offsets, uint32_t lo_bits, int32_t weight,
+    const uint32_t *__restrict__ low_offsets, uint32_t lo_bits, uint32_t hi_bits, int32_t weight,
     uint64_t *__restrict__ out, unsigned long long *__restrict__ count, uint64_t capacity) {
-  const uint64_t high = blockIdx.x;
-  uint32_t begin = 0, end = 1u << lo_bits;
-  if (weight >= 0) {
-    const int32_t need = weight - __popcll(high);
-    if (need < 0 || need > static_cast<int32_t>(lo_bits)) return;
-    begin = low_offsets[need];
-    end = low_offsets[need + 1];
-  }
-  for (uint32_t first = begin; first < end; first += kThreads) {  // uniform trip count
-    const uint32_t at = first + threadIdx.x;
-    const bool live = at < end;
-    const uint64_t x = (high << lo_bits) | (live ? (weight >= 0 ? low_words[at] : at) : 0u);
-    const bool keep = live && is_smallest(g, 0, e_end, x);
-    append(keep, x, out, count, capacity);
+  for (uint64_t high = blockIdx.x; high < (1ull << hi_bits); high += gridDim.x) {
+    uint32_t begin = 0, end = 1u << lo_bits;
+    if (weight >= 0) {
+      const int32_t need = weight - __popcll(high);
+      if (need < 0 || need > static_cast<int32_t>(lo_bits)) continue;
+      begin = low_offsets[need];
+      end = low_offsets[need + 1];
+    }
+    for (uint32_t first = begin; first < end; first += kThreads) {  // uniform trip count
+      const uint32_t at = first + threadIdx.x;
+      const bool live = at < end;
+      const uint64_t x = (high << lo_bits) | (live ? (weight >= 0 ? low_words[at] : at) : 0u);
+      const bool keep = live && is_smallest(g, 0, e_end, x);
+      append(keep, x, out, count, capacity);
+    }
   }
 }
 
@@ -370,8 +375,9 @@ int asp_sector_enumerate(asp_operator const *op, int32_t hamming_weight, uint64_
   ASP_HIP_TRY(hipMemsetAsync(d_count.ptr, 0, 4 * sizeof(unsigned long long), s));
   uint64_t cap_a = P ? room(e1) : static_cast<uint64_t>(candidates) + 1;
   ASP_TRY(d_a.alloc(cap_a));
-  hipLaunchKernelGGL(k_sector_generate, dim3(1u << hi_bits), dim3(kThreads), 0, s, g, e1, d_words.ptr,
-                     d_offsets.ptr, lo_bits, hamming_weight, d_a.ptr, d_count.ptr + 0, cap_a);
+  hipLaunchKernelGGL(k_sector_generate, dim3(std::min(1u << hi_bits, kMaxGenerateBlocks)),
+                     dim3(kThreads), 0, s, g, e1, d_words.ptr, d_offsets.ptr, lo_bits, hi_bits,
+                     hamming_weight, d_a.ptr, d_count.ptr + 0, cap_a);
   ASP_HIP_TRY(hipGetLastError());
   unsigned long long have = 0;
   auto fetch = [&](int which, uint64_t cap) -> int {
