@@ -96,6 +96,21 @@ class SaChainsSnapshot(ctypes.Structure):
     ]
 
 
+class SaChainsItem(ctypes.Structure):
+    """Mirror of ``asp_sa_chains_item`` (include/asp.h)."""
+
+    _fields_ = [
+        ("chains", c_void_p),
+        ("betas", c_void_p),
+        ("num_sweeps", c_u32),
+        ("order", c_u32),
+        ("flags", c_u32),
+        ("out_trace", c_void_p),
+        ("out_tracked_best", c_void_p),
+        ("out_improved", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/asp.h declares
 SIGNATURES = {
     "asp_last_error": (ctypes.c_char_p, []),
@@ -182,6 +197,8 @@ SIGNATURES = {
     "asp_sa_chains_result": (c_int, [c_void_p, c_void_p, c_void_p]),
     "asp_sa_chains_export": (c_int, [c_void_p, ctypes.POINTER(SaChainsSnapshot)]),
     "asp_sa_chains_import": (c_int, [c_void_p, ctypes.POINTER(SaChainsSnapshot)]),
+    "asp_sa_chains_advance_batch": (c_int, [ctypes.POINTER(SaChainsItem), c_u32]),
+    "asp_sa_chains_batch_last_ms": (c_float, []),
     "asp_sa_anneal_batch": (c_int, [ctypes.POINTER(SaBatchItem), c_u32]),
     "asp_sa_batch_last_ms": (c_float, []),
     "asp_sa_greedy": (c_int, [c_void_p, c_u32, c_void_p, c_void_p, ctypes.POINTER(c_u32)]),

@@ -644,6 +644,114 @@ def anneal_until(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: in
     return x, e, done
 
 
+def advance_chains(chains, betas, sweep_order=None, progress: bool = False):
+    """``chains[i].advance(betas[i], sweep_order[i])`` for every ``i`` in ONE device call
+    (``asp_sa_chains_advance_batch``): exactly the same chains, but the handles share
+    launches the way the problems of ``anneal_batch`` do.  ``chains``: ``Chains`` of distinct
+    Hamiltonians; ``betas``: one array per handle (lengths may differ, an empty one runs nothing);
+    ``sweep_order``: one value for all or one per handle.  ``progress=True`` returns
+    ``[(tracked_best int64[R], improved), ...]``: every chain's best tracked energy after the segment
+    and the number of chains whose best fell during it — one copy for the whole batch, no export per
+    handle; else ``None``."""
+    chains = list(chains)
+    n = len(chains)
+    for c in chains:
+        if not isinstance(c, Chains):
+            raise TypeError("'chains' must hold Chains objects")
+    if isinstance(sweep_order, (list, tuple)):
+        orders = list(sweep_order)
+    else:
+        orders = [sweep_order] * n
+    betas = list(betas)
+    if not (len(betas) == len(orders) == n):
+        raise ValueError("advance_chains: %d handles, %d beta arrays and %d sweep orders" % (n, len(betas), len(orders)))
+    betas = [np.ascontiguousarray(b, dtype=np.float64).reshape(-1) for b in betas]
+    orders = [Chains._ORDERS[resolve_sweep_order(o)] for o in orders]
+    items = (_lib.SaChainsItem * max(n, 1))()
+    out = []  # (also keeps the output buffers alive over the call)
+    for i, c in enumerate(chains):
+        items[i].chains = c._live()
+        items[i].betas = betas[i].ctypes.data if betas[i].shape[0] else None
+        items[i].num_sweeps = betas[i].shape[0]
+        items[i].order = orders[i]
+        items[i].flags = 0
+        if progress:
+            best = np.zeros(max(c.repetitions, 1), dtype=np.int64)
+            improved = ctypes.c_uint32(0)
+            items[i].out_tracked_best = best.ctypes.data
+            items[i].out_improved = ctypes.addressof(improved)
+            out.append((best, improved, c.repetitions))
+    _lib.check(_lib.load().asp_sa_chains_advance_batch(items, ctypes.c_uint32(n)))
+    if not progress:
+        return None
+    return [(best[:reps], int(improved.value)) for best, improved, reps in out]
+
+
+def anneal_batch_until(hamiltonians, seed=None, number_sweeps: int = 5120, repetitions: int = 64,
+                       only_best: bool = True, beta0: Optional[float] = None, beta1: Optional[float] = None,
+                       sweep_order: Optional[str] = None, check_every: int = 512,
+                       patience: Optional[int] = None):
+    """``[anneal_until(h, seed=seed, number_sweeps=..., repetitions=..., ...) for h in hamiltonians]``
+    with every segment of all problems still running in one device call (``advance_chains``): problem
+    ``i`` stops once none of its chains improved for ``patience`` consecutive segments and is left out
+    of the later calls.  Returns ``[(x, e, sweeps_run), ...]``; with ``patience=None`` nothing stops
+    early and ``(x, e)`` is ``anneal_batch(...)``'s element.  ``seed`` as in ``anneal_batch``."""
+    order = resolve_sweep_order(sweep_order)  # (first: a bad order fails without a GPU)
+    check_every = int(check_every)
+    if check_every < 1:
+        raise ValueError("'check_every' must be positive")
+    if patience is not None and int(patience) < 1:
+        raise ValueError("'patience' must be positive or None")
+    hamiltonians = list(hamiltonians)
+    n = len(hamiltonians)
+    for h in hamiltonians:
+        if not isinstance(h, Hamiltonian):
+            raise TypeError("'hamiltonians' must hold Hamiltonian objects")
+    if len({id(h) for h in hamiltonians}) != n:
+        raise ValueError("anneal_batch_until: every problem needs its own Hamiltonian object")
+    repetitions = int(repetitions)
+    if repetitions < 1:
+        raise ValueError("'repetitions' must be positive")
+    if seed is None or np.ndim(seed) == 0:
+        seeds = [_resolve_seed(seed) for _ in range(n)] if seed is None else [_resolve_seed(seed)] * n
+    else:
+        seeds = [_resolve_seed(x) for x in seed]
+    schedules = []
+    for h in hamiltonians:
+        b0, b1 = beta0, beta1
+        if b0 is None or b1 is None:
+            info = h.info()
+            b0 = info.beta0_auto if b0 is None else b0
+            b1 = info.beta1_auto if b1 is None else b1
+        schedules.append(make_schedule(float(b0), float(b1), number_sweeps))
+    handles = []
+    try:
+        for h, s in zip(hamiltonians, seeds):
+            handles.append(Chains(h, seed=s, repetitions=repetitions))
+        still = [0] * n
+        done = [0] * n
+        running = [i for i in range(n) if schedules[i].shape[0] > 0]
+        while running:
+            told = advance_chains([handles[i] for i in running],
+                                  [schedules[i][done[i]:done[i] + check_every] for i in running],
+                                  sweep_order=order, progress=True)
+            later = []
+            for i, (_, improved) in zip(running, told):
+                done[i] = min(done[i] + check_every, schedules[i].shape[0])
+                still[i] = 0 if improved else still[i] + 1
+                if done[i] < schedules[i].shape[0] and not (patience is not None and still[i] >= int(patience)):
+                    later.append(i)
+            running = later
+        results = []
+        for i, c in enumerate(handles):
+            x, e = c.result(only_best=only_best)
+            results.append((x, e, done[i]))
+    finally:
+        for c in handles:
+            c.close()
+    return results
+
+
 def anneal_with_traces(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: int = 5120,
                        beta0: Optional[float] = None, beta1: Optional[float] = None,
                        sweep_order: Optional[str] = "colour"):

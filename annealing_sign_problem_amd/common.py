@@ -301,12 +301,16 @@ def _project_on_frozen(model: IsingModel, x: np.ndarray, frozen_spins) -> np.nda
 
 
 def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_sweeps: int = 5120,
-                       repetitions: int = 64, sweep_order: Optional[str] = None, mode: str = "sa"):
+                       repetitions: int = 64, sweep_order: Optional[str] = None, mode: str = "sa",
+                       check_every: Optional[int] = None, patience: Optional[int] = None):
     """``[solve_ising_model(m, mode, f, seed, number_sweeps, repetitions) for m, f in
     zip(models, frozen_spins)]`` with all annealing chains of all models in ONE device call
     (``sa.anneal_batch``): the same result for every model, at the throughput of a full chip
     instead of one small launch per model.  ``mode="greedy"``: the greedy solves of all models in
-    one call (``sa.greedy_solve_batch``), with the same projection on the frozen spins."""
+    one call (``sa.greedy_solve_batch``), with the same projection on the frozen spins.
+    ``patience`` (not in the reference; default off): every model's ladder runs in segments of
+    ``check_every`` sweeps (default 512) and stops once none of its chains improved for ``patience``
+    consecutive segments (``sa.anneal_batch_until``) — fewer sweeps, results that may differ."""
     models = list(models)
     frozen = [None] * len(models) if frozen_spins is None else list(frozen_spins)
     if mode == "greedy":
@@ -315,6 +319,12 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
     if mode != "sa":
         raise ValueError(
             "invalid mode specified: '{}'; expected either 'sa' or 'greedy'".format(mode))
+    if patience is not None:
+        best = sa.anneal_batch_until([m.ising_hamiltonian for m in models], seed=seed,
+                                     number_sweeps=number_sweeps, repetitions=repetitions, only_best=True,
+                                     sweep_order=sweep_order, patience=patience,
+                                     check_every=512 if check_every is None else check_every)
+        return [_project_on_frozen(m, x, f) for m, (x, _, _), f in zip(models, best, frozen)]
     best = sa.anneal_batch([m.ising_hamiltonian for m in models], seed=seed,
                            number_sweeps=number_sweeps, repetitions=repetitions, only_best=True,
                            sweep_order=sweep_order)

@@ -10,7 +10,9 @@
 // the closed call's chain, bit for bit.  gfx950 only.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "asp_common.hpp"
@@ -58,6 +60,45 @@ std::vector<uint64_t> staged(const uint64_t *x, uint64_t stride, uint32_t count,
 }
 
 bool nothing_to_run(const asp_sa_chains *c) { return c->repetitions == 0 || c->plan->host.num_spins == 0; }
+
+// Progress of a batched segment (asp_sa_chains_advance_batch): what asp_sa_chains_export before and
+// after the segment would tell, for every handle of the batch in ONE buffer and one copy to the host.
+// Row i of `table` describes handle i; its chains own `out` entries [at, at + chains) of three planes
+// of `total` entries each: the best tracked energies before the segment (kept on the device), after
+// it, and the current ones (the host's entry 0 of the next trace); improved[i] counts the chains whose
+// best fell strictly.
+struct ProgressRow {
+  const long long *e_cur, *e_best;
+  uint64_t at;
+  uint32_t chains;
+};
+// after = false: before the sweeps (plane 0); true: after them (planes 1 and 2, the counts).
+// A workgroup per handle.
+__global__ __launch_bounds__(256) void k_chains_progress(const ProgressRow *table, uint64_t total, bool after,
+                                                         long long *__restrict__ out,
+                                                         uint32_t *__restrict__ improved) {
+  const ProgressRow row = table[blockIdx.x];
+  uint32_t fell = 0;
+  for (uint32_t r = threadIdx.x; r < row.chains; r += blockDim.x) {
+    const long long best = row.e_best[r];
+    if (!after) {
+      out[row.at + r] = best;
+    } else {
+      out[total + row.at + r] = best;
+      out[2 * total + row.at + r] = row.e_cur[r];
+      fell += best < out[row.at + r] ? 1u : 0u;
+    }
+  }
+  if (!after) return;
+  __shared__ uint32_t sum;
+  if (threadIdx.x == 0) sum = 0;
+  __syncthreads();
+  if (fell) atomicAdd(&sum, fell);
+  __syncthreads();
+  if (threadIdx.x == 0) improved[blockIdx.x] = sum;
+}
+
+thread_local float g_chains_batch_ms = 0.0f;
 
 }  // namespace
 
@@ -158,6 +199,123 @@ int asp_sa_chains_advance(asp_sa_chains *c, double const *betas, uint32_t num_sw
     for (uint32_t r = 0; r < R; ++r) out_trace[static_cast<uint64_t>(r) * (num_sweeps + 1ull)] = start[r];
   }
   c->sweeps_done += num_sweeps;
+  return ASP_OK;
+}
+
+float asp_sa_chains_batch_last_ms(void) { return g_chains_batch_ms; }
+
+int asp_sa_chains_advance_batch(asp_sa_chains_item const *items, uint32_t count) {
+  asp_clear_error();
+  g_chains_batch_ms = 0.0f;
+  if (count == 0) return ASP_OK;
+  if (!items) return asp::set_error(ASP_ERR_INVALID, "null items");
+  // ---- validation: every item before any device work and before any output is written ----
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_chains_item &it = items[i];
+    if (!it.chains) return asp::set_error(ASP_ERR_INVALID, "item %u: null chains handle", i);
+    if (it.num_sweeps && !it.betas) return asp::set_error(ASP_ERR_INVALID, "item %u: null betas", i);
+    if (it.order > 1u) return asp::set_error(ASP_ERR_INVALID, "item %u: order must be 0 (colour) or 1 (shuffled)", i);
+    if (it.flags != 0) return asp::set_error(ASP_ERR_INVALID, "item %u: unknown flags 0x%x", i, it.flags);
+    if (static_cast<uint64_t>(it.chains->sweeps_done) + it.num_sweeps > 0xFFFFFFFEull) {
+      return asp::set_error(ASP_ERR_INVALID, "item %u: %u sweeps after %u exceed the 2^32 - 2 sweep indices of a chain",
+                            i, it.num_sweeps, it.chains->sweeps_done);
+    }
+    for (uint32_t t = 0; t < it.num_sweeps; ++t) {
+      if (!(it.betas[t] >= 0.0)) return asp::set_error(ASP_ERR_INVALID, "item %u: betas[%u] is not >= 0", i, t);
+    }
+  }
+  {
+    // (a plan's work buffers serve one segment at a time; the same handle twice is the same plan twice,
+    // reported as what it is)
+    std::vector<std::pair<const asp_sa_plan *, uint32_t>> plans(count);
+    for (uint32_t i = 0; i < count; ++i) plans[i] = {items[i].chains->plan, i};
+    std::sort(plans.begin(), plans.end());
+    for (uint32_t i = 1; i < count; ++i) {
+      if (plans[i].first != plans[i - 1].first) continue;
+      const uint32_t a = plans[i - 1].second, b = plans[i].second;
+      if (items[a].chains == items[b].chains) {
+        return asp::set_error(ASP_ERR_INVALID, "items %u and %u are the same handle", a, b);
+      }
+      return asp::set_error(ASP_ERR_INVALID, "items %u and %u are handles of one plan", a, b);
+    }
+  }
+  ASP_TRY(asp::bind_device());
+  // ---- progress, before: the best tracked energies of every handle that is asked about ----
+  bool wanted = false;
+  std::vector<ProgressRow> rows(count);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_chains *c = items[i].chains;
+    rows[i] = ProgressRow{c->e_cur.ptr, c->e_best.ptr, total, c->repetitions};
+    total += c->repetitions;
+    wanted = wanted || items[i].out_tracked_best || items[i].out_improved;
+  }
+  asp::DeviceBuffer<ProgressRow> d_rows;
+  asp::DeviceBuffer<long long> d_progress;  // [3][total] | improved[count] in the words behind
+  asp::ScopedStream progress_stream;
+  const uint64_t progress_words = 3 * total + (count + 1ull) / 2;
+  uint32_t *d_improved = nullptr;
+  if (total != 0) {
+    ASP_TRY(progress_stream.acquire());
+    ASP_TRY(d_rows.alloc(count));
+    ASP_TRY(d_progress.alloc(progress_words));
+    d_improved = reinterpret_cast<uint32_t *>(d_progress.ptr + 3 * total);
+    ASP_TRY(d_rows.upload(rows.data(), count, progress_stream.stream));
+    if (wanted) {
+      hipLaunchKernelGGL(k_chains_progress, dim3(count), dim3(256), 0, progress_stream.stream, d_rows.ptr, total,
+                         false, d_progress.ptr, d_improved);
+      ASP_HIP_TRY(hipGetLastError());
+    }
+    ASP_HIP_TRY(hipStreamSynchronize(progress_stream.stream));
+  }
+  // ---- the segments: per visiting order, the handles that fit in shared launches ----
+  std::vector<std::vector<int64_t>> starts(count);  // entry 0 of every traced row: NOT reset to 0
+  std::vector<asp::ChainsSegment> colour, shuffled;
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_chains_item &it = items[i];
+    if (it.out_trace) starts[i] = it.chains->h_e_cur;
+    if (it.num_sweeps == 0 || nothing_to_run(it.chains)) {
+      if (it.out_trace) {  // (no spins: the energy stays where it is; no sweeps: the single entry below)
+        for (uint64_t k = 0; k < static_cast<uint64_t>(it.chains->repetitions) * (it.num_sweeps + 1ull); ++k) {
+          it.out_trace[k] = 0;
+        }
+      }
+      continue;
+    }
+    (it.order == 0 ? colour : shuffled).push_back(asp::ChainsSegment{it.chains, it.betas, it.num_sweeps, it.out_trace});
+  }
+  if (!shuffled.empty()) {
+    ASP_TRY(asp::sa_chains_advance_shuffled_batch(shuffled.data(), static_cast<uint32_t>(shuffled.size()),
+                                                  &g_chains_batch_ms));
+  }
+  if (!colour.empty()) {
+    ASP_TRY(asp::sa_chains_advance_colour_batch(colour.data(), static_cast<uint32_t>(colour.size()),
+                                                &g_chains_batch_ms));
+  }
+  // ---- progress, after: one gather launch and one copy for the whole batch ----
+  std::vector<long long> h_progress(progress_words, 0);
+  if (total != 0) {
+    hipLaunchKernelGGL(k_chains_progress, dim3(count), dim3(256), 0, progress_stream.stream, d_rows.ptr, total, true,
+                       d_progress.ptr, d_improved);
+    ASP_HIP_TRY(hipGetLastError());
+    ASP_TRY(d_progress.download(h_progress.data(), progress_words, progress_stream.stream));
+    ASP_HIP_TRY(hipStreamSynchronize(progress_stream.stream));
+  }
+  const uint32_t *h_improved = reinterpret_cast<const uint32_t *>(h_progress.data() + 3 * total);
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_chains_item &it = items[i];
+    asp_sa_chains *c = it.chains;
+    const uint32_t R = c->repetitions;
+    for (uint32_t r = 0; r < R; ++r) c->h_e_cur[r] = h_progress[2 * total + rows[i].at + r];
+    if (it.out_tracked_best) {
+      for (uint32_t r = 0; r < R; ++r) it.out_tracked_best[r] = h_progress[total + rows[i].at + r];
+    }
+    if (it.out_improved) *it.out_improved = total != 0 ? h_improved[i] : 0u;
+    if (it.out_trace) {
+      for (uint32_t r = 0; r < R; ++r) it.out_trace[static_cast<uint64_t>(r) * (it.num_sweeps + 1ull)] = starts[i][r];
+    }
+    c->sweeps_done += it.num_sweeps;
+  }
   return ASP_OK;
 }
 

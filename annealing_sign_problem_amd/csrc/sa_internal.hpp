@@ -109,4 +109,17 @@ int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uin
 int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace);
 int sa_chains_advance_shuffled(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace);
 
+// The items of asp_sa_chains_advance_batch that run sweeps (validated; distinct handles of distinct
+// plans with spins and chains, num_sweeps > 0), one visiting order at a time: every segment is exactly
+// its sa_chains_advance_colour / _shuffled call, the handles that fit share launches.  h_e_cur of the
+// handles is the caller's to refresh; adds the device time of the sweep launches to *sweep_ms.
+struct ChainsSegment {
+  asp_sa_chains *chains;
+  double const *betas;
+  uint32_t num_sweeps;
+  int64_t *trace;  // nullptr, or HOST [repetitions][num_sweeps + 1]: the segment runs alone
+};
+int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms);
+int sa_chains_advance_shuffled_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms);
+
 }  // namespace asp

@@ -1740,6 +1740,77 @@ __global__ __launch_bounds__(256) void k_chains_state_out(const T *__restrict__ 
   }
 }
 
+// The same for MANY handles at once (asp_sa_chains_advance_batch, order 1): a descriptor per handle and
+// a slot table of (handle, group) — out: (handle, chain) —, one launch each way per state type instead
+// of one per handle; the three integers per chain and the best configurations go through one
+// gather / scatter launch instead of four copies per handle.
+struct ChainsStateProblem {
+  uint64_t *x_cur, *x_best;  // the handle: [chains][words], original order, bit = +1
+  long long *e_cur, *e_best;
+  unsigned long long *accepted;
+  void *state;               // the run: ShuffledArgs::state, [groups][num_spins] bytes or words
+  uint64_t *best;            // [padded][words]
+  long long *w_e_cur, *w_e_best;  // [padded]
+  unsigned long long *w_accepted;
+  uint32_t num_spins, words, chains, m, padded;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void k_chains_state_in_batch(const ChainsStateProblem *problems,
+                                                              const ShuffledSlot *slots) {
+  const ShuffledSlot slot = slots[blockIdx.x];
+  const ChainsStateProblem &d = problems[slot.problem];
+  const uint32_t g = slot.group;
+  T *state = static_cast<T *>(d.state);
+  for (uint32_t i = blockIdx.y * blockDim.x + threadIdx.x; i < d.num_spins; i += gridDim.y * blockDim.x) {
+    uint32_t mask = 0;
+    for (uint32_t j = 0; j < d.m; ++j) {
+      const uint64_t r = static_cast<uint64_t>(g) * d.m + j;
+      if (r >= d.chains) break;
+      mask |= (static_cast<uint32_t>((d.x_cur[r * d.words + (i >> 6)] >> (i & 63u)) & 1ull) ^ 1u) << j;
+    }
+    state[static_cast<uint64_t>(g) * d.num_spins + i] = static_cast<T>(mask);
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_chains_state_out_batch(const ChainsStateProblem *problems,
+                                                               const ShuffledSlot *chains) {
+  const ShuffledSlot slot = chains[blockIdx.x];
+  const ChainsStateProblem &d = problems[slot.problem];
+  const uint32_t r = slot.group, lane = threadIdx.x & 63u;
+  const T *state_g = static_cast<const T *>(d.state) + static_cast<uint64_t>(r / d.m) * d.num_spins;
+  for (uint32_t w = blockIdx.y * (blockDim.x >> 6) + (threadIdx.x >> 6); w < d.words; w += gridDim.y * (blockDim.x >> 6)) {
+    const uint32_t i = w * 64u + lane;  // (w is uniform over the wavefront)
+    bool up = false;
+    if (i < d.num_spins) up = ((static_cast<uint32_t>(state_g[i]) >> (r % d.m)) & 1u) == 0u;
+    const uint64_t word = __ballot(up);
+    if (lane == 0) d.x_cur[static_cast<uint64_t>(r) * d.words + w] = word;
+  }
+}
+// IN: handle -> run (the chains padding the last group: integers 0, as load_resume); else run -> handle.
+// A workgroup row per handle.
+template <bool IN>
+__global__ __launch_bounds__(256) void k_chains_carried_batch(const ChainsStateProblem *problems) {
+  const ChainsStateProblem &d = problems[blockIdx.x];
+  const uint64_t first = static_cast<uint64_t>(blockIdx.y) * blockDim.x + threadIdx.x;
+  const uint64_t step = static_cast<uint64_t>(gridDim.y) * blockDim.x;
+  if constexpr (IN) {
+    for (uint64_t r = first; r < d.padded; r += step) {
+      const bool live = r < d.chains;
+      d.w_e_cur[r] = live ? d.e_cur[r] : 0ll;
+      d.w_e_best[r] = live ? d.e_best[r] : 0ll;
+      d.w_accepted[r] = live ? d.accepted[r] : 0ull;
+    }
+    for (uint64_t k = first; k < static_cast<uint64_t>(d.chains) * d.words; k += step) d.best[k] = d.x_best[k];
+  } else {
+    for (uint64_t r = first; r < d.chains; r += step) {
+      d.e_cur[r] = d.w_e_cur[r];
+      d.e_best[r] = d.w_e_best[r];
+      d.accepted[r] = d.w_accepted[r];
+    }
+    for (uint64_t k = first; k < static_cast<uint64_t>(d.chains) * d.words; k += step) d.x_best[k] = d.best[k];
+  }
+}
+
 // The value p - 8 t0, for the segments of a handle.  The sweep kernels index the call's betas and trace
 // rows with the GLOBAL sweep index t (the one of the random words): a.betas[t], a.trace[.. + t + 1].  In
 // a closed call t starts at 0; in a segment it starts at t0, so the kernel is handed a base that lies
@@ -1945,6 +2016,7 @@ struct ShuffledRun {
   // and trace through rebased()) —, no launch initialises, and nothing is reported but the state.
   asp_sa_chains *resume = nullptr;
   uint32_t t0 = 0;
+  bool resume_shared = false;  // set by the batched driver: it loads and stores the handles of its runs together
 
   uint64_t K = 0;
   uint32_t words = 0, groups = 0, waves = 1, level_cap = 0, quad_cap = 0, order_threads = 64, lanes_per_row = 1;
@@ -2529,6 +2601,7 @@ struct ShuffledRun {
 
   // The end of a segment: the chains back into the handle (queued).
   int finish_resume() {
+    if (resume_shared) return ASP_OK;  // (run_shuffled_group wrote every handle of the group back)
     hipStream_t s = p->stream;
     const uint64_t R = repetitions;
     const dim3 grid(repetitions, std::min(words / 4u + 1u, 1024u));
@@ -2673,6 +2746,69 @@ struct EventPool {
   }
 };
 
+// The handles of the group's runs (ShuffledRun::resume) into the runs' buffers before an attempt
+// (`in`), or out of them after the attempt that succeeded: one launch per state type and one for the
+// integers and best configurations, for all handles; queued on `stream` and waited for.
+int move_group_state(const std::vector<ShuffledRun *> &runs, bool in, hipStream_t stream) {
+  std::vector<ChainsStateProblem> problems;
+  std::vector<ShuffledSlot> slots[2];  // [0]: a byte per spin, [1]: kGlobal's word
+  uint32_t rows[2] = {1, 1};
+  for (ShuffledRun *r : runs) {
+    if (!r->resume) continue;
+    asp_sa_chains *c = r->resume;
+    const uint32_t k = static_cast<uint32_t>(problems.size());
+    ChainsStateProblem d{};
+    d.x_cur = c->x_cur.ptr;
+    d.x_best = c->x_best.ptr;
+    d.e_cur = c->e_cur.ptr;
+    d.e_best = c->e_best.ptr;
+    d.accepted = c->accepted.ptr;
+    d.state = r->d_state.ptr;
+    d.best = r->d_best.ptr;
+    d.w_e_cur = r->d_ecur.ptr;
+    d.w_e_best = r->d_ebest.ptr;
+    d.w_accepted = r->d_accepted.ptr;
+    d.num_spins = static_cast<uint32_t>(r->K);
+    d.words = r->words;
+    d.chains = r->repetitions;
+    d.m = static_cast<uint32_t>(r->m);
+    d.padded = static_cast<uint32_t>(r->padded);
+    problems.push_back(d);
+    const int t = r->layout == kGlobal ? 1 : 0;
+    const uint32_t count = in ? r->groups : r->repetitions;
+    for (uint32_t g = 0; g < count; ++g) slots[t].push_back(ShuffledSlot{k, g});
+    const uint64_t want = in ? (r->K + 255) / 256 : r->words / 4u + 1u;
+    rows[t] = std::max(rows[t], static_cast<uint32_t>(std::min<uint64_t>(want, 64)));
+  }
+  if (problems.empty()) return ASP_OK;
+  DeviceBuffer<ChainsStateProblem> d_problems;
+  DeviceBuffer<ShuffledSlot> d_slots[2];
+  asp::StreamFence fence(stream);  // (the tables die with this scope)
+  ASP_TRY(d_problems.alloc(problems.size()));
+  ASP_TRY(d_problems.upload(problems.data(), problems.size(), stream));
+  const dim3 carried(static_cast<uint32_t>(problems.size()), 4);
+  if (in) hipLaunchKernelGGL(k_chains_carried_batch<true>, carried, dim3(256), 0, stream, d_problems.ptr);
+  for (int t = 0; t < 2; ++t) {
+    if (slots[t].empty()) continue;
+    ASP_TRY(d_slots[t].alloc(slots[t].size()));
+    ASP_TRY(d_slots[t].upload(slots[t].data(), slots[t].size(), stream));
+    const dim3 grid(static_cast<uint32_t>(slots[t].size()), rows[t]);
+    if (in && t == 0) {
+      hipLaunchKernelGGL(k_chains_state_in_batch<uint8_t>, grid, dim3(256), 0, stream, d_problems.ptr, d_slots[t].ptr);
+    } else if (in) {
+      hipLaunchKernelGGL(k_chains_state_in_batch<uint32_t>, grid, dim3(256), 0, stream, d_problems.ptr, d_slots[t].ptr);
+    } else if (t == 0) {
+      hipLaunchKernelGGL(k_chains_state_out_batch<uint8_t>, grid, dim3(256), 0, stream, d_problems.ptr, d_slots[t].ptr);
+    } else {
+      hipLaunchKernelGGL(k_chains_state_out_batch<uint32_t>, grid, dim3(256), 0, stream, d_problems.ptr, d_slots[t].ptr);
+    }
+  }
+  if (!in) hipLaunchKernelGGL(k_chains_carried_batch<false>, carried, dim3(256), 0, stream, d_problems.ptr);
+  ASP_HIP_TRY(hipGetLastError());
+  ASP_HIP_TRY(hipStreamSynchronize(stream));
+  return ASP_OK;
+}
+
 // Problems with the same number of sweeps in SHARED launches: per chunk one order launch over
 // (problem, sweep) and one sweep launch per class of workgroup shape over (problem, group of
 // chains) — descriptors of every problem and chunk in one device table, uploaded once.  A launch
@@ -2689,6 +2825,7 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
   for (ShuffledRun *r : runs) {
     r->batched = true;
     r->teams = 1;
+    r->resume_shared = r->resume != nullptr;
   }
   // (declared before the streams: released after the streams have been waited for, also on an
   // early error return)
@@ -2876,6 +3013,8 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
       ASP_TRY(d_oargs_wide.upload(oargs_wide.data(), oargs_wide.size(), os0));
     }
     ASP_HIP_TRY(hipStreamSynchronize(os0));
+    // (segments of handles: every attempt starts from the handles' state, which is untouched so far)
+    ASP_TRY(move_group_state(runs, true, os0));
     // ---- the pipeline of runs' enqueue(), with shared launches ----
     const uint32_t nsets = static_cast<uint32_t>(runs[0]->nsets), nlanes = static_cast<uint32_t>(runs[0]->nlanes);
     ASP_HIP_TRY(hipEventRecord(t_begin, os0));
@@ -2928,6 +3067,8 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
     }
     if (!again) break;
   }
+  // (... and is written back only now, after the attempt that succeeded)
+  ASP_TRY(move_group_state(runs, false, order_stream[0].stream));
   float ms = 0.0f;
   ASP_HIP_TRY(hipEventElapsedTime(&ms, t_begin, t_end));
   if (sweep_ms) *sweep_ms += ms;
@@ -3096,6 +3237,113 @@ int sa_chains_advance_shuffled(asp_sa_chains *c, double const *betas, uint32_t n
   }
   ASP_TRY(run.finish_enqueue());
   return run.finish_wait();
+}
+
+// Many segments in the shuffled order: sa_shuffled_batch for runs in their resume form — the same
+// chains per group for the batch, lane packing and one team; segments of equal length share launches
+// (run_shuffled_group, with every handle's own t0), a traced segment and a group of one take the
+// single-handle path.
+int sa_chains_advance_shuffled_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms) {
+  std::vector<uint32_t> shared;
+  auto alone = [&](const ChainsSegment &g) -> int {
+    asp_sa_plan *p = g.chains->plan;
+    p->last_sweep_ms = p->last_total_ms = 0.0f;
+    ASP_TRY(sa_chains_advance_shuffled(g.chains, g.betas, g.num_sweeps, g.trace));
+    if (sweep_ms) *sweep_ms += p->last_sweep_ms;
+    return ASP_OK;
+  };
+  for (uint32_t i = 0; i < count; ++i) {
+    if (segs[i].trace) {
+      ASP_TRY(alone(segs[i]));  // (the batched launches have no trace form)
+    } else {
+      shared.push_back(i);
+    }
+  }
+  {
+    // (a segment that no other shares its length with is a group of one: the single-handle path, with
+    // the launcher's own choices, before any run is set up)
+    std::vector<uint32_t> lengths, kept;
+    for (uint32_t i : shared) lengths.push_back(segs[i].num_sweeps);
+    std::sort(lengths.begin(), lengths.end());
+    for (uint32_t i : shared) {
+      const auto same = std::equal_range(lengths.begin(), lengths.end(), segs[i].num_sweeps);
+      if (same.second - same.first >= 2) {
+        kept.push_back(i);
+      } else {
+        ASP_TRY(alone(segs[i]));
+      }
+    }
+    shared.swap(kept);
+  }
+  if (shared.empty()) return ASP_OK;
+  const uint32_t n = static_cast<uint32_t>(shared.size());
+  uint64_t budget = 16ull << 30;  // bytes of visiting orders for the whole batch, per buffer set
+  if (const char *env = std::getenv("ASP_SHUFFLED_BATCH_BYTES")) budget = std::strtoull(env, nullptr, 10);
+  // chains per workgroup for the whole batch: as many as still leave two workgroups per compute unit
+  int m = 1;
+  bool saturates = false;
+  {
+    const int num_cus = segs[shared[0]].chains->plan->num_cus;
+    for (int cand : {4, 2}) {
+      uint64_t groups = 0;
+      for (uint32_t i : shared) groups += (segs[i].chains->repetitions + cand - 1) / cand;
+      if (groups >= 2ull * static_cast<uint64_t>(num_cus)) {
+        m = cand;
+        saturates = true;
+        break;
+      }
+    }
+  }
+  std::vector<std::unique_ptr<ShuffledRun>> runs;
+  runs.reserve(n);
+  for (uint32_t i : shared) {
+    asp_sa_chains *c = segs[i].chains;
+    runs.emplace_back(new ShuffledRun());
+    ShuffledRun &r = *runs.back();
+    r.p = c->plan;
+    r.seed = c->seed;
+    r.betas = segs[i].betas;
+    r.num_sweeps = segs[i].num_sweeps;
+    r.repetitions = c->repetitions;
+    r.replica_offset = c->replica_offset;
+    r.resume = c;
+    r.t0 = c->sweeps_done;
+    r.budget = std::max<uint64_t>(64ull << 20, std::min<uint64_t>(3ull << 30, budget / n));
+    if (!c->plan->shuffled_m) {
+      r.forced_m = m;
+      // (a cluster beyond the word layout in a batch that fills the chip: see sa_shuffled_batch)
+      if (saturates && c->plan->host.num_spins * 4ull > c->plan->max_lds * 15 / 16) r.forced_m = 8;
+    }
+    r.batch_saturates = saturates;
+    ASP_TRY(r.setup());
+  }
+  std::vector<bool> taken(runs.size(), false);
+  for (size_t i = 0; i < runs.size(); ++i) {
+    if (taken[i]) continue;
+    std::vector<ShuffledRun *> group;
+    for (size_t j = i; j < runs.size(); ++j) {
+      if (!taken[j] && runs[j]->num_sweeps == runs[i]->num_sweeps &&
+          shuffled_batch_kernel_for(runs[j]->m, kBytes, false)) {
+        group.push_back(runs[j].get());
+        taken[j] = true;
+      }
+    }
+    taken[i] = true;
+    if (group.size() >= 2) {
+      ASP_TRY(run_shuffled_group(group, sweep_ms));
+    } else {
+      // (a group of one all the same — its partners' geometry has no batched kernel: as above)
+      runs[i].reset();
+      ASP_TRY(alone(segs[shared[i]]));
+    }
+  }
+  for (auto &r : runs) {
+    if (r) ASP_TRY(r->finish_enqueue());
+  }
+  for (auto &r : runs) {
+    if (r) ASP_TRY(r->finish_wait());
+  }
+  return ASP_OK;
 }
 
 }  // namespace asp

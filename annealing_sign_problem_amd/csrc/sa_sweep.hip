@@ -44,6 +44,7 @@
 #include <cstdlib>
 #include <initializer_list>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "asp_common.hpp"
@@ -829,9 +830,20 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
   if constexpr (Res::kEnabled) {
     // the state the next segment starts from (the spins were last written before the final barriers)
     if (tid < M) res.e_cur[static_cast<uint64_t>(group) * M + tid] = book[tid];
-    SweepArgs fin = a;
-    fin.best_perm = res.cur_perm;
-    snapshot<M, LAYOUT>(spins, fin, group, (1u << M) - 1u);
+    if constexpr (std::is_same_v<Args, SweepArgs>) {
+      SweepArgs fin = a;
+      fin.best_perm = res.cur_perm;
+      snapshot<M, LAYOUT>(spins, fin, group, (1u << M) - 1u);
+    } else {
+      // (arguments in the constant address space, k_sa_sweep_resume_batch: what snapshot() reads of
+      // them, with the current words as the target; k_sa_sweep_resume keeps its code)
+      struct FinalWords {
+        uint64_t *best_perm;
+        uint32_t num_blocks;
+      };
+      const FinalWords fin{res.cur_perm, a.num_blocks};
+      snapshot<M, LAYOUT>(spins, fin, group, (1u << M) - 1u);
+    }
   }
 }
 
@@ -905,6 +917,33 @@ __global__ __launch_bounds__(kMaxThreads) void k_sa_descent_batch(DescentBatchAr
   using ConstProblem = const DescentProblem __attribute__((address_space(4)));
   ConstProblem *d = reinterpret_cast<ConstProblem *>(reinterpret_cast<uintptr_t>(b.problems + problem));
   sa_sweep_body<1, true, LAYOUT>(d->s, 0u, StopWhenStill{d->sweeps_done});
+}
+
+// Many SEGMENTS in one launch (asp_sa_chains_advance_batch, order 0): workgroup -> (handle, group of
+// M chains) through the slot table of k_sa_sweep_batch; every handle's SweepArgs and its Resume part
+// (its own sign words, tracked energies and sweep index base) in a wrapper read through the constant
+// address space, as DescentProblem is — SweepArgs stays as it is.  Every chain is the one
+// k_sa_sweep_resume advances: the body is the same.
+struct ResumeProblem {
+  SweepArgs s;  // trace: nullptr (a traced segment runs alone)
+  Resume r;
+};
+struct ResumeBatchArgs {
+  const ResumeProblem *problems;
+  const BatchSlot *slots;  // [8][slots_per_xcd]
+  uint32_t slots_per_xcd;
+};
+
+template <int M, int LAYOUT>
+__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_resume_batch(ResumeBatchArgs b) {
+  const BatchSlot slot = b.slots[(blockIdx.x & 7u) * b.slots_per_xcd + (blockIdx.x >> 3)];
+  const uint32_t problem = __builtin_amdgcn_readfirstlane(slot.problem);
+  if (problem == 0xFFFFFFFFu) return;
+  // (the constant address space: see k_sa_sweep_batch)
+  using ConstProblem = const ResumeProblem __attribute__((address_space(4)));
+  ConstProblem *d = reinterpret_cast<ConstProblem *>(reinterpret_cast<uintptr_t>(b.problems + problem));
+  sa_sweep_body<M, false, LAYOUT>(d->s, __builtin_amdgcn_readfirstlane(slot.group), NoEarlyStop{},
+                                  Resume{d->r.cur_perm, d->r.e_cur, d->r.t0});
 }
 
 // ---------------------------------------------------------------------------
@@ -1438,6 +1477,74 @@ __global__ __launch_bounds__(256) void k_permute_bits_problems(const DescentProb
       word |= (up ^ 1ull) << l;
     }
     d.x0_perm[b] = word;
+  }
+}
+
+// The handles of a batched segment (asp_sa_chains_advance_batch, order 0) into and out of the form
+// k_sa_sweep_resume_batch runs them in: what sa_chains_advance_colour does with two permute launches,
+// two unpermute launches and six copies PER HANDLE, for all handles in one launch each way.
+struct ChainsIo {
+  uint64_t *x_cur, *x_best;  // the handle: [chains][words], original order, bit = +1
+  long long *e_cur, *e_best;
+  unsigned long long *accepted;
+  uint64_t *cur_perm, *best_perm;  // the launch: [padded][num_blocks] sign words (bit = -1)
+  long long *w_e_cur, *w_tracked;  // [padded]
+  unsigned long long *w_accepted;
+  const uint32_t *spin_of_pos, *pos_of_spin;
+  uint64_t num_spins;
+  uint32_t num_blocks, words, chains;
+};
+// in: a workgroup per (handle, chain of the padded groups); the chains padding the last group start
+// with every spin up and integers 0, as in the single segment.
+__global__ __launch_bounds__(256) void k_chains_permute_problems(const ChainsIo *problems,
+                                                                const BatchSlot *chains) {
+  const BatchSlot c = chains[blockIdx.x];
+  const ChainsIo &io = problems[c.problem];
+  const uint64_t r = c.group;
+  const bool live = r < io.chains;
+  for (uint32_t b = threadIdx.x; b < io.num_blocks; b += blockDim.x) {
+    uint64_t cur = 0, best = 0;
+    if (live) {
+      for (uint32_t l = 0; l < 64; ++l) {
+        const uint32_t spin = io.spin_of_pos[b * 64u + l];
+        if (spin == kDummySpin) continue;
+        const uint64_t at = r * io.words + (spin >> 6);
+        cur |= (((io.x_cur[at] >> (spin & 63u)) & 1ull) ^ 1ull) << l;
+        best |= (((io.x_best[at] >> (spin & 63u)) & 1ull) ^ 1ull) << l;
+      }
+    }
+    io.cur_perm[r * io.num_blocks + b] = cur;
+    io.best_perm[r * io.num_blocks + b] = best;
+  }
+  if (threadIdx.x == 0) {
+    io.w_e_cur[r] = live ? io.e_cur[r] : 0ll;
+    io.w_tracked[r] = live ? io.e_best[r] : 0ll;
+    io.w_accepted[r] = live ? io.accepted[r] : 0ull;
+  }
+}
+// out: a workgroup per (handle, chain)
+__global__ __launch_bounds__(256) void k_chains_unpermute_problems(const ChainsIo *problems,
+                                                                  const BatchSlot *chains) {
+  const BatchSlot c = chains[blockIdx.x];
+  const ChainsIo &io = problems[c.problem];
+  const uint64_t r = c.group;
+  const uint64_t *cur = io.cur_perm + r * io.num_blocks, *best = io.best_perm + r * io.num_blocks;
+  for (uint32_t w = threadIdx.x; w < io.words; w += blockDim.x) {
+    uint64_t cur_word = 0, best_word = 0;
+    for (uint32_t j = 0; j < 64; ++j) {
+      const uint64_t spin = static_cast<uint64_t>(w) * 64u + j;
+      if (spin >= io.num_spins) break;
+      const uint32_t pos = io.pos_of_spin[spin];
+      cur_word |= (((cur[pos >> 6] >> (pos & 63u)) & 1ull) ^ 1ull) << j;
+      best_word |= (((best[pos >> 6] >> (pos & 63u)) & 1ull) ^ 1ull) << j;
+    }
+    io.x_cur[r * io.words + w] = cur_word;
+    io.x_best[r * io.words + w] = best_word;
+  }
+  if (threadIdx.x == 0) {
+    io.e_cur[r] = io.w_e_cur[r];
+    io.e_best[r] = io.w_tracked[r];
+    io.accepted[r] = io.w_accepted[r];
   }
 }
 
@@ -2349,6 +2456,29 @@ uint32_t widest_color(const asp::SaHostLayout &L) {
   return widest;
 }
 
+// What asp_sa_anneal_batch and the batched segments (sa_chains_advance_colour_batch) decide alike, in
+// one place: the wavefront counts of the launch classes, and the layout and wavefronts of a problem
+// that fits a byte per position (the thresholds are measured; see asp_sa_anneal_batch).
+constexpr uint32_t kBatchWaves[] = {1, 2, 3, 4, 6, 8, 12, 16};
+constexpr int kNumBatchWaves = sizeof kBatchWaves / sizeof kBatchWaves[0];
+constexpr uint64_t kBatchWideMax = 10000, kBatchSmallMax = 10000;
+
+int batch_waves_index(uint32_t waves) {
+  for (int c = 0; c < kNumBatchWaves; ++c) {
+    if (waves <= kBatchWaves[c]) return c;
+  }
+  return kNumBatchWaves - 1;
+}
+int batch_layout_in_lds(const asp_sa_plan *p) {  // kWide or kBytes
+  const asp::SaHostLayout &L = p->host;
+  return p->allow_wide && p->ell_col4.ptr && L.num_spins <= kBatchWideMax && sweep_lds_bytes(L, kWide) <= p->max_lds
+             ? kWide
+             : kBytes;
+}
+uint32_t batch_waves(const asp::SaHostLayout &L) {
+  return std::min<uint32_t>(widest_color(L), L.num_spins <= kBatchSmallMax ? 4u : 16u);
+}
+
 struct BatchEntry {
   uint32_t item;     // index into the caller's array
   uint32_t waves;    // wavefronts per workgroup this problem wants
@@ -2429,7 +2559,6 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
       alone.push_back(i);
       continue;
     }
-    const uint32_t widest = widest_color(L);
     BatchEntry e{};
     e.item = i;
     // Layout and wavefronts per workgroup in a shared launch.  Small problems — several
@@ -2438,14 +2567,9 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
     // 1e2..1e4 spins, 128 problems: 109 / 133 / 152 G flips/s, 512: 152 / 200 / 213).  Larger ones keep a byte per spin — the word layout would leave them
     // one workgroup per CU — and take 16 wavefronts (the sampled-cluster pipeline's order-2 models,
     // 1e4..2e5 spins, cap 4 / 8 / 16: 150 / 234 / 279 G flips/s; profiles/r03_batch_tune_real.txt).
-    const uint64_t wide_max = 10000, small_max = 10000;
-    e.layout = !bytes_fit ? (nibbles_fit ? kNibbles : kBits)
-                          : (p->allow_wide && p->ell_col4.ptr && L.num_spins <= wide_max &&
-                                     sweep_lds_bytes(L, kWide) <= p->max_lds
-                                 ? kWide
-                                 : kBytes);
-    const uint32_t cap = L.num_spins <= small_max ? 4u : 16u;
-    e.waves = std::min<uint32_t>(widest, cap);
+    // (kBatchWideMax, kBatchSmallMax: both 10000)
+    e.layout = !bytes_fit ? (nibbles_fit ? kNibbles : kBits) : batch_layout_in_lds(p);
+    e.waves = batch_waves(L);
     e.work = static_cast<double>(it.num_sweeps) * static_cast<double>(L.ell_off.back() + L.num_blocks);
     entries.push_back(e);
   }
@@ -2470,18 +2594,12 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
   const size_t max_lds = first->max_lds;
   // ---- size classes: workgroups of one launch have one thread count ----
   // A launch class = (wavefront count, spin layout): kWaves[c / 4] wavefronts, layout c % 4.
-  static const uint32_t kWaves[] = {1, 2, 3, 4, 6, 8, 12, 16};
+  const auto &kWaves = kBatchWaves;
   static const int kLayouts[] = {kWide, kBytes, kBits, kNibbles};
-  constexpr int kNumWaves = sizeof kWaves / sizeof kWaves[0];
+  constexpr int kNumWaves = kNumBatchWaves;
   constexpr int kNumClasses = 4 * kNumWaves;
   auto class_of = [&](const BatchEntry &e) {
-    int w = kNumWaves - 1;
-    for (int c = 0; c < kNumWaves; ++c) {
-      if (e.waves <= kWaves[c]) {
-        w = c;
-        break;
-      }
-    }
+    const int w = batch_waves_index(e.waves);
     return 4 * w + (e.layout == kWide ? 0 : (e.layout == kBytes ? 1 : (e.layout == kBits ? 2 : 3)));
   };
   auto waves_of_class = [&](int c) { return kWaves[c / 4]; };
@@ -2783,6 +2901,299 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Batched segments of resumable chains, colour order (asp_sa_chains_advance_batch)
+// ---------------------------------------------------------------------------
+// The launch grouping of asp_sa_anneal_batch — one launch per wavefront count and layout class (a
+// word or a byte per position), four or two chains per workgroup when that still fills the chip —
+// with k_sa_sweep_resume_batch in place of k_sa_sweep_batch, and the handles' state permuted in and
+// out by one launch each way.  Segments that need the bit-packed layouts, plans with a forced
+// geometry or layout, traced segments and a group of one run as sa_chains_advance_colour.
+// Two deliberate differences from the closed batch, whose helpers (kBatchWaves, batch_layout_in_lds,
+// batch_waves) this shares: a cluster beyond a byte per position runs alone here even where four bits
+// per position would fit (the nibble class has no resume form), and the closed batch's tuning aid
+// ASP_BATCH_M is not read (chains per workgroup never change a result).
+
+namespace asp {
+
+int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms) {
+  struct Entry {
+    uint32_t seg;
+    uint32_t waves;
+    int layout;  // kWide or kBytes
+    double work;
+    uint64_t beta_at;
+  };
+  std::vector<Entry> entries;
+  std::vector<uint32_t> alone;
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_plan *p = segs[i].chains->plan;
+    const SaHostLayout &L = p->host;
+    const bool bytes_fit = sweep_lds_bytes(L, kBytes) <= p->max_lds;
+    if (segs[i].trace || !bytes_fit || p->force_m || p->force_threads || p->force_packed) {
+      alone.push_back(i);
+      continue;
+    }
+    // (layout and wavefronts per workgroup in a shared launch: asp_sa_anneal_batch's, measured there)
+    Entry e{};
+    e.seg = i;
+    e.layout = batch_layout_in_lds(p);
+    e.waves = batch_waves(L);
+    e.work = static_cast<double>(segs[i].num_sweeps) * static_cast<double>(L.ell_off.back() + L.num_blocks);
+    entries.push_back(e);
+  }
+  if (entries.size() == 1) {
+    alone.push_back(entries[0].seg);
+    entries.clear();
+  }
+  for (uint32_t i : alone) {
+    asp_sa_plan *p = segs[i].chains->plan;
+    p->last_sweep_ms = p->last_total_ms = 0.0f;
+    ASP_TRY(sa_chains_advance_colour(segs[i].chains, segs[i].betas, segs[i].num_sweeps, segs[i].trace));
+    if (sweep_ms) *sweep_ms += p->last_sweep_ms;
+  }
+  if (entries.empty()) return ASP_OK;
+
+  const asp_sa_plan *first = segs[entries[0].seg].chains->plan;
+  const int num_cus = first->num_cus;
+  const auto &kWaves = kBatchWaves;
+  constexpr int kNumWaves = kNumBatchWaves;
+  constexpr int kNumClasses = 2 * kNumWaves;  // class = 2 * (index of the wavefront count) + (bytes ? 1 : 0)
+  auto waves_index = [&](const Entry &e) { return batch_waves_index(e.waves); };
+  // chains per workgroup for the batch: four — the word layout — or two when that still gives every
+  // SIMD a wavefront, else one (asp_sa_anneal_batch's rule)
+  int m = 1;
+  for (int cand : {4, 2}) {
+    uint64_t waves = 0;
+    for (const Entry &e : entries) {
+      const uint32_t reps = segs[e.seg].chains->repetitions;
+      waves += static_cast<uint64_t>((reps + cand - 1) / cand) * kWaves[waves_index(e)];
+    }
+    if (waves >= static_cast<uint64_t>(num_cus) * 4u) {
+      m = cand;
+      break;
+    }
+  }
+  for (Entry &e : entries) {
+    if (e.layout == kWide && m != 4) e.layout = kBytes;  // (the word layout exists for four chains)
+  }
+  auto class_of = [&](const Entry &e) { return 2 * waves_index(e) + (e.layout == kWide ? 0 : 1); };
+  // ---- per-handle offsets into the launch's buffers ----
+  struct Offsets {
+    uint64_t perm, stat, cache, groups, padded;
+  };
+  std::vector<Offsets> off(entries.size());
+  uint64_t n_perm = 0, n_stat = 0, n_cache = 0, n_betas = 0, n_chains = 0;
+  bool use_cache = true;
+  for (size_t k = 0; k < entries.size(); ++k) {
+    const asp_sa_chains *c = segs[entries[k].seg].chains;
+    const SaHostLayout &L = c->plan->host;
+    const uint64_t groups = (c->repetitions + static_cast<uint64_t>(m) - 1) / m, padded = groups * m;
+    off[k] = Offsets{n_perm, n_stat, n_cache, groups, padded};
+    n_perm += padded * L.num_blocks;
+    n_stat += padded;
+    n_cache += padded * L.num_blocks * 64ull;
+    n_chains += c->repetitions;
+    entries[k].beta_at = n_betas;
+    n_betas += segs[entries[k].seg].num_sweeps;
+    use_cache = use_cache && c->plan->use_field_cache;
+  }
+  if (n_cache * sizeof(double) > (32ull << 30)) use_cache = false;
+
+  ScopedStream main_stream;
+  ASP_TRY(main_stream.acquire());
+  hipStream_t s = main_stream.stream;
+  ScopedStream class_stream[kNumClasses];
+  DeviceBuffer<double> d_betas, d_cache;
+  DeviceBuffer<uint64_t> d_best, d_cur;
+  DeviceBuffer<long long> d_tracked, d_e_cur;
+  DeviceBuffer<unsigned long long> d_accepted;
+  DeviceBuffer<ResumeProblem> d_problems;
+  DeviceBuffer<ChainsIo> d_io;
+  DeviceBuffer<BatchSlot> d_slots, d_chains_in, d_chains_out;
+  StreamFence fence(s);
+  ASP_TRY(d_betas.alloc(n_betas));
+  ASP_TRY(d_best.alloc(n_perm));
+  ASP_TRY(d_cur.alloc(n_perm));
+  ASP_TRY(d_tracked.alloc(n_stat));
+  ASP_TRY(d_e_cur.alloc(n_stat));
+  ASP_TRY(d_accepted.alloc(n_stat));
+  if (use_cache && d_cache.alloc(n_cache) != ASP_OK) {
+    asp_clear_error();  // the cache is an optimisation: run without it
+    use_cache = false;
+  }
+  // ---- descriptors ----
+  std::vector<double> h_betas(n_betas);
+  std::vector<ResumeProblem> h_problems(entries.size());
+  std::vector<ChainsIo> h_io(entries.size());
+  std::vector<BatchSlot> h_chains_in, h_chains_out;
+  h_chains_in.reserve(n_stat);
+  h_chains_out.reserve(n_chains);
+  for (size_t k = 0; k < entries.size(); ++k) {
+    const ChainsSegment &seg = segs[entries[k].seg];
+    asp_sa_chains *c = seg.chains;
+    const asp_sa_plan *p = c->plan;
+    const SaHostLayout &L = p->host;
+    std::copy(seg.betas, seg.betas + seg.num_sweeps, h_betas.begin() + entries[k].beta_at);
+    ColourLaunch form;
+    form.wide = entries[k].layout == kWide;
+    ResumeProblem rp{};
+    rp.s = plan_sweep_args(p, form);
+    rp.s.betas = d_betas.ptr + entries[k].beta_at;
+    rp.s.x0_perm = nullptr;
+    rp.s.best_perm = d_best.ptr + off[k].perm;
+    rp.s.tracked = d_tracked.ptr + off[k].stat;
+    rp.s.accepted = d_accepted.ptr + off[k].stat;
+    rp.s.seed = c->seed;
+    rp.s.num_sweeps = seg.num_sweeps;
+    rp.s.replica_first = c->replica_offset;
+    rp.s.field_cache = use_cache ? d_cache.ptr + off[k].cache : nullptr;
+    rp.s.cache_enter_flips = cache_enter_flips_of(L);
+    rp.s.trace = nullptr;
+    rp.r = Resume{d_cur.ptr + off[k].perm, d_e_cur.ptr + off[k].stat, c->sweeps_done};
+    h_problems[k] = rp;
+    ChainsIo io{};
+    io.x_cur = c->x_cur.ptr;
+    io.x_best = c->x_best.ptr;
+    io.e_cur = c->e_cur.ptr;
+    io.e_best = c->e_best.ptr;
+    io.accepted = c->accepted.ptr;
+    io.cur_perm = rp.r.cur_perm;
+    io.best_perm = rp.s.best_perm;
+    io.w_e_cur = rp.r.e_cur;
+    io.w_tracked = rp.s.tracked;
+    io.w_accepted = rp.s.accepted;
+    io.spin_of_pos = p->spin_of_pos.ptr;
+    io.pos_of_spin = p->pos_of_spin.ptr;
+    io.num_spins = L.num_spins;
+    io.num_blocks = L.num_blocks;
+    io.words = c->words;
+    io.chains = c->repetitions;
+    h_io[k] = io;
+    for (uint32_t r = 0; r < off[k].padded; ++r) h_chains_in.push_back(BatchSlot{static_cast<uint32_t>(k), r});
+    for (uint32_t r = 0; r < c->repetitions; ++r) h_chains_out.push_back(BatchSlot{static_cast<uint32_t>(k), r});
+  }
+  // ---- slot tables: per class, handles longest first, dealt to the 8 XCDs (asp_sa_anneal_batch) ----
+  struct ClassLaunch {
+    uint64_t slot_at = 0;
+    uint32_t slots_per_xcd = 0;
+    size_t lds = 0;
+    bool used = false;
+  };
+  ClassLaunch launches[kNumClasses];
+  std::vector<BatchSlot> h_slots;
+  for (int cl = 0; cl < kNumClasses; ++cl) {
+    std::vector<size_t> members;
+    for (size_t k = 0; k < entries.size(); ++k) {
+      if (class_of(entries[k]) == cl) members.push_back(k);
+    }
+    if (members.empty()) continue;
+    std::stable_sort(members.begin(), members.end(),
+                     [&](size_t a, size_t b) { return entries[a].work > entries[b].work; });
+    std::vector<BatchSlot> per_xcd[8];
+    uint64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t k : members) {
+      int x = 0;
+      for (int j = 1; j < 8; ++j) {
+        if (load[j] < load[x]) x = j;
+      }
+      for (uint32_t g = 0; g < off[k].groups; ++g) per_xcd[x].push_back(BatchSlot{static_cast<uint32_t>(k), g});
+      load[x] += off[k].groups;
+      launches[cl].lds = std::max(launches[cl].lds, sweep_lds_bytes(segs[entries[k].seg].chains->plan->host,
+                                                                    cl % 2 == 0 ? kWide : kBytes));
+    }
+    uint32_t most = 0;
+    for (int x = 0; x < 8; ++x) most = std::max<uint32_t>(most, static_cast<uint32_t>(per_xcd[x].size()));
+    launches[cl].used = true;
+    launches[cl].slot_at = h_slots.size();
+    launches[cl].slots_per_xcd = most;
+    for (int x = 0; x < 8; ++x) {
+      per_xcd[x].resize(most, BatchSlot{0xFFFFFFFFu, 0});
+      h_slots.insert(h_slots.end(), per_xcd[x].begin(), per_xcd[x].end());
+    }
+  }
+  ASP_TRY(d_problems.alloc(h_problems.size()));
+  ASP_TRY(d_io.alloc(h_io.size()));
+  ASP_TRY(d_slots.alloc(h_slots.size()));
+  ASP_TRY(d_chains_in.alloc(h_chains_in.size()));
+  ASP_TRY(d_chains_out.alloc(h_chains_out.size()));
+  ASP_TRY(d_betas.upload(h_betas.data(), h_betas.size(), s));
+  ASP_TRY(d_problems.upload(h_problems.data(), h_problems.size(), s));
+  ASP_TRY(d_io.upload(h_io.data(), h_io.size(), s));
+  ASP_TRY(d_slots.upload(h_slots.data(), h_slots.size(), s));
+  ASP_TRY(d_chains_in.upload(h_chains_in.data(), h_chains_in.size(), s));
+  ASP_TRY(d_chains_out.upload(h_chains_out.data(), h_chains_out.size(), s));
+  hipLaunchKernelGGL(k_chains_permute_problems, dim3(static_cast<unsigned>(h_chains_in.size())), dim3(256), 0, s,
+                     d_io.ptr, d_chains_in.ptr);
+  ASP_HIP_TRY(hipGetLastError());
+  hipEvent_t ev[2 + kNumClasses] = {};
+  struct EventGuard {
+    hipEvent_t *ev;
+    int n;
+    ~EventGuard() {
+      for (int i = 0; i < n; ++i) {
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+      }
+    }
+  } event_guard{ev, 2 + kNumClasses};
+  for (auto &e : ev) ASP_HIP_TRY(hipEventCreate(&e));
+  ASP_HIP_TRY(hipEventRecord(ev[0], s));
+  // ---- one sweep launch per class, each on its own stream so that they share the chip ----
+  using Kernel = void (*)(ResumeBatchArgs);
+  Kernel kernel_of_layout[2] = {k_sa_sweep_resume_batch<4, kWide>, nullptr};  // [class % 2]
+  switch (m) {
+    case 1: kernel_of_layout[1] = k_sa_sweep_resume_batch<1, kBytes>; break;
+    case 2: kernel_of_layout[1] = k_sa_sweep_resume_batch<2, kBytes>; break;
+    default: kernel_of_layout[1] = k_sa_sweep_resume_batch<4, kBytes>; break;
+  }
+  // (a kernel serves every wavefront class of its layout, on streams that run side by side: its
+  // dynamic LDS limit is set once, to the largest of them, before the first launch)
+  for (int layout = 0; layout < 2; ++layout) {
+    size_t most_lds = 0;
+    for (int cl = layout; cl < kNumClasses; cl += 2) {
+      if (launches[cl].used) most_lds = std::max(most_lds, launches[cl].lds);
+    }
+    if (most_lds > 64 * 1024) {
+      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel_of_layout[layout]),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(most_lds)));
+    }
+  }
+  for (int cl = 0; cl < kNumClasses; ++cl) {
+    if (!launches[cl].used) continue;
+    ASP_TRY(class_stream[cl].acquire());
+    hipStream_t cs = class_stream[cl].stream;
+    ASP_HIP_TRY(hipStreamWaitEvent(cs, ev[0], 0));
+    ResumeBatchArgs b{d_problems.ptr, d_slots.ptr + launches[cl].slot_at, launches[cl].slots_per_xcd};
+    const Kernel kernel = kernel_of_layout[cl % 2];
+    hipLaunchKernelGGL(kernel, dim3(8u * launches[cl].slots_per_xcd), dim3(64u * kWaves[cl / 2]),
+                       launches[cl].lds, cs, b);
+    ASP_HIP_TRY(hipGetLastError());
+    ASP_HIP_TRY(hipEventRecord(ev[2 + cl], cs));
+    ASP_HIP_TRY(hipStreamWaitEvent(s, ev[2 + cl], 0));
+  }
+  ASP_HIP_TRY(hipEventRecord(ev[1], s));
+  // ---- the state back into the handles (after the attempt: the colour order has no retry) ----
+  hipLaunchKernelGGL(k_chains_unpermute_problems, dim3(static_cast<unsigned>(h_chains_out.size())), dim3(256), 0, s,
+                     d_io.ptr, d_chains_out.ptr);
+  ASP_HIP_TRY(hipGetLastError());
+  ASP_HIP_TRY(hipStreamSynchronize(s));
+  float ms = 0.0f;
+  ASP_HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  if (sweep_ms) *sweep_ms += ms;
+  for (size_t k = 0; k < entries.size(); ++k) {
+    asp_sa_plan *p = segs[entries[k].seg].chains->plan;
+    const int cl = class_of(entries[k]);
+    p->last_m = m;
+    p->last_layout = cl % 2 == 0 ? kWide : kBytes;
+    p->last_threads = static_cast<int>(64u * kWaves[cl / 2]);
+    p->last_groups = static_cast<int>(off[k].groups);
+    p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_chains_batch_last_ms
+  }
+  return ASP_OK;
+}
+
+}  // namespace asp
 
 // ---------------------------------------------------------------------------
 // Batched greedy solve: many problems' descents in shared launches

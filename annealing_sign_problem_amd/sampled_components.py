@@ -268,15 +268,24 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
     return solved([entry for item in enumerate(clusters) for entry in stage(item)])
 
 
+def early_stop_of(args) -> dict:
+    """--anneal-patience / --anneal-check-every as the ``early_stop`` keyword of :func:`anneal_staged`
+    and :func:`process_clusters_batched`; empty without them, so that every call is the one it was."""
+    if getattr(args, "anneal_patience", None) is None:
+        return {}
+    return {"early_stop": {"patience": args.anneal_patience, "check_every": args.anneal_check_every}}
+
+
 def anneal_staged(staged, clusters: Sequence[np.ndarray], annealing: bool,
-                  sweep_order: Optional[str] = None) -> List[List[OptimizationResult]]:
+                  sweep_order: Optional[str] = None,
+                  early_stop: Optional[dict] = None) -> List[List[OptimizationResult]]:
     """Second half: the annealing of ALL staged models — every cluster at every order — in one
     batched device call, scored and sorted back into one list of results per cluster."""
     if annealing and staged:
         started = time.perf_counter()
         solutions = common.solve_ising_models([m for _, m, _, _, _ in staged],
                                               [clusters[c] for c, _, _, _, _ in staged],
-                                              sweep_order=sweep_order)
+                                              sweep_order=sweep_order, **(early_stop or {}))
         if os.environ.get("ASP_PIPELINE_TIMING"):  # development aid
             spins = sum(m.size for _, m, _, _, _ in staged)
             seconds = time.perf_counter() - started
@@ -297,13 +306,14 @@ def process_clusters_batched(clusters: Sequence[np.ndarray], hamiltonian, ground
                              noisy_ground_state, noisy_log_coeff_fn, order: int,
                              global_cutoff: float, annealing: bool, jobs: int = 1,
                              sweep_order: Optional[str] = None,
-                             greedy_batch: bool = False) -> List[List[OptimizationResult]]:
+                             greedy_batch: bool = False,
+                             early_stop: Optional[dict] = None) -> List[List[OptimizationResult]]:
     """``[process_cluster(c, ...) for c in clusters]`` with the annealing of ALL models — every
     cluster at every order — in one batched device call (:func:`stage_clusters`, then
     :func:`anneal_staged`); the results are identical to the per-cluster loop."""
     staged = stage_clusters(clusters, hamiltonian, ground_state, noisy_ground_state, noisy_log_coeff_fn,
                             order, global_cutoff, jobs, **({"greedy_batch": True} if greedy_batch else {}))
-    return anneal_staged(staged, clusters, annealing, sweep_order)
+    return anneal_staged(staged, clusters, annealing, sweep_order, **({"early_stop": early_stop} if early_stop else {}))
 
 
 def parse_command_line(argv=None):
@@ -333,6 +343,12 @@ def parse_command_line(argv=None):
                         help="clusters whose annealing chains share one batched device call "
                              "(asp_sa_anneal_batch); 1 = one call per model, as the reference's "
                              "loop.  The output does not depend on it")
+    parser.add_argument("--anneal-patience", type=int, default=None, metavar="N",
+                        help="stop a model's annealing once none of its chains improved for N consecutive "
+                             "segments (batched annealing, --batch > 1; asp_sa_chains_advance_batch).  Off "
+                             "by default: early stopping changes the results")
+    parser.add_argument("--anneal-check-every", type=int, default=None, metavar="S",
+                        help="sweeps per segment of --anneal-patience (default 512)")
     parser.add_argument("--sweep-order", type=str, default="shuffled", choices=["colour", "shuffled"],
                         help="visiting order of the annealing sweeps: 'shuffled' (default: a fresh "
                              "random order every sweep, the reference annealer's statistics) or "
@@ -351,7 +367,15 @@ def parse_command_line(argv=None):
     parser.add_argument("--jobs", type=int, default=1,
                         help="host threads building / solving clusters concurrently (independent "
                              "plans and HIP streams on one GPU; the output does not depend on it)")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.anneal_check_every is not None and args.anneal_patience is None:
+        parser.error("--anneal-check-every needs --anneal-patience")
+    if args.anneal_patience is not None:
+        if args.anneal_patience < 1 or (args.anneal_check_every is not None and args.anneal_check_every < 1):
+            parser.error("--anneal-patience and --anneal-check-every must be positive")
+        if not args.annealing or args.batch <= 1:
+            parser.error("--anneal-patience needs --annealing and --batch > 1 (it stops batched segments)")
+    return args
 
 
 def load_input(args):
@@ -523,7 +547,8 @@ def _worker_chunk(indices):
         chunk = process_clusters_batched(some, w["hamiltonian"], w["ground_state"], w["noisy_ground_state"],
                                          w["log_coeff_fn"], args.order, args.global_cutoff, args.annealing,
                                          jobs=args.jobs, sweep_order=args.sweep_order,
-                                         **({"greedy_batch": True} if args.greedy_batch else {}))
+                                         **({"greedy_batch": True} if args.greedy_batch else {}),
+                                         **early_stop_of(args))
         return report([",".join(r.to_csv_str() for r in columns) for columns in chunk])
 
     def work(cluster):
@@ -715,7 +740,8 @@ def _main_in_group(args, asp_dist, created_group, phase):
             chunk = process_clusters_batched(some[start:start + args.batch], hamiltonian,
                                              ground_state, noisy_ground_state, noisy_log_coeff_fn,
                                              args.order, args.global_cutoff, args.annealing,
-                                             jobs=args.jobs, sweep_order=args.sweep_order, **greedy_batch)
+                                             jobs=args.jobs, sweep_order=args.sweep_order, **greedy_batch,
+                                             **early_stop_of(args))
             lines += [",".join(r.to_csv_str() for r in columns) for columns in chunk]
         return lines
 
@@ -756,7 +782,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
 
                     def solve(some, staged=staged):  # (`some` is this rank's share of the round)
                         return [",".join(x.to_csv_str() for x in columns)
-                                for columns in anneal_staged(staged, some, True, args.sweep_order)]
+                                for columns in anneal_staged(staged, some, True, args.sweep_order, **early_stop_of(args))]
 
                     lines = asp_dist.map_sharded_many(rounds[r], solve)
                     if writer:
@@ -809,7 +835,8 @@ def _main_in_group(args, asp_dist, created_group, phase):
                     if not some:
                         break
                     upcoming = builder.submit(next_round)
-                    append(lines_of(anneal_staged(staged, some, args.annealing, args.sweep_order)))
+                    append(lines_of(anneal_staged(staged, some, args.annealing, args.sweep_order,
+                                                  **early_stop_of(args))))
         else:
             while True:
                 some = list(itertools.islice(clusters, step))

@@ -551,6 +551,45 @@ typedef struct asp_sa_chains_snapshot {
 int asp_sa_chains_export(asp_sa_chains *c, asp_sa_chains_snapshot *s);
 int asp_sa_chains_import(asp_sa_chains *c, asp_sa_chains_snapshot const *s);  /* all five arrays required */
 
+/* MANY handles advanced in one call ("Batched segments") — early stopping,
+ * checkpointing and re-heating for the production shape, many small clusters at once.  Item i is exactly
+ * asp_sa_chains_advance(chains, betas, num_sweeps, order, out_trace): afterwards every handle holds the
+ * same five state arrays and sweeps_done, bit for bit, for any composition and order of the batch and
+ * however the items differ in num_sweeps, order, sweeps_done, repetitions, seed or replica offset; the
+ * continuation law extends to batched segments, and single and batched segments may alternate on one
+ * handle.  The handles that fit share launches the way asp_sa_anneal_batch's problems do: order 1 —
+ * segments of equal length in the shared order and sweep launches of the closed batch, every handle
+ * with its own first sweep index; order 0 — one launch per wavefront count and layout class.  State goes
+ * in and out of all handles in one launch per direction and state type, not per handle.  Traced items,
+ * plans with a forced geometry or layout, clusters beyond a byte per position (order 0) and a group of
+ * one take asp_sa_chains_advance's path inside the call.
+ *  - out_tracked_best / out_improved: what asp_sa_chains_export before and after the segment would
+ *    tell — every chain's tracked_best after it, and the number of chains whose tracked_best fell
+ *    strictly during it — gathered for the whole batch by one small kernel and one copy (no export per
+ *    handle).  Items with num_sweeps = 0 get their outputs too, improved = 0.
+ *  - All items are validated before any device work and before any output is written;
+ *    ASP_ERR_INVALID with the item's index in the message: null items with count > 0, a null handle,
+ *    null betas with num_sweeps > 0, a negative or NaN beta, an order above 1, non-zero flags, the same
+ *    handle twice, two handles of one plan (a plan's work buffers serve one segment at a time),
+ *    sweeps_done + num_sweeps > 2^32 - 2.  count = 0 needs no device; handles with no chains or no
+ *    spins are fine.
+ *  - Any OTHER error (a device or allocation failure after validation) leaves the handles of the batch
+ *    UNDEFINED: some may hold the state after their segment while sweeps_done still counts the sweeps
+ *    before it.  Import a snapshot into them, or destroy them; handles outside the batch are untouched. */
+typedef struct asp_sa_chains_item {
+  asp_sa_chains *chains;
+  double const *betas;        /* num_sweeps values */
+  uint32_t num_sweeps;
+  uint32_t order;             /* 0 colour, 1 shuffled */
+  uint32_t flags;             /* 0; anything else is ASP_ERR_INVALID */
+  int64_t *out_trace;         /* NULL, or HOST [repetitions][num_sweeps + 1] as in asp_sa_chains_advance */
+  int64_t *out_tracked_best;  /* NULL, or HOST [repetitions]: tracked_best after the segment */
+  uint32_t *out_improved;     /* NULL, or one word: chains whose tracked_best fell strictly in this segment */
+} asp_sa_chains_item;
+int asp_sa_chains_advance_batch(asp_sa_chains_item const *items, uint32_t count);
+/* Device time (ms) of the sweep launches of this thread's last asp_sa_chains_advance_batch call. */
+float asp_sa_chains_batch_last_ms(void);
+
 /* MANY independent problems in one call — the shape of the reference's production job: tens of
  * thousands of sampled clusters, each solved with 64 repetitions x 5120 sweeps
  * (Makefile:9,115-127; experiments/sampled_connected_components.py:764-767; common.py:236-239).

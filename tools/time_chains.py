@@ -11,6 +11,14 @@ between the handle and the work buffers), median and spread over --repeat runs a
 segmented run is compared with the closed call bit for bit first.  With ASP_LIB_TAG set (and
 ASP_NO_REBUILD=1) the library is an older tagged build without the handle: only the closed call is
 timed — the yardstick of the same session.  Output goes to profiles/chains_timing.txt by hand.
+
+    python tools/time_chains.py --batch 64 [--size 3000] [--chains 64] [--sweeps 5120] [--segment 512]
+
+Batch mode (asp_sa_chains_advance_batch): --batch handles of distinct planted clusters of --size spins,
+the ladder in segments of --segment sweeps, (a) all handles per segment in one advance_chains call,
+(b) the same handles advanced one by one (the only route before the batched call), (c) the closed
+asp_sa_anneal_batch on the same problems; wall times, in both orders, (a) and (b) checked against (c)
+bit for bit.
 """
 import argparse
 import os
@@ -30,15 +38,62 @@ def spread(values):
     return "%9.2f ms (min %.2f, max %.2f)" % (statistics.median(values), min(values), max(values))
 
 
+def batch_mode(a):
+    problems = [synthetic.planted_cluster(a.size, seed=1000 + k)[:2] for k in range(a.batch)]
+    hams = [sa.Hamiltonian(J, h) for J, h in problems]
+    ladders = [sa.make_schedule(h.info().beta0_auto, h.info().beta1_auto, a.sweeps) for h in hams]
+    print("batch of %d clusters, K=%d chains=%d sweeps=%d segments of %d repeat=%d" % (
+        a.batch, a.size, a.chains, a.sweeps, a.segment, a.repeat), flush=True)
+    for order in a.orders.split(","):
+        shuffled = order == "shuffled"
+        timings = {"c closed batch": [], "a batched segments": [], "b one handle at a time": []}
+        for k in range(a.repeat + 1):
+            t0 = time.perf_counter()
+            closed = sa.anneal_batch_raw(hams, [1] * a.batch, ladders, [a.chains] * a.batch, shuffled=shuffled)
+            wall_c = (time.perf_counter() - t0) * 1e3
+            walls = {}
+            for name in ("a batched segments", "b one handle at a time"):
+                t0 = time.perf_counter()
+                handles = [sa.Chains(h, seed=1, repetitions=a.chains) for h in hams]
+                for first in range(0, a.sweeps, a.segment):
+                    parts = [ladder[first:first + a.segment] for ladder in ladders]
+                    if name.startswith("a"):
+                        sa.advance_chains(handles, parts, sweep_order=order, progress=True)
+                    else:
+                        for c, part in zip(handles, parts):
+                            c.advance(part, sweep_order=order)
+                results = [c.result() for c in handles]
+                for c in handles:
+                    c.close()
+                walls[name] = (time.perf_counter() - t0) * 1e3
+                for (xs, es), (cxs, ces) in zip(results, closed):
+                    if not (np.array_equal(xs, cxs) and es.tobytes() == ces.tobytes()):
+                        raise SystemExit("%s, %s: NOT the closed batch's chains" % (order, name))
+            if k:  # (the first round warms up)
+                timings["c closed batch"].append(wall_c)
+                for name, wall in walls.items():
+                    timings[name].append(wall)
+        for name in ("a batched segments", "b one handle at a time", "c closed batch"):
+            print("%-8s (%s): wall %s" % (order, name, spread(timings[name])), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--size", type=int, default=10000)
+    p.add_argument("--batch", type=int, default=0, help="batch mode: this many handles (see the module's text)")
+    p.add_argument("--segment", type=int, default=512)
+    p.add_argument("--size", type=int, default=None, help="spins (default 10000; batch mode 3000)")
     p.add_argument("--chains", type=int, default=64)
     p.add_argument("--sweeps", type=int, default=5120)
     p.add_argument("--segments", default="1,10,80")
     p.add_argument("--repeat", type=int, default=3)
     p.add_argument("--orders", default="colour,shuffled")
     a = p.parse_args()
+    if a.batch:
+        a.size = 3000 if a.size is None else a.size
+        _lib.load()
+        print("library %s fingerprint %s" % (os.path.basename(_lib.library_path()), build.built_fingerprint()))
+        return batch_mode(a)
+    a.size = 10000 if a.size is None else a.size
     lib = _lib.load()
     has_chains = hasattr(lib, "asp_sa_chains_create")
     print("library %s fingerprint %s%s" % (os.path.basename(_lib.library_path()), build.built_fingerprint(),
