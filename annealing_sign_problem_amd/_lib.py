@@ -111,6 +111,21 @@ class SaChainsItem(ctypes.Structure):
     ]
 
 
+class SaChainsResampleItem(ctypes.Structure):
+    """Mirror of ``asp_sa_chains_resample_item`` (include/asp.h)."""
+
+    _fields_ = [
+        ("chains", c_void_p),
+        ("dbeta", c_double),
+        ("draw", c_u32),
+        ("flags", c_u32),
+        ("out_source", c_void_p),
+        ("out_energy", c_void_p),
+        ("out_q", c_void_p),
+        ("out_survivors", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/asp.h declares
 SIGNATURES = {
     "asp_last_error": (ctypes.c_char_p, []),
@@ -199,6 +214,10 @@ SIGNATURES = {
     "asp_sa_chains_import": (c_int, [c_void_p, ctypes.POINTER(SaChainsSnapshot)]),
     "asp_sa_chains_advance_batch": (c_int, [ctypes.POINTER(SaChainsItem), c_u32]),
     "asp_sa_chains_batch_last_ms": (c_float, []),
+    "asp_sa_chains_gather": (c_int, [c_void_p, c_void_p]),
+    "asp_sa_chains_resample": (c_int, [c_void_p, c_double, c_u32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "asp_sa_chains_resample_batch": (c_int, [ctypes.POINTER(SaChainsResampleItem), c_u32]),
+    "asp_sa_chains_resample_last_ms": (c_float, []),
     "asp_sa_anneal_batch": (c_int, [ctypes.POINTER(SaBatchItem), c_u32]),
     "asp_sa_batch_last_ms": (c_float, []),
     "asp_sa_greedy": (c_int, [c_void_p, c_u32, c_void_p, c_void_p, ctypes.POINTER(c_u32)]),

@@ -37,6 +37,9 @@ __all__ = [
     "anneal_traces",
     "anneal_until",
     "Chains",
+    "resample_chains",
+    "population_anneal",
+    "population_anneal_batch",
     "greedy_solve",
     "greedy_solve_batch",
     "signs_to_bits",
@@ -581,6 +584,26 @@ class Chains:
         snap.sweeps_done = sweeps_done
         _lib.check(_lib.load().asp_sa_chains_import(self._live(), ctypes.byref(snap)))
 
+    def gather(self, source) -> None:
+        """Slot ``j`` of all five state arrays becomes slot ``source[j]`` (``asp_sa_chains_gather``,
+        DESIGN.md §4.11) — what ``load_state`` of the fancy-indexed ``state()`` does, on the device.
+        Any map of ``repetitions`` entries below ``repetitions``: repeats, cycles, a reversal."""
+        source = np.asarray(source)
+        if source.shape != (self.repetitions,) or source.dtype.kind not in "iu":
+            raise ValueError("'source' must hold {} chain indices".format(self.repetitions))
+        if np.any(source < 0) or np.any(source >= 2**32):
+            raise ValueError("'source' must hold chain indices")
+        source = np.ascontiguousarray(source, dtype=np.uint32)
+        _lib.check(_lib.load().asp_sa_chains_gather(self._live(), _lib.ptr(source)))
+
+    def resample(self, dbeta: float, draw: int = 0):
+        """One population-annealing step (law ASP-PA-1): the chains are weighted by
+        ``exp(-dbeta * E)`` of their current configurations and resampled systematically on the
+        device.  Returns ``(source uint32[R], energies float64[R], survivors)``: the chain every slot
+        was taken from, the energies before the step and the number of distinct sources.  ``draw``
+        picks the random offset (a Philox counter word), for more than one step at one sweep count."""
+        return resample_chains([self], [dbeta], [draw])[0]
+
     def close(self) -> None:
         """Destroy the device handle now."""
         if self._handle is not None:
@@ -750,6 +773,105 @@ def anneal_batch_until(hamiltonians, seed=None, number_sweeps: int = 5120, repet
         for c in handles:
             c.close()
     return results
+
+
+def resample_chains(chains, dbetas, draws=0):
+    """``chains[i].resample(dbetas[i], draws[i])`` for every ``i`` in ONE device call
+    (``asp_sa_chains_resample_batch``): the same bits, but weights, selection and the
+    gather of all handles share launches and every output comes back in one copy.  ``chains``:
+    ``Chains`` of distinct Hamiltonians; ``dbetas`` and ``draws``: one value for all or one per handle.
+    Returns ``[(source, energies, survivors), ...]``."""
+    chains = list(chains)
+    n = len(chains)
+    for c in chains:
+        if not isinstance(c, Chains):
+            raise TypeError("'chains' must hold Chains objects")
+    dbetas = [float(dbetas)] * n if np.ndim(dbetas) == 0 else [float(d) for d in dbetas]
+    draws = [int(draws)] * n if np.ndim(draws) == 0 else [int(d) for d in draws]
+    if not (len(dbetas) == len(draws) == n):
+        raise ValueError("resample_chains: %d handles, %d steps and %d draws" % (n, len(dbetas), len(draws)))
+    if any(not 0 <= d < 2**32 for d in draws):
+        raise ValueError("'draws' must fit 32 bits")
+    items = (_lib.SaChainsResampleItem * max(n, 1))()
+    out = []  # (also keeps the output buffers alive over the call)
+    for i, c in enumerate(chains):
+        source = np.zeros(c.repetitions, dtype=np.uint32)
+        energies = np.zeros(c.repetitions, dtype=np.float64)
+        survivors = ctypes.c_uint32(0)
+        items[i].chains = c._live()
+        items[i].dbeta = dbetas[i]
+        items[i].draw = draws[i]
+        items[i].flags = 0
+        items[i].out_source = source.ctypes.data
+        items[i].out_energy = energies.ctypes.data
+        items[i].out_survivors = ctypes.addressof(survivors)
+        out.append((source, energies, survivors))
+    _lib.check(_lib.load().asp_sa_chains_resample_batch(items, ctypes.c_uint32(n)))
+    return [(source, energies, int(survivors.value)) for source, energies, survivors in out]
+
+
+def population_anneal_batch(hamiltonians, seed=None, number_steps: int = 512, sweeps_per_step: int = 10,
+                            beta0: Optional[float] = None, beta1: Optional[float] = None, repetitions: int = 64,
+                            only_best: bool = True, sweep_order: Optional[str] = None, resample: bool = True):
+    """``[population_anneal(h, seed=seed, ...) for h in hamiltonians]`` with every step of all problems
+    in one ``advance_chains`` call and one ``resample_chains`` call — identical results.  ``seed`` as
+    in ``anneal_batch``.  Chains stay on this rank."""
+    order = resolve_sweep_order(sweep_order)  # (first: a bad order fails without a GPU)
+    number_steps, sweeps_per_step = int(number_steps), int(sweeps_per_step)
+    if number_steps < 1 or sweeps_per_step < 1:
+        raise ValueError("'number_steps' and 'sweeps_per_step' must be positive")
+    hamiltonians = list(hamiltonians)
+    n = len(hamiltonians)
+    for h in hamiltonians:
+        if not isinstance(h, Hamiltonian):
+            raise TypeError("'hamiltonians' must hold Hamiltonian objects")
+    if len({id(h) for h in hamiltonians}) != n:
+        raise ValueError("population_anneal_batch: every problem needs its own Hamiltonian object")
+    repetitions = int(repetitions)
+    if repetitions < 1:
+        raise ValueError("'repetitions' must be positive")
+    if seed is None or np.ndim(seed) == 0:
+        seeds = [_resolve_seed(seed) for _ in range(n)] if seed is None else [_resolve_seed(seed)] * n
+    else:
+        seeds = [_resolve_seed(x) for x in seed]
+    ladders = []
+    for h in hamiltonians:
+        b0, b1 = beta0, beta1
+        if b0 is None or b1 is None:
+            info = h.info()
+            b0 = info.beta0_auto if b0 is None else b0
+            b1 = info.beta1_auto if b1 is None else b1
+        ladders.append(make_schedule(float(b0), float(b1), number_steps))
+    handles = []
+    try:
+        for h, s in zip(hamiltonians, seeds):
+            handles.append(Chains(h, seed=s, repetitions=repetitions))
+        for k in range(number_steps):
+            if resample and k >= 1:
+                resample_chains(handles, [ladder[k] - ladder[k - 1] for ladder in ladders], 0)
+            advance_chains(handles, [np.full(sweeps_per_step, ladder[k]) for ladder in ladders], sweep_order=order)
+        results = [c.result(only_best=only_best) for c in handles]
+    finally:
+        for c in handles:
+            c.close()
+    return results
+
+
+def population_anneal(hamiltonian: Hamiltonian, seed=None, number_steps: int = 512, sweeps_per_step: int = 10,
+                      beta0: Optional[float] = None, beta1: Optional[float] = None, repetitions: int = 64,
+                      only_best: bool = True, sweep_order: Optional[str] = None, resample: bool = True):
+    """Population annealing: ``repetitions`` chains visit the temperatures
+    ``np.geomspace(beta0, beta1, number_steps)`` (the automatic defaults of ``anneal``) with
+    ``sweeps_per_step`` sweeps at each, and before every step but the first they are reweighted by
+    ``exp(-(beta_k - beta_{k-1}) E)`` and resampled on the device (``Chains.resample``, draw 0), so that
+    low-energy chains are cloned into the slots of high-energy ones — the same sweeps as ``anneal``
+    with ``number_steps * sweeps_per_step`` of them.  Returns what ``anneal`` returns.
+    ``resample=False`` is exactly ``anneal`` on the schedule ``np.repeat(temperatures,
+    sweeps_per_step)`` (the continuation law, §4.10).  Chains stay on this rank."""
+    if not isinstance(hamiltonian, Hamiltonian):
+        raise TypeError("'hamiltonian' must be a Hamiltonian")
+    return population_anneal_batch([hamiltonian], seed, number_steps, sweeps_per_step, beta0, beta1, repetitions,
+                                   only_best, sweep_order, resample)[0]
 
 
 def anneal_with_traces(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: int = 5120,

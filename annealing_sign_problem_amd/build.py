@@ -38,6 +38,7 @@ SOURCES = [
     "sa_sweep.hip",
     "sa_shuffled.hip",
     "sa_chains.hip",
+    "sa_population.hip",
 ]
 
 # -ffp-contract=off: the parity contract needs every multiply/add rounded on its

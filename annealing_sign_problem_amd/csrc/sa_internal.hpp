@@ -69,7 +69,8 @@ struct asp_sa_plan {
 
 // The chains behind asp_sa_chains_create: everything a continuation needs, on the
 // device and independent of the sweep order and of every launch choice — configurations packed in
-// ORIGINAL spin order (bit = +1) and three integers per chain.  Sized once, at create.
+// ORIGINAL spin order (bit = +1) and three integers per chain.  Sized once, at create (the second set
+// below: at the handle's first gather).
 struct asp_sa_chains {
   asp_sa_plan *plan = nullptr;
   uint64_t seed = 0;
@@ -79,6 +80,11 @@ struct asp_sa_chains {
   asp::DeviceBuffer<long long> e_cur, e_best;       // [repetitions] tracked energies (fixed point)
   asp::DeviceBuffer<unsigned long long> accepted;   // [repetitions]
   std::vector<int64_t> h_e_cur;                     // host copy of e_cur (entry 0 of a segment's trace)
+  // A second set of the five arrays, allocated by the first asp_sa_chains_gather /
+  // _resample of the handle: a gather writes it and the two sets change places.
+  asp::DeviceBuffer<uint64_t> x_cur_to, x_best_to;
+  asp::DeviceBuffer<long long> e_cur_to, e_best_to;
+  asp::DeviceBuffer<unsigned long long> accepted_to;
 };
 
 namespace asp {

@@ -500,7 +500,8 @@ int asp_sa_last_shuffled_fill(asp_sa_plan const *p, double *lane_fill, double *r
  * Between calls a handle holds, per chain, two configurations in original spin order and three
  * integers — nothing that depends on the visiting order or on a launch choice —, so segments may
  * change `order`, and export -> import into another handle of the same plan continues the same chains.
- * Buffers are sized once, at create.  Launch forms: a segment in the shuffled order runs every form
+ * Buffers are sized once, at create (a handle that is gathered or resampled adds a second set then:
+ * below).  Launch forms: a segment in the shuffled order runs every form
  * of asp_sa_anneal_shuffled (spin layouts, chains per group, lane packing, asp_sa_set_shuffled_launch
  * / _teams); a segment in the colour order runs every spin layout and group size of asp_sa_anneal
  * (asp_sa_set_launch, _set_packed, _set_wide and _set_field_cache are honoured) but NO team launches:
@@ -589,6 +590,62 @@ typedef struct asp_sa_chains_item {
 int asp_sa_chains_advance_batch(asp_sa_chains_item const *items, uint32_t count);
 /* Device time (ms) of the sweep launches of this thread's last asp_sa_chains_advance_batch call. */
 float asp_sa_chains_batch_last_ms(void);
+
+/* POPULATION ANNEALING on a handle (law "ASP-PA-1"): between two temperatures the
+ * chains are reweighted by exp(-dbeta E) and resampled ON THE DEVICE, so that low-energy chains are
+ * cloned into the slots of high-energy ones — no export, host arithmetic and import per handle and step.
+ *
+ * asp_sa_chains_gather: all five state arrays of slot j (x_current, x_best, tracked_current,
+ * tracked_best, accepted) become those of slot source[j], for every j at once; source: HOST
+ * [repetitions], any map (repeats, cycles, a reversal) — the primitive of user-defined schemes.
+ * sweeps_done is unchanged; tracked energies are from then on relative to the first configuration of
+ * the chain's LINEAGE; clones diverge afterwards because the random words of a sweep depend on the
+ * slot's replica id.  ASP_ERR_INVALID, before any device work: a null handle, a null source, an entry
+ * >= repetitions.
+ *
+ * asp_sa_chains_resample, for a handle of R chains:
+ *  1. E_r = the reported energy (asp_sa_energy's double) of chain r's CURRENT configuration;
+ *  2. w_r = expneg(dbeta * (E_r - min E)) with the annealer's expneg and one rounding per operation
+ *     (the best chain has w = 1; dbeta * gap >= 23 gives w = 0);
+ *  3. q_r = (uint64) floor(w_r 2^31), C_s = sum of q_r over r < s, T = C_R — integers from here on;
+ *  4. v = word 0 of Philox4x32-10(counter (sweeps_done, draw, 0xFFFFFFFD, 0), key seed) — a counter no
+ *     sweep, start or visiting order uses —, U = floor(v T / 2^32);
+ *  5. systematic resampling: slot j takes source[j] = the s with R C_s <= j T + U < R C_{s+1} (source
+ *     is non-decreasing, chain s gets floor or ceil of R q_s / T copies, dbeta = 0 is the identity);
+ *  6. asp_sa_chains_gather with that map.
+ * Outputs (HOST, each may be NULL): out_source[R], out_energy[R] (E_r before the step), out_q[R],
+ * out_survivors (the number of distinct sources).  Handles with no chains or plans with no spins run
+ * nothing: energies 0, q = 2^31, the identity.  ASP_ERR_INVALID: a null handle, a dbeta that is
+ * negative, NaN or infinite; ASP_ERR_TOO_LARGE: more than 65536 chains (the products of step 5 fit 64
+ * bits up to there); both before any device work.
+ *
+ * asp_sa_chains_resample_batch: many handles in one call — item i is exactly asp_sa_chains_resample
+ * (chains, dbeta, draw, out_*), the same bits for any composition and order of the batch (the single
+ * call IS the batch of one).  Energies run per plan on the plans' streams; weights, prefix sums,
+ * selection and survivor counts are ONE launch with a workgroup per handle, the gather one launch per
+ * state type over (handle, destination chain, words), and every output of the batch comes back in one
+ * copy.  Validation is that of asp_sa_chains_advance_batch: every item before any device work and
+ * before any output is written, the item's index in the message; null items with count > 0, non-zero
+ * flags, the same handle twice and two handles of one plan are ASP_ERR_INVALID; count = 0 needs no
+ * device.  Any OTHER error leaves the handles of the batch UNDEFINED, as documented there.  The first
+ * gather or resample of a handle allocates a second set of its five state arrays, kept until destroy. */
+int asp_sa_chains_gather(asp_sa_chains *c, uint32_t const *source);
+int asp_sa_chains_resample(asp_sa_chains *c, double dbeta, uint32_t draw, uint32_t *out_source,
+                           double *out_energy, uint64_t *out_q, uint32_t *out_survivors);
+typedef struct asp_sa_chains_resample_item {
+  asp_sa_chains *chains;
+  double dbeta;             /* finite, >= 0 */
+  uint32_t draw;            /* the caller's draw index (word 1 of the Philox counter) */
+  uint32_t flags;           /* 0; anything else is ASP_ERR_INVALID */
+  uint32_t *out_source;     /* NULL, or HOST [repetitions] */
+  double *out_energy;       /* NULL, or HOST [repetitions]: reported energies before the step */
+  uint64_t *out_q;          /* NULL, or HOST [repetitions]: integer weights */
+  uint32_t *out_survivors;  /* NULL, or one word: distinct sources */
+} asp_sa_chains_resample_item;
+int asp_sa_chains_resample_batch(asp_sa_chains_resample_item const *items, uint32_t count);
+/* Device time (ms) of this thread's last asp_sa_chains_resample(_batch) call: from its first launch
+ * (the energies) to the end of the gather, HIP events on the call's stream. */
+float asp_sa_chains_resample_last_ms(void);
 
 /* MANY independent problems in one call — the shape of the reference's production job: tens of
  * thousands of sampled clusters, each solved with 64 repetitions x 5120 sweeps
