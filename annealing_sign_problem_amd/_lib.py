@@ -218,6 +218,8 @@ SIGNATURES = {
     "asp_sa_chains_resample": (c_int, [c_void_p, c_double, c_u32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "asp_sa_chains_resample_batch": (c_int, [ctypes.POINTER(SaChainsResampleItem), c_u32]),
     "asp_sa_chains_resample_last_ms": (c_float, []),
+    "asp_sa_chains_advance_ladder": (c_int, [c_void_p, c_void_p, c_u32, c_u32, c_void_p]),
+    "asp_sa_chains_exchange": (c_int, [c_void_p, c_void_p, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "asp_sa_anneal_batch": (c_int, [ctypes.POINTER(SaBatchItem), c_u32]),
     "asp_sa_batch_last_ms": (c_float, []),
     "asp_sa_greedy": (c_int, [c_void_p, c_u32, c_void_p, c_void_p, ctypes.POINTER(c_u32)]),

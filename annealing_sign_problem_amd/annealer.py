@@ -40,6 +40,7 @@ __all__ = [
     "resample_chains",
     "population_anneal",
     "population_anneal_batch",
+    "parallel_tempering",
     "greedy_solve",
     "greedy_solve_batch",
     "signs_to_bits",
@@ -528,6 +529,54 @@ class Chains:
                                                      ctypes.c_uint32(order), _lib.ptr(rows)))
         return rows
 
+    def _chain_betas(self, chain_betas) -> np.ndarray:
+        chain_betas = np.ascontiguousarray(chain_betas, dtype=np.float64)
+        if chain_betas.shape != (self.repetitions,):
+            raise ValueError("'chain_betas' must hold {} inverse temperatures".format(self.repetitions))
+        if not np.all(np.isfinite(chain_betas) & (chain_betas >= 0.0)):
+            raise ValueError("'chain_betas' must be finite and not negative")
+        return chain_betas
+
+    def advance_ladder(self, chain_betas, number_sweeps: int, sweep_order: Optional[str] = None,
+                       trace: bool = False):
+        """Run ``number_sweeps`` more sweeps with chain ``r`` at inverse temperature ``chain_betas[r]``
+        throughout (``asp_sa_chains_advance_ladder``, the ladder law of DESIGN.md §4.10): chain ``r``
+        ends exactly where ``advance(np.full(number_sweeps, chain_betas[r]))`` would take it on a
+        handle of its own.  ``sweep_order`` and ``trace`` as in ``advance``."""
+        order = self._ORDERS[resolve_sweep_order(sweep_order)]
+        chain_betas = self._chain_betas(chain_betas)
+        number_sweeps = int(number_sweeps)
+        if not 0 <= number_sweeps < 2**32:
+            raise ValueError("'number_sweeps' must be a number of sweeps")
+        handle = self._live()
+        rows = np.zeros((self.repetitions, number_sweeps + 1), dtype=np.int64) if trace else None
+        _lib.check(_lib.load().asp_sa_chains_advance_ladder(handle, _lib.ptr(chain_betas),
+                                                            ctypes.c_uint32(number_sweeps), ctypes.c_uint32(order),
+                                                            _lib.ptr(rows)))
+        return rows
+
+    def exchange(self, chain_betas, parity: int, draw: int = 0):
+        """One replica-exchange step (law ASP-PT-1) on the device: the slots ``k`` and
+        ``k + 1`` for every ``k`` of parity ``parity`` swap their configurations with probability
+        ``min(1, exp((beta[k+1] - beta[k]) * (E[k+1] - E[k])))``; the temperatures stay with the slots.
+        Returns ``(source uint32[R], energies float64[R], accepted)``: the slot every slot's state was
+        taken from, the energies before the step and the number of pairs that swapped.  ``draw`` picks
+        the random words (a Philox counter word), for more than one step at one sweep count."""
+        chain_betas = self._chain_betas(chain_betas)
+        parity, draw = int(parity), int(draw)
+        if parity not in (0, 1):
+            raise ValueError("'parity' must be 0 or 1")
+        if not 0 <= draw < 2**32:
+            raise ValueError("'draw' must fit 32 bits")
+        handle = self._live()
+        source = np.zeros(self.repetitions, dtype=np.uint32)
+        energies = np.zeros(self.repetitions, dtype=np.float64)
+        accepted = ctypes.c_uint32(0)
+        _lib.check(_lib.load().asp_sa_chains_exchange(handle, _lib.ptr(chain_betas), ctypes.c_uint32(parity),
+                                                      ctypes.c_uint32(draw), _lib.ptr(source), _lib.ptr(energies),
+                                                      ctypes.byref(accepted)))
+        return source, energies, int(accepted.value)
+
     def result(self, only_best: bool = False):
         """The best configuration so far of every chain and its energy, ``(xs[R, words], es[R])`` —
         what ``anneal(..., only_best=False)`` returns; ``only_best=True``: the best of them."""
@@ -872,6 +921,38 @@ def population_anneal(hamiltonian: Hamiltonian, seed=None, number_steps: int = 5
         raise TypeError("'hamiltonian' must be a Hamiltonian")
     return population_anneal_batch([hamiltonian], seed, number_steps, sweeps_per_step, beta0, beta1, repetitions,
                                    only_best, sweep_order, resample)[0]
+
+
+def parallel_tempering(hamiltonian: Hamiltonian, seed=None, number_rounds: int = 512, sweeps_per_round: int = 10,
+                       beta0: Optional[float] = None, beta1: Optional[float] = None, repetitions: int = 64,
+                       only_best: bool = True, sweep_order: Optional[str] = None, exchange: bool = True):
+    """Parallel tempering: ``repetitions`` chains sit on the temperature ladder
+    ``make_schedule(beta0, beta1, repetitions)`` (the automatic defaults of ``anneal``), slot ``k`` at
+    ``ladder[k]`` throughout.  Round ``j`` is ``sweeps_per_round`` sweeps of every chain at its own
+    temperature (``Chains.advance_ladder``) followed — except after the last round — by a
+    replica-exchange step between neighbouring slots on the device (``Chains.exchange`` with parity
+    ``j & 1``, draw 0).  Returns what ``anneal`` returns.  ``exchange=False`` is ``repetitions``
+    independent constant-temperature chains (the ladder law, §4.10).  Chains stay on this rank."""
+    order = resolve_sweep_order(sweep_order)  # (first: a bad order fails without a GPU)
+    number_rounds, sweeps_per_round = int(number_rounds), int(sweeps_per_round)
+    if number_rounds < 1 or sweeps_per_round < 1:
+        raise ValueError("'number_rounds' and 'sweeps_per_round' must be positive")
+    if not isinstance(hamiltonian, Hamiltonian):
+        raise TypeError("'hamiltonian' must be a Hamiltonian")
+    repetitions = int(repetitions)
+    if repetitions < 1:
+        raise ValueError("'repetitions' must be positive")
+    if beta0 is None or beta1 is None:
+        info = hamiltonian.info()
+        beta0 = info.beta0_auto if beta0 is None else beta0
+        beta1 = info.beta1_auto if beta1 is None else beta1
+    ladder = make_schedule(float(beta0), float(beta1), repetitions)
+    with Chains(hamiltonian, seed=seed, repetitions=repetitions) as chains:
+        for j in range(number_rounds):
+            chains.advance_ladder(ladder, sweeps_per_round, sweep_order=order)
+            if exchange and j + 1 < number_rounds:
+                chains.exchange(ladder, j & 1, 0)
+        return chains.result(only_best=only_best)
 
 
 def anneal_with_traces(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: int = 5120,

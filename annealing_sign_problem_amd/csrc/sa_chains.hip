@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <utility>
 #include <vector>
@@ -191,6 +192,40 @@ int asp_sa_chains_advance(asp_sa_chains *c, double const *betas, uint32_t num_sw
     c->plan->last_sweep_ms = c->plan->last_total_ms = 0.0f;
     ASP_TRY(order == 0 ? asp::sa_chains_advance_colour(c, betas, num_sweeps, out_trace)
                        : asp::sa_chains_advance_shuffled(c, betas, num_sweeps, out_trace));
+  } else if (out_trace) {
+    // (no spins: the energy stays where it is; no sweeps: the single entry below)
+    for (uint64_t k = 0; k < static_cast<uint64_t>(R) * (num_sweeps + 1ull); ++k) out_trace[k] = 0;
+  }
+  if (out_trace) {
+    for (uint32_t r = 0; r < R; ++r) out_trace[static_cast<uint64_t>(r) * (num_sweeps + 1ull)] = start[r];
+  }
+  c->sweeps_done += num_sweeps;
+  return ASP_OK;
+}
+
+int asp_sa_chains_advance_ladder(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps, uint32_t order,
+                                 int64_t *out_trace) {
+  asp_clear_error();
+  if (!c) return asp::set_error(ASP_ERR_INVALID, "null chains handle");
+  const uint32_t R = c->repetitions;
+  if (R && !chain_betas) return asp::set_error(ASP_ERR_INVALID, "null chain_betas");
+  if (order > 1u) return asp::set_error(ASP_ERR_INVALID, "order must be 0 (colour) or 1 (shuffled)");
+  if (static_cast<uint64_t>(c->sweeps_done) + num_sweeps > 0xFFFFFFFEull) {
+    return asp::set_error(ASP_ERR_INVALID, "%u sweeps after %u exceed the 2^32 - 2 sweep indices of a chain",
+                          num_sweeps, c->sweeps_done);
+  }
+  for (uint32_t r = 0; r < R; ++r) {
+    // (an infinite beta times dE = 0 is not a number: the law needs a finite one)
+    if (!(chain_betas[r] >= 0.0) || std::isinf(chain_betas[r])) {
+      return asp::set_error(ASP_ERR_INVALID, "chain_betas[%u] is not a finite number >= 0", r);
+    }
+  }
+  ASP_TRY(asp::bind_device());
+  const std::vector<int64_t> start = c->h_e_cur;  // entry 0 of every row: NOT reset to 0
+  if (num_sweeps != 0 && !nothing_to_run(c)) {
+    c->plan->last_sweep_ms = c->plan->last_total_ms = 0.0f;
+    ASP_TRY(order == 0 ? asp::sa_chains_advance_ladder_colour(c, chain_betas, num_sweeps, out_trace)
+                       : asp::sa_chains_advance_ladder_shuffled(c, chain_betas, num_sweeps, out_trace));
   } else if (out_trace) {
     // (no spins: the energy stays where it is; no sweeps: the single entry below)
     for (uint64_t k = 0; k < static_cast<uint64_t>(R) * (num_sweeps + 1ull); ++k) out_trace[k] = 0;

@@ -115,6 +115,12 @@ int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uin
 int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace);
 int sa_chains_advance_shuffled(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace);
 
+// One LADDER segment (asp_sa_chains_advance_ladder; the same contract): chain r runs its num_sweeps sweeps
+// at chain_betas[r] (HOST [repetitions], validated).  The launch forms of sa_chains_advance_colour /
+// _shuffled (the shuffled order: one team), with the per-chain-beta instantiations of the sweep kernels.
+int sa_chains_advance_ladder_colour(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps, int64_t *trace);
+int sa_chains_advance_ladder_shuffled(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps, int64_t *trace);
+
 // The items of asp_sa_chains_advance_batch that run sweeps (validated; distinct handles of distinct
 // plans with spins and chains, num_sweeps > 0), one visiting order at a time: every segment is exactly
 // its sa_chains_advance_colour / _shuffled call, the handles that fit share launches.  h_e_cur of the

@@ -153,6 +153,49 @@ __global__ __launch_bounds__(kThreads) void k_population_gather_integers(const G
   }
 }
 
+// Steps 2-5 of ASP-PT-1, a thread per pair: thread j owns the pair (k, k + 1),
+// k = parity + 2 j, and — where that pair does not exist — the slot k alone (the last slot of an odd
+// remainder); thread 0 also owns slot 0 when parity = 1.  Every slot of the handle is written by exactly
+// one thread.  back: energy[R] (64-bit words, what the host reads back) | source u32[R] | accepted u32
+// (zeroed before the launch).  Plain vector stores and one atomic add per accepted pair.
+struct ExchangeArgs {
+  const double *energy;  // [R] reported energies of the current configurations
+  const double *beta;    // [R] the slots' inverse temperatures
+  uint64_t seed;
+  uint32_t chains, sweeps_done, parity, draw;
+};
+__global__ __launch_bounds__(kThreads) void k_exchange_select(ExchangeArgs a, uint64_t *__restrict__ energy_out,
+                                                              uint32_t *__restrict__ source,
+                                                              uint32_t *__restrict__ accepted) {
+  const uint32_t R = a.chains;
+  const uint64_t j = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  const uint64_t k64 = a.parity + 2ull * j;
+  if (j == 0 && a.parity == 1u && R != 0u) {
+    energy_out[0] = static_cast<uint64_t>(__double_as_longlong(a.energy[0]));
+    source[0] = 0u;
+  }
+  if (k64 >= R) return;
+  const uint32_t k = static_cast<uint32_t>(k64);
+  const double e0 = a.energy[k];
+  energy_out[k] = static_cast<uint64_t>(__double_as_longlong(e0));
+  if (k + 1u >= R) {  // (no partner)
+    source[k] = k;
+    return;
+  }
+  const double e1 = a.energy[k + 1u];
+  energy_out[k + 1u] = static_cast<uint64_t>(__double_as_longlong(e1));
+  const double x = __dmul_rn(__dadd_rn(a.beta[k + 1u], -a.beta[k]), __dadd_rn(e0, -e1));
+  bool swap = x <= 0.0;
+  if (!swap) {
+    const Philox4 rnd = philox4x32_10(k, a.sweeps_done, 0xFFFFFFFCu, a.draw, static_cast<uint32_t>(a.seed),
+                                      static_cast<uint32_t>(a.seed >> 32));
+    swap = metropolis_accept_word(rnd.w[0], x);
+  }
+  source[k] = swap ? k + 1u : k;
+  source[k + 1u] = swap ? k : k + 1u;
+  if (swap) atomicAdd(accepted, 1u);
+}
+
 int ensure_second_set(asp_sa_chains *c) {
   const uint64_t state_words = static_cast<uint64_t>(c->repetitions) * c->words;
   ASP_TRY(c->x_cur_to.ensure(state_words));
@@ -249,6 +292,75 @@ int asp_sa_chains_gather(asp_sa_chains *c, uint32_t const *source) {
 }
 
 float asp_sa_chains_resample_last_ms(void) { return g_resample_ms; }
+
+int asp_sa_chains_exchange(asp_sa_chains *c, double const *chain_betas, uint32_t parity, uint32_t draw,
+                           uint32_t *out_source, double *out_energy, uint32_t *out_accepted) {
+  asp_clear_error();
+  if (!c) return asp::set_error(ASP_ERR_INVALID, "null chains handle");
+  const uint32_t R = c->repetitions;
+  if (R && !chain_betas) return asp::set_error(ASP_ERR_INVALID, "null chain_betas");
+  if (parity > 1u) return asp::set_error(ASP_ERR_INVALID, "parity must be 0 or 1");
+  for (uint32_t r = 0; r < R; ++r) {
+    if (!(chain_betas[r] >= 0.0) || std::isinf(chain_betas[r])) {
+      return asp::set_error(ASP_ERR_INVALID, "chain_betas[%u] is not a finite number >= 0", r);
+    }
+  }
+  asp_sa_plan *p = c->plan;
+  if (R == 0 || p->host.num_spins == 0) {
+    // no chains or no spins: nothing runs; every energy is 0 and the map the identity
+    for (uint32_t r = 0; r < R; ++r) {
+      if (out_source) out_source[r] = r;
+      if (out_energy) out_energy[r] = 0.0;
+    }
+    if (out_accepted) *out_accepted = 0u;
+    return ASP_OK;
+  }
+  ASP_TRY(asp::bind_device());
+  // what comes back in one copy: energy[R] | source u32[R] | accepted u32
+  const uint64_t source_at = R, accepted_at = source_at + (R + 1ull) / 2, back_words = accepted_at + 1;
+  std::vector<uint64_t> h_back(back_words, 0);
+  asp::DeviceBuffer<uint64_t> d_back;
+  asp::DeviceBuffer<double> d_beta;
+  asp::DeviceBuffer<GatherRow> d_rows;
+  hipStream_t s = p->stream;
+  asp::StreamFence fence(s);
+  ASP_TRY(ensure_second_set(c));
+  ASP_TRY(d_back.alloc(back_words));
+  ASP_TRY(d_beta.alloc(R));
+  ASP_TRY(d_rows.alloc(1));
+  ASP_TRY(p->w_x0_perm.ensure(static_cast<uint64_t>(R) * p->host.num_blocks));
+  ASP_TRY(p->w_partial.ensure(static_cast<uint64_t>(R) * p->host.num_blocks));
+  ASP_TRY(p->w_e.ensure(R));
+  const std::vector<GatherRow> rows(1, gather_row(c, 0));
+  ASP_TRY(d_beta.upload(chain_betas, R, s));
+  ASP_TRY(d_rows.upload(rows.data(), 1, s));
+  uint32_t *d_source = reinterpret_cast<uint32_t *>(d_back.ptr + source_at);
+  uint32_t *d_accepted = reinterpret_cast<uint32_t *>(d_back.ptr + accepted_at);
+  ASP_HIP_TRY(hipMemsetAsync(d_accepted, 0, sizeof(uint64_t), s));
+  ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
+  // step 1: the reported energies of the current configurations (step 1 of ASP-PA-1)
+  ASP_TRY(asp::sa_permute_bits(p, c->x_cur.ptr, R, p->w_x0_perm.ptr));
+  ASP_TRY(asp::sa_energies_of_perm(p, p->w_x0_perm.ptr, R, p->w_partial.ptr, p->w_e.ptr));
+  // steps 2-5: a thread per pair (one more for the slot a parity of 1 leaves at the front)
+  const ExchangeArgs args{p->w_e.ptr, d_beta.ptr, c->seed, R, c->sweeps_done, parity, draw};
+  const uint32_t threads = R / 2u + 1u;
+  hipLaunchKernelGGL(k_exchange_select, dim3((threads + kThreads - 1) / kThreads), dim3(kThreads), 0, s, args,
+                     d_back.ptr, d_source, d_accepted);
+  ASP_HIP_TRY(hipGetLastError());
+  // step 6: the gather of asp_sa_chains_gather
+  ASP_TRY(launch_gather(rows, d_rows.ptr, d_source, s));
+  ASP_HIP_TRY(hipEventRecord(p->ev[3], s));
+  ASP_TRY(d_back.download(h_back.data(), back_words, s));
+  ASP_HIP_TRY(hipStreamSynchronize(s));
+  p->last_sweep_ms = 0.0f;
+  ASP_HIP_TRY(hipEventElapsedTime(&p->last_total_ms, p->ev[0], p->ev[3]));
+  const uint32_t *h_source = reinterpret_cast<const uint32_t *>(h_back.data() + source_at);
+  adopt(c, h_source);
+  if (out_source) std::memcpy(out_source, h_source, R * sizeof(uint32_t));
+  if (out_energy) std::memcpy(out_energy, h_back.data(), R * sizeof(double));
+  if (out_accepted) *out_accepted = *reinterpret_cast<const uint32_t *>(h_back.data() + accepted_at);
+  return ASP_OK;
+}
 
 int asp_sa_chains_resample_batch(asp_sa_chains_resample_item const *items, uint32_t count) {
   asp_clear_error();

@@ -987,6 +987,19 @@ struct ShuffledTraceArgs : ShuffledArgs {
   uint32_t trace_chains, trace_stride;
 };
 
+// The arguments of the LADDER kernels (asp_sa_chains_advance_ladder, order 1; DESIGN.md §4.10 "Ladder
+// law"): every chain of the call runs all its sweeps at its own inverse temperature; `betas` is not
+// read.  A struct of their own again, so that the kernels above keep their arguments and their code.
+template <typename Base>
+struct ShuffledLadderArgsOf : Base {
+  static constexpr bool kLadder = true;
+  const double *chain_betas;  // [groups_total * chains per group]; the chains padding the last group: 0
+};
+template <typename Args, typename = void>
+inline constexpr bool kLadderArgs = false;
+template <typename Args>
+inline constexpr bool kLadderArgs<Args, std::void_t<decltype(Args::kLadder)>> = true;
+
 // Spins stay in LDS in ORIGINAL order, in one of four layouts: a 32-bit word per spin (kWide: byte
 // m = 0x80 * chain m is -1; up to four chains), a byte per spin (kBytes: bit m; up to eight), and —
 // for clusters beyond the capacity of bytes — four bits per spin (kNibbles: up to four chains,
@@ -1262,6 +1275,9 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
                 "a packed layout holds as many chains as it has bits per spin, in one team");
   static_assert(MT <= 8 && (TEAMS == 1 || TEAMS == 2), "a byte holds eight chains");
   static_assert(!PK || (WIDE && TEAMS == 1), "lane packing: wide layout, one team");
+  // LADDER: chain c of the call runs at a.chain_betas[c] in every sweep (ShuffledLadderArgsOf)
+  constexpr bool LADDER = kLadderArgs<Args>;
+  static_assert(!LADDER || TEAMS == 1, "a ladder segment runs one team");
   constexpr uint32_t CH = PK ? 64u : 8u;  // chains of a workgroup the bookkeeping arrays hold
   extern __shared__ __align__(16) uint8_t lds[];
   if (a.status[kStatBad] != 0u) return;  // an order kernel ran out of room: the host repeats the call
@@ -1375,6 +1391,21 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
   }
 
   uint32_t one_hi[4] = {0x3FF00000u, 0x3FF00000u, 0x3FF00000u, 0x3FF00000u};
+  // LADDER: the betas of this wavefront's (lane packing: this lane's group's) M chains, read once —
+  // wave-uniform without lane packing; the groups past the call's last one run at 0 and are never applied.
+  // Eight chains (bytes, never lane-packed) read theirs where they are used instead, once per visit
+  // (scalar loads of one cache line): held for the whole launch they cost the instantiation 52 B of
+  // scratch where k_sa_sweep_shuffled<8, kBytes> has none.
+  constexpr bool HELD = LADDER && M <= 4;
+  static_assert(!LADDER || HELD || !PK, "betas read at the point of use are wave-uniform");
+  [[maybe_unused]] double ladder_beta[HELD ? M : 1];
+  if constexpr (HELD) {
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const uint64_t at = first_chain + (PK ? lg * M : c0) + m;
+      ladder_beta[m] = group_live ? a.chain_betas[at] : 0.0;
+    }
+  }
 #if ASP_SHUF_TIMING
   unsigned long long ticks[kTimingSlots] = {0, 0, 0, 0, 0, 0};
   unsigned long long tick_last = __builtin_readcyclecounter();
@@ -1384,7 +1415,18 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
   const uint32_t slab_bytes = 16u << log_s;
   for (uint32_t tt = 0; tt < a.chunk_sweeps; ++tt) {
     const uint32_t t = a.first_sweep + tt;
-    const double beta = a.betas[t];
+    double beta = 0.0;
+    if constexpr (!LADDER) beta = a.betas[t];
+    // the inverse temperature of chain m of the wavefront in this sweep
+    const auto beta_of = [&]([[maybe_unused]] int m) {
+      if constexpr (HELD) {
+        return ladder_beta[m];
+      } else if constexpr (LADDER) {
+        return a.chain_betas[first_chain + c0 + m];
+      } else {
+        return beta;
+      }
+    };
     const uint32_t levels = a.num_levels[tt];
     {
       const uint32_t *g_level_block = a.level_block + static_cast<uint64_t>(tt) * (a.level_cap + 1u);
@@ -1535,7 +1577,7 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
             const bool negative = (own >> (WIDE ? 8 * m + 7 : m)) & 1u;  // s = -1
             de[m] = __dmul_rn(negative ? 2.0 : -2.0, g);
             // dE <= 0 is accepted and beta * dE >= 23 rejected whatever the draw
-            need = need || (valid && !(de[m] <= 0.0) && !(__dmul_rn(beta, de[m]) >= 23.0));
+            need = need || (valid && !(de[m] <= 0.0) && !(__dmul_rn(beta_of(m), de[m]) >= 23.0));
           }
           uint32_t flip = 0;
           if (__ballot(need) != 0ull) {
@@ -1549,7 +1591,7 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
                 rnd = philox4x32_10(spin, t, have, 0u, key0, key1);
               }
               const bool accept = valid && (de[m] <= 0.0 || metropolis_accept_word(pick_word(rnd, r & 3u),
-                                                                                   __dmul_rn(beta, de[m])));
+                                                                                   __dmul_rn(beta_of(m), de[m])));
               flip |= (accept ? 1u : 0u) << m;
             }
           } else {
@@ -1686,6 +1728,17 @@ using ShuffledTraceKernel = ShuffledKernelOf<true>;
 template <int M, int LAYOUT, int TEAMS, bool PK = false, bool TRACE = false>
 __global__ __launch_bounds__(512) void k_sa_sweep_shuffled(ShuffledArgsOf<TRACE> a) {
   shuffled_sweep_body<M, LAYOUT, TEAMS, PK, TRACE>(a, blockIdx.x);
+}
+
+// One ladder segment of a handle (asp_sa_chains_advance_ladder, order 1): every layout, group size and
+// lane packing of k_sa_sweep_shuffled, one team.
+template <bool TRACE>
+using ShuffledLadderArgs = ShuffledLadderArgsOf<ShuffledArgsOf<TRACE>>;
+template <bool TRACE>
+using ShuffledLadderKernelOf = void (*)(ShuffledLadderArgs<TRACE>);
+template <int M, int LAYOUT, bool PK = false, bool TRACE = false>
+__global__ __launch_bounds__(512) void k_sa_sweep_shuffled_ladder(ShuffledLadderArgs<TRACE> a) {
+  shuffled_sweep_body<M, LAYOUT, 1, PK, TRACE>(a, blockIdx.x);
 }
 
 // Many problems in one launch: workgroup -> (problem, workgroup of the problem) through a slot
@@ -1890,6 +1943,45 @@ ShuffledTraceKernel shuffled_trace_kernel_for(int m, int layout, int teams, bool
   return shuffled_kernel_of<true>(m, layout, teams, packed_lanes);
 }
 
+// The ladder kernel of the same form (one team).
+template <bool TRACE>
+ShuffledLadderKernelOf<TRACE> shuffled_ladder_kernel_of(int m, int layout, bool packed_lanes) {
+  if (packed_lanes) {
+    if (layout != kWide) return nullptr;
+    switch (m) {
+      case 1: return k_sa_sweep_shuffled_ladder<1, kWide, true, TRACE>;
+      case 2: return k_sa_sweep_shuffled_ladder<2, kWide, true, TRACE>;
+      case 4: return k_sa_sweep_shuffled_ladder<4, kWide, true, TRACE>;
+      default: return nullptr;
+    }
+  }
+  if (layout == kWide) {
+    switch (m) {
+      case 1: return k_sa_sweep_shuffled_ladder<1, kWide, false, TRACE>;
+      case 2: return k_sa_sweep_shuffled_ladder<2, kWide, false, TRACE>;
+      case 4: return k_sa_sweep_shuffled_ladder<4, kWide, false, TRACE>;
+      default: return nullptr;
+    }
+  }
+  if (layout == kNibbles) {
+    switch (m) {
+      case 1: return k_sa_sweep_shuffled_ladder<1, kNibbles, false, TRACE>;
+      case 2: return k_sa_sweep_shuffled_ladder<2, kNibbles, false, TRACE>;
+      case 4: return k_sa_sweep_shuffled_ladder<4, kNibbles, false, TRACE>;
+      default: return nullptr;
+    }
+  }
+  if (layout == kBits) return m == 1 ? k_sa_sweep_shuffled_ladder<1, kBits, false, TRACE> : nullptr;
+  if (layout == kGlobal) return m == 1 ? k_sa_sweep_shuffled_ladder<1, kGlobal, false, TRACE> : nullptr;
+  switch (m) {
+    case 1: return k_sa_sweep_shuffled_ladder<1, kBytes, false, TRACE>;
+    case 2: return k_sa_sweep_shuffled_ladder<2, kBytes, false, TRACE>;
+    case 4: return k_sa_sweep_shuffled_ladder<4, kBytes, false, TRACE>;
+    case 8: return k_sa_sweep_shuffled_ladder<8, kBytes, false, TRACE>;
+    default: return nullptr;
+  }
+}
+
 // spins (of `groups` groups: lane packing) | delta[CH] book[3 CH] | flags (16 B) | meta[block_cap] |
 // level_block[level_cap + 2]; CH = 8 chains, 64 with lane packing (groups > 0)
 size_t sweep_lds_bytes(uint64_t K, int layout, uint32_t level_cap, uint32_t block_cap, uint32_t groups = 0) {
@@ -2016,6 +2108,10 @@ struct ShuffledRun {
   // and trace through rebased()) —, no launch initialises, and nothing is reported but the state.
   asp_sa_chains *resume = nullptr;
   uint32_t t0 = 0;
+  // A LADDER segment (asp_sa_chains_advance_ladder, order 1): HOST [repetitions] inverse temperatures,
+  // chain r runs every sweep of the segment at chain_betas[r]; `betas` is unused, d_betas holds the
+  // padded chains' values, the launches are the ladder kernels of the form chosen (one team).
+  const double *chain_betas = nullptr;
   bool resume_shared = false;  // set by the batched driver: it loads and stores the handles of its runs together
 
   uint64_t K = 0;
@@ -2072,12 +2168,14 @@ struct ShuffledRun {
       trivial = true;
       return ASP_OK;
     }
-    if ((!resume && (!out_x || !out_e)) || (num_sweeps && !betas)) return asp::set_error(ASP_ERR_INVALID, "null argument");
+    if ((!resume && (!out_x || !out_e)) || (num_sweeps && !betas && !chain_betas)) {
+      return asp::set_error(ASP_ERR_INVALID, "null argument");
+    }
     if (num_sweeps >= 0xFFFFFFFEu) return asp::set_error(ASP_ERR_INVALID, "num_sweeps too large");
     if (static_cast<uint64_t>(replica_offset) + repetitions + 8 > 0xFFFFFFFFull) {
       return asp::set_error(ASP_ERR_INVALID, "replica ids exceed 32 bits");
     }
-    for (uint32_t t = 0; t < num_sweeps; ++t) {
+    for (uint32_t t = 0; t < num_sweeps && !chain_betas; ++t) {
       if (!(betas[t] >= 0.0)) return asp::set_error(ASP_ERR_INVALID, "betas[%u] is not >= 0", t);
     }
     const asp::SaHostLayout &L = p->host;
@@ -2133,7 +2231,7 @@ struct ShuffledRun {
     // against 100 with 2048 — a visit is bound by the compute unit's fill rate from L2 (a block is
     // 22 KiB, four or five blocks per level and CU), not by the issue rate of its wavefront, and
     // the partner team adds load instructions without adding bandwidth.
-    teams = p->shuffled_teams == 2 && m >= 2 && waves <= 4 ? 2 : 1;
+    teams = p->shuffled_teams == 2 && m >= 2 && waves <= 4 && !chain_betas ? 2 : 1;
     groups = (repetitions + m - 1) / m;
     padded = static_cast<uint64_t>(groups) * m;
     level_cap = static_cast<uint32_t>(std::min<double>(static_cast<double>(K), 2.0 * levels_guess + 32.0));
@@ -2208,7 +2306,7 @@ struct ShuffledRun {
       ASP_TRY(p->w_trace.ensure(trace_elems()));
       ASP_HIP_TRY(hipMemsetAsync(p->w_trace.ptr, 0, trace_elems() * sizeof(long long), s));
     }
-    ASP_TRY(d_betas.alloc(num_sweeps));
+    ASP_TRY(d_betas.alloc(chain_betas ? padded : num_sweeps));
     // (a byte per spin and group between chunks — or, beyond every LDS layout, the chains' spin words)
     const bool spins_in_hbm = shuffled_layout_for(K, m, level_cap, words + level_cap, p->max_lds) == kGlobal;
     ASP_TRY(d_state.alloc(static_cast<uint64_t>(groups) * K * (spins_in_hbm ? 4 : 1)));
@@ -2220,7 +2318,12 @@ struct ShuffledRun {
     ASP_TRY(d_partial.alloc(static_cast<uint64_t>(repetitions) * L.num_blocks));
     ASP_TRY(d_e.alloc(repetitions));
     ASP_TRY(d_status.alloc(kStatusWords));
-    ASP_TRY(d_betas.upload(betas, num_sweeps, s));
+    if (chain_betas) {
+      if (padded > repetitions) ASP_HIP_TRY(hipMemsetAsync(d_betas.ptr + repetitions, 0, (padded - repetitions) * 8, s));
+      ASP_TRY(d_betas.upload(chain_betas, repetitions, s));
+    } else {
+      ASP_TRY(d_betas.upload(betas, num_sweeps, s));
+    }
     if (x0) {
       ASP_TRY(d_x0.alloc(words));
       ASP_TRY(d_x0.upload(x0, words, s));
@@ -2263,6 +2366,8 @@ struct ShuffledRun {
   }
   ShuffledKernel kernel = nullptr;
   ShuffledTraceKernel trace_kernel = nullptr;  // the traced instantiation of `kernel` (out_trace)
+  ShuffledLadderKernelOf<false> ladder_kernel = nullptr;       // chain_betas: the ladder form of `kernel` ...
+  ShuffledLadderKernelOf<true> ladder_trace_kernel = nullptr;  // ... and of `trace_kernel`
   int nsets = 1, nlanes = 1;
   OrderArgs oa{};
   ShuffledArgs sa{};
@@ -2391,7 +2496,7 @@ struct ShuffledRun {
     ASP_TRY(d_state.ensure(static_cast<uint64_t>(groups) * K * (layout == kGlobal ? 4 : 1)));
     sa = ShuffledArgs{};
     sa.status = d_status.ptr;
-    sa.betas = rebased(d_betas.ptr, t0);
+    sa.betas = chain_betas ? nullptr : rebased(d_betas.ptr, t0);  // (a ladder segment never reads them)
     sa.x0 = x0 ? d_x0.ptr : nullptr;
     sa.state = d_state.ptr;
     sa.best = d_best.ptr;
@@ -2463,10 +2568,19 @@ struct ShuffledRun {
     }
     // (a traced call: the traced instantiation of the form just chosen)
     trace_kernel = out_trace ? shuffled_trace_kernel_for(m, layout, teams, packed_lanes) : nullptr;
+    const void *launched = out_trace ? reinterpret_cast<const void *>(trace_kernel)
+                                     : reinterpret_cast<const void *>(kernel);
+    if (chain_betas) {
+      ladder_kernel = shuffled_ladder_kernel_of<false>(m, layout, packed_lanes);
+      ladder_trace_kernel = shuffled_ladder_kernel_of<true>(m, layout, packed_lanes);
+      if (!ladder_kernel || !ladder_trace_kernel) {
+        return asp::set_error(ASP_ERR_INVALID, "no ladder sweep for %d chains per group in layout %d", m, layout);
+      }
+      launched = out_trace ? reinterpret_cast<const void *>(ladder_trace_kernel)
+                           : reinterpret_cast<const void *>(ladder_kernel);
+    }
     if (lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(out_trace ? reinterpret_cast<const void *>(trace_kernel)
-                                                : reinterpret_cast<const void *>(kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+      ASP_HIP_TRY(hipFuncSetAttribute(launched, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     }
     if (order_lds > 64 * 1024) {
       ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wide_orders ? k_shuffled_orders<true> : k_shuffled_orders<false>),
@@ -2530,7 +2644,19 @@ struct ShuffledRun {
         t_args.trace = rebased(p->w_trace.ptr, t0);
         t_args.trace_chains = repetitions;
         t_args.trace_stride = num_sweeps + 1u;
-        hipLaunchKernelGGL(trace_kernel, dim3(wgs), dim3(waves * teams * 64), lds, s, t_args);
+        if (chain_betas) {
+          ShuffledLadderArgs<true> l_args{};
+          static_cast<ShuffledTraceArgs &>(l_args) = t_args;
+          l_args.chain_betas = d_betas.ptr;
+          hipLaunchKernelGGL(ladder_trace_kernel, dim3(wgs), dim3(waves * 64), lds, s, l_args);
+        } else {
+          hipLaunchKernelGGL(trace_kernel, dim3(wgs), dim3(waves * teams * 64), lds, s, t_args);
+        }
+      } else if (chain_betas) {
+        ShuffledLadderArgs<false> l_args{};
+        static_cast<ShuffledArgs &>(l_args) = s_args;
+        l_args.chain_betas = d_betas.ptr;
+        hipLaunchKernelGGL(ladder_kernel, dim3(wgs), dim3(waves * 64), lds, s, l_args);
       } else {
         hipLaunchKernelGGL(kernel, dim3(wgs), dim3(waves * teams * 64), lds, s, s_args);
       }
@@ -3223,6 +3349,29 @@ int sa_chains_advance_shuffled(asp_sa_chains *c, double const *betas, uint32_t n
   run.p = c->plan;
   run.seed = c->seed;
   run.betas = betas;
+  run.num_sweeps = num_sweeps;
+  run.repetitions = c->repetitions;
+  run.replica_offset = c->replica_offset;
+  run.out_trace = trace;
+  run.resume = c;
+  run.t0 = c->sweeps_done;
+  ASP_TRY(run.setup());
+  bool again = true;
+  while (again) {
+    ASP_TRY(run.enqueue());
+    ASP_TRY(run.collect(&again));
+  }
+  ASP_TRY(run.finish_enqueue());
+  return run.finish_wait();
+}
+
+// One LADDER segment in the shuffled order: the same run with one beta per chain.
+int sa_chains_advance_ladder_shuffled(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps,
+                                      int64_t *trace) {
+  ShuffledRun run;
+  run.p = c->plan;
+  run.seed = c->seed;
+  run.chain_betas = chain_betas;
   run.num_sweeps = num_sweeps;
   run.repetitions = c->repetitions;
   run.replica_offset = c->replica_offset;

@@ -395,12 +395,63 @@ struct StopWhenStill {
 // what they were.
 struct NoResume {
   static constexpr bool kEnabled = false;
+  static constexpr bool kLadder = false;
 };
 struct Resume {
   static constexpr bool kEnabled = true;
+  static constexpr bool kLadder = false;
   uint64_t *cur_perm;  // [groups * M][num_blocks] sign-bit words: start of every chain in, final state out
   long long *e_cur;    // [groups * M] current tracked energy, in and out
   uint32_t t0;         // sweeps the chains have behind them
+};
+// ResumeLadder: a Resume segment in which every chain runs at its OWN inverse temperature, constant
+// over the segment (asp_sa_chains_advance_ladder, DESIGN.md §4.10 "Ladder law"): a.betas is never
+// read, replica m of the group reads chain_betas once before the sweep loop.  The inert bytes stay
+// valid inside the segment — a certain rejection of replica m was certain at replica m's beta, which
+// does not change — and nothing is carried in from the segment before (which may have run colder):
+// cache_ctl, the dirty and the inert bytes live in LDS and are set up by every launch, cached mode is
+// entered with every block stale, and an inert byte is only read for a block evaluated since.
+struct ResumeLadder {
+  static constexpr bool kEnabled = true;
+  static constexpr bool kLadder = true;
+  uint64_t *cur_perm;
+  long long *e_cur;
+  uint32_t t0;
+  const double *chain_betas;  // [groups * M]; the chains padding the last group: 0
+};
+
+// The inverse temperature of replica m: the sweep's shared one, or (ResumeLadder) the replica's own —
+// workgroup-uniform, so scalar registers.  One or two replicas read theirs once before the sweep loop
+// and hold them.  Four and eight read them where they are used, once per visit of a block (scalar loads
+// of one cache line that stays in the scalar cache): those instantiations have no scalar register to
+// spare, and 2 M more held for the whole launch went to scratch (M = 8 bytes: 160 B against the 32 B of
+// k_sa_sweep_resume, M = 4 words: 36 B against none; read at the point of use: 84 B and 12 B, spilled
+// around the accept phase of a visit, not in the k-loop).
+template <int M, bool LADDER>
+struct LadderBetas {
+  template <typename Res>
+  __device__ __forceinline__ LadderBetas(const Res &, uint32_t) {}
+  __device__ __forceinline__ double of(int, double beta) const { return beta; }
+};
+template <int M>
+struct LadderBetas<M, true> {
+  static constexpr bool kHeld = M <= 2;
+  double own[kHeld ? M : 1];
+  const double *mine;  // the group's M values
+  __device__ __forceinline__ LadderBetas(const ResumeLadder &res, uint32_t group)
+      : mine(res.chain_betas + static_cast<uint64_t>(group) * M) {
+    if constexpr (kHeld) {
+#pragma unroll
+      for (int m = 0; m < M; ++m) own[m] = mine[m];
+    }
+  }
+  __device__ __forceinline__ double of(int m, double) const {
+    if constexpr (kHeld) {
+      return own[m];
+    } else {
+      return mine[m];
+    }
+  }
 };
 
 // DESCENT = true: strict-descent sweeps (accept iff dE < 0, no random numbers, no beta: a.betas is
@@ -548,6 +599,8 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     a.trace[(static_cast<uint64_t>(group) * M + tid) * (a.num_sweeps + 1ull)] = start;
   }
   double mult[4] = {1.0, 1.0, 1.0, 1.0};  // kWide's multipliers (low words stay 0)
+  // ResumeLadder: the replicas' own betas (workgroup-uniform: scalar registers)
+  const LadderBetas<M, Res::kLadder> ladder(res, group);
   // StopWhenStill: sweeps performed, and the chain's accepted flips before the running sweep
   [[maybe_unused]] uint32_t sweeps_done = a.num_sweeps;
   [[maybe_unused]] long long flips_before = 0;
@@ -555,14 +608,14 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     uint32_t t_draw = t;  // the sweep index of the random words: global over the segments of a handle
     if constexpr (Res::kEnabled) t_draw += res.t0;
     double beta;
-    if constexpr (DESCENT) {
+    if constexpr (DESCENT || Res::kLadder) {
       beta = 0.0;  // unused by the descent rule: a certain rejection there is dE >= 0 at any beta
     } else {
       beta = a.betas[t];
     }
     // wave-uniform: cached fields are in use during this sweep
     const bool cached = cache_available && __builtin_amdgcn_readfirstlane(cache_ctl[1]) != 0;
-    if constexpr (!DESCENT) {
+    if constexpr (!DESCENT && !Res::kLadder) {
       if (cached && t > 0 && beta < a.betas[t - 1]) {
         // certain rejections are only certain for non-decreasing beta (workgroup-uniform branch)
         for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) inert[b] = 0;
@@ -670,7 +723,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
           if constexpr (DESCENT) {
             open = open || (valid && de[m] < 0.0);
           } else {
-            const bool maybe = valid && !(__dmul_rn(beta, de[m]) >= 23.0);  // not a certain rejection
+            const bool maybe = valid && !(__dmul_rn(ladder.of(m, beta), de[m]) >= 23.0);  // not a certain rejection
             open = open || maybe;
             need = need || (maybe && !(de[m] <= 0.0));
           }
@@ -693,7 +746,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
             }
             const uint32_t word = pick_word(rnd, r & 3u);
             const bool accept =
-                valid && (de[m] <= 0.0 || metropolis_accept_word(word, __dmul_rn(beta, de[m])));
+                valid && (de[m] <= 0.0 || metropolis_accept_word(word, __dmul_rn(ladder.of(m, beta), de[m])));
             accept_mask |= (accept ? 1u : 0u) << m;
           }
         } else {
@@ -856,6 +909,12 @@ __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep(SweepArgs a) {
 template <int M, int LAYOUT>
 __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_resume(SweepArgs a, Resume r) {
   sa_sweep_body<M, false, LAYOUT, SweepArgs, NoEarlyStop, Resume>(a, blockIdx.x, NoEarlyStop{}, r);
+}
+
+// One ladder segment of a handle in the colour order (asp_sa_chains_advance_ladder, order 0).
+template <int M, int LAYOUT>
+__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_ladder(SweepArgs a, ResumeLadder r) {
+  sa_sweep_body<M, false, LAYOUT, SweepArgs, NoEarlyStop, ResumeLadder>(a, blockIdx.x, NoEarlyStop{}, r);
 }
 
 // Many PROBLEMS in one launch (asp_sa_anneal_batch): workgroup -> (problem, group of M replicas)
@@ -1609,6 +1668,22 @@ ResumeKernel resume_kernel_for(int m, int layout) {
   }
 }
 
+// ... and of a ladder segment: the same forms, one for one.
+using LadderKernel = void (*)(SweepArgs, ResumeLadder);
+LadderKernel ladder_kernel_for(int m, int layout) {
+  if (layout == kBits) return k_sa_sweep_ladder<1, kBits>;
+  if (layout == kGlobal) return k_sa_sweep_ladder<1, kGlobal>;
+  if (layout == kWide) return m == 4 ? k_sa_sweep_ladder<4, kWide> : nullptr;
+  if (layout == kNibbles) return m == 4 ? k_sa_sweep_ladder<4, kNibbles> : nullptr;
+  switch (m) {
+    case 1: return k_sa_sweep_ladder<1, kBytes>;
+    case 2: return k_sa_sweep_ladder<2, kBytes>;
+    case 4: return k_sa_sweep_ladder<4, kBytes>;
+    case 8: return k_sa_sweep_ladder<8, kBytes>;
+    default: return nullptr;
+  }
+}
+
 size_t sweep_lds_bytes(const asp::SaHostLayout &L, int layout) {
   // spins | delta[8] book[24] | flag (16 B) | meta[num_blocks]
   // ... | cache_ctl[4] | dirty[num_blocks] | inert[num_blocks] (each rounded up to 16 B)
@@ -2176,43 +2251,74 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
   return ASP_OK;
 }
 
+// One segment of a handle in the colour order (below); chain_betas: nullptr, or HOST [repetitions] — a
+// ladder segment, `betas` unused.
+int chains_advance_colour(asp_sa_chains *c, double const *betas, double const *chain_betas, uint32_t num_sweeps,
+                          int64_t *trace);
+
 }  // namespace
 
 namespace asp {
+
+int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace) {
+  return chains_advance_colour(c, betas, nullptr, num_sweeps, trace);
+}
+
+int sa_chains_advance_ladder_colour(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps,
+                                    int64_t *trace) {
+  return chains_advance_colour(c, nullptr, chain_betas, num_sweeps, trace);
+}
+
+}  // namespace asp
+
+namespace {
 
 // One segment of a handle in the colour order: the handle's original-order configurations are
 // permuted into the plan's block order (current and best, every chain its own), k_sa_sweep_resume
 // runs the sweeps from the carried integers with sweep index base c->sweeps_done, and both
 // configurations go back.  The launch is run_chains' minus teams: the same choice of chains per
 // group and spin layout, honouring asp_sa_set_launch / _set_packed / _set_wide; asp_sa_set_team
-// is ignored (a handle runs one workgroup per group of chains).
-int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace) {
+// is ignored (a handle runs one workgroup per group of chains).  A ladder segment takes the same form
+// with k_sa_sweep_ladder in place of k_sa_sweep_resume and one beta per (padded) chain in w_betas.
+int chains_advance_colour(asp_sa_chains *c, double const *betas, double const *chain_betas, uint32_t num_sweeps,
+                          int64_t *trace) {
   asp_sa_plan *p = c->plan;
-  const SaHostLayout &L = p->host;
+  const asp::SaHostLayout &L = p->host;
   const uint64_t K = L.num_spins;
   const uint32_t words = c->words, repetitions = c->repetitions;
   const ColourLaunch chosen = choose_colour_launch(p, repetitions, false, trace != nullptr);
   const int m = chosen.m, threads = chosen.threads, layout = chosen.layout;
   const size_t lds = sweep_lds_bytes(L, layout);
   if (lds > p->max_lds) {
-    return set_error(ASP_ERR_TOO_LARGE, "%zu B of LDS needed, %zu B available", lds, p->max_lds);
+    return asp::set_error(ASP_ERR_TOO_LARGE, "%zu B of LDS needed, %zu B available", lds, p->max_lds);
   }
-  ResumeKernel kernel = resume_kernel_for(m, layout);
-  if (!kernel) return set_error(ASP_ERR_INVALID, "no resumable sweep for %d chains per group", m);
+  const bool ladder = chain_betas != nullptr;
+  ResumeKernel kernel = ladder ? nullptr : resume_kernel_for(m, layout);
+  LadderKernel ladder_kernel = ladder ? ladder_kernel_for(m, layout) : nullptr;
+  if (!kernel && !ladder_kernel) {
+    return asp::set_error(ASP_ERR_INVALID, "no resumable sweep for %d chains per group", m);
+  }
+  const void *kernel_address = ladder ? reinterpret_cast<const void *>(ladder_kernel)
+                                      : reinterpret_cast<const void *>(kernel);
   const uint32_t groups = (repetitions + m - 1) / m;
   const uint64_t padded = static_cast<uint64_t>(groups) * m;
   hipStream_t s = p->stream;
-  StreamFence fence(s);
+  asp::StreamFence fence(s);
   if (chosen.global) ASP_TRY(p->w_spins.ensure(static_cast<uint64_t>(groups) * L.num_blocks));
-  ASP_TRY(p->w_betas.ensure(num_sweeps));
+  ASP_TRY(p->w_betas.ensure(ladder ? padded : num_sweeps));
   ASP_TRY(p->w_best.ensure(padded * L.num_blocks));
   ASP_TRY(p->w_cur_perm.ensure(padded * L.num_blocks));
   ASP_TRY(p->w_tracked.ensure(padded));
   ASP_TRY(p->w_accepted.ensure(padded));
   ASP_TRY(p->w_e_cur.ensure(padded));
-  ASP_TRY(p->w_betas.upload(betas, num_sweeps, s));
+  if (ladder) {
+    ASP_TRY(p->w_betas.upload(chain_betas, repetitions, s));
+  } else {
+    ASP_TRY(p->w_betas.upload(betas, num_sweeps, s));
+  }
   // (the chains padding the last group: all spins up, integers 0; their results are never read)
   if (padded > repetitions) {
+    if (ladder) ASP_HIP_TRY(hipMemsetAsync(p->w_betas.ptr + repetitions, 0, (padded - repetitions) * 8, s));
     const uint64_t tail = (padded - repetitions) * L.num_blocks * sizeof(uint64_t);
     ASP_HIP_TRY(hipMemsetAsync(p->w_best.ptr + static_cast<uint64_t>(repetitions) * L.num_blocks, 0, tail, s));
     ASP_HIP_TRY(hipMemsetAsync(p->w_cur_perm.ptr + static_cast<uint64_t>(repetitions) * L.num_blocks, 0, tail, s));
@@ -2224,11 +2330,11 @@ int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num
   ASP_HIP_TRY(hipMemcpyAsync(p->w_e_cur.ptr, c->e_cur.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
   ASP_HIP_TRY(hipMemcpyAsync(p->w_tracked.ptr, c->e_best.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
   ASP_HIP_TRY(hipMemcpyAsync(p->w_accepted.ptr, c->accepted.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
-  ASP_TRY(sa_permute_bits(p, c->x_cur.ptr, repetitions, p->w_cur_perm.ptr));
-  ASP_TRY(sa_permute_bits(p, c->x_best.ptr, repetitions, p->w_best.ptr));
+  ASP_TRY(asp::sa_permute_bits(p, c->x_cur.ptr, repetitions, p->w_cur_perm.ptr));
+  ASP_TRY(asp::sa_permute_bits(p, c->x_best.ptr, repetitions, p->w_best.ptr));
 
   SweepArgs args = plan_sweep_args(p, chosen);
-  args.betas = p->w_betas.ptr;
+  args.betas = ladder ? nullptr : p->w_betas.ptr;  // (a ladder segment never reads them)
   args.x0_perm = nullptr;
   args.best_perm = p->w_best.ptr;
   args.tracked = p->w_tracked.ptr;
@@ -2241,13 +2347,18 @@ int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num
     args.trace = p->w_trace.ptr;
   }
   if (p->use_field_cache && !chosen.packed) attach_field_cache(p, padded, &args);
-  Resume res{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done};
   if (lds > 64 * 1024) {
-    ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    ASP_HIP_TRY(hipFuncSetAttribute(kernel_address, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    static_cast<int>(lds)));
   }
   ASP_HIP_TRY(hipEventRecord(p->ev[1], s));
-  hipLaunchKernelGGL(kernel, dim3(groups), dim3(threads), lds, s, args, res);
+  if (ladder) {
+    const ResumeLadder res{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done, p->w_betas.ptr};
+    hipLaunchKernelGGL(ladder_kernel, dim3(groups), dim3(threads), lds, s, args, res);
+  } else {
+    const Resume res{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done};
+    hipLaunchKernelGGL(kernel, dim3(groups), dim3(threads), lds, s, args, res);
+  }
   ASP_HIP_TRY(hipGetLastError());
   ASP_HIP_TRY(hipEventRecord(p->ev[2], s));
   const dim3 grid((words + 3) / 4, (repetitions + kUnpermuteChains - 1) / kUnpermuteChains);
@@ -2276,7 +2387,7 @@ int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num
   return ASP_OK;
 }
 
-}  // namespace asp
+}  // namespace
 
 extern "C" {
 

@@ -533,6 +533,23 @@ void asp_sa_chains_destroy(asp_sa_chains *c);
 int asp_sa_chains_advance(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, uint32_t order,
                           int64_t *out_trace);
 
+/* A LADDER segment ("Ladder law"): every chain runs at its OWN inverse temperature,
+ * chain_betas: HOST [repetitions].  Afterwards chain r of the handle is in exactly the state it would
+ * have after asp_sa_chains_advance with betas = {chain_betas[r]} x num_sweeps on a handle that holds
+ * that one chain alone — replica id replica_offset + r, the same seed, start and sweeps_done: all five
+ * state arrays, sweeps_done and row r of out_trace.  Hence equal entries are asp_sa_chains_advance on a
+ * constant segment, bit for bit; ladder segments, ordinary segments, gather, resample, exchange and
+ * export / import alternate freely on a handle; and nothing depends on a launch choice.  Launch forms:
+ * those of asp_sa_chains_advance in either order (asp_sa_set_launch, _set_packed, _set_wide,
+ * _set_field_cache and asp_sa_set_shuffled_launch are honoured, lane packing included), except that
+ * the shuffled order always runs ONE team (asp_sa_set_shuffled_teams is ignored).
+ * ASP_ERR_INVALID, before any device work and before any output is written: a null handle, null
+ * chain_betas with repetitions > 0, an entry that is negative, NaN or infinite, an order other than 0
+ * or 1, sweeps_done + num_sweeps > 2^32 - 2.  num_sweeps = 0 runs nothing and writes column 0 of the
+ * trace; plans without spins and handles without chains run nothing. */
+int asp_sa_chains_advance_ladder(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps, uint32_t order,
+                                 int64_t *out_trace);
+
 /* The best configuration so far of every chain and its energy — what the closed call returns:
  * out_x[repetitions * ceil(K/64)], out_e[repetitions] (host or device pointers). */
 int asp_sa_chains_result(asp_sa_chains *c, uint64_t *out_x, double *out_e);
@@ -646,6 +663,31 @@ int asp_sa_chains_resample_batch(asp_sa_chains_resample_item const *items, uint3
 /* Device time (ms) of this thread's last asp_sa_chains_resample(_batch) call: from its first launch
  * (the energies) to the end of the gather, HIP events on the call's stream. */
 float asp_sa_chains_resample_last_ms(void);
+
+/* PARALLEL TEMPERING on a handle (law "ASP-PT-1"): the slots of a handle are the rungs
+ * of a temperature ladder (asp_sa_chains_advance_ladder), and a replica-exchange step swaps the
+ * configurations of neighbouring rungs ON THE DEVICE.  For a handle of R chains, slot k at chain_betas[k]:
+ *  1. E_r = the reported energy (asp_sa_energy's double) of chain r's CURRENT configuration — step 1 of
+ *     asp_sa_chains_resample;
+ *  2. the pairs are (k, k + 1) for every k = parity (mod 2) with k + 1 < R, parity 0 or 1: slots are
+ *     paired by index (the caller keeps the ladder sorted; that is neither required nor checked);
+ *  3. x_k = (beta_{k+1} - beta_k) * (E_k - E_{k+1}), one rounding per operation;
+ *  4. the pair swaps iff x_k <= 0 or u < expneg(x_k) — the annealer's acceptance rule — with
+ *     u = (v_k + 0.5) 2^-32, v_k = word 0 of Philox4x32-10(counter (k, sweeps_done, 0xFFFFFFFC, draw),
+ *     key seed): a counter no proposal, start, visiting order or resampling uses.  The swap
+ *     probability is min(1, exp((beta_{k+1} - beta_k)(E_{k+1} - E_k))), the standard exchange rule; a
+ *     colder slot that holds the higher energy always swaps;
+ *  5. source = the identity, except source[k] = k + 1 and source[k + 1] = k for a pair that swaps;
+ *  6. asp_sa_chains_gather with that map: configurations move, temperatures stay with the slots; all
+ *     five state arrays move (tracked energies are relative to a lineage); sweeps_done is unchanged.
+ * Outputs (HOST, each may be NULL), back in one copy: out_source[R], out_energy[R] (E_r before the step),
+ * out_accepted (the number of pairs that swapped).  R <= 1 or a parity without a pair: the identity,
+ * accepted = 0.  Handles with no chains or plans with no spins run nothing: energies 0, the identity.
+ * ASP_ERR_INVALID, before any device work and before any output is written: a null handle, null
+ * chain_betas with repetitions > 0, parity > 1, an entry of chain_betas that is negative, NaN or
+ * infinite.  asp_sa_last_total_ms of the plan is the device time of the step (energies to gather). */
+int asp_sa_chains_exchange(asp_sa_chains *c, double const *chain_betas, uint32_t parity, uint32_t draw,
+                           uint32_t *out_source, double *out_energy, uint32_t *out_accepted);
 
 /* MANY independent problems in one call — the shape of the reference's production job: tens of
  * thousands of sampled clusters, each solved with 64 repetitions x 5120 sweeps
