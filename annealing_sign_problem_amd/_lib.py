@@ -126,6 +126,36 @@ class SaChainsResampleItem(ctypes.Structure):
     ]
 
 
+class SaChainsLadderItem(ctypes.Structure):
+    """Mirror of ``asp_sa_chains_ladder_item`` (include/asp.h)."""
+
+    _fields_ = [
+        ("chains", c_void_p),
+        ("chain_betas", c_void_p),
+        ("num_sweeps", c_u32),
+        ("order", c_u32),
+        ("flags", c_u32),
+        ("out_trace", c_void_p),
+        ("out_tracked_best", c_void_p),
+        ("out_improved", c_void_p),
+    ]
+
+
+class SaChainsExchangeItem(ctypes.Structure):
+    """Mirror of ``asp_sa_chains_exchange_item`` (include/asp.h)."""
+
+    _fields_ = [
+        ("chains", c_void_p),
+        ("chain_betas", c_void_p),
+        ("parity", c_u32),
+        ("draw", c_u32),
+        ("flags", c_u32),
+        ("out_source", c_void_p),
+        ("out_energy", c_void_p),
+        ("out_accepted", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/asp.h declares
 SIGNATURES = {
     "asp_last_error": (ctypes.c_char_p, []),
@@ -220,6 +250,9 @@ SIGNATURES = {
     "asp_sa_chains_resample_last_ms": (c_float, []),
     "asp_sa_chains_advance_ladder": (c_int, [c_void_p, c_void_p, c_u32, c_u32, c_void_p]),
     "asp_sa_chains_exchange": (c_int, [c_void_p, c_void_p, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
+    "asp_sa_chains_advance_ladder_batch": (c_int, [ctypes.POINTER(SaChainsLadderItem), c_u32]),
+    "asp_sa_chains_exchange_batch": (c_int, [ctypes.POINTER(SaChainsExchangeItem), c_u32]),
+    "asp_sa_chains_exchange_last_ms": (c_float, []),
     "asp_sa_anneal_batch": (c_int, [ctypes.POINTER(SaBatchItem), c_u32]),
     "asp_sa_batch_last_ms": (c_float, []),
     "asp_sa_greedy": (c_int, [c_void_p, c_u32, c_void_p, c_void_p, ctypes.POINTER(c_u32)]),

@@ -41,6 +41,9 @@ __all__ = [
     "population_anneal",
     "population_anneal_batch",
     "parallel_tempering",
+    "parallel_tempering_batch",
+    "advance_ladder_chains",
+    "exchange_chains",
     "greedy_solve",
     "greedy_solve_batch",
     "signs_to_bits",
@@ -953,6 +956,143 @@ def parallel_tempering(hamiltonian: Hamiltonian, seed=None, number_rounds: int =
             if exchange and j + 1 < number_rounds:
                 chains.exchange(ladder, j & 1, 0)
         return chains.result(only_best=only_best)
+
+
+def _per_handle(value, n: int, name: str) -> list:
+    """``value`` as a list of ``n``: one value for all handles or one per handle."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        values = list(value)
+        if len(values) != n:
+            raise ValueError("%s: %d handles, %d values" % (name, n, len(values)))
+        return values
+    return [value] * n
+
+
+def advance_ladder_chains(chains, chain_betas, number_sweeps, sweep_order=None, progress: bool = False):
+    """``chains[i].advance_ladder(chain_betas[i], number_sweeps[i], sweep_order[i])`` for every ``i`` in
+    ONE device call (``asp_sa_chains_advance_ladder_batch``): exactly the same chains,
+    but the handles share launches the way ``advance_chains``' do.  ``chains``: ``Chains`` of distinct
+    Hamiltonians; ``chain_betas``: one array of ``repetitions`` inverse temperatures per handle;
+    ``number_sweeps`` and ``sweep_order``: one value for all or one per handle.  Returns what
+    ``advance_chains`` returns."""
+    chains = list(chains)
+    n = len(chains)
+    for c in chains:
+        if not isinstance(c, Chains):
+            raise TypeError("'chains' must hold Chains objects")
+    chain_betas = list(chain_betas)
+    if len(chain_betas) != n:
+        raise ValueError("advance_ladder_chains: %d handles, %d ladders" % (n, len(chain_betas)))
+    sweeps = [int(k) for k in _per_handle(number_sweeps, n, "advance_ladder_chains: 'number_sweeps'")]
+    orders = _per_handle(sweep_order, n, "advance_ladder_chains: 'sweep_order'")
+    if any(not 0 <= k < 2**32 for k in sweeps):
+        raise ValueError("'number_sweeps' must be a number of sweeps")
+    orders = [Chains._ORDERS[resolve_sweep_order(o)] for o in orders]
+    ladders = [c._chain_betas(b) for c, b in zip(chains, chain_betas)]
+    items = (_lib.SaChainsLadderItem * max(n, 1))()
+    out = []  # (also keeps the output buffers alive over the call)
+    for i, c in enumerate(chains):
+        items[i].chains = c._live()
+        items[i].chain_betas = ladders[i].ctypes.data
+        items[i].num_sweeps = sweeps[i]
+        items[i].order = orders[i]
+        items[i].flags = 0
+        if progress:
+            best = np.zeros(max(c.repetitions, 1), dtype=np.int64)
+            improved = ctypes.c_uint32(0)
+            items[i].out_tracked_best = best.ctypes.data
+            items[i].out_improved = ctypes.addressof(improved)
+            out.append((best, improved, c.repetitions))
+    _lib.check(_lib.load().asp_sa_chains_advance_ladder_batch(items, ctypes.c_uint32(n)))
+    if not progress:
+        return None
+    return [(best[:reps], int(improved.value)) for best, improved, reps in out]
+
+
+def exchange_chains(chains, chain_betas, parity, draws=0):
+    """``chains[i].exchange(chain_betas[i], parity[i], draws[i])`` for every ``i`` in ONE device call
+    (``asp_sa_chains_exchange_batch``): the same bits, but the selection and the gather
+    of all handles share launches and every output comes back in one copy.  ``parity`` and ``draws``:
+    one value for all or one per handle.  Returns ``[(source, energies, accepted), ...]``."""
+    chains = list(chains)
+    n = len(chains)
+    for c in chains:
+        if not isinstance(c, Chains):
+            raise TypeError("'chains' must hold Chains objects")
+    chain_betas = list(chain_betas)
+    if len(chain_betas) != n:
+        raise ValueError("exchange_chains: %d handles, %d ladders" % (n, len(chain_betas)))
+    parities = [int(x) for x in _per_handle(parity, n, "exchange_chains: 'parity'")]
+    draws = [int(x) for x in _per_handle(draws, n, "exchange_chains: 'draws'")]
+    if any(x not in (0, 1) for x in parities):
+        raise ValueError("'parity' must be 0 or 1")
+    if any(not 0 <= d < 2**32 for d in draws):
+        raise ValueError("'draws' must fit 32 bits")
+    ladders = [c._chain_betas(b) for c, b in zip(chains, chain_betas)]
+    items = (_lib.SaChainsExchangeItem * max(n, 1))()
+    out = []  # (also keeps the output buffers alive over the call)
+    for i, c in enumerate(chains):
+        source = np.zeros(c.repetitions, dtype=np.uint32)
+        energies = np.zeros(c.repetitions, dtype=np.float64)
+        accepted = ctypes.c_uint32(0)
+        items[i].chains = c._live()
+        items[i].chain_betas = ladders[i].ctypes.data
+        items[i].parity = parities[i]
+        items[i].draw = draws[i]
+        items[i].flags = 0
+        items[i].out_source = source.ctypes.data
+        items[i].out_energy = energies.ctypes.data
+        items[i].out_accepted = ctypes.addressof(accepted)
+        out.append((source, energies, accepted))
+    _lib.check(_lib.load().asp_sa_chains_exchange_batch(items, ctypes.c_uint32(n)))
+    return [(source, energies, int(accepted.value)) for source, energies, accepted in out]
+
+
+def parallel_tempering_batch(hamiltonians, seed=None, number_rounds: int = 512, sweeps_per_round: int = 10,
+                             beta0: Optional[float] = None, beta1: Optional[float] = None, repetitions: int = 64,
+                             only_best: bool = True, sweep_order: Optional[str] = None, exchange: bool = True):
+    """``[parallel_tempering(h, seed=seed, ...) for h in hamiltonians]`` with every round of all problems
+    in one ``advance_ladder_chains`` call and — except after the last round — one ``exchange_chains``
+    call: identical results.  ``seed`` as in ``anneal_batch``.  Chains stay on this rank."""
+    order = resolve_sweep_order(sweep_order)  # (first: a bad order fails without a GPU)
+    number_rounds, sweeps_per_round = int(number_rounds), int(sweeps_per_round)
+    if number_rounds < 1 or sweeps_per_round < 1:
+        raise ValueError("'number_rounds' and 'sweeps_per_round' must be positive")
+    hamiltonians = list(hamiltonians)
+    n = len(hamiltonians)
+    for h in hamiltonians:
+        if not isinstance(h, Hamiltonian):
+            raise TypeError("'hamiltonians' must hold Hamiltonian objects")
+    if len({id(h) for h in hamiltonians}) != n:
+        raise ValueError("parallel_tempering_batch: every problem needs its own Hamiltonian object")
+    repetitions = int(repetitions)
+    if repetitions < 1:
+        raise ValueError("'repetitions' must be positive")
+    if seed is None or np.ndim(seed) == 0:
+        seeds = [_resolve_seed(seed) for _ in range(n)] if seed is None else [_resolve_seed(seed)] * n
+    else:
+        seeds = [_resolve_seed(x) for x in seed]
+    ladders = []
+    for h in hamiltonians:
+        b0, b1 = beta0, beta1
+        if b0 is None or b1 is None:
+            info = h.info()
+            b0 = info.beta0_auto if b0 is None else b0
+            b1 = info.beta1_auto if b1 is None else b1
+        ladders.append(make_schedule(float(b0), float(b1), repetitions))
+    handles = []
+    try:
+        for h, s in zip(hamiltonians, seeds):
+            handles.append(Chains(h, seed=s, repetitions=repetitions))
+        for j in range(number_rounds):
+            advance_ladder_chains(handles, ladders, sweeps_per_round, sweep_order=order)
+            if exchange and j + 1 < number_rounds:
+                exchange_chains(handles, ladders, j & 1, 0)
+        results = [c.result(only_best=only_best) for c in handles]
+    finally:
+        for c in handles:
+            c.close()
+    return results
 
 
 def anneal_with_traces(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: int = 5120,

@@ -302,7 +302,8 @@ def _project_on_frozen(model: IsingModel, x: np.ndarray, frozen_spins) -> np.nda
 
 def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_sweeps: int = 5120,
                        repetitions: int = 64, sweep_order: Optional[str] = None, mode: str = "sa",
-                       check_every: Optional[int] = None, patience: Optional[int] = None):
+                       check_every: Optional[int] = None, patience: Optional[int] = None,
+                       method: str = "anneal"):
     """``[solve_ising_model(m, mode, f, seed, number_sweeps, repetitions) for m, f in
     zip(models, frozen_spins)]`` with all annealing chains of all models in ONE device call
     (``sa.anneal_batch``): the same result for every model, at the throughput of a full chip
@@ -310,7 +311,20 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
     one call (``sa.greedy_solve_batch``), with the same projection on the frozen spins.
     ``patience`` (not in the reference; default off): every model's ladder runs in segments of
     ``check_every`` sweeps (default 512) and stops once none of its chains improved for ``patience``
-    consecutive segments (``sa.anneal_batch_until``) — fewer sweeps, results that may differ."""
+    consecutive segments (``sa.anneal_batch_until``) — fewer sweeps, results that may differ.
+    ``method`` (not in the reference; default ``"anneal"``): ``"population"`` or ``"tempering"`` solve
+    every model with ``sa.population_anneal_batch`` / ``sa.parallel_tempering_batch`` instead, in
+    ``number_sweeps // 10`` steps / rounds of ten sweeps — the sweep count of the plain call."""
+    if method not in ("anneal", "population", "tempering"):
+        raise ValueError(
+            "invalid method specified: '{}'; expected 'anneal', 'population' or 'tempering'".format(method))
+    if method != "anneal":
+        if mode != "sa":
+            raise ValueError("'method' selects an annealing method: it needs mode='sa'")
+        if patience is not None:
+            raise ValueError("method='{}' cannot be combined with 'patience'".format(method))
+        if int(number_sweeps) < 10:
+            raise ValueError("method='{}' runs steps of ten sweeps: 'number_sweeps' must be at least 10".format(method))
     models = list(models)
     frozen = [None] * len(models) if frozen_spins is None else list(frozen_spins)
     if mode == "greedy":
@@ -319,6 +333,16 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
     if mode != "sa":
         raise ValueError(
             "invalid mode specified: '{}'; expected either 'sa' or 'greedy'".format(mode))
+    if method != "anneal":
+        hamiltonians = [m.ising_hamiltonian for m in models]
+        steps = int(number_sweeps) // 10
+        if method == "population":
+            best = sa.population_anneal_batch(hamiltonians, seed=seed, number_steps=steps, sweeps_per_step=10,
+                                              repetitions=repetitions, only_best=True, sweep_order=sweep_order)
+        else:
+            best = sa.parallel_tempering_batch(hamiltonians, seed=seed, number_rounds=steps, sweeps_per_round=10,
+                                               repetitions=repetitions, only_best=True, sweep_order=sweep_order)
+        return [_project_on_frozen(m, x, f) for m, (x, _), f in zip(models, best, frozen)]
     if patience is not None:
         best = sa.anneal_batch_until([m.ising_hamiltonian for m in models], seed=seed,
                                      number_sweeps=number_sweeps, repetitions=repetitions, only_best=True,

@@ -101,6 +101,106 @@ __global__ __launch_bounds__(256) void k_chains_progress(const ProgressRow *tabl
 
 thread_local float g_chains_batch_ms = 0.0f;
 
+// One validated item of asp_sa_chains_advance_batch (betas) or asp_sa_chains_advance_ladder_batch
+// (chain_betas); a call holds one kind only.
+struct BatchSegment {
+  asp_sa_chains *chains;
+  double const *betas, *chain_betas;
+  uint32_t num_sweeps, order;
+  int64_t *out_trace, *out_tracked_best;
+  uint32_t *out_improved;
+};
+
+int check_distinct_plans(const std::vector<BatchSegment> &items) {
+  std::vector<asp_sa_chains *> handles(items.size());
+  for (size_t i = 0; i < items.size(); ++i) handles[i] = items[i].chains;
+  return asp::check_distinct_plans(handles);
+}
+
+// The device half of the two batched advances: progress before, the segments, progress after.
+int run_batch_segments(const std::vector<BatchSegment> &items) {
+  const uint32_t count = static_cast<uint32_t>(items.size());
+  ASP_TRY(asp::bind_device());
+  // ---- progress, before: the best tracked energies of every handle that is asked about ----
+  bool wanted = false;
+  std::vector<ProgressRow> rows(count);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_chains *c = items[i].chains;
+    rows[i] = ProgressRow{c->e_cur.ptr, c->e_best.ptr, total, c->repetitions};
+    total += c->repetitions;
+    wanted = wanted || items[i].out_tracked_best || items[i].out_improved;
+  }
+  asp::DeviceBuffer<ProgressRow> d_rows;
+  asp::DeviceBuffer<long long> d_progress;  // [3][total] | improved[count] in the words behind
+  asp::ScopedStream progress_stream;
+  const uint64_t progress_words = 3 * total + (count + 1ull) / 2;
+  uint32_t *d_improved = nullptr;
+  if (total != 0) {
+    ASP_TRY(progress_stream.acquire());
+    ASP_TRY(d_rows.alloc(count));
+    ASP_TRY(d_progress.alloc(progress_words));
+    d_improved = reinterpret_cast<uint32_t *>(d_progress.ptr + 3 * total);
+    ASP_TRY(d_rows.upload(rows.data(), count, progress_stream.stream));
+    if (wanted) {
+      hipLaunchKernelGGL(k_chains_progress, dim3(count), dim3(256), 0, progress_stream.stream, d_rows.ptr, total,
+                         false, d_progress.ptr, d_improved);
+      ASP_HIP_TRY(hipGetLastError());
+    }
+    ASP_HIP_TRY(hipStreamSynchronize(progress_stream.stream));
+  }
+  // ---- the segments: per visiting order, the handles that fit in shared launches ----
+  std::vector<std::vector<int64_t>> starts(count);  // entry 0 of every traced row: NOT reset to 0
+  std::vector<asp::ChainsSegment> colour, shuffled;
+  for (uint32_t i = 0; i < count; ++i) {
+    const BatchSegment &it = items[i];
+    if (it.out_trace) starts[i] = it.chains->h_e_cur;
+    if (it.num_sweeps == 0 || nothing_to_run(it.chains)) {
+      if (it.out_trace) {  // (no spins: the energy stays where it is; no sweeps: the single entry below)
+        for (uint64_t k = 0; k < static_cast<uint64_t>(it.chains->repetitions) * (it.num_sweeps + 1ull); ++k) {
+          it.out_trace[k] = 0;
+        }
+      }
+      continue;
+    }
+    (it.order == 0 ? colour : shuffled)
+        .push_back(asp::ChainsSegment{it.chains, it.betas, it.num_sweeps, it.out_trace, it.chain_betas});
+  }
+  if (!shuffled.empty()) {
+    ASP_TRY(asp::sa_chains_advance_shuffled_batch(shuffled.data(), static_cast<uint32_t>(shuffled.size()),
+                                                  &g_chains_batch_ms));
+  }
+  if (!colour.empty()) {
+    ASP_TRY(asp::sa_chains_advance_colour_batch(colour.data(), static_cast<uint32_t>(colour.size()),
+                                                &g_chains_batch_ms));
+  }
+  // ---- progress, after: one gather launch and one copy for the whole batch ----
+  std::vector<long long> h_progress(progress_words, 0);
+  if (total != 0) {
+    hipLaunchKernelGGL(k_chains_progress, dim3(count), dim3(256), 0, progress_stream.stream, d_rows.ptr, total, true,
+                       d_progress.ptr, d_improved);
+    ASP_HIP_TRY(hipGetLastError());
+    ASP_TRY(d_progress.download(h_progress.data(), progress_words, progress_stream.stream));
+    ASP_HIP_TRY(hipStreamSynchronize(progress_stream.stream));
+  }
+  const uint32_t *h_improved = reinterpret_cast<const uint32_t *>(h_progress.data() + 3 * total);
+  for (uint32_t i = 0; i < count; ++i) {
+    const BatchSegment &it = items[i];
+    asp_sa_chains *c = it.chains;
+    const uint32_t R = c->repetitions;
+    for (uint32_t r = 0; r < R; ++r) c->h_e_cur[r] = h_progress[2 * total + rows[i].at + r];
+    if (it.out_tracked_best) {
+      for (uint32_t r = 0; r < R; ++r) it.out_tracked_best[r] = h_progress[total + rows[i].at + r];
+    }
+    if (it.out_improved) *it.out_improved = total != 0 ? h_improved[i] : 0u;
+    if (it.out_trace) {
+      for (uint32_t r = 0; r < R; ++r) it.out_trace[static_cast<uint64_t>(r) * (it.num_sweeps + 1ull)] = starts[i][r];
+    }
+    c->sweeps_done += it.num_sweeps;
+  }
+  return ASP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -259,99 +359,48 @@ int asp_sa_chains_advance_batch(asp_sa_chains_item const *items, uint32_t count)
       if (!(it.betas[t] >= 0.0)) return asp::set_error(ASP_ERR_INVALID, "item %u: betas[%u] is not >= 0", i, t);
     }
   }
-  {
-    // (a plan's work buffers serve one segment at a time; the same handle twice is the same plan twice,
-    // reported as what it is)
-    std::vector<std::pair<const asp_sa_plan *, uint32_t>> plans(count);
-    for (uint32_t i = 0; i < count; ++i) plans[i] = {items[i].chains->plan, i};
-    std::sort(plans.begin(), plans.end());
-    for (uint32_t i = 1; i < count; ++i) {
-      if (plans[i].first != plans[i - 1].first) continue;
-      const uint32_t a = plans[i - 1].second, b = plans[i].second;
-      if (items[a].chains == items[b].chains) {
-        return asp::set_error(ASP_ERR_INVALID, "items %u and %u are the same handle", a, b);
-      }
-      return asp::set_error(ASP_ERR_INVALID, "items %u and %u are handles of one plan", a, b);
-    }
-  }
-  ASP_TRY(asp::bind_device());
-  // ---- progress, before: the best tracked energies of every handle that is asked about ----
-  bool wanted = false;
-  std::vector<ProgressRow> rows(count);
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < count; ++i) {
-    const asp_sa_chains *c = items[i].chains;
-    rows[i] = ProgressRow{c->e_cur.ptr, c->e_best.ptr, total, c->repetitions};
-    total += c->repetitions;
-    wanted = wanted || items[i].out_tracked_best || items[i].out_improved;
-  }
-  asp::DeviceBuffer<ProgressRow> d_rows;
-  asp::DeviceBuffer<long long> d_progress;  // [3][total] | improved[count] in the words behind
-  asp::ScopedStream progress_stream;
-  const uint64_t progress_words = 3 * total + (count + 1ull) / 2;
-  uint32_t *d_improved = nullptr;
-  if (total != 0) {
-    ASP_TRY(progress_stream.acquire());
-    ASP_TRY(d_rows.alloc(count));
-    ASP_TRY(d_progress.alloc(progress_words));
-    d_improved = reinterpret_cast<uint32_t *>(d_progress.ptr + 3 * total);
-    ASP_TRY(d_rows.upload(rows.data(), count, progress_stream.stream));
-    if (wanted) {
-      hipLaunchKernelGGL(k_chains_progress, dim3(count), dim3(256), 0, progress_stream.stream, d_rows.ptr, total,
-                         false, d_progress.ptr, d_improved);
-      ASP_HIP_TRY(hipGetLastError());
-    }
-    ASP_HIP_TRY(hipStreamSynchronize(progress_stream.stream));
-  }
-  // ---- the segments: per visiting order, the handles that fit in shared launches ----
-  std::vector<std::vector<int64_t>> starts(count);  // entry 0 of every traced row: NOT reset to 0
-  std::vector<asp::ChainsSegment> colour, shuffled;
+  std::vector<BatchSegment> segments(count);
   for (uint32_t i = 0; i < count; ++i) {
     const asp_sa_chains_item &it = items[i];
-    if (it.out_trace) starts[i] = it.chains->h_e_cur;
-    if (it.num_sweeps == 0 || nothing_to_run(it.chains)) {
-      if (it.out_trace) {  // (no spins: the energy stays where it is; no sweeps: the single entry below)
-        for (uint64_t k = 0; k < static_cast<uint64_t>(it.chains->repetitions) * (it.num_sweeps + 1ull); ++k) {
-          it.out_trace[k] = 0;
-        }
-      }
-      continue;
-    }
-    (it.order == 0 ? colour : shuffled).push_back(asp::ChainsSegment{it.chains, it.betas, it.num_sweeps, it.out_trace});
+    segments[i] = BatchSegment{it.chains,    it.betas,         nullptr, it.num_sweeps, it.order,
+                               it.out_trace, it.out_tracked_best, it.out_improved};
   }
-  if (!shuffled.empty()) {
-    ASP_TRY(asp::sa_chains_advance_shuffled_batch(shuffled.data(), static_cast<uint32_t>(shuffled.size()),
-                                                  &g_chains_batch_ms));
-  }
-  if (!colour.empty()) {
-    ASP_TRY(asp::sa_chains_advance_colour_batch(colour.data(), static_cast<uint32_t>(colour.size()),
-                                                &g_chains_batch_ms));
-  }
-  // ---- progress, after: one gather launch and one copy for the whole batch ----
-  std::vector<long long> h_progress(progress_words, 0);
-  if (total != 0) {
-    hipLaunchKernelGGL(k_chains_progress, dim3(count), dim3(256), 0, progress_stream.stream, d_rows.ptr, total, true,
-                       d_progress.ptr, d_improved);
-    ASP_HIP_TRY(hipGetLastError());
-    ASP_TRY(d_progress.download(h_progress.data(), progress_words, progress_stream.stream));
-    ASP_HIP_TRY(hipStreamSynchronize(progress_stream.stream));
-  }
-  const uint32_t *h_improved = reinterpret_cast<const uint32_t *>(h_progress.data() + 3 * total);
+  ASP_TRY(check_distinct_plans(segments));
+  return run_batch_segments(segments);
+}
+
+int asp_sa_chains_advance_ladder_batch(asp_sa_chains_ladder_item const *items, uint32_t count) {
+  asp_clear_error();
+  g_chains_batch_ms = 0.0f;
+  if (count == 0) return ASP_OK;
+  if (!items) return asp::set_error(ASP_ERR_INVALID, "null items");
+  // ---- validation: every item before any device work and before any output is written ----
   for (uint32_t i = 0; i < count; ++i) {
-    const asp_sa_chains_item &it = items[i];
-    asp_sa_chains *c = it.chains;
-    const uint32_t R = c->repetitions;
-    for (uint32_t r = 0; r < R; ++r) c->h_e_cur[r] = h_progress[2 * total + rows[i].at + r];
-    if (it.out_tracked_best) {
-      for (uint32_t r = 0; r < R; ++r) it.out_tracked_best[r] = h_progress[total + rows[i].at + r];
+    const asp_sa_chains_ladder_item &it = items[i];
+    if (!it.chains) return asp::set_error(ASP_ERR_INVALID, "item %u: null chains handle", i);
+    const uint32_t R = it.chains->repetitions;
+    if (R && !it.chain_betas) return asp::set_error(ASP_ERR_INVALID, "item %u: null chain_betas", i);
+    if (it.order > 1u) return asp::set_error(ASP_ERR_INVALID, "item %u: order must be 0 (colour) or 1 (shuffled)", i);
+    if (it.flags != 0) return asp::set_error(ASP_ERR_INVALID, "item %u: unknown flags 0x%x", i, it.flags);
+    if (static_cast<uint64_t>(it.chains->sweeps_done) + it.num_sweeps > 0xFFFFFFFEull) {
+      return asp::set_error(ASP_ERR_INVALID, "item %u: %u sweeps after %u exceed the 2^32 - 2 sweep indices of a chain",
+                            i, it.num_sweeps, it.chains->sweeps_done);
     }
-    if (it.out_improved) *it.out_improved = total != 0 ? h_improved[i] : 0u;
-    if (it.out_trace) {
-      for (uint32_t r = 0; r < R; ++r) it.out_trace[static_cast<uint64_t>(r) * (it.num_sweeps + 1ull)] = starts[i][r];
+    for (uint32_t r = 0; r < R; ++r) {
+      // (an infinite beta times dE = 0 is not a number: the law needs a finite one)
+      if (!(it.chain_betas[r] >= 0.0) || std::isinf(it.chain_betas[r])) {
+        return asp::set_error(ASP_ERR_INVALID, "item %u: chain_betas[%u] is not a finite number >= 0", i, r);
+      }
     }
-    c->sweeps_done += it.num_sweeps;
   }
-  return ASP_OK;
+  std::vector<BatchSegment> segments(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_chains_ladder_item &it = items[i];
+    segments[i] = BatchSegment{it.chains,    nullptr,          it.chain_betas, it.num_sweeps, it.order,
+                               it.out_trace, it.out_tracked_best, it.out_improved};
+  }
+  ASP_TRY(check_distinct_plans(segments));
+  return run_batch_segments(segments);
 }
 
 int asp_sa_chains_result(asp_sa_chains *c, uint64_t *out_x, double *out_e) {

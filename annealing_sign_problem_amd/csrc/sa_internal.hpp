@@ -4,7 +4,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "asp_common.hpp"
@@ -89,6 +91,25 @@ struct asp_sa_chains {
 
 namespace asp {
 
+// What every batched call over handles checks once its own arguments are valid: the (non-null) handles
+// of a batch are distinct handles of distinct plans — a plan's work buffers serve one call at a time; the
+// same handle twice is the same plan twice, reported as what it is.  ASP_ERR_INVALID with both indices.
+inline int check_distinct_plans(const std::vector<asp_sa_chains *> &handles) {
+  const uint32_t count = static_cast<uint32_t>(handles.size());
+  std::vector<std::pair<const asp_sa_plan *, uint32_t>> plans(count);
+  for (uint32_t i = 0; i < count; ++i) plans[i] = {handles[i]->plan, i};
+  std::sort(plans.begin(), plans.end());
+  for (uint32_t i = 1; i < count; ++i) {
+    if (plans[i].first != plans[i - 1].first) continue;
+    const uint32_t a = plans[i - 1].second, b = plans[i].second;
+    if (handles[a] == handles[b]) {
+      return set_error(ASP_ERR_INVALID, "items %u and %u are the same handle", a, b);
+    }
+    return set_error(ASP_ERR_INVALID, "items %u and %u are handles of one plan", a, b);
+  }
+  return ASP_OK;
+}
+
 template <typename T>
 int upload_vector(DeviceBuffer<T> &dst, const std::vector<T> &src, hipStream_t stream) {
   ASP_TRY(dst.alloc(src.size()));
@@ -125,11 +146,16 @@ int sa_chains_advance_ladder_shuffled(asp_sa_chains *c, double const *chain_beta
 // plans with spins and chains, num_sweeps > 0), one visiting order at a time: every segment is exactly
 // its sa_chains_advance_colour / _shuffled call, the handles that fit share launches.  h_e_cur of the
 // handles is the caller's to refresh; adds the device time of the sweep launches to *sweep_ms.
+// A batch of LADDER segments (asp_sa_chains_advance_ladder_batch): chain_betas set in EVERY segment of
+// the call (HOST [repetitions], validated; `betas` unused) — every segment is exactly its
+// sa_chains_advance_ladder_colour / _shuffled call, in the shared launches' per-chain-beta forms.
+// Ladder and plain segments never share a call.
 struct ChainsSegment {
   asp_sa_chains *chains;
   double const *betas;
   uint32_t num_sweeps;
   int64_t *trace;  // nullptr, or HOST [repetitions][num_sweeps + 1]: the segment runs alone
+  double const *chain_betas = nullptr;  // a ladder segment: one inverse temperature per chain
 };
 int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms);
 int sa_chains_advance_shuffled_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms);

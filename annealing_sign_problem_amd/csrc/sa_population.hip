@@ -196,6 +196,56 @@ __global__ __launch_bounds__(kThreads) void k_exchange_select(ExchangeArgs a, ui
   if (swap) atomicAdd(accepted, 1u);
 }
 
+// The same steps for MANY handles in one launch (asp_sa_chains_exchange_batch): row i of `table`
+// describes live handle i, whose slots own entries [at, at + chains) of energy_out and of source and
+// whose counter is accepted[i] (zeroed before the launch).  blockIdx.x: handle; blockIdx.y strides over
+// the handle's pair threads j, each with exactly the ownership and the arithmetic of k_exchange_select.
+struct ExchangeRow {
+  const double *energy;  // [chains] reported energies of the current configurations
+  const double *beta;    // [chains] the slots' inverse temperatures
+  uint64_t seed;
+  uint64_t at;
+  uint32_t chains, sweeps_done, parity, draw;
+};
+__global__ __launch_bounds__(kThreads) void k_exchange_select_batch(const ExchangeRow *table,
+                                                                    uint64_t *__restrict__ energy_out,
+                                                                    uint32_t *__restrict__ source,
+                                                                    uint32_t *__restrict__ accepted) {
+  const ExchangeRow row = table[blockIdx.x];
+  const uint32_t R = row.chains;
+  uint64_t *row_energy = energy_out + row.at;
+  uint32_t *row_source = source + row.at;
+  const uint64_t pairs = R / 2u + 1ull;  // threads of the single launch: one more for a parity of 1
+  for (uint64_t j = static_cast<uint64_t>(blockIdx.y) * kThreads + threadIdx.x; j < pairs;
+       j += static_cast<uint64_t>(gridDim.y) * kThreads) {
+    const uint64_t k64 = row.parity + 2ull * j;
+    if (j == 0 && row.parity == 1u && R != 0u) {
+      row_energy[0] = static_cast<uint64_t>(__double_as_longlong(row.energy[0]));
+      row_source[0] = 0u;
+    }
+    if (k64 >= R) continue;
+    const uint32_t k = static_cast<uint32_t>(k64);
+    const double e0 = row.energy[k];
+    row_energy[k] = static_cast<uint64_t>(__double_as_longlong(e0));
+    if (k + 1u >= R) {  // (no partner)
+      row_source[k] = k;
+      continue;
+    }
+    const double e1 = row.energy[k + 1u];
+    row_energy[k + 1u] = static_cast<uint64_t>(__double_as_longlong(e1));
+    const double x = __dmul_rn(__dadd_rn(row.beta[k + 1u], -row.beta[k]), __dadd_rn(e0, -e1));
+    bool swap = x <= 0.0;
+    if (!swap) {
+      const Philox4 rnd = philox4x32_10(k, row.sweeps_done, 0xFFFFFFFCu, row.draw, static_cast<uint32_t>(row.seed),
+                                        static_cast<uint32_t>(row.seed >> 32));
+      swap = metropolis_accept_word(rnd.w[0], x);
+    }
+    row_source[k] = swap ? k + 1u : k;
+    row_source[k + 1u] = swap ? k : k + 1u;
+    if (swap) atomicAdd(accepted + blockIdx.x, 1u);
+  }
+}
+
 int ensure_second_set(asp_sa_chains *c) {
   const uint64_t state_words = static_cast<uint64_t>(c->repetitions) * c->words;
   ASP_TRY(c->x_cur_to.ensure(state_words));
@@ -258,6 +308,7 @@ struct Events {
 };
 
 thread_local float g_resample_ms = 0.0f;
+thread_local float g_exchange_ms = 0.0f;
 
 }  // namespace
 
@@ -362,6 +413,143 @@ int asp_sa_chains_exchange(asp_sa_chains *c, double const *chain_betas, uint32_t
   return ASP_OK;
 }
 
+float asp_sa_chains_exchange_last_ms(void) { return g_exchange_ms; }
+
+int asp_sa_chains_exchange_batch(asp_sa_chains_exchange_item const *items, uint32_t count) {
+  asp_clear_error();
+  g_exchange_ms = 0.0f;
+  if (count == 0) return ASP_OK;
+  if (!items) return asp::set_error(ASP_ERR_INVALID, "null items");
+  // ---- validation: every item before any device work and before any output is written ----
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_chains_exchange_item &it = items[i];
+    if (it.flags != 0) return asp::set_error(ASP_ERR_INVALID, "item %u: unknown flags 0x%x", i, it.flags);
+    if (!it.chains) return asp::set_error(ASP_ERR_INVALID, "item %u: null chains handle", i);
+    const uint32_t R = it.chains->repetitions;
+    if (R && !it.chain_betas) return asp::set_error(ASP_ERR_INVALID, "item %u: null chain_betas", i);
+    if (it.parity > 1u) return asp::set_error(ASP_ERR_INVALID, "item %u: parity must be 0 or 1", i);
+    for (uint32_t r = 0; r < R; ++r) {
+      if (!(it.chain_betas[r] >= 0.0) || std::isinf(it.chain_betas[r])) {
+        return asp::set_error(ASP_ERR_INVALID, "item %u: chain_betas[%u] is not a finite number >= 0", i, r);
+      }
+    }
+  }
+  {
+    std::vector<asp_sa_chains *> handles(count);
+    for (uint32_t i = 0; i < count; ++i) handles[i] = items[i].chains;
+    ASP_TRY(asp::check_distinct_plans(handles));
+  }
+  // ---- the live handles (chains and spins) and their places in the batch's back buffer ----
+  std::vector<uint32_t> live;
+  std::vector<ExchangeRow> select;
+  std::vector<double> h_beta;
+  uint64_t total = 0;
+  uint32_t most_pairs = 1;
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_chains *c = items[i].chains;
+    if (c->repetitions == 0 || c->plan->host.num_spins == 0) continue;
+    live.push_back(i);
+    select.push_back(ExchangeRow{nullptr, nullptr, c->seed, total, c->repetitions, c->sweeps_done, items[i].parity,
+                                 items[i].draw});
+    h_beta.insert(h_beta.end(), items[i].chain_betas, items[i].chain_betas + c->repetitions);
+    total += c->repetitions;
+    most_pairs = std::max(most_pairs, c->repetitions / 2u + 1u);
+  }
+  const uint32_t n = static_cast<uint32_t>(live.size());
+  // what comes back in one copy: energy[total] | source u32[total] | accepted u32[n]
+  const uint64_t source_at = total, accepted_at = source_at + (total + 1) / 2;
+  const uint64_t back_words = accepted_at + (n + 1ull) / 2;
+  std::vector<uint64_t> h_back(back_words, 0);
+  if (n != 0) {
+    ASP_TRY(asp::bind_device());
+    asp::DeviceBuffer<ExchangeRow> d_select;
+    asp::DeviceBuffer<GatherRow> d_gather;
+    asp::DeviceBuffer<uint64_t> d_back;
+    asp::DeviceBuffer<double> d_beta;
+    Events ev;
+    asp::ScopedStream batch;
+    ASP_TRY(batch.acquire());
+    hipStream_t s = batch.stream;
+    ASP_HIP_TRY(hipEventCreate(&ev.begin));
+    ASP_HIP_TRY(hipEventCreate(&ev.end));
+    ASP_TRY(d_select.alloc(n));
+    ASP_TRY(d_gather.alloc(n));
+    ASP_TRY(d_back.alloc(back_words));
+    ASP_TRY(d_beta.alloc(total));
+    std::vector<GatherRow> gather(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      asp_sa_chains *c = items[live[k]].chains;
+      asp_sa_plan *p = c->plan;
+      ASP_TRY(ensure_second_set(c));
+      ASP_TRY(p->w_x0_perm.ensure(static_cast<uint64_t>(c->repetitions) * p->host.num_blocks));
+      ASP_TRY(p->w_partial.ensure(static_cast<uint64_t>(c->repetitions) * p->host.num_blocks));
+      ASP_TRY(p->w_e.ensure(c->repetitions));
+      select[k].energy = p->w_e.ptr;
+      select[k].beta = d_beta.ptr + select[k].at;
+      gather[k] = gather_row(c, select[k].at);
+    }
+    // (declared after the buffers: on an early return every stream is waited for before they go)
+    struct PlanFences {
+      std::vector<hipStream_t> streams;
+      ~PlanFences() {
+        for (hipStream_t stream : streams) (void)hipStreamSynchronize(stream);
+      }
+    } fences;
+    fences.streams.push_back(s);
+    ASP_HIP_TRY(hipEventRecord(ev.begin, s));
+    // step 1: the reported energies of the current configurations, on every plan's own stream
+    for (uint32_t k = 0; k < n; ++k) {
+      asp_sa_chains *c = items[live[k]].chains;
+      asp_sa_plan *p = c->plan;
+      fences.streams.push_back(p->stream);
+      ASP_TRY(asp::sa_permute_bits(p, c->x_cur.ptr, c->repetitions, p->w_x0_perm.ptr));
+      ASP_TRY(asp::sa_energies_of_perm(p, p->w_x0_perm.ptr, c->repetitions, p->w_partial.ptr, p->w_e.ptr));
+      ASP_HIP_TRY(hipEventRecord(p->ev[0], p->stream));
+      ASP_HIP_TRY(hipStreamWaitEvent(s, p->ev[0], 0));
+    }
+    // steps 2-5 and 6: one launch each for the whole batch, then one copy back
+    ASP_TRY(d_select.upload(select.data(), n, s));
+    ASP_TRY(d_gather.upload(gather.data(), n, s));
+    ASP_TRY(d_beta.upload(h_beta.data(), total, s));
+    uint32_t *d_source = reinterpret_cast<uint32_t *>(d_back.ptr + source_at);
+    uint32_t *d_accepted = reinterpret_cast<uint32_t *>(d_back.ptr + accepted_at);
+    ASP_HIP_TRY(hipMemsetAsync(d_accepted, 0, (back_words - accepted_at) * sizeof(uint64_t), s));
+    const unsigned y = std::min((most_pairs + kThreads - 1) / kThreads, 1024u);
+    hipLaunchKernelGGL(k_exchange_select_batch, dim3(n, y), dim3(kThreads), 0, s, d_select.ptr, d_back.ptr, d_source,
+                       d_accepted);
+    ASP_HIP_TRY(hipGetLastError());
+    ASP_TRY(launch_gather(gather, d_gather.ptr, d_source, s));
+    ASP_HIP_TRY(hipEventRecord(ev.end, s));
+    ASP_TRY(d_back.download(h_back.data(), back_words, s));
+    ASP_HIP_TRY(hipStreamSynchronize(s));
+    ASP_HIP_TRY(hipEventElapsedTime(&g_exchange_ms, ev.begin, ev.end));
+  }
+  // ---- the handles' new state and the outputs ----
+  const uint32_t *h_source = reinterpret_cast<const uint32_t *>(h_back.data() + source_at);
+  const uint32_t *h_accepted = reinterpret_cast<const uint32_t *>(h_back.data() + accepted_at);
+  for (uint32_t k = 0; k < n; ++k) {
+    const asp_sa_chains_exchange_item &it = items[live[k]];
+    const uint64_t at = select[k].at;
+    const uint32_t R = it.chains->repetitions;
+    adopt(it.chains, h_source + at);
+    if (it.out_source) std::memcpy(it.out_source, h_source + at, R * sizeof(uint32_t));
+    if (it.out_energy) std::memcpy(it.out_energy, h_back.data() + at, R * sizeof(double));
+    if (it.out_accepted) *it.out_accepted = h_accepted[k];
+  }
+  for (uint32_t i = 0; i < count; ++i) {
+    const asp_sa_chains_exchange_item &it = items[i];
+    const uint32_t R = it.chains->repetitions;
+    if (R != 0 && it.chains->plan->host.num_spins != 0) continue;
+    // no chains or no spins: nothing runs; every energy is 0 and the map the identity
+    for (uint32_t r = 0; r < R; ++r) {
+      if (it.out_source) it.out_source[r] = r;
+      if (it.out_energy) it.out_energy[r] = 0.0;
+    }
+    if (it.out_accepted) *it.out_accepted = 0u;
+  }
+  return ASP_OK;
+}
+
 int asp_sa_chains_resample_batch(asp_sa_chains_resample_item const *items, uint32_t count) {
   asp_clear_error();
   g_resample_ms = 0.0f;
@@ -382,19 +570,9 @@ int asp_sa_chains_resample_batch(asp_sa_chains_resample_item const *items, uint3
     }
   }
   {
-    // (a plan's work buffers serve one call at a time; the same handle twice is the same plan twice,
-    // reported as what it is)
-    std::vector<std::pair<const asp_sa_plan *, uint32_t>> plans(count);
-    for (uint32_t i = 0; i < count; ++i) plans[i] = {items[i].chains->plan, i};
-    std::sort(plans.begin(), plans.end());
-    for (uint32_t i = 1; i < count; ++i) {
-      if (plans[i].first != plans[i - 1].first) continue;
-      const uint32_t a = plans[i - 1].second, b = plans[i].second;
-      if (items[a].chains == items[b].chains) {
-        return asp::set_error(ASP_ERR_INVALID, "items %u and %u are the same handle", a, b);
-      }
-      return asp::set_error(ASP_ERR_INVALID, "items %u and %u are handles of one plan", a, b);
-    }
+    std::vector<asp_sa_chains *> handles(count);
+    for (uint32_t i = 0; i < count; ++i) handles[i] = items[i].chains;
+    ASP_TRY(asp::check_distinct_plans(handles));
   }
   // ---- the live handles (chains and spins) and their places in the batch's planes ----
   std::vector<uint32_t> live;

@@ -1757,6 +1757,23 @@ __global__ __launch_bounds__(512) void k_sa_sweep_shuffled_batch(const ShuffledA
   shuffled_sweep_body<M, LAYOUT, 1, PK, false>(*a, __builtin_amdgcn_readfirstlane(slot.group));
 }
 
+// Many LADDER segments in one launch (asp_sa_chains_advance_ladder_batch, order 1): the same slot table
+// over descriptors that carry every problem's per-chain betas (ShuffledLadderArgsOf), one team.  Every
+// chain is the one k_sa_sweep_shuffled_ladder advances: the body is the same.
+using ShuffledLadderBatchArgs = ShuffledLadderArgsOf<ShuffledArgs>;
+template <int M, int LAYOUT, bool PK = false>
+__global__ __launch_bounds__(512) void k_sa_sweep_shuffled_ladder_batch(const ShuffledLadderBatchArgs *problems,
+                                                                        const ShuffledSlot *slots) {
+  using ConstArgs = const ShuffledLadderBatchArgs __attribute__((address_space(4)));
+  static_assert(kLadderArgs<ShuffledLadderBatchArgs __attribute__((address_space(4)))>,
+                "the body must see the descriptor as ladder arguments through the address space too");
+  const ShuffledSlot slot = slots[blockIdx.x];
+  if (slot.problem == 0xFFFFFFFFu) return;  // (padding of the XCD-aware slot table)
+  ConstArgs *a = reinterpret_cast<ConstArgs *>(
+      reinterpret_cast<uintptr_t>(problems + __builtin_amdgcn_readfirstlane(slot.problem)));
+  shuffled_sweep_body<M, LAYOUT, 1, PK, false>(*a, __builtin_amdgcn_readfirstlane(slot.group));
+}
+
 // The chains of an asp_sa_chains handle into and out of the form the sweep kernels
 // carry a chain in between two chunks: ShuffledArgs::state, [groups][K] with bit j of entry i = spin i
 // of chain g * m + j is -1 — a byte per spin, or kGlobal's 32-bit word (T).  The handle keeps every
@@ -2860,6 +2877,46 @@ ShuffledBatchKernel shuffled_batch_kernel_for(int m, int layout, bool packed_lan
   }
 }
 
+// The ladder form of the same kernel (run_shuffled_group with ShuffledRun::chain_betas).
+using ShuffledLadderBatchKernel = void (*)(const ShuffledLadderBatchArgs *, const ShuffledSlot *);
+
+ShuffledLadderBatchKernel shuffled_ladder_batch_kernel_for(int m, int layout, bool packed_lanes) {
+  if (packed_lanes) {
+    if (layout != kWide) return nullptr;
+    switch (m) {
+      case 1: return k_sa_sweep_shuffled_ladder_batch<1, kWide, true>;
+      case 2: return k_sa_sweep_shuffled_ladder_batch<2, kWide, true>;
+      case 4: return k_sa_sweep_shuffled_ladder_batch<4, kWide, true>;
+      default: return nullptr;
+    }
+  }
+  if (layout == kWide) {
+    switch (m) {
+      case 1: return k_sa_sweep_shuffled_ladder_batch<1, kWide>;
+      case 2: return k_sa_sweep_shuffled_ladder_batch<2, kWide>;
+      case 4: return k_sa_sweep_shuffled_ladder_batch<4, kWide>;
+      default: return nullptr;
+    }
+  }
+  if (layout == kNibbles) {
+    switch (m) {
+      case 1: return k_sa_sweep_shuffled_ladder_batch<1, kNibbles>;
+      case 2: return k_sa_sweep_shuffled_ladder_batch<2, kNibbles>;
+      case 4: return k_sa_sweep_shuffled_ladder_batch<4, kNibbles>;
+      default: return nullptr;
+    }
+  }
+  if (layout == kBits) return m == 1 ? k_sa_sweep_shuffled_ladder_batch<1, kBits> : nullptr;
+  if (layout == kGlobal) return m == 1 ? k_sa_sweep_shuffled_ladder_batch<1, kGlobal> : nullptr;
+  switch (m) {
+    case 1: return k_sa_sweep_shuffled_ladder_batch<1, kBytes>;
+    case 2: return k_sa_sweep_shuffled_ladder_batch<2, kBytes>;
+    case 4: return k_sa_sweep_shuffled_ladder_batch<4, kBytes>;
+    case 8: return k_sa_sweep_shuffled_ladder_batch<8, kBytes>;
+    default: return nullptr;
+  }
+}
+
 struct EventPool {
   std::vector<hipEvent_t> events;
   ~EventPool() {
@@ -2941,8 +2998,17 @@ int move_group_state(const std::vector<ShuffledRun *> &runs, bool in, hipStream_
 // per problem and chunk does not overlap on the device however many streams it is spread over
 // (64 clusters: 21 s, as long as one after the other); the chip needs the workgroups of many
 // problems inside ONE grid.  Every chain is the one its own asp_sa_anneal_shuffled call produces.
+// A group of LADDER runs (ShuffledRun::chain_betas set in every one; ladder and plain runs never share
+// a group): the same launches with the ladder batch kernels over ShuffledLadderArgsOf descriptors,
+// every run's chain_betas pointing at its own padded d_betas.
 int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
   const uint32_t P = static_cast<uint32_t>(runs.size());
+  const bool ladder = runs[0]->chain_betas != nullptr;
+  for (ShuffledRun *r : runs) {
+    if ((r->chain_betas != nullptr) != ladder) {
+      return asp::set_error(ASP_ERR_INVALID, "ladder and plain segments cannot share launches");
+    }
+  }
   const uint32_t num_sweeps = runs[0]->num_sweeps;
   // one block size for the shared order launch: the largest any problem wants (the workgroups of
   // a smaller problem retire the wavefronts beyond its own OrderArgs::threads at once)
@@ -2957,6 +3023,7 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
   // early error return)
   DeviceBuffer<OrderArgs> d_oargs, d_oargs_wide;
   DeviceBuffer<ShuffledArgs> d_sargs;
+  DeviceBuffer<ShuffledLadderBatchArgs> d_largs;  // (a ladder group: in place of d_sargs)
   asp::ScopedStream order_stream[ShuffledRun::kLanes];
   for (auto &o : order_stream) ASP_TRY(o.acquire());
   // Classes of KERNEL: (layout, lane packing).  Wavefronts per workgroup and spins per block are
@@ -3038,7 +3105,11 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
                      [](const std::unique_ptr<Class> &x, const std::unique_ptr<Class> &y) { return x->lds > y->lds; });
     // (a kernel is keyed by (m, layout, packing), a class also by its wavefronts and block size:
     // classes may share a kernel, and its dynamic-LDS limit must cover the largest of them)
-    std::vector<std::pair<ShuffledBatchKernel, size_t>> kernel_lds;
+    std::vector<std::pair<const void *, size_t>> kernel_lds;
+    auto class_kernel = [&](int m, int layout, bool packed_lanes) -> const void * {
+      return ladder ? reinterpret_cast<const void *>(shuffled_ladder_batch_kernel_for(m, layout, packed_lanes))
+                    : reinterpret_cast<const void *>(shuffled_batch_kernel_for(m, layout, packed_lanes));
+    };
     for (auto &c : classes) {
       // the longest problems first: a workgroup's time is sweeps x levels x one block visit whatever
       // the cluster's size, but the large clusters have more levels and wider rows
@@ -3067,7 +3138,7 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
       ASP_TRY(c->slots.alloc(slots.size()));
       ASP_TRY(c->slots.upload(slots.data(), slots.size(), c->stream.stream));
       ASP_HIP_TRY(hipStreamSynchronize(c->stream.stream));  // `slots` dies with this scope
-      ShuffledBatchKernel kernel = shuffled_batch_kernel_for(c->m, c->layout, c->packed_lanes);
+      const void *kernel = class_kernel(c->m, c->layout, c->packed_lanes);
       if (!kernel) return asp::set_error(ASP_ERR_INVALID, "no batched shuffled kernel for %d chains per group", c->m);
       bool seen = false;
       for (auto &k : kernel_lds) {
@@ -3086,8 +3157,8 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
     }
     for (auto &k : kernel_lds) {
       if (k.second > 64 * 1024) {
-        ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k.first),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(k.second)));
+        ASP_HIP_TRY(hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        static_cast<int>(k.second)));
       }
     }
     // the wide order launches (large clusters): shapes for the largest of them; problems of the
@@ -3131,9 +3202,20 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
     }
     hipStream_t os0 = order_stream[0].stream;
     ASP_TRY(d_oargs.ensure(oargs.size()));
-    ASP_TRY(d_sargs.ensure(sargs.size()));
     ASP_TRY(d_oargs.upload(oargs.data(), oargs.size(), os0));
-    ASP_TRY(d_sargs.upload(sargs.data(), sargs.size(), os0));
+    std::vector<ShuffledLadderBatchArgs> largs;  // (alive until os0 has been waited for, below)
+    if (ladder) {
+      largs.resize(sargs.size());
+      for (size_t k = 0; k < sargs.size(); ++k) {
+        static_cast<ShuffledArgs &>(largs[k]) = sargs[k];
+        largs[k].chain_betas = runs[k % P]->d_betas.ptr;  // [padded], the padding chains' values 0 (setup())
+      }
+      ASP_TRY(d_largs.ensure(largs.size()));
+      ASP_TRY(d_largs.upload(largs.data(), largs.size(), os0));
+    } else {
+      ASP_TRY(d_sargs.ensure(sargs.size()));
+      ASP_TRY(d_sargs.upload(sargs.data(), sargs.size(), os0));
+    }
     if (Pw) {
       ASP_TRY(d_oargs_wide.ensure(oargs_wide.size()));
       ASP_TRY(d_oargs_wide.upload(oargs_wide.data(), oargs_wide.size(), os0));
@@ -3172,9 +3254,15 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
       for (auto &c : classes) {
         hipStream_t cs = c->stream.stream;
         if (now) ASP_HIP_TRY(hipStreamWaitEvent(cs, ordered[which], 0));
-        ShuffledBatchKernel kernel = shuffled_batch_kernel_for(c->m, c->layout, c->packed_lanes);
-        hipLaunchKernelGGL(kernel, dim3(c->num_slots), dim3(c->waves * 64), c->lds, cs,
-                           d_sargs.ptr + static_cast<size_t>(turn) * P, c->slots.ptr);
+        if (ladder) {
+          ShuffledLadderBatchKernel kernel = shuffled_ladder_batch_kernel_for(c->m, c->layout, c->packed_lanes);
+          hipLaunchKernelGGL(kernel, dim3(c->num_slots), dim3(c->waves * 64), c->lds, cs,
+                             d_largs.ptr + static_cast<size_t>(turn) * P, c->slots.ptr);
+        } else {
+          ShuffledBatchKernel kernel = shuffled_batch_kernel_for(c->m, c->layout, c->packed_lanes);
+          hipLaunchKernelGGL(kernel, dim3(c->num_slots), dim3(c->waves * 64), c->lds, cs,
+                             d_sargs.ptr + static_cast<size_t>(turn) * P, c->slots.ptr);
+        }
         ASP_HIP_TRY(hipGetLastError());
         ASP_HIP_TRY(hipEventRecord(c->swept[which], cs));
       }
@@ -3397,7 +3485,11 @@ int sa_chains_advance_shuffled_batch(const ChainsSegment *segs, uint32_t count, 
   auto alone = [&](const ChainsSegment &g) -> int {
     asp_sa_plan *p = g.chains->plan;
     p->last_sweep_ms = p->last_total_ms = 0.0f;
-    ASP_TRY(sa_chains_advance_shuffled(g.chains, g.betas, g.num_sweeps, g.trace));
+    if (g.chain_betas) {
+      ASP_TRY(sa_chains_advance_ladder_shuffled(g.chains, g.chain_betas, g.num_sweeps, g.trace));
+    } else {
+      ASP_TRY(sa_chains_advance_shuffled(g.chains, g.betas, g.num_sweeps, g.trace));
+    }
     if (sweep_ms) *sweep_ms += p->last_sweep_ms;
     return ASP_OK;
   };
@@ -3452,6 +3544,7 @@ int sa_chains_advance_shuffled_batch(const ChainsSegment *segs, uint32_t count, 
     r.p = c->plan;
     r.seed = c->seed;
     r.betas = segs[i].betas;
+    r.chain_betas = segs[i].chain_betas;  // (a batch of ladder segments: set in every one)
     r.num_sweeps = segs[i].num_sweeps;
     r.repetitions = c->repetitions;
     r.replica_offset = c->replica_offset;

@@ -1005,6 +1005,32 @@ __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_resume_batch(ResumeBat
                                   Resume{d->r.cur_perm, d->r.e_cur, d->r.t0});
 }
 
+// Many LADDER segments in one launch (asp_sa_chains_advance_ladder_batch, order 0): the same table of
+// slots, the handle's ResumeLadder part beside its SweepArgs — chain_betas points at the handle's
+// [groups * M] values inside the batch's one concatenated buffer (the chains padding a last group: 0).
+// Every chain is the one k_sa_sweep_ladder advances: the body is the same.
+struct LadderProblem {
+  SweepArgs s;  // betas: nullptr (never read); trace: nullptr (a traced segment runs alone)
+  ResumeLadder r;
+};
+struct LadderBatchArgs {
+  const LadderProblem *problems;
+  const BatchSlot *slots;  // [8][slots_per_xcd]
+  uint32_t slots_per_xcd;
+};
+
+template <int M, int LAYOUT>
+__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_ladder_batch(LadderBatchArgs b) {
+  const BatchSlot slot = b.slots[(blockIdx.x & 7u) * b.slots_per_xcd + (blockIdx.x >> 3)];
+  const uint32_t problem = __builtin_amdgcn_readfirstlane(slot.problem);
+  if (problem == 0xFFFFFFFFu) return;
+  // (the constant address space: see k_sa_sweep_batch)
+  using ConstProblem = const LadderProblem __attribute__((address_space(4)));
+  ConstProblem *d = reinterpret_cast<ConstProblem *>(reinterpret_cast<uintptr_t>(b.problems + problem));
+  sa_sweep_body<M, false, LAYOUT>(d->s, __builtin_amdgcn_readfirstlane(slot.group), NoEarlyStop{},
+                                  ResumeLadder{d->r.cur_perm, d->r.e_cur, d->r.t0, d->r.chain_betas});
+}
+
 // ---------------------------------------------------------------------------
 // Team sweep: ONE chain spread over G workgroups (few chains on a large cluster)
 // ---------------------------------------------------------------------------
@@ -3026,9 +3052,20 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
 // per position would fit (the nibble class has no resume form), and the closed batch's tuning aid
 // ASP_BATCH_M is not read (chains per workgroup never change a result).
 
+// A batch of LADDER segments (asp_sa_chains_advance_ladder_batch; every segment with chain_betas): the
+// same grouping, class rule, LDS limit and state permute, with LadderProblem descriptors and
+// k_sa_sweep_ladder_batch; the per-chain betas of all handles go up in the one concatenated buffer, every
+// handle's part padded with zeros to whole groups; the segments that run alone take
+// sa_chains_advance_ladder_colour.
+
 namespace asp {
 
-int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms) {
+namespace {
+
+template <bool LADDER>
+int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms) {
+  using Problem = std::conditional_t<LADDER, LadderProblem, ResumeProblem>;
+  using ProblemBatchArgs = std::conditional_t<LADDER, LadderBatchArgs, ResumeBatchArgs>;
   struct Entry {
     uint32_t seg;
     uint32_t waves;
@@ -3061,7 +3098,11 @@ int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, fl
   for (uint32_t i : alone) {
     asp_sa_plan *p = segs[i].chains->plan;
     p->last_sweep_ms = p->last_total_ms = 0.0f;
-    ASP_TRY(sa_chains_advance_colour(segs[i].chains, segs[i].betas, segs[i].num_sweeps, segs[i].trace));
+    if constexpr (LADDER) {
+      ASP_TRY(sa_chains_advance_ladder_colour(segs[i].chains, segs[i].chain_betas, segs[i].num_sweeps, segs[i].trace));
+    } else {
+      ASP_TRY(sa_chains_advance_colour(segs[i].chains, segs[i].betas, segs[i].num_sweeps, segs[i].trace));
+    }
     if (sweep_ms) *sweep_ms += p->last_sweep_ms;
   }
   if (entries.empty()) return ASP_OK;
@@ -3107,7 +3148,7 @@ int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, fl
     n_cache += padded * L.num_blocks * 64ull;
     n_chains += c->repetitions;
     entries[k].beta_at = n_betas;
-    n_betas += segs[entries[k].seg].num_sweeps;
+    n_betas += LADDER ? padded : segs[entries[k].seg].num_sweeps;  // (a ladder: one beta per padded chain)
     use_cache = use_cache && c->plan->use_field_cache;
   }
   if (n_cache * sizeof(double) > (32ull << 30)) use_cache = false;
@@ -3120,7 +3161,7 @@ int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, fl
   DeviceBuffer<uint64_t> d_best, d_cur;
   DeviceBuffer<long long> d_tracked, d_e_cur;
   DeviceBuffer<unsigned long long> d_accepted;
-  DeviceBuffer<ResumeProblem> d_problems;
+  DeviceBuffer<Problem> d_problems;
   DeviceBuffer<ChainsIo> d_io;
   DeviceBuffer<BatchSlot> d_slots, d_chains_in, d_chains_out;
   StreamFence fence(s);
@@ -3135,8 +3176,8 @@ int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, fl
     use_cache = false;
   }
   // ---- descriptors ----
-  std::vector<double> h_betas(n_betas);
-  std::vector<ResumeProblem> h_problems(entries.size());
+  std::vector<double> h_betas(n_betas, 0.0);  // (a ladder: the chains padding a last group stay 0)
+  std::vector<Problem> h_problems(entries.size());
   std::vector<ChainsIo> h_io(entries.size());
   std::vector<BatchSlot> h_chains_in, h_chains_out;
   h_chains_in.reserve(n_stat);
@@ -3146,12 +3187,16 @@ int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, fl
     asp_sa_chains *c = seg.chains;
     const asp_sa_plan *p = c->plan;
     const SaHostLayout &L = p->host;
-    std::copy(seg.betas, seg.betas + seg.num_sweeps, h_betas.begin() + entries[k].beta_at);
+    if constexpr (LADDER) {
+      std::copy(seg.chain_betas, seg.chain_betas + c->repetitions, h_betas.begin() + entries[k].beta_at);
+    } else {
+      std::copy(seg.betas, seg.betas + seg.num_sweeps, h_betas.begin() + entries[k].beta_at);
+    }
     ColourLaunch form;
     form.wide = entries[k].layout == kWide;
-    ResumeProblem rp{};
+    Problem rp{};
     rp.s = plan_sweep_args(p, form);
-    rp.s.betas = d_betas.ptr + entries[k].beta_at;
+    rp.s.betas = LADDER ? nullptr : d_betas.ptr + entries[k].beta_at;  // (a ladder segment never reads them)
     rp.s.x0_perm = nullptr;
     rp.s.best_perm = d_best.ptr + off[k].perm;
     rp.s.tracked = d_tracked.ptr + off[k].stat;
@@ -3162,7 +3207,12 @@ int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, fl
     rp.s.field_cache = use_cache ? d_cache.ptr + off[k].cache : nullptr;
     rp.s.cache_enter_flips = cache_enter_flips_of(L);
     rp.s.trace = nullptr;
-    rp.r = Resume{d_cur.ptr + off[k].perm, d_e_cur.ptr + off[k].stat, c->sweeps_done};
+    if constexpr (LADDER) {
+      rp.r = ResumeLadder{d_cur.ptr + off[k].perm, d_e_cur.ptr + off[k].stat, c->sweeps_done,
+                          d_betas.ptr + entries[k].beta_at};
+    } else {
+      rp.r = Resume{d_cur.ptr + off[k].perm, d_e_cur.ptr + off[k].stat, c->sweeps_done};
+    }
     h_problems[k] = rp;
     ChainsIo io{};
     io.x_cur = c->x_cur.ptr;
@@ -3251,12 +3301,22 @@ int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, fl
   for (auto &e : ev) ASP_HIP_TRY(hipEventCreate(&e));
   ASP_HIP_TRY(hipEventRecord(ev[0], s));
   // ---- one sweep launch per class, each on its own stream so that they share the chip ----
-  using Kernel = void (*)(ResumeBatchArgs);
-  Kernel kernel_of_layout[2] = {k_sa_sweep_resume_batch<4, kWide>, nullptr};  // [class % 2]
-  switch (m) {
-    case 1: kernel_of_layout[1] = k_sa_sweep_resume_batch<1, kBytes>; break;
-    case 2: kernel_of_layout[1] = k_sa_sweep_resume_batch<2, kBytes>; break;
-    default: kernel_of_layout[1] = k_sa_sweep_resume_batch<4, kBytes>; break;
+  using Kernel = void (*)(ProblemBatchArgs);
+  Kernel kernel_of_layout[2] = {nullptr, nullptr};  // [class % 2]
+  if constexpr (LADDER) {
+    kernel_of_layout[0] = k_sa_sweep_ladder_batch<4, kWide>;
+    switch (m) {
+      case 1: kernel_of_layout[1] = k_sa_sweep_ladder_batch<1, kBytes>; break;
+      case 2: kernel_of_layout[1] = k_sa_sweep_ladder_batch<2, kBytes>; break;
+      default: kernel_of_layout[1] = k_sa_sweep_ladder_batch<4, kBytes>; break;
+    }
+  } else {
+    kernel_of_layout[0] = k_sa_sweep_resume_batch<4, kWide>;
+    switch (m) {
+      case 1: kernel_of_layout[1] = k_sa_sweep_resume_batch<1, kBytes>; break;
+      case 2: kernel_of_layout[1] = k_sa_sweep_resume_batch<2, kBytes>; break;
+      default: kernel_of_layout[1] = k_sa_sweep_resume_batch<4, kBytes>; break;
+    }
   }
   // (a kernel serves every wavefront class of its layout, on streams that run side by side: its
   // dynamic LDS limit is set once, to the largest of them, before the first launch)
@@ -3275,7 +3335,7 @@ int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, fl
     ASP_TRY(class_stream[cl].acquire());
     hipStream_t cs = class_stream[cl].stream;
     ASP_HIP_TRY(hipStreamWaitEvent(cs, ev[0], 0));
-    ResumeBatchArgs b{d_problems.ptr, d_slots.ptr + launches[cl].slot_at, launches[cl].slots_per_xcd};
+    ProblemBatchArgs b{d_problems.ptr, d_slots.ptr + launches[cl].slot_at, launches[cl].slots_per_xcd};
     const Kernel kernel = kernel_of_layout[cl % 2];
     hipLaunchKernelGGL(kernel, dim3(8u * launches[cl].slots_per_xcd), dim3(64u * kWaves[cl / 2]),
                        launches[cl].lds, cs, b);
@@ -3302,6 +3362,13 @@ int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, fl
     p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_chains_batch_last_ms
   }
   return ASP_OK;
+}
+
+}  // namespace
+
+int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms) {
+  if (count != 0 && segs[0].chain_betas) return chains_advance_colour_batch<true>(segs, count, sweep_ms);
+  return chains_advance_colour_batch<false>(segs, count, sweep_ms);
 }
 
 }  // namespace asp

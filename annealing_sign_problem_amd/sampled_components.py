@@ -269,8 +269,10 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
 
 
 def early_stop_of(args) -> dict:
-    """--anneal-patience / --anneal-check-every as the ``early_stop`` keyword of :func:`anneal_staged`
+    """--anneal-patience / --anneal-check-every / --anneal-method as the ``early_stop`` keyword of :func:`anneal_staged`
     and :func:`process_clusters_batched`; empty without them, so that every call is the one it was."""
+    if getattr(args, "anneal_method", "anneal") != "anneal":  # (never together with --anneal-patience)
+        return {"early_stop": {"method": args.anneal_method}}
     if getattr(args, "anneal_patience", None) is None:
         return {}
     return {"early_stop": {"patience": args.anneal_patience, "check_every": args.anneal_check_every}}
@@ -280,7 +282,11 @@ def anneal_staged(staged, clusters: Sequence[np.ndarray], annealing: bool,
                   sweep_order: Optional[str] = None,
                   early_stop: Optional[dict] = None) -> List[List[OptimizationResult]]:
     """Second half: the annealing of ALL staged models — every cluster at every order — in one
-    batched device call, scored and sorted back into one list of results per cluster."""
+    batched device call, scored and sorted back into one list of results per cluster.
+    ``early_stop``: despite its name (it began as the early stopping alone) the dict of EVERY extra
+    keyword of :func:`common.solve_ising_models` that the command line selects, passed on as it is —
+    ``{"patience": N, "check_every": S}`` (--anneal-patience) or ``{"method": "population" |
+    "tempering"}`` (--anneal-method, which selects another algorithm); see :func:`early_stop_of`."""
     if annealing and staged:
         started = time.perf_counter()
         solutions = common.solve_ising_models([m for _, m, _, _, _ in staged],
@@ -310,7 +316,9 @@ def process_clusters_batched(clusters: Sequence[np.ndarray], hamiltonian, ground
                              early_stop: Optional[dict] = None) -> List[List[OptimizationResult]]:
     """``[process_cluster(c, ...) for c in clusters]`` with the annealing of ALL models — every
     cluster at every order — in one batched device call (:func:`stage_clusters`, then
-    :func:`anneal_staged`); the results are identical to the per-cluster loop."""
+    :func:`anneal_staged`); the results are identical to the per-cluster loop.  ``early_stop``: the
+    extra keywords of :func:`common.solve_ising_models` (early stopping or the annealing method), as in
+    :func:`anneal_staged`."""
     staged = stage_clusters(clusters, hamiltonian, ground_state, noisy_ground_state, noisy_log_coeff_fn,
                             order, global_cutoff, jobs, **({"greedy_batch": True} if greedy_batch else {}))
     return anneal_staged(staged, clusters, annealing, sweep_order, **({"early_stop": early_stop} if early_stop else {}))
@@ -349,6 +357,12 @@ def parse_command_line(argv=None):
                              "by default: early stopping changes the results")
     parser.add_argument("--anneal-check-every", type=int, default=None, metavar="S",
                         help="sweeps per segment of --anneal-patience (default 512)")
+    parser.add_argument("--anneal-method", type=str, default="anneal", choices=["anneal", "population", "tempering"],
+                        help="how the batched annealing solves a model: 'anneal' (default: the schedule of "
+                             "the reference), 'population' (population annealing, population_anneal_batch) or "
+                             "'tempering' (parallel tempering, parallel_tempering_batch), both in steps of ten "
+                             "sweeps with the same sweep count.  Needs --annealing and --batch > 1, and is not "
+                             "combined with --anneal-patience: the other methods change the results")
     parser.add_argument("--sweep-order", type=str, default="shuffled", choices=["colour", "shuffled"],
                         help="visiting order of the annealing sweeps: 'shuffled' (default: a fresh "
                              "random order every sweep, the reference annealer's statistics) or "
@@ -375,6 +389,12 @@ def parse_command_line(argv=None):
             parser.error("--anneal-patience and --anneal-check-every must be positive")
         if not args.annealing or args.batch <= 1:
             parser.error("--anneal-patience needs --annealing and --batch > 1 (it stops batched segments)")
+    if args.anneal_method != "anneal":
+        if args.anneal_patience is not None:
+            parser.error("--anneal-method {} cannot be combined with --anneal-patience".format(args.anneal_method))
+        if not args.annealing or args.batch <= 1:
+            parser.error("--anneal-method {} needs --annealing and --batch > 1 (it runs batched "
+                         "segments)".format(args.anneal_method))
     return args
 
 

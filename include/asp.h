@@ -550,6 +550,37 @@ int asp_sa_chains_advance(asp_sa_chains *c, double const *betas, uint32_t num_sw
 int asp_sa_chains_advance_ladder(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps, uint32_t order,
                                  int64_t *out_trace);
 
+/* MANY handles' ladder segments in one call ("Batched forms"; declared here beside the
+ * single call, asp_sa_chains_item is described below).  Item i is exactly asp_sa_chains_advance_ladder
+ * (chains, chain_betas, num_sweeps, order, out_trace): all five state arrays, sweeps_done and the trace
+ * with the same bits, for any composition and order of the batch and however the items differ in
+ * num_sweeps, order, sweeps_done, repetitions, seed or replica offset.  The handles share launches as in
+ * asp_sa_chains_advance_batch, in the per-chain-beta forms of its kernels: order 0 — one launch per
+ * wavefront count and layout class, the per-chain betas of all handles in one buffer; order 1 — segments
+ * of equal length in the shared order and sweep launches, one team.  Traced items, plans with a forced
+ * geometry or layout, clusters beyond a byte per position (order 0), a length no other item has
+ * (order 1) and a group of one take asp_sa_chains_advance_ladder's path inside the call.  Ladder
+ * batches, plain batches, single calls, gather, resample, exchange and export / import alternate freely
+ * on a handle.  out_tracked_best / out_improved as in asp_sa_chains_item; asp_sa_chains_batch_last_ms
+ * reports the sweep time of the call.
+ * All items are validated before any device work and before any output is written; ASP_ERR_INVALID with
+ * the item's index in the message: null items with count > 0, a null handle, null chain_betas with
+ * repetitions > 0, an entry that is negative, NaN or infinite, an order above 1, non-zero flags, the
+ * same handle twice, two handles of one plan, sweeps_done + num_sweeps > 2^32 - 2.  count = 0 needs no
+ * device; handles without chains and plans without spins run nothing (column 0 of a trace is written).
+ * Any OTHER error leaves the handles of the batch UNDEFINED, as for asp_sa_chains_advance_batch. */
+typedef struct asp_sa_chains_ladder_item {
+  asp_sa_chains *chains;
+  double const *chain_betas;  /* HOST [repetitions] */
+  uint32_t num_sweeps;
+  uint32_t order;             /* 0 colour, 1 shuffled */
+  uint32_t flags;             /* 0; anything else is ASP_ERR_INVALID */
+  int64_t *out_trace;         /* NULL, or HOST [repetitions][num_sweeps + 1] */
+  int64_t *out_tracked_best;  /* as asp_sa_chains_item */
+  uint32_t *out_improved;
+} asp_sa_chains_ladder_item;
+int asp_sa_chains_advance_ladder_batch(asp_sa_chains_ladder_item const *items, uint32_t count);
+
 /* The best configuration so far of every chain and its energy — what the closed call returns:
  * out_x[repetitions * ceil(K/64)], out_e[repetitions] (host or device pointers). */
 int asp_sa_chains_result(asp_sa_chains *c, uint64_t *out_x, double *out_e);
@@ -688,6 +719,31 @@ float asp_sa_chains_resample_last_ms(void);
  * infinite.  asp_sa_last_total_ms of the plan is the device time of the step (energies to gather). */
 int asp_sa_chains_exchange(asp_sa_chains *c, double const *chain_betas, uint32_t parity, uint32_t draw,
                            uint32_t *out_source, double *out_energy, uint32_t *out_accepted);
+
+/* MANY handles' exchange steps in one call ("Batched forms"): item i is exactly
+ * asp_sa_chains_exchange(chains, chain_betas, parity, draw, out_*) — steps 1-6 of ASP-PT-1 unchanged,
+ * the same bits for any composition and order of the batch.  Energies run per plan on the plans'
+ * streams; steps 2-5 of all handles are ONE launch over a table of rows (every slot's source and energy
+ * word written by exactly one thread, one atomic add per accepted pair to the row's counter), the gather
+ * one launch per state type over all handles, and energy | source | accepted of every handle come back
+ * in one copy.  Validation as in asp_sa_chains_resample_batch — every item before any device work and
+ * before any output is written, the item's index in the message: null items with count > 0, a null
+ * handle, null chain_betas with repetitions > 0, an entry that is negative, NaN or infinite, parity > 1,
+ * non-zero flags, the same handle twice, two handles of one plan.  count = 0 needs no device; handles
+ * without chains and plans without spins run nothing (energies 0, the identity, accepted 0).  Any OTHER
+ * error leaves the handles of the batch UNDEFINED. */
+typedef struct asp_sa_chains_exchange_item {
+  asp_sa_chains *chains;
+  double const *chain_betas;  /* HOST [repetitions] */
+  uint32_t parity, draw, flags;
+  uint32_t *out_source;       /* NULL, or HOST [repetitions] */
+  double *out_energy;         /* NULL, or HOST [repetitions]: reported energies before the step */
+  uint32_t *out_accepted;     /* NULL, or one word: pairs that swapped */
+} asp_sa_chains_exchange_item;
+int asp_sa_chains_exchange_batch(asp_sa_chains_exchange_item const *items, uint32_t count);
+/* Device time (ms) of this thread's last asp_sa_chains_exchange_batch call: from its first launch (the
+ * energies) to the end of the gather, HIP events on the call's stream. */
+float asp_sa_chains_exchange_last_ms(void);
 
 /* MANY independent problems in one call — the shape of the reference's production job: tens of
  * thousands of sampled clusters, each solved with 64 repetitions x 5120 sweeps
