@@ -486,7 +486,8 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
   uint32_t *improved_flag = reinterpret_cast<uint32_t *>(book + 24);
   uint2 *meta = reinterpret_cast<uint2 *>(book + 26);  // per block {first ELL slab, width}
   // cache control: [0] flips of the running sweep, [1] 1 while the field cache is in use,
-  // [2] 1 when the cache was just switched on (dirty bytes must be set);
+  // [2] 1 when the cache was just switched on (dirty bytes must be set),
+  // [3] the ticket counter that hands a colour's blocks to the wavefronts;
   // then one dirty byte per block (bit m: replica m's cached fields are stale)
   // (the bit-packed layout keeps no per-block arrays in LDS besides the spin words: block
   // metadata is read from HBM with scalar loads, the field cache is not available)
@@ -582,6 +583,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     cache_ctl[0] = 0;
     cache_ctl[1] = 0;
     cache_ctl[2] = 0;
+    cache_ctl[3] = 0;  // block tickets drawn so far (colour loop)
   }
   if constexpr (Res::kEnabled) {
     // (the best configuration so far is in a.best_perm already and stays unless the segment
@@ -604,6 +606,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
   // StopWhenStill: sweeps performed, and the chain's accepted flips before the running sweep
   [[maybe_unused]] uint32_t sweeps_done = a.num_sweeps;
   [[maybe_unused]] long long flips_before = 0;
+  uint32_t ticket_base = 0;  // cache_ctl[3] at the start of the running colour (workgroup-uniform)
   for (uint32_t t = 0; t < a.num_sweeps; ++t) {
     uint32_t t_draw = t;  // the sweep index of the random words: global over the segments of a handle
     if constexpr (Res::kEnabled) t_draw += res.t0;
@@ -633,7 +636,21 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     for (uint32_t c = 0; c < a.num_colors; ++c) {
       const uint32_t b_begin = a.color_block_start[c];
       const uint32_t b_end = a.color_block_start[c + 1];
-      for (uint32_t b = b_begin + wave; b < b_end; b += waves) {
+      // The colour's blocks go to the wavefronts in ascending order (widest rows first, the plan
+      // sorts a colour by descending degree), each to the first wavefront that is free: the first
+      // `waves` blocks one per wavefront, every later one by a ticket drawn from cache_ctl[3].  The
+      // ticket of the NEXT block is drawn before the visit of this one and read after it, so no
+      // visit ends on a wait for the atomic (the visit's first LDS read returns in order behind it
+      // and does wait for it); every wavefront that visits a block therefore ends the
+      // colour on one ticket past b_end, and the colour draws exactly b_end - b_begin tickets in
+      // all.  The counter is never reset: when the colour barrier is passed it stands at
+      // ticket_base + (b_end - b_begin) in every wavefront's books (mod 2^32).
+      uint32_t ticket = 0;
+      for (uint32_t b = b_begin + wave; b < b_end;
+           b = b_begin + waves + (__builtin_amdgcn_readfirstlane(ticket) - ticket_base)) {
+        // (atomicInc, not atomicAdd: hipcc rewrites an LDS atomicAdd into a wave reduction and one more
+        // dependent wait in front of every visit; measured slower)
+        if (lane == 0) ticket = atomicInc(&cache_ctl[3], 0xFFFFFFFFu);
         const uint32_t p = b * 64u + lane;
         bool reuse = false;
         if (cached) {
@@ -808,6 +825,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
           }
         }
       }
+      ticket_base += b_end - b_begin;
       __syncthreads();
     }
 
