@@ -459,16 +459,28 @@ struct LadderBetas<M, true> {
 // after every sweep.
 // The whole anneal of one group of M replicas by one workgroup; `group` = index of the group
 // inside its problem (k_sa_sweep: the workgroup id; k_sa_sweep_batch: looked up in a table).
+// ALIGNED (M = 4 only): the host promises a.replica_first % 4 == 0 (aligned_replicas()), so every
+// group is one whole Philox call, call r0 >> 2, and replica m takes word m of it, known at compile
+// time.  Without the promise the first replica's place in its call is a run-time value, the visit
+// keeps a second call path for a group that straddles two calls and selects every replica's word
+// with pick_word (three v_cndmask_b32 on scalar masks per replica).  Same counters, same words:
+// the chains are the generic body's.
 template <int M, bool DESCENT, int LAYOUT, typename Args, typename Stop = NoEarlyStop,
-          typename Res = NoResume>
+          typename Res = NoResume, bool ALIGNED = false>
 __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t group,
                                               const Stop stop = Stop{}, const Res res = Res{}) {
   static_assert(DESCENT || !Stop::kEnabled, "only a descent can stop early");
+  static_assert(!ALIGNED || (!DESCENT && M == 4), "an aligned group is one whole Philox call");
   static_assert(!DESCENT || !Res::kEnabled, "a descent is never resumed");
   constexpr bool GLOBAL = LAYOUT == kGlobal;
   constexpr bool PACKED = LAYOUT == kBits || GLOBAL;  // one bit per position
   constexpr bool WIDE = LAYOUT == kWide;
   constexpr bool NIBBLES = LAYOUT == kNibbles;
+  // The lean energy bookkeeping of a visit (see the accept loop) for up to four replicas.  Eight
+  // replicas and the ladder segment of four in words keep the per-flip form: they have no vector
+  // register to spare in the accept phase, and the lean form's two more sent them to scratch
+  // (DESIGN.md section 6).
+  constexpr bool kLeanBook = M <= 4 && !(Res::kLadder && WIDE);
   static_assert(!PACKED || M == 1, "the bit-packed layouts hold one replica");
   static_assert(!NIBBLES || (M <= 4 && !DESCENT), "the nibble layout holds up to four replicas");
   static_assert(!WIDE || (M <= 4 && !DESCENT), "the wide layout holds up to four replicas");
@@ -535,12 +547,19 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
         uint32_t have = 0xFFFFFFFFu;
 #pragma unroll
         for (int m = 0; m < M; ++m) {
-          const uint32_t r = r0 + m;
-          if (m == 0 || (r >> 2) != have) {
-            have = r >> 2;
-            rnd = philox4x32_10(spin, 0xFFFFFFFFu, have, 0u, key0, key1);
+          uint32_t word;
+          if constexpr (ALIGNED) {
+            if (m == 0) rnd = philox4x32_10(spin, 0xFFFFFFFFu, r0 >> 2, 0u, key0, key1);
+            word = rnd.w[m];
+          } else {
+            const uint32_t r = r0 + m;
+            if (m == 0 || (r >> 2) != have) {
+              have = r >> 2;
+              rnd = philox4x32_10(spin, 0xFFFFFFFFu, have, 0u, key0, key1);
+            }
+            word = pick_word(rnd, r & 3u);
           }
-          const uint32_t up = pick_word(rnd, r & 3u) & 1u;  // 1 -> s = +1 -> sign bit 0
+          const uint32_t up = word & 1u;  // 1 -> s = +1 -> sign bit 0
           byte |= (up ^ 1u) << replica_bit<M, LAYOUT>(m);
         }
       }
@@ -625,8 +644,11 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
         __syncthreads();
       }
     }
-    long long q_acc[M];
+    // q_acc: the fixed-point energy changes of the lane's accepted flips; kLeanBook: plus
+    // 0x4338000000000000 per visit (see the accept loop), arithmetic modulo 2^64
+    unsigned long long q_acc[M];
     uint32_t n_acc[M];  // accepted flips of this lane in this sweep (< 2^32 blocks per sweep)
+    [[maybe_unused]] uint32_t visits = 0;  // blocks this wavefront evaluated in this sweep (wave-uniform)
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       q_acc[m] = 0;
@@ -661,6 +683,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
             continue;
           }
         }
+        if constexpr (kLeanBook) visits += 1;
         // {first slab, width}: one broadcast LDS read (two scalar loads when bit-packed)
         const uint2 info =
             PACKED ? make_uint2(static_cast<uint32_t>(a.ell_off[b]), a.block_width[b]) : meta[b];
@@ -750,39 +773,82 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
         // branch around the 10 Philox rounds and the exp filter.  Counter-based RNG: skipping
         // a draw changes nothing downstream.
         const bool draw = !DESCENT && __ballot(need) != 0ull;
+        // the accepted proposals: bit m of accept_mask, or (kLeanBook) all ones in took[m]
         uint32_t accept_mask = 0;
+        [[maybe_unused]] uint32_t took[M];
         if (draw) {
           Philox4 rnd{};
           uint32_t have = 0xFFFFFFFFu;
 #pragma unroll
           for (int m = 0; m < M; ++m) {
-            const uint32_t r = r0 + m;
-            if (m == 0 || (r >> 2) != have) {
-              have = r >> 2;
-              rnd = philox4x32_10(spin, t_draw, have, 0u, key0, key1);
+            uint32_t word;
+            if constexpr (ALIGNED) {
+              // one call for the four replicas, the word a compile-time pick (no selection)
+              if (m == 0) rnd = philox4x32_10(spin, t_draw, r0 >> 2, 0u, key0, key1);
+              word = rnd.w[m];
+            } else {
+              const uint32_t r = r0 + m;
+              if (m == 0 || (r >> 2) != have) {
+                have = r >> 2;
+                rnd = philox4x32_10(spin, t_draw, have, 0u, key0, key1);
+              }
+              word = pick_word(rnd, r & 3u);
             }
-            const uint32_t word = pick_word(rnd, r & 3u);
             const bool accept =
                 valid && (de[m] <= 0.0 || metropolis_accept_word(word, __dmul_rn(ladder.of(m, beta), de[m])));
-            accept_mask |= (accept ? 1u : 0u) << m;
+            if constexpr (kLeanBook) {
+              took[m] = accept ? 0xFFFFFFFFu : 0u;
+            } else {
+              accept_mask |= (accept ? 1u : 0u) << m;
+            }
           }
         } else {
 #pragma unroll
           for (int m = 0; m < M; ++m) {
             // (no draw needed: DESCENT, or every proposal decided)
             const bool accept = valid && (DESCENT ? de[m] < 0.0 : de[m] <= 0.0);
-            accept_mask |= (accept ? 1u : 0u) << m;
+            if constexpr (kLeanBook) {
+              took[m] = accept ? 0xFFFFFFFFu : 0u;
+            } else {
+              accept_mask |= (accept ? 1u : 0u) << m;
+            }
           }
         }
+        // Energy bookkeeping.  rint(dE * 2^S) as int64: |dE * 2^S| < 2^51 by the plan's choice of
+        // S, so adding 1.5 * 2^52 leaves the rounded integer in the mantissa (ties to even, = rint):
+        // the sum's bit pattern is 0x4338000000000000 + rint(dE * 2^S).
+        if constexpr (kLeanBook) {
+          // No branch and no selection: EVERY replica adds the bit pattern of dE * scale_m +
+          // 1.5 * 2^52, where scale_m is 2^S for an accepted proposal and 0 otherwise (2^S is a
+          // power of two: its low word is 0 and the high word is masked) — dE is finite, so a
+          // proposal that is not accepted adds the bare constant.  The `visits` constants come
+          // off once per sweep, in front of the reduction, modulo 2^64.  One fma is the multiply
+          // followed by the add: dE * 2^S is exact — the fma then rounds the very sum the add
+          // rounds — or it underflows, to something below 2^-1022 either way, and both sums round
+          // to 1.5 * 2^52.  v_fma_f64 reads one scalar operand, so the constant is put in vector
+          // registers here, after the k-loop: held for the whole launch it costs every
+          // instantiation two registers more.
+          double round_bias = 0x1.8p52;
+          asm volatile("" : "+v"(round_bias));
+          const uint32_t scale_hi = static_cast<uint32_t>(__double2hiint(a.scale));
 #pragma unroll
-        for (int m = 0; m < M; ++m) {
-          if ((accept_mask >> m) & 1u) {
-            flip |= 1u << m;
-            // rint(dE * 2^S) as int64: |dE * 2^S| < 2^51 by the plan's choice of S, so adding
-            // 1.5 * 2^52 leaves the rounded integer in the mantissa (ties to even, = rint)
-            q_acc[m] += __double_as_longlong(__dadd_rn(__dmul_rn(de[m], a.scale), 0x1.8p52)) -
-                        0x4338000000000000ll;
-            n_acc[m] += 1;
+          for (int m = 0; m < M; ++m) {
+            flip |= took[m] & (1u << m);
+            const double scale_m = __hiloint2double(static_cast<int>(scale_hi & took[m]), 0);
+            q_acc[m] += static_cast<unsigned long long>(
+                __double_as_longlong(__builtin_fma(de[m], scale_m, round_bias)));
+            n_acc[m] -= took[m];  // + 1 when accepted
+          }
+        } else {
+#pragma unroll
+          for (int m = 0; m < M; ++m) {
+            if ((accept_mask >> m) & 1u) {
+              flip |= 1u << m;
+              q_acc[m] += static_cast<unsigned long long>(
+                  __double_as_longlong(__dadd_rn(__dmul_rn(de[m], a.scale), 0x1.8p52)) -
+                  0x4338000000000000ll);
+              n_acc[m] += 1;
+            }
           }
         }
         if constexpr (PACKED) {
@@ -832,7 +898,9 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     // ---- exact (integer) reduction of the sweep's energy change ----
 #pragma unroll
     for (int m = 0; m < M; ++m) {
-      const long long v = wave_sum_i64(q_acc[m]);
+      // kLeanBook: the visits' constants off, modulo 2^64 (the true sum fits: the plan's S)
+      const long long v = wave_sum_i64(static_cast<long long>(
+          kLeanBook ? q_acc[m] - visits * 0x4338000000000000ull : q_acc[m]));
       const long long n = wave_sum_i64(static_cast<long long>(n_acc[m]));
       if (lane == 0 && n != 0) {
         atomicAdd(reinterpret_cast<unsigned long long *>(&delta[m]),
@@ -918,9 +986,9 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
   }
 }
 
-template <int M, bool DESCENT, int LAYOUT>
+template <int M, bool DESCENT, int LAYOUT, bool ALIGNED = false>
 __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep(SweepArgs a) {
-  sa_sweep_body<M, DESCENT, LAYOUT>(a, blockIdx.x);
+  sa_sweep_body<M, DESCENT, LAYOUT, SweepArgs, NoEarlyStop, NoResume, ALIGNED>(a, blockIdx.x);
 }
 
 // One segment of an asp_sa_chains handle in the colour order (asp_sa_chains_advance, order 0).
@@ -1679,17 +1747,30 @@ namespace {
 
 using SweepKernel = void (*)(SweepArgs);
 
-SweepKernel sweep_kernel_for(int m, bool descent, int layout) {
+// A group of four replicas that starts on a multiple of four is one whole Philox call (the ALIGNED
+// form of sa_sweep_body): any sharding of the chains by multiples of four.  Eight replicas stay
+// generic: an aligned visit of two calls back to back needed 36 B of scratch against 28 B.
+bool aligned_replicas(int m, uint32_t replica_first) { return m == 4 && replica_first % 4u == 0; }
+
+// `aligned`: aligned_replicas() holds for the launch.  The closed call's kernels of four replicas
+// have the ALIGNED form; every other kernel is the generic one, which is right for any first replica.
+SweepKernel sweep_kernel_for(int m, bool descent, int layout, bool aligned = false) {
   if (layout == kBits) return descent ? k_sa_sweep<1, true, kBits> : k_sa_sweep<1, false, kBits>;
   if (layout == kGlobal) {
     return descent ? k_sa_sweep<1, true, kGlobal> : k_sa_sweep<1, false, kGlobal>;
   }
-  if (layout == kWide) return m == 4 ? k_sa_sweep<4, false, kWide> : nullptr;
-  if (layout == kNibbles) return m == 4 ? k_sa_sweep<4, false, kNibbles> : nullptr;
+  if (layout == kWide) {
+    if (m != 4) return nullptr;
+    return aligned ? k_sa_sweep<4, false, kWide, true> : k_sa_sweep<4, false, kWide>;
+  }
+  if (layout == kNibbles) {
+    if (m != 4) return nullptr;
+    return aligned ? k_sa_sweep<4, false, kNibbles, true> : k_sa_sweep<4, false, kNibbles>;
+  }
   switch (m) {
     case 1: return descent ? k_sa_sweep<1, true, kBytes> : k_sa_sweep<1, false, kBytes>;
     case 2: return k_sa_sweep<2, false, kBytes>;
-    case 4: return k_sa_sweep<4, false, kBytes>;
+    case 4: return aligned ? k_sa_sweep<4, false, kBytes, true> : k_sa_sweep<4, false, kBytes>;
     case 8: return k_sa_sweep<8, false, kBytes>;
     default: return nullptr;
   }
@@ -2236,7 +2317,7 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
     ASP_HIP_TRY(hipMemcpyAsync(&p->team_abort_host, ta.abort, sizeof p->team_abort_host,
                                hipMemcpyDeviceToHost, s));
   } else {
-    SweepKernel kernel = sweep_kernel_for(m, descent, layout);
+    SweepKernel kernel = sweep_kernel_for(m, descent, layout, aligned_replicas(m, replica_offset));
     if (lds > 64 * 1024) {
       ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize,
