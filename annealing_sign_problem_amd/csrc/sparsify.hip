@@ -13,8 +13,10 @@
 // matrix, M'_ji found by binary search in row j; lock-free union by atomicCAS, larger root under
 // smaller, so the final root of a component is its smallest spin — deterministic) -> k_flatten ->
 // k_mark_component (+ check that every frozen spin is in it) -> scan -> k_slice_rows<count> ->
-// scan -> k_slice_rows<emit>.  Integer/latency-bound streaming over the non-zeros: 12 B/non-zero in, 12 B per
-// kept non-zero out; no MFMA.
+// scan -> k_slice_rows<emit>.  Integer/latency-bound streaming over the non-zeros: 12 B/non-zero of
+// input, read four times (k_abs_max 8 B, k_hook_edges 12 B plus the probes of row j and the frozen
+// bytes, k_slice_rows<count> 4 B, k_slice_rows<emit> 12 B: 36 B/non-zero unless L2 holds them, not
+// measured), 12 B per kept non-zero out; no MFMA.
 #include <algorithm>
 #include <cstring>
 #include <vector>
