@@ -253,6 +253,9 @@ SIGNATURES = {
     "asp_sa_chains_advance_ladder_batch": (c_int, [ctypes.POINTER(SaChainsLadderItem), c_u32]),
     "asp_sa_chains_exchange_batch": (c_int, [ctypes.POINTER(SaChainsExchangeItem), c_u32]),
     "asp_sa_chains_exchange_last_ms": (c_float, []),
+    "asp_sa_chains_cluster_move": (c_int, [c_void_p, c_void_p, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
+    "asp_sa_chains_cluster_move_last_ms": (c_float, []),
+    "asp_sa_chains_set_cluster_planes": (c_int, [c_void_p, c_int]),
     "asp_sa_anneal_batch": (c_int, [ctypes.POINTER(SaBatchItem), c_u32]),
     "asp_sa_batch_last_ms": (c_float, []),
     "asp_sa_greedy": (c_int, [c_void_p, c_u32, c_void_p, c_void_p, ctypes.POINTER(c_u32)]),

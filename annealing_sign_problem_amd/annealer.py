@@ -42,6 +42,7 @@ __all__ = [
     "population_anneal_batch",
     "parallel_tempering",
     "parallel_tempering_batch",
+    "parallel_tempering_cluster",
     "advance_ladder_chains",
     "exchange_chains",
     "greedy_solve",
@@ -580,6 +581,38 @@ class Chains:
                                                       ctypes.byref(accepted)))
         return source, energies, int(accepted.value)
 
+    def cluster_move(self, pairs, draw: int = 0):
+        """One isoenergetic cluster move (Houdayer's move; law ASP-ICM-1) per pair on the
+        device: the chains ``a`` and ``b`` of every row ``(a, b)`` of ``pairs`` — an ``(P, 2)`` array-like of
+        slots, each named at most once; pair slots of equal temperature — flip one connected cluster of the
+        sites on which their current configurations differ.  The sum of the two energies is conserved and
+        nothing is rejected.  Returns ``(differing uint32[P], sizes uint32[P], deltas int64[P])``: the
+        number of differing sites, the size of the flipped cluster and the change of chain ``a``'s tracked
+        energy (chain ``b``'s is the opposite).  ``draw`` picks the random words (a Philox counter word),
+        for more than one move at one sweep count; the same move again undoes it."""
+        pairs = np.asarray(pairs)
+        if pairs.size == 0:
+            pairs = np.zeros((0, 2), dtype=np.uint32)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
+            raise ValueError("'pairs' must be an (P, 2) array of chain indices")
+        if np.any(pairs < 0) or np.any(pairs >= self.repetitions):
+            raise ValueError("'pairs' must hold chain indices below {}".format(self.repetitions))
+        if np.unique(pairs).size != pairs.size:
+            raise ValueError("'pairs' names a chain more than once")
+        draw = int(draw)
+        if not 0 <= draw < 2**32:
+            raise ValueError("'draw' must fit 32 bits")
+        handle = self._live()
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32)
+        count = pairs.shape[0]
+        differing = np.zeros(count, dtype=np.uint32)
+        sizes = np.zeros(count, dtype=np.uint32)
+        deltas = np.zeros(count, dtype=np.int64)
+        _lib.check(_lib.load().asp_sa_chains_cluster_move(handle, _lib.ptr(pairs), ctypes.c_uint32(count),
+                                                          ctypes.c_uint32(draw), _lib.ptr(differing),
+                                                          _lib.ptr(sizes), _lib.ptr(deltas)))
+        return differing, sizes, deltas
+
     def result(self, only_best: bool = False):
         """The best configuration so far of every chain and its energy, ``(xs[R, words], es[R])`` —
         what ``anneal(..., only_best=False)`` returns; ``only_best=True``: the best of them."""
@@ -955,6 +988,48 @@ def parallel_tempering(hamiltonian: Hamiltonian, seed=None, number_rounds: int =
             chains.advance_ladder(ladder, sweeps_per_round, sweep_order=order)
             if exchange and j + 1 < number_rounds:
                 chains.exchange(ladder, j & 1, 0)
+        return chains.result(only_best=only_best)
+
+
+def parallel_tempering_cluster(hamiltonian: Hamiltonian, seed=None, number_rounds: int = 512,
+                               sweeps_per_round: int = 10, beta0: Optional[float] = None,
+                               beta1: Optional[float] = None, repetitions: int = 64, only_best: bool = True,
+                               sweep_order: Optional[str] = None, exchange: bool = True, cluster_rungs=None):
+    """Parallel tempering with isoenergetic cluster moves: ``repetitions`` (even) chains,
+    two per rung of the ladder ``make_schedule(beta0, beta1, repetitions // 2)`` laid out as a hairpin —
+    slot ``k`` and slot ``repetitions - 1 - k`` both run at ``ladder[k]``.  Round ``j`` is
+    ``Chains.advance_ladder``, then ``Chains.cluster_move`` of the pairs ``(k, repetitions - 1 - k)`` of
+    the coldest ``cluster_rungs`` rungs (``None``: all of them) with draw 0 — on every round, the last
+    included — and, except after the last round, ``Chains.exchange(hairpin, j & 1, 0)``.  Returns what
+    ``anneal`` returns.  Chains stay on this rank."""
+    order = resolve_sweep_order(sweep_order)  # (first: a bad order fails without a GPU)
+    number_rounds, sweeps_per_round = int(number_rounds), int(sweeps_per_round)
+    if number_rounds < 1 or sweeps_per_round < 1:
+        raise ValueError("'number_rounds' and 'sweeps_per_round' must be positive")
+    if not isinstance(hamiltonian, Hamiltonian):
+        raise TypeError("'hamiltonian' must be a Hamiltonian")
+    repetitions = int(repetitions)
+    if repetitions < 2 or repetitions % 2:
+        raise ValueError("'repetitions' must be even and positive: two chains per rung")
+    rungs = repetitions // 2
+    cluster_rungs = rungs if cluster_rungs is None else int(cluster_rungs)
+    if not 0 <= cluster_rungs <= rungs:
+        raise ValueError("'cluster_rungs' must be between 0 and {}".format(rungs))
+    if beta0 is None or beta1 is None:
+        info = hamiltonian.info()
+        beta0 = info.beta0_auto if beta0 is None else beta0
+        beta1 = info.beta1_auto if beta1 is None else beta1
+    ladder = make_schedule(float(beta0), float(beta1), rungs)
+    hairpin = np.concatenate([ladder, ladder[::-1]])
+    # (the ladder runs hot to cold: the coldest rungs are the last ones)
+    pairs = np.array([(k, repetitions - 1 - k) for k in range(rungs - cluster_rungs, rungs)],
+                     dtype=np.uint32).reshape(-1, 2)
+    with Chains(hamiltonian, seed=seed, repetitions=repetitions) as chains:
+        for j in range(number_rounds):
+            chains.advance_ladder(hairpin, sweeps_per_round, sweep_order=order)
+            chains.cluster_move(pairs, 0)
+            if exchange and j + 1 < number_rounds:
+                chains.exchange(hairpin, j & 1, 0)
         return chains.result(only_best=only_best)
 
 

@@ -39,6 +39,7 @@ SOURCES = [
     "sa_shuffled.hip",
     "sa_chains.hip",
     "sa_population.hip",
+    "sa_cluster.hip",
 ]
 
 # -ffp-contract=off: the parity contract needs every multiply/add rounded on its

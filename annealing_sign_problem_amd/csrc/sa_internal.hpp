@@ -66,6 +66,12 @@ struct asp_sa_plan {
   uint32_t last_shuffled_log_s = 6, last_shuffled_wgs = 0;  // block size and workgroups of the last shuffled call
   uint32_t last_shuffled_blocks = 0, last_shuffled_quads = 0;  // most blocks / quads of one sweep of that call
   float last_order_ms = 0.0f;              // device time of the last call's order kernels
+  // Cluster moves (csrc/sa_cluster.hip; uploaded on first use): rows of A over ORIGINAL indices as a plain
+  // CSR (ascending columns, no padding), the field in original order, and the per-pair bit planes of the
+  // HBM form ([pairs][3][2 words] 32-bit words)
+  asp::DeviceBuffer<uint32_t> cluster_row_ptr, cluster_col;
+  asp::DeviceBuffer<double> cluster_val, cluster_field;
+  asp::DeviceBuffer<uint32_t> cluster_scratch;
 };
 
 
@@ -87,6 +93,7 @@ struct asp_sa_chains {
   asp::DeviceBuffer<uint64_t> x_cur_to, x_best_to;
   asp::DeviceBuffer<long long> e_cur_to, e_best_to;
   asp::DeviceBuffer<unsigned long long> accepted_to;
+  int cluster_planes = 0;  // asp_sa_chains_set_cluster_planes: 0 auto, 1 bit planes in LDS, 2 in HBM
 };
 
 namespace asp {

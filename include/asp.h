@@ -745,6 +745,40 @@ int asp_sa_chains_exchange_batch(asp_sa_chains_exchange_item const *items, uint3
  * energies) to the end of the gather, HIP events on the call's stream. */
 float asp_sa_chains_exchange_last_ms(void);
 
+/* ISOENERGETIC CLUSTER MOVES on a handle (law "ASP-ICM-1"; Houdayer's move): two chains
+ * flip one connected cluster of the sites on which their current configurations differ — rejection-free,
+ * and the only update here that is not local.  pairs: HOST u32[2 num_pairs], pair p = (a, b) =
+ * (pairs[2p], pairs[2p + 1]); every slot < repetitions and named at most once over all pairs.  The caller
+ * pairs slots of equal temperature (neither required nor checked).  Each pair, independently:
+ *  1. d = x_current[a] XOR x_current[b] (bits from num_spins on cleared), n = popcount(d); n = 0: nothing
+ *     changes for the pair (size 0, delta 0);
+ *  2. v = word 0 of Philox4x32-10(counter (a, sweeps_done, 0xFFFFFFFB, draw), key seed) — a counter no
+ *     proposal, start, visiting order, resampling or exchange uses —, U = floor(v n / 2^32); the seed site
+ *     i0 is the U-th set bit of d in ascending site index, counted from 0;
+ *  3. C = the connected component of i0 in the graph of A = offdiag(J + J^T) induced on {i : d_i = 1};
+ *  4. for every i in C: acc = +0.0; for the entries of row i of A in ascending column with d_j = 0:
+ *     acc = fma(A_ij, s_j^a, acc); g = acc + h_i; dE_i = s_i^a = +1 ? -2 g : 2 g; q_i = (int64)
+ *     rint(dE_i 2^S), one rounding per operation as in a proposal of the annealer; Q = sum of q_i over C
+ *     (replica b's sum is exactly -Q);
+ *  5. x_current[a] ^= C, x_current[b] ^= C, tracked_current[a] += Q, tracked_current[b] -= Q;
+ *  6. for a and for b: tracked_current < tracked_best (strictly) makes the current configuration and
+ *     energy the best ones.  accepted and sweeps_done do not change; slots in no pair are untouched.
+ * The same call again (same draw, no sweep in between) restores x_current and tracked_current bit for bit.
+ * Outputs (HOST [num_pairs], each may be NULL), back in one copy with the touched slots' tracked energies:
+ * out_differing (n), out_size (|C|), out_delta (Q).  In place, on the plan's stream.  ASP_ERR_INVALID,
+ * before any device work and before any output is written: a null handle, null pairs with num_pairs > 0,
+ * an entry that is not below repetitions (its index in the message), a slot named twice (both indices).
+ * num_pairs = 0, a handle without chains and a plan without spins run nothing and need no device. */
+int asp_sa_chains_cluster_move(asp_sa_chains *c, uint32_t const *pairs, uint32_t num_pairs, uint32_t draw,
+                               uint32_t *out_differing, uint32_t *out_size, int64_t *out_delta);
+/* Device time (ms) of this thread's last asp_sa_chains_cluster_move call (its kernel, HIP events on the
+ * plan's stream); 0 when nothing ran. */
+float asp_sa_chains_cluster_move_last_ms(void);
+/* Where the move keeps its three bit planes (differing, member, frontier) per pair — for tests and timing:
+ * 0 automatic (LDS when they fit, else HBM), 1 LDS (ASP_ERR_TOO_LARGE at the move when they do not fit),
+ * 2 a per-pair slab in HBM.  Results never depend on it. */
+int asp_sa_chains_set_cluster_planes(asp_sa_chains *c, int where);
+
 /* MANY independent problems in one call — the shape of the reference's production job: tens of
  * thousands of sampled clusters, each solved with 64 repetitions x 5120 sweeps
  * (Makefile:9,115-127; experiments/sampled_connected_components.py:764-767; common.py:236-239).
