@@ -49,6 +49,7 @@ struct asp_sa_plan {
   }
   int team_mode = -1;  // asp_sa_set_team: -1 auto, 0 off, G >= 2 forced
   bool use_field_cache = true;
+  bool use_post = true;  // asp_sa_set_post: k_sa_post for the pass after a sweep launch
   uint32_t team_abort_host = 0;  // landing place of the watchdog flag's asynchronous read-back
   uint32_t team_watchdog_trips = 0;  // calls of this plan that the team barrier's watchdog cut short (each ~5 s lost)
   // Shuffled sweep (csrc/sa_shuffled.hip; uploaded on first use): rows of A over ORIGINAL

@@ -1540,6 +1540,113 @@ __global__ __launch_bounds__(512) void k_sa_energy_blocks_multi(EnergyArgs a, ui
   }
 }
 
+// The pass after a sweep launch in one kernel: the block sums of k_sa_energy_blocks_multi<R> and, when
+// `x` is given, the configurations in original order (k_unpermute_bits), from ONE staging of the
+// R sign-word rows.  The rows are staged in the sweep's even-bit byte layout (a byte per position,
+// configuration k at bit 2k), so the row sums run on the sweep's own k-loop: buffer loads with one
+// quad in flight ahead, one ds_read_u8 per term for the R configurations, one v_lshl_or_b32 and one
+// f64 FMA per term and configuration.  fma(J, +-1.0, acc) is acc + (+-J) bit for bit (the product
+// is exact), the terms arrive in ascending k, and everything after the row sum is
+// energy_blocks_body's: the partial sums are the bits of the kernels above.  No quad past the
+// block is loaded.  Block metadata comes from scalar loads (the block index is wave-uniform).
+struct PostArgs {
+  EnergyArgs e;
+  const uint32_t *pos_of_spin;
+  uint64_t *x;  // nullptr, or [count][words] configurations in original order (bit = +1)
+  uint64_t num_spins;
+  uint32_t words;
+};
+
+template <int R>
+__global__ __launch_bounds__(kMaxThreads) void k_sa_post(PostArgs pa, uint32_t count) {
+  static_assert(R <= 4, "the even-bit byte holds four configurations");
+  extern __shared__ __align__(16) uint8_t lds[];  // [num_blocks * 64] spin bytes
+  const EnergyArgs &a = pa.e;
+  // accumulate addresses the spin bytes absolutely: the dynamic LDS block must be the first
+  // (this kernel declares no static LDS)
+  if (reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t *)lds) != 0) {
+    __builtin_trap();
+  }
+  const uint32_t r0 = blockIdx.x * R;
+  const uint32_t live = count - r0 < static_cast<uint32_t>(R) ? count - r0 : R;
+  const uint64_t *rows = a.perm_words + static_cast<uint64_t>(r0) * a.num_blocks;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t waves = blockDim.x >> 6;
+  // a wavefront per block: the R words of the block are scalar loads, the lane's bits one byte
+  // (rows beyond `live` stay 0: their sums are computed and never stored)
+  for (uint32_t b = wave; b < a.num_blocks; b += waves) {
+    uint32_t byte = 0;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      if (static_cast<uint32_t>(k) >= live) break;  // workgroup-uniform
+      const uint64_t word = rows[static_cast<uint64_t>(k) * a.num_blocks + b];
+      byte |= static_cast<uint32_t>((word >> lane) & 1ull) << (2 * k);
+    }
+    lds[b * 64u + lane] = static_cast<uint8_t>(byte);
+  }
+  __syncthreads();  // the bytes are read-only from here on
+  double mult[4] = {1.0, 1.0, 1.0, 1.0};  // (kWide's, unused by bytes)
+  for (uint32_t b = wave; b < a.num_blocks; b += waves) {
+    const uint32_t quads = a.block_width[b] >> 2;
+    const uint64_t first_quad = a.ell_off[b] >> 2;
+    const uint4 *col = reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u;
+    const double2 *val = reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u;
+    const BlockStream stream{col + lane, block_rsrc(col), block_rsrc(val), lane * 16u};
+    const uint32_t p = b * 64u + lane;
+    const double field = a.field_pos[p];  // consumed after the row sum
+    double acc[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) acc[k] = 0.0;
+    // prefetch distance one, scalar loop control, no conditional load inside the loop body; the
+    // last one or two quads are an epilogue, so nothing past the block is loaded (an empty
+    // block's first load reads the next block's first quad or the plan's tail slabs, unused)
+    Quad qa, qb;
+    load_quad(qa, stream, 0);
+    uint32_t i = 0;
+    for (; i + 2 < quads; i += 2) {
+      load_quad(qb, stream, i + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      accumulate<R, kBytes>(qa, lds, acc, mult);
+      __builtin_amdgcn_sched_barrier(0);
+      load_quad(qa, stream, i + 2);
+      __builtin_amdgcn_sched_barrier(0);
+      accumulate<R, kBytes>(qb, lds, acc, mult);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (i + 2 == quads) {
+      load_quad(qb, stream, i + 1);
+      accumulate<R, kBytes>(qa, lds, acc, mult);
+      accumulate<R, kBytes>(qb, lds, acc, mult);
+    } else if (i < quads) {
+      accumulate<R, kBytes>(qa, lds, acc, mult);
+    }
+    const uint32_t own = lds[p];
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      if (static_cast<uint32_t>(k) >= live) break;  // workgroup-uniform
+      const double g = __dadd_rn(__dmul_rn(0.5, acc[k]), field);
+      const bool negative = (own >> (2 * k)) & 1u;
+      const double total = wave_tree_sum_f64(negative ? -g : g);
+      if (lane == 0) a.partial[static_cast<uint64_t>(r0 + k) * a.num_blocks + b] = total;
+    }
+  }
+  if (pa.x == nullptr) return;
+  // a wavefront per output word: lane j owns spin 64 w + j, its position is read coalesced, its
+  // byte once, and the word of each live configuration is one ballot
+  for (uint32_t w = wave; w < pa.words; w += waves) {
+    const uint64_t spin = static_cast<uint64_t>(w) * 64u + lane;
+    const bool real = spin < pa.num_spins;
+    const uint32_t byte = real ? static_cast<uint32_t>(lds[pa.pos_of_spin[spin]]) : 0u;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      if (static_cast<uint32_t>(k) >= live) break;  // workgroup-uniform
+      const uint64_t word = __ballot(real && ((byte >> (2 * k)) & 1u) == 0u);
+      if (lane == 0) pa.x[static_cast<uint64_t>(r0 + k) * pa.words + w] = word;
+    }
+  }
+}
+
 // One wavefront per configuration folds its block sums 64 at a time, in place.
 __device__ __forceinline__ void energy_fold_body(double *partial, uint32_t num_blocks,
                                                  double diag_sum, double *out_e, const uint32_t r) {
@@ -1942,15 +2049,31 @@ void attach_field_cache(asp_sa_plan *p, uint64_t padded, SweepArgs *args) {
   }
 }
 
+// out_x: nullptr, or [count][ceil(K/64)] — the configurations in original order (bit = +1) as well:
+// written by k_sa_post where it runs, by k_unpermute_bits behind the older energy kernels.
 int energies_of_perm(asp_sa_plan *p, const uint64_t *perm_words, uint32_t count, double *partial,
-                     double *out_e) {
+                     double *out_e, uint64_t *out_x = nullptr) {
   const asp::SaHostLayout &L = p->host;
   if (count == 0) return ASP_OK;
   EnergyArgs ea{p->block_width.ptr, p->ell_off.ptr, p->ell_col.ptr, p->ell_val.ptr,
                 p->field_pos.ptr,   perm_words,     partial,        L.num_blocks};
   const size_t lds = static_cast<size_t>(L.num_blocks) * sizeof(uint64_t);
+  const uint32_t words = static_cast<uint32_t>((L.num_spins + 63) / 64);
   constexpr int kShare = 4;  // configurations per workgroup sharing the coupling loads
-  if (count >= 2 * kShare && lds * kShare <= p->max_lds) {
+  const size_t post_lds = static_cast<size_t>(L.num_blocks) * 64;  // a byte per position
+  if (count >= 2 * kShare && p->use_post && post_lds <= p->max_lds) {
+    // (asp_sa_set_post; plans whose bytes do not fit the LDS keep the kernels below)
+    if (post_lds > 64 * 1024) {
+      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sa_post<kShare>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      static_cast<int>(post_lds)));
+    }
+    const PostArgs pa{ea, p->pos_of_spin.ptr, out_x, L.num_spins, words};
+    const uint32_t waves = std::min<uint32_t>(16u, L.num_blocks);
+    hipLaunchKernelGGL(k_sa_post<kShare>, dim3((count + kShare - 1) / kShare), dim3(64 * waves),
+                       post_lds, p->stream, pa, count);
+    out_x = nullptr;  // done
+  } else if (count >= 2 * kShare && lds * kShare <= p->max_lds) {
     if (lds * kShare > 64 * 1024) {
       ASP_HIP_TRY(hipFuncSetAttribute(
           reinterpret_cast<const void *>(k_sa_energy_blocks_multi<kShare>),
@@ -1970,6 +2093,12 @@ int energies_of_perm(asp_sa_plan *p, const uint64_t *perm_words, uint32_t count,
   }
   hipLaunchKernelGGL(k_sa_energy_fold, dim3(count), dim3(64), 0, p->stream, partial, L.num_blocks,
                      L.diag_sum, out_e);
+  if (out_x != nullptr) {
+    hipLaunchKernelGGL(k_unpermute_bits,
+                       dim3((words + 3) / 4, (count + kUnpermuteChains - 1) / kUnpermuteChains), dim3(256),
+                       0, p->stream, perm_words, L.num_blocks, p->pos_of_spin.ptr, L.num_spins, words,
+                       count, out_x);
+  }
   ASP_HIP_TRY(hipGetLastError());
   return ASP_OK;
 }
@@ -2098,6 +2227,12 @@ int asp_sa_set_launch(asp_sa_plan *p, int replicas_per_group, int threads) {
 int asp_sa_set_field_cache(asp_sa_plan *p, int enable) {
   if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
   p->use_field_cache = enable != 0;
+  return ASP_OK;
+}
+
+int asp_sa_set_post(asp_sa_plan *p, int enable) {
+  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
+  p->use_post = enable != 0;
   return ASP_OK;
 }
 
@@ -2330,12 +2465,8 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
     ASP_HIP_TRY(hipEventRecord(p->ev[2], s));
   }
   // the first `repetitions` rows of best_perm are the real replicas
-  ASP_TRY(energies_of_perm(p, d_best.ptr, repetitions, d_partial.ptr, d_e.ptr));
-  hipLaunchKernelGGL(k_unpermute_bits,
-                     dim3((words + 3) / 4, (repetitions + kUnpermuteChains - 1) / kUnpermuteChains),
-                     dim3(256), 0, s, d_best.ptr, L.num_blocks, p->pos_of_spin.ptr, K, words,
-                     repetitions, d_x.ptr);
-  ASP_HIP_TRY(hipGetLastError());
+  // ... their reported energies and, in the same pass, their configurations in original order
+  ASP_TRY(energies_of_perm(p, d_best.ptr, repetitions, d_partial.ptr, d_e.ptr, d_x.ptr));
   ASP_HIP_TRY(hipEventRecord(p->ev[3], s));
   // hipMemcpyDefault: out_x / out_e may be host pointers (the usual call) or device pointers
   // (distributed.py hands over RCCL-ready tensors, so a gather needs no host round trip)

@@ -399,6 +399,14 @@ int asp_sa_team_watchdog_trips(asp_sa_plan const *p, uint32_t *of_plan, uint64_t
  * Pure optimisation of frozen sweeps; results are identical with it on or off. */
 int asp_sa_set_field_cache(asp_sa_plan *p, int enable);
 
+/* The pass after the sweeps (default on): for eight or more configurations whose sign bytes fit the
+ * LDS (up to ~1.6e5 spins), the reported energies (and, in asp_sa_anneal / _trace, the unpermuted
+ * configurations) come from one kernel that stages four configurations as the sweep's spin bytes
+ * and sums the rows with the sweep's k-loop.  enable = 0 keeps the older energy and unpermute
+ * kernels, which fewer configurations and larger plans use anyway (tests, measurements).
+ * Pure optimisation; energies and configurations are identical with it on or off. */
+int asp_sa_set_post(asp_sa_plan *p, int enable);
+
 /* Run `repetitions` independent annealing chains (global replica ids
  * replica_offset .. replica_offset+repetitions-1) of num_sweeps sweeps, sweep t
  * at inverse temperature betas[t].  x0 == NULL: random initial spins from the
