@@ -263,6 +263,11 @@ SIGNATURES = {
     "asp_sa_greedy_batch": (c_int, [ctypes.POINTER(SaGreedyItem), c_u32]),
     "asp_sa_greedy_batch_last_ms": (c_int, [ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
     "asp_sa_greedy_tree_host": (c_int, [c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "asp_sa_greedy_tree": (c_int, [c_void_p, c_void_p]),
+    "asp_sa_greedy_tree_batch": (c_int, [c_void_p, c_u32, c_void_p]),
+    "asp_sa_set_greedy_tree": (c_int, [c_void_p, c_int]),
+    "asp_sa_greedy_tree_last_ms": (c_float, []),
+    "asp_sa_greedy_tree_last_split_ms": (c_int, [ctypes.POINTER(c_float)] * 3),
     "asp_sa_last_sweep_ms": (c_float, [c_void_p]),
     "asp_sa_last_total_ms": (c_float, [c_void_p]),
     "asp_sa_last_stats": (c_int, [c_void_p, c_u32, c_void_p, c_void_p]),

@@ -1192,16 +1192,19 @@ def anneal_with_traces(hamiltonian: Hamiltonian, x0=None, seed=None, number_swee
     return xs[0].copy(), e_current[0], e_best[0]
 
 
-def greedy_solve(hamiltonian: Hamiltonian):
-    """Strongest-coupling-first greedy sign assignment (common.py:250)."""
-    from .greedy import greedy_solve as _greedy
+def greedy_solve(hamiltonian: Hamiltonian, tree=None):
+    """Strongest-coupling-first greedy sign assignment (common.py:250).  ``tree``: ``"host"`` or
+    ``"device"``, where the strongest-coupling tree is built (``None``: ``$ASP_GREEDY_TREE`` or
+    ``"host"``); the result does not depend on it."""
+    from . import greedy as _greedy
 
-    return _greedy(hamiltonian)
+    return _greedy.greedy_solve(hamiltonian, _greedy.MAX_RELAXATION_SWEEPS, tree)
 
 
-def greedy_solve_batch(hamiltonians, max_sweeps=None, return_sweeps: bool = False):
+def greedy_solve_batch(hamiltonians, max_sweeps=None, return_sweeps: bool = False, tree=None):
     """``[greedy_solve(h) for h in hamiltonians]`` in one device call (``asp_sa_greedy_batch``):
-    identical results, the descents of all problems in shared launches."""
+    identical results, the descents of all problems in shared launches.  ``tree``: as in
+    :func:`greedy_solve` (with ``"device"`` the trees share launches too and never leave the device)."""
     from . import greedy as _greedy
 
     hamiltonians = list(hamiltonians)
@@ -1209,4 +1212,4 @@ def greedy_solve_batch(hamiltonians, max_sweeps=None, return_sweeps: bool = Fals
         if not isinstance(h, Hamiltonian):
             raise TypeError("'hamiltonians' must hold Hamiltonian objects")
     return _greedy.greedy_solve_batch(
-        hamiltonians, _greedy.MAX_RELAXATION_SWEEPS if max_sweeps is None else max_sweeps, return_sweeps)
+        hamiltonians, _greedy.MAX_RELAXATION_SWEEPS if max_sweeps is None else max_sweeps, return_sweeps, tree)

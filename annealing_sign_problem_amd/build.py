@@ -35,6 +35,7 @@ SOURCES = [
     "sparsify.hip",
     "sa_plan.cpp",
     "greedy.cpp",
+    "greedy_tree.hip",
     "sa_sweep.hip",
     "sa_shuffled.hip",
     "sa_chains.hip",

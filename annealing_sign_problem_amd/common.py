@@ -274,17 +274,20 @@ def solve_ising_model(
     repetitions: int = 64,
     only_best: bool = True,
     sweep_order: Optional[str] = None,
+    tree: Optional[str] = None,
 ) -> np.ndarray:
     """Optimise the signs of ``model`` and project them onto ``frozen_spins``
     (common.py:232-261).  ``sweep_order`` (not in the reference): ``"shuffled"``, a fresh random
     order every sweep as in the reference's annealer — the default, so that the drop-in call has
     the reference's law —, or ``"colour"``, this package's fixed colour order (faster, a different
-    chain; ``sa.anneal``); ``None`` = ``$ASP_SWEEP_ORDER`` or shuffled."""
+    chain; ``sa.anneal``); ``None`` = ``$ASP_SWEEP_ORDER`` or shuffled.
+    ``tree`` (not in the reference; ``mode="greedy"``): ``"host"`` or ``"device"``, where the greedy
+    solver's strongest-coupling tree is built; ``None`` = ``$ASP_GREEDY_TREE`` or host.  The same signs."""
     if mode == "sa":
         x, _ = sa.anneal(model.ising_hamiltonian, seed=seed, number_sweeps=number_sweeps,
                          repetitions=repetitions, only_best=only_best, sweep_order=sweep_order)
     elif mode == "greedy":
-        x, _ = sa.greedy_solve(model.ising_hamiltonian)
+        x, _ = sa.greedy_solve(model.ising_hamiltonian, tree=tree)
     else:
         raise ValueError(
             "invalid mode specified: '{}'; expected either 'sa' or 'greedy'".format(mode))
@@ -303,7 +306,7 @@ def _project_on_frozen(model: IsingModel, x: np.ndarray, frozen_spins) -> np.nda
 def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_sweeps: int = 5120,
                        repetitions: int = 64, sweep_order: Optional[str] = None, mode: str = "sa",
                        check_every: Optional[int] = None, patience: Optional[int] = None,
-                       method: str = "anneal"):
+                       method: str = "anneal", tree: Optional[str] = None):
     """``[solve_ising_model(m, mode, f, seed, number_sweeps, repetitions) for m, f in
     zip(models, frozen_spins)]`` with all annealing chains of all models in ONE device call
     (``sa.anneal_batch``): the same result for every model, at the throughput of a full chip
@@ -314,7 +317,8 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
     consecutive segments (``sa.anneal_batch_until``) — fewer sweeps, results that may differ.
     ``method`` (not in the reference; default ``"anneal"``): ``"population"`` or ``"tempering"`` solve
     every model with ``sa.population_anneal_batch`` / ``sa.parallel_tempering_batch`` instead, in
-    ``number_sweeps // 10`` steps / rounds of ten sweeps — the sweep count of the plain call."""
+    ``number_sweeps // 10`` steps / rounds of ten sweeps — the sweep count of the plain call.
+    ``tree`` (``mode="greedy"``): as in :func:`solve_ising_model`."""
     if method not in ("anneal", "population", "tempering"):
         raise ValueError(
             "invalid method specified: '{}'; expected 'anneal', 'population' or 'tempering'".format(method))
@@ -328,7 +332,7 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
     models = list(models)
     frozen = [None] * len(models) if frozen_spins is None else list(frozen_spins)
     if mode == "greedy":
-        solved = sa.greedy_solve_batch([m.ising_hamiltonian for m in models])
+        solved = sa.greedy_solve_batch([m.ising_hamiltonian for m in models], tree=tree)
         return [_project_on_frozen(m, x, f) for m, (x, _), f in zip(models, solved, frozen)]
     if mode != "sa":
         raise ValueError(

@@ -254,7 +254,14 @@ __global__ __launch_bounds__(kThreads) void k_cluster_move(ClusterArgs a) {
   }
 }
 
-// Rows of A over original indices and the field in original order, uploaded on a plan's first move.
+thread_local float g_cluster_ms = 0.0f;
+
+}  // namespace
+
+namespace asp {
+
+// Rows of A over original indices and the field in original order, uploaded on a plan's first move
+// (or first device tree, csrc/greedy_tree.hip).
 int ensure_rows(asp_sa_plan *p) {
   if (p->cluster_row_ptr.ptr) return ASP_OK;
   const asp::SaHostLayout &L = p->host;
@@ -279,9 +286,7 @@ int ensure_rows(asp_sa_plan *p) {
   return ASP_OK;
 }
 
-thread_local float g_cluster_ms = 0.0f;
-
-}  // namespace
+}  // namespace asp
 
 extern "C" {
 
@@ -327,7 +332,7 @@ int asp_sa_chains_cluster_move(asp_sa_chains *c, uint32_t const *pairs, uint32_t
     return ASP_OK;
   }
   ASP_TRY(asp::bind_device());
-  ASP_TRY(ensure_rows(p));
+  ASP_TRY(asp::ensure_rows(p));
   const uint32_t W = c->words;
   const size_t plane_bytes = 3ull * 8ull * W;
   const bool fits = plane_bytes + kStaticLds <= p->max_lds;

@@ -73,6 +73,7 @@ struct asp_sa_plan {
   asp::DeviceBuffer<uint32_t> cluster_row_ptr, cluster_col;
   asp::DeviceBuffer<double> cluster_val, cluster_field;
   asp::DeviceBuffer<uint32_t> cluster_scratch;
+  int greedy_tree = 0;  // asp_sa_set_greedy_tree: 0 host tree, 1 device tree (forest placed by size), 2 forest in HBM
 };
 
 
@@ -117,6 +118,10 @@ inline int check_distinct_plans(const std::vector<asp_sa_chains *> &handles) {
   }
   return ASP_OK;
 }
+
+// Rows of A over original indices and the field in original order (asp_sa_plan::cluster_*), uploaded
+// on first use; shared by the cluster moves (csrc/sa_cluster.hip) and the device tree (csrc/greedy_tree.hip).
+int ensure_rows(asp_sa_plan *p);
 
 template <typename T>
 int upload_vector(DeviceBuffer<T> &dst, const std::vector<T> &src, hipStream_t stream) {

@@ -2677,9 +2677,18 @@ int asp_sa_greedy(asp_sa_plan *p, uint32_t max_sweeps, uint64_t *out_x, double *
     *out_e = 0.0;
     return ASP_OK;
   }
-  // 1. strongest-coupling-first cluster merging on the host (O(E log E))
+  // 1. strongest-coupling-first cluster merging: on the host (O(E log E)), or the same tree on the
+  // device (asp_sa_set_greedy_tree, csrc/greedy_tree.hip)
   std::vector<uint64_t> x(words, 0);
-  ASP_TRY(asp::greedy_tree_signs(L, x.data()));
+  if (p->greedy_tree != 0) {
+    ASP_TRY(asp::bind_device());
+    const asp::GreedyTreeTarget target{p, nullptr, x.data()};
+    float split_ms[3] = {0.0f, 0.0f, 0.0f};
+    ASP_TRY(asp::greedy_tree_device(&target, 1, p->stream, split_ms));
+    asp::greedy_tree_record_ms(split_ms, false);
+  } else {
+    ASP_TRY(asp::greedy_tree_signs(L, x.data()));
+  }
   return greedy_relax(p, max_sweeps, x, out_x, out_e, out_sweeps, false);
 }
 
@@ -3678,7 +3687,9 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
     shared.clear();
   }
   if (live.empty()) return ASP_OK;
-  // ---- the host trees of ALL live items, on the pool (greedy.cpp) ----
+  // ---- the trees: the host trees of the live items that ask for them, on the pool (greedy.cpp); the
+  // device trees (asp_sa_set_greedy_tree, csrc/greedy_tree.hip) of the items that run alone here, and
+  // those of the shared launches below, straight into the buffer the state permute reads ----
   std::vector<uint64_t> tree_at(count, 0);  // offset of item i's words in h_x0
   uint64_t n_words = 0;
   for (uint32_t i : live) {
@@ -3687,15 +3698,37 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
   }
   std::vector<uint64_t> h_x0(n_words, 0);
   {
-    std::vector<const asp::SaHostLayout *> layouts(live.size());
-    std::vector<uint64_t *> outs(live.size());
-    for (size_t k = 0; k < live.size(); ++k) {
-      layouts[k] = &items[live[k]].plan->host;
-      outs[k] = h_x0.data() + tree_at[live[k]];
+    std::vector<const asp::SaHostLayout *> layouts;
+    std::vector<uint64_t *> outs;
+    for (uint32_t i : live) {
+      if (items[i].plan->greedy_tree != 0) continue;
+      layouts.push_back(&items[i].plan->host);
+      outs.push_back(h_x0.data() + tree_at[i]);
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    asp::greedy_tree_signs_many(layouts.data(), outs.data(), live.size());
-    g_greedy_tree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (!layouts.empty()) {
+      const auto t0 = std::chrono::steady_clock::now();
+      asp::greedy_tree_signs_many(layouts.data(), outs.data(), layouts.size());
+      g_greedy_tree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+  }
+  bool device_trees_ran = false;
+  {
+    std::vector<asp::GreedyTreeTarget> targets;
+    for (uint32_t i : alone) {
+      if (items[i].plan->greedy_tree != 0) {
+        targets.push_back(asp::GreedyTreeTarget{items[i].plan, nullptr, h_x0.data() + tree_at[i]});
+      }
+    }
+    if (!targets.empty()) {
+      asp::ScopedStream tree_stream;
+      ASP_TRY(tree_stream.acquire());
+      float split_ms[3] = {0.0f, 0.0f, 0.0f};
+      ASP_TRY(asp::greedy_tree_device(targets.data(), static_cast<uint32_t>(targets.size()), tree_stream.stream,
+                                      split_ms));
+      asp::greedy_tree_record_ms(split_ms, false);
+      device_trees_ran = true;
+      g_greedy_tree_ms += split_ms[0] + split_ms[1] + split_ms[2];
+    }
   }
   for (uint32_t i : alone) {
     const asp_sa_greedy_item &it = items[i];
@@ -3864,7 +3897,22 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
   ASP_TRY(d_post.alloc(n));
   ASP_TRY(d_slots.alloc(h_slots.size()));
   ASP_TRY(d_chains.alloc(n));
-  ASP_TRY(d_x0.upload(h_x0_shared.data(), n_x, s));
+  {
+    // host trees go up in one copy; device trees are written where the permute reads them (a batch of
+    // device trees only moves no tree words over PCIe)
+    std::vector<asp::GreedyTreeTarget> targets;
+    for (size_t k = 0; k < n; ++k) {
+      asp_sa_plan *p = items[shared[k]].plan;
+      if (p->greedy_tree != 0) targets.push_back(asp::GreedyTreeTarget{p, d_x0.ptr + off[k].x, nullptr});
+    }
+    if (targets.size() != n) ASP_TRY(d_x0.upload(h_x0_shared.data(), n_x, s));
+    if (!targets.empty()) {
+      float split_ms[3] = {0.0f, 0.0f, 0.0f};
+      ASP_TRY(asp::greedy_tree_device(targets.data(), static_cast<uint32_t>(targets.size()), s, split_ms));
+      asp::greedy_tree_record_ms(split_ms, device_trees_ran);
+      g_greedy_tree_ms += split_ms[0] + split_ms[1] + split_ms[2];
+    }
+  }
   ASP_TRY(d_problems.upload(h_problems.data(), n, s));
   ASP_TRY(d_post.upload(h_post.data(), n, s));
   ASP_TRY(d_slots.upload(h_slots.data(), h_slots.size(), s));

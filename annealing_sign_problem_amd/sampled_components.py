@@ -378,6 +378,9 @@ def parse_command_line(argv=None):
                         help="solve the greedy models of a round of --batch clusters with ONE batched "
                              "call (greedy_solve_batch) instead of one greedy_solve per model; the "
                              "output is the same")
+    parser.add_argument("--greedy-tree", choices=("host", "device"), default=None,
+                        help="where the greedy solver builds its strongest-coupling tree (default: "
+                             "$ASP_GREEDY_TREE or host); the output is the same")
     parser.add_argument("--jobs", type=int, default=1,
                         help="host threads building / solving clusters concurrently (independent "
                              "plans and HIP streams on one GPU; the output does not depend on it)")
@@ -651,9 +654,24 @@ def _main_with_workers(args):
 
 
 def main(argv=None):
+    args = parse_command_line(argv)
+    if args.greedy_tree is None:
+        return _main(args)
+    # --greedy-tree: every greedy solve of this run reads it (worker processes and a child inherit it)
+    before = os.environ.get("ASP_GREEDY_TREE")
+    os.environ["ASP_GREEDY_TREE"] = args.greedy_tree
+    try:
+        return _main(args)
+    finally:
+        if before is None:
+            os.environ.pop("ASP_GREEDY_TREE", None)
+        else:
+            os.environ["ASP_GREEDY_TREE"] = before
+
+
+def _main(args):
     from . import distributed as asp_dist
 
-    args = parse_command_line(argv)
     started = time.perf_counter()
 
     def phase(name):  # development aid: ASP_PIPELINE_TIMING=1 prints the wall time of the phases

@@ -857,13 +857,38 @@ typedef struct asp_sa_greedy_item {
 } asp_sa_greedy_item;
 int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count);
 /* Of this thread's last asp_sa_greedy_batch call, in ms (either pointer may be NULL): wall time of
- * the host trees on the pool, and device time of the descent launches (HIP events around the
+ * the host trees on the pool plus device time of the device trees (asp_sa_set_greedy_tree), and device
+ * time of the descent launches (HIP events around the
  * shared launches, plus the last chunk's of every item that ran alone). */
 int asp_sa_greedy_batch_last_ms(float *tree_ms, float *descent_ms);
 
 /* Host-only: the cluster-merging half of asp_sa_greedy (no relaxation, no device). */
 int asp_sa_greedy_tree_host(uint64_t num_spins, int64_t const *indptr, int32_t const *indices,
                             double const *data, double const *field, uint64_t *out_x);
+
+/* The same tree ON THE DEVICE (csrc/greedy_tree.hip): the configuration of
+ * ASP-GREEDY-1's steps 1-3, ceil(K/64) words, equal to asp_sa_greedy_tree_host's word for word.  The bonds
+ * are built and sorted by shared launches (a stable radix sort of ~bits(|w|)), every problem is one
+ * workgroup of k_greedy_tree — the signed forest in LDS when it fits the plan's limit, in a slab of HBM
+ * otherwise —, and the orientation by the field and the packing are one more launch.
+ * asp_sa_greedy_tree_batch: many plans in shared launches; item i equals the single call, for any order
+ * and composition of the batch.  ASP_ERR_INVALID, before any device work and before any output is
+ * written: a null plan, a null out_x, the same plan twice (a batch names the item's index).  count = 0
+ * needs no device; a plan with K = 0 runs nothing and leaves its out_x untouched; a plan without bonds
+ * returns the field-oriented all-isolated configuration. */
+int asp_sa_greedy_tree(asp_sa_plan *p, uint64_t *out_x);
+int asp_sa_greedy_tree_batch(asp_sa_plan *const *plans, uint32_t count, uint64_t *const *out_x);
+/* Which tree asp_sa_greedy and asp_sa_greedy_batch build for this plan (clamped to 0 .. 2): 0 the host
+ * tree (default), 1 the device tree with the forest placed by size, 2 the device tree with the forest
+ * forced into HBM.  A batch may mix them; results, out_sweeps included, never depend on it.  The device
+ * trees of a batch's shared launches are written straight into the buffer the state permute reads. */
+int asp_sa_set_greedy_tree(asp_sa_plan *p, int where);
+/* Device time (ms, HIP events) of the tree launches of this thread's last asp_sa_greedy_tree(_batch),
+ * asp_sa_greedy or asp_sa_greedy_batch call that built device trees; asp_sa_greedy_batch_last_ms's
+ * tree_ms is the wall time of the host pool plus this.  The split (any pointer may be NULL): bonds and
+ * sort, k_greedy_tree, orientation and packing. */
+float asp_sa_greedy_tree_last_ms(void);
+int asp_sa_greedy_tree_last_split_ms(float *bonds_sort_ms, float *tree_ms, float *orient_ms);
 
 /* Device time (ms, HIP events on the launch stream) of the sweep kernel of the
  * last asp_sa_anneal call, and of everything device-side in that call. */
