@@ -31,6 +31,7 @@ __all__ = [
     "save_ground_state",
     "compute_accuracy_and_overlap",
     "make_hamiltonian_extension",
+    "extension_spins",
     "sparsify_using_global_cutoff",
     "get_strongest_off_diag",
     "binary_search",
@@ -361,12 +362,22 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
 
 def make_hamiltonian_extension(model: IsingModel, log_psi_fn) -> IsingModel:
     """One-hop extension of a cluster: every state connected to it (common.py:516-522)."""
-    if _on_device(model.quantum_hamiltonian):
-        spins = model.quantum_hamiltonian.device().extend(model.spins)  # sorted and unique
-    else:
-        spins, _, _ = _batched_apply(model.quantum_hamiltonian, model.spins)
-        spins = np.unique(spins, axis=0)
+    spins = extension_spins(model.quantum_hamiltonian, model.spins)
     return make_ising_model(spins, model.quantum_hamiltonian, log_psi_fn=log_psi_fn)
+
+
+def extension_spins(hamiltonian, spins) -> np.ndarray:
+    """The sorted unique states connected to ``spins`` (their own included).  In a symmetry sector
+    with a character -1 a connection can point at an orbit of norm 0: its coefficient is exactly 0
+    and it is no basis state, so it is left out (on the device: asp_operator_extend)."""
+    if _on_device(hamiltonian):
+        return hamiltonian.device().extend(spins)  # sorted and unique
+    other, _, _ = _batched_apply(hamiltonian, spins)
+    other = np.unique(other, axis=0)
+    group = getattr(hamiltonian.basis, "group", None)
+    if group is not None and getattr(group, "spin_inversion", 0) < 0:
+        other = other[group.state_info(other)[2] > 0]
+    return other
 
 
 def get_strongest_off_diag(matrix) -> np.ndarray:

@@ -433,11 +433,15 @@ __global__ __launch_bounds__(kThreads) void k_sym_rows(SymArgs a) {
 // extension: sorted unique targets
 // ---------------------------------------------------------------------------
 
+// `drop`: the value that stands for "no state" (k_symmetrise / k_symmetrise_rows in extension mode),
+// left out when `dropping`.
 __global__ __launch_bounds__(kThreads) void k_flag_first(const uint64_t *__restrict__ sorted,
-                                                        uint64_t n, uint32_t *__restrict__ flag) {
+                                                        uint64_t n, bool dropping, uint64_t drop,
+                                                        uint32_t *__restrict__ flag) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (i >= n) return;
-  flag[i] = (i == 0 || sorted[i] != sorted[i - 1]) ? 1u : 0u;
+  const bool first = i == 0 || sorted[i] != sorted[i - 1];
+  flag[i] = (first && !(dropping && sorted[i] == drop)) ? 1u : 0u;
 }
 
 __global__ __launch_bounds__(kThreads) void k_scatter_first(const uint64_t *__restrict__ sorted,
@@ -457,6 +461,24 @@ __global__ __launch_bounds__(kThreads) void k_scatter_first(const uint64_t *__re
 // stabiliser) / |G|.  One lane per state, all lanes walk the permutations together, so the
 // destination table (u8[P][64], site i -> table[g][i]) is read with scalar loads.  Spin inversion
 // needs no second walk: the flipped image is the complement of the plain one.
+//
+// The character is numpy's (SymmetryGroup.state_info): that of inversion iff the smallest FLIPPED
+// image lies strictly below the smallest PLAIN image.  The two minima are kept apart, because on an
+// orbit that inversion maps onto itself a plain and a flipped image coincide, and which of them one
+// sequential walk meets first depends on the order of the elements.  With character -1 such orbits
+// have norm 0, the coefficient is (c * chi) * 0, and only the sign of that zero tells the rules
+// apart; the reference is numpy, bit for bit.
+//
+// Orbits of norm 0 (a stabiliser element of character -1) are not basis states:
+//   * as a SOURCE they are an error: k_source_norms / k_symmetrise_rows count them in `outside`,
+//     and every entry point fails with ASP_ERR_INVALID once it has read the counter (together with
+//     a size it copies back anyway);
+//   * as a TARGET they stay in asp_operator_apply's output with their representative and
+//     coefficient exactly 0 (Operator.to_sparse skips them by that), contribute nothing to the
+//     coupling build (they are in no key set), and are left out of the extension: in extension
+//     mode the kernels write g.mask in their place — all sites up, which inversion maps to 0, so
+//     never a representative in a group with inversion, the only groups that have norm 0 — and
+//     k_flag_first drops that value after the sort.
 
 struct StateInfo {
   uint64_t representative;
@@ -465,9 +487,9 @@ struct StateInfo {
 };
 
 __device__ __forceinline__ StateInfo state_info(const SymmetryArgs &g, uint64_t x) {
-  uint64_t best = x;  // the identity is element 0
+  uint64_t plain = x;       // the identity is element 0
+  uint64_t flipped = ~0ull;  // (no flipped image yet; never below a plain one)
   int32_t stabiliser = 0;
-  bool through_flip = false;
   for (uint32_t e = 0; e < g.num_permutations; ++e) {
     const uint8_t *dst = g.table + static_cast<size_t>(e) * 64u;
     uint64_t y = 0;
@@ -475,44 +497,43 @@ __device__ __forceinline__ StateInfo state_info(const SymmetryArgs &g, uint64_t 
       y |= ((x >> i) & 1ull) << dst[i];
     }
     stabiliser += y == x ? 1 : 0;
-    if (y < best) {
-      best = y;
-      through_flip = false;
-    }
+    plain = y < plain ? y : plain;
     if (g.inversion != 0) {
       const uint64_t z = ~y & g.mask;
       stabiliser += z == x ? g.inversion : 0;
-      if (z < best) {
-        best = z;
-        through_flip = true;
-      }
+      flipped = z < flipped ? z : flipped;
     }
   }
+  const bool through_flip = g.inversion != 0 && flipped < plain;
   const double order = static_cast<double>(g.num_permutations) * (g.inversion != 0 ? 2.0 : 1.0);
   StateInfo out;
-  out.representative = best;
+  out.representative = through_flip ? flipped : plain;
   out.character = (through_flip && g.inversion < 0) ? -1.0 : 1.0;
   // the same expression as the numpy reference: sqrt(max(stabiliser, 0) / |G|)
   out.norm = sqrt(static_cast<double>(stabiliser > 0 ? stabiliser : 0) / order);
   return out;
 }
 
-// norm of every source state (row)
+// norm of every source state (row); `outside` (may be null) counts the sources of norm 0
 __global__ __launch_bounds__(kThreads) void k_source_norms(SymmetryArgs g,
                                                           const uint64_t *__restrict__ keys,
-                                                          uint64_t n, double *__restrict__ norms) {
+                                                          uint64_t n, double *__restrict__ norms,
+                                                          unsigned long long *__restrict__ outside) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (i >= n) return;
-  norms[i] = state_info(g, keys[i]).norm;
+  const double norm = state_info(g, keys[i]).norm;
+  norms[i] = norm;
+  if (outside && norm == 0.0) atomicAdd(outside, 1ull);
 }
 
 // Every emitted connection: target -> representative, coefficient -> c * chi * norm(target) /
-// norm(source).  The row of an entry is found by bisection in the offsets.
+// norm(source).  The row of an entry is found by bisection in the offsets.  `extension`: targets
+// of norm 0 become g.mask ("no state").
 __global__ __launch_bounds__(kThreads) void k_symmetrise(SymmetryArgs g,
                                                         const int64_t *__restrict__ offsets,
                                                         uint64_t num_rows,
                                                         const double *__restrict__ source_norms,
-                                                        uint64_t total,
+                                                        uint64_t total, bool extension,
                                                         uint64_t *__restrict__ other_keys,
                                                         double *__restrict__ other_coeffs) {
   const uint64_t e = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
@@ -527,7 +548,7 @@ __global__ __launch_bounds__(kThreads) void k_symmetrise(SymmetryArgs g,
     }
   }
   const StateInfo info = state_info(g, other_keys[e]);
-  other_keys[e] = info.representative;
+  other_keys[e] = (extension && info.norm == 0.0) ? g.mask : info.representative;
   // numpy: values * character * norm / source_norm, left to right
   other_coeffs[e] = __ddiv_rn(__dmul_rn(__dmul_rn(other_coeffs[e], info.character), info.norm),
                               source_norms[lo]);
@@ -540,15 +561,18 @@ __global__ __launch_bounds__(kThreads) void k_symmetrise(SymmetryArgs g,
 // stabiliser, i.e. its norm; then lanes over the row's targets, every element costing one LDS
 // broadcast read, two table bytes and an XOR instead of a number_spins-bit permutation.  The
 // elements are walked in the same order with the same comparisons as state_info, so the
-// representatives, characters and norms are the same bits.  (Measured on the 36-site kagome model,
-// 144 permutations x inversion: the two kernels it replaces were half of the device time of the
-// sampled-cluster pipeline, profiles/r03_pipeline_greedy_kernel_stats.csv.)
+// representatives, characters and norms are the same bits; `outside` and `extension` as there.
+// (Measured on the 36-site kagome model, 144 permutations x inversion: the two kernels it replaces
+// were half of the device time of the sampled-cluster pipeline,
+// profiles/r03_pipeline_greedy_kernel_stats.csv.)
 // LDS: images u64[kWaves][P] | destination table, transposed, u8[number_spins][P].
 __global__ __launch_bounds__(kThreads) void k_symmetrise_rows(SymmetryArgs g,
                                                              const uint64_t *__restrict__ keys,
                                                              uint64_t num_rows,
                                                              const int64_t *__restrict__ offsets,
                                                              double *__restrict__ source_norms,
+                                                             unsigned long long *__restrict__ outside,
+                                                             bool extension,
                                                              uint64_t *__restrict__ other_keys,
                                                              double *__restrict__ other_coeffs) {
   extern __shared__ __align__(16) uint8_t symmetry_lds[];
@@ -584,7 +608,10 @@ __global__ __launch_bounds__(kThreads) void k_symmetrise_rows(SymmetryArgs g,
   const double order = static_cast<double>(P) * (g.inversion != 0 ? 2.0 : 1.0);
   // the same expression as state_info / the numpy reference: sqrt(max(stabiliser, 0) / |G|)
   const double source_norm = sqrt(static_cast<double>(stabiliser > 0 ? stabiliser : 0) / order);
-  if (lane == 0) source_norms[r] = source_norm;
+  if (lane == 0) {
+    source_norms[r] = source_norm;
+    if (source_norm == 0.0) atomicAdd(outside, 1ull);
+  }
   // ---- the row's targets, 64 at a time ----
   const int64_t begin = offsets[r], end = offsets[r + 1];
   for (int64_t base = begin; base < end; base += 64) {
@@ -596,12 +623,14 @@ __global__ __launch_bounds__(kThreads) void k_symmetrise_rows(SymmetryArgs g,
     // the usual case, at most two flipped bits: their sites once, outside the walk over the group
     const uint32_t i0 = flipped ? static_cast<uint32_t>(__builtin_ctzll(m)) * P : 0u;
     const uint32_t i1 = flipped ? static_cast<uint32_t>(63 - __builtin_clzll(m)) * P : 0u;
-    uint64_t best = t;  // the identity is element 0
+    uint64_t plain_min = t;         // the identity is element 0
+    uint64_t flipped_min = ~0ull;   // smallest flipped image (state_info's minimum rule)
     int32_t fixed = 0;
-    bool through_flip = false;
     for (uint32_t e = 0; e < P; ++e) {
       uint64_t image_m = 0;
       if (flipped > 2) {
+        // (not reachable through two-site bonds, which flip at most two sites; kept for operators
+        // with wider terms)
         for (uint64_t x = m; x != 0; x &= x - 1) {
           image_m |= 1ull << where[static_cast<uint32_t>(__builtin_ctzll(x)) * P + e];
         }
@@ -610,23 +639,18 @@ __global__ __launch_bounds__(kThreads) void k_symmetrise_rows(SymmetryArgs g,
       }
       const uint64_t y = mine[e] ^ image_m;
       fixed += y == t ? 1 : 0;
-      if (y < best) {
-        best = y;
-        through_flip = false;
-      }
+      plain_min = y < plain_min ? y : plain_min;
       if (g.inversion != 0) {
         const uint64_t z = ~y & g.mask;
         fixed += z == t ? g.inversion : 0;
-        if (z < best) {
-          best = z;
-          through_flip = true;
-        }
+        flipped_min = z < flipped_min ? z : flipped_min;
       }
     }
     if (on) {
-      const double character = (through_flip && g.inversion < 0) ? -1.0 : 1.0;
+      const bool by_flip = g.inversion != 0 && flipped_min < plain_min;
+      const double character = (by_flip && g.inversion < 0) ? -1.0 : 1.0;
       const double norm = sqrt(static_cast<double>(fixed > 0 ? fixed : 0) / order);
-      other_keys[at] = best;
+      other_keys[at] = (extension && norm == 0.0) ? g.mask : (by_flip ? flipped_min : plain_min);
       // numpy: values * character * norm / source_norm, left to right (as k_symmetrise)
       other_coeffs[at] = __ddiv_rn(__dmul_rn(__dmul_rn(other_coeffs[at], character), norm), source_norm);
     }
@@ -695,12 +719,36 @@ int count_connections(const asp_operator *op, uint64_t n, const uint64_t *keys, 
   return ASP_OK;
 }
 
-// After k_apply<true>: representatives and rescaled coefficients for a symmetry-adapted basis.
-// Fails with ASP_ERR_INVALID when a source state lies outside the sector (norm 0).
+// What the symmetrise pass leaves behind besides the entries: the source norms and the number of
+// sources outside the sector (norm 0), which the caller reads with the next size it copies back.
+struct Symmetrised {
+  DeviceBuffer<double> d_norms;
+  DeviceBuffer<unsigned long long> d_outside;
+  unsigned long long outside = 0;
+  // queues the copy of the counter (no-op for a plain basis); valid after the next synchronisation
+  int fetch(hipStream_t stream) {
+    if (!d_outside.ptr) return ASP_OK;
+    return d_outside.download(&outside, 1, stream);
+  }
+  // after that synchronisation: ASP_ERR_INVALID when a source lies outside the sector
+  int check() const {
+    if (outside == 0) return ASP_OK;
+    return asp::set_error(ASP_ERR_INVALID,
+                          "%llu states lie outside the symmetry sector (norm 0: an element of their "
+                          "stabiliser has character -1); they are not basis states", outside);
+  }
+};
+
+// After k_apply<true>: representatives and rescaled coefficients for a symmetry-adapted basis;
+// `extension`: targets of norm 0 become the "no state" value instead.  A source state outside the
+// sector (norm 0) makes the entry point fail with ASP_ERR_INVALID: Symmetrised::fetch / check.
 int symmetrise_batch(const asp_operator *op, uint64_t n, const ApplyBatch &w, uint64_t *d_other,
-                     double *d_coeffs, DeviceBuffer<double> *d_norms, hipStream_t stream) {
+                     double *d_coeffs, Symmetrised *sym, bool extension, hipStream_t stream) {
   if (op->num_permutations == 0 || n == 0) return ASP_OK;
+  DeviceBuffer<double> *d_norms = &sym->d_norms;
   ASP_TRY(d_norms->alloc(n));
+  ASP_TRY(sym->d_outside.alloc(1));
+  ASP_HIP_TRY(hipMemsetAsync(sym->d_outside.ptr, 0, sizeof(unsigned long long), stream));
   const SymmetryArgs g = op->symmetry();
   // a wavefront per row (k_symmetrise_rows) when the group's tables fit the LDS; the entry-wise
   // kernels otherwise (ASP_SYMMETRISE_ROWS=0: always; tests compare the two)
@@ -714,12 +762,13 @@ int symmetrise_batch(const asp_operator *op, uint64_t n, const ApplyBatch &w, ui
                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     }
     hipLaunchKernelGGL(k_symmetrise_rows, dim3(grid_for(n, kWaves)), dim3(kThreads), lds, stream, g,
-                       w.d_keys.ptr, n, w.d_offsets.ptr, d_norms->ptr, d_other, d_coeffs);
+                       w.d_keys.ptr, n, w.d_offsets.ptr, d_norms->ptr, sym->d_outside.ptr, extension,
+                       d_other, d_coeffs);
   } else {
     hipLaunchKernelGGL(k_source_norms, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, stream, g,
-                       w.d_keys.ptr, n, d_norms->ptr);
+                       w.d_keys.ptr, n, d_norms->ptr, sym->d_outside.ptr);
     hipLaunchKernelGGL(k_symmetrise, dim3(grid_for(w.total, kThreads)), dim3(kThreads), 0, stream, g,
-                       w.d_offsets.ptr, n, d_norms->ptr, w.total, d_other, d_coeffs);
+                       w.d_offsets.ptr, n, d_norms->ptr, w.total, extension, d_other, d_coeffs);
   }
   ASP_HIP_TRY(hipGetLastError());
   return ASP_OK;
@@ -733,7 +782,8 @@ int ising_with_duplicates(const asp_operator *op, uint64_t K, const uint64_t *ke
   Timer timer;
   ApplyBatch w;
   DeviceBuffer<uint64_t> d_other;
-  DeviceBuffer<double> d_coeffs, d_norms, d_psi, d_mval, d_val;
+  DeviceBuffer<double> d_coeffs, d_psi, d_mval, d_val;
+  Symmetrised sym;
   DeviceBuffer<unsigned long long> d_slots, d_missing;
   DeviceBuffer<uint32_t> d_mrow_nnz, d_row_nnz;
   DeviceBuffer<int64_t> d_mrow_start, d_row_start, d_scratch;
@@ -747,7 +797,7 @@ int ising_with_duplicates(const asp_operator *op, uint64_t K, const uint64_t *ke
                      op->d_bonds.ptr, op->num_bonds, w.d_keys.ptr, K, w.d_offsets.ptr, nullptr,
                      d_other.ptr, d_coeffs.ptr);
   ASP_HIP_TRY(hipGetLastError());
-  ASP_TRY(symmetrise_batch(op, K, w, d_other.ptr, d_coeffs.ptr, &d_norms, stream));
+  ASP_TRY(symmetrise_batch(op, K, w, d_other.ptr, d_coeffs.ptr, &sym, false, stream));
   uint64_t slots_n = 1024;
   while (slots_n < 2 * K) slots_n <<= 1;
   ASP_TRY(d_psi.alloc(K));
@@ -792,7 +842,9 @@ int ising_with_duplicates(const asp_operator *op, uint64_t K, const uint64_t *ke
   int64_t merged = 0;
   ASP_HIP_TRY(hipMemcpyAsync(&merged, d_mrow_start.ptr + K, sizeof merged, hipMemcpyDeviceToHost,
                              stream));
+  ASP_TRY(sym.fetch(stream));
   ASP_HIP_TRY(hipStreamSynchronize(stream));
+  ASP_TRY(sym.check());  // (before a coefficient divided by a zero norm reaches a sum)
   ASP_TRY(d_mcol.alloc(static_cast<uint64_t>(merged)));
   ASP_TRY(d_mval.alloc(static_cast<uint64_t>(merged)));
   m.mrow_start = d_mrow_start.ptr;
@@ -1008,19 +1060,20 @@ int asp_operator_state_info(asp_operator const *op, uint64_t n, uint64_t const *
     DeviceBuffer<double> d_norms;
     ASP_TRY(d_norms.alloc(n));
     hipLaunchKernelGGL(k_source_norms, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, stream, g,
-                       d_keys.ptr, n, d_norms.ptr);
+                       d_keys.ptr, n, d_norms.ptr, nullptr);
     ASP_HIP_TRY(hipGetLastError());
     ASP_TRY(d_norms.download(norms, n, stream));
     ASP_HIP_TRY(hipStreamSynchronize(stream));
   }
   hipLaunchKernelGGL(k_symmetrise, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, stream, g,
-                     d_offsets.ptr, n, d_ones.ptr, n, d_keys.ptr, d_coeffs.ptr);
+                     d_offsets.ptr, n, d_ones.ptr, n, false, d_keys.ptr, d_coeffs.ptr);
   ASP_HIP_TRY(hipGetLastError());
   if (representatives) ASP_TRY(d_keys.download(representatives, n, stream));
   std::vector<double> signed_norm(characters ? n : 0);
   if (characters) ASP_TRY(d_coeffs.download(signed_norm.data(), n, stream));
   ASP_HIP_TRY(hipStreamSynchronize(stream));
   if (characters) {
+    // (1 * chi) * norm: the sign is the character; a state of norm 0 (-0.0 < 0.0 is false) reports +1
     for (uint64_t i = 0; i < n; ++i) characters[i] = signed_norm[i] < 0.0 ? -1.0 : 1.0;
   }
   return ASP_OK;
@@ -1055,7 +1108,8 @@ int asp_operator_apply(asp_operator const *op, uint64_t n, uint64_t const *keys,
                           (unsigned long long)w.total, (unsigned long long)capacity);
   }
   DeviceBuffer<uint64_t> d_other;
-  DeviceBuffer<double> d_coeffs, d_norms;
+  DeviceBuffer<double> d_coeffs;
+  Symmetrised sym;
   asp::StreamFence fence(stream);  // error exits wait for the stream before the buffers go
   ASP_TRY(d_other.alloc(w.total));
   ASP_TRY(d_coeffs.alloc(w.total));
@@ -1064,14 +1118,15 @@ int asp_operator_apply(asp_operator const *op, uint64_t n, uint64_t const *keys,
                        op->d_bonds.ptr, op->num_bonds, w.d_keys.ptr, n, w.d_offsets.ptr, nullptr,
                        d_other.ptr, d_coeffs.ptr);
     ASP_HIP_TRY(hipGetLastError());
-    ASP_TRY(symmetrise_batch(op, n, w, d_other.ptr, d_coeffs.ptr, &d_norms, stream));
+    ASP_TRY(symmetrise_batch(op, n, w, d_other.ptr, d_coeffs.ptr, &sym, false, stream));
   }
   ASP_TRY(timer.stop());
   ASP_TRY(d_other.download(other_keys, w.total, stream));
   ASP_TRY(d_coeffs.download(other_coeffs, w.total, stream));
+  ASP_TRY(sym.fetch(stream));
   ASP_HIP_TRY(hipStreamSynchronize(stream));
   timer.finish();
-  return ASP_OK;
+  return sym.check();
 }
 
 namespace {
@@ -1216,7 +1271,8 @@ int asp_operator_extend(asp_operator const *op, uint64_t n, uint64_t const *keys
   const uint64_t N = w.total;
   if (N >= (1ull << 32)) return asp::set_error(ASP_ERR_TOO_LARGE, "more than 2^32 connections");
   DeviceBuffer<uint64_t> d_targets, d_sorted, d_unique;
-  DeviceBuffer<double> d_coeffs, d_norms;  // written by k_apply<true>, not used here
+  DeviceBuffer<double> d_coeffs;  // written by k_apply<true>, not used here
+  Symmetrised sym;
   DeviceBuffer<uint32_t> d_flag;
   DeviceBuffer<int64_t> d_pos, d_scratch;
   DeviceBuffer<uint8_t> d_temp;
@@ -1231,8 +1287,11 @@ int asp_operator_extend(asp_operator const *op, uint64_t n, uint64_t const *keys
                      op->d_bonds.ptr, op->num_bonds, w.d_keys.ptr, n, w.d_offsets.ptr, nullptr,
                      d_targets.ptr, d_coeffs.ptr);
   ASP_HIP_TRY(hipGetLastError());
-  // symmetry-adapted basis: the extension is the set of the targets' REPRESENTATIVES
-  ASP_TRY(symmetrise_batch(op, n, w, d_targets.ptr, d_coeffs.ptr, &d_norms, stream));
+  // symmetry-adapted basis: the extension is the set of the targets' REPRESENTATIVES, without the
+  // orbits of norm 0 (not basis states), which arrive as the "no state" value and are dropped
+  ASP_TRY(symmetrise_batch(op, n, w, d_targets.ptr, d_coeffs.ptr, &sym, true, stream));
+  const asp::SymmetryArgs g = op->symmetry();
+  const bool dropping = op->num_permutations != 0 && op->inversion < 0;
   size_t temp_bytes = 0;
   ASP_HIP_TRY(rocprim::radix_sort_keys(nullptr, temp_bytes, d_targets.ptr, d_sorted.ptr, N, 0,
                                        op->number_spins, stream));
@@ -1240,11 +1299,13 @@ int asp_operator_extend(asp_operator const *op, uint64_t n, uint64_t const *keys
   ASP_HIP_TRY(rocprim::radix_sort_keys(d_temp.ptr, temp_bytes, d_targets.ptr, d_sorted.ptr, N, 0,
                                        op->number_spins, stream));
   hipLaunchKernelGGL(k_flag_first, dim3(grid_for(N, kThreads)), dim3(kThreads), 0, stream,
-                     d_sorted.ptr, N, d_flag.ptr);
+                     d_sorted.ptr, N, dropping, g.mask, d_flag.ptr);
   ASP_TRY(asp::exclusive_scan_u32(d_flag.ptr, N, d_pos.ptr, d_scratch.ptr, stream));
   int64_t unique = 0;
   ASP_HIP_TRY(hipMemcpyAsync(&unique, d_pos.ptr + N, sizeof unique, hipMemcpyDeviceToHost, stream));
+  ASP_TRY(sym.fetch(stream));
   ASP_HIP_TRY(hipStreamSynchronize(stream));
+  ASP_TRY(sym.check());
   *count = static_cast<uint64_t>(unique);
   if (capacity == 0 && !out) {  // sizing call
     ASP_TRY(timer.stop());

@@ -492,7 +492,8 @@ class DeviceOperator:
         return indptr, col[:z], val[:z]  # (views: see ising)
 
     def extend(self, keys) -> np.ndarray:
-        """Sorted unique union of the targets of ``keys`` (their own states included)."""
+        """Sorted unique union of the targets of ``keys`` (their own states included; in a
+        symmetry sector their representatives, without the orbits of norm 0)."""
         import ctypes
 
         _lib = self._lib_module

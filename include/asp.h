@@ -178,7 +178,14 @@ void asp_operator_destroy(asp_operator *op);
  * representative of the target and the coefficient c * chi(g) * norm(target) / norm(source),
  * norm(s)^2 = (sum of the stabiliser's characters) / |G|, and asp_operator_extend the sorted
  * unique representatives.  Equal targets within a row are not merged (asp_operator_ising
- * then runs its duplicate-keeping variant). */
+ * then runs its duplicate-keeping variant).
+ * The character of a state is that of inversion iff its smallest flipped image lies strictly below
+ * its smallest plain image (SymmetryGroup.state_info's rule).  With spin_inversion = -1 an orbit
+ * whose stabiliser holds an element of character -1 has norm 0 and is no basis state: as a KEY it
+ * makes asp_operator_apply, asp_operator_ising, asp_operator_ising_csr and asp_operator_extend
+ * fail with ASP_ERR_INVALID (the message names the sector; outputs are unspecified then); as a
+ * TARGET it stays in asp_operator_apply's output with its representative and coefficient exactly
+ * 0, and is left out of asp_operator_extend's set. */
 int asp_operator_set_symmetry(asp_operator *op, uint32_t num_permutations, uint8_t const *table,
                               int32_t spin_inversion);
 /* (representative, character of a group element mapping the key onto it, norm) of n keys; any
