@@ -100,6 +100,16 @@ int shutdown_pools();
 // Compute units and opt-in LDS bytes per workgroup of the current device (queried once).
 int device_limits(int *num_cus, size_t *max_lds);
 
+// A launch with more than 64 KB of dynamic LDS needs the kernel opted in first; at or below that
+// nothing is to do.  The limit belongs to the KERNEL, not to the launch: where launches of one kernel
+// run side by side, set it once, to the largest of them, before the first.
+inline int allow_dynamic_lds(const void *kernel, size_t bytes) {
+  if (bytes > 64 * 1024) {
+    ASP_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
+  }
+  return ASP_OK;
+}
+
 // ---- owning device buffer --------------------------------------------------
 template <typename T>
 struct DeviceBuffer {

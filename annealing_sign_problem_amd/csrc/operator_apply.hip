@@ -757,10 +757,7 @@ int symmetrise_batch(const asp_operator *op, uint64_t n, const ApplyBatch &w, ui
   bool by_rows = lds <= 160u * 1024u;
   if (const char *env = std::getenv("ASP_SYMMETRISE_ROWS")) by_rows = by_rows && std::atoi(env) != 0;
   if (by_rows) {
-    if (lds > 64u * 1024u) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_symmetrise_rows),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    }
+    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_symmetrise_rows), lds));
     hipLaunchKernelGGL(k_symmetrise_rows, dim3(grid_for(n, kWaves)), dim3(kThreads), lds, stream, g,
                        w.d_keys.ptr, n, w.d_offsets.ptr, d_norms->ptr, sym->d_outside.ptr, extension,
                        d_other, d_coeffs);
@@ -831,10 +828,7 @@ int ising_with_duplicates(const asp_operator *op, uint64_t K, const uint64_t *ke
   }
   for (const void *kernel : {reinterpret_cast<const void *>(k_merge_rows<false>),
                              reinterpret_cast<const void *>(k_merge_rows<true>)}) {
-    if (lds > 64u * 1024u) {
-      ASP_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(lds)));
-    }
+    ASP_TRY(asp::allow_dynamic_lds(kernel, lds));
   }
   hipLaunchKernelGGL(k_merge_rows<false>, dim3(grid_for(K, kWaves)), dim3(kThreads), lds, stream, m);
   ASP_HIP_TRY(hipGetLastError());
@@ -1221,11 +1215,7 @@ int operator_ising(asp_operator const *op, uint64_t num_spins, uint64_t const *k
     return asp::set_error(ASP_ERR_TOO_LARGE, "%u bonds need %zu bytes of LDS per workgroup",
                           op->num_bonds, lds);
   }
-  if (lds > 64u * 1024u) {
-    ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ising_rows<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>(lds)));
-  }
+  ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_ising_rows<true>), lds));
   hipLaunchKernelGGL(k_ising_rows<true>, dim3(grid_for(K, kWaves)), dim3(kThreads), lds, stream, a);
   ASP_HIP_TRY(hipGetLastError());
   ASP_TRY(timer.stop());

@@ -129,6 +129,46 @@ int upload_vector(DeviceBuffer<T> &dst, const std::vector<T> &src, hipStream_t s
   return dst.upload(src.data(), src.size(), stream);
 }
 
+struct EventPool {
+  std::vector<hipEvent_t> events;
+  ~EventPool() {
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+  }
+  int make(hipEvent_t *out, bool timing = false) {
+    ASP_HIP_TRY(hipEventCreateWithFlags(out, timing ? hipEventDefault : hipEventDisableTiming));
+    events.push_back(*out);
+    return ASP_OK;
+  }
+};
+
+// XCD-aware slot lists of one shared launch.  Workgroups are dealt round-robin over the chip's eight
+// XCDs (blocks b and b + 8 share one, each XCD with an L2 of its own), so the workgroups of ONE member
+// get slots of one XCD — what every workgroup of the member reads is then fetched from HBM by one L2
+// instead of eight (a placement for speed only: nothing depends on it).  The members (indices, in the
+// caller's order) go in descending work_of(member), stable, each whole — groups_of(member) slots
+// {member, 0 .. groups - 1} — to the XCD with the fewest slots so far (ties: lowest index): balanced
+// and deterministic.  Every list is then padded to the longest with {0xFFFFFFFF, 0}; returns that
+// length.  How the eight lists are flattened is the caller's.
+constexpr int kXcds = 8;
+template <typename Slot, typename WorkOf, typename GroupsOf>
+uint32_t deal_to_xcds(std::vector<uint32_t> members, WorkOf work_of, GroupsOf groups_of,
+                      std::vector<Slot> (&per_xcd)[kXcds]) {
+  std::stable_sort(members.begin(), members.end(), [&](uint32_t a, uint32_t b) { return work_of(a) > work_of(b); });
+  for (auto &list : per_xcd) list.clear();
+  for (uint32_t k : members) {
+    int least = 0;
+    for (int x = 1; x < kXcds; ++x) {
+      if (per_xcd[x].size() < per_xcd[least].size()) least = x;
+    }
+    const uint32_t groups = groups_of(k);
+    for (uint32_t g = 0; g < groups; ++g) per_xcd[least].push_back(Slot{k, g});
+  }
+  size_t longest = 0;
+  for (auto &list : per_xcd) longest = std::max(longest, list.size());
+  for (auto &list : per_xcd) list.resize(longest, Slot{0xFFFFFFFFu, 0u});
+  return static_cast<uint32_t>(longest);
+}
+
 // perm[c][b] = sign words (bit = 1: s = -1) of configuration c in the plan's block order, from
 // packed original-order configurations x[c][ceil(K/64)] (bit = 1: s = +1); on the plan's stream.
 int sa_permute_bits(asp_sa_plan *p, const uint64_t *x, uint32_t count, uint64_t *perm);

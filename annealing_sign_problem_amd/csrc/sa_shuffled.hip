@@ -2596,13 +2596,9 @@ struct ShuffledRun {
       launched = out_trace ? reinterpret_cast<const void *>(ladder_trace_kernel)
                            : reinterpret_cast<const void *>(ladder_kernel);
     }
-    if (lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(launched, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    }
-    if (order_lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wide_orders ? k_shuffled_orders<true> : k_shuffled_orders<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(order_lds)));
-    }
+    ASP_TRY(asp::allow_dynamic_lds(launched, lds));
+    ASP_TRY(asp::allow_dynamic_lds(
+        reinterpret_cast<const void *>(wide_orders ? k_shuffled_orders<true> : k_shuffled_orders<false>), order_lds));
     ASP_TRY(plan_buffers(chunk));
     WidePartsMax wide;
     if (wide_orders) {
@@ -2917,18 +2913,6 @@ ShuffledLadderBatchKernel shuffled_ladder_batch_kernel_for(int m, int layout, bo
   }
 }
 
-struct EventPool {
-  std::vector<hipEvent_t> events;
-  ~EventPool() {
-    for (hipEvent_t e : events) (void)hipEventDestroy(e);
-  }
-  int make(hipEvent_t *out, bool timing = false) {
-    ASP_HIP_TRY(hipEventCreateWithFlags(out, timing ? hipEventDefault : hipEventDisableTiming));
-    events.push_back(*out);
-    return ASP_OK;
-  }
-};
-
 // The handles of the group's runs (ShuffledRun::resume) into the runs' buffers before an attempt
 // (`in`), or out of them after the attempt that succeeded: one launch per state type and one for the
 // integers and best configurations, for all handles; queued on `stream` and waited for.
@@ -3043,7 +3027,7 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
     size_t lds = 0;
     hipEvent_t swept[ShuffledRun::kSets] = {};
   };
-  EventPool events;
+  asp::EventPool events;
   hipEvent_t ordered[ShuffledRun::kSets], t_begin, t_end;
   for (auto &e : ordered) ASP_TRY(events.make(&e));
   ASP_TRY(events.make(&t_begin, true));
@@ -3062,14 +3046,8 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
       of = std::max(of, r->order_lds);
     }
     for (ShuffledRun *r : runs) ASP_HIP_TRY(hipStreamSynchronize(r->p->stream));  // schedules up, status zeroed
-    if (order_lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_shuffled_orders_batch<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(order_lds)));
-    }
-    if (order_lds_wide > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_shuffled_orders_batch<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(order_lds_wide)));
-    }
+    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_shuffled_orders_batch<false>), order_lds));
+    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_shuffled_orders_batch<true>), order_lds_wide));
     std::vector<std::unique_ptr<Class>> classes;
     for (uint32_t i = 0; i < P; ++i) {
       ShuffledRun *r = runs[i];
@@ -3111,28 +3089,16 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
                     : reinterpret_cast<const void *>(shuffled_batch_kernel_for(m, layout, packed_lanes));
     };
     for (auto &c : classes) {
-      // the longest problems first: a workgroup's time is sweeps x levels x one block visit whatever
-      // the cluster's size, but the large clusters have more levels and wider rows
-      std::stable_sort(c->members.begin(), c->members.end(),
-                       [&](uint32_t x, uint32_t y) { return runs[x]->K > runs[y]->K; });
-      // XCD-aware slot table: workgroups are dealt round-robin over the chip's eight XCDs (blocks b
-      // and b + 8 share one, each XCD with an L2 of its own), so the workgroups of ONE problem get
-      // slots of equal index mod 8 — the sweep's coupling stream, read by every workgroup of the
-      // problem, is then fetched from HBM by one L2 instead of eight (a placement for speed only:
-      // nothing depends on it).  Problems go to the XCD with the fewest workgroups so far.
-      std::vector<ShuffledSlot> per_xcd[8];
-      for (uint32_t i : c->members) {
-        int least = 0;
-        for (int x = 1; x < 8; ++x) {
-          if (per_xcd[x].size() < per_xcd[least].size()) least = x;
-        }
-        for (uint32_t g = 0; g < runs[i]->wgs; ++g) per_xcd[least].push_back(ShuffledSlot{i, g});
-      }
-      size_t longest = 0;
-      for (auto &list : per_xcd) longest = std::max(longest, list.size());
+      // XCD-aware slot table (asp::deal_to_xcds), the longest problems first: a workgroup's time is
+      // sweeps x levels x one block visit whatever the cluster's size, but the large clusters have more
+      // levels and wider rows.  Flattened interleaved: the kernel reads slots[blockIdx.x], so the
+      // workgroups of ONE problem get slots of equal index mod 8 and share the coupling stream in one L2.
+      std::vector<ShuffledSlot> per_xcd[asp::kXcds];
+      const uint32_t longest = asp::deal_to_xcds(
+          c->members, [&](uint32_t i) { return runs[i]->K; }, [&](uint32_t i) { return runs[i]->wgs; }, per_xcd);
       std::vector<ShuffledSlot> slots;
-      for (size_t j = 0; j < longest; ++j) {
-        for (auto &list : per_xcd) slots.push_back(j < list.size() ? list[j] : ShuffledSlot{0xFFFFFFFFu, 0u});
+      for (uint32_t j = 0; j < longest; ++j) {
+        for (auto &list : per_xcd) slots.push_back(list[j]);
       }
       c->num_slots = static_cast<uint32_t>(slots.size());
       ASP_TRY(c->slots.alloc(slots.size()));
@@ -3155,12 +3121,7 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
                      c->m, c->layout, int(c->packed_lanes), c->members.size(), c->num_slots, c->waves, c->lds);
       }
     }
-    for (auto &k : kernel_lds) {
-      if (k.second > 64 * 1024) {
-        ASP_HIP_TRY(hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        static_cast<int>(k.second)));
-      }
-    }
+    for (auto &k : kernel_lds) ASP_TRY(asp::allow_dynamic_lds(k.first, k.second));
     // the wide order launches (large clusters): shapes for the largest of them; problems of the
     // fused path leave these kernels at once
     WidePartsMax wide;

@@ -43,7 +43,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <initializer_list>
+#include <memory>
 #include <mutex>
+#include <numeric>
 #include <type_traits>
 #include <vector>
 
@@ -2063,32 +2065,20 @@ int energies_of_perm(asp_sa_plan *p, const uint64_t *perm_words, uint32_t count,
   const size_t post_lds = static_cast<size_t>(L.num_blocks) * 64;  // a byte per position
   if (count >= 2 * kShare && p->use_post && post_lds <= p->max_lds) {
     // (asp_sa_set_post; plans whose bytes do not fit the LDS keep the kernels below)
-    if (post_lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sa_post<kShare>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(post_lds)));
-    }
+    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_sa_post<kShare>), post_lds));
     const PostArgs pa{ea, p->pos_of_spin.ptr, out_x, L.num_spins, words};
     const uint32_t waves = std::min<uint32_t>(16u, L.num_blocks);
     hipLaunchKernelGGL(k_sa_post<kShare>, dim3((count + kShare - 1) / kShare), dim3(64 * waves),
                        post_lds, p->stream, pa, count);
     out_x = nullptr;  // done
   } else if (count >= 2 * kShare && lds * kShare <= p->max_lds) {
-    if (lds * kShare > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(
-          reinterpret_cast<const void *>(k_sa_energy_blocks_multi<kShare>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds * kShare)));
-    }
+    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_sa_energy_blocks_multi<kShare>), lds * kShare));
     hipLaunchKernelGGL(k_sa_energy_blocks_multi<kShare>, dim3((count + kShare - 1) / kShare),
                        dim3(512), lds * kShare, p->stream, ea, count);
   } else if (lds > p->max_lds) {
     hipLaunchKernelGGL(k_sa_energy_blocks<false>, dim3(count), dim3(512), 0, p->stream, ea);
   } else {
-    if (lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sa_energy_blocks<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(lds)));
-    }
+    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_sa_energy_blocks<true>), lds));
     hipLaunchKernelGGL(k_sa_energy_blocks<true>, dim3(count), dim3(512), lds, p->stream, ea);
   }
   hipLaunchKernelGGL(k_sa_energy_fold, dim3(count), dim3(64), 0, p->stream, partial, L.num_blocks,
@@ -2422,10 +2412,7 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
     ta.flips = reinterpret_cast<uint64_t *>(area + head_bytes);
     const void *team_kernel = descent ? reinterpret_cast<const void *>(k_sa_sweep_team<true>)
                                       : reinterpret_cast<const void *>(k_sa_sweep_team<false>);
-    if (lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(team_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(lds)));
-    }
+    ASP_TRY(asp::allow_dynamic_lds(team_kernel, lds));
     ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
     ASP_HIP_TRY(hipEventRecord(p->ev[1], s));
     // An ORDINARY launch: team * repetitions <= CUs workgroups, each fitting a CU by itself,
@@ -2453,11 +2440,7 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
                                hipMemcpyDeviceToHost, s));
   } else {
     SweepKernel kernel = sweep_kernel_for(m, descent, layout, aligned_replicas(m, replica_offset));
-    if (lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(lds)));
-    }
+    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(kernel), lds));
     ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
     ASP_HIP_TRY(hipEventRecord(p->ev[1], s));
     hipLaunchKernelGGL(kernel, dim3(groups), dim3(threads), lds, s, args);
@@ -2603,10 +2586,7 @@ int chains_advance_colour(asp_sa_chains *c, double const *betas, double const *c
     args.trace = p->w_trace.ptr;
   }
   if (p->use_field_cache && !chosen.packed) attach_field_cache(p, padded, &args);
-  if (lds > 64 * 1024) {
-    ASP_HIP_TRY(hipFuncSetAttribute(kernel_address, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>(lds)));
-  }
+  ASP_TRY(asp::allow_dynamic_lds(kernel_address, lds));
   ASP_HIP_TRY(hipEventRecord(p->ev[1], s));
   if (ladder) {
     const ResumeLadder res{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done, p->w_betas.ptr};
@@ -2855,6 +2835,147 @@ uint32_t batch_waves(const asp::SaHostLayout &L) {
   return std::min<uint32_t>(widest_color(L), L.num_spins <= kBatchSmallMax ? 4u : 16u);
 }
 
+// ---- the shared launches of a batch ----
+// What the three batched entry points below (closed anneals, segments of handles, greedy descents) do
+// alike.  A member — a problem of `groups` workgroups taking about `work` each and `lds` bytes — belongs
+// to a class of workgroup shape; a class is ONE launch of 8 * slots_per_xcd workgroups over its XCD-aware
+// slot table [8][slots_per_xcd] (asp::deal_to_xcds, x-major: the kernels read
+// slots[(b & 7) * slots_per_xcd + (b >> 3)]), on a stream of its own so that the classes share the chip.
+struct ClassMember {
+  int cls;
+  double work;
+  uint32_t groups;
+  size_t lds;
+};
+struct ClassLaunch {
+  uint64_t slot_at = 0;
+  uint32_t slots_per_xcd = 0;
+  size_t lds = 0;  // the largest of its members
+  bool used = false;
+  hipEvent_t done = nullptr;  // recorded behind its launch
+};
+template <typename Args>  // {problems, slots, slots_per_xcd}
+struct ClassKernel {
+  void (*kernel)(Args);
+  uint32_t threads;
+};
+
+// Declared BEFORE the device buffers of an entry point (h_slots outlives the upload; the streams are
+// waited for and released after the buffers' StreamFence).
+struct ClassLauncher {
+  std::vector<ClassLaunch> launches;
+  std::vector<BatchSlot> h_slots;  // the classes' tables one after the other, for ONE upload
+  // [class]; an array, destroyed in reverse: the streams go back to the pool last acquired first, so
+  // every call leaves the pool — and with it the hardware queues of the next call's streams — as it was
+  std::unique_ptr<asp::ScopedStream[]> streams;
+  asp::EventPool events;
+  hipEvent_t begin = nullptr, end = nullptr;  // on the main stream around the launches, with timing
+
+  // The slot tables, and a stream and an event for every used class.
+  int build(const std::vector<ClassMember> &members, int num_classes) {
+    launches.assign(num_classes, ClassLaunch{});
+    streams.reset(new asp::ScopedStream[num_classes]);
+    for (int c = 0; c < num_classes; ++c) {
+      std::vector<uint32_t> of_class;
+      for (uint32_t k = 0; k < members.size(); ++k) {
+        if (members[k].cls != c) continue;
+        of_class.push_back(k);
+        launches[c].lds = std::max(launches[c].lds, members[k].lds);
+      }
+      if (of_class.empty()) continue;
+      std::vector<BatchSlot> per_xcd[asp::kXcds];
+      launches[c].used = true;
+      launches[c].slot_at = h_slots.size();
+      launches[c].slots_per_xcd = asp::deal_to_xcds(
+          of_class, [&](uint32_t k) { return members[k].work; }, [&](uint32_t k) { return members[k].groups; },
+          per_xcd);
+      for (auto &list : per_xcd) h_slots.insert(h_slots.end(), list.begin(), list.end());
+      ASP_TRY(streams[c].acquire());
+      ASP_TRY(events.make(&launches[c].done));
+    }
+    ASP_TRY(events.make(&begin, true));
+    return events.make(&end, true);
+  }
+
+  // Every used class c: kernel_of(c).kernel(Args{problems, its part of the uploaded slot table}) on the
+  // class's stream, between `begin` and `end` on the main stream `s`, which waits for all of them.
+  template <typename Args, typename Problem, typename KernelOf>
+  int run(hipStream_t s, const Problem *problems, const BatchSlot *d_slots, KernelOf kernel_of) {
+    const int num_classes = static_cast<int>(launches.size());
+    // (classes share kernels and run side by side: a kernel's dynamic-LDS limit is set once, to the
+    // largest class that uses it, before the first launch)
+    std::vector<std::pair<const void *, size_t>> kernel_lds;
+    for (int c = 0; c < num_classes; ++c) {
+      if (!launches[c].used) continue;
+      const void *address = reinterpret_cast<const void *>(kernel_of(c).kernel);
+      auto seen = std::find_if(kernel_lds.begin(), kernel_lds.end(), [&](auto &k) { return k.first == address; });
+      if (seen == kernel_lds.end()) {
+        kernel_lds.emplace_back(address, launches[c].lds);
+      } else {
+        seen->second = std::max(seen->second, launches[c].lds);
+      }
+    }
+    for (auto &k : kernel_lds) ASP_TRY(asp::allow_dynamic_lds(k.first, k.second));
+    const int rc = [&]() -> int {
+      ASP_HIP_TRY(hipEventRecord(begin, s));
+      for (int c = 0; c < num_classes; ++c) {
+        const ClassLaunch &l = launches[c];
+        if (!l.used) continue;
+        const ClassKernel<Args> k = kernel_of(c);
+        hipStream_t cs = streams[c].stream;
+        ASP_HIP_TRY(hipStreamWaitEvent(cs, begin, 0));
+        hipLaunchKernelGGL(k.kernel, dim3(8u * l.slots_per_xcd), dim3(k.threads), l.lds, cs,
+                           Args{problems, d_slots + l.slot_at, l.slots_per_xcd});
+        ASP_HIP_TRY(hipGetLastError());
+        ASP_HIP_TRY(hipEventRecord(l.done, cs));
+        ASP_HIP_TRY(hipStreamWaitEvent(s, l.done, 0));
+      }
+      ASP_HIP_TRY(hipEventRecord(end, s));
+      return ASP_OK;
+    }();
+    if (rc != ASP_OK) {
+      // the main stream may not have joined every class: wait for them here, so that the caller's
+      // buffers, fenced on the main stream alone, do not go back to the pool under a running class
+      for (int c = 0; c < num_classes; ++c) {
+        if (launches[c].used) (void)hipStreamSynchronize(streams[c].stream);
+      }
+    }
+    return rc;
+  }
+};
+
+// The pass after the sweeps of a batch — reported energies (the kernels and so the reduction order of
+// energies_of_perm) and original-order bits of every chain's best configuration: a problem's descriptor,
+// and the three launches over (problem, chain) slots.
+PostProblem post_problem_of(const asp_sa_plan *p, const uint64_t *best, double *partial, double *out_e,
+                            uint64_t *out_x) {
+  const asp::SaHostLayout &L = p->host;
+  PostProblem pp{};
+  pp.e = EnergyArgs{p->block_width.ptr, p->ell_off.ptr, p->ell_col.ptr, p->ell_val.ptr,
+                    p->field_pos.ptr,   best,           partial,        L.num_blocks};
+  pp.pos_of_spin = p->pos_of_spin.ptr;
+  pp.num_spins = L.num_spins;
+  pp.words = static_cast<uint32_t>((L.num_spins + 63) / 64);
+  pp.diag_sum = L.diag_sum;
+  pp.out_e = out_e;
+  pp.out_x = out_x;
+  return pp;
+}
+// energy_lds: the sign words of the largest problem (num_blocks * 8 bytes), staged in LDS when they fit
+int launch_post_batch(const PostProblem *d_post, const BatchSlot *d_chains, unsigned chains, size_t energy_lds,
+                      size_t max_lds, hipStream_t s) {
+  if (energy_lds > max_lds) {
+    hipLaunchKernelGGL(k_sa_energy_blocks_batch<false>, dim3(chains), dim3(512), 0, s, d_post, d_chains);
+  } else {
+    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_sa_energy_blocks_batch<true>), energy_lds));
+    hipLaunchKernelGGL(k_sa_energy_blocks_batch<true>, dim3(chains), dim3(512), energy_lds, s, d_post, d_chains);
+  }
+  hipLaunchKernelGGL(k_sa_energy_fold_batch, dim3(chains), dim3(64), 0, s, d_post, d_chains);
+  hipLaunchKernelGGL(k_unpermute_bits_batch, dim3(chains), dim3(256), 0, s, d_post, d_chains);
+  ASP_HIP_TRY(hipGetLastError());
+  return ASP_OK;
+}
+
 struct BatchEntry {
   uint32_t item;     // index into the caller's array
   uint32_t waves;    // wavefronts per workgroup this problem wants
@@ -2868,6 +2989,34 @@ struct BatchEntry {
 extern "C" {
 
 float asp_sa_batch_last_ms(void) { return g_batch_sweep_ms; }
+
+int asp_sa_batch_slots_host(uint32_t count, double const *work, uint32_t const *groups, uint32_t *slots_per_xcd,
+                            uint32_t *slots, uint64_t capacity) {
+  asp_clear_error();
+  if (!slots_per_xcd || (count && (!work || !groups))) return asp::set_error(ASP_ERR_INVALID, "null argument");
+  const auto too_small = [&] {
+    return asp::set_error(ASP_ERR_INVALID, "the table does not fit %llu slots",
+                          static_cast<unsigned long long>(slots ? capacity : 0));
+  };
+  // (the eight lists hold all groups between them: a table that cannot fit is refused before it is built)
+  uint64_t all_groups = 0;
+  for (uint32_t k = 0; k < count; ++k) all_groups += groups[k];
+  if (all_groups > capacity) return too_small();
+  std::vector<uint32_t> members(count);
+  std::iota(members.begin(), members.end(), 0u);
+  std::vector<BatchSlot> per_xcd[asp::kXcds];
+  const uint32_t longest = asp::deal_to_xcds(
+      members, [&](uint32_t k) { return work[k]; }, [&](uint32_t k) { return groups[k]; }, per_xcd);
+  if (uint64_t{asp::kXcds} * longest > capacity || (longest && !slots)) return too_small();
+  *slots_per_xcd = longest;
+  for (const auto &list : per_xcd) {
+    for (const BatchSlot &slot : list) {
+      *slots++ = slot.problem;
+      *slots++ = slot.group;
+    }
+  }
+  return ASP_OK;
+}
 
 int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
   asp_clear_error();
@@ -3050,7 +3199,7 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
   asp::ScopedStream main_stream;
   ASP_TRY(main_stream.acquire());
   hipStream_t s = main_stream.stream;
-  asp::ScopedStream class_stream[kNumClasses];
+  ClassLauncher launcher;
   DeviceBuffer<double> d_betas, d_partial, d_e, d_cache;
   DeviceBuffer<uint64_t> d_best, d_x;
   DeviceBuffer<long long> d_tracked;
@@ -3075,101 +3224,42 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
   std::vector<SweepArgs> h_problems(entries.size());
   std::vector<PostProblem> h_post(entries.size());
   std::vector<BatchSlot> h_chains;
+  std::vector<ClassMember> members(entries.size());
   h_chains.reserve(n_e);
   size_t energy_lds = 0;
   for (size_t k = 0; k < entries.size(); ++k) {
     const asp_sa_batch_item &it = items[entries[k].item];
     const asp_sa_plan *p = it.plan;
     const asp::SaHostLayout &L = p->host;
-    const bool wide = entries[k].layout == kWide;
     const bool packed = entries[k].layout == kBits;
     std::copy(it.betas, it.betas + it.num_sweeps, h_betas.begin() + entries[k].beta_at);
-    SweepArgs a{};
-    a.color_block_start = p->color_block_start.ptr;
-    a.block_width = p->block_width.ptr;
-    a.ell_off = p->ell_off.ptr;
-    a.ell_col = wide ? p->ell_col4.ptr : p->ell_col.ptr;
-    a.ell_val = p->ell_val.ptr;
-    a.spin_of_pos = p->spin_of_pos.ptr;
-    a.field_pos = p->field_pos.ptr;
+    ColourLaunch form;
+    form.wide = entries[k].layout == kWide;
+    SweepArgs a = plan_sweep_args(p, form);
     a.betas = d_betas.ptr + entries[k].beta_at;
-    a.x0_perm = nullptr;
     a.best_perm = d_best.ptr + off[k].best;
     a.tracked = d_tracked.ptr + off[k].stat;
     a.accepted = d_accepted.ptr + off[k].stat;
     a.seed = it.seed;
-    a.scale = std::ldexp(1.0, L.energy_scale_exp);
-    a.num_colors = L.num_colors;
-    a.num_blocks = L.num_blocks;
     a.num_sweeps = it.num_sweeps;
     a.replica_first = it.replica_offset;
     // (the bit-packed layout runs without the field cache, as in the single-problem launch)
     a.field_cache = use_cache && !packed ? d_cache.ptr + off[k].cache : nullptr;
-    const double degree =
-        std::max(1.0, static_cast<double>(L.a_col.size()) / static_cast<double>(L.num_spins));
-    a.cache_enter_flips =
-        packed ? 0u : static_cast<uint32_t>(std::max(1.0, 0.7 * static_cast<double>(L.num_blocks) / degree));
-    a.spin_words = nullptr;
-    a.trace = nullptr;
+    a.cache_enter_flips = packed ? 0u : cache_enter_flips_of(L);
     h_problems[k] = a;
-    PostProblem pp{};
-    pp.e = EnergyArgs{p->block_width.ptr, p->ell_off.ptr, p->ell_col.ptr, p->ell_val.ptr,
-                      p->field_pos.ptr, d_best.ptr + off[k].best, d_partial.ptr + off[k].partial,
-                      L.num_blocks};
-    pp.pos_of_spin = p->pos_of_spin.ptr;
-    pp.num_spins = L.num_spins;
-    pp.words = static_cast<uint32_t>((L.num_spins + 63) / 64);
-    pp.diag_sum = L.diag_sum;
-    pp.out_e = d_e.ptr + off[k].e;
-    pp.out_x = d_x.ptr + off[k].x;
-    h_post[k] = pp;
+    h_post[k] = post_problem_of(p, d_best.ptr + off[k].best, d_partial.ptr + off[k].partial, d_e.ptr + off[k].e,
+                                d_x.ptr + off[k].x);
     for (uint32_t r = 0; r < it.repetitions; ++r) {
       h_chains.push_back(BatchSlot{static_cast<uint32_t>(k), r});
     }
     energy_lds = std::max(energy_lds, static_cast<size_t>(L.num_blocks) * sizeof(uint64_t));
+    const int c = class_of(entries[k]);
+    members[k] = ClassMember{c, entries[k].work, static_cast<uint32_t>(off[k].groups),
+                             sweep_lds_bytes(L, layout_of_class(c))};
   }
-  // ---- slot tables: per class, problems longest first, dealt round-robin to the 8 XCDs ----
-  struct ClassLaunch {
-    uint64_t slot_at = 0;
-    uint32_t slots_per_xcd = 0;
-    size_t lds = 0;
-    bool used = false;
-  };
-  ClassLaunch launches[kNumClasses];
-  std::vector<BatchSlot> h_slots;
-  for (int c = 0; c < kNumClasses; ++c) {
-    std::vector<size_t> members;
-    for (size_t k = 0; k < entries.size(); ++k) {
-      if (class_of(entries[k]) == c) members.push_back(k);
-    }
-    if (members.empty()) continue;
-    std::stable_sort(members.begin(), members.end(),
-                     [&](size_t a, size_t b) { return entries[a].work > entries[b].work; });
-    std::vector<BatchSlot> per_xcd[8];
-    uint64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (size_t k : members) {
-      // the XCD with the fewest groups so far (ties: lowest index): balanced and deterministic
-      int x = 0;
-      for (int j = 1; j < 8; ++j) {
-        if (load[j] < load[x]) x = j;
-      }
-      for (uint32_t g = 0; g < off[k].groups; ++g) {
-        per_xcd[x].push_back(BatchSlot{static_cast<uint32_t>(k), g});
-      }
-      load[x] += off[k].groups;
-      launches[c].lds = std::max(
-          launches[c].lds, sweep_lds_bytes(items[entries[k].item].plan->host, layout_of_class(c)));
-    }
-    uint32_t most = 0;
-    for (int x = 0; x < 8; ++x) most = std::max<uint32_t>(most, static_cast<uint32_t>(per_xcd[x].size()));
-    launches[c].used = true;
-    launches[c].slot_at = h_slots.size();
-    launches[c].slots_per_xcd = most;
-    for (int x = 0; x < 8; ++x) {
-      per_xcd[x].resize(most, BatchSlot{0xFFFFFFFFu, 0});
-      h_slots.insert(h_slots.end(), per_xcd[x].begin(), per_xcd[x].end());
-    }
-  }
+  // ---- slot tables: per class, problems longest first, dealt to the 8 XCDs ----
+  ASP_TRY(launcher.build(members, kNumClasses));
+  const std::vector<BatchSlot> &h_slots = launcher.h_slots;
   ASP_TRY(d_problems.alloc(h_problems.size()));
   ASP_TRY(d_post.alloc(h_post.size()));
   ASP_TRY(d_slots.alloc(h_slots.size()));
@@ -3180,70 +3270,22 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
   ASP_TRY(d_slots.upload(h_slots.data(), h_slots.size(), s));
   ASP_TRY(d_chains.upload(h_chains.data(), h_chains.size(), s));
   ASP_HIP_TRY(hipMemsetAsync(d_accepted.ptr, 0, n_stat * sizeof(unsigned long long), s));
-  hipEvent_t ev[2 + kNumClasses] = {};
-  struct EventGuard {
-    hipEvent_t *ev;
-    int n;
-    ~EventGuard() {
-      for (int i = 0; i < n; ++i) {
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
-      }
+  // ---- one sweep launch per class ----
+  ASP_TRY(launcher.run<BatchArgs>(s, d_problems.ptr, d_slots.ptr, [&](int c) -> ClassKernel<BatchArgs> {
+    const uint32_t threads = 64u * waves_of_class(c);
+    if (layout_of_class(c) == kWide) return {k_sa_sweep_batch<4, kWide>, threads};
+    if (layout_of_class(c) == kBits) return {k_sa_sweep_batch<1, kBits>, threads};
+    if (layout_of_class(c) == kNibbles) return {k_sa_sweep_batch<4, kNibbles>, threads};
+    switch (m_of_class[c]) {
+      case 1: return {k_sa_sweep_batch<1, kBytes>, threads};
+      case 2: return {k_sa_sweep_batch<2, kBytes>, threads};
+      case 4: return {k_sa_sweep_batch<4, kBytes>, threads};
+      default: return {k_sa_sweep_batch<8, kBytes>, threads};
     }
-  } event_guard{ev, 2 + kNumClasses};
-  for (auto &e : ev) ASP_HIP_TRY(hipEventCreate(&e));
-  ASP_HIP_TRY(hipEventRecord(ev[0], s));
-  // ---- one sweep launch per class, each on its own stream so that they share the chip ----
-  for (int c = 0; c < kNumClasses; ++c) {
-    if (!launches[c].used) continue;
-    ASP_TRY(class_stream[c].acquire());
-    hipStream_t cs = class_stream[c].stream;
-    ASP_HIP_TRY(hipStreamWaitEvent(cs, ev[0], 0));
-    BatchArgs b{d_problems.ptr, d_slots.ptr + launches[c].slot_at, launches[c].slots_per_xcd};
-    using BatchKernel = void (*)(BatchArgs);
-    BatchKernel kernel = nullptr;
-    if (layout_of_class(c) == kWide) {
-      kernel = k_sa_sweep_batch<4, kWide>;
-    } else if (layout_of_class(c) == kBits) {
-      kernel = k_sa_sweep_batch<1, kBits>;
-    } else if (layout_of_class(c) == kNibbles) {
-      kernel = k_sa_sweep_batch<4, kNibbles>;
-    } else {
-      switch (m_of_class[c]) {
-        case 1: kernel = k_sa_sweep_batch<1, kBytes>; break;
-        case 2: kernel = k_sa_sweep_batch<2, kBytes>; break;
-        case 4: kernel = k_sa_sweep_batch<4, kBytes>; break;
-        default: kernel = k_sa_sweep_batch<8, kBytes>; break;
-      }
-    }
-    if (launches[c].lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(launches[c].lds)));
-    }
-    hipLaunchKernelGGL(kernel, dim3(8u * launches[c].slots_per_xcd), dim3(64u * waves_of_class(c)),
-                       launches[c].lds, cs, b);
-    ASP_HIP_TRY(hipGetLastError());
-    ASP_HIP_TRY(hipEventRecord(ev[2 + c], cs));
-    ASP_HIP_TRY(hipStreamWaitEvent(s, ev[2 + c], 0));
-  }
-  ASP_HIP_TRY(hipEventRecord(ev[1], s));
+  }));
   // ---- energies and original-order bits of every chain's best configuration ----
-  const unsigned chains = static_cast<unsigned>(h_chains.size());
-  if (energy_lds > max_lds) {
-    hipLaunchKernelGGL(k_sa_energy_blocks_batch<false>, dim3(chains), dim3(512), 0, s, d_post.ptr,
-                       d_chains.ptr);
-  } else {
-    if (energy_lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(
-          reinterpret_cast<const void *>(k_sa_energy_blocks_batch<true>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(energy_lds)));
-    }
-    hipLaunchKernelGGL(k_sa_energy_blocks_batch<true>, dim3(chains), dim3(512), energy_lds, s,
-                       d_post.ptr, d_chains.ptr);
-  }
-  hipLaunchKernelGGL(k_sa_energy_fold_batch, dim3(chains), dim3(64), 0, s, d_post.ptr, d_chains.ptr);
-  hipLaunchKernelGGL(k_unpermute_bits_batch, dim3(chains), dim3(256), 0, s, d_post.ptr, d_chains.ptr);
-  ASP_HIP_TRY(hipGetLastError());
+  ASP_TRY(launch_post_batch(d_post.ptr, d_chains.ptr, static_cast<unsigned>(h_chains.size()), energy_lds, max_lds,
+                            s));
   std::vector<uint64_t> h_x(n_x);
   std::vector<double> h_e(n_e);
   std::vector<long long> h_tracked(n_stat);
@@ -3254,7 +3296,7 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
   ASP_TRY(d_accepted.download(h_accepted.data(), n_stat, s));
   ASP_HIP_TRY(hipStreamSynchronize(s));
   float ms = 0.0f;
-  ASP_HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  ASP_HIP_TRY(hipEventElapsedTime(&ms, launcher.begin, launcher.end));
   g_batch_sweep_ms += ms;
   for (size_t k = 0; k < entries.size(); ++k) {
     const asp_sa_batch_item &it = items[entries[k].item];
@@ -3395,7 +3437,7 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
   ScopedStream main_stream;
   ASP_TRY(main_stream.acquire());
   hipStream_t s = main_stream.stream;
-  ScopedStream class_stream[kNumClasses];
+  ClassLauncher launcher;
   DeviceBuffer<double> d_betas, d_cache;
   DeviceBuffer<uint64_t> d_best, d_cur;
   DeviceBuffer<long long> d_tracked, d_e_cur;
@@ -3419,6 +3461,7 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
   std::vector<Problem> h_problems(entries.size());
   std::vector<ChainsIo> h_io(entries.size());
   std::vector<BatchSlot> h_chains_in, h_chains_out;
+  std::vector<ClassMember> members(entries.size());
   h_chains_in.reserve(n_stat);
   h_chains_out.reserve(n_chains);
   for (size_t k = 0; k < entries.size(); ++k) {
@@ -3473,46 +3516,13 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
     h_io[k] = io;
     for (uint32_t r = 0; r < off[k].padded; ++r) h_chains_in.push_back(BatchSlot{static_cast<uint32_t>(k), r});
     for (uint32_t r = 0; r < c->repetitions; ++r) h_chains_out.push_back(BatchSlot{static_cast<uint32_t>(k), r});
+    const int cl = class_of(entries[k]);
+    members[k] = ClassMember{cl, entries[k].work, static_cast<uint32_t>(off[k].groups),
+                             sweep_lds_bytes(L, cl % 2 == 0 ? kWide : kBytes)};
   }
-  // ---- slot tables: per class, handles longest first, dealt to the 8 XCDs (asp_sa_anneal_batch) ----
-  struct ClassLaunch {
-    uint64_t slot_at = 0;
-    uint32_t slots_per_xcd = 0;
-    size_t lds = 0;
-    bool used = false;
-  };
-  ClassLaunch launches[kNumClasses];
-  std::vector<BatchSlot> h_slots;
-  for (int cl = 0; cl < kNumClasses; ++cl) {
-    std::vector<size_t> members;
-    for (size_t k = 0; k < entries.size(); ++k) {
-      if (class_of(entries[k]) == cl) members.push_back(k);
-    }
-    if (members.empty()) continue;
-    std::stable_sort(members.begin(), members.end(),
-                     [&](size_t a, size_t b) { return entries[a].work > entries[b].work; });
-    std::vector<BatchSlot> per_xcd[8];
-    uint64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (size_t k : members) {
-      int x = 0;
-      for (int j = 1; j < 8; ++j) {
-        if (load[j] < load[x]) x = j;
-      }
-      for (uint32_t g = 0; g < off[k].groups; ++g) per_xcd[x].push_back(BatchSlot{static_cast<uint32_t>(k), g});
-      load[x] += off[k].groups;
-      launches[cl].lds = std::max(launches[cl].lds, sweep_lds_bytes(segs[entries[k].seg].chains->plan->host,
-                                                                    cl % 2 == 0 ? kWide : kBytes));
-    }
-    uint32_t most = 0;
-    for (int x = 0; x < 8; ++x) most = std::max<uint32_t>(most, static_cast<uint32_t>(per_xcd[x].size()));
-    launches[cl].used = true;
-    launches[cl].slot_at = h_slots.size();
-    launches[cl].slots_per_xcd = most;
-    for (int x = 0; x < 8; ++x) {
-      per_xcd[x].resize(most, BatchSlot{0xFFFFFFFFu, 0});
-      h_slots.insert(h_slots.end(), per_xcd[x].begin(), per_xcd[x].end());
-    }
-  }
+  // ---- slot tables: per class, handles longest first, dealt to the 8 XCDs ----
+  ASP_TRY(launcher.build(members, kNumClasses));
+  const std::vector<BatchSlot> &h_slots = launcher.h_slots;
   ASP_TRY(d_problems.alloc(h_problems.size()));
   ASP_TRY(d_io.alloc(h_io.size()));
   ASP_TRY(d_slots.alloc(h_slots.size()));
@@ -3527,19 +3537,7 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
   hipLaunchKernelGGL(k_chains_permute_problems, dim3(static_cast<unsigned>(h_chains_in.size())), dim3(256), 0, s,
                      d_io.ptr, d_chains_in.ptr);
   ASP_HIP_TRY(hipGetLastError());
-  hipEvent_t ev[2 + kNumClasses] = {};
-  struct EventGuard {
-    hipEvent_t *ev;
-    int n;
-    ~EventGuard() {
-      for (int i = 0; i < n; ++i) {
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
-      }
-    }
-  } event_guard{ev, 2 + kNumClasses};
-  for (auto &e : ev) ASP_HIP_TRY(hipEventCreate(&e));
-  ASP_HIP_TRY(hipEventRecord(ev[0], s));
-  // ---- one sweep launch per class, each on its own stream so that they share the chip ----
+  // ---- one sweep launch per class ----
   using Kernel = void (*)(ProblemBatchArgs);
   Kernel kernel_of_layout[2] = {nullptr, nullptr};  // [class % 2]
   if constexpr (LADDER) {
@@ -3557,39 +3555,16 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
       default: kernel_of_layout[1] = k_sa_sweep_resume_batch<4, kBytes>; break;
     }
   }
-  // (a kernel serves every wavefront class of its layout, on streams that run side by side: its
-  // dynamic LDS limit is set once, to the largest of them, before the first launch)
-  for (int layout = 0; layout < 2; ++layout) {
-    size_t most_lds = 0;
-    for (int cl = layout; cl < kNumClasses; cl += 2) {
-      if (launches[cl].used) most_lds = std::max(most_lds, launches[cl].lds);
-    }
-    if (most_lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel_of_layout[layout]),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(most_lds)));
-    }
-  }
-  for (int cl = 0; cl < kNumClasses; ++cl) {
-    if (!launches[cl].used) continue;
-    ASP_TRY(class_stream[cl].acquire());
-    hipStream_t cs = class_stream[cl].stream;
-    ASP_HIP_TRY(hipStreamWaitEvent(cs, ev[0], 0));
-    ProblemBatchArgs b{d_problems.ptr, d_slots.ptr + launches[cl].slot_at, launches[cl].slots_per_xcd};
-    const Kernel kernel = kernel_of_layout[cl % 2];
-    hipLaunchKernelGGL(kernel, dim3(8u * launches[cl].slots_per_xcd), dim3(64u * kWaves[cl / 2]),
-                       launches[cl].lds, cs, b);
-    ASP_HIP_TRY(hipGetLastError());
-    ASP_HIP_TRY(hipEventRecord(ev[2 + cl], cs));
-    ASP_HIP_TRY(hipStreamWaitEvent(s, ev[2 + cl], 0));
-  }
-  ASP_HIP_TRY(hipEventRecord(ev[1], s));
+  ASP_TRY(launcher.run<ProblemBatchArgs>(s, d_problems.ptr, d_slots.ptr, [&](int cl) {
+    return ClassKernel<ProblemBatchArgs>{kernel_of_layout[cl % 2], 64u * kWaves[cl / 2]};
+  }));
   // ---- the state back into the handles (after the attempt: the colour order has no retry) ----
   hipLaunchKernelGGL(k_chains_unpermute_problems, dim3(static_cast<unsigned>(h_chains_out.size())), dim3(256), 0, s,
                      d_io.ptr, d_chains_out.ptr);
   ASP_HIP_TRY(hipGetLastError());
   ASP_HIP_TRY(hipStreamSynchronize(s));
   float ms = 0.0f;
-  ASP_HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  ASP_HIP_TRY(hipEventElapsedTime(&ms, launcher.begin, launcher.end));
   if (sweep_ms) *sweep_ms += ms;
   for (size_t k = 0; k < entries.size(); ++k) {
     asp_sa_plan *p = segs[entries[k].seg].chains->plan;
@@ -3739,16 +3714,13 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
   }
   if (shared.empty()) return ASP_OK;
 
-  // ---- launch classes: workgroups of one launch have one wavefront count ----
-  static const uint32_t kWaves[] = {1, 2, 3, 4, 6, 8, 12, 16};
-  constexpr int kNumClasses = sizeof kWaves / sizeof kWaves[0];
+  // ---- launch classes: workgroups of one launch have one wavefront count (kBatchWaves) ----
   const size_t n = shared.size();
   struct Offsets {
     uint64_t blocks, cache, x;  // best / x0_perm / partial rows; field cache; packed words
   };
   std::vector<Offsets> off(n);
-  std::vector<int> class_of(n);
-  std::vector<double> work(n);
+  std::vector<ClassMember> members(n);
   uint64_t n_blocks = 0, n_cache = 0, n_x = 0;
   size_t energy_lds = 0;
   bool use_cache = true;
@@ -3761,15 +3733,9 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
     n_x += (L.num_spins + 63) / 64;
     // one wavefront per block of the widest colour class, at most 16: the single path's choice
     const uint32_t waves = std::min<uint32_t>(widest_color(L), 16u);
-    int c = kNumClasses - 1;
-    for (int j = 0; j < kNumClasses; ++j) {
-      if (waves <= kWaves[j]) {
-        c = j;
-        break;
-      }
-    }
-    class_of[k] = c;
-    work[k] = static_cast<double>(L.ell_off.back() + L.num_blocks);
+    // (every member is one workgroup: the dealing to the XCDs comes out round-robin)
+    members[k] = ClassMember{batch_waves_index(waves), static_cast<double>(L.ell_off.back() + L.num_blocks), 1u,
+                             sweep_lds_bytes(L, kBytes)};
     energy_lds = std::max(energy_lds, static_cast<size_t>(L.num_blocks) * sizeof(uint64_t));
     use_cache = use_cache && p->use_field_cache;
   }
@@ -3780,14 +3746,14 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
   std::vector<uint64_t> h_x0_shared(n_x);
   std::vector<DescentProblem> h_problems(n);
   std::vector<PostProblem> h_post(n);
-  std::vector<BatchSlot> h_chains(n), h_slots;
+  std::vector<BatchSlot> h_chains(n);
   std::vector<uint64_t> h_x(n_x);
   std::vector<double> h_e(n);
   std::vector<uint32_t> h_sweeps(n);
   asp::ScopedStream main_stream;
   ASP_TRY(main_stream.acquire());
   hipStream_t s = main_stream.stream;
-  asp::ScopedStream class_stream[kNumClasses];
+  ClassLauncher launcher;
   DeviceBuffer<uint64_t> d_x0, d_x0_perm, d_best, d_x;
   DeviceBuffer<double> d_partial, d_e, d_cache;
   DeviceBuffer<long long> d_tracked;
@@ -3820,79 +3786,26 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
               h_x0_shared.begin() + off[k].x);
     DescentProblem d{};
     SweepArgs &a = d.s;
-    a.color_block_start = p->color_block_start.ptr;
-    a.block_width = p->block_width.ptr;
-    a.ell_off = p->ell_off.ptr;
-    a.ell_col = p->ell_col.ptr;
-    a.ell_val = p->ell_val.ptr;
-    a.spin_of_pos = p->spin_of_pos.ptr;
-    a.field_pos = p->field_pos.ptr;
-    a.betas = nullptr;  // the descent reads none
+    a = plan_sweep_args(p, ColourLaunch{});  // (bytes; betas stay null and the seed 0: the descent reads neither)
     a.x0_perm = d_x0_perm.ptr + off[k].blocks;
     a.best_perm = d_best.ptr + off[k].blocks;
     a.tracked = d_tracked.ptr + k;
     a.accepted = d_accepted.ptr + k;
-    a.seed = 0;
-    a.scale = std::ldexp(1.0, L.energy_scale_exp);
-    a.num_colors = L.num_colors;
-    a.num_blocks = L.num_blocks;
     a.num_sweeps = it.max_sweeps;
-    a.replica_first = 0;
     // the field cache and its inert blocks as in the single path: late sweeps flip little
     a.field_cache = use_cache ? d_cache.ptr + off[k].cache : nullptr;
-    const double degree =
-        std::max(1.0, static_cast<double>(L.a_col.size()) / static_cast<double>(L.num_spins));
-    a.cache_enter_flips =
-        static_cast<uint32_t>(std::max(1.0, 0.7 * static_cast<double>(L.num_blocks) / degree));
-    a.spin_words = nullptr;
-    a.trace = nullptr;
+    a.cache_enter_flips = cache_enter_flips_of(L);
     d.x0 = d_x0.ptr + off[k].x;
     d.x0_perm = d_x0_perm.ptr + off[k].blocks;
     d.sweeps_done = d_sweeps.ptr + k;
     h_problems[k] = d;
-    PostProblem pp{};
-    pp.e = EnergyArgs{p->block_width.ptr, p->ell_off.ptr, p->ell_col.ptr, p->ell_val.ptr,
-                      p->field_pos.ptr, d_best.ptr + off[k].blocks, d_partial.ptr + off[k].blocks,
-                      L.num_blocks};
-    pp.pos_of_spin = p->pos_of_spin.ptr;
-    pp.num_spins = L.num_spins;
-    pp.words = static_cast<uint32_t>(words);
-    pp.diag_sum = L.diag_sum;
-    pp.out_e = d_e.ptr + k;
-    pp.out_x = d_x.ptr + off[k].x;
-    h_post[k] = pp;
+    h_post[k] = post_problem_of(p, d_best.ptr + off[k].blocks, d_partial.ptr + off[k].blocks, d_e.ptr + k,
+                                d_x.ptr + off[k].x);
     h_chains[k] = BatchSlot{static_cast<uint32_t>(k), 0u};
   }
-  // ---- slot tables: per class, problems longest first, dealt round-robin to the 8 XCDs ----
-  struct ClassLaunch {
-    uint64_t slot_at = 0;
-    uint32_t slots_per_xcd = 0;
-    size_t lds = 0;
-    bool used = false;
-  };
-  ClassLaunch launches[kNumClasses];
-  for (int c = 0; c < kNumClasses; ++c) {
-    std::vector<size_t> members;
-    for (size_t k = 0; k < n; ++k) {
-      if (class_of[k] == c) members.push_back(k);
-    }
-    if (members.empty()) continue;
-    std::stable_sort(members.begin(), members.end(), [&](size_t a, size_t b) { return work[a] > work[b]; });
-    std::vector<BatchSlot> per_xcd[8];
-    for (size_t j = 0; j < members.size(); ++j) {
-      per_xcd[j % 8].push_back(BatchSlot{static_cast<uint32_t>(members[j]), 0u});
-      launches[c].lds =
-          std::max(launches[c].lds, sweep_lds_bytes(items[shared[members[j]]].plan->host, kBytes));
-    }
-    const uint32_t most = static_cast<uint32_t>(per_xcd[0].size());  // XCD 0 is dealt to first
-    launches[c].used = true;
-    launches[c].slot_at = h_slots.size();
-    launches[c].slots_per_xcd = most;
-    for (int x = 0; x < 8; ++x) {
-      per_xcd[x].resize(most, BatchSlot{0xFFFFFFFFu, 0});
-      h_slots.insert(h_slots.end(), per_xcd[x].begin(), per_xcd[x].end());
-    }
-  }
+  // ---- slot tables: per class, problems longest first, dealt to the 8 XCDs ----
+  ASP_TRY(launcher.build(members, kNumBatchWaves));
+  const std::vector<BatchSlot> &h_slots = launcher.h_slots;
   ASP_TRY(d_problems.alloc(n));
   ASP_TRY(d_post.alloc(n));
   ASP_TRY(d_slots.alloc(h_slots.size()));
@@ -3917,65 +3830,22 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
   ASP_TRY(d_post.upload(h_post.data(), n, s));
   ASP_TRY(d_slots.upload(h_slots.data(), h_slots.size(), s));
   ASP_TRY(d_chains.upload(h_chains.data(), n, s));
-  hipEvent_t ev[2 + kNumClasses] = {};
-  struct EventGuard {
-    hipEvent_t *ev;
-    int n;
-    ~EventGuard() {
-      for (int i = 0; i < n; ++i) {
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
-      }
-    }
-  } event_guard{ev, 2 + kNumClasses};
-  for (auto &e : ev) ASP_HIP_TRY(hipEventCreate(&e));
   // every problem's tree signs into block order: one launch
   hipLaunchKernelGGL(k_permute_bits_problems, dim3(static_cast<unsigned>(n)), dim3(256), 0, s,
                      d_problems.ptr);
   ASP_HIP_TRY(hipGetLastError());
-  ASP_HIP_TRY(hipEventRecord(ev[0], s));
-  // ---- one descent launch per class, each on its own stream so that they share the chip ----
-  for (int c = 0; c < kNumClasses; ++c) {
-    if (!launches[c].used) continue;
-    ASP_TRY(class_stream[c].acquire());
-    hipStream_t cs = class_stream[c].stream;
-    ASP_HIP_TRY(hipStreamWaitEvent(cs, ev[0], 0));
-    DescentBatchArgs b{d_problems.ptr, d_slots.ptr + launches[c].slot_at, launches[c].slots_per_xcd};
-    if (launches[c].lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sa_descent_batch<kBytes>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(launches[c].lds)));
-    }
-    hipLaunchKernelGGL(k_sa_descent_batch<kBytes>, dim3(8u * launches[c].slots_per_xcd),
-                       dim3(64u * kWaves[c]), launches[c].lds, cs, b);
-    ASP_HIP_TRY(hipGetLastError());
-    ASP_HIP_TRY(hipEventRecord(ev[2 + c], cs));
-    ASP_HIP_TRY(hipStreamWaitEvent(s, ev[2 + c], 0));
-  }
-  ASP_HIP_TRY(hipEventRecord(ev[1], s));
-  // ---- energies (the kernels and so the reduction order of energies_of_perm) and
-  // original-order bits of every problem's final configuration ----
-  const unsigned chains = static_cast<unsigned>(n);
-  if (energy_lds > max_lds) {
-    hipLaunchKernelGGL(k_sa_energy_blocks_batch<false>, dim3(chains), dim3(512), 0, s, d_post.ptr,
-                       d_chains.ptr);
-  } else {
-    if (energy_lds > 64 * 1024) {
-      ASP_HIP_TRY(hipFuncSetAttribute(
-          reinterpret_cast<const void *>(k_sa_energy_blocks_batch<true>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(energy_lds)));
-    }
-    hipLaunchKernelGGL(k_sa_energy_blocks_batch<true>, dim3(chains), dim3(512), energy_lds, s,
-                       d_post.ptr, d_chains.ptr);
-  }
-  hipLaunchKernelGGL(k_sa_energy_fold_batch, dim3(chains), dim3(64), 0, s, d_post.ptr, d_chains.ptr);
-  hipLaunchKernelGGL(k_unpermute_bits_batch, dim3(chains), dim3(256), 0, s, d_post.ptr, d_chains.ptr);
-  ASP_HIP_TRY(hipGetLastError());
+  // ---- one descent launch per class ----
+  ASP_TRY(launcher.run<DescentBatchArgs>(s, d_problems.ptr, d_slots.ptr, [&](int c) {
+    return ClassKernel<DescentBatchArgs>{k_sa_descent_batch<kBytes>, 64u * kBatchWaves[c]};
+  }));
+  // ---- energies and original-order bits of every problem's final configuration ----
+  ASP_TRY(launch_post_batch(d_post.ptr, d_chains.ptr, static_cast<unsigned>(n), energy_lds, max_lds, s));
   ASP_TRY(d_x.download(h_x.data(), n_x, s));
   ASP_TRY(d_e.download(h_e.data(), n, s));
   ASP_TRY(d_sweeps.download(h_sweeps.data(), n, s));
   ASP_HIP_TRY(hipStreamSynchronize(s));
   float ms = 0.0f;
-  ASP_HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  ASP_HIP_TRY(hipEventElapsedTime(&ms, launcher.begin, launcher.end));
   g_greedy_descent_ms += ms;
   for (size_t k = 0; k < n; ++k) {
     const asp_sa_greedy_item &it = items[shared[k]];
@@ -3988,7 +3858,7 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
     p->last_accepted.clear();
     p->last_m = 1;
     p->last_layout = kBytes;
-    p->last_threads = static_cast<int>(64u * kWaves[class_of[k]]);
+    p->last_threads = static_cast<int>(64u * kBatchWaves[members[k].cls]);
     p->last_groups = 1;
     p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_greedy_batch_last_ms
   }

@@ -355,6 +355,17 @@ int asp_sa_layout_host(uint64_t num_spins, int64_t const *indptr, int32_t const 
                        double const *data, double const *field, asp_sa_info *info,
                        int32_t *colors, uint32_t *position);
 
+/* Host-only (inspection, CPU tests): where the shared launches of the batched calls (asp_sa_anneal_batch,
+ * asp_sa_chains_advance_batch, asp_sa_greedy_batch) place the workgroups of ONE launch class.  Member k
+ * < count has groups[k] workgroups of about work[k] each.  The members go in descending work, stable,
+ * each whole to the XCD (of eight) with the fewest workgroups so far, ties to the lowest index; the eight
+ * lists are padded to the longest, *slots_per_xcd, with (0xFFFFFFFF, 0).  slots: the table as uploaded,
+ * [8][*slots_per_xcd] pairs (member, group) of uint32 — workgroup b of the launch reads pair
+ * (b % 8) * *slots_per_xcd + b / 8 —; capacity: the pairs it holds.  ASP_ERR_INVALID with nothing written
+ * when the table needs more.  Placement changes speed only, never a result. */
+int asp_sa_batch_slots_host(uint32_t count, double const *work, uint32_t const *groups,
+                            uint32_t *slots_per_xcd, uint32_t *slots, uint64_t capacity);
+
 /* Host-only: the visiting order of sweep `sweep` of the SHUFFLED variant (asp_sa_anneal_shuffled):
  * order[k] = k-th spin visited (level-major), level_of_position[k] = its level, *num_levels the
  * number of levels.  Any output may be NULL. */
