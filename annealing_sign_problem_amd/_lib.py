@@ -204,6 +204,8 @@ SIGNATURES = {
                                        c_void_p, ctypes.POINTER(c_u64)]),
     "asp_operator_extend": (c_int, [c_void_p, c_u64, c_void_p, c_u64, c_void_p,
                                     ctypes.POINTER(c_u64)]),
+    "asp_operator_field": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_u64, c_void_p, c_void_p,
+                                   ctypes.c_double, c_void_p, ctypes.POINTER(c_u64)]),
     "asp_operator_last_ms": (c_float, []),
     "asp_sparsify_component": (c_int, [c_u64, c_void_p, c_void_p, c_void_p, c_void_p,
                                        ctypes.c_double, c_u64, c_void_p, ctypes.POINTER(c_u64),

@@ -29,6 +29,7 @@ SOURCES = [
     "build_matrix.hip",
     "ising_elements.hip",
     "operator_apply.hip",
+    "operator_field.hip",
     "sector_basis.hip",
     "key_table.hip",
     "plain_basis.hip",

@@ -168,7 +168,12 @@ def make_ising_model(
 
     ``J = (M + M^T) / 2`` with ``M_ij = H_ij |psi_i| |psi_j|`` over the states of
     the cluster (psi L2-normalised over the cluster), zero field, and the signs of
-    psi as the initial configuration.  One deliberate difference: for NON-unique
+    psi as the initial configuration.  ``external_field=True`` (`assert False` in the reference;
+    this package's device operators only): the field is the boundary field of the cluster in its
+    one-hop extension, ``h_r = 2 * sum_e H_er |psi_r| psi_e / c`` over the connections e that leave
+    the cluster, amplitudes from ``log_psi_fn`` and c the cluster's norm, so that
+    energy differences of the model are those of the full vector with the environment's signs
+    kept.  One deliberate difference: for NON-unique
     input the reference indexes the already-deduplicated array with first-occurrence
     positions of the original (common.py:149), which is an indexing slip; here the
     sorted unique states are kept and ``log_psi`` is taken at first occurrences.
@@ -177,9 +182,12 @@ def make_ising_model(
         raise ValueError("at least one of log_psi or log_psi_fn should be specified")
     if external_field and log_psi_fn is None:
         raise ValueError("log_psi_fn should be specified when external_field=True")
-    if external_field:
-        # the reference's branch is `assert False` (common.py:199-202)
-        raise NotImplementedError("external_field=True is not implemented by the reference")
+    if external_field and not _on_device(quantum_hamiltonian):
+        # the reference's branch is `assert False` (common.py:199-202); the field is built by the
+        # device operator alone (DeviceOperator.field)
+        raise NotImplementedError(
+            "external_field=True needs one of this package's device operators (operators.Operator with "
+            "real matrices); it is not implemented for foreign operator objects, nor by the reference")
 
     spins = np.asarray(spins, dtype=np.uint64)
     if not (spins.ndim == 1 and (spins.shape[0] < 2 or bool(np.all(spins[1:] > spins[:-1])))):
@@ -204,8 +212,11 @@ def make_ising_model(
     if not np.allclose(psi.imag, 0, atol=1e-6):
         raise ValueError("expected all wavefunction coefficients to be real")
     psi = np.ascontiguousarray(psi.real)
-    psi /= norm2(psi)
+    cluster_norm = norm2(psi)
+    psi /= cluster_norm
 
+    field = np.zeros(n) if not external_field else _boundary_field(
+        quantum_hamiltonian, spins, psi, log_psi_fn, cluster_norm)
     matrix = None
     ising_hamiltonian = None
     if _on_device(quantum_hamiltonian):
@@ -216,7 +227,7 @@ def make_ising_model(
         try:
             # row-major, columns ascending, no duplicates (csrc/operator_apply.hip): canonical CSR
             indptr, col, val = quantum_hamiltonian.device().ising_csr(spins, psi)
-            ising_hamiltonian = sa.Hamiltonian.from_canonical_csr(indptr, col, val, np.zeros(n))
+            ising_hamiltonian = sa.Hamiltonian.from_canonical_csr(indptr, col, val, field)
         except _lib.AspError as error:
             if error.code != -3:
                 raise
@@ -228,9 +239,29 @@ def make_ising_model(
         matrix = 0.5 * (matrix + matrix.T)
         matrix.sort_indices()
         matrix = matrix.tocoo()
-        ising_hamiltonian = sa.Hamiltonian(matrix, np.zeros(n, dtype=np.float64))
+        ising_hamiltonian = sa.Hamiltonian(matrix, field)
     x0 = sa.signs_to_bits(np.sign(psi))
     return IsingModel(spins, quantum_hamiltonian, ising_hamiltonian, x0, basis_index)
+
+
+def _boundary_field(hamiltonian, spins, psi, log_psi_fn, cluster_norm: float) -> np.ndarray:
+    """The field of ``make_ising_model(..., external_field=True)``: the environment is the one-hop
+    extension of the cluster, its signed amplitudes come from ``log_psi_fn`` in the cluster's
+    normalisation, and ``scale = 2`` (ASP-FIELD-1)."""
+    env_keys = extension_spins(hamiltonian, spins)
+    if hasattr(log_psi_fn, "index_of"):  # (ground_state_to_log_coeff_fn's closure)
+        env_log_psi = log_psi_fn.at_index(log_psi_fn.index_of(env_keys))
+    else:
+        env_log_psi = log_psi_fn(env_keys)
+    env_psi = np.exp(env_log_psi, dtype=np.complex128)
+    if not np.allclose(env_psi.imag, 0, atol=1e-6):
+        raise ValueError("expected all wavefunction coefficients to be real")
+    env_psi = np.ascontiguousarray(env_psi.real)
+    env_psi /= cluster_norm
+    field, unresolved = hamiltonian.device().field(spins, psi, env_keys, env_psi, scale=2.0)
+    if unresolved > 0:
+        raise ValueError("{} connections leave the cluster for states outside its environment".format(unresolved))
+    return field
 
 
 def compute_accuracy_and_overlap(
@@ -360,10 +391,13 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
     return [_project_on_frozen(m, x, f) for m, (x, _), f in zip(models, best, frozen)]
 
 
-def make_hamiltonian_extension(model: IsingModel, log_psi_fn) -> IsingModel:
-    """One-hop extension of a cluster: every state connected to it (common.py:516-522)."""
+def make_hamiltonian_extension(model: IsingModel, log_psi_fn, external_field: bool = False) -> IsingModel:
+    """One-hop extension of a cluster: every state connected to it (common.py:516-522).
+    ``external_field`` (not in the reference): passed on to :func:`make_ising_model`."""
     spins = extension_spins(model.quantum_hamiltonian, model.spins)
-    return make_ising_model(spins, model.quantum_hamiltonian, log_psi_fn=log_psi_fn)
+    if not external_field:
+        return make_ising_model(spins, model.quantum_hamiltonian, log_psi_fn=log_psi_fn)
+    return make_ising_model(spins, model.quantum_hamiltonian, log_psi_fn=log_psi_fn, external_field=True)
 
 
 def extension_spins(hamiltonian, spins) -> np.ndarray:

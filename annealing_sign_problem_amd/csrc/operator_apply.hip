@@ -30,21 +30,15 @@
 
 namespace {
 
+using asp::ApplyBatch;
 using asp::Bond;
 using asp::DeviceBuffer;
+using asp::find_key;
+using asp::mix64;
 using asp::SymmetryArgs;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
 
 __global__ __launch_bounds__(kThreads) void k_key_insert(const uint64_t *__restrict__ keys,
                                                         uint64_t n,
@@ -56,21 +50,6 @@ __global__ __launch_bounds__(kThreads) void k_key_insert(const uint64_t *__restr
   const unsigned long long entry = (h & 0xFFFFFFFF00000000ull) | (i + 1);
   uint64_t at = h & mask;
   while (atomicCAS(&slots[at], 0ull, entry) != 0ull) at = (at + 1) & mask;
-}
-
-// Index of `needle` in keys, or -1.
-__device__ __forceinline__ int64_t find_key(const unsigned long long *__restrict__ slots,
-                                            uint64_t mask, const uint64_t *__restrict__ keys,
-                                            uint64_t needle) {
-  const uint64_t h = mix64(needle);
-  const uint32_t fingerprint = static_cast<uint32_t>(h >> 32);
-  for (uint64_t at = h & mask;; at = (at + 1) & mask) {
-    const unsigned long long slot = slots[at];
-    if (slot == 0) return -1;
-    if (static_cast<uint32_t>(slot >> 32) != fingerprint) continue;
-    const uint32_t idx = static_cast<uint32_t>(slot) - 1u;
-    if (keys[idx] == needle) return idx;
-  }
 }
 
 __device__ __forceinline__ uint32_t wave_exclusive_scan_u32(uint32_t v, uint32_t lane,
@@ -690,13 +669,6 @@ unsigned grid_for(uint64_t items, uint64_t per_block) {
 
 namespace {
 
-// other_counts / offsets / total of a batch; on return the inputs are resident.
-struct ApplyBatch {
-  DeviceBuffer<uint64_t> d_keys;
-  DeviceBuffer<int64_t> d_counts, d_offsets, d_scratch;
-  uint64_t total = 0;
-};
-
 int count_connections(const asp_operator *op, uint64_t n, const uint64_t *keys, ApplyBatch *w,
                       hipStream_t stream) {
   ASP_TRY(w->d_keys.alloc(n));
@@ -901,6 +873,41 @@ int check_operator(const asp_operator *op) {
 }
 
 }  // namespace
+
+// ---- for operator_field.hip (operator_internal.hpp) ----
+namespace asp {
+
+int connection_list(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
+                    hipStream_t stream) {
+  Symmetrised sym;
+  StreamFence fence(stream);
+  ASP_TRY(count_connections(op, n, keys, &out->batch, stream));
+  ASP_TRY(out->d_other.alloc(out->batch.total));
+  ASP_TRY(out->d_coeffs.alloc(out->batch.total));
+  if (n == 0) return ASP_OK;
+  hipLaunchKernelGGL(k_apply<true>, dim3(grid_for(n, kWaves)), dim3(kThreads), 0, stream,
+                     op->d_bonds.ptr, op->num_bonds, out->batch.d_keys.ptr, n, out->batch.d_offsets.ptr,
+                     nullptr, out->d_other.ptr, out->d_coeffs.ptr);
+  ASP_HIP_TRY(hipGetLastError());
+  ASP_TRY(symmetrise_batch(op, n, out->batch, out->d_other.ptr, out->d_coeffs.ptr, &sym, false, stream));
+  ASP_TRY(sym.fetch(stream));
+  ASP_HIP_TRY(hipStreamSynchronize(stream));
+  return sym.check();
+}
+
+int key_hash_build(const uint64_t *d_keys, uint64_t n, unsigned long long *d_slots, uint64_t slots_n,
+                   hipStream_t stream) {
+  ASP_HIP_TRY(hipMemsetAsync(d_slots, 0, slots_n * sizeof(unsigned long long), stream));
+  if (n == 0) return ASP_OK;
+  hipLaunchKernelGGL(k_key_insert, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, stream, d_keys, n,
+                     d_slots, slots_n - 1);
+  ASP_HIP_TRY(hipGetLastError());
+  return ASP_OK;
+}
+
+void set_operator_last_ms(float ms) { g_last_ms = ms; }
+
+}  // namespace asp
 
 extern "C" {
 

@@ -1,4 +1,4 @@
-// Internals of asp_operator shared by operator_apply.hip and sector_basis.hip.
+// Internals of asp_operator shared by operator_apply.hip, operator_field.hip and sector_basis.hip.
 #pragma once
 
 #include <cstdint>
@@ -21,6 +21,67 @@ struct SymmetryArgs {
   int32_t inversion;  // 0, +1, -1
   uint64_t mask;      // low number_spins bits
 };
+
+// ---- the cluster's key hash (device side) -----------------------------------
+// slots u64[2^s]: open addressing, {fingerprint:32 | index+1:32}, 0 = empty; filled by
+// asp::key_hash_build (k_key_insert, operator_apply.hip).
+#ifdef __HIPCC__
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
+// Index of `needle` in keys, or -1.
+__device__ __forceinline__ int64_t find_key(const unsigned long long *__restrict__ slots,
+                                            uint64_t mask, const uint64_t *__restrict__ keys,
+                                            uint64_t needle) {
+  const uint64_t h = mix64(needle);
+  const uint32_t fingerprint = static_cast<uint32_t>(h >> 32);
+  for (uint64_t at = h & mask;; at = (at + 1) & mask) {
+    const unsigned long long slot = slots[at];
+    if (slot == 0) return -1;
+    if (static_cast<uint32_t>(slot >> 32) != fingerprint) continue;
+    const uint32_t idx = static_cast<uint32_t>(slot) - 1u;
+    if (keys[idx] == needle) return idx;
+  }
+}
+#endif
+
+// other_counts / offsets / total of a batch; on return the inputs are resident.
+struct ApplyBatch {
+  DeviceBuffer<uint64_t> d_keys;
+  DeviceBuffer<int64_t> d_counts, d_offsets, d_scratch;
+  uint64_t total = 0;
+};
+
+// The connections of a batch as asp_operator_apply returns them, left on the device: row r's
+// entries at [batch.d_offsets[r], batch.d_offsets[r + 1]), the diagonal entry first; for a
+// symmetry-adapted basis the representatives and rescaled coefficients, duplicates kept.
+struct ConnectionList {
+  ApplyBatch batch;
+  DeviceBuffer<uint64_t> d_other;
+  DeviceBuffer<double> d_coeffs;
+};
+
+}  // namespace asp
+
+struct asp_operator;
+
+namespace asp {
+
+// Fills `out` on `stream` and waits for it; ASP_ERR_INVALID when a key lies outside the symmetry
+// sector (norm 0).  Declare a StreamFence after `out`.
+int connection_list(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
+                    hipStream_t stream);
+// Clears slots[slots_n] (a power of two >= 2n) and inserts the n device keys.
+int key_hash_build(const uint64_t *d_keys, uint64_t n, unsigned long long *d_slots, uint64_t slots_n,
+                   hipStream_t stream);
+// What asp_operator_last_ms reports for the calling thread.
+void set_operator_last_ms(float ms);
 
 }  // namespace asp
 

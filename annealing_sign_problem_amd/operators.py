@@ -491,6 +491,38 @@ class DeviceOperator:
         z = int(nnz.value)
         return indptr, col[:z], val[:z]  # (views: see ising)
 
+    def field(self, keys, psi, env_keys, env_psi, scale: float = 2.0) -> Tuple[np.ndarray, int]:
+        """Boundary field of the cluster ``keys`` (ascending, unique; amplitudes ``psi``) in the
+        environment ``env_keys`` (ascending, unique; signed amplitudes ``env_psi`` in the same
+        normalisation), specification ASP-FIELD-1: ``(field f64[K], unresolved)``
+        with ``field[r] = scale * sum((coeff * |psi_r|) * env_psi[p])`` over the connections of
+        row r that leave the cluster, added in connection order, and the number of connections
+        with a non-zero coefficient that end neither in the cluster nor in the environment.
+        ``env_keys=None``: an empty environment."""
+        import ctypes
+
+        _lib = self._lib_module
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        psi = np.ascontiguousarray(psi, dtype=np.float64)
+        if psi.shape != keys.shape:
+            raise ValueError("psi and keys differ in length")
+        if env_keys is None:
+            env_keys = env_psi = None
+            e = 0
+        else:
+            env_keys = np.ascontiguousarray(env_keys, dtype=np.uint64)
+            env_psi = np.ascontiguousarray(env_psi, dtype=np.float64)
+            if env_psi.shape != env_keys.shape:
+                raise ValueError("env_psi and env_keys differ in length")
+            e = env_keys.shape[0]
+        k = keys.shape[0]
+        out = np.zeros(max(k, 1), dtype=np.float64)
+        unresolved = ctypes.c_uint64(0)
+        _lib.check(self._lib.asp_operator_field(self._handle, k, _lib.ptr(keys), _lib.ptr(psi), e,
+                                                _lib.ptr(env_keys), _lib.ptr(env_psi), float(scale),
+                                                _lib.ptr(out), ctypes.byref(unresolved)))
+        return out[:k], int(unresolved.value)
+
     def extend(self, keys) -> np.ndarray:
         """Sorted unique union of the targets of ``keys`` (their own states included; in a
         symmetry sector their representatives, without the orbits of norm 0)."""

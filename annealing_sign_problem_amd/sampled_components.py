@@ -195,17 +195,20 @@ def exact_signs_and_weights(cluster, model, ground_state, basis):
 
 def process_cluster(cluster, hamiltonian, ground_state, noisy_ground_state, noisy_log_coeff_fn,
                     order: int, global_cutoff: float, annealing: bool,
-                    sweep_order: Optional[str] = None) -> List[OptimizationResult]:
-    """driver :726-751."""
+                    sweep_order: Optional[str] = None,
+                    external_field: bool = False) -> List[OptimizationResult]:
+    """driver :726-751.  ``external_field`` (not in the driver; default off): every model carries the
+    boundary field of its environment (``make_ising_model(..., external_field=True)``)."""
+    field = {"external_field": True} if external_field else {}  # (without it every call is the one it was)
     basis = hamiltonian.basis
     results = []
     h = None
     for i in range(order + 1):
         if i == 0:
-            h = common.make_ising_model(cluster, hamiltonian, log_psi_fn=noisy_log_coeff_fn)
+            h = common.make_ising_model(cluster, hamiltonian, log_psi_fn=noisy_log_coeff_fn, **field)
             exact_signs, weights = exact_signs_and_weights(cluster, h, ground_state, basis)
         else:
-            h = common.make_hamiltonian_extension(h, noisy_log_coeff_fn)
+            h = common.make_hamiltonian_extension(h, noisy_log_coeff_fn, **field)
             h = common.sparsify_using_global_cutoff(h, global_cutoff, cluster)
         r = solve_and_test_model(h, cluster, exact_signs, weights, annealing, sweep_order)
         r.amplitude_overlap = amplitude_overlap(h.spins, ground_state, noisy_ground_state, basis,
@@ -216,15 +219,17 @@ def process_cluster(cluster, hamiltonian, ground_state, noisy_ground_state, nois
 
 def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, noisy_ground_state,
                    noisy_log_coeff_fn, order: int, global_cutoff: float, jobs: int = 1,
-                   greedy_batch: bool = False):
+                   greedy_batch: bool = False, external_field: bool = False):
     """First half of :func:`process_clusters_batched`: the models of every order of every cluster,
     each with its greedy result — a list of ``(cluster index, model, exact_signs, weights, result
     so far)`` in cluster order.  The models of a cluster do not depend on its solutions (the
     extension of order i grows from the model of order i-1, common.py:516), so they can all be
     built before anything is annealed.  ``greedy_batch``: the models are built first (on the
     ``jobs`` threads) and ALL of them are then solved by one ``greedy_solve_batch`` call instead
-    of one ``greedy_solve`` each; the results are the same."""
+    of one ``greedy_solve`` each; the results are the same.  ``external_field``: as in
+    :func:`process_cluster`."""
     basis = hamiltonian.basis
+    field = {"external_field": True} if external_field else {}
 
     def stage(item):
         """Models of every order of one cluster, each with its greedy result."""
@@ -233,10 +238,10 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
         out = []
         for i in range(order + 1):
             if i == 0:
-                h = common.make_ising_model(cluster, hamiltonian, log_psi_fn=noisy_log_coeff_fn)
+                h = common.make_ising_model(cluster, hamiltonian, log_psi_fn=noisy_log_coeff_fn, **field)
                 exact_signs, weights = exact_signs_and_weights(cluster, h, ground_state, basis)
             else:
-                h = common.make_hamiltonian_extension(h, noisy_log_coeff_fn)
+                h = common.make_hamiltonian_extension(h, noisy_log_coeff_fn, **field)
                 h = common.sparsify_using_global_cutoff(h, global_cutoff, cluster)
             if greedy_batch:  # (the greedy columns are filled in below)
                 r = OptimizationResult(h.size, float("nan"), float("nan"), float("nan"), float("nan"),
@@ -266,6 +271,12 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
         with ThreadPoolExecutor(max_workers=jobs) as pool:
             return solved([entry for part in pool.map(stage, enumerate(clusters)) for entry in part])
     return solved([entry for item in enumerate(clusters) for entry in stage(item)])
+
+
+def external_field_of(args) -> dict:
+    """--external-field as the ``external_field`` keyword of the model-building functions; empty without
+    it, so that every call is the one it was."""
+    return {"external_field": True} if getattr(args, "external_field", False) else {}
 
 
 def early_stop_of(args) -> dict:
@@ -313,14 +324,16 @@ def process_clusters_batched(clusters: Sequence[np.ndarray], hamiltonian, ground
                              global_cutoff: float, annealing: bool, jobs: int = 1,
                              sweep_order: Optional[str] = None,
                              greedy_batch: bool = False,
-                             early_stop: Optional[dict] = None) -> List[List[OptimizationResult]]:
+                             early_stop: Optional[dict] = None,
+                             external_field: bool = False) -> List[List[OptimizationResult]]:
     """``[process_cluster(c, ...) for c in clusters]`` with the annealing of ALL models — every
     cluster at every order — in one batched device call (:func:`stage_clusters`, then
     :func:`anneal_staged`); the results are identical to the per-cluster loop.  ``early_stop``: the
     extra keywords of :func:`common.solve_ising_models` (early stopping or the annealing method), as in
-    :func:`anneal_staged`."""
+    :func:`anneal_staged`.  ``external_field``: as in :func:`process_cluster`."""
     staged = stage_clusters(clusters, hamiltonian, ground_state, noisy_ground_state, noisy_log_coeff_fn,
-                            order, global_cutoff, jobs, **({"greedy_batch": True} if greedy_batch else {}))
+                            order, global_cutoff, jobs, **({"greedy_batch": True} if greedy_batch else {}),
+                            **({"external_field": True} if external_field else {}))
     return anneal_staged(staged, clusters, annealing, sweep_order, **({"early_stop": early_stop} if early_stop else {}))
 
 
@@ -381,6 +394,11 @@ def parse_command_line(argv=None):
     parser.add_argument("--greedy-tree", choices=("host", "device"), default=None,
                         help="where the greedy solver builds its strongest-coupling tree (default: "
                              "$ASP_GREEDY_TREE or host); the output is the same")
+    parser.add_argument("--external-field", default=False, action="store_true",
+                        help="give every model the boundary field of its environment "
+                             "(make_ising_model(..., external_field=True)): the amplitudes of the states "
+                             "one hop outside the model act on it with their signs.  --global-cutoff still "
+                             "only selects spins: a spin it drops is not moved into the environment")
     parser.add_argument("--jobs", type=int, default=1,
                         help="host threads building / solving clusters concurrently (independent "
                              "plans and HIP streams on one GPU; the output does not depend on it)")
@@ -571,13 +589,13 @@ def _worker_chunk(indices):
                                          w["log_coeff_fn"], args.order, args.global_cutoff, args.annealing,
                                          jobs=args.jobs, sweep_order=args.sweep_order,
                                          **({"greedy_batch": True} if args.greedy_batch else {}),
-                                         **early_stop_of(args))
+                                         **early_stop_of(args), **external_field_of(args))
         return report([",".join(r.to_csv_str() for r in columns) for columns in chunk])
 
     def work(cluster):
         return process_cluster(cluster, w["hamiltonian"], w["ground_state"], w["noisy_ground_state"],
                                w["log_coeff_fn"], args.order, args.global_cutoff, args.annealing,
-                               args.sweep_order)
+                               args.sweep_order, **external_field_of(args))
 
     if args.jobs > 1 and len(some) > 1:
         from concurrent.futures import ThreadPoolExecutor
@@ -594,6 +612,8 @@ def _write_header(args):
                     "min_cluster_size", "max_cluster_size", "keep_probability",
                     "number_sweeps", "repetitions"]:
             f.write("# {} = {}\n".format(key, getattr(args, key)))
+        if getattr(args, "external_field", False):
+            f.write("# external_field = True\n")
         f.write("# {}\n".format(OptimizationResult.csv_header()))
 
 
@@ -759,7 +779,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
     def work(cluster):
         return process_cluster(cluster, hamiltonian, ground_state, noisy_ground_state,
                                noisy_log_coeff_fn, args.order, args.global_cutoff, args.annealing,
-                               args.sweep_order)
+                               args.sweep_order, **external_field_of(args))
 
     # (the keyword is passed only with --greedy-batch: without it every call is the one it was)
     greedy_batch = {"greedy_batch": True} if args.greedy_batch else {}
@@ -779,7 +799,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                                              ground_state, noisy_ground_state, noisy_log_coeff_fn,
                                              args.order, args.global_cutoff, args.annealing,
                                              jobs=args.jobs, sweep_order=args.sweep_order, **greedy_batch,
-                                             **early_stop_of(args))
+                                             **early_stop_of(args), **external_field_of(args))
             lines += [",".join(r.to_csv_str() for r in columns) for columns in chunk]
         return lines
 
@@ -810,7 +830,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
             def stage(some):
                 return stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
                                       noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
-                                      **greedy_batch)
+                                      **greedy_batch, **external_field_of(args))
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(stage, my_share(0)) if rounds else None
@@ -864,7 +884,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                 some = list(itertools.islice(clusters, step))
                 return some, stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
                                             noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
-                                            **greedy_batch)
+                                            **greedy_batch, **external_field_of(args))
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(next_round)

@@ -291,8 +291,30 @@ int asp_operator_ising_csr(asp_operator const *op, uint64_t num_spins, uint64_t 
 int asp_operator_extend(asp_operator const *op, uint64_t n, uint64_t const *keys,
                         uint64_t capacity, uint64_t *out, uint64_t *count);
 
+/* Boundary field of a cluster, specification ASP-FIELD-1: the miss branch of the
+ * reference's coupling build (cbits/build_matrix.c:49) with counts = 1.  keys[num_spins] ascending
+ * and unique with signed amplitudes psi (only |psi_r| is used); env_keys[num_env] ascending and
+ * unique with signed amplitudes env_psi in the same normalisation.  For every row r, over the
+ * entries asp_operator_apply returns for keys[r], in its order (equal targets not merged):
+ *     acc = +0.0
+ *     target in keys:                  nothing  (the diagonal entry included, whatever the
+ *                                               environment says about that state)
+ *     target = env_keys[p]:            acc = acc + ((coeff * |psi_r|) * env_psi[p])
+ *     neither, and coeff != 0:         ++*unresolved  (contributes nothing)
+ *     field[r] = scale * acc
+ * every operation rounded on its own, the adds in that order: scale = 1 is the reference's field
+ * bit for bit, scale = 2 (make_ising_model) makes c^2 (s'Js + h's) differ from the quantum energy
+ * of the full vector with the cluster's signs replaced by s by a constant (c: the cluster's norm).
+ * Host pointers; unresolved may be NULL.  ASP_ERR_INVALID before any device work for a null
+ * handle, null keys / psi / field with num_spins > 0, null env_keys / env_psi with num_env > 0 and
+ * keys that are not ascending; for a key of norm 0 in a -1 sector as asp_operator_ising.
+ * num_spins = 0 runs nothing and needs no device; num_env = 0 is legal (field = scale * +0.0). */
+int asp_operator_field(asp_operator const *op, uint64_t num_spins, uint64_t const *keys, double const *psi,
+                       uint64_t num_env, uint64_t const *env_keys, double const *env_psi, double scale,
+                       double *field, uint64_t *unresolved /* may be NULL */);
+
 /* Device time (ms, HIP events, no host<->HBM copies) of this thread's last
- * asp_operator_apply / _ising / _extend call. */
+ * asp_operator_apply / _ising / _extend / _field call. */
 float asp_operator_last_ms(void);
 
 /* ------------------------------------------------------------------------- */
