@@ -15,7 +15,7 @@ SMALL_MODELS = heisenberg_kagome_16 heisenberg_kagome_18 j1j2_square_4x4 sk_16_1
 DATA ?= physical_systems/data-large
 OUT ?= experiments
 
-.PHONY: all build test test-gpu bench small clusters kagome_36 pyrochlore_32 sk_32_1
+.PHONY: all build test test-gpu bench small clusters kagome_36 pyrochlore_32 sk_32_1 noise quality_check
 all: build
 
 build:
@@ -39,6 +39,29 @@ $(OUT)/%.csv:
 		--output $@.wip --repetitions 1024 \
 		--number-sweeps 100,200,400,800,1600,3200,6400,12800,25600,51200,102400,204800 && \
 	mv $@.wip $@
+
+# `make noise MODEL=...`: influence of amplitude noise on the greedy solver (reference Makefile:37-44:
+# 1000 noise levels x 100 repetitions), every draw on a reweighted clone of one plan, $(BATCH) draws per
+# greedy_solve_batch; then the quartiles per bin of the amplitude overlap (<model>_stats.csv)
+NOISE_STEPS ?= 1000
+NOISE_REPETITIONS ?= 100
+BATCH ?= 16
+noise: $(OUT)/noise/$(MODEL).csv
+
+$(OUT)/noise/%.csv:
+	@mkdir -p $(OUT)/noise
+	$(PYTHON) -m annealing_sign_problem_amd.influence_of_noise --model $* --seed $(SEED) \
+		--output $@.wip --steps $(NOISE_STEPS) --repetitions $(NOISE_REPETITIONS) --batch $(BATCH) && \
+	mv $@.wip $@
+	$(PYTHON) -c "from annealing_sign_problem_amd.influence_of_noise import postprocess_influence_of_noise as p; p('$@')"
+
+# `make quality_check` (reference Makefile:46-48): sign accuracy and overlap of the greedy solver on the
+# exact amplitudes of the small models
+quality_check:
+	@for model in $(SMALL_MODELS); do \
+		printf '%s,' $$model; \
+		$(PYTHON) -m annealing_sign_problem_amd.influence_of_noise --model $$model --quality || exit 1; \
+	done
 
 # `make kagome_36`-style run (greedy only, extension order $(ORDER), global cutoff) on $(MODEL)
 clusters:

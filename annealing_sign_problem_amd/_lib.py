@@ -216,6 +216,10 @@ SIGNATURES = {
     "asp_sa_plan_info": (c_int, [c_void_p, ctypes.POINTER(SaInfo)]),
     "asp_sa_layout_host": (c_int, [c_u64, c_void_p, c_void_p, c_void_p, c_void_p,
                                    ctypes.POINTER(SaInfo), c_void_p, c_void_p]),
+    "asp_sa_layout_build_count": (c_u64, []),
+    "asp_sa_plan_reweight": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "asp_sa_plan_reweight_last_ms": (c_float, [c_void_p]),
+    "asp_sa_plan_clone": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
     "asp_sa_batch_slots_host": (c_int, [c_u32, c_void_p, c_void_p, ctypes.POINTER(c_u32), c_void_p, c_u64]),
     "asp_sa_shuffled_order_host": (c_int, [c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_u32,
                                            c_void_p, c_void_p, ctypes.POINTER(c_u32)]),

@@ -32,6 +32,7 @@ from . import _lib
 
 __all__ = [
     "Hamiltonian",
+    "PatternMismatch",
     "anneal",
     "anneal_batch",
     "anneal_traces",
@@ -83,6 +84,11 @@ def make_schedule(beta0: float, beta1: float, number_sweeps: int) -> np.ndarray:
     if number_sweeps == 1:
         return np.array([beta1], dtype=np.float64)
     return np.geomspace(beta0, beta1, number_sweeps).astype(np.float64)
+
+
+class PatternMismatch(ValueError):
+    """:meth:`Hamiltonian.reweight` was given couplings on another sparsity pattern than the plan's
+    (or numbers under which ``J + J^T`` gains or loses an entry): the plan cannot take them."""
 
 
 class Hamiltonian:
@@ -158,7 +164,7 @@ class Hamiltonian:
 
     def plan(self):
         """The (cached) device-resident sweep plan handle."""
-        key = (id(self.exchange), id(self.field), self.exchange.nnz)
+        key = self._key()
         if self._plan is not None and self._plan_key == key:
             return self._plan
         self.release()
@@ -197,6 +203,78 @@ class Hamiltonian:
             self.release()
         except Exception:
             pass
+
+    # -- new numbers on the same pattern ------------------------------------------
+    def _key(self):
+        return (id(self.exchange), id(self.field), self.exchange.nnz)
+
+    def reweight(self, data, field=None, indptr=None, indices=None) -> "Hamiltonian":
+        """New couplings ``data`` (in the order of ``exchange.data``; ``None`` keeps them) and / or a
+        new ``field`` on the SAME sparsity pattern, in place: the device plan takes the numbers without
+        being rebuilt (``asp_sa_plan_reweight``: no colouring, no permutation, no ELL fill) and
+        afterwards equals, bit for bit, the plan of ``Hamiltonian(new exchange, new field)``.
+        ``indptr`` / ``indices``, when given, are compared with the pattern; any difference — and
+        numbers under which ``J + J^T`` gains or loses an entry — raises :class:`PatternMismatch`
+        and leaves the object as it was.  Live :class:`Chains` of this object must be closed first.
+        ``exchange`` and ``field`` become new frozen objects that share the frozen index arrays."""
+        m = self.exchange
+        if indptr is not None and not np.array_equal(np.asarray(indptr), m.indptr):
+            raise PatternMismatch("'indptr' differs from the pattern of this Hamiltonian")
+        if indices is not None and not np.array_equal(np.asarray(indices), m.indices):
+            raise PatternMismatch("'indices' differ from the pattern of this Hamiltonian")
+        if data is None and field is None:
+            raise ValueError("at least one of 'data' and 'field' must be given")
+        if data is not None:
+            data = np.array(data, dtype=np.float64, order="C", copy=True).reshape(-1)
+            if data.shape[0] != m.nnz:
+                raise PatternMismatch("{} couplings given, the pattern has {}".format(data.shape[0], m.nnz))
+        if field is not None:
+            field = np.array(field, dtype=np.float64, order="C", copy=True)
+            if field.shape != (self.size,):
+                raise ValueError("'field' must have shape ({},)".format(self.size))
+        plan = self.plan()
+        old_indptr, old_indices, _, _ = self._arrays()
+        lib = _lib.load()
+        rc = lib.asp_sa_plan_reweight(plan, ctypes.c_uint64(m.nnz), _lib.ptr(old_indptr), _lib.ptr(old_indices),
+                                      _lib.ptr(data), _lib.ptr(field))
+        if rc != 0:
+            message = _lib.last_error()
+            if "pattern mismatch" in message:
+                raise PatternMismatch(message)
+            raise _lib.AspError(rc, message)
+        if data is not None:
+            data.flags.writeable = False  # (before scipy takes its view of it)
+            matrix = scipy.sparse.csr_matrix((data, m.indices, m.indptr), shape=m.shape, copy=False)
+            matrix.has_sorted_indices = True
+            matrix.has_canonical_format = True
+            self.exchange = matrix
+        if field is not None:
+            field.flags.writeable = False
+            self.field = field
+        self._plan_key = self._key()
+        return self
+
+    def reweighted(self, data, field=None, indptr=None, indices=None) -> "Hamiltonian":
+        """A NEW Hamiltonian with these numbers on the pattern of this one (which is left alone and
+        gets its plan built if it has none): its plan is a clone of this one's (``asp_sa_plan_clone``:
+        the same structure, own buffers and stream, no preprocessing) reweighted as in
+        :meth:`reweight`.  The two objects can go into one batched call."""
+        source = self.plan()
+        lib = _lib.load()
+        handle = ctypes.c_void_p()
+        _lib.check(lib.asp_sa_plan_clone(source, ctypes.byref(handle)))
+        other = Hamiltonian.__new__(Hamiltonian)
+        other.exchange = self.exchange
+        other.field = self.field
+        other._plan = handle
+        other._plan_key = other._key()
+        _lib.track(other)
+        try:
+            other.reweight(data, field, indptr, indices)
+        except Exception:
+            other.release()
+            raise
+        return other
 
     # -- energy ----------------------------------------------------------------
     def energy(self, x) -> float:

@@ -42,6 +42,7 @@ SOURCES = [
     "sa_chains.hip",
     "sa_population.hip",
     "sa_cluster.hip",
+    "sa_reweight.hip",
 ]
 
 # -ffp-contract=off: the parity contract needs every multiply/add rounded on its

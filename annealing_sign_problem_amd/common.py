@@ -23,6 +23,7 @@ from . import annealer as sa
 __all__ = [
     "IsingModel",
     "make_ising_model",
+    "reweight_ising_model",
     "solve_ising_model",
     "solve_ising_models",
     "dump_ising_model_to_hdf5",
@@ -208,15 +209,7 @@ def make_ising_model(
         spins = np.ascontiguousarray(spins[:, 0])
     n = spins.shape[0]
 
-    psi = np.exp(log_psi, dtype=np.complex128)
-    if not np.allclose(psi.imag, 0, atol=1e-6):
-        raise ValueError("expected all wavefunction coefficients to be real")
-    psi = np.ascontiguousarray(psi.real)
-    cluster_norm = norm2(psi)
-    psi /= cluster_norm
-
-    field = np.zeros(n) if not external_field else _boundary_field(
-        quantum_hamiltonian, spins, psi, log_psi_fn, cluster_norm)
+    psi, field = _cluster_amplitudes_and_field(quantum_hamiltonian, spins, log_psi, log_psi_fn, external_field)
     matrix = None
     ising_hamiltonian = None
     if _on_device(quantum_hamiltonian):
@@ -242,6 +235,82 @@ def make_ising_model(
         ising_hamiltonian = sa.Hamiltonian(matrix, field)
     x0 = sa.signs_to_bits(np.sign(psi))
     return IsingModel(spins, quantum_hamiltonian, ising_hamiltonian, x0, basis_index)
+
+
+def _cluster_amplitudes_and_field(hamiltonian, spins, log_psi, log_psi_fn, external_field: bool):
+    """``(psi, field)`` of a cluster's Ising model from the log-amplitudes of its states: real
+    amplitudes L2-normalised over the cluster (common.py:211-216) and the zero or boundary field.
+    One place for :func:`make_ising_model` and :func:`reweight_ising_model`, whose models must agree
+    bit for bit."""
+    psi = np.exp(log_psi, dtype=np.complex128)
+    if not np.allclose(psi.imag, 0, atol=1e-6):
+        raise ValueError("expected all wavefunction coefficients to be real")
+    psi = np.ascontiguousarray(psi.real)
+    cluster_norm = norm2(psi)
+    psi /= cluster_norm
+    field = np.zeros(spins.shape[0]) if not external_field else _boundary_field(
+        hamiltonian, spins, psi, log_psi_fn, cluster_norm)
+    return psi, field
+
+
+def reweight_ising_model(
+    model: IsingModel,
+    log_psi: Optional[np.ndarray] = None,
+    log_psi_fn: Optional[Callable[[np.ndarray], np.ndarray]] = None,
+    external_field: bool = False,
+    out: Optional[IsingModel] = None,
+) -> IsingModel:
+    """``make_ising_model(model.spins, model.quantum_hamiltonian, log_psi, log_psi_fn, external_field)``
+    — the same states and operator, new amplitudes — for a model of one of this package's device
+    operators, WITHOUT rebuilding the annealer's plan: the couplings keep their sparsity pattern as long
+    as no amplitude vanishes, so the new values (``device().ising_csr``, amplitudes normalised as in
+    :func:`make_ising_model`) go onto a clone of ``model``'s plan (``Hamiltonian.reweighted``), or with
+    ``out=`` — a model this function returned earlier — into that model's Hamiltonian in place
+    (``Hamiltonian.reweight``; a pool of clones serves a loop of any length).  ``exchange``, ``field``,
+    ``initial_signs`` and every result of the returned model equal ``make_ising_model``'s bit for bit.
+    When the pattern did change (``sa.PatternMismatch``), or for an operator without a device action,
+    the result IS ``make_ising_model(...)`` — never an error; ``out`` is then left as it was."""
+    if log_psi is None and log_psi_fn is None:
+        raise ValueError("at least one of log_psi or log_psi_fn should be specified")
+    if external_field and log_psi_fn is None:
+        raise ValueError("log_psi_fn should be specified when external_field=True")
+    operator, spins = model.quantum_hamiltonian, model.spins
+
+    def fresh():
+        return make_ising_model(spins, operator, log_psi=log_psi, log_psi_fn=log_psi_fn,
+                                external_field=external_field)
+
+    if not _on_device(operator):
+        return fresh()
+    basis_index = model.basis_index
+    values = log_psi
+    if values is None:
+        if hasattr(log_psi_fn, "index_of"):
+            if basis_index is None:
+                basis_index = log_psi_fn.index_of(spins)
+            values = log_psi_fn.at_index(basis_index)
+        else:
+            values = log_psi_fn(spins)
+    psi, field = _cluster_amplitudes_and_field(operator, spins, values, log_psi_fn, external_field)
+    try:
+        indptr, col, val = operator.device().ising_csr(spins, psi)
+    except _lib.AspError as error:
+        if error.code != -3:
+            raise
+        return fresh()
+    try:
+        if out is not None:
+            hamiltonian = out.ising_hamiltonian.reweight(val, field, indptr, col)
+        else:
+            hamiltonian = model.ising_hamiltonian.reweighted(val, field, indptr, col)
+    except sa.PatternMismatch:
+        return fresh()
+    x0 = sa.signs_to_bits(np.sign(psi))
+    if out is not None:
+        out.initial_signs = x0
+        out.basis_index = basis_index
+        return out
+    return IsingModel(spins, operator, hamiltonian, x0, basis_index)
 
 
 def _boundary_field(hamiltonian, spins, psi, log_psi_fn, cluster_norm: float) -> np.ndarray:

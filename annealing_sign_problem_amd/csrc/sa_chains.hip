@@ -261,6 +261,8 @@ int asp_sa_chains_create(asp_sa_plan *p, uint64_t seed, uint32_t repetitions, ui
     delete c;
     return rc;
   }
+  c->live_of_plan = p->live_chains;
+  c->live_of_plan->fetch_add(1, std::memory_order_relaxed);
   *out = c;
   return ASP_OK;
 }
@@ -268,6 +270,7 @@ int asp_sa_chains_create(asp_sa_plan *p, uint64_t seed, uint32_t repetitions, ui
 void asp_sa_chains_destroy(asp_sa_chains *c) {
   // (every entry point waits for its stream before it returns: the buffers are idle; the plan is
   // not touched, so a handle may outlive its plan as long as it is only destroyed)
+  if (c && c->live_of_plan) c->live_of_plan->fetch_sub(1, std::memory_order_relaxed);
   delete c;
 }
 

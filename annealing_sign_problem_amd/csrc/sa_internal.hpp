@@ -5,15 +5,55 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
+#include <memory>
+#include <mutex>
 #include <utility>
 #include <vector>
 
 #include "asp_common.hpp"
 #include "sa_plan.hpp"
 
+namespace asp {
+
+// What asp_sa_plan_reweight needs besides the layout (csrc/sa_reweight.hip): the CSR
+// pattern the plan was created from, kept to compare a reweight's pattern with exactly, and — built by
+// the family's first reweight, on the host from the pattern and the layout, uploaded once — where every
+// entry of A comes from and goes to.  Immutable once built; a plan and its clones share one.
+struct SaPattern {
+  uint64_t nnz = 0;
+  std::vector<int64_t> indptr;   // num_spins + 1 (empty: no spins)
+  std::vector<int32_t> indices;  // nnz
+  std::mutex build;              // (two clones may ask for the maps at the same time)
+  bool built = false;
+  static constexpr uint32_t kNone = 0xFFFFFFFFu;
+  // per entry e of A (row i, k-th of the row, column j):
+  std::vector<uint32_t> src_ij, src_ji;  // positions of J_ij and J_ji in `data`, kNone where absent
+  std::vector<uint64_t> ell_slot;        // its element of ell_val
+  std::vector<uint32_t> rq_slot;         // its element of rq_val (the rows padded to quads)
+  std::vector<int64_t> diag_pos;         // per row: the position of J_ii in `data`, or -1
+  // stored off-diagonal pairs that A does NOT hold (J_ij + J_ji was exactly 0 at creation): they must
+  // still cancel after a reweight, or a fresh plan would have one more entry; second = -1: one-sided
+  std::vector<std::pair<int64_t, int64_t>> dropped;
+  DeviceBuffer<uint32_t> d_src_ij, d_src_ji, d_rq_slot;
+  DeviceBuffer<uint64_t> d_ell_slot;
+  DeviceBuffer<int64_t> d_a_ptr;
+};
+
+}  // namespace asp
+
 struct asp_sa_plan {
   asp::SaHostLayout host;
+  std::shared_ptr<asp::SaPattern> pattern;  // set by asp_sa_plan_create, shared by asp_sa_plan_clone
+  // handles of asp_sa_chains_create that are alive (a handle may outlive its plan, so it holds the
+  // counter too): asp_sa_plan_reweight refuses while there is one
+  std::shared_ptr<std::atomic<int>> live_chains = std::make_shared<std::atomic<int>>(0);
+  // asp_sa_plan_reweight's staging (grown on demand and kept): the new data and field, the merged
+  // values of A, per row sum |A_ij| and the smallest non-zero 2 |A_ij|, the count of cancelled entries
+  asp::DeviceBuffer<double> rw_data, rw_field, rw_a_val, rw_row_sum, rw_row_min;
+  asp::DeviceBuffer<uint32_t> rw_zeros;
+  float rw_last_ms = 0.0f;  // asp_sa_plan_reweight_last_ms
   hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   float last_sweep_ms = 0.0f, last_total_ms = 0.0f;
@@ -83,6 +123,7 @@ struct asp_sa_plan {
 // below: at the handle's first gather).
 struct asp_sa_chains {
   asp_sa_plan *plan = nullptr;
+  std::shared_ptr<std::atomic<int>> live_of_plan;  // asp_sa_plan::live_chains, counted down at destroy
   uint64_t seed = 0;
   uint32_t repetitions = 0, replica_offset = 0, words = 0;
   uint32_t sweeps_done = 0;
@@ -118,6 +159,11 @@ inline int check_distinct_plans(const std::vector<asp_sa_chains *> &handles) {
   }
   return ASP_OK;
 }
+
+// What asp_sa_plan_create does once p->host is filled — stream, events, device limits and the uploads of
+// the layout —, for asp_sa_plan_clone as well (csrc/sa_sweep.hip).  ASP_OK, or the error recorded; the
+// caller destroys the plan.
+int sa_plan_device_setup(asp_sa_plan *p);
 
 // Rows of A over original indices and the field in original order (asp_sa_plan::cluster_*), uploaded
 // on first use; shared by the cluster moves (csrc/sa_cluster.hip) and the device tree (csrc/greedy_tree.hip).

@@ -4,6 +4,7 @@
 #include "sa_plan.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -58,11 +59,33 @@ unsigned host_threads(uint64_t n) {
   return std::max(1u, std::min(4u, hw ? hw : 1u));
 }
 
+std::atomic<uint64_t> g_layout_builds{0};  // asp_sa_layout_build_count
+
 }  // namespace
+
+void sa_finish_scales(double bound, double max_delta, double min_delta, SaHostLayout *out) {
+  SaHostLayout &L = *out;
+  L.energy_scale_exp = 0;
+  if (bound > 0.0) {
+    // S: the whole tracked range 2B stays below 2^60 and a single |dE| <= max_delta stays
+    // below 2^50, so the kernel can round dE * 2^S to int64 with one f64 add (|x| < 2^51)
+    int e = 0, e_single = 0;
+    (void)std::frexp(2.0 * bound, &e);    // 2B < 2^e
+    (void)std::frexp(max_delta, &e_single);  // max_delta < 2^e_single
+    L.energy_scale_exp = std::clamp(std::min(60 - e, 50 - e_single), -1000, 1000);
+  }
+  if (max_delta > 0.0 && std::isfinite(min_delta)) {
+    L.beta0_auto = std::log(2.0) / max_delta;
+    L.beta1_auto = std::log(100.0) / min_delta;
+  } else {
+    L.beta0_auto = L.beta1_auto = 1.0;
+  }
+}
 
 int build_sa_layout(uint64_t num_spins, const int64_t *indptr, const int32_t *indices,
                     const double *data, const double *field, SaHostLayout *out) {
   const uint64_t n = num_spins;
+  g_layout_builds.fetch_add(1, std::memory_order_relaxed);
   // ASP_PLAN_TIMING=1: stage times of this function on stderr (development aid)
   const bool timing = std::getenv("ASP_PLAN_TIMING") != nullptr;
   auto clock_now = [] { return std::chrono::steady_clock::now(); };
@@ -515,20 +538,7 @@ int build_sa_layout(uint64_t num_spins, const int64_t *indptr, const int32_t *in
     max_delta = std::max(max_delta, 2.0 * (row + h));
   }
   if (!std::isfinite(bound)) return set_error(ASP_ERR_INVALID, "couplings overflow double range");
-  if (bound > 0.0) {
-    // S: the whole tracked range 2B stays below 2^60 and a single |dE| <= max_delta stays
-    // below 2^50, so the kernel can round dE * 2^S to int64 with one f64 add (|x| < 2^51)
-    int e = 0, e_single = 0;
-    (void)std::frexp(2.0 * bound, &e);    // 2B < 2^e
-    (void)std::frexp(max_delta, &e_single);  // max_delta < 2^e_single
-    L.energy_scale_exp = std::clamp(std::min(60 - e, 50 - e_single), -1000, 1000);
-  }
-  if (max_delta > 0.0 && std::isfinite(min_delta)) {
-    L.beta0_auto = std::log(2.0) / max_delta;
-    L.beta1_auto = std::log(100.0) / min_delta;
-  } else {
-    L.beta0_auto = L.beta1_auto = 1.0;
-  }
+  sa_finish_scales(bound, max_delta, min_delta, &L);
   stage("scales");
   return ASP_OK;
 }
@@ -666,6 +676,10 @@ extern "C" int asp_sa_shuffled_order_host(uint64_t num_spins, int64_t const *ind
   }
   if (num_levels) *num_levels = levels;
   return ASP_OK;
+}
+
+extern "C" uint64_t asp_sa_layout_build_count(void) {
+  return asp::g_layout_builds.load(std::memory_order_relaxed);
 }
 
 static void fill_info(const asp::SaHostLayout &L, asp_sa_info *info) {

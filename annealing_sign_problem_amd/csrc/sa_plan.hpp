@@ -51,6 +51,11 @@ struct SaHostLayout {
 int build_sa_layout(uint64_t num_spins, const int64_t *indptr, const int32_t *indices,
                     const double *data, const double *field, SaHostLayout *out);
 
+// The last step of build_sa_layout, shared with asp_sa_plan_reweight (csrc/sa_reweight.hip): the
+// energy scale and the automatic betas from B = 1/2 sum|A| + sum|h|, max_i 2 (sum_j |A_ij| + |h_i|)
+// and the smallest non-zero 2|A_ij| / 2|h_i| (+inf: none), summed in build_sa_layout's order.
+void sa_finish_scales(double bound, double max_delta, double min_delta, SaHostLayout *out);
+
 // Visiting orders of the "shuffled" sweep: sweep t visits the spins in ascending
 // (priority, index), priority_t(i) = word 0 of Philox4x32-10(counter (i, t, 0xFFFFFFFE, 0), key
 // seed).  A sequential sweep in that order equals visiting the LEVELS of the priority graph one

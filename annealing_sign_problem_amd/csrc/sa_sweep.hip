@@ -2097,6 +2097,40 @@ int energies_of_perm(asp_sa_plan *p, const uint64_t *perm_words, uint32_t count,
 
 namespace asp {
 
+int sa_plan_device_setup(asp_sa_plan *p) {
+  const SaHostLayout &L = p->host;
+  bool ok = stream_acquire(&p->stream) == ASP_OK;
+  for (auto &e : p->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+  if (!ok) set_error(ASP_ERR_HIP, "could not create HIP stream/events");
+  int num_cus = 0;
+  size_t max_lds = 0;
+  if (ok && device_limits(&num_cus, &max_lds) == ASP_OK) {
+    p->num_cus = num_cus;
+    p->max_lds = max_lds;
+  }
+  ok = ok && upload_vector(p->color_block_start, L.color_block_start, p->stream) == ASP_OK &&
+       upload_vector(p->block_width, L.block_width, p->stream) == ASP_OK &&
+       upload_vector(p->ell_off, L.ell_off, p->stream) == ASP_OK &&
+       upload_vector(p->ell_col, L.ell_col, p->stream) == ASP_OK &&
+       upload_vector(p->ell_val, L.ell_val, p->stream) == ASP_OK &&
+       upload_vector(p->spin_of_pos, L.spin_of_pos, p->stream) == ASP_OK &&
+       upload_vector(p->pos_of_spin, L.pos_of_spin, p->stream) == ASP_OK &&
+       upload_vector(p->field_pos, L.field_pos, p->stream) == ASP_OK;
+  if (ok && sweep_lds_bytes(L, kWide) <= p->max_lds) {
+    std::vector<uint32_t> scaled(L.ell_col.size());
+    for (size_t i = 0; i < scaled.size(); ++i) scaled[i] = L.ell_col[i] * 4u;
+    ok = upload_vector(p->ell_col4, scaled, p->stream) == ASP_OK &&
+         hipStreamSynchronize(p->stream) == hipSuccess;  // `scaled` dies with this scope
+  }
+  if (ok && hipStreamSynchronize(p->stream) != hipSuccess) {
+    set_error(ASP_ERR_HIP, "plan upload failed");
+    ok = false;
+  }
+  if (ok) return ASP_OK;
+  if (error_state().code == ASP_OK) set_error(ASP_ERR_HIP, "plan upload failed");
+  return error_state().code;
+}
+
 int sa_permute_bits(asp_sa_plan *p, const uint64_t *x, uint32_t count, uint64_t *perm) {
   const SaHostLayout &L = p->host;
   const uint64_t total = static_cast<uint64_t>(count) * L.num_blocks;
@@ -2130,7 +2164,13 @@ asp_sa_plan *asp_sa_plan_create(uint64_t num_spins, int64_t const *indptr, int32
     delete p;
     return nullptr;
   }
-  const asp::SaHostLayout &L = p->host;
+  p->pattern = std::make_shared<asp::SaPattern>();
+  if (num_spins > 0) {
+    // the pattern, for asp_sa_plan_reweight to compare with (validated above)
+    p->pattern->nnz = static_cast<uint64_t>(indptr[num_spins]);
+    p->pattern->indptr.assign(indptr, indptr + num_spins + 1);
+    p->pattern->indices.assign(indices, indices + p->pattern->nnz);
+  }
   // ASP_SA_TEAM=0: no team sweeps in this process — several processes share the device (worker
   // processes or ranks of the pipeline on one GPU), and a team launch needs all its workgroups
   // resident together, which another process's kernels can prevent (the watchdog then costs
@@ -2139,34 +2179,7 @@ asp_sa_plan *asp_sa_plan_create(uint64_t num_spins, int64_t const *indptr, int32
     const int team = std::atoi(env);
     if (team == 0 || team == 2 || team == 4 || team == 8) p->team_mode = team;
   }
-  bool ok = asp::stream_acquire(&p->stream) == ASP_OK;
-  for (auto &e : p->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  if (!ok) asp::set_error(ASP_ERR_HIP, "could not create HIP stream/events");
-  int num_cus = 0;
-  size_t max_lds = 0;
-  if (ok && asp::device_limits(&num_cus, &max_lds) == ASP_OK) {
-    p->num_cus = num_cus;
-    p->max_lds = max_lds;
-  }
-  ok = ok && upload_vector(p->color_block_start, L.color_block_start, p->stream) == ASP_OK &&
-       upload_vector(p->block_width, L.block_width, p->stream) == ASP_OK &&
-       upload_vector(p->ell_off, L.ell_off, p->stream) == ASP_OK &&
-       upload_vector(p->ell_col, L.ell_col, p->stream) == ASP_OK &&
-       upload_vector(p->ell_val, L.ell_val, p->stream) == ASP_OK &&
-       upload_vector(p->spin_of_pos, L.spin_of_pos, p->stream) == ASP_OK &&
-       upload_vector(p->pos_of_spin, L.pos_of_spin, p->stream) == ASP_OK &&
-       upload_vector(p->field_pos, L.field_pos, p->stream) == ASP_OK;
-  if (ok && sweep_lds_bytes(L, kWide) <= p->max_lds) {
-    std::vector<uint32_t> scaled(L.ell_col.size());
-    for (size_t i = 0; i < scaled.size(); ++i) scaled[i] = L.ell_col[i] * 4u;
-    ok = upload_vector(p->ell_col4, scaled, p->stream) == ASP_OK &&
-         hipStreamSynchronize(p->stream) == hipSuccess;  // `scaled` dies with this scope
-  }
-  if (ok && hipStreamSynchronize(p->stream) != hipSuccess) {
-    asp::set_error(ASP_ERR_HIP, "plan upload failed");
-    ok = false;
-  }
-  if (!ok) {
+  if (asp::sa_plan_device_setup(p) != ASP_OK) {
     asp_sa_plan_destroy(p);
     return nullptr;
   }

@@ -377,6 +377,37 @@ int asp_sa_layout_host(uint64_t num_spins, int64_t const *indptr, int32_t const 
                        double const *data, double const *field, asp_sa_info *info,
                        int32_t *colors, uint32_t *position);
 
+/* How often the host preprocessing (colouring, permutation, sliced ELL) has run in this process:
+ * asp_sa_plan_create, asp_sa_layout_host and asp_sa_shuffled_order_host each count one; the two calls
+ * below count none. */
+uint64_t asp_sa_layout_build_count(void);
+
+/* New numbers on the SAME pattern, in place and without the host preprocessing:
+ * afterwards the plan is indistinguishable, bit for bit, from asp_sa_plan_create(K, indptr, indices,
+ * data, field) — every field of asp_sa_plan_info, energies, anneals and traces in both orders, chains
+ * created afterwards, ladder / exchange / resample / cluster moves, the greedy solver with every tree.
+ * (nnz, indptr, indices) must equal the arrays the plan was created from, entry for entry; data == NULL
+ * keeps the couplings, field == NULL the field (both NULL: ASP_ERR_INVALID; a plan without spins: a
+ * no-op).  The device merges J_ij + J_ji of every coupling of the plan from the uploaded data and
+ * scatters it into every value array the plan holds at that moment; the host layout and the scales
+ * follow.  ASP_ERR_INVALID, with the plan answering exactly as before the call: a NULL plan (no device
+ * needed), another pattern, a live asp_sa_chains handle of the plan (its tracked energies belong to the
+ * old couplings), non-finite numbers or an overflowing bound (asp_sa_plan_create's messages), and a
+ * changed pattern of J + J^T — a coupling of the plan whose new J_ij + J_ji is exactly 0 (a fresh plan
+ * would drop it) or a stored pair that cancelled at creation and no longer does ("pattern mismatch"
+ * starts the message of every pattern error). */
+int asp_sa_plan_reweight(asp_sa_plan *p, uint64_t nnz, int64_t const *indptr, int32_t const *indices,
+                         double const *data, double const *field);
+/* Device time (ms, HIP events) of the plan's last successful asp_sa_plan_reweight: uploads, kernels
+ * and the read-back of the row sums. */
+float asp_sa_plan_reweight_last_ms(asp_sa_plan const *p);
+/* A second plan with the structure and the numbers of *p, made without the host preprocessing: its own
+ * stream, events, work buffers and arrays (it outlives *p), the launch settings of *p (asp_sa_set_launch,
+ * _set_packed, _set_wide, _set_team, _set_field_cache, _set_post, _set_shuffled_launch, _set_shuffled_teams,
+ * _set_greedy_tree) and none of its chains.  What asp_sa_greedy_batch and the other batched calls need
+ * to solve several reweighted copies of one model at once: they refuse one plan twice. */
+int asp_sa_plan_clone(asp_sa_plan const *p, asp_sa_plan **out);
+
 /* Host-only (inspection, CPU tests): where the shared launches of the batched calls (asp_sa_anneal_batch,
  * asp_sa_chains_advance_batch, asp_sa_greedy_batch) place the workgroups of ONE launch class.  Member k
  * < count has groups[k] workgroups of about work[k] each.  The members go in descending work, stable,
