@@ -15,7 +15,8 @@ SMALL_MODELS = heisenberg_kagome_16 heisenberg_kagome_18 j1j2_square_4x4 sk_16_1
 DATA ?= physical_systems/data-large
 OUT ?= experiments
 
-.PHONY: all build test test-gpu bench small clusters kagome_36 pyrochlore_32 sk_32_1 noise quality_check
+.PHONY: all build test test-gpu bench small clusters kagome_36 pyrochlore_32 sk_32_1 noise quality_check \
+	couplings is_frustrated small_amplitude_overlaps
 all: build
 
 build:
@@ -61,6 +62,35 @@ quality_check:
 	@for model in $(SMALL_MODELS); do \
 		printf '%s,' $$model; \
 		$(PYTHON) -m annealing_sign_problem_amd.influence_of_noise --model $$model --quality || exit 1; \
+	done
+
+# `make couplings`, `make is_frustrated`, `make small_amplitude_overlaps` (reference Makefile: the
+# experiments/couplings/%.csv rule, `is_frustrated` and `small_amplitude_overlaps`): |J| of all bonds in
+# descending order, the probability that a bond of a given strength is not frustrated, and the overlap of
+# the amplitudes with random ones, for the small models; the statistics run on the GPU.
+# `make is_frustrated MODEL=heisenberg_kagome_36` (any model outside SMALL_MODELS): ground state and Ising
+# model of the whole symmetry sector stay on the device.
+couplings: $(SMALL_MODELS:%=$(OUT)/couplings/%.csv)
+
+$(OUT)/couplings/%.csv:
+	@mkdir -p $(OUT)/couplings
+	$(PYTHON) -m annealing_sign_problem_amd.coupling_analysis --model $* --couplings $@.wip && mv $@.wip $@
+
+ifeq ($(origin MODEL),command line)
+is_frustrated: $(OUT)/is_frustrated/$(MODEL).csv
+else
+is_frustrated: $(SMALL_MODELS:%=$(OUT)/is_frustrated/%.csv)
+endif
+
+$(OUT)/is_frustrated/%.csv:
+	@mkdir -p $(OUT)/is_frustrated
+	$(PYTHON) -m annealing_sign_problem_amd.coupling_analysis --model $* \
+		$(if $(filter $*,$(SMALL_MODELS)),,--sector) --is-frustrated $@.wip && mv $@.wip $@
+
+small_amplitude_overlaps:
+	@for model in $(SMALL_MODELS); do \
+		printf '%s: ' $$model; \
+		$(PYTHON) -m annealing_sign_problem_amd.coupling_analysis --model $$model --smallest-overlap || exit 1; \
 	done
 
 # `make kagome_36`-style run (greedy only, extension order $(ORDER), global cutoff) on $(MODEL)

@@ -156,6 +156,21 @@ class SaChainsExchangeItem(ctypes.Structure):
     ]
 
 
+class BondsSummary(ctypes.Structure):
+    """Mirror of ``asp_bonds_summary`` (include/asp.h)."""
+
+    _fields_ = [
+        ("num_spins", c_u64),
+        ("stored", c_u64),
+        ("bonds", c_u64),
+        ("frustrated", c_u64),
+        ("rows_with_bonds", c_u64),
+        ("strongest_frustrated", c_u64),
+        ("max_abs", c_double),
+        ("min_abs", c_double),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/asp.h declares
 SIGNATURES = {
     "asp_last_error": (ctypes.c_char_p, []),
@@ -281,6 +296,16 @@ SIGNATURES = {
     "asp_sa_last_launch": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                                    ctypes.POINTER(c_int)]),
     "asp_sa_energy": (c_int, [c_void_p, c_u32, c_void_p, c_void_p]),
+    "asp_bonds_create": (c_int, [c_u64, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
+    "asp_bonds_set_signs": (c_int, [c_void_p, c_void_p]),
+    "asp_bonds_get_summary": (c_int, [c_void_p, ctypes.POINTER(BondsSummary)]),
+    "asp_bonds_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "asp_bonds_histogram": (c_int, [c_void_p, c_u32, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_u64),
+                                    ctypes.POINTER(c_u64)]),
+    "asp_bonds_magnitudes": (c_int, [c_void_p, c_u64, c_void_p]),
+    "asp_bonds_destroy": (None, [c_void_p]),
+    "asp_bonds_last_ms": (c_float, []),
+    "asp_sector_bonds_create": (c_int, [c_u64, c_u32, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

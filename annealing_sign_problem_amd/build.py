@@ -34,6 +34,7 @@ SOURCES = [
     "key_table.hip",
     "plain_basis.hip",
     "sparsify.hip",
+    "bond_stats.hip",
     "sa_plan.cpp",
     "greedy.cpp",
     "greedy_tree.hip",

@@ -35,6 +35,9 @@ __all__ = [
     "extension_spins",
     "sparsify_using_global_cutoff",
     "get_strongest_off_diag",
+    "cluster_statistics",
+    "coupling_distribution",
+    "probability_of_frustration",
     "binary_search",
     "monte_carlo_sampling",
     "add_noise_to_amplitudes",
@@ -491,6 +494,72 @@ def get_strongest_off_diag(matrix) -> np.ndarray:
     out = np.zeros(m.shape[0], dtype=m.data.dtype)
     np.maximum.at(out, rows, magnitude)
     return out
+
+
+def cluster_statistics(spins, quantum_hamiltonian, ground_state) -> dict:
+    """``{"spins", "bonds", "frustrated", "largest_frustrated"}`` of the Ising model of a cluster
+    with the ground state's own signs — the four numbers common.py:439-478 logs: the number of bonds
+    (off-diagonal non-zeros, both directions), the fraction of them that is frustrated
+    (``J_ij s_i s_j > 0``) and the fraction of spins whose strongest bond is.  One deliberate
+    difference: the reference takes ``argmax`` of the SIGNED matrix with its implicit zeros (it
+    computes ``positive_matrix`` and never uses it); here the strongest bond is the one of largest
+    magnitude, the smallest column on a tie."""
+    from .bonds import BondStatistics
+
+    log_psi_fn = ground_state_to_log_coeff_fn(ground_state, quantum_hamiltonian.basis)
+    model = make_ising_model(spins, quantum_hamiltonian, log_psi_fn=log_psi_fn)
+    with BondStatistics(model.ising_hamiltonian, model.initial_signs) as stats:
+        summary = stats.summary
+    size, bonds = model.size, summary["bonds"]
+    return {"spins": size, "bonds": bonds,
+            "frustrated": summary["frustrated"] / bonds if bonds else float("nan"),
+            "largest_frustrated": summary["strongest_frustrated"] / size if size else float("nan")}
+
+
+def coupling_distribution(model: IsingModel) -> np.ndarray:
+    """``|J_ij|`` of all bonds of the model in descending order (common.py:955-959), sorted on the
+    device."""
+    from .bonds import BondStatistics
+
+    with BondStatistics(model.ising_hamiltonian, model.initial_signs) as stats:
+        return stats.magnitudes()
+
+
+def probability_of_frustration(model, signs=None, bins: int = 50, span: float = 20.0, min_count: int = 100):
+    """``(x, y, normal, frustrated)``: the probability ``y`` that a bond of strength ``x`` is NOT
+    frustrated (common.py:977-1001).  ``bins`` log-space edges from ``lo = max(log max|J| - span,
+    log min|J|)`` to ``log max|J|``; ``normal`` and ``frustrated`` are the counts of the ``bins - 1``
+    bins, ``y = normal / (normal + frustrated)`` with NaN where the total is below ``min_count``, and
+    ``x = exp`` of the bin centres.  ``signs``: packed sign bits, by default ``model.initial_signs``.
+    ``model`` may also be a :class:`.bonds.BondStatistics` (its signs are used unless given)."""
+    from .bonds import BondStatistics, log_edges
+
+    bins = int(bins)
+    if bins < 2:
+        raise ValueError("'bins' counts the edges: at least 2")
+    owned = not isinstance(model, BondStatistics)
+    stats = BondStatistics(model.ising_hamiltonian, model.initial_signs if signs is None else signs) if owned else model
+    try:
+        if not owned and signs is not None:
+            stats.set_signs(signs)
+        summary = stats.summary
+        if summary["bonds"] == 0:
+            raise ValueError("the model has no bonds")
+        hi = np.log(summary["max_abs"])
+        lo = max(hi - span, np.log(summary["min_abs"]))
+        if not lo < hi:
+            raise ValueError("all bonds have the same strength: there is nothing to bin")
+        normal, frustrated, _, _ = stats.histogram(log_edges(lo, hi, bins))
+    finally:
+        if owned:
+            stats.release()
+    log_bins = np.linspace(lo, hi, bins)
+    total = normal + frustrated
+    with np.errstate(divide="ignore", invalid="ignore"):
+        y = normal / total
+    y[total < min_count] = float("nan")
+    x = np.exp(0.5 * (log_bins[:-1] + log_bins[1:]))
+    return x, y, normal, frustrated
 
 
 def sparsify_component(exchange, is_frozen, reltol: float, anchor: int):

@@ -978,6 +978,64 @@ int asp_sa_last_launch(asp_sa_plan const *p, int *replicas_per_group, int *threa
 /* E(x) for `count` packed configurations (host in, host out). */
 int asp_sa_energy(asp_sa_plan *p, uint32_t count, uint64_t const *x, double *out_e);
 
+/* ------------------------------------------------------------------------- */
+/* Bond statistics (csrc/bond_stats.hip, specification ASP-BONDS-1,          */
+/* DESIGN.md 3.6): common.py:439-478, 940-960 and 963-1002 of the reference  */
+/* ------------------------------------------------------------------------- */
+
+/* A square CSR matrix J (K rows; the columns of a row unique, in any order; the diagonal and explicit
+ * zeros may be stored) and one sign bit per spin (bit i of word i / 64 set: s_i = +1) kept on the
+ * device.  A BOND is a stored entry with j != i and J_ij != 0 — (i, j) and (j, i) are two bonds — and
+ * it is FRUSTRATED iff (s_i == s_j) == (J_ij > 0), i.e. J_ij s_i s_j > 0.  Every result is an integer
+ * count, an extremum of bit patterns or a sorted copy: exact, whatever the launch geometry.
+ * Host pointers.  K = 0 and a matrix without bonds are valid and give zeros; an indptr that is not
+ * monotone, a column outside [0, K) and data that is not finite are ASP_ERR_INVALID, 2^30 spins or
+ * more ASP_ERR_TOO_LARGE.  (That the columns of a row are unique is the caller's promise.) */
+typedef struct asp_bonds asp_bonds;
+typedef struct asp_bonds_summary {
+  uint64_t num_spins, stored, bonds, frustrated, rows_with_bonds, strongest_frustrated;
+  double max_abs, min_abs;
+} asp_bonds_summary;
+/* stored: entries of the matrix; max_abs and min_abs over the bonds, 0 without bonds;
+ * strongest_frustrated: rows whose strongest bond is frustrated. */
+
+/* Uploads the matrix and the signs and runs the row pass. */
+int asp_bonds_create(uint64_t num_spins, int64_t const *indptr, int32_t const *indices,
+                     double const *data, uint64_t const *sign_words, asp_bonds **out);
+/* Other signs on the resident matrix: runs the row pass again. */
+int asp_bonds_set_signs(asp_bonds *b, uint64_t const *sign_words);
+int asp_bonds_get_summary(asp_bonds const *b, asp_bonds_summary *out);
+/* Per row (K entries each, any pointer may be NULL): the largest |J_ij| with j != i, or 0 without a
+ * bond (common.get_strongest_off_diag); the smallest column that attains it, or -1; whether that bond
+ * is frustrated.  The strongest bond is the one of largest MAGNITUDE (the reference's
+ * cluster_statistics takes the argmax of the signed matrix). */
+int asp_bonds_rows(asp_bonds const *b, double *strongest, int32_t *strongest_col,
+                   uint8_t *strongest_frustrated);
+/* Bonds per bin of |J|: edges[num_bins + 1] finite and strictly ascending, 1 <= num_bins <= 4096; bin
+ * k holds edges[k] <= |J| < edges[k + 1], the last bin also |J| == edges[num_bins] (np.histogram's
+ * rule).  normal[num_bins] and frustrated[num_bins]; *below and *above (either may be NULL) receive
+ * the bonds outside the edges. */
+int asp_bonds_histogram(asp_bonds const *b, uint32_t num_bins, double const *edges, uint64_t *normal,
+                        uint64_t *frustrated, uint64_t *below, uint64_t *above);
+/* |J| of all bonds in descending order, bit for bit np.sort(np.abs(bonds))[::-1]; fails with
+ * ASP_ERR_INVALID when capacity < summary.bonds. */
+int asp_bonds_magnitudes(asp_bonds const *b, uint64_t capacity, double *out);
+void asp_bonds_destroy(asp_bonds *b);
+/* Device time (ms, HIP events) of the kernels of this thread's last asp_bonds_create,
+ * asp_bonds_set_signs, asp_bonds_histogram, asp_bonds_magnitudes or asp_sector_bonds_create call;
+ * copies between host and device are not in it. */
+float asp_bonds_last_ms(void);
+
+/* The same handle for the Ising model of a whole symmetry sector, built on the device from DEVICE
+ * pointers: the ELL arrays of asp_sector_rows (slot k of row i at [k * n + i]) and the ground state.
+ *   H_ij = sum, in slot order from +0.0, of val over the slots of row i with idx == j (the unused
+ *          slots (i, 0.0) fall out with the diagonal); H_ji likewise from row j;
+ *   M_ij = (H_ij |psi_j|) |psi_i|,  J_ij = 0.5 (M_ij + M_ji),  every operation rounded on its own;
+ * row i holds the distinct targets j != i of its slots with J_ij != 0, in the order of their first
+ * slot; s_i = +1 iff psi_i >= 0.  The input arrays are only read and are not needed afterwards. */
+int asp_sector_bonds_create(uint64_t n, uint32_t width, uint32_t const *idx_dev, double const *val_dev,
+                            double const *psi_dev, asp_bonds **out);
+
 #ifdef __cplusplus
 }
 #endif
