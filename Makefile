@@ -16,7 +16,7 @@ DATA ?= physical_systems/data-large
 OUT ?= experiments
 
 .PHONY: all build test test-gpu bench small clusters kagome_36 pyrochlore_32 sk_32_1 noise quality_check \
-	couplings is_frustrated small_amplitude_overlaps
+	couplings is_frustrated small_amplitude_overlaps local_energy
 all: build
 
 build:
@@ -100,6 +100,19 @@ clusters:
 		--output $(OUT)/$(MODEL)/noise_$(NOISE)/cutoff_$(CUTOFF)/$(MODEL).csv$(JOBID) \
 		--order $(ORDER) --noise $(NOISE) --no-annealing --global-cutoff $(CUTOFF) \
 		--number-samples $(NUMBER_SAMPLES) --jobs $(JOBS)
+
+# `make local_energy MODEL=...`: local energies of the recovered signs on $(NUMBER_SAMPLES) samples drawn from
+# |psi|^2 (the reference's compute_local_energy, experiments/sampled_connected_components.py:324-359): every sample's
+# one-hop neighbourhood as a cluster, its signs from SIGNS = greedy | sa | exact at extension order $(ORDER), all
+# local energies in one device call.  EXTERNAL_FIELD=1 gives the models their boundary field.
+SIGNS ?= greedy
+EXTERNAL_FIELD ?=
+local_energy:
+	@mkdir -p $(OUT)/local_energy
+	$(PYTHON) -m annealing_sign_problem_amd.local_energy --model $(MODEL) --seed $(SEED) \
+		--number-samples $(NUMBER_SAMPLES) --sampled-power 2 --order $(ORDER) --global-cutoff $(CUTOFF) \
+		--signs $(SIGNS) --noise $(NOISE) $(if $(EXTERNAL_FIELD),--external-field) --jobs $(JOBS) \
+		--output $(OUT)/local_energy/$(MODEL)_order$(ORDER)_$(SIGNS)$(if $(EXTERNAL_FIELD),_field).csv
 
 # The reference's large targets (Makefile:101-141): greedy only, order $(ORDER), cutoff $(CUTOFF),
 # $(NUMBER_SAMPLES) sampled clusters (reference: 50000), on the model's own symmetry-adapted basis.

@@ -30,6 +30,7 @@ SOURCES = [
     "ising_elements.hip",
     "operator_apply.hip",
     "operator_field.hip",
+    "operator_local_energy.hip",
     "sector_basis.hip",
     "key_table.hip",
     "plain_basis.hip",

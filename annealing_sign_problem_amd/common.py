@@ -33,6 +33,8 @@ __all__ = [
     "compute_accuracy_and_overlap",
     "make_hamiltonian_extension",
     "extension_spins",
+    "local_energies",
+    "variational_energy",
     "sparsify_using_global_cutoff",
     "get_strongest_off_diag",
     "cluster_statistics",
@@ -484,6 +486,43 @@ def extension_spins(hamiltonian, spins) -> np.ndarray:
     if group is not None and getattr(group, "spin_inversion", 0) < 0:
         other = other[group.state_info(other)[2] > 0]
     return other
+
+
+def local_energies(hamiltonian, spins, signed_psi, rows=None):
+    """``(hphi, eloc, missing)`` of the state with the signed amplitudes ``signed_psi`` (any
+    normalisation) on the ascending unique states ``spins``, specification ASP-ELOC-1 (DESIGN.md
+    §3.7): ``hphi[r] = sum_s' H_ss' psi_s'`` over the connections of row r that stay inside
+    ``spins``, ``eloc[r] = hphi[r] / psi_r`` and the number of connections with a non-zero matrix
+    element that leave ``spins`` (they contribute nothing).  ``rows``: positions in ``spins``, any
+    order, repeats allowed; ``None``: every state.  Not in the reference, whose local energy
+    (experiments/sampled_connected_components.py:294-312) loops over the connections in Python;
+    this package's device operators only."""
+    if not _on_device(hamiltonian):
+        raise NotImplementedError(
+            "local energies need one of this package's device operators (operators.Operator with real "
+            "matrices); they are not implemented for foreign operator objects")
+    spins = np.asarray(spins, dtype=np.uint64)
+    if spins.ndim > 1:
+        spins = np.ascontiguousarray(spins[:, 0])
+    return hamiltonian.device().local_energy(spins, signed_psi, None, rows)
+
+
+def variational_energy(hamiltonian, spins, signed_psi) -> Tuple[float, int]:
+    """``(energy, missing_total)``: the Rayleigh quotient ``sum_r psi_r (H psi)_r / sum_r psi_r^2`` of
+    the state with the signed amplitudes ``signed_psi`` on ``spins``, from :func:`local_energies`
+    (``H`` restricted to ``spins``), and the number of connections that leave ``spins``.  Over a full
+    basis that number is 0 and the energy is ``Operator.expectation``."""
+    if not _on_device(hamiltonian):
+        raise NotImplementedError(
+            "the variational energy needs one of this package's device operators (operators.Operator with "
+            "real matrices); it is not implemented for foreign operator objects")
+    signed_psi = np.ascontiguousarray(signed_psi, dtype=np.float64)
+    spins = np.asarray(spins, dtype=np.uint64)
+    if spins.ndim > 1:
+        spins = np.ascontiguousarray(spins[:, 0])
+    # (no quotient per row: a state of amplitude zero is legal here)
+    hphi, _, missing = hamiltonian.device()._local_energy(spins, signed_psi, None, None, False)
+    return dot(signed_psi, hphi) / dot(signed_psi, signed_psi), int(missing.sum(dtype=np.int64))
 
 
 def get_strongest_off_diag(matrix) -> np.ndarray:

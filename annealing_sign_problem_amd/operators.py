@@ -523,6 +523,48 @@ class DeviceOperator:
                                                 _lib.ptr(out), ctypes.byref(unresolved)))
         return out[:k], int(unresolved.value)
 
+    def local_energy(self, keys, phi, offsets=None, rows=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Local energies of the signed amplitudes ``phi`` (any normalisation) over the table
+        ``keys``, specification ASP-ELOC-1: ``(hphi f64[N], eloc f64[N],
+        missing u32[N])`` with ``hphi[r] = sum(coeff * phi[p])`` over the connections of row r
+        whose target is ``keys[p]`` of the row's own segment, added in connection order (the
+        diagonal first), ``eloc[r] = hphi[r] / phi[rows[r]]`` and the number of connections with
+        a non-zero coefficient that leave the segment.  ``offsets`` (u64[S + 1], from 0,
+        non-decreasing) cuts the table into segments, each ascending and unique, each with signs
+        of its own; ``None``: one segment.  ``rows``: indices into the table, any order, repeats
+        allowed; ``None``: every entry."""
+        return self._local_energy(keys, phi, offsets, rows, True)
+
+    def _local_energy(self, keys, phi, offsets, rows, want_eloc: bool):
+        """:meth:`local_energy`; without ``want_eloc`` the quotient is not asked for (``eloc`` is
+        ``None``), so that rows of amplitude zero are legal."""
+        _lib = self._lib_module
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        if keys.ndim != 1 or phi.shape != keys.shape:
+            raise ValueError("phi and keys differ in length")
+        t = keys.shape[0]
+        if offsets is None:
+            offsets = np.array([0, t], dtype=np.uint64)
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            if offsets.ndim != 1 or offsets.shape[0] < 1 or int(offsets[-1]) != t:
+                raise ValueError("offsets should run from 0 to the number of keys")
+        if rows is None:
+            rows = np.arange(t, dtype=np.uint64)
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.uint64)
+            if rows.ndim != 1:
+                raise ValueError("rows should be one-dimensional")
+        n = rows.shape[0]
+        hphi = np.zeros(max(n, 1), dtype=np.float64)
+        eloc = np.zeros(max(n, 1), dtype=np.float64) if want_eloc else None
+        missing = np.zeros(max(n, 1), dtype=np.uint32)
+        _lib.check(self._lib.asp_operator_local_energy(
+            self._handle, offsets.shape[0] - 1, _lib.ptr(offsets), _lib.ptr(keys), _lib.ptr(phi), n,
+            _lib.ptr(rows), _lib.ptr(hphi), _lib.ptr(eloc), _lib.ptr(missing)))
+        return hphi[:n], (eloc[:n] if want_eloc else None), missing[:n]
+
     def extend(self, keys) -> np.ndarray:
         """Sorted unique union of the targets of ``keys`` (their own states included; in a
         symmetry sector their representatives, without the orbits of norm 0)."""

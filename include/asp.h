@@ -313,8 +313,33 @@ int asp_operator_field(asp_operator const *op, uint64_t num_spins, uint64_t cons
                        uint64_t num_env, uint64_t const *env_keys, double const *env_psi, double scale,
                        double *field, uint64_t *unresolved /* may be NULL */);
 
+/* Local energies of signed amplitudes, specification ASP-ELOC-1:
+ *     E_loc(s) = sum_s' H_ss' phi_s' / phi_s
+ * for many small tables in one call.  num_segments tables lie concatenated in keys / phi
+ * [T = offsets[num_segments]]: segment g is [offsets[g], offsets[g + 1]), its keys ascending and
+ * unique, phi its signed amplitudes in any normalisation; segments may be empty and a state may sit
+ * in any number of them (each with its own amplitude).  rows[num_rows] are indices into the table,
+ * in any order, with repeats; the segment of a row is the one whose range holds rows[r].  For every
+ * row, over the entries asp_operator_apply returns for keys[rows[r]], in its order (the diagonal
+ * entry first; equal targets not merged):
+ *     acc = +0.0 ; lost = 0
+ *     target = keys[p], p in the row's segment:   acc = acc + (coeff * phi[p])
+ *     otherwise, and coeff != 0:                  ++lost  (contributes nothing)
+ *     hphi[r] = acc ; eloc[r] = acc / phi[rows[r]] ; missing[r] = lost
+ * every operation rounded on its own, the adds in that order.  Negating phi over a whole segment
+ * leaves eloc and negates hphi, bit for bit, wherever the sum is not zero (a sum that is exactly
+ * zero is +0.0 either way).  Host pointers; each of hphi, eloc and missing may be NULL.  ASP_ERR_INVALID before any device work and before any output is written for a null
+ * handle, null offsets with num_segments > 0, offsets[0] != 0 or decreasing offsets, null keys /
+ * phi with T > 0, a segment that is not ascending and unique, null rows with num_rows > 0,
+ * rows[r] >= T and, when eloc is wanted, a phi[rows[r]] that is zero, NaN or infinite; for a row
+ * key of norm 0 in a -1 sector as asp_operator_field.  ASP_ERR_TOO_LARGE for T >= 2^32 - 1 or
+ * num_rows >= 2^31 - 1.  num_rows = 0 runs nothing and needs no device. */
+int asp_operator_local_energy(asp_operator const *op, uint64_t num_segments, uint64_t const *offsets,
+                              uint64_t const *keys, double const *phi, uint64_t num_rows,
+                              uint64_t const *rows, double *hphi, double *eloc, uint32_t *missing);
+
 /* Device time (ms, HIP events, no host<->HBM copies) of this thread's last
- * asp_operator_apply / _ising / _extend / _field call. */
+ * asp_operator_apply / _ising / _extend / _field / _local_energy call. */
 float asp_operator_last_ms(void);
 
 /* ------------------------------------------------------------------------- */
