@@ -217,6 +217,8 @@ SIGNATURES = {
                                    c_void_p, ctypes.POINTER(c_u64)]),
     "asp_operator_ising_csr": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_u64, c_void_p, c_void_p,
                                        c_void_p, ctypes.POINTER(c_u64)]),
+    "asp_operator_ising_segments": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_u64, c_void_p,
+                                            c_void_p, c_void_p, ctypes.POINTER(c_u64)]),
     "asp_operator_extend": (c_int, [c_void_p, c_u64, c_void_p, c_u64, c_void_p,
                                     ctypes.POINTER(c_u64)]),
     "asp_operator_field": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_u64, c_void_p, c_void_p,

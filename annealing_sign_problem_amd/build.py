@@ -31,6 +31,7 @@ SOURCES = [
     "operator_apply.hip",
     "operator_field.hip",
     "operator_local_energy.hip",
+    "operator_ising_segments.hip",
     "sector_basis.hip",
     "key_table.hip",
     "plain_basis.hip",

@@ -23,6 +23,7 @@ from . import annealer as sa
 __all__ = [
     "IsingModel",
     "make_ising_model",
+    "make_ising_models",
     "reweight_ising_model",
     "solve_ising_model",
     "solve_ising_models",
@@ -32,6 +33,7 @@ __all__ = [
     "save_ground_state",
     "compute_accuracy_and_overlap",
     "make_hamiltonian_extension",
+    "make_hamiltonian_extensions",
     "extension_spins",
     "local_energies",
     "variational_energy",
@@ -195,23 +197,7 @@ def make_ising_model(
             "external_field=True needs one of this package's device operators (operators.Operator with "
             "real matrices); it is not implemented for foreign operator objects, nor by the reference")
 
-    spins = np.asarray(spins, dtype=np.uint64)
-    if not (spins.ndim == 1 and (spins.shape[0] < 2 or bool(np.all(spins[1:] > spins[:-1])))):
-        # (the pipeline's clusters and extensions arrive sorted and unique: no sort for them)
-        spins, first, multiplicity = np.unique(spins, return_index=True, return_counts=True, axis=0)
-        if np.any(multiplicity != 1):
-            warnings.warn("'spins' were not unique, are you sure this is what you want?")
-            if log_psi is not None:
-                log_psi = np.asarray(log_psi)[first]
-    basis_index = None
-    if log_psi is None:
-        if hasattr(log_psi_fn, "index_of"):  # (ground_state_to_log_coeff_fn's closure)
-            basis_index = log_psi_fn.index_of(spins)
-            log_psi = log_psi_fn.at_index(basis_index)
-        else:
-            log_psi = log_psi_fn(spins)
-    if spins.ndim > 1:
-        spins = np.ascontiguousarray(spins[:, 0])
+    spins, log_psi, basis_index = _cluster_states(spins, log_psi, log_psi_fn)
     n = spins.shape[0]
 
     psi, field = _cluster_amplitudes_and_field(quantum_hamiltonian, spins, log_psi, log_psi_fn, external_field)
@@ -240,6 +226,97 @@ def make_ising_model(
         ising_hamiltonian = sa.Hamiltonian(matrix, field)
     x0 = sa.signs_to_bits(np.sign(psi))
     return IsingModel(spins, quantum_hamiltonian, ising_hamiltonian, x0, basis_index)
+
+
+def make_ising_models(clusters, quantum_hamiltonian, log_psis=None, log_psi_fn=None, external_field: bool = False):
+    """``[make_ising_model(c, quantum_hamiltonian, log_psi=l, log_psi_fn=log_psi_fn,
+    external_field=external_field) for c, l in zip(clusters, log_psis)]`` (not in the reference) with
+    the couplings of ALL clusters built in one device call (``DeviceOperator.ising_csr_segments``,
+    ASP-ISING-SEG-1): the same models field by field — ``spins``, the exchange's CSR
+    arrays as bits, ``field``, ``initial_signs``, ``basis_index``.  Everything else is done per cluster
+    as there: sort and unique, the amplitudes and their normalisation, the ``index_of`` / ``at_index``
+    shortcut of the ground-state closure and, with ``external_field=True``, the boundary field.
+    ``log_psis``: one array per cluster, or ``None``.  Foreign operator objects, and operators whose
+    segmented call is refused with ASP_ERR_INVALID (one-directional matrix elements with duplicates),
+    take the loop."""
+    clusters = list(clusters)
+    log_psis = [None] * len(clusters) if log_psis is None else list(log_psis)
+    if len(log_psis) != len(clusters):
+        raise ValueError("'log_psis' should hold one array per cluster")
+
+    def loop():
+        return [make_ising_model(c, quantum_hamiltonian, log_psi=l, log_psi_fn=log_psi_fn,
+                                 external_field=external_field) for c, l in zip(clusters, log_psis)]
+
+    if not _on_device(quantum_hamiltonian) or not clusters:
+        return loop()
+    if log_psi_fn is None and any(l is None for l in log_psis):
+        raise ValueError("at least one of log_psi or log_psi_fn should be specified")
+    if external_field and log_psi_fn is None:
+        raise ValueError("log_psi_fn should be specified when external_field=True")
+    prepared = []
+    for spins, log_psi in zip(clusters, log_psis):
+        spins, log_psi, basis_index = _cluster_states(spins, log_psi, log_psi_fn)
+        psi, field = _cluster_amplitudes_and_field(quantum_hamiltonian, spins, log_psi, log_psi_fn, external_field)
+        prepared.append((spins, basis_index, psi, field))
+    offsets = np.zeros(len(prepared) + 1, dtype=np.uint64)
+    np.cumsum([p[0].shape[0] for p in prepared], out=offsets[1:])
+    try:
+        indptr, col, val = quantum_hamiltonian.device().ising_csr_segments(
+            np.concatenate([p[0] for p in prepared]), np.concatenate([p[2] for p in prepared]), offsets)
+    except _lib.AspError as error:
+        if error.code != -3:
+            raise
+        return loop()
+    models = []
+    for g, (spins, basis_index, psi, field) in enumerate(prepared):
+        first, last = int(offsets[g]), int(offsets[g + 1])
+        begin, end = int(indptr[first]), int(indptr[last])
+        # the global indptr rebased to the segment; the columns are local already
+        hamiltonian = sa.Hamiltonian.from_canonical_csr(indptr[first:last + 1] - begin, col[begin:end].copy(),
+                                                        val[begin:end].copy(), field)
+        models.append(IsingModel(spins, quantum_hamiltonian, hamiltonian, sa.signs_to_bits(np.sign(psi)),
+                                 basis_index))
+    return models
+
+
+def make_hamiltonian_extensions(models, log_psi_fn, external_field: bool = False):
+    """``[make_hamiltonian_extension(m, log_psi_fn, external_field) for m in models]`` (not in the
+    reference) with the couplings of all extensions built in one device call
+    (:func:`make_ising_models`); the models share one operator."""
+    models = list(models)
+    if not models:
+        return []
+    operator = models[0].quantum_hamiltonian
+    if any(m.quantum_hamiltonian is not operator for m in models):
+        return [make_hamiltonian_extension(m, log_psi_fn, external_field) for m in models]
+    extended = [extension_spins(operator, m.spins) for m in models]
+    return make_ising_models(extended, operator, log_psi_fn=log_psi_fn, external_field=external_field)
+
+
+def _cluster_states(spins, log_psi, log_psi_fn):
+    """``(spins, log_psi, basis_index)`` of a cluster as :func:`make_ising_model` takes it: the states
+    sorted and unique, their log-amplitudes (given, or from ``log_psi_fn``) and, when the closure looked
+    them up, their positions in the basis.  One place for :func:`make_ising_model` and
+    :func:`make_ising_models`."""
+    spins = np.asarray(spins, dtype=np.uint64)
+    if not (spins.ndim == 1 and (spins.shape[0] < 2 or bool(np.all(spins[1:] > spins[:-1])))):
+        # (the pipeline's clusters and extensions arrive sorted and unique: no sort for them)
+        spins, first, multiplicity = np.unique(spins, return_index=True, return_counts=True, axis=0)
+        if np.any(multiplicity != 1):
+            warnings.warn("'spins' were not unique, are you sure this is what you want?")
+            if log_psi is not None:
+                log_psi = np.asarray(log_psi)[first]
+    basis_index = None
+    if log_psi is None:
+        if hasattr(log_psi_fn, "index_of"):  # (ground_state_to_log_coeff_fn's closure)
+            basis_index = log_psi_fn.index_of(spins)
+            log_psi = log_psi_fn.at_index(basis_index)
+        else:
+            log_psi = log_psi_fn(spins)
+    if spins.ndim > 1:
+        spins = np.ascontiguousarray(spins[:, 0])
+    return spins, log_psi, basis_index
 
 
 def _cluster_amplitudes_and_field(hamiltonian, spins, log_psi, log_psi_fn, external_field: bool):

@@ -35,6 +35,7 @@ using asp::Bond;
 using asp::DeviceBuffer;
 using asp::find_key;
 using asp::mix64;
+using asp::Symmetrised;
 using asp::SymmetryArgs;
 
 constexpr int kThreads = 256;
@@ -691,26 +692,6 @@ int count_connections(const asp_operator *op, uint64_t n, const uint64_t *keys, 
   return ASP_OK;
 }
 
-// What the symmetrise pass leaves behind besides the entries: the source norms and the number of
-// sources outside the sector (norm 0), which the caller reads with the next size it copies back.
-struct Symmetrised {
-  DeviceBuffer<double> d_norms;
-  DeviceBuffer<unsigned long long> d_outside;
-  unsigned long long outside = 0;
-  // queues the copy of the counter (no-op for a plain basis); valid after the next synchronisation
-  int fetch(hipStream_t stream) {
-    if (!d_outside.ptr) return ASP_OK;
-    return d_outside.download(&outside, 1, stream);
-  }
-  // after that synchronisation: ASP_ERR_INVALID when a source lies outside the sector
-  int check() const {
-    if (outside == 0) return ASP_OK;
-    return asp::set_error(ASP_ERR_INVALID,
-                          "%llu states lie outside the symmetry sector (norm 0: an element of their "
-                          "stabiliser has character -1); they are not basis states", outside);
-  }
-};
-
 // After k_apply<true>: representatives and rescaled coefficients for a symmetry-adapted basis;
 // `extension`: targets of norm 0 become the "no state" value instead.  A source state outside the
 // sector (norm 0) makes the entry point fail with ASP_ERR_INVALID: Symmetrised::fetch / check.
@@ -877,10 +858,8 @@ int check_operator(const asp_operator *op) {
 // ---- for operator_field.hip (operator_internal.hpp) ----
 namespace asp {
 
-int connection_list(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
-                    hipStream_t stream) {
-  Symmetrised sym;
-  StreamFence fence(stream);
+int connection_list_queue(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
+                          Symmetrised *sym, hipStream_t stream) {
   ASP_TRY(count_connections(op, n, keys, &out->batch, stream));
   ASP_TRY(out->d_other.alloc(out->batch.total));
   ASP_TRY(out->d_coeffs.alloc(out->batch.total));
@@ -889,7 +868,15 @@ int connection_list(const asp_operator *op, uint64_t n, const uint64_t *keys, Co
                      op->d_bonds.ptr, op->num_bonds, out->batch.d_keys.ptr, n, out->batch.d_offsets.ptr,
                      nullptr, out->d_other.ptr, out->d_coeffs.ptr);
   ASP_HIP_TRY(hipGetLastError());
-  ASP_TRY(symmetrise_batch(op, n, out->batch, out->d_other.ptr, out->d_coeffs.ptr, &sym, false, stream));
+  return symmetrise_batch(op, n, out->batch, out->d_other.ptr, out->d_coeffs.ptr, sym, false, stream);
+}
+
+int connection_list(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
+                    hipStream_t stream) {
+  Symmetrised sym;
+  StreamFence fence(stream);
+  ASP_TRY(connection_list_queue(op, n, keys, out, &sym, stream));
+  if (n == 0) return ASP_OK;
   ASP_TRY(sym.fetch(stream));
   ASP_HIP_TRY(hipStreamSynchronize(stream));
   return sym.check();

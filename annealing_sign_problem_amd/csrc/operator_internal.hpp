@@ -1,4 +1,5 @@
-// Internals of asp_operator shared by operator_apply.hip, operator_field.hip and sector_basis.hip.
+// Internals of asp_operator shared by operator_apply.hip, operator_field.hip, operator_local_energy.hip,
+// operator_ising_segments.hip and sector_basis.hip.
 #pragma once
 
 #include <cstdint>
@@ -67,6 +68,26 @@ struct ConnectionList {
   DeviceBuffer<double> d_coeffs;
 };
 
+// What the symmetrise pass leaves behind besides the entries: the source norms and the number of
+// sources outside the sector (norm 0), which the caller reads with the next size it copies back.
+struct Symmetrised {
+  DeviceBuffer<double> d_norms;
+  DeviceBuffer<unsigned long long> d_outside;
+  unsigned long long outside = 0;
+  // queues the copy of the counter (no-op for a plain basis); valid after the next synchronisation
+  int fetch(hipStream_t stream) {
+    if (!d_outside.ptr) return ASP_OK;
+    return d_outside.download(&outside, 1, stream);
+  }
+  // after that synchronisation: ASP_ERR_INVALID when a source lies outside the sector
+  int check() const {
+    if (outside == 0) return ASP_OK;
+    return set_error(ASP_ERR_INVALID,
+                     "%llu states lie outside the symmetry sector (norm 0: an element of their "
+                     "stabiliser has character -1); they are not basis states", outside);
+  }
+};
+
 }  // namespace asp
 
 struct asp_operator;
@@ -77,6 +98,11 @@ namespace asp {
 // sector (norm 0).  Declare a StreamFence after `out`.
 int connection_list(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
                     hipStream_t stream);
+// connection_list up to its last wait: the entries are queued on `stream`, and the sources outside the
+// sector are counted in `sym` (Symmetrised::fetch, a synchronisation, then check).  The caller holds a
+// StreamFence declared after `out` and `sym`.
+int connection_list_queue(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
+                          Symmetrised *sym, hipStream_t stream);
 // Clears slots[slots_n] (a power of two >= 2n) and inserts the n device keys.
 int key_hash_build(const uint64_t *d_keys, uint64_t n, unsigned long long *d_slots, uint64_t slots_n,
                    hipStream_t stream);

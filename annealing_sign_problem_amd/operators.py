@@ -491,6 +491,40 @@ class DeviceOperator:
         z = int(nnz.value)
         return indptr, col[:z], val[:z]  # (views: see ising)
 
+    def ising_csr_segments(self, keys, psi, offsets) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """:meth:`ising_csr` of many clusters in one call, specification ASP-ISING-SEG-1 (DESIGN.md
+        §3.8): ``offsets`` (u64[S + 1], from 0, non-decreasing) cuts ``keys`` / ``psi`` into segments,
+        each ascending and unique with amplitudes normalised over the segment.  ``(indptr i64[T + 1],
+        col i32, val f64)``: ONE global ``indptr`` from 0, columns local to their segment; segment
+        ``g``'s rows, rebased by ``indptr[offsets[g]]``, are ``ising_csr`` of its keys bit for bit."""
+        import ctypes
+
+        _lib = self._lib_module
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        psi = np.ascontiguousarray(psi, dtype=np.float64)
+        if keys.ndim != 1 or psi.shape != keys.shape:
+            raise ValueError("psi and keys differ in length")
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        t = keys.shape[0]
+        if offsets.ndim != 1 or offsets.shape[0] < 1 or int(offsets[-1]) != t:
+            raise ValueError("offsets should run from 0 to the number of keys")
+        capacity = t * self.max_connections
+        nnz = ctypes.c_uint64(0)
+        indptr = np.zeros(t + 1, dtype=np.int64)
+        while True:
+            col = np.empty(max(capacity, 1), dtype=np.int32)
+            val = np.empty(max(capacity, 1), dtype=np.float64)
+            rc = self._lib.asp_operator_ising_segments(
+                self._handle, offsets.shape[0] - 1, _lib.ptr(offsets), _lib.ptr(keys), _lib.ptr(psi), capacity,
+                _lib.ptr(indptr), _lib.ptr(col), _lib.ptr(val), ctypes.byref(nnz))
+            if rc != 0 and int(nnz.value) > capacity:
+                capacity = int(nnz.value)
+                continue
+            _lib.check(rc)
+            break
+        z = int(nnz.value)
+        return indptr, col[:z], val[:z]  # (views: see ising)
+
     def field(self, keys, psi, env_keys, env_psi, scale: float = 2.0) -> Tuple[np.ndarray, int]:
         """Boundary field of the cluster ``keys`` (ascending, unique; amplitudes ``psi``) in the
         environment ``env_keys`` (ascending, unique; signed amplitudes ``env_psi`` in the same

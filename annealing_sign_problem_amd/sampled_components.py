@@ -219,7 +219,7 @@ def process_cluster(cluster, hamiltonian, ground_state, noisy_ground_state, nois
 
 def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, noisy_ground_state,
                    noisy_log_coeff_fn, order: int, global_cutoff: float, jobs: int = 1,
-                   greedy_batch: bool = False, external_field: bool = False):
+                   greedy_batch: bool = False, external_field: bool = False, build_batch: bool = False):
     """First half of :func:`process_clusters_batched`: the models of every order of every cluster,
     each with its greedy result — a list of ``(cluster index, model, exact_signs, weights, result
     so far)`` in cluster order.  The models of a cluster do not depend on its solutions (the
@@ -227,9 +227,45 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
     built before anything is annealed.  ``greedy_batch``: the models are built first (on the
     ``jobs`` threads) and ALL of them are then solved by one ``greedy_solve_batch`` call instead
     of one ``greedy_solve`` each; the results are the same.  ``external_field``: as in
-    :func:`process_cluster`."""
+    :func:`process_cluster`.  ``build_batch``: the staging runs level by level — for order i all
+    clusters are extended (per cluster), the couplings of ALL their models are built in one segmented
+    device call (``common.make_ising_models``) and the models are sparsified (per
+    cluster) — instead of cluster by cluster; the models and the results are the same."""
     basis = hamiltonian.basis
     field = {"external_field": True} if external_field else {}
+
+    def each(function, items):
+        """``[function(x) for x in items]`` on the ``jobs`` threads."""
+        if jobs > 1 and len(items) > 1:
+            from concurrent.futures import ThreadPoolExecutor
+
+            with ThreadPoolExecutor(max_workers=jobs) as pool:
+                return list(pool.map(function, items))
+        return [function(x) for x in items]
+
+    def result_of(cluster, h, exact_signs, weights):
+        if greedy_batch:  # (the greedy columns are filled in below)
+            r = OptimizationResult(h.size, float("nan"), float("nan"), float("nan"), float("nan"), float("nan"))
+        else:
+            r = solve_and_test_model(h, cluster, exact_signs, weights, annealing=False)
+        r.amplitude_overlap = amplitude_overlap(h.spins, ground_state, noisy_ground_state, basis, h.basis_index)
+        return r
+
+    def stage_levels():
+        """:func:`stage` of every cluster, one order of all clusters at a time."""
+        count = len(clusters)
+        levels = []
+        models = common.make_ising_models(clusters, hamiltonian, log_psi_fn=noisy_log_coeff_fn, **field)
+        truth = each(lambda c: exact_signs_and_weights(clusters[c], models[c], ground_state, basis), range(count))
+        for i in range(order + 1):
+            if i > 0:
+                models = common.make_hamiltonian_extensions(models, noisy_log_coeff_fn, **field)
+                models = each(lambda c: common.sparsify_using_global_cutoff(models[c], global_cutoff, clusters[c]),
+                              range(count))
+            levels.append(list(zip(models, each(lambda c: result_of(clusters[c], models[c], *truth[c]),
+                                                range(count)))))
+        return [(c, levels[i][c][0], truth[c][0], truth[c][1], levels[i][c][1])
+                for c in range(count) for i in range(order + 1)]
 
     def stage(item):
         """Models of every order of one cluster, each with its greedy result."""
@@ -243,14 +279,7 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
             else:
                 h = common.make_hamiltonian_extension(h, noisy_log_coeff_fn, **field)
                 h = common.sparsify_using_global_cutoff(h, global_cutoff, cluster)
-            if greedy_batch:  # (the greedy columns are filled in below)
-                r = OptimizationResult(h.size, float("nan"), float("nan"), float("nan"), float("nan"),
-                                       float("nan"))
-            else:
-                r = solve_and_test_model(h, cluster, exact_signs, weights, annealing=False)
-            r.amplitude_overlap = amplitude_overlap(h.spins, ground_state, noisy_ground_state, basis,
-                                                    h.basis_index)
-            out.append((index, h, exact_signs, weights, r))
+            out.append((index, h, exact_signs, weights, result_of(cluster, h, exact_signs, weights)))
         return out
 
     def solved(staged):
@@ -262,21 +291,24 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
                                                                                           weights)
         return staged
 
+    if build_batch and len(clusters) > 0:
+        return solved(stage_levels())
     # the builds of different clusters are independent and their C calls release the GIL: --jobs
     # host threads keep several in flight on the GPU (own streams); order of the list = cluster
     # order either way
-    if jobs > 1 and len(clusters) > 1:
-        from concurrent.futures import ThreadPoolExecutor
-
-        with ThreadPoolExecutor(max_workers=jobs) as pool:
-            return solved([entry for part in pool.map(stage, enumerate(clusters)) for entry in part])
-    return solved([entry for item in enumerate(clusters) for entry in stage(item)])
+    return solved([entry for part in each(stage, list(enumerate(clusters))) for entry in part])
 
 
 def external_field_of(args) -> dict:
     """--external-field as the ``external_field`` keyword of the model-building functions; empty without
     it, so that every call is the one it was."""
     return {"external_field": True} if getattr(args, "external_field", False) else {}
+
+
+def build_batch_of(args) -> dict:
+    """--build-batch as the ``build_batch`` keyword of :func:`stage_clusters` and
+    :func:`process_clusters_batched`; empty without it, so that every call is the one it was."""
+    return {"build_batch": True} if getattr(args, "build_batch", False) else {}
 
 
 def early_stop_of(args) -> dict:
@@ -325,15 +357,18 @@ def process_clusters_batched(clusters: Sequence[np.ndarray], hamiltonian, ground
                              sweep_order: Optional[str] = None,
                              greedy_batch: bool = False,
                              early_stop: Optional[dict] = None,
-                             external_field: bool = False) -> List[List[OptimizationResult]]:
+                             external_field: bool = False,
+                             build_batch: bool = False) -> List[List[OptimizationResult]]:
     """``[process_cluster(c, ...) for c in clusters]`` with the annealing of ALL models — every
     cluster at every order — in one batched device call (:func:`stage_clusters`, then
     :func:`anneal_staged`); the results are identical to the per-cluster loop.  ``early_stop``: the
     extra keywords of :func:`common.solve_ising_models` (early stopping or the annealing method), as in
-    :func:`anneal_staged`.  ``external_field``: as in :func:`process_cluster`."""
+    :func:`anneal_staged`.  ``external_field``: as in :func:`process_cluster`.  ``build_batch``: as in
+    :func:`stage_clusters`."""
     staged = stage_clusters(clusters, hamiltonian, ground_state, noisy_ground_state, noisy_log_coeff_fn,
                             order, global_cutoff, jobs, **({"greedy_batch": True} if greedy_batch else {}),
-                            **({"external_field": True} if external_field else {}))
+                            **({"external_field": True} if external_field else {}),
+                            **({"build_batch": True} if build_batch else {}))
     return anneal_staged(staged, clusters, annealing, sweep_order, **({"early_stop": early_stop} if early_stop else {}))
 
 
@@ -391,6 +426,11 @@ def parse_command_line(argv=None):
                         help="solve the greedy models of a round of --batch clusters with ONE batched "
                              "call (greedy_solve_batch) instead of one greedy_solve per model; the "
                              "output is the same")
+    parser.add_argument("--build-batch", default=False, action="store_true",
+                        help="build the couplings of a round of --batch clusters with ONE segmented device "
+                             "call per order (make_ising_models, asp_operator_ising_segments) instead of one "
+                             "call per cluster; needs --batch > 1 and --annealing or --greedy-batch; the "
+                             "output is the same")
     parser.add_argument("--greedy-tree", choices=("host", "device"), default=None,
                         help="where the greedy solver builds its strongest-coupling tree (default: "
                              "$ASP_GREEDY_TREE or host); the output is the same")
@@ -416,6 +456,8 @@ def parse_command_line(argv=None):
         if not args.annealing or args.batch <= 1:
             parser.error("--anneal-method {} needs --annealing and --batch > 1 (it runs batched "
                          "segments)".format(args.anneal_method))
+    if args.build_batch and (args.batch <= 1 or not (args.annealing or args.greedy_batch)):
+        parser.error("--build-batch needs --batch > 1 and --annealing or --greedy-batch (it builds a round at once)")
     return args
 
 
@@ -589,7 +631,7 @@ def _worker_chunk(indices):
                                          w["log_coeff_fn"], args.order, args.global_cutoff, args.annealing,
                                          jobs=args.jobs, sweep_order=args.sweep_order,
                                          **({"greedy_batch": True} if args.greedy_batch else {}),
-                                         **early_stop_of(args), **external_field_of(args))
+                                         **early_stop_of(args), **external_field_of(args), **build_batch_of(args))
         return report([",".join(r.to_csv_str() for r in columns) for columns in chunk])
 
     def work(cluster):
@@ -799,7 +841,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                                              ground_state, noisy_ground_state, noisy_log_coeff_fn,
                                              args.order, args.global_cutoff, args.annealing,
                                              jobs=args.jobs, sweep_order=args.sweep_order, **greedy_batch,
-                                             **early_stop_of(args), **external_field_of(args))
+                                             **early_stop_of(args), **external_field_of(args), **build_batch_of(args))
             lines += [",".join(r.to_csv_str() for r in columns) for columns in chunk]
         return lines
 
@@ -830,7 +872,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
             def stage(some):
                 return stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
                                       noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
-                                      **greedy_batch, **external_field_of(args))
+                                      **greedy_batch, **external_field_of(args), **build_batch_of(args))
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(stage, my_share(0)) if rounds else None
@@ -884,7 +926,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                 some = list(itertools.islice(clusters, step))
                 return some, stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
                                             noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
-                                            **greedy_batch, **external_field_of(args))
+                                            **greedy_batch, **external_field_of(args), **build_batch_of(args))
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(next_round)

@@ -284,6 +284,34 @@ int asp_operator_ising(asp_operator const *op, uint64_t num_spins, uint64_t cons
 int asp_operator_ising_csr(asp_operator const *op, uint64_t num_spins, uint64_t const *keys,
                            double const *psi, uint64_t capacity, int64_t *indptr, int32_t *col,
                            double *val, uint64_t *nnz);
+/* Many clusters' coupling build in one call, specification ASP-ISING-SEG-1.  The
+ * segment conventions are ASP-ELOC-1's (asp_operator_local_energy below): num_segments tables lie
+ * concatenated in keys / psi [T = offsets[num_segments]], segment g is [offsets[g], offsets[g + 1]),
+ * its keys ascending and unique, psi its amplitudes ALREADY normalised by the caller over that
+ * segment (the library does not touch the normalisation); segments may be empty and a state may sit
+ * in any number of them.  The law: for every segment g with n_g keys let (ip, c, v) be what
+ *     asp_operator_ising_csr(op, n_g, keys + offsets[g], psi + offsets[g], ...)
+ * returns; then indptr[offsets[g] + i] - indptr[offsets[g]] == ip[i] for i = 0 ... n_g, and the
+ * entries indptr[offsets[g]] ... indptr[offsets[g + 1]] of col and val equal c and v, val bit for
+ * bit.  indptr is ONE global i64[T + 1] starting at 0; col is SEGMENT-LOCAL (the position within the
+ * segment's keys).  Both variants of asp_operator_ising are covered: the pair-fused pass for
+ * asp_operator_unique_targets(op) == 1, and the duplicate-keeping one otherwise (duplicates summed
+ * in connection order from 0, 0.5 * (Mhat_rj + Mhat_jr), pruned iff that sum is 0).  *nnz receives
+ * the total.  Host pointers.
+ * Before any device work and before any output is written: ASP_ERR_INVALID for a null handle, a
+ * null nnz, null offsets with num_segments > 0, offsets[0] != 0 or decreasing offsets, null keys /
+ * psi with T > 0 and a segment that is not ascending and unique (the message names the segment and
+ * the index within it); ASP_ERR_TOO_LARGE for T >= 2^31 - 1 and for the LDS condition of
+ * asp_operator_ising.  capacity == 0 with indptr, col and val all NULL is a sizing call; *nnz >
+ * capacity or a missing output pointer gives ASP_ERR_INVALID with *nnz set and no output written.
+ * A key of norm 0 in a -1 sector gives ASP_ERR_INVALID as in asp_operator_ising; a coupling without
+ * its mirror in the duplicate variant gives ASP_ERR_INVALID, the message naming the first such
+ * segment.  T == 0: *nnz = 0, indptr[0] = 0 when indptr is given, and no device is needed.  The
+ * number of launches and of host synchronisations (two, or three in the duplicate variant) does
+ * not depend on num_segments. */
+int asp_operator_ising_segments(asp_operator const *op, uint64_t num_segments, uint64_t const *offsets,
+                                uint64_t const *keys, double const *psi, uint64_t capacity,
+                                int64_t *indptr, int32_t *col, double *val, uint64_t *nnz);
 
 /* make_hamiltonian_extension's state set (common.py:516-522): the sorted unique
  * union of every key's targets (its own diagonal entry included).  *count receives
@@ -339,7 +367,7 @@ int asp_operator_local_energy(asp_operator const *op, uint64_t num_segments, uin
                               uint64_t const *rows, double *hphi, double *eloc, uint32_t *missing);
 
 /* Device time (ms, HIP events, no host<->HBM copies) of this thread's last
- * asp_operator_apply / _ising / _extend / _field / _local_energy call. */
+ * asp_operator_apply / _ising / _ising_segments / _extend / _field / _local_energy call. */
 float asp_operator_last_ms(void);
 
 /* ------------------------------------------------------------------------- */
