@@ -120,6 +120,29 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
   return v;
 }
 
+// The same sum modulo 2^64 with the total in lane 63 ONLY (the other lanes end with partial sums),
+// by data-parallel-primitive moves between registers: no LDS round trip.  Shifts by 1, 2, 4 and 8
+// inside every row of 16 lanes leave the row's sum in its last lane (a lane the shift has no source
+// for adds the `old` operand, 0); row_bcast 15 adds that lane to rows 1 and 3, row_bcast 31 adds lane
+// 31 to rows 2 and 3.  Every lane of the wavefront must be active.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long dpp_add_u64(unsigned long long v) {
+  const uint32_t lo = static_cast<uint32_t>(
+      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<uint32_t>(v)), CTRL, ROW_MASK, 0xF, false));
+  const uint32_t hi = static_cast<uint32_t>(
+      __builtin_amdgcn_update_dpp(0, static_cast<int>(static_cast<uint32_t>(v >> 32)), CTRL, ROW_MASK, 0xF, false));
+  return v + ((static_cast<unsigned long long>(hi) << 32) | lo);
+}
+__device__ __forceinline__ unsigned long long wave_sum_lane63_u64(unsigned long long v) {
+  v = dpp_add_u64<0x111, 0xF>(v);  // row_shr:1
+  v = dpp_add_u64<0x112, 0xF>(v);  // row_shr:2
+  v = dpp_add_u64<0x114, 0xF>(v);  // row_shr:4
+  v = dpp_add_u64<0x118, 0xF>(v);  // row_shr:8
+  v = dpp_add_u64<0x142, 0xA>(v);  // row_bcast:15 into rows 1 and 3
+  v = dpp_add_u64<0x143, 0xC>(v);  // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
 // Butterfly sum over the 64 lanes; every lane ends with the balanced-tree total
 // ((v0+v1)+(v2+v3))+... (f64 addition commutes, so all lanes agree bitwise).
 __device__ __forceinline__ double wave_tree_sum_f64(double v) {
@@ -898,18 +921,41 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     }
 
     // ---- exact (integer) reduction of the sweep's energy change ----
+    // Sums between registers with the totals in lane 63, and only in a wavefront some lane of which
+    // accepted a flip in this sweep: in every other one each lane holds 0 flips and an energy
+    // change of 0 (kLeanBook: q_acc = visits * 0x4338000000000000 exactly, a proposal that is not
+    // accepted adds the bare constant), and nothing would be added below.  The flip counts travel two
+    // to a 64-bit sum: a lane accepts at most one flip per block, so the low count's total stays
+    // below 64 * num_blocks < 2^32 and never carries into the high one.
+    {
+      uint32_t any = 0;
 #pragma unroll
-    for (int m = 0; m < M; ++m) {
-      // kLeanBook: the visits' constants off, modulo 2^64 (the true sum fits: the plan's S)
-      const long long v = wave_sum_i64(static_cast<long long>(
-          kLeanBook ? q_acc[m] - visits * 0x4338000000000000ull : q_acc[m]));
-      const long long n = wave_sum_i64(static_cast<long long>(n_acc[m]));
-      if (lane == 0 && n != 0) {
-        atomicAdd(reinterpret_cast<unsigned long long *>(&delta[m]),
-                  static_cast<unsigned long long>(v));
-        atomicAdd(reinterpret_cast<unsigned long long *>(&book[16 + m]),
-                  static_cast<unsigned long long>(n));
-        if (cache_available) atomicAdd(&cache_ctl[0], static_cast<uint32_t>(n));
+      for (int m = 0; m < M; ++m) any |= n_acc[m];
+      if (__ballot(any != 0) != 0ull) {
+#pragma unroll
+        for (int m0 = 0; m0 < M; m0 += 2) {
+          unsigned long long v[2] = {0, 0};
+#pragma unroll
+          for (int j = 0; j < 2 && m0 + j < M; ++j) {
+            // kLeanBook: the visits' constants off, modulo 2^64 (the true sum fits: the plan's S)
+            v[j] = wave_sum_lane63_u64(
+                kLeanBook ? q_acc[m0 + j] - visits * 0x4338000000000000ull : q_acc[m0 + j]);
+          }
+          const unsigned long long n2 = wave_sum_lane63_u64(
+              n_acc[m0] | (m0 + 1 < M ? static_cast<unsigned long long>(n_acc[m0 + 1 < M ? m0 + 1 : m0]) << 32 : 0ull));
+          if (lane == 63) {
+#pragma unroll
+            for (int j = 0; j < 2 && m0 + j < M; ++j) {
+              const uint32_t n = static_cast<uint32_t>(n2 >> (32 * j));
+              if (n != 0) {
+                atomicAdd(reinterpret_cast<unsigned long long *>(&delta[m0 + j]), v[j]);
+                atomicAdd(reinterpret_cast<unsigned long long *>(&book[16 + m0 + j]),
+                          static_cast<unsigned long long>(n));
+                if (cache_available) atomicAdd(&cache_ctl[0], n);
+              }
+            }
+          }
+        }
       }
     }
     __syncthreads();
