@@ -1718,54 +1718,34 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
   }
 }
 
+// The four argument structs of a single problem's launch: the closed call and a segment of a handle
+// (asp_sa_chains_advance, order 1), a LADDER segment (asp_sa_chains_advance_ladder), each with or without
+// the per-sweep trace.
 template <bool TRACE>
 using ShuffledArgsOf = std::conditional_t<TRACE, ShuffledTraceArgs, ShuffledArgs>;
 template <bool TRACE>
-using ShuffledKernelOf = void (*)(ShuffledArgsOf<TRACE>);
-using ShuffledKernel = ShuffledKernelOf<false>;
-using ShuffledTraceKernel = ShuffledKernelOf<true>;
-
-template <int M, int LAYOUT, int TEAMS, bool PK = false, bool TRACE = false>
-__global__ __launch_bounds__(512) void k_sa_sweep_shuffled(ShuffledArgsOf<TRACE> a) {
-  shuffled_sweep_body<M, LAYOUT, TEAMS, PK, TRACE>(a, blockIdx.x);
-}
-
-// One ladder segment of a handle (asp_sa_chains_advance_ladder, order 1): every layout, group size and
-// lane packing of k_sa_sweep_shuffled, one team.
-template <bool TRACE>
 using ShuffledLadderArgs = ShuffledLadderArgsOf<ShuffledArgsOf<TRACE>>;
-template <bool TRACE>
-using ShuffledLadderKernelOf = void (*)(ShuffledLadderArgs<TRACE>);
-template <int M, int LAYOUT, bool PK = false, bool TRACE = false>
-__global__ __launch_bounds__(512) void k_sa_sweep_shuffled_ladder(ShuffledLadderArgs<TRACE> a) {
-  shuffled_sweep_body<M, LAYOUT, 1, PK, TRACE>(a, blockIdx.x);
+template <typename Args>
+inline constexpr bool kTraceArgs = std::is_base_of_v<ShuffledTraceArgs, Args>;
+
+template <int M, int LAYOUT, int TEAMS, bool PK, typename Args>
+__global__ __launch_bounds__(512) void k_sa_sweep_shuffled(Args a) {
+  shuffled_sweep_body<M, LAYOUT, TEAMS, PK, kTraceArgs<Args>>(a, blockIdx.x);
 }
 
 // Many problems in one launch: workgroup -> (problem, workgroup of the problem) through a slot
 // table, the problem's arguments through a descriptor table (csrc/sa_sweep.hip: k_sa_sweep_batch).
+// Args = ShuffledArgs, or ShuffledLadderBatchArgs for many LADDER segments
+// (asp_sa_chains_advance_ladder_batch, order 1): descriptors that carry every problem's per-chain betas.
+// One team; every chain is the one k_sa_sweep_shuffled advances: the body is the same.
 struct ShuffledSlot {
   uint32_t problem, group;
 };
-template <int M, int LAYOUT, bool PK = false>
-__global__ __launch_bounds__(512) void k_sa_sweep_shuffled_batch(const ShuffledArgs *problems,
-                                                                 const ShuffledSlot *slots) {
-  using ConstArgs = const ShuffledArgs __attribute__((address_space(4)));
-  const ShuffledSlot slot = slots[blockIdx.x];
-  if (slot.problem == 0xFFFFFFFFu) return;  // (padding of the XCD-aware slot table)
-  ConstArgs *a = reinterpret_cast<ConstArgs *>(
-      reinterpret_cast<uintptr_t>(problems + __builtin_amdgcn_readfirstlane(slot.problem)));
-  shuffled_sweep_body<M, LAYOUT, 1, PK, false>(*a, __builtin_amdgcn_readfirstlane(slot.group));
-}
-
-// Many LADDER segments in one launch (asp_sa_chains_advance_ladder_batch, order 1): the same slot table
-// over descriptors that carry every problem's per-chain betas (ShuffledLadderArgsOf), one team.  Every
-// chain is the one k_sa_sweep_shuffled_ladder advances: the body is the same.
 using ShuffledLadderBatchArgs = ShuffledLadderArgsOf<ShuffledArgs>;
-template <int M, int LAYOUT, bool PK = false>
-__global__ __launch_bounds__(512) void k_sa_sweep_shuffled_ladder_batch(const ShuffledLadderBatchArgs *problems,
-                                                                        const ShuffledSlot *slots) {
-  using ConstArgs = const ShuffledLadderBatchArgs __attribute__((address_space(4)));
-  static_assert(kLadderArgs<ShuffledLadderBatchArgs __attribute__((address_space(4)))>,
+template <int M, int LAYOUT, bool PK, typename Args>
+__global__ __launch_bounds__(512) void k_sa_sweep_shuffled_batch(const Args *problems, const ShuffledSlot *slots) {
+  using ConstArgs = const Args __attribute__((address_space(4)));
+  static_assert(kLadderArgs<Args __attribute__((address_space(4)))> == kLadderArgs<Args>,
                 "the body must see the descriptor as ladder arguments through the address space too");
   const ShuffledSlot slot = slots[blockIdx.x];
   if (slot.problem == 0xFFFFFFFFu) return;  // (padding of the XCD-aware slot table)
@@ -1778,13 +1758,11 @@ __global__ __launch_bounds__(512) void k_sa_sweep_shuffled_ladder_batch(const Sh
 // carry a chain in between two chunks: ShuffledArgs::state, [groups][K] with bit j of entry i = spin i
 // of chain g * m + j is -1 — a byte per spin, or kGlobal's 32-bit word (T).  The handle keeps every
 // chain packed in original order (bit = +1), whatever m and layout the launcher picks per segment.
-// in: a workgroup column per group, threads over the spins; the chains padding the last group start
-// with every spin up.
+// in: a workgroup column (blockIdx.y) per group g, threads over the spins; the chains padding the last
+// group start with every spin up.
 template <typename T>
-__global__ __launch_bounds__(256) void k_chains_state_in(const uint64_t *__restrict__ x, uint32_t words,
-                                                        uint32_t num_spins, uint32_t chains, uint32_t m,
-                                                        T *__restrict__ state) {
-  const uint32_t g = blockIdx.x;
+__device__ __forceinline__ void chains_state_in(const uint64_t *__restrict__ x, uint32_t words, uint32_t num_spins,
+                                                uint32_t chains, uint32_t m, T *__restrict__ state, uint32_t g) {
   for (uint32_t i = blockIdx.y * blockDim.x + threadIdx.x; i < num_spins; i += gridDim.y * blockDim.x) {
     uint32_t mask = 0;
     for (uint32_t j = 0; j < m; ++j) {
@@ -1795,11 +1773,11 @@ __global__ __launch_bounds__(256) void k_chains_state_in(const uint64_t *__restr
     state[static_cast<uint64_t>(g) * num_spins + i] = static_cast<T>(mask);
   }
 }
-// out: a wavefront per word of a chain (lane j owns spin 64 w + j), the word is one ballot.
+// out: chain r, a wavefront per word of it (lane j owns spin 64 w + j), the word is one ballot.
 template <typename T>
-__global__ __launch_bounds__(256) void k_chains_state_out(const T *__restrict__ state, uint32_t num_spins,
-                                                         uint32_t words, uint32_t m, uint64_t *__restrict__ x) {
-  const uint32_t r = blockIdx.x, lane = threadIdx.x & 63u;
+__device__ __forceinline__ void chains_state_out(const T *__restrict__ state, uint32_t num_spins, uint32_t words,
+                                                 uint32_t m, uint64_t *__restrict__ x, uint32_t r) {
+  const uint32_t lane = threadIdx.x & 63u;
   const T *state_g = state + static_cast<uint64_t>(r / m) * num_spins;
   for (uint32_t w = blockIdx.y * (blockDim.x >> 6) + (threadIdx.x >> 6); w < words; w += gridDim.y * (blockDim.x >> 6)) {
     const uint32_t i = w * 64u + lane;  // (w is uniform over the wavefront)
@@ -1808,6 +1786,18 @@ __global__ __launch_bounds__(256) void k_chains_state_out(const T *__restrict__ 
     const uint64_t word = __ballot(up);
     if (lane == 0) x[static_cast<uint64_t>(r) * words + w] = word;
   }
+}
+// One handle: its arguments by value (a segment of one handle is bound by latency: no table to upload).
+template <typename T>
+__global__ __launch_bounds__(256) void k_chains_state_in(const uint64_t *__restrict__ x, uint32_t words,
+                                                        uint32_t num_spins, uint32_t chains, uint32_t m,
+                                                        T *__restrict__ state) {
+  chains_state_in<T>(x, words, num_spins, chains, m, state, blockIdx.x);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_chains_state_out(const T *__restrict__ state, uint32_t num_spins,
+                                                         uint32_t words, uint32_t m, uint64_t *__restrict__ x) {
+  chains_state_out<T>(state, num_spins, words, m, x, blockIdx.x);
 }
 
 // The same for MANY handles at once (asp_sa_chains_advance_batch, order 1): a descriptor per handle and
@@ -1829,32 +1819,14 @@ __global__ __launch_bounds__(256) void k_chains_state_in_batch(const ChainsState
                                                               const ShuffledSlot *slots) {
   const ShuffledSlot slot = slots[blockIdx.x];
   const ChainsStateProblem &d = problems[slot.problem];
-  const uint32_t g = slot.group;
-  T *state = static_cast<T *>(d.state);
-  for (uint32_t i = blockIdx.y * blockDim.x + threadIdx.x; i < d.num_spins; i += gridDim.y * blockDim.x) {
-    uint32_t mask = 0;
-    for (uint32_t j = 0; j < d.m; ++j) {
-      const uint64_t r = static_cast<uint64_t>(g) * d.m + j;
-      if (r >= d.chains) break;
-      mask |= (static_cast<uint32_t>((d.x_cur[r * d.words + (i >> 6)] >> (i & 63u)) & 1ull) ^ 1u) << j;
-    }
-    state[static_cast<uint64_t>(g) * d.num_spins + i] = static_cast<T>(mask);
-  }
+  chains_state_in<T>(d.x_cur, d.words, d.num_spins, d.chains, d.m, static_cast<T *>(d.state), slot.group);
 }
 template <typename T>
 __global__ __launch_bounds__(256) void k_chains_state_out_batch(const ChainsStateProblem *problems,
                                                                const ShuffledSlot *chains) {
   const ShuffledSlot slot = chains[blockIdx.x];
   const ChainsStateProblem &d = problems[slot.problem];
-  const uint32_t r = slot.group, lane = threadIdx.x & 63u;
-  const T *state_g = static_cast<const T *>(d.state) + static_cast<uint64_t>(r / d.m) * d.num_spins;
-  for (uint32_t w = blockIdx.y * (blockDim.x >> 6) + (threadIdx.x >> 6); w < d.words; w += gridDim.y * (blockDim.x >> 6)) {
-    const uint32_t i = w * 64u + lane;  // (w is uniform over the wavefront)
-    bool up = false;
-    if (i < d.num_spins) up = ((static_cast<uint32_t>(state_g[i]) >> (r % d.m)) & 1u) == 0u;
-    const uint64_t word = __ballot(up);
-    if (lane == 0) d.x_cur[static_cast<uint64_t>(r) * d.words + w] = word;
-  }
+  chains_state_out<T>(static_cast<const T *>(d.state), d.num_spins, d.words, d.m, d.x_cur, slot.group);
 }
 // IN: handle -> run (the chains padding the last group: integers 0, as load_resume); else run -> handle.
 // A workgroup row per handle.
@@ -1897,106 +1869,97 @@ T *rebased(T *p, uint32_t t0) {
   return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) - 8ull * t0);
 }
 
-// m = chains per group; teams = 2: two teams of m / 2 chains (wide: m = 4 or 2; bytes: m = 8 or 4);
-// packed_lanes: blocks of fewer than 64 spins, several groups per wavefront (wide layout, one team)
-template <bool TRACE>
-ShuffledKernelOf<TRACE> shuffled_kernel_of(int m, int layout, int teams, bool packed_lanes) {
-  if (packed_lanes) {
-    if (layout != kWide || teams != 1) return nullptr;
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled<1, kWide, 1, true, TRACE>;
-      case 2: return k_sa_sweep_shuffled<2, kWide, 1, true, TRACE>;
-      case 4: return k_sa_sweep_shuffled<4, kWide, 1, true, TRACE>;
-      default: return nullptr;
-    }
+// A FORM of the sweep kernel: M chains per team in layout LAYOUT, TEAMS teams of a workgroup (m = M x TEAMS
+// chains per group), PK: lane packing — blocks of fewer than 64 spins, several groups per wavefront.
+template <int M, int LAYOUT, int TEAMS = 1, bool PK = false>
+struct Form {
+  static constexpr int kM = M, kLayout = LAYOUT, kTeams = TEAMS;
+  static constexpr bool kPacked = PK;
+  static constexpr bool is(int m, int layout, int teams, bool packed_lanes) {
+    return m == M * TEAMS && layout == LAYOUT && teams == TEAMS && packed_lanes == PK;
   }
-  if (teams == 2) {
-    if (layout == kWide) {
-      switch (m) {
-        case 2: return k_sa_sweep_shuffled<1, kWide, 2, false, TRACE>;
-        case 4: return k_sa_sweep_shuffled<2, kWide, 2, false, TRACE>;
-        default: return nullptr;
-      }
-    }
-    if (layout != kBytes) return nullptr;
-    switch (m) {
-      case 4: return k_sa_sweep_shuffled<2, kBytes, 2, false, TRACE>;
-      case 8: return k_sa_sweep_shuffled<4, kBytes, 2, false, TRACE>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kWide) {
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled<1, kWide, 1, false, TRACE>;
-      case 2: return k_sa_sweep_shuffled<2, kWide, 1, false, TRACE>;
-      case 4: return k_sa_sweep_shuffled<4, kWide, 1, false, TRACE>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kNibbles) {
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled<1, kNibbles, 1, false, TRACE>;
-      case 2: return k_sa_sweep_shuffled<2, kNibbles, 1, false, TRACE>;
-      case 4: return k_sa_sweep_shuffled<4, kNibbles, 1, false, TRACE>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kBits) return m == 1 ? k_sa_sweep_shuffled<1, kBits, 1, false, TRACE> : nullptr;
-  if (layout == kGlobal) return m == 1 ? k_sa_sweep_shuffled<1, kGlobal, 1, false, TRACE> : nullptr;
-  switch (m) {
-    case 1: return k_sa_sweep_shuffled<1, kBytes, 1, false, TRACE>;
-    case 2: return k_sa_sweep_shuffled<2, kBytes, 1, false, TRACE>;
-    case 4: return k_sa_sweep_shuffled<4, kBytes, 1, false, TRACE>;
-    case 8: return k_sa_sweep_shuffled<8, kBytes, 1, false, TRACE>;
-    default: return nullptr;
-  }
-}
-ShuffledKernel shuffled_kernel_for(int m, int layout, int teams = 1, bool packed_lanes = false) {
-  return shuffled_kernel_of<false>(m, layout, teams, packed_lanes);
-}
-// The instantiation that also writes ShuffledTraceArgs::trace — the same forms, one for one, so that a
-// traced call runs the layout, chains per group, packing and teams of the untraced one.
-ShuffledTraceKernel shuffled_trace_kernel_for(int m, int layout, int teams, bool packed_lanes) {
-  return shuffled_kernel_of<true>(m, layout, teams, packed_lanes);
-}
+};
+template <typename... Forms>
+struct FormList {};
+// Every form there is: each kernel family below has exactly these (a family without two teams: those of
+// one team), so that a traced, ladder or batched run has the layout, chains per group and packing of the
+// plain one.
+using ShuffledForms = FormList<
+    Form<1, kBytes>, Form<2, kBytes>, Form<4, kBytes>, Form<8, kBytes>,                // eight chains: bytes only
+    Form<1, kWide>, Form<2, kWide>, Form<4, kWide>,
+    Form<1, kNibbles>, Form<2, kNibbles>, Form<4, kNibbles>,
+    Form<1, kBits>, Form<1, kGlobal>,                                                  // one chain per workgroup
+    Form<1, kWide, 1, true>, Form<2, kWide, 1, true>, Form<4, kWide, 1, true>,         // lane packing
+    Form<1, kWide, 2>, Form<2, kWide, 2>, Form<2, kBytes, 2>, Form<4, kBytes, 2>>;     // two teams of m / 2 chains
 
-// The ladder kernel of the same form (one team).
-template <bool TRACE>
-ShuffledLadderKernelOf<TRACE> shuffled_ladder_kernel_of(int m, int layout, bool packed_lanes) {
-  if (packed_lanes) {
-    if (layout != kWide) return nullptr;
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled_ladder<1, kWide, true, TRACE>;
-      case 2: return k_sa_sweep_shuffled_ladder<2, kWide, true, TRACE>;
-      case 4: return k_sa_sweep_shuffled_ladder<4, kWide, true, TRACE>;
-      default: return nullptr;
+template <typename... Forms>
+constexpr bool form_listed(FormList<Forms...>, int m, int layout, int teams, bool packed_lanes) {
+  return (Forms::is(m, layout, teams, packed_lanes) || ...);
+}
+constexpr bool shuffled_form_exists(int m, int layout, int teams = 1, bool packed_lanes = false) {
+  return form_listed(ShuffledForms{}, m, layout, teams, packed_lanes);
+}
+static_assert(shuffled_form_exists(8, kBytes) && !shuffled_form_exists(8, kWide) && !shuffled_form_exists(8, kNibbles) &&
+                  !shuffled_form_exists(8, kBits) && !shuffled_form_exists(8, kGlobal) && !shuffled_form_exists(16, kBytes) &&
+                  !shuffled_form_exists(3, kBytes) && !shuffled_form_exists(0, kBytes),
+              "1, 2, 4 or 8 chains per group, 8 in the byte layout only");
+static_assert(shuffled_form_exists(1, kBits) && shuffled_form_exists(1, kGlobal) && !shuffled_form_exists(2, kBits) &&
+                  !shuffled_form_exists(2, kGlobal) && !shuffled_form_exists(4, kBits) && !shuffled_form_exists(4, kGlobal),
+              "a bit per spin and the spins in HBM: one chain per workgroup");
+static_assert(shuffled_form_exists(2, kWide, 2) && shuffled_form_exists(4, kWide, 2) && shuffled_form_exists(4, kBytes, 2) &&
+                  shuffled_form_exists(8, kBytes, 2) && !shuffled_form_exists(1, kWide, 2) && !shuffled_form_exists(8, kWide, 2) &&
+                  !shuffled_form_exists(2, kBytes, 2) && !shuffled_form_exists(16, kBytes, 2) &&
+                  !shuffled_form_exists(2, kNibbles, 2) && !shuffled_form_exists(4, kNibbles, 2) &&
+                  !shuffled_form_exists(2, kBits, 2) && !shuffled_form_exists(2, kGlobal, 2) &&
+                  !shuffled_form_exists(4, kWide, 3) && !shuffled_form_exists(4, kWide, 0),
+              "two teams: wide with 2 or 4 chains per group, bytes with 4 or 8");
+static_assert(shuffled_form_exists(1, kWide, 1, true) && shuffled_form_exists(2, kWide, 1, true) &&
+                  shuffled_form_exists(4, kWide, 1, true) && !shuffled_form_exists(8, kWide, 1, true) &&
+                  !shuffled_form_exists(4, kBytes, 1, true) && !shuffled_form_exists(8, kBytes, 1, true) &&
+                  !shuffled_form_exists(4, kNibbles, 1, true) && !shuffled_form_exists(1, kBits, 1, true) &&
+                  !shuffled_form_exists(1, kGlobal, 1, true) && !shuffled_form_exists(2, kWide, 2, true) &&
+                  !shuffled_form_exists(4, kWide, 2, true),
+              "lane packing: the wide layout, at most four chains per group, one team");
+
+// A kernel FAMILY gives the kernel of a form: Family::Kernel of<Form>(), and kTwoTeams — whether it has the
+// forms of two teams at all (a family without them does not instantiate them).
+// One problem per launch, its arguments by value (ShuffledArgsOf<TRACE>; ShuffledLadderArgs<TRACE>: one team).
+template <typename Args>
+struct SingleFamily {
+  using Kernel = void (*)(Args);
+  static constexpr bool kTwoTeams = !kLadderArgs<Args>;
+  template <typename F>
+  static Kernel of() {
+    return k_sa_sweep_shuffled<F::kM, F::kLayout, F::kTeams, F::kPacked, Args>;
+  }
+};
+// Many problems per launch (run_shuffled_group), descriptors of ShuffledArgs or ShuffledLadderBatchArgs.
+template <typename Args>
+struct BatchFamily {
+  using Kernel = void (*)(const Args *, const ShuffledSlot *);
+  static constexpr bool kTwoTeams = false;
+  template <typename F>
+  static Kernel of() {
+    return k_sa_sweep_shuffled_batch<F::kM, F::kLayout, F::kPacked, Args>;
+  }
+};
+
+// The family's kernel for m chains per group, or nullptr: no such form (in this family).
+template <typename Family, typename... Forms>
+typename Family::Kernel shuffled_kernel_in(FormList<Forms...>, int m, int layout, int teams, bool packed_lanes) {
+  typename Family::Kernel kernel = nullptr;
+  auto take = [&](auto form) {
+    using F = decltype(form);
+    if constexpr (F::kTeams == 1 || Family::kTwoTeams) {
+      if (F::is(m, layout, teams, packed_lanes)) kernel = Family::template of<F>();
     }
-  }
-  if (layout == kWide) {
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled_ladder<1, kWide, false, TRACE>;
-      case 2: return k_sa_sweep_shuffled_ladder<2, kWide, false, TRACE>;
-      case 4: return k_sa_sweep_shuffled_ladder<4, kWide, false, TRACE>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kNibbles) {
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled_ladder<1, kNibbles, false, TRACE>;
-      case 2: return k_sa_sweep_shuffled_ladder<2, kNibbles, false, TRACE>;
-      case 4: return k_sa_sweep_shuffled_ladder<4, kNibbles, false, TRACE>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kBits) return m == 1 ? k_sa_sweep_shuffled_ladder<1, kBits, false, TRACE> : nullptr;
-  if (layout == kGlobal) return m == 1 ? k_sa_sweep_shuffled_ladder<1, kGlobal, false, TRACE> : nullptr;
-  switch (m) {
-    case 1: return k_sa_sweep_shuffled_ladder<1, kBytes, false, TRACE>;
-    case 2: return k_sa_sweep_shuffled_ladder<2, kBytes, false, TRACE>;
-    case 4: return k_sa_sweep_shuffled_ladder<4, kBytes, false, TRACE>;
-    case 8: return k_sa_sweep_shuffled_ladder<8, kBytes, false, TRACE>;
-    default: return nullptr;
-  }
+  };
+  (take(Forms{}), ...);
+  return kernel;
+}
+template <typename Family>
+typename Family::Kernel shuffled_kernel_of(int m, int layout, int teams, bool packed_lanes) {
+  return shuffled_kernel_in<Family>(ShuffledForms{}, m, layout, teams, packed_lanes);
 }
 
 // spins (of `groups` groups: lane packing) | delta[CH] book[3 CH] | flags (16 B) | meta[block_cap] |
@@ -2381,10 +2344,10 @@ struct ShuffledRun {
     w.stream = clamp((blocks + per_workgroup - 1) / per_workgroup, 128);
     return w;
   }
-  ShuffledKernel kernel = nullptr;
-  ShuffledTraceKernel trace_kernel = nullptr;  // the traced instantiation of `kernel` (out_trace)
-  ShuffledLadderKernelOf<false> ladder_kernel = nullptr;       // chain_betas: the ladder form of `kernel` ...
-  ShuffledLadderKernelOf<true> ladder_trace_kernel = nullptr;  // ... and of `trace_kernel`
+  // The sweep kernel of the attempt — of SingleFamily<Args>, Args by (out_trace, chain_betas) — and the
+  // launch of a chunk with it (choose_sweep<Args>()).
+  void *sweep_kernel = nullptr;
+  int (ShuffledRun::*launch_sweep)(const ShuffledArgs &) = nullptr;
   int nsets = 1, nlanes = 1;
   OrderArgs oa{};
   ShuffledArgs sa{};
@@ -2566,6 +2529,43 @@ struct ShuffledRun {
     *s_out = y;
   }
 
+  // The attempt's kernel, of the family with arguments Args, in the form plan_sizes() chose; the closed
+  // call falls back from two teams to one where the width and layout have no two-team form.
+  template <typename Args>
+  int choose_sweep() {
+    using Family = SingleFamily<Args>;
+    typename Family::Kernel kernel = shuffled_kernel_of<Family>(m, layout, teams, packed_lanes);
+    if (!kernel && teams == 2) {
+      teams = 1;
+      kernel = shuffled_kernel_of<Family>(m, layout, 1, packed_lanes);
+    }
+    if (!kernel) {
+      return asp::set_error(ASP_ERR_INVALID, kLadderArgs<Args> ? "no ladder sweep for %d chains per group in layout %d"
+                                                               : "no shuffled sweep for %d chains per group in layout %d",
+                            m, layout);
+    }
+    sweep_kernel = reinterpret_cast<void *>(kernel);
+    launch_sweep = &ShuffledRun::launch_sweep_as<Args>;
+    return asp::allow_dynamic_lds(sweep_kernel, lds);
+  }
+
+  // One chunk's sweep launch on the plan's stream: the family's arguments from the chunk's (chunk_args()).
+  template <typename Args>
+  int launch_sweep_as(const ShuffledArgs &chunk_sweep) {
+    Args a{};
+    static_cast<ShuffledArgs &>(a) = chunk_sweep;
+    if constexpr (kTraceArgs<Args>) {
+      a.trace = rebased(p->w_trace.ptr, t0);
+      a.trace_chains = repetitions;
+      a.trace_stride = num_sweeps + 1u;
+    }
+    if constexpr (kLadderArgs<Args>) a.chain_betas = d_betas.ptr;
+    const auto kernel = reinterpret_cast<typename SingleFamily<Args>::Kernel>(sweep_kernel);
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(waves * teams * 64), lds, p->stream, a);
+    ASP_HIP_TRY(hipGetLastError());
+    return ASP_OK;
+  }
+
   // Queues one whole attempt (all chunks) on the run's streams; returns without waiting.
   int enqueue() {
     if (trivial) return ASP_OK;
@@ -2578,25 +2578,11 @@ struct ShuffledRun {
       if (!swept[i]) ASP_HIP_TRY(hipEventCreateWithFlags(&swept[i], hipEventDisableTiming));
     }
     ASP_TRY(plan_sizes());
-    kernel = shuffled_kernel_for(m, layout, teams, packed_lanes);
-    if (!kernel) {  // (no two-team form of this width and layout)
-      teams = 1;
-      kernel = shuffled_kernel_for(m, layout, 1, packed_lanes);
-    }
-    // (a traced call: the traced instantiation of the form just chosen)
-    trace_kernel = out_trace ? shuffled_trace_kernel_for(m, layout, teams, packed_lanes) : nullptr;
-    const void *launched = out_trace ? reinterpret_cast<const void *>(trace_kernel)
-                                     : reinterpret_cast<const void *>(kernel);
     if (chain_betas) {
-      ladder_kernel = shuffled_ladder_kernel_of<false>(m, layout, packed_lanes);
-      ladder_trace_kernel = shuffled_ladder_kernel_of<true>(m, layout, packed_lanes);
-      if (!ladder_kernel || !ladder_trace_kernel) {
-        return asp::set_error(ASP_ERR_INVALID, "no ladder sweep for %d chains per group in layout %d", m, layout);
-      }
-      launched = out_trace ? reinterpret_cast<const void *>(ladder_trace_kernel)
-                           : reinterpret_cast<const void *>(ladder_kernel);
+      ASP_TRY(out_trace ? choose_sweep<ShuffledLadderArgs<true>>() : choose_sweep<ShuffledLadderArgs<false>>());
+    } else {
+      ASP_TRY(out_trace ? choose_sweep<ShuffledTraceArgs>() : choose_sweep<ShuffledArgs>());
     }
-    ASP_TRY(asp::allow_dynamic_lds(launched, lds));
     ASP_TRY(asp::allow_dynamic_lds(
         reinterpret_cast<const void *>(wide_orders ? k_shuffled_orders<true> : k_shuffled_orders<false>), order_lds));
     ASP_TRY(plan_buffers(chunk));
@@ -2651,29 +2637,7 @@ struct ShuffledRun {
 
         ASP_HIP_TRY(hipStreamWaitEvent(s, ordered[which], 0));
       }
-      if (out_trace) {
-        ShuffledTraceArgs t_args{};
-        static_cast<ShuffledArgs &>(t_args) = s_args;
-        t_args.trace = rebased(p->w_trace.ptr, t0);
-        t_args.trace_chains = repetitions;
-        t_args.trace_stride = num_sweeps + 1u;
-        if (chain_betas) {
-          ShuffledLadderArgs<true> l_args{};
-          static_cast<ShuffledTraceArgs &>(l_args) = t_args;
-          l_args.chain_betas = d_betas.ptr;
-          hipLaunchKernelGGL(ladder_trace_kernel, dim3(wgs), dim3(waves * 64), lds, s, l_args);
-        } else {
-          hipLaunchKernelGGL(trace_kernel, dim3(wgs), dim3(waves * teams * 64), lds, s, t_args);
-        }
-      } else if (chain_betas) {
-        ShuffledLadderArgs<false> l_args{};
-        static_cast<ShuffledArgs &>(l_args) = s_args;
-        l_args.chain_betas = d_betas.ptr;
-        hipLaunchKernelGGL(ladder_kernel, dim3(wgs), dim3(waves * 64), lds, s, l_args);
-      } else {
-        hipLaunchKernelGGL(kernel, dim3(wgs), dim3(waves * teams * 64), lds, s, s_args);
-      }
-      ASP_HIP_TRY(hipGetLastError());
+      ASP_TRY((this->*launch_sweep)(s_args));
       ASP_HIP_TRY(hipEventRecord(swept[which], s));
       first_launch = false;
     }
@@ -2828,90 +2792,40 @@ struct ShuffledRun {
     }
     return ASP_OK;
   }
+
+  // The attempts of a run that has its launches to itself, until the capacities suffice.
+  int attempts() {
+    bool again = true;
+    while (again) {
+      ASP_TRY(enqueue());
+      ASP_TRY(collect(&again));
+    }
+    return ASP_OK;
+  }
+
+  // The whole of a run that runs alone, from set-up to the results at the caller.
+  int alone() {
+    ASP_TRY(setup());
+    ASP_TRY(attempts());
+    ASP_TRY(finish_enqueue());
+    return finish_wait();
+  }
+
+  // A segment of a handle: `betas` [num_sweeps], or `chain_betas` [repetitions] for a ladder segment.
+  void segment_of(asp_sa_chains *c, const double *betas_, const double *chain_betas_, uint32_t num_sweeps_,
+                  int64_t *trace) {
+    p = c->plan;
+    seed = c->seed;
+    betas = betas_;
+    chain_betas = chain_betas_;
+    num_sweeps = num_sweeps_;
+    repetitions = c->repetitions;
+    replica_offset = c->replica_offset;
+    out_trace = trace;
+    resume = c;
+    t0 = c->sweeps_done;
+  }
 };
-
-}  // namespace
-
-namespace {
-
-using ShuffledBatchKernel = void (*)(const ShuffledArgs *, const ShuffledSlot *);
-
-ShuffledBatchKernel shuffled_batch_kernel_for(int m, int layout, bool packed_lanes) {
-  if (packed_lanes) {
-    if (layout != kWide) return nullptr;
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled_batch<1, kWide, true>;
-      case 2: return k_sa_sweep_shuffled_batch<2, kWide, true>;
-      case 4: return k_sa_sweep_shuffled_batch<4, kWide, true>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kWide) {
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled_batch<1, kWide>;
-      case 2: return k_sa_sweep_shuffled_batch<2, kWide>;
-      case 4: return k_sa_sweep_shuffled_batch<4, kWide>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kNibbles) {
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled_batch<1, kNibbles>;
-      case 2: return k_sa_sweep_shuffled_batch<2, kNibbles>;
-      case 4: return k_sa_sweep_shuffled_batch<4, kNibbles>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kBits) return m == 1 ? k_sa_sweep_shuffled_batch<1, kBits> : nullptr;
-  if (layout == kGlobal) return m == 1 ? k_sa_sweep_shuffled_batch<1, kGlobal> : nullptr;
-  switch (m) {
-    case 1: return k_sa_sweep_shuffled_batch<1, kBytes>;
-    case 2: return k_sa_sweep_shuffled_batch<2, kBytes>;
-    case 4: return k_sa_sweep_shuffled_batch<4, kBytes>;
-    case 8: return k_sa_sweep_shuffled_batch<8, kBytes>;
-    default: return nullptr;
-  }
-}
-
-// The ladder form of the same kernel (run_shuffled_group with ShuffledRun::chain_betas).
-using ShuffledLadderBatchKernel = void (*)(const ShuffledLadderBatchArgs *, const ShuffledSlot *);
-
-ShuffledLadderBatchKernel shuffled_ladder_batch_kernel_for(int m, int layout, bool packed_lanes) {
-  if (packed_lanes) {
-    if (layout != kWide) return nullptr;
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled_ladder_batch<1, kWide, true>;
-      case 2: return k_sa_sweep_shuffled_ladder_batch<2, kWide, true>;
-      case 4: return k_sa_sweep_shuffled_ladder_batch<4, kWide, true>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kWide) {
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled_ladder_batch<1, kWide>;
-      case 2: return k_sa_sweep_shuffled_ladder_batch<2, kWide>;
-      case 4: return k_sa_sweep_shuffled_ladder_batch<4, kWide>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kNibbles) {
-    switch (m) {
-      case 1: return k_sa_sweep_shuffled_ladder_batch<1, kNibbles>;
-      case 2: return k_sa_sweep_shuffled_ladder_batch<2, kNibbles>;
-      case 4: return k_sa_sweep_shuffled_ladder_batch<4, kNibbles>;
-      default: return nullptr;
-    }
-  }
-  if (layout == kBits) return m == 1 ? k_sa_sweep_shuffled_ladder_batch<1, kBits> : nullptr;
-  if (layout == kGlobal) return m == 1 ? k_sa_sweep_shuffled_ladder_batch<1, kGlobal> : nullptr;
-  switch (m) {
-    case 1: return k_sa_sweep_shuffled_ladder_batch<1, kBytes>;
-    case 2: return k_sa_sweep_shuffled_ladder_batch<2, kBytes>;
-    case 4: return k_sa_sweep_shuffled_ladder_batch<4, kBytes>;
-    case 8: return k_sa_sweep_shuffled_ladder_batch<8, kBytes>;
-    default: return nullptr;
-  }
-}
 
 // The handles of the group's runs (ShuffledRun::resume) into the runs' buffers before an attempt
 // (`in`), or out of them after the attempt that succeeded: one launch per state type and one for the
@@ -3025,6 +2939,7 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
     asp::ScopedStream stream;
     uint32_t num_slots = 0;
     size_t lds = 0;
+    void *kernel = nullptr;  // of BatchFamily<ShuffledLadderBatchArgs> in a ladder group, else <ShuffledArgs>
     hipEvent_t swept[ShuffledRun::kSets] = {};
   };
   asp::EventPool events;
@@ -3084,10 +2999,8 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
     // (a kernel is keyed by (m, layout, packing), a class also by its wavefronts and block size:
     // classes may share a kernel, and its dynamic-LDS limit must cover the largest of them)
     std::vector<std::pair<const void *, size_t>> kernel_lds;
-    auto class_kernel = [&](int m, int layout, bool packed_lanes) -> const void * {
-      return ladder ? reinterpret_cast<const void *>(shuffled_ladder_batch_kernel_for(m, layout, packed_lanes))
-                    : reinterpret_cast<const void *>(shuffled_batch_kernel_for(m, layout, packed_lanes));
-    };
+    using PlainKernels = BatchFamily<ShuffledArgs>;
+    using LadderKernels = BatchFamily<ShuffledLadderBatchArgs>;
     for (auto &c : classes) {
       // XCD-aware slot table (asp::deal_to_xcds), the longest problems first: a workgroup's time is
       // sweeps x levels x one block visit whatever the cluster's size, but the large clusters have more
@@ -3104,16 +3017,19 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
       ASP_TRY(c->slots.alloc(slots.size()));
       ASP_TRY(c->slots.upload(slots.data(), slots.size(), c->stream.stream));
       ASP_HIP_TRY(hipStreamSynchronize(c->stream.stream));  // `slots` dies with this scope
-      const void *kernel = class_kernel(c->m, c->layout, c->packed_lanes);
-      if (!kernel) return asp::set_error(ASP_ERR_INVALID, "no batched shuffled kernel for %d chains per group", c->m);
+      c->kernel = ladder ? reinterpret_cast<void *>(
+                               shuffled_kernel_of<LadderKernels>(c->m, c->layout, 1, c->packed_lanes))
+                         : reinterpret_cast<void *>(
+                               shuffled_kernel_of<PlainKernels>(c->m, c->layout, 1, c->packed_lanes));
+      if (!c->kernel) return asp::set_error(ASP_ERR_INVALID, "no batched shuffled kernel for %d chains per group", c->m);
       bool seen = false;
       for (auto &k : kernel_lds) {
-        if (k.first == kernel) {
+        if (k.first == c->kernel) {
           k.second = std::max(k.second, c->lds);
           seen = true;
         }
       }
-      if (!seen) kernel_lds.emplace_back(kernel, c->lds);
+      if (!seen) kernel_lds.emplace_back(c->kernel, c->lds);
     }
     if (std::getenv("ASP_SHUFFLED_HOST_TIMING")) {
       for (auto &c : classes) {
@@ -3216,11 +3132,11 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
         hipStream_t cs = c->stream.stream;
         if (now) ASP_HIP_TRY(hipStreamWaitEvent(cs, ordered[which], 0));
         if (ladder) {
-          ShuffledLadderBatchKernel kernel = shuffled_ladder_batch_kernel_for(c->m, c->layout, c->packed_lanes);
+          const auto kernel = reinterpret_cast<LadderKernels::Kernel>(c->kernel);
           hipLaunchKernelGGL(kernel, dim3(c->num_slots), dim3(c->waves * 64), c->lds, cs,
                              d_largs.ptr + static_cast<size_t>(turn) * P, c->slots.ptr);
         } else {
-          ShuffledBatchKernel kernel = shuffled_batch_kernel_for(c->m, c->layout, c->packed_lanes);
+          const auto kernel = reinterpret_cast<PlainKernels::Kernel>(c->kernel);
           hipLaunchKernelGGL(kernel, dim3(c->num_slots), dim3(c->waves * 64), c->lds, cs,
                              d_sargs.ptr + static_cast<size_t>(turn) * P, c->slots.ptr);
         }
@@ -3254,36 +3170,21 @@ int run_shuffled_group(std::vector<ShuffledRun *> &runs, float *sweep_ms) {
   return ASP_OK;
 }
 
-}  // namespace
-
-namespace asp {
-
-// The shuffled items of asp_sa_anneal_batch (csrc/sa_sweep.hip): every item is exactly its own
-// asp_sa_anneal_shuffled call.  Items are grouped by their number of sweeps; the problems of a
-// group share launches (run_shuffled_group), a group of one takes the single-problem path.
-int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uint32_t count, float *sweep_ms) {
-  // ASP_SHUFFLED_HOST_TIMING=1: wall-clock phases of this function on stderr (development aid)
-  const bool host_timing = std::getenv("ASP_SHUFFLED_HOST_TIMING") != nullptr;
-  auto phase_start = std::chrono::steady_clock::now();
-  auto phase = [&](const char *name) {
-    if (!host_timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "  shuffled batch: %-18s %8.2f ms\n", name,
-                 std::chrono::duration<double, std::milli>(now - phase_start).count());
-    phase_start = now;
-  };
-  std::vector<std::unique_ptr<ShuffledRun>> runs;
-  runs.reserve(count);
+// What a batch — the closed one and the batched segments — decides for its runs as a whole, then every
+// run's set-up: ALL of it before the first launch, so an invalid item fails the call before anything is
+// queued.  A batch of one forces nothing.
+int setup_batch(std::vector<std::unique_ptr<ShuffledRun>> &runs) {
+  const size_t n = runs.size();
   uint64_t budget = 16ull << 30;  // bytes of visiting orders for the whole batch, per buffer set
   if (const char *env = std::getenv("ASP_SHUFFLED_BATCH_BYTES")) budget = std::strtoull(env, nullptr, 10);
   // chains per workgroup for the whole batch: as many as still leave two workgroups per compute unit
   int m = 1;
   bool saturates = false;  // more groups of chains than the chip holds workgroups (two per compute unit)
-  if (count > 1) {
-    const int num_cus = items[which[0]].plan ? items[which[0]].plan->num_cus : 256;
+  if (n > 1) {
+    const int num_cus = runs[0]->p ? runs[0]->p->num_cus : 256;
     for (int cand : {4, 2}) {
       uint64_t groups = 0;
-      for (uint32_t k = 0; k < count; ++k) groups += (items[which[k]].repetitions + cand - 1) / cand;
+      for (auto &r : runs) groups += (r->repetitions + cand - 1) / cand;
       if (groups >= 2ull * static_cast<uint64_t>(num_cus)) {
         m = cand;
         saturates = true;
@@ -3292,42 +3193,36 @@ int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uin
     }
   }
   const int big_m = 8;  // chains per workgroup of the clusters beyond the word layout, in a batch that fills the chip
-  for (uint32_t k = 0; k < count; ++k) {
-    const asp_sa_batch_item &it = items[which[k]];
-    runs.emplace_back(new ShuffledRun());
-    ShuffledRun &r = *runs.back();
-    r.p = it.plan;
-    r.seed = it.seed;
-    r.betas = it.betas;
-    r.num_sweeps = it.num_sweeps;
-    r.repetitions = it.repetitions;
-    r.replica_offset = it.replica_offset;
-    r.out_x = it.out_x;
-    r.out_e = it.out_e;
-    r.budget = std::max<uint64_t>(64ull << 20, std::min<uint64_t>(3ull << 30, budget / count));
-    if (count > 1 && it.plan && !it.plan->shuffled_m) {
-      r.forced_m = m;
+  for (auto &r : runs) {
+    r->budget = std::max<uint64_t>(64ull << 20, std::min<uint64_t>(3ull << 30, budget / n));
+    if (n > 1 && r->p && !r->p->shuffled_m) {
+      r->forced_m = m;
       // A cluster beyond the word layout (a word per spin and four chains: ~3.8e4 spins) in a batch
       // that fills the chip: eight chains per workgroup in the byte layout (setup() falls back to
       // four / one where bytes do not fit either).  The sweep's coupling stream — 12 bytes per
       // coupling, written once and read by EVERY workgroup of the problem — is the traffic of such a
       // model: 350 bytes per spin and sweep over M chains; the real kagome_36 order-2 models (3.5e4 ..
       // 3e5 spins, 64 chains each) moved 87 bytes per flip at M = 4.
-      if (saturates && it.plan->host.num_spins * 4ull > it.plan->max_lds * 15 / 16) r.forced_m = big_m;
+      if (saturates && r->p->host.num_spins * 4ull > r->p->max_lds * 15 / 16) r->forced_m = big_m;
     }
-    r.batch_saturates = saturates;
-    ASP_TRY(r.setup());
+    r->batch_saturates = saturates;
+    ASP_TRY(r->setup());
   }
-  phase("setup");
-  // groups of equal ladder length (and equal chains per workgroup: a plan with a forced width
-  // keeps it and runs alone)
+  return ASP_OK;
+}
+
+// The launches of a batch's set-up runs: groups of equal ladder length (and equal chains per workgroup: a
+// plan with a forced width keeps it) share launches (run_shuffled_group); `single(i)` runs run i, a group
+// of one.  Trivial runs join no group.
+template <typename Single>
+int launch_batch(std::vector<std::unique_ptr<ShuffledRun>> &runs, float *sweep_ms, Single single) {
   std::vector<bool> taken(runs.size(), false);
   for (size_t i = 0; i < runs.size(); ++i) {
     if (taken[i] || runs[i]->trivial) continue;
     std::vector<ShuffledRun *> group;
     for (size_t j = i; j < runs.size(); ++j) {
       if (!taken[j] && !runs[j]->trivial && runs[j]->num_sweeps == runs[i]->num_sweeps &&
-          shuffled_batch_kernel_for(runs[j]->m, kBytes, false)) {
+          shuffled_form_exists(runs[j]->m, kBytes)) {
         group.push_back(runs[j].get());
         taken[j] = true;
       }
@@ -3336,29 +3231,11 @@ int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uin
     if (group.size() >= 2) {
       ASP_TRY(run_shuffled_group(group, sweep_ms));
     } else {
-      ShuffledRun &r = *runs[i];
-      bool again = true;
-      while (again) {
-        ASP_TRY(r.enqueue());
-        ASP_TRY(r.collect(&again));
-      }
+      ASP_TRY(single(i));
     }
   }
-  phase("launches + wait");
-  for (auto &r : runs) ASP_TRY(r->finish_enqueue());
-  for (auto &r : runs) {
-    ASP_TRY(r->finish_wait());
-    if (sweep_ms && r->p && !r->batched) *sweep_ms += r->p->last_sweep_ms;
-  }
-  phase("energies + copies");
-  runs.clear();
-  phase("release");
   return ASP_OK;
 }
-
-}  // namespace asp
-
-namespace {
 
 // One single-problem call, with (asp_sa_anneal_shuffled_trace) or without per-sweep traces.
 int run_shuffled(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_sweeps, uint32_t repetitions,
@@ -3376,81 +3253,88 @@ int run_shuffled(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t nu
   run.out_x = out_x;
   run.out_e = out_e;
   run.out_trace = out_trace;
-  ASP_TRY(run.setup());
-  bool again = true;
-  while (again) {
-    ASP_TRY(run.enqueue());
-    ASP_TRY(run.collect(&again));
-  }
-  ASP_TRY(run.finish_enqueue());
-  return run.finish_wait();
+  return run.alone();
+}
+
+// One segment of a handle, plain (`betas`) or ladder (`chain_betas`), by itself: a ShuffledRun in its
+// resume form — the launcher's every choice (chains per group, spin layout, lane packing, teams of a
+// workgroup, chunk size, the retry with larger capacities) is the closed call's.
+int segment_alone(asp_sa_chains *c, double const *betas, double const *chain_betas, uint32_t num_sweeps,
+                  int64_t *trace) {
+  ShuffledRun run;
+  run.segment_of(c, betas, chain_betas, num_sweeps, trace);
+  return run.alone();
 }
 
 }  // namespace
 
 namespace asp {
 
-// One segment of a handle in the shuffled order: a ShuffledRun in its resume form — the launcher's
-// every choice (chains per group, spin layout, lane packing, teams of a workgroup, chunk size, the
-// retry with larger capacities) is the closed call's.
-int sa_chains_advance_shuffled(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace) {
-  ShuffledRun run;
-  run.p = c->plan;
-  run.seed = c->seed;
-  run.betas = betas;
-  run.num_sweeps = num_sweeps;
-  run.repetitions = c->repetitions;
-  run.replica_offset = c->replica_offset;
-  run.out_trace = trace;
-  run.resume = c;
-  run.t0 = c->sweeps_done;
-  ASP_TRY(run.setup());
-  bool again = true;
-  while (again) {
-    ASP_TRY(run.enqueue());
-    ASP_TRY(run.collect(&again));
+// The shuffled items of asp_sa_anneal_batch (csrc/sa_sweep.hip): every item is exactly its own
+// asp_sa_anneal_shuffled call.  Items are grouped by their number of sweeps; the problems of a
+// group share launches (run_shuffled_group), a group of one continues as the single-problem call does,
+// with the batch's choices.
+int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uint32_t count, float *sweep_ms) {
+  // ASP_SHUFFLED_HOST_TIMING=1: wall-clock phases of this function on stderr (development aid)
+  const bool host_timing = std::getenv("ASP_SHUFFLED_HOST_TIMING") != nullptr;
+  auto phase_start = std::chrono::steady_clock::now();
+  auto phase = [&](const char *name) {
+    if (!host_timing) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "  shuffled batch: %-18s %8.2f ms\n", name,
+                 std::chrono::duration<double, std::milli>(now - phase_start).count());
+    phase_start = now;
+  };
+  std::vector<std::unique_ptr<ShuffledRun>> runs;
+  runs.reserve(count);
+  for (uint32_t k = 0; k < count; ++k) {
+    const asp_sa_batch_item &it = items[which[k]];
+    runs.emplace_back(new ShuffledRun());
+    ShuffledRun &r = *runs.back();
+    r.p = it.plan;
+    r.seed = it.seed;
+    r.betas = it.betas;
+    r.num_sweeps = it.num_sweeps;
+    r.repetitions = it.repetitions;
+    r.replica_offset = it.replica_offset;
+    r.out_x = it.out_x;
+    r.out_e = it.out_e;
   }
-  ASP_TRY(run.finish_enqueue());
-  return run.finish_wait();
+  ASP_TRY(setup_batch(runs));
+  phase("setup");
+  ASP_TRY(launch_batch(runs, sweep_ms, [&](size_t i) { return runs[i]->attempts(); }));
+  phase("launches + wait");
+  for (auto &r : runs) ASP_TRY(r->finish_enqueue());
+  for (auto &r : runs) {
+    ASP_TRY(r->finish_wait());
+    if (sweep_ms && r->p && !r->batched) *sweep_ms += r->p->last_sweep_ms;
+  }
+  phase("energies + copies");
+  runs.clear();
+  phase("release");
+  return ASP_OK;
 }
 
-// One LADDER segment in the shuffled order: the same run with one beta per chain.
+// One segment of a handle in the shuffled order, and one LADDER segment: the same run with one beta per
+// chain.
+int sa_chains_advance_shuffled(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace) {
+  return segment_alone(c, betas, nullptr, num_sweeps, trace);
+}
 int sa_chains_advance_ladder_shuffled(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps,
                                       int64_t *trace) {
-  ShuffledRun run;
-  run.p = c->plan;
-  run.seed = c->seed;
-  run.chain_betas = chain_betas;
-  run.num_sweeps = num_sweeps;
-  run.repetitions = c->repetitions;
-  run.replica_offset = c->replica_offset;
-  run.out_trace = trace;
-  run.resume = c;
-  run.t0 = c->sweeps_done;
-  ASP_TRY(run.setup());
-  bool again = true;
-  while (again) {
-    ASP_TRY(run.enqueue());
-    ASP_TRY(run.collect(&again));
-  }
-  ASP_TRY(run.finish_enqueue());
-  return run.finish_wait();
+  return segment_alone(c, nullptr, chain_betas, num_sweeps, trace);
 }
 
-// Many segments in the shuffled order: sa_shuffled_batch for runs in their resume form — the same
-// chains per group for the batch, lane packing and one team; segments of equal length share launches
+// Many segments in the shuffled order: the batch of sa_shuffled_batch for runs in their resume form — the
+// same chains per group for the batch, lane packing and one team; segments of equal length share launches
 // (run_shuffled_group, with every handle's own t0), a traced segment and a group of one take the
-// single-handle path.
+// single-handle path, with the launcher's own choices.
 int sa_chains_advance_shuffled_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms) {
   std::vector<uint32_t> shared;
   auto alone = [&](const ChainsSegment &g) -> int {
     asp_sa_plan *p = g.chains->plan;
     p->last_sweep_ms = p->last_total_ms = 0.0f;
-    if (g.chain_betas) {
-      ASP_TRY(sa_chains_advance_ladder_shuffled(g.chains, g.chain_betas, g.num_sweeps, g.trace));
-    } else {
-      ASP_TRY(sa_chains_advance_shuffled(g.chains, g.betas, g.num_sweeps, g.trace));
-    }
+    ASP_TRY(segment_alone(g.chains, g.chain_betas ? nullptr : g.betas, g.chain_betas, g.num_sweeps, g.trace));
     if (sweep_ms) *sweep_ms += p->last_sweep_ms;
     return ASP_OK;
   };
@@ -3462,8 +3346,7 @@ int sa_chains_advance_shuffled_batch(const ChainsSegment *segs, uint32_t count, 
     }
   }
   {
-    // (a segment that no other shares its length with is a group of one: the single-handle path, with
-    // the launcher's own choices, before any run is set up)
+    // (a segment that no other shares its length with is a group of one: before any run is set up)
     std::vector<uint32_t> lengths, kept;
     for (uint32_t i : shared) lengths.push_back(segs[i].num_sweeps);
     std::sort(lengths.begin(), lengths.end());
@@ -3478,68 +3361,19 @@ int sa_chains_advance_shuffled_batch(const ChainsSegment *segs, uint32_t count, 
     shared.swap(kept);
   }
   if (shared.empty()) return ASP_OK;
-  const uint32_t n = static_cast<uint32_t>(shared.size());
-  uint64_t budget = 16ull << 30;  // bytes of visiting orders for the whole batch, per buffer set
-  if (const char *env = std::getenv("ASP_SHUFFLED_BATCH_BYTES")) budget = std::strtoull(env, nullptr, 10);
-  // chains per workgroup for the whole batch: as many as still leave two workgroups per compute unit
-  int m = 1;
-  bool saturates = false;
-  {
-    const int num_cus = segs[shared[0]].chains->plan->num_cus;
-    for (int cand : {4, 2}) {
-      uint64_t groups = 0;
-      for (uint32_t i : shared) groups += (segs[i].chains->repetitions + cand - 1) / cand;
-      if (groups >= 2ull * static_cast<uint64_t>(num_cus)) {
-        m = cand;
-        saturates = true;
-        break;
-      }
-    }
-  }
   std::vector<std::unique_ptr<ShuffledRun>> runs;
-  runs.reserve(n);
+  runs.reserve(shared.size());
   for (uint32_t i : shared) {
-    asp_sa_chains *c = segs[i].chains;
     runs.emplace_back(new ShuffledRun());
-    ShuffledRun &r = *runs.back();
-    r.p = c->plan;
-    r.seed = c->seed;
-    r.betas = segs[i].betas;
-    r.chain_betas = segs[i].chain_betas;  // (a batch of ladder segments: set in every one)
-    r.num_sweeps = segs[i].num_sweeps;
-    r.repetitions = c->repetitions;
-    r.replica_offset = c->replica_offset;
-    r.resume = c;
-    r.t0 = c->sweeps_done;
-    r.budget = std::max<uint64_t>(64ull << 20, std::min<uint64_t>(3ull << 30, budget / n));
-    if (!c->plan->shuffled_m) {
-      r.forced_m = m;
-      // (a cluster beyond the word layout in a batch that fills the chip: see sa_shuffled_batch)
-      if (saturates && c->plan->host.num_spins * 4ull > c->plan->max_lds * 15 / 16) r.forced_m = 8;
-    }
-    r.batch_saturates = saturates;
-    ASP_TRY(r.setup());
+    // (a batch of ladder segments: chain_betas set in every one)
+    runs.back()->segment_of(segs[i].chains, segs[i].betas, segs[i].chain_betas, segs[i].num_sweeps, nullptr);
   }
-  std::vector<bool> taken(runs.size(), false);
-  for (size_t i = 0; i < runs.size(); ++i) {
-    if (taken[i]) continue;
-    std::vector<ShuffledRun *> group;
-    for (size_t j = i; j < runs.size(); ++j) {
-      if (!taken[j] && runs[j]->num_sweeps == runs[i]->num_sweeps &&
-          shuffled_batch_kernel_for(runs[j]->m, kBytes, false)) {
-        group.push_back(runs[j].get());
-        taken[j] = true;
-      }
-    }
-    taken[i] = true;
-    if (group.size() >= 2) {
-      ASP_TRY(run_shuffled_group(group, sweep_ms));
-    } else {
-      // (a group of one all the same — its partners' geometry has no batched kernel: as above)
-      runs[i].reset();
-      ASP_TRY(alone(segs[shared[i]]));
-    }
-  }
+  ASP_TRY(setup_batch(runs));
+  // (a group of one all the same — its partners' geometry has no batched kernel: its run is dropped)
+  ASP_TRY(launch_batch(runs, sweep_ms, [&](size_t i) {
+    runs[i].reset();
+    return alone(segs[shared[i]]);
+  }));
   for (auto &r : runs) {
     if (r) ASP_TRY(r->finish_enqueue());
   }
@@ -3555,7 +3389,7 @@ extern "C" {
 
 int asp_sa_set_shuffled_launch(asp_sa_plan *p, int chains_per_group, int wavefronts) {
   if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  if (chains_per_group != 0 && !shuffled_kernel_for(chains_per_group, kBytes)) {
+  if (chains_per_group != 0 && !shuffled_form_exists(chains_per_group, kBytes)) {
     return asp::set_error(ASP_ERR_INVALID, "chains_per_group must be 0, 1, 2, 4 or 8");
   }
   if (wavefronts < 0 || wavefronts > 8) return asp::set_error(ASP_ERR_INVALID, "wavefronts must be 0..8");

@@ -234,6 +234,65 @@ def test_chains_per_group(order, per_group):
         c.close()
 
 
+LARGE_REPS, LARGE_SWEEPS = 5, 5
+_LARGE = {}
+
+
+def _large_chains(ham, j):
+    from annealing_sign_problem_amd import annealer as sa
+
+    return sa.Chains(ham, seed=4321 + j, repetitions=LARGE_REPS, replica_offset=2 + j)
+
+
+def _large(k):
+    """Two plans of the cluster of tests/test_gpu_sa_trace_shuffled.py::test_trace_in_the_layouts_of_large_clusters
+    (mean degree 6), a schedule, and the state of five chains per plan after the single-handle segment: the
+    reference, built once per size."""
+    from annealing_sign_problem_amd import annealer as sa
+    from annealing_sign_problem_amd import synthetic
+
+    if k not in _LARGE:
+        J, h, _ = synthetic.planted_cluster(k, seed=5, mean_degree=6.0)
+        hams = [sa.Hamiltonian(J, h) for _ in range(2)]
+        info = hams[0].info()
+        betas = sa.make_schedule(max(info.beta0_auto, 1e-3), min(max(info.beta1_auto, 1.0), 1e6), LARGE_SWEEPS)
+        want = []
+        for j, ham in enumerate(hams):
+            with _large_chains(ham, j) as single:
+                single.advance(betas, sweep_order="shuffled")
+                want.append(single.state())
+        _LARGE[k] = hams, betas, want
+    return _LARGE[k]
+
+
+@pytest.mark.parametrize("k,forced_m,expect_m", [(170000, 4, 4), (170000, 0, 1), (300000, 0, 1)])
+def test_batched_segments_in_the_layouts_of_large_clusters(k, forced_m, expect_m):
+    """The batched kernels in four bits (four chains per group, the last group ragged, and one chain) and
+    one bit per spin — the layout is whatever fits the LDS —: two handles of equal segment length in one
+    call are their single-handle segments."""
+    from annealing_sign_problem_amd import _lib
+    from annealing_sign_problem_amd import annealer as sa
+
+    lib = _lib.load()
+    hams, betas, want = _large(k)
+    for ham in hams:
+        _lib.check(lib.asp_sa_set_shuffled_launch(ham.plan(), forced_m, 0))
+    chains = [_large_chains(ham, j) for j, ham in enumerate(hams)]
+    try:
+        sa.advance_chains(chains, [betas, betas], sweep_order="shuffled")
+        for j, c in enumerate(chains):
+            assert _launch(hams[j])[0] == expect_m
+            got = c.state()
+            for name in STATE:
+                assert np.array_equal(got[name], want[j][name]), (j, name)
+            assert int(got["sweeps_done"]) == LARGE_SWEEPS
+    finally:
+        for c in chains:
+            c.close()
+        for ham in hams:
+            _lib.check(lib.asp_sa_set_shuffled_launch(ham.plan(), 0, 0))
+
+
 @pytest.mark.parametrize("order", [0, 1])
 def test_alternation_and_snapshots(order):
     from annealing_sign_problem_amd import annealer as sa

@@ -131,6 +131,47 @@ def test_equal_betas_are_advance_bit_for_bit(order, K, R):
     assert np.array_equal(got, want)
 
 
+_LARGE = {}
+
+
+def _large(k):
+    """The cluster of tests/test_gpu_sa_trace_shuffled.py::test_trace_in_the_layouts_of_large_clusters (mean
+    degree 6), built once per size."""
+    from annealing_sign_problem_amd import annealer as sa
+    from annealing_sign_problem_amd import synthetic
+
+    if k not in _LARGE:
+        J, h, _ = synthetic.planted_cluster(k, seed=5, mean_degree=6.0)
+        ham = sa.Hamiltonian(J, h)
+        info = ham.info()
+        _LARGE[k] = ham, float(np.sqrt(max(info.beta0_auto, 1e-3) * min(max(info.beta1_auto, 1.0), 1e6)))
+    return _LARGE[k]
+
+
+@pytest.mark.parametrize("trace", [True, False])
+@pytest.mark.parametrize("k,forced_m,expect_m", [(70000, 4, 4), (170000, 4, 4), (300000, 0, 1)])
+def test_equal_betas_are_advance_in_the_layouts_of_large_clusters(k, forced_m, expect_m, trace):
+    """The ladder kernels in a byte, four bits and one bit per spin (clusters beyond a word per spin; the
+    layout is whatever fits the LDS), five chains — at four per group the last group is ragged —: the
+    shuffled ladder segment with equal betas is the plain segment, in state and in trace."""
+    from annealing_sign_problem_amd import _lib
+    from annealing_sign_problem_amd import annealer as sa
+
+    ham, beta = _large(k)
+    _lib.check(_lib.load().asp_sa_set_shuffled_launch(ham.plan(), forced_m, 0))
+    R, sweeps = 5, 5
+    with sa.Chains(ham, seed=4321, repetitions=R, replica_offset=2) as ladder:
+        got = ladder.advance_ladder(np.full(R, beta), sweeps, sweep_order="shuffled", trace=trace)
+        assert _form(ham)[2] == expect_m
+        state = ladder.state()
+    with sa.Chains(ham, seed=4321, repetitions=R, replica_offset=2) as plain:
+        want = plain.advance(np.full(sweeps, beta), sweep_order="shuffled", trace=trace)
+        assert _form(ham)[2] == expect_m
+        _same_state(state, plain.state())
+    if trace:
+        assert got.shape == (R, sweeps + 1) and np.array_equal(got, want)
+
+
 def test_zero_sweeps_write_column_zero_only():
     from annealing_sign_problem_amd import annealer as sa
 

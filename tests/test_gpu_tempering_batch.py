@@ -150,6 +150,61 @@ def test_batched_ladder_segments_are_the_single_segments(order):
         c.close()
 
 
+LARGE_REPS, LARGE_SWEEPS = 5, 5
+_LARGE = {}
+
+
+def _large_chains(ham, j):
+    from annealing_sign_problem_amd import annealer as sa
+
+    return sa.Chains(ham, seed=4321 + j, repetitions=LARGE_REPS, replica_offset=2 + j)
+
+
+def _large(k):
+    """Two plans of the cluster of tests/test_gpu_sa_trace_shuffled.py::test_trace_in_the_layouts_of_large_clusters
+    (mean degree 6), a ladder, and the state of five chains per plan after the single-handle ladder segment:
+    the reference, built once per size."""
+    from annealing_sign_problem_amd import annealer as sa
+    from annealing_sign_problem_amd import synthetic
+
+    if k not in _LARGE:
+        J, h, _ = synthetic.planted_cluster(k, seed=5, mean_degree=6.0)
+        hams = [sa.Hamiltonian(J, h) for _ in range(2)]
+        ladder = _chain_betas(hams[0].info(), LARGE_REPS)
+        want = []
+        for j, ham in enumerate(hams):
+            with _large_chains(ham, j) as single:
+                single.advance_ladder(ladder, LARGE_SWEEPS, sweep_order="shuffled")
+                want.append(single.state())
+        _LARGE[k] = hams, ladder, want
+    return _LARGE[k]
+
+
+@pytest.mark.parametrize("k,forced_m,expect_m", [(170000, 4, 4), (170000, 0, 1), (300000, 0, 1)])
+def test_batched_ladder_segments_in_the_layouts_of_large_clusters(k, forced_m, expect_m):
+    """The batched ladder kernels in four bits (four chains per group, the last group ragged, and one chain)
+    and one bit per spin — the layout is whatever fits the LDS —: two handles in one call are their
+    single-handle ladder segments."""
+    from annealing_sign_problem_amd import _lib
+    from annealing_sign_problem_amd import annealer as sa
+
+    lib = _lib.load()
+    hams, ladder, want = _large(k)
+    for ham in hams:
+        _lib.check(lib.asp_sa_set_shuffled_launch(ham.plan(), forced_m, 0))
+    chains = [_large_chains(ham, j) for j, ham in enumerate(hams)]
+    try:
+        sa.advance_ladder_chains(chains, [ladder, ladder], LARGE_SWEEPS, sweep_order="shuffled")
+        for j, c in enumerate(chains):
+            assert _launch(hams[j])[0] == expect_m
+            _same_dict(c.state(), want[j])
+    finally:
+        for c in chains:
+            c.close()
+        for ham in hams:
+            _lib.check(lib.asp_sa_set_shuffled_launch(ham.plan(), 0, 0))
+
+
 # ---- 2. mixed call -------------------------------------------------------------------------------------
 
 def _raw_chains(ham, seed, repetitions):
