@@ -65,9 +65,15 @@ struct asp_sa_plan {
   std::vector<uint64_t> last_accepted;
   int num_cus = 256;
   size_t max_lds = 160 * 1024;
+  // asp_sa_set_lds_limit (0: the device's): the LDS per workgroup the SPIN LAYOUT of a sweep is chosen
+  // for, in both orders — spin_lds() wherever bytes / nibbles / bits / HBM is decided; what a launch
+  // may ask for, the order build's and the team sweep's LDS stay with max_lds
+  size_t spin_lds_limit = 0;
+  size_t spin_lds() const { return spin_lds_limit ? std::min(spin_lds_limit, max_lds) : max_lds; }
   asp::DeviceBuffer<uint32_t> color_block_start, block_width, ell_col, spin_of_pos, pos_of_spin;
   asp::DeviceBuffer<uint32_t> ell_col4;  // columns as LDS byte addresses of the wide layout (if it fits)
   int last_layout = 0;
+  int last_spin_layout = 0;  // asp_sa_last_spin_layout: the spin layout behind last_layout's 4 and 5 too
   asp::DeviceBuffer<uint64_t> ell_off;
   asp::DeviceBuffer<double> ell_val, field_pos;
   // per-call work buffers, grown on demand and kept (a plan is used by one thread at a time)

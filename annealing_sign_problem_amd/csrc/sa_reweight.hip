@@ -354,6 +354,7 @@ int asp_sa_plan_clone(asp_sa_plan const *p, asp_sa_plan **out) {
   c->force_m = p->force_m;
   c->force_threads = p->force_threads;
   c->force_packed = p->force_packed;
+  c->spin_lds_limit = p->spin_lds_limit;
   c->allow_wide = p->allow_wide;
   c->team_mode = p->team_mode;
   c->use_field_cache = p->use_field_cache;

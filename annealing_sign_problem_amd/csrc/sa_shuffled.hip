@@ -1523,14 +1523,28 @@ __device__ __forceinline__ void shuffled_sweep_body(const Args &a, const uint32_
         if (busy) {
           const uint32_t quads = held_quads;
           // the row sums in the order k = 0, 1, 2, ... of the row (= ascending column: the
-          // oracle's); the LDS gather of quad j + 1 is issued before the FMAs of quad j (past the
-          // block's last quad it reads whatever the registers held: harmless, never applied)
+          // oracle's); the gather of quad j + 1 is issued before the FMAs of quad j.  Past the
+          // block's last quad (and for quad 0 of a block of isolated spins) the column registers hold
+          // whatever request_quads left in them, and what is gathered there is never applied.  In the
+          // LDS layouts that gather is harmless: an LDS read of any address returns a value or zero and
+          // cannot fault, so it stays unconditional and the visit straight-line.  With the spins in HBM
+          // it would be a load from the chain's words + an undefined 32-bit offset, up to 4 GiB past
+          // them: there a gather is issued only for a quad the block has (`quads` is wave-uniform).
+          const auto loaded = [&]([[maybe_unused]] uint32_t j) {
+            if constexpr (GLOBAL) {
+              return j < quads;
+            } else {
+              return true;
+            }
+          };
           uint32_t sa[4], sb[4];
-          gather_quad<LAYOUT, PK>(hq[0], sa, gbase, spins);
+          if (loaded(0u)) gather_quad<LAYOUT, PK>(hq[0], sa, gbase, spins);
 #pragma unroll
           for (int j = 0; j < kHeldQuads; ++j) {
             if (static_cast<uint32_t>(j) < quads) {
-              if (j + 1 < kHeldQuads) gather_quad<LAYOUT, PK>(hq[j + 1], (j & 1) ? sa : sb, gbase, spins);
+              if (j + 1 < kHeldQuads && loaded(static_cast<uint32_t>(j) + 1u)) {
+                gather_quad<LAYOUT, PK>(hq[j + 1], (j & 1) ? sa : sb, gbase, spins);
+              }
               __builtin_amdgcn_sched_barrier(0);
               if constexpr (TEAMS > 1) {  // this team's chains to the low end (a plain VOP2 shift)
 #pragma unroll
@@ -2221,13 +2235,13 @@ struct ShuffledRun {
     // Clusters beyond the capacity of a byte per spin: four bits per spin and at most four chains
     // per workgroup, or a bit per spin and one chain (the largest order-2 models of the
     // sampled-cluster pipeline: 1.5e5..3.2e5 spins)
-    while (m > 1 && shuffled_layout_for(K, m, level_cap, words + level_cap, p->max_lds) < 0) m >>= 1;
+    while (m > 1 && shuffled_layout_for(K, m, level_cap, words + level_cap, p->spin_lds()) < 0) m >>= 1;
     if (m != wanted_m) {
       groups = (repetitions + m - 1) / m;
       padded = static_cast<uint64_t>(groups) * m;
     }
     {
-      const int fits = shuffled_layout_for(K, m, level_cap, words + level_cap, p->max_lds);
+      const int fits = shuffled_layout_for(K, m, level_cap, words + level_cap, p->spin_lds());
       if (fits == kNibbles || fits == kBits) teams = 1;  // (the packed layouts have one team)
     }
     // Lane packing: a level holds about K / levels spins.  When that is well below a wavefront, the
@@ -2258,7 +2272,7 @@ struct ShuffledRun {
       }
       while (want < 64u && 64u / want > groups) want <<= 1;
       while (want < 64u && sweep_lds_bytes(K, kWide, level_cap, static_cast<uint32_t>((K + want - 1) / want) + level_cap,
-                                           64u / want) > p->max_lds) {
+                                           64u / want) > p->spin_lds()) {
         want <<= 1;
       }
       if (want < 64u) {
@@ -2288,7 +2302,7 @@ struct ShuffledRun {
     }
     ASP_TRY(d_betas.alloc(chain_betas ? padded : num_sweeps));
     // (a byte per spin and group between chunks — or, beyond every LDS layout, the chains' spin words)
-    const bool spins_in_hbm = shuffled_layout_for(K, m, level_cap, words + level_cap, p->max_lds) == kGlobal;
+    const bool spins_in_hbm = shuffled_layout_for(K, m, level_cap, words + level_cap, p->spin_lds()) == kGlobal;
     ASP_TRY(d_state.alloc(static_cast<uint64_t>(groups) * K * (spins_in_hbm ? 4 : 1)));
     ASP_TRY(d_best.alloc(padded * words));
     ASP_TRY(d_ecur.alloc(padded));
@@ -2357,7 +2371,7 @@ struct ShuffledRun {
     const uint32_t max_quads = p->rq_max_quads;
     const uint32_t S = 1u << log_s;
     block_cap = blocks_of_spins() + level_cap;
-    if (packed_lanes && sweep_lds_bytes(K, kWide, level_cap, block_cap, 64u >> log_s) > p->max_lds) {
+    if (packed_lanes && sweep_lds_bytes(K, kWide, level_cap, block_cap, 64u >> log_s) > p->spin_lds()) {
       // (the capacities grew since setup(): back to blocks of 64 spins, one group per workgroup)
       packed_lanes = false;
       log_s = 6;
@@ -2366,7 +2380,7 @@ struct ShuffledRun {
     }
     // a word per spin (the one-instruction sign) when that fits the LDS beside the sweep's tables,
     // else a byte, else four bits (m <= 4) or one (m = 1)
-    layout = packed_lanes ? kWide : shuffled_layout_for(K, m, level_cap, block_cap, p->max_lds);
+    layout = packed_lanes ? kWide : shuffled_layout_for(K, m, level_cap, block_cap, p->spin_lds());
     if (layout < 0) {
       return asp::set_error(ASP_ERR_TOO_LARGE, "the shuffled sweep keeps its spins in LDS: %llu spins with %d "
                                                "chains per workgroup do not fit", (unsigned long long)K, m);
@@ -2780,6 +2794,7 @@ struct ShuffledRun {
     ASP_HIP_TRY(hipStreamSynchronize(p->stream));
     p->last_m = m;
     p->last_layout = 5;
+    p->last_spin_layout = layout;  // (lane packing: kWide)
     p->last_threads = static_cast<int>(waves * teams * 64);
     p->last_groups = static_cast<int>(groups);
     p->last_shuffled_log_s = log_s;
@@ -3203,7 +3218,7 @@ int setup_batch(std::vector<std::unique_ptr<ShuffledRun>> &runs) {
       // coupling, written once and read by EVERY workgroup of the problem — is the traffic of such a
       // model: 350 bytes per spin and sweep over M chains; the real kagome_36 order-2 models (3.5e4 ..
       // 3e5 spins, 64 chains each) moved 87 bytes per flip at M = 4.
-      if (saturates && r->p->host.num_spins * 4ull > r->p->max_lds * 15 / 16) r->forced_m = big_m;
+      if (saturates && r->p->host.num_spins * 4ull > r->p->spin_lds() * 15 / 16) r->forced_m = big_m;
     }
     r->batch_saturates = saturates;
     ASP_TRY(r->setup());

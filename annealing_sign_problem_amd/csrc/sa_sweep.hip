@@ -2037,10 +2037,10 @@ ColourLaunch choose_colour_launch(const asp_sa_plan *p, uint32_t repetitions, bo
   // One byte per position when that fits the LDS; otherwise one BIT per position, one replica
   // per workgroup (flips applied by wavefront ballot) — 8x the capacity.
   c.packed = p->force_packed != 0;
-  if (!c.packed && sweep_lds_bytes(L, kBytes) > p->max_lds) {
+  if (!c.packed && sweep_lds_bytes(L, kBytes) > p->spin_lds()) {
     // ... or, with chains enough for four per workgroup, four bits per position: twice the
     // capacity of bytes and still four replicas sharing every coupling load
-    if (!descent && !traced && c.m >= 4 && sweep_lds_bytes(L, kNibbles) <= p->max_lds) {
+    if (!descent && !traced && c.m >= 4 && sweep_lds_bytes(L, kNibbles) <= p->spin_lds()) {
       c.nibbles = true;
       c.m = 4;
     } else {
@@ -2048,13 +2048,13 @@ ColourLaunch choose_colour_launch(const asp_sa_plan *p, uint32_t repetitions, bo
     }
   }
   // not even a bit per position fits the LDS: keep the words in HBM (no size limit, slow)
-  c.global = p->force_packed == 2 || (c.packed && sweep_lds_bytes(L, kBits) > p->max_lds);
+  c.global = p->force_packed == 2 || (c.packed && sweep_lds_bytes(L, kBits) > p->spin_lds());
   if (c.packed) c.m = 1;
   // A word per position (SDWA sign trick) when four replicas share the
   // workgroup and the words fit; results do not depend on the layout.
   // (measured: +2..12 % with four replicas per workgroup, nothing with two)
   c.wide = !c.packed && !c.nibbles && !descent && p->allow_wide && c.m == 4 && p->ell_col4.ptr != nullptr &&
-           sweep_lds_bytes(L, kWide) <= p->max_lds;
+           sweep_lds_bytes(L, kWide) <= p->spin_lds();
   c.layout = c.global ? kGlobal : (c.packed ? kBits : (c.nibbles ? kNibbles : (c.wide ? kWide : kBytes)));
   return c;
 }
@@ -2308,6 +2308,14 @@ int asp_sa_set_wide(asp_sa_plan *p, int allow) {
 
 int asp_sa_last_layout(asp_sa_plan const *p) { return p ? p->last_layout : -1; }
 
+int asp_sa_last_spin_layout(asp_sa_plan const *p) { return p ? p->last_spin_layout : -1; }
+
+int asp_sa_set_lds_limit(asp_sa_plan *p, uint64_t bytes) {
+  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
+  p->spin_lds_limit = static_cast<size_t>(std::min<uint64_t>(bytes, p->max_lds));  // (0, or >= the device's: the device's)
+  return ASP_OK;
+}
+
 int asp_sa_set_packed(asp_sa_plan *p, int packed) {
   if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
   p->force_packed = packed < 0 ? 0 : (packed > 2 ? 2 : packed);
@@ -2542,6 +2550,7 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
   }
   p->last_m = m;
   p->last_layout = team >= 2 ? 4 : layout;
+  p->last_spin_layout = layout;
   p->last_threads = threads;
   p->last_groups = static_cast<int>(groups);
   ASP_HIP_TRY(hipEventElapsedTime(&p->last_sweep_ms, p->ev[1], p->ev[2]));
@@ -2674,7 +2683,7 @@ int chains_advance_colour(asp_sa_chains *c, double const *betas, double const *c
   }
   ASP_HIP_TRY(hipStreamSynchronize(s));
   p->last_m = m;
-  p->last_layout = layout;
+  p->last_layout = p->last_spin_layout = layout;
   p->last_threads = threads;
   p->last_groups = static_cast<int>(groups);
   ASP_HIP_TRY(hipEventElapsedTime(&p->last_sweep_ms, p->ev[1], p->ev[2]));
@@ -2886,7 +2895,7 @@ int batch_waves_index(uint32_t waves) {
 }
 int batch_layout_in_lds(const asp_sa_plan *p) {  // kWide or kBytes
   const asp::SaHostLayout &L = p->host;
-  return p->allow_wide && p->ell_col4.ptr && L.num_spins <= kBatchWideMax && sweep_lds_bytes(L, kWide) <= p->max_lds
+  return p->allow_wide && p->ell_col4.ptr && L.num_spins <= kBatchWideMax && sweep_lds_bytes(L, kWide) <= p->spin_lds()
              ? kWide
              : kBytes;
 }
@@ -3136,9 +3145,9 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
     // LOSES against running those problems one after the other as team sweeps, every chain spread
     // over four CUs (a round of 64 clusters of the pipeline, largest model 157 706 spins: 5.9 s
     // against 4.05 s; ASP_BATCH_BITS=1 puts them into the shared launches all the same).
-    const bool bytes_fit = L.num_spins > 0 && sweep_lds_bytes(L, kBytes) <= p->max_lds;
-    const bool nibbles_fit = L.num_spins > 0 && sweep_lds_bytes(L, kNibbles) <= p->max_lds && batch_nibbles;
-    const bool bits_fit = L.num_spins > 0 && sweep_lds_bytes(L, kBits) <= p->max_lds && batch_bits;
+    const bool bytes_fit = L.num_spins > 0 && sweep_lds_bytes(L, kBytes) <= p->spin_lds();
+    const bool nibbles_fit = L.num_spins > 0 && sweep_lds_bytes(L, kNibbles) <= p->spin_lds() && batch_nibbles;
+    const bool bits_fit = L.num_spins > 0 && sweep_lds_bytes(L, kBits) <= p->spin_lds() && batch_bits;
     if (!(bytes_fit || nibbles_fit || bits_fit) || p->force_m || p->force_threads || p->force_packed) {
       alone.push_back(i);
       continue;
@@ -3369,7 +3378,7 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
                             h_accepted.begin() + off[k].stat + it.repetitions);
     const int c = class_of(entries[k]);
     p->last_m = m_of_class[c];
-    p->last_layout = layout_of_class(c);
+    p->last_layout = p->last_spin_layout = layout_of_class(c);
     p->last_threads = static_cast<int>(64u * waves_of_class(c));
     p->last_groups = static_cast<int>(off[k].groups);
     p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_batch_last_ms
@@ -3418,7 +3427,7 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
   for (uint32_t i = 0; i < count; ++i) {
     const asp_sa_plan *p = segs[i].chains->plan;
     const SaHostLayout &L = p->host;
-    const bool bytes_fit = sweep_lds_bytes(L, kBytes) <= p->max_lds;
+    const bool bytes_fit = sweep_lds_bytes(L, kBytes) <= p->spin_lds();
     if (segs[i].trace || !bytes_fit || p->force_m || p->force_threads || p->force_packed) {
       alone.push_back(i);
       continue;
@@ -3629,7 +3638,7 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
     asp_sa_plan *p = segs[entries[k].seg].chains->plan;
     const int cl = class_of(entries[k]);
     p->last_m = m;
-    p->last_layout = cl % 2 == 0 ? kWide : kBytes;
+    p->last_layout = p->last_spin_layout = cl % 2 == 0 ? kWide : kBytes;
     p->last_threads = static_cast<int>(64u * kWaves[cl / 2]);
     p->last_groups = static_cast<int>(off[k].groups);
     p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_chains_batch_last_ms
@@ -3710,7 +3719,7 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
     }
     live.push_back(i);
     const bool forced = p->force_m || p->force_threads || p->force_packed || p->team_mode >= 2;
-    if (forced || sweep_lds_bytes(p->host, kBytes) > p->max_lds) {
+    if (forced || sweep_lds_bytes(p->host, kBytes) > p->spin_lds()) {
       alone.push_back(i);
     } else {
       shared.push_back(i);
@@ -3916,7 +3925,7 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
     p->last_tracked.clear();  // (the shared launches bring no per-chain statistics back)
     p->last_accepted.clear();
     p->last_m = 1;
-    p->last_layout = kBytes;
+    p->last_layout = p->last_spin_layout = kBytes;
     p->last_threads = static_cast<int>(64u * kBatchWaves[members[k].cls]);
     p->last_groups = 1;
     p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_greedy_batch_last_ms

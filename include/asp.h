@@ -456,7 +456,7 @@ int asp_sa_plan_reweight(asp_sa_plan *p, uint64_t nnz, int64_t const *indptr, in
 float asp_sa_plan_reweight_last_ms(asp_sa_plan const *p);
 /* A second plan with the structure and the numbers of *p, made without the host preprocessing: its own
  * stream, events, work buffers and arrays (it outlives *p), the launch settings of *p (asp_sa_set_launch,
- * _set_packed, _set_wide, _set_team, _set_field_cache, _set_post, _set_shuffled_launch, _set_shuffled_teams,
+ * _set_packed, _set_lds_limit, _set_wide, _set_team, _set_field_cache, _set_post, _set_shuffled_launch, _set_shuffled_teams,
  * _set_greedy_tree) and none of its chains.  What asp_sa_greedy_batch and the other batched calls need
  * to solve several reweighted copies of one model at once: they refuse one plan twice. */
 int asp_sa_plan_clone(asp_sa_plan const *p, asp_sa_plan **out);
@@ -484,24 +484,42 @@ int asp_sa_shuffled_order_host(uint64_t num_spins, int64_t const *indptr, int32_
  * replicas_per_group in {1,2,4,8}; threads multiple of 64, <= 1024. */
 int asp_sa_set_launch(asp_sa_plan *p, int replicas_per_group, int threads);
 
-/* Layout of the spins: by default one LDS byte per spin position (bit m = replica m of the
+/* Layout of the spins in the COLOUR order (the shuffled order ignores this setting and
+ * asp_sa_set_wide): by default one LDS byte per spin position (bit m = replica m of the
  * workgroup); automatically one LDS BIT per position with one replica per workgroup when the
- * bytes do not fit (K beyond ~1.4e5), and the same bit words kept in HBM when not even the
- * bits fit (K beyond ~1.3e6; slow, but no size limit).  packed = 1 / 2 forces the LDS-bit /
- * HBM-bit layout (tests, measurements), 0 restores the automatic choice.  Results never
- * depend on the layout. */
+ * bytes do not fit the LDS of a workgroup (160 KiB at 74 bytes per block of 64 positions, tables
+ * included: ~1.4e5 positions — the one threshold the comments below mean by "the capacity of a byte
+ * per position"), and the same bit words kept in HBM when not even the bits fit (8 bytes per block:
+ * beyond ~1.3e6; slow, but no size limit).  packed = 1 / 2 forces the LDS-bit / HBM-bit layout
+ * (tests, measurements), 0 restores the automatic choice; asp_sa_set_lds_limit moves the thresholds
+ * themselves.  Results never depend on the layout. */
 int asp_sa_set_packed(asp_sa_plan *p, int packed);
 
 /* With four replicas per workgroup and up to ~4e4 spins the kernel keeps a 32-bit word
  * per position (one byte per replica), which makes the sign of a coupling term a single SDWA
  * instruction.  allow = 0 keeps the byte layout (tests, measurements); default 1.
- * Beyond the capacity of a byte per position (~1.4e5 spins) and with chains enough for four per
- * workgroup, four bits per position (up to ~2.4e5 spins; flips are LDS atomics); otherwise a bit
- * per position and one chain per workgroup.
+ * Beyond the capacity of a byte per position (asp_sa_set_packed's threshold, ~1.4e5) and with chains
+ * enough for four per workgroup, four bits per position (42 bytes per block: up to ~2.4e5; flips are
+ * LDS atomics); otherwise a bit per position and one chain per workgroup.
  * asp_sa_last_layout: 0 = bytes, 1 = bits in LDS, 2 = words, 3 = bits in HBM, 6 = nibbles, for
  * the last anneal/greedy call. */
 int asp_sa_set_wide(asp_sa_plan *p, int allow);
 int asp_sa_last_layout(asp_sa_plan const *p);
+/* Tests, measurements: choose the spin layouts of this plan's sweeps, in both orders, as if the
+ * device had `bytes` of LDS per workgroup.  0 restores the device's; values above it are clamped.
+ * Only the choice between words, bytes, nibbles, bits and HBM (and, in the shuffled order, the chains
+ * per workgroup and the lane packing that follow from it) looks at the limit: a launch still asks for
+ * the LDS it needs, and the order build and the team sweep keep the device's.  A limit that not even
+ * the shuffled order's HBM layout fits (its per-sweep tables stay in LDS) is ASP_ERR_TOO_LARGE with
+ * nothing launched; the colour order's HBM layout fits any limit.  Handles hold nothing that depends
+ * on the layout between segments: the limit may change while they are live.  asp_sa_plan_clone copies
+ * it.  Results never depend on it. */
+int asp_sa_set_lds_limit(asp_sa_plan *p, uint64_t bytes);
+/* Spin layout of the plan's last sweep call in either order, in asp_sa_last_layout's codes
+ * (0 bytes, 1 bits in LDS, 2 words, 3 words in HBM, 6 nibbles; lane packing reports 2; a team launch
+ * its bits, 1).  asp_sa_last_layout itself is unchanged (5 for the shuffled order, 4 for a team
+ * launch).  NULL plan: -1. */
+int asp_sa_last_spin_layout(asp_sa_plan const *p);
 
 /* Few chains on a large cluster (chains <= CUs / 2, e.g. the reference's default of 64
  * repetitions): each chain is spread over a TEAM of 2, 4 or 8 workgroups that split every colour

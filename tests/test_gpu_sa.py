@@ -1397,11 +1397,12 @@ def test_shuffled_fill_statistics():
     assert fills[False][0] < 0.3 < fills[True][0]  # ~9 spins per level: 64-lane blocks are mostly padding
 
 
-def test_shuffled_sweep_with_the_spins_in_hbm(monkeypatch):
+def test_shuffled_sweep_with_the_spins_in_hbm():
     """Beyond a bit per spin in LDS (~6e5 spins) the default visiting order keeps a chain's spins as
     words in HBM (one chain per workgroup, every gather an L2 access): slow, but `sa.anneal` then
     accepts a cluster of any size in its default order, as it does in the colour order.  Parity on
-    a cluster that needs it (sparse, so that the oracle finishes), and forced on a small one."""
+    a cluster that needs it (sparse, so that the oracle finishes); the same layout on small clusters,
+    chosen through asp_sa_set_lds_limit, at every edge: tests/test_gpu_sa_small_layouts.py."""
     from annealing_sign_problem_amd import _lib
     from annealing_sign_problem_amd import annealer as sa
 
