@@ -164,6 +164,15 @@ def ising_elements(keys, psi, other_keys, other_coeffs, other_counts):
     return indices[:n], member[:n].astype(bool), elements[:n], offsets
 
 
+def _takes_host_route(error) -> bool:
+    """A refusal of the fused coupling build after which the host route (``ising_elements`` + scipy)
+    does the job: ASP_ERR_INVALID (duplicates with one-directional matrix elements), and the ONE
+    ASP_ERR_TOO_LARGE of the emit pass whose rows do not fit the LDS of a workgroup — 1137 bonds or
+    more, i.e. all-to-all models from 49 sites.  Any other size refusal stays an
+    error."""
+    return error.code == -3 or (error.code == -4 and "bytes of LDS" in str(error))
+
+
 def make_ising_model(
     spins,
     quantum_hamiltonian,
@@ -213,7 +222,7 @@ def make_ising_model(
             indptr, col, val = quantum_hamiltonian.device().ising_csr(spins, psi)
             ising_hamiltonian = sa.Hamiltonian.from_canonical_csr(indptr, col, val, field)
         except _lib.AspError as error:
-            if error.code != -3:
+            if not _takes_host_route(error):
                 raise
     if ising_hamiltonian is None:
         other_spins, other_coeffs, other_counts = _batched_apply(quantum_hamiltonian, spins)
@@ -265,7 +274,7 @@ def make_ising_models(clusters, quantum_hamiltonian, log_psis=None, log_psi_fn=N
         indptr, col, val = quantum_hamiltonian.device().ising_csr_segments(
             np.concatenate([p[0] for p in prepared]), np.concatenate([p[2] for p in prepared]), offsets)
     except _lib.AspError as error:
-        if error.code != -3:
+        if not _takes_host_route(error):
             raise
         return loop()
     models = []
@@ -377,7 +386,7 @@ def reweight_ising_model(
     try:
         indptr, col, val = operator.device().ising_csr(spins, psi)
     except _lib.AspError as error:
-        if error.code != -3:
+        if not _takes_host_route(error):
             raise
         return fresh()
     try:

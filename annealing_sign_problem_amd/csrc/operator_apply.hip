@@ -1244,6 +1244,16 @@ int asp_operator_extend(asp_operator const *op, uint64_t n, uint64_t const *keys
   *count = 0;
   if (n && !keys) return asp::set_error(ASP_ERR_INVALID, "null keys");
   if (n == 0) return ASP_OK;
+  // the sort below looks at the bits [0, number_spins) only: a key with a higher bit (and with it
+  // its targets) would come out in the wrong place, or twice
+  if (op->number_spins < 64) {
+    for (uint64_t i = 0; i < n; ++i) {
+      if (keys[i] >> op->number_spins) {
+        return asp::set_error(ASP_ERR_INVALID, "key %llu has a bit at or above site %u",
+                              (unsigned long long)i, op->number_spins);
+      }
+    }
+  }
   asp::ScopedStream scoped;
   ASP_TRY(scoped.acquire());
   hipStream_t stream = scoped.stream;

@@ -315,7 +315,10 @@ int asp_operator_ising_segments(asp_operator const *op, uint64_t num_segments, u
 
 /* make_hamiltonian_extension's state set (common.py:516-522): the sorted unique
  * union of every key's targets (its own diagonal entry included).  *count receives
- * the size; out needs capacity >= *count (capacity 0 / NULL sizes it). */
+ * the size; out needs capacity >= *count (capacity 0 / NULL sizes it); *count > capacity is
+ * ASP_ERR_INVALID with *count set and out not written.  Keys need not be sorted or unique, but
+ * every key must lie below 2^number_spins: the set is sorted on the bits [0, number_spins), so a
+ * key with a higher bit is refused with ASP_ERR_INVALID before any launch (*count = 0). */
 int asp_operator_extend(asp_operator const *op, uint64_t n, uint64_t const *keys,
                         uint64_t capacity, uint64_t *out, uint64_t *count);
 
