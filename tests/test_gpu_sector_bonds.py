@@ -1,50 +1,23 @@
 """The Ising model of a whole symmetry sector, built on the device from the sector's ELL matrix and a
 state vector (asp_sector_bonds_create, BondStatistics.from_sector): the law is restated in
-numpy on the downloaded arrays and the handle's statistics must equal it exactly — on the whole sector
-of heisenberg_kagome_18 with its ground state, and on two small sectors of tests/sector_cases.py with
-vectors that have zeros and both signs.  Against the CSR route on the same basis (make_ising_model +
-BondStatistics) the two roundings may differ, so only the number of bonds and the frustration of the
-bonds that are not tiny are compared."""
+numpy (tests/sector_bond_cases.py) and the handle's statistics must equal it exactly — on the whole sector
+of heisenberg_kagome_18 with its ground state, on two small sectors of tests/sector_cases.py with
+vectors that have zeros and both signs, and on the synthetic ELL inputs of tests/sector_bond_cases.py,
+which reach the sizes, slot patterns and roundings that no real operator gives
+(tests/test_sector_bond_cases.py shows which wrong reading of the law each of them would catch).  Against
+the CSR route on the same basis (make_ising_model + BondStatistics) the two roundings may differ, so only
+the number of bonds and the frustration of the bonds that are not tiny are compared."""
 import numpy as np
 import pytest
 
 import bond_cases
+import sector_bond_cases
 import sector_cases
+from sector_bond_cases import sector_law
 
 pytestmark = pytest.mark.gpu
 
-
-def sector_law(idx, val, psi):
-    """CSR ``(indptr, indices, data)`` of the sector's Ising model, columns ascending.
-    H_ij = sum in slot order, from +0.0, of val over the slots of row i with idx == j;
-    M_ij = (H_ij |psi_j|) |psi_i|; J_ij = 0.5 (M_ij + M_ji); kept iff J_ij != 0, j != i."""
-    width, n = idx.shape
-    rows = np.repeat(np.arange(n, dtype=np.int64), width)
-    cols = idx.T.astype(np.int64).ravel()     # row i's slots, in slot order
-    vals = val.T.ravel()
-    key = rows * n + cols
-    order = np.argsort(key, kind="stable")    # (slot order survives within a pair)
-    key, vals = key[order], vals[order]
-    pairs, start, count = np.unique(key, return_index=True, return_counts=True)
-    group = np.repeat(np.arange(pairs.shape[0]), count)
-    rank = np.arange(key.shape[0]) - start[group]
-    h = np.zeros(pairs.shape[0])              # +0.0
-    for r in range(int(count.max())):         # one addition per pair and pass: strictly in slot order
-        now = rank == r
-        h[group[now]] = h[group[now]] + vals[now]
-    i, j = pairs // n, pairs % n
-    off = i != j
-    pairs, i, j, h_ij = pairs[off], i[off], j[off], h[off]
-    at = np.searchsorted(pairs, j * n + i)
-    found = (at < pairs.shape[0]) & (pairs[np.minimum(at, pairs.shape[0] - 1)] == j * n + i)
-    h_ji = np.where(found, h_ij[np.minimum(at, pairs.shape[0] - 1)], 0.0)
-    a = np.abs(psi)
-    m_ij = (h_ij * a[j]) * a[i]
-    m_ji = (h_ji * a[i]) * a[j]
-    coupling = 0.5 * (m_ij + m_ji)
-    keep = coupling != 0
-    indptr = np.concatenate([[0], np.cumsum(np.bincount(i[keep], minlength=n))]).astype(np.int64)
-    return indptr, j[keep].astype(np.int32), coupling[keep]
+SUMMARY = ("num_spins", "stored", "bonds", "frustrated", "rows_with_bonds", "strongest_frustrated")
 
 
 def _sector(operator):
@@ -54,7 +27,7 @@ def _sector(operator):
     return sector_ed.SectorMatrix(operator, representatives, norms)
 
 
-def _check(matrix, psi):
+def _check(matrix, psi, may_be_empty=False):
     """The handle of (matrix, psi) against the restated law; returns (stats, law's CSR, law)."""
     from annealing_sign_problem_amd.bonds import BondStatistics, log_edges
 
@@ -63,22 +36,125 @@ def _check(matrix, psi):
     host_psi = psi.cpu().numpy()
     indptr, indices, data = sector_law(idx, val, host_psi)
     law = bond_cases.bond_law(indptr, indices, data, bond_cases.pack(np.where(host_psi >= 0, 1, -1)))
-    assert law["bonds"] > 0 and law["bonds"] == law["stored"]
+    assert (may_be_empty or law["bonds"] > 0) and law["bonds"] == law["stored"]
     stats = BondStatistics.from_sector(matrix, psi)
+    _equals(stats, law)
+    if law["bonds"] == 0:
+        return stats, (indptr, indices, data), law
+    edges = sector_bond_cases.histogram_edges(law, log_edges)
+    got, want = stats.histogram(edges), bond_cases.histogram_law(law, edges)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and got[2:] == want[2:]
+    assert got[3] == 0 and int(got[0].sum() + got[1].sum()) + got[2] == law["bonds"]
+    return stats, (indptr, indices, data), law
+
+
+def _equals(stats, law):
+    """Summary, rows() and magnitudes() of the handle against a bond_cases.bond_law result."""
     summary = stats.summary
-    for field in ("num_spins", "stored", "bonds", "frustrated", "rows_with_bonds", "strongest_frustrated"):
+    for field in SUMMARY:
         assert summary[field] == law[field], field
     assert summary["max_abs"] == law["max_abs"] and summary["min_abs"] == law["min_abs"]
     strongest, col, frustrated = stats.rows()
     assert np.array_equal(strongest, law["strongest"]) and np.array_equal(col, law["strongest_col"])
     assert np.array_equal(frustrated, law["strongest_frustrated_rows"])
-    hi = np.log(law["max_abs"])
-    edges = log_edges(max(hi - 20.0, np.log(law["min_abs"])), hi, 50)
-    got, want = stats.histogram(edges), bond_cases.histogram_law(law, edges)
-    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and got[2:] == want[2:]
-    assert got[3] == 0 and int(got[0].sum() + got[1].sum()) + got[2] == law["bonds"]
     assert np.array_equal(stats.magnitudes(), bond_cases.magnitudes_law(law))
-    return stats, (indptr, indices, data), law
+
+
+class _Ell:
+    """What from_sector reads of a sector_ed.SectorMatrix: n, width and the two device arrays."""
+
+    def __init__(self, idx, val):
+        import torch
+
+        self.width, self.n = idx.shape
+        self.idx = torch.tensor(idx.view(np.int32), device="cuda")  # (the device array holds the u32 as i32)
+        self.val = torch.tensor(val, device="cuda")
+
+
+def _upload(name):
+    import torch
+
+    idx, val, psi = sector_bond_cases.CASES[name]
+    return _Ell(idx, val), torch.tensor(psi, device="cuda")
+
+
+def _same_bits(tensor, array):
+    host = tensor.cpu().numpy()
+    return host.shape == array.shape and host.tobytes() == array.tobytes()
+
+
+@pytest.mark.parametrize("name", list(sector_bond_cases.CASES))
+def test_synthetic_case_equals_the_restated_law(name):
+    idx, val, psi = sector_bond_cases.CASES[name]
+    matrix, device_psi = _upload(name)
+    n = psi.shape[0]
+    stats, (indptr, indices, data), law = _check(matrix, device_psi, may_be_empty=True)
+    with stats:
+        assert law["stored"] == sector_bond_cases.law(name)[0][-1] == stats.summary["stored"]
+        # the inputs are only read
+        assert _same_bits(matrix.idx, idx.view(np.int32)) and _same_bits(matrix.val, val)
+        assert _same_bits(device_psi, psi)
+        # other signs on the device-built matrix: all plus, a bond is frustrated iff its coupling is positive
+        first = stats.summary
+        rows = stats.rows()
+        plus = bond_cases.bond_law(indptr, indices, data, bond_cases.pack(np.ones(n)))
+        assert plus["frustrated"] == np.count_nonzero(data > 0)
+        assert stats.set_signs(bond_cases.pack(np.ones(n))) is stats
+        assert stats.summary["frustrated"] == np.count_nonzero(data > 0)
+        _equals(stats, plus)
+        stats.set_signs(bond_cases.pack(sector_bond_cases.sector_signs(psi)))  # and back
+        assert stats.summary == first
+        assert all(np.array_equal(a, b) for a, b in zip(stats.rows(), rows))
+        _equals(stats, law)
+
+
+def _coupled_slot(idx, val, psi):
+    """(slot, row) of a used slot with a value whose two states both have an amplitude."""
+    width, n = idx.shape
+    for i in range(n):
+        for k in range(width):
+            j = int(idx[k, i])
+            if j != i and val[k, i] != 0 and psi[i] != 0 and psi[j] != 0:
+                return k, i
+    raise AssertionError("no coupled slot")
+
+
+def test_non_finite_input_is_refused_and_the_repaired_input_is_not():
+    from annealing_sign_problem_amd import _lib
+    from annealing_sign_problem_amd.bonds import BondStatistics
+
+    idx, val, psi = sector_bond_cases.CASES["n65"]
+    slot, state = _coupled_slot(idx, val, psi)
+    matrix, device_psi = _upload("n65")
+    for where, bad in (("psi", np.nan), ("psi", np.inf), ("psi", -np.inf), ("val", np.nan)):
+        target = device_psi if where == "psi" else matrix.val
+        at = (state,) if where == "psi" else (slot, state)
+        good = target[at].item()
+        target[at] = bad
+        with pytest.raises(_lib.AspError) as err:
+            BondStatistics.from_sector(matrix, device_psi)
+        assert err.value.code == -3 and "not finite" in str(err.value), (where, bad)  # ASP_ERR_INVALID
+        target[at] = good
+        assert _same_bits(device_psi, psi) and _same_bits(matrix.val, val)
+        stats, _, _ = _check(matrix, device_psi)  # the same inputs, repaired: the law again
+        stats.release()
+
+
+def test_from_sector_checks_its_state_vector():
+    import torch
+
+    from annealing_sign_problem_amd.bonds import BondStatistics
+
+    idx, val, psi = sector_bond_cases.CASES["n65"]
+    matrix, device_psi = _upload("n65")
+    strided = torch.tensor(np.repeat(psi, 2), device="cuda")[::2]
+    assert strided.shape == device_psi.shape and torch.equal(strided, device_psi) and not strided.is_contiguous()
+    for bad in (device_psi.to(torch.float32), device_psi.cpu(), strided, device_psi[:64],
+                torch.cat([device_psi, device_psi[:1]]), device_psi.reshape(1, -1)):
+        with pytest.raises(ValueError):
+            BondStatistics.from_sector(matrix, bad)
+    stats, _, _ = _check(matrix, device_psi)
+    stats.release()
 
 
 @pytest.mark.parametrize("name", ["ring12 any magnetisation, field on all bonds",
@@ -91,7 +167,6 @@ def test_small_sector_equals_the_restated_law(name):
     rng = np.random.default_rng(11)
     psi = rng.standard_normal(matrix.n)
     psi[rng.random(matrix.n) < 0.1] = 0.0  # states without amplitude have no bonds
-    psi[1] = -0.0
     psi /= np.linalg.norm(psi)
     idx = matrix.idx.cpu().numpy()
     # the duplicate-keeping law is exercised: some row reaches one target through several slots
