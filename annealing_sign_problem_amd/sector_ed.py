@@ -143,6 +143,7 @@ def lanczos_ground_state(matrix: SectorMatrix, tol: float = 1e-9, max_iterations
     energy, ritz, residual = None, None, None
     tick = time.time()
     used = 0
+    scale = 1.0
     for j in range(steps):
         basis[j].copy_(v)
         matrix.matvec(v, out=w)
@@ -152,7 +153,11 @@ def lanczos_ground_state(matrix: SectorMatrix, tol: float = 1e-9, max_iterations
             w -= torch.mv(basis[: j + 1].t(), torch.mv(basis[: j + 1], w))
         beta = float(torch.linalg.vector_norm(w))
         used = j + 1
-        done = beta < 1e-13 or used == steps
+        # breakdown (the Krylov space is complete) is judged against the size of the matrix as the
+        # recurrence has seen it, with the floor of 1 that the convergence criterion has too: the
+        # same matrix times a constant > 1 stops at the same step
+        scale = max(scale, abs(alphas[-1]), beta)
+        done = beta < 1e-13 * scale or used == steps
         if used % 5 == 0 or done:
             if used == 1:  # a one-dimensional Krylov space (n = 1, or the start vector is an eigenvector)
                 theta, s = np.asarray(alphas), np.ones((1, 1))
@@ -263,6 +268,7 @@ def lanczos_two_pass(matrix, tol: float = 1e-9, max_iterations: int = 1000, seed
         total = torch.zeros_like(v) if combine is not None else None
         alphas, betas = [], []
         beta = 0.0
+        scale = 1.0
         for j in range(steps):
             if total is not None:
                 total.add_(v, alpha=float(combine[j]))
@@ -276,7 +282,8 @@ def lanczos_two_pass(matrix, tol: float = 1e-9, max_iterations: int = 1000, seed
             alphas.append(alpha)
             beta = float(torch.linalg.vector_norm(w))
             if combine is None:
-                done = beta < 1e-13 or j + 1 == steps
+                scale = max(scale, abs(alpha), beta)  # (see lanczos_ground_state)
+                done = beta < 1e-13 * scale or j + 1 == steps
                 if (j + 1) % 10 == 0 or done:
                     if len(alphas) == 1:  # a one-dimensional Krylov space (see lanczos_ground_state)
                         theta, s = np.array([alphas[0]]), np.ones((1, 1))
