@@ -33,7 +33,7 @@
 //     (integer adds commute, so the parallel reduction is deterministic); the
 //     best configuration is snapshotted to HBM at sweep granularity;
 //   * DESCENT instantiation: strict-descent sweeps without random numbers (the
-//     greedy solver's relaxation); k_sa_descent_batch runs the descents of many
+//     greedy solver's relaxation); k_sa_sweep_batch<.., DescentProblem> runs the descents of many
 //     problems in one launch, each workgroup stopping after its first sweep
 //     without a flip.
 // f64-VALU- and vector-memory-bound integer+f64 work: no MFMA.
@@ -401,7 +401,7 @@ __device__ __forceinline__ void snapshot(const uint8_t *spins, const Args &a, ui
 // How a descent ends (DESCENT only).  NoEarlyStop: all num_sweeps sweeps run (the annealer; the
 // chunks of asp_sa_greedy, whose host looks at the flip count between chunks).  StopWhenStill:
 // the workgroup leaves after the first sweep that flipped nothing and reports the number of
-// sweeps it performed (k_sa_descent_batch).
+// sweeps it performed (k_sa_sweep_batch over DescentProblem).
 struct NoEarlyStop {
   static constexpr bool kEnabled = false;
 };
@@ -1022,7 +1022,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
       fin.best_perm = res.cur_perm;
       snapshot<M, LAYOUT>(spins, fin, group, (1u << M) - 1u);
     } else {
-      // (arguments in the constant address space, k_sa_sweep_resume_batch: what snapshot() reads of
+      // (arguments in the constant address space, k_sa_sweep_batch's segments: what snapshot() reads of
       // them, with the current words as the target; k_sa_sweep_resume keeps its code)
       struct FinalWords {
         uint64_t *best_perm;
@@ -1039,16 +1039,11 @@ __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep(SweepArgs a) {
   sa_sweep_body<M, DESCENT, LAYOUT, SweepArgs, NoEarlyStop, NoResume, ALIGNED>(a, blockIdx.x);
 }
 
-// One segment of an asp_sa_chains handle in the colour order (asp_sa_chains_advance, order 0).
-template <int M, int LAYOUT>
-__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_resume(SweepArgs a, Resume r) {
-  sa_sweep_body<M, false, LAYOUT, SweepArgs, NoEarlyStop, Resume>(a, blockIdx.x, NoEarlyStop{}, r);
-}
-
-// One ladder segment of a handle in the colour order (asp_sa_chains_advance_ladder, order 0).
-template <int M, int LAYOUT>
-__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_ladder(SweepArgs a, ResumeLadder r) {
-  sa_sweep_body<M, false, LAYOUT, SweepArgs, NoEarlyStop, ResumeLadder>(a, blockIdx.x, NoEarlyStop{}, r);
+// One segment of an asp_sa_chains handle in the colour order: Res = Resume (asp_sa_chains_advance, order 0)
+// or ResumeLadder (asp_sa_chains_advance_ladder, order 0).
+template <int M, int LAYOUT, typename Res>
+__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_resume(SweepArgs a, Res r) {
+  sa_sweep_body<M, false, LAYOUT, SweepArgs, NoEarlyStop, Res>(a, blockIdx.x, NoEarlyStop{}, r);
 }
 
 // Many PROBLEMS in one launch (asp_sa_anneal_batch): workgroup -> (problem, group of M replicas)
@@ -1062,14 +1057,43 @@ struct BatchSlot {
   uint32_t problem;  // 0xFFFFFFFF: padding slot
   uint32_t group;
 };
+template <typename Problem>  // SweepArgs, or one of the wrappers below
 struct BatchArgs {
-  const SweepArgs *problems;
+  const Problem *problems;
   const BatchSlot *slots;  // [8][slots_per_xcd]
   uint32_t slots_per_xcd;
 };
 
-template <int M, int LAYOUT>
-__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_batch(BatchArgs b) {
+// What a launch needs beyond SweepArgs lives in a wrapper, so that SweepArgs — shared by every
+// annealing kernel, whose register assignment follows its layout — stays as it is.
+//
+// Many DESCENTS in one launch (asp_sa_greedy_batch): every problem is one chain, so its group is
+// always 0.  Each problem starts from its own configuration (s.x0_perm), runs strict-descent sweeps
+// until one flips nothing or s.num_sweeps (the caller's max_sweeps) are done — decided by the workgroup
+// that owns the whole chain, with no host round trip — and leaves the number of sweeps in its own word.
+struct DescentProblem {
+  SweepArgs s;            // betas: nullptr (never read); num_sweeps: the cap; trace: nullptr
+  const uint64_t *x0;     // the tree's configuration, packed in original order (bit = +1)
+  uint64_t *x0_perm;      // = s.x0_perm, written by k_permute_bits_problems
+  uint32_t *sweeps_done;  // sweeps performed
+};
+// Many SEGMENTS in one launch (asp_sa_chains_advance_batch, order 0): every handle's SweepArgs and its
+// Resume part (its own sign words, tracked energies and sweep index base).  Every chain is the one
+// k_sa_sweep_resume advances: the body is the same.
+struct ResumeProblem {
+  SweepArgs s;  // trace: nullptr (a traced segment runs alone)
+  Resume r;
+};
+// Many LADDER segments in one launch (asp_sa_chains_advance_ladder_batch, order 0): chain_betas points
+// at the handle's [groups * M] values inside the batch's one concatenated buffer (the chains padding a
+// last group: 0).
+struct LadderProblem {
+  SweepArgs s;  // betas: nullptr (never read); trace: nullptr (a traced segment runs alone)
+  ResumeLadder r;
+};
+
+template <int M, int LAYOUT, typename Problem>
+__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_batch(BatchArgs<Problem> b) {
   const BatchSlot slot = b.slots[(blockIdx.x & 7u) * b.slots_per_xcd + (blockIdx.x >> 3)];
   const uint32_t problem = __builtin_amdgcn_readfirstlane(slot.problem);
   if (problem == 0xFFFFFFFFu) return;
@@ -1077,92 +1101,20 @@ __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_batch(BatchArgs b) {
   // compiler may then re-load a field where it needs it instead of keeping all forty of them in
   // registers (as a by-value copy it spilled SGPRs into VGPR lanes and VGPRs to scratch:
   // 128 VGPRs + 68 B of scratch against the single-problem kernel's 112 and none; +8 %).
-  using ConstArgs = const SweepArgs __attribute__((address_space(4)));
-  ConstArgs *a = reinterpret_cast<ConstArgs *>(reinterpret_cast<uintptr_t>(b.problems + problem));
-  sa_sweep_body<M, false, LAYOUT>(*a, __builtin_amdgcn_readfirstlane(slot.group));
-}
-
-// Many DESCENTS in one launch (asp_sa_greedy_batch): workgroup -> problem through the slot table
-// of k_sa_sweep_batch (every problem is one chain, so its group is always 0).  Each problem starts
-// from its own configuration (s.x0_perm), runs strict-descent sweeps until one flips nothing or
-// s.num_sweeps (the caller's max_sweeps) are done — decided here, by the workgroup that owns the
-// whole chain, with no host round trip — and leaves the number of sweeps in its own word.  What
-// the descent needs beyond SweepArgs lives in this wrapper, so that SweepArgs — shared by every
-// annealing kernel, whose register assignment follows its layout — stays as it is.
-struct DescentProblem {
-  SweepArgs s;            // betas: nullptr (never read); num_sweeps: the cap; trace: nullptr
-  const uint64_t *x0;     // the tree's configuration, packed in original order (bit = +1)
-  uint64_t *x0_perm;      // = s.x0_perm, written by k_permute_bits_problems
-  uint32_t *sweeps_done;  // sweeps performed
-};
-struct DescentBatchArgs {
-  const DescentProblem *problems;
-  const BatchSlot *slots;  // [8][slots_per_xcd]
-  uint32_t slots_per_xcd;
-};
-
-template <int LAYOUT>
-__global__ __launch_bounds__(kMaxThreads) void k_sa_descent_batch(DescentBatchArgs b) {
-  const BatchSlot slot = b.slots[(blockIdx.x & 7u) * b.slots_per_xcd + (blockIdx.x >> 3)];
-  const uint32_t problem = __builtin_amdgcn_readfirstlane(slot.problem);
-  if (problem == 0xFFFFFFFFu) return;
-  // (the constant address space: see k_sa_sweep_batch)
-  using ConstProblem = const DescentProblem __attribute__((address_space(4)));
+  using ConstProblem = const Problem __attribute__((address_space(4)));
   ConstProblem *d = reinterpret_cast<ConstProblem *>(reinterpret_cast<uintptr_t>(b.problems + problem));
-  sa_sweep_body<1, true, LAYOUT>(d->s, 0u, StopWhenStill{d->sweeps_done});
-}
-
-// Many SEGMENTS in one launch (asp_sa_chains_advance_batch, order 0): workgroup -> (handle, group of
-// M chains) through the slot table of k_sa_sweep_batch; every handle's SweepArgs and its Resume part
-// (its own sign words, tracked energies and sweep index base) in a wrapper read through the constant
-// address space, as DescentProblem is — SweepArgs stays as it is.  Every chain is the one
-// k_sa_sweep_resume advances: the body is the same.
-struct ResumeProblem {
-  SweepArgs s;  // trace: nullptr (a traced segment runs alone)
-  Resume r;
-};
-struct ResumeBatchArgs {
-  const ResumeProblem *problems;
-  const BatchSlot *slots;  // [8][slots_per_xcd]
-  uint32_t slots_per_xcd;
-};
-
-template <int M, int LAYOUT>
-__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_resume_batch(ResumeBatchArgs b) {
-  const BatchSlot slot = b.slots[(blockIdx.x & 7u) * b.slots_per_xcd + (blockIdx.x >> 3)];
-  const uint32_t problem = __builtin_amdgcn_readfirstlane(slot.problem);
-  if (problem == 0xFFFFFFFFu) return;
-  // (the constant address space: see k_sa_sweep_batch)
-  using ConstProblem = const ResumeProblem __attribute__((address_space(4)));
-  ConstProblem *d = reinterpret_cast<ConstProblem *>(reinterpret_cast<uintptr_t>(b.problems + problem));
-  sa_sweep_body<M, false, LAYOUT>(d->s, __builtin_amdgcn_readfirstlane(slot.group), NoEarlyStop{},
-                                  Resume{d->r.cur_perm, d->r.e_cur, d->r.t0});
-}
-
-// Many LADDER segments in one launch (asp_sa_chains_advance_ladder_batch, order 0): the same table of
-// slots, the handle's ResumeLadder part beside its SweepArgs — chain_betas points at the handle's
-// [groups * M] values inside the batch's one concatenated buffer (the chains padding a last group: 0).
-// Every chain is the one k_sa_sweep_ladder advances: the body is the same.
-struct LadderProblem {
-  SweepArgs s;  // betas: nullptr (never read); trace: nullptr (a traced segment runs alone)
-  ResumeLadder r;
-};
-struct LadderBatchArgs {
-  const LadderProblem *problems;
-  const BatchSlot *slots;  // [8][slots_per_xcd]
-  uint32_t slots_per_xcd;
-};
-
-template <int M, int LAYOUT>
-__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_ladder_batch(LadderBatchArgs b) {
-  const BatchSlot slot = b.slots[(blockIdx.x & 7u) * b.slots_per_xcd + (blockIdx.x >> 3)];
-  const uint32_t problem = __builtin_amdgcn_readfirstlane(slot.problem);
-  if (problem == 0xFFFFFFFFu) return;
-  // (the constant address space: see k_sa_sweep_batch)
-  using ConstProblem = const LadderProblem __attribute__((address_space(4)));
-  ConstProblem *d = reinterpret_cast<ConstProblem *>(reinterpret_cast<uintptr_t>(b.problems + problem));
-  sa_sweep_body<M, false, LAYOUT>(d->s, __builtin_amdgcn_readfirstlane(slot.group), NoEarlyStop{},
-                                  ResumeLadder{d->r.cur_perm, d->r.e_cur, d->r.t0, d->r.chain_betas});
+  // how the body runs each descriptor
+  if constexpr (std::is_same_v<Problem, SweepArgs>) {
+    sa_sweep_body<M, false, LAYOUT>(*d, __builtin_amdgcn_readfirstlane(slot.group));
+  } else if constexpr (std::is_same_v<Problem, DescentProblem>) {
+    sa_sweep_body<M, true, LAYOUT>(d->s, 0u, StopWhenStill{d->sweeps_done});
+  } else if constexpr (std::is_same_v<Problem, ResumeProblem>) {
+    sa_sweep_body<M, false, LAYOUT>(d->s, __builtin_amdgcn_readfirstlane(slot.group), NoEarlyStop{},
+                                    Resume{d->r.cur_perm, d->r.e_cur, d->r.t0});
+  } else {
+    sa_sweep_body<M, false, LAYOUT>(d->s, __builtin_amdgcn_readfirstlane(slot.group), NoEarlyStop{},
+                                    ResumeLadder{d->r.cur_perm, d->r.e_cur, d->r.t0, d->r.chain_betas});
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1807,7 +1759,7 @@ __global__ __launch_bounds__(256) void k_permute_bits_problems(const DescentProb
 }
 
 // The handles of a batched segment (asp_sa_chains_advance_batch, order 0) into and out of the form
-// k_sa_sweep_resume_batch runs them in: what sa_chains_advance_colour does with two permute launches,
+// k_sa_sweep_batch runs their segments in: what sa_chains_advance_colour does with two permute launches,
 // two unpermute launches and six copies PER HANDLE, for all handles in one launch each way.
 struct ChainsIo {
   uint64_t *x_cur, *x_best;  // the handle: [chains][words], original order, bit = +1
@@ -1900,68 +1852,110 @@ __global__ __launch_bounds__(256) void k_unpermute_bits_batch(const PostProblem 
 
 namespace {
 
-using SweepKernel = void (*)(SweepArgs);
+// A FORM of the sweep kernel: M chains per group (one workgroup) in layout LAYOUT.
+template <int M, int LAYOUT>
+struct Form {
+  static constexpr int kM = M, kLayout = LAYOUT;
+  static constexpr bool is(int m, int layout) { return m == M && layout == LAYOUT; }
+};
+template <typename... Forms>
+struct FormList {};
+// Every form there is.  A kernel family below has these or a subset of them and nothing else, so that a
+// resumed, ladder or batched run takes a form the closed call has.
+using ColourForms = FormList<Form<1, kBytes>, Form<2, kBytes>, Form<4, kBytes>, Form<8, kBytes>,  // eight chains: bytes only
+                             Form<4, kWide>, Form<4, kNibbles>,    // a word, four bits per position: four chains
+                             Form<1, kBits>, Form<1, kGlobal>>;    // a bit per position: one chain per workgroup
+
+template <typename... Forms>
+constexpr bool form_listed(FormList<Forms...>, int m, int layout) {
+  return (Forms::is(m, layout) || ...);
+}
+constexpr bool colour_form_exists(int m, int layout) { return form_listed(ColourForms{}, m, layout); }
+static_assert(colour_form_exists(1, kBytes) && colour_form_exists(2, kBytes) && colour_form_exists(4, kBytes) &&
+                  colour_form_exists(8, kBytes) && !colour_form_exists(0, kBytes) && !colour_form_exists(3, kBytes) &&
+                  !colour_form_exists(16, kBytes),
+              "1, 2, 4 or 8 chains per group in the byte layout");
+static_assert(colour_form_exists(4, kWide) && colour_form_exists(4, kNibbles) && !colour_form_exists(1, kWide) &&
+                  !colour_form_exists(2, kWide) && !colour_form_exists(8, kWide) && !colour_form_exists(1, kNibbles) &&
+                  !colour_form_exists(2, kNibbles) && !colour_form_exists(8, kNibbles),
+              "a word and four bits per position: four chains per group");
+static_assert(colour_form_exists(1, kBits) && colour_form_exists(1, kGlobal) && !colour_form_exists(2, kBits) &&
+                  !colour_form_exists(4, kBits) && !colour_form_exists(2, kGlobal) && !colour_form_exists(4, kGlobal),
+              "a bit per position, in LDS or in HBM: one chain per workgroup");
 
 // A group of four replicas that starts on a multiple of four is one whole Philox call (the ALIGNED
 // form of sa_sweep_body): any sharding of the chains by multiples of four.  Eight replicas stay
 // generic: an aligned visit of two calls back to back needed 36 B of scratch against 28 B.
 bool aligned_replicas(int m, uint32_t replica_first) { return m == 4 && replica_first % 4u == 0; }
 
-// `aligned`: aligned_replicas() holds for the launch.  The closed call's kernels of four replicas
-// have the ALIGNED form; every other kernel is the generic one, which is right for any first replica.
-SweepKernel sweep_kernel_for(int m, bool descent, int layout, bool aligned = false) {
-  if (layout == kBits) return descent ? k_sa_sweep<1, true, kBits> : k_sa_sweep<1, false, kBits>;
-  if (layout == kGlobal) {
-    return descent ? k_sa_sweep<1, true, kGlobal> : k_sa_sweep<1, false, kGlobal>;
+// A kernel FAMILY gives the kernel of a form, Family::of<Form>(), for the forms it has<Form>().
+// The closed call: every form; strict descent (DESCENT) in the forms of one chain, the ALIGNED variant
+// (aligned_replicas() holds for the launch) in those of four; every other kernel is the generic one,
+// which is right for any first replica.
+template <bool DESCENT, bool ALIGNED>
+struct ClosedFamily {
+  using Kernel = void (*)(SweepArgs);
+  template <typename F>
+  static constexpr bool has() {
+    return DESCENT ? (F::kM == 1 && !ALIGNED) : (!ALIGNED || F::kM == 4);
   }
-  if (layout == kWide) {
-    if (m != 4) return nullptr;
-    return aligned ? k_sa_sweep<4, false, kWide, true> : k_sa_sweep<4, false, kWide>;
+  template <typename F>
+  static Kernel of() {
+    return k_sa_sweep<F::kM, DESCENT, F::kLayout, ALIGNED>;
   }
-  if (layout == kNibbles) {
-    if (m != 4) return nullptr;
-    return aligned ? k_sa_sweep<4, false, kNibbles, true> : k_sa_sweep<4, false, kNibbles>;
+};
+// A handle's segment (Res = Resume) or ladder segment (ResumeLadder): every form of the closed call, no teams.
+template <typename Res>
+struct SegmentFamily {
+  using Kernel = void (*)(SweepArgs, Res);
+  template <typename F>
+  static constexpr bool has() {
+    return true;
   }
-  switch (m) {
-    case 1: return descent ? k_sa_sweep<1, true, kBytes> : k_sa_sweep<1, false, kBytes>;
-    case 2: return k_sa_sweep<2, false, kBytes>;
-    case 4: return aligned ? k_sa_sweep<4, false, kBytes, true> : k_sa_sweep<4, false, kBytes>;
-    case 8: return k_sa_sweep<8, false, kBytes>;
-    default: return nullptr;
+  template <typename F>
+  static Kernel of() {
+    return k_sa_sweep_resume<F::kM, F::kLayout, Res>;
   }
+};
+// The shared launches of many problems, by descriptor: closed anneals (SweepArgs) in every form with the
+// spins in LDS; segments and ladder segments in bytes up to four chains and words (a cluster beyond
+// a byte per position runs alone); descents as one chain in bytes.
+template <typename Problem>
+struct BatchFamily {
+  using Kernel = void (*)(BatchArgs<Problem>);
+  template <typename F>
+  static constexpr bool has() {
+    if (std::is_same_v<Problem, SweepArgs>) return F::kLayout != kGlobal;
+    if (std::is_same_v<Problem, DescentProblem>) return F::kM == 1 && F::kLayout == kBytes;
+    return (F::kLayout == kBytes && F::kM <= 4) || F::kLayout == kWide;
+  }
+  template <typename F>
+  static Kernel of() {
+    return k_sa_sweep_batch<F::kM, F::kLayout, Problem>;
+  }
+};
+
+// The family's kernel for m chains per group in `layout`, or nullptr: no such form (in this family).
+template <typename Family, typename... Forms>
+typename Family::Kernel colour_kernel_in(FormList<Forms...>, int m, int layout) {
+  typename Family::Kernel kernel = nullptr;
+  auto take = [&](auto form) {
+    using F = decltype(form);
+    if constexpr (Family::template has<F>()) {
+      if (F::is(m, layout)) kernel = Family::template of<F>();
+    }
+  };
+  (take(Forms{}), ...);
+  return kernel;
 }
-
-using ResumeKernel = void (*)(SweepArgs, Resume);
-
-// The forms of a handle's segment: every spin layout and group size of the closed call, no teams.
-ResumeKernel resume_kernel_for(int m, int layout) {
-  if (layout == kBits) return k_sa_sweep_resume<1, kBits>;
-  if (layout == kGlobal) return k_sa_sweep_resume<1, kGlobal>;
-  if (layout == kWide) return m == 4 ? k_sa_sweep_resume<4, kWide> : nullptr;
-  if (layout == kNibbles) return m == 4 ? k_sa_sweep_resume<4, kNibbles> : nullptr;
-  switch (m) {
-    case 1: return k_sa_sweep_resume<1, kBytes>;
-    case 2: return k_sa_sweep_resume<2, kBytes>;
-    case 4: return k_sa_sweep_resume<4, kBytes>;
-    case 8: return k_sa_sweep_resume<8, kBytes>;
-    default: return nullptr;
-  }
+template <typename Family>
+typename Family::Kernel colour_kernel_of(int m, int layout) {
+  return colour_kernel_in<Family>(ColourForms{}, m, layout);
 }
-
-// ... and of a ladder segment: the same forms, one for one.
-using LadderKernel = void (*)(SweepArgs, ResumeLadder);
-LadderKernel ladder_kernel_for(int m, int layout) {
-  if (layout == kBits) return k_sa_sweep_ladder<1, kBits>;
-  if (layout == kGlobal) return k_sa_sweep_ladder<1, kGlobal>;
-  if (layout == kWide) return m == 4 ? k_sa_sweep_ladder<4, kWide> : nullptr;
-  if (layout == kNibbles) return m == 4 ? k_sa_sweep_ladder<4, kNibbles> : nullptr;
-  switch (m) {
-    case 1: return k_sa_sweep_ladder<1, kBytes>;
-    case 2: return k_sa_sweep_ladder<2, kBytes>;
-    case 4: return k_sa_sweep_ladder<4, kBytes>;
-    case 8: return k_sa_sweep_ladder<8, kBytes>;
-    default: return nullptr;
-  }
+ClosedFamily<false, false>::Kernel closed_kernel_of(int m, bool descent, int layout, uint32_t replica_first) {
+  if (descent) return colour_kernel_of<ClosedFamily<true, false>>(m, layout);
+  if (aligned_replicas(m, replica_first)) return colour_kernel_of<ClosedFamily<false, true>>(m, layout);
+  return colour_kernel_of<ClosedFamily<false, false>>(m, layout);
 }
 
 size_t sweep_lds_bytes(const asp::SaHostLayout &L, int layout) {
@@ -1982,13 +1976,19 @@ size_t team_lds_bytes(const asp::SaHostLayout &L) {
          2 * (((static_cast<size_t>(L.num_blocks) + 15) / 16) * 16);
 }
 
+// blocks of the largest colour class
+uint32_t widest_color(const asp::SaHostLayout &L) {
+  uint32_t widest = 1;
+  for (uint32_t c = 0; c < L.num_colors; ++c) {
+    widest = std::max(widest, L.color_block_start[c + 1] - L.color_block_start[c]);
+  }
+  return widest;
+}
+
 // Launch geometry: as many replicas per group as still leaves one group per CU,
 // as many wavefronts as a colour class has blocks.
 void choose_launch(const asp_sa_plan *p, uint32_t repetitions, int *m_out, int *threads_out) {
-  uint32_t widest = 1;  // blocks of the largest colour class
-  for (uint32_t c = 0; c < p->host.num_colors; ++c) {
-    widest = std::max(widest, p->host.color_block_start[c + 1] - p->host.color_block_start[c]);
-  }
+  const uint32_t widest = widest_color(p->host);
   int m = 1;
   bool two_per_cu = false;
   if (p->force_m) {
@@ -2027,8 +2027,9 @@ void choose_launch(const asp_sa_plan *p, uint32_t repetitions, int *m_out, int *
 // the segments of a handle (sa_chains_advance_colour), so that both take the same form.
 struct ColourLaunch {
   int m = 1, threads = 64, layout = kBytes;
-  bool packed = false, nibbles = false, global = false, wide = false;
 };
+// a bit per position, in LDS or in HBM (forced by asp_sa_set_packed or chosen: the launch is the same)
+bool bit_packed(int layout) { return layout == kBits || layout == kGlobal; }
 ColourLaunch choose_colour_launch(const asp_sa_plan *p, uint32_t repetitions, bool descent, bool traced) {
   const asp::SaHostLayout &L = p->host;
   ColourLaunch c;
@@ -2036,46 +2037,61 @@ ColourLaunch choose_colour_launch(const asp_sa_plan *p, uint32_t repetitions, bo
   if (descent) c.m = 1;
   // One byte per position when that fits the LDS; otherwise one BIT per position, one replica
   // per workgroup (flips applied by wavefront ballot) — 8x the capacity.
-  c.packed = p->force_packed != 0;
-  if (!c.packed && sweep_lds_bytes(L, kBytes) > p->spin_lds()) {
+  bool packed = p->force_packed != 0, nibbles = false;
+  if (!packed && sweep_lds_bytes(L, kBytes) > p->spin_lds()) {
     // ... or, with chains enough for four per workgroup, four bits per position: twice the
     // capacity of bytes and still four replicas sharing every coupling load
     if (!descent && !traced && c.m >= 4 && sweep_lds_bytes(L, kNibbles) <= p->spin_lds()) {
-      c.nibbles = true;
+      nibbles = true;
       c.m = 4;
     } else {
-      c.packed = true;
+      packed = true;
     }
   }
   // not even a bit per position fits the LDS: keep the words in HBM (no size limit, slow)
-  c.global = p->force_packed == 2 || (c.packed && sweep_lds_bytes(L, kBits) > p->spin_lds());
-  if (c.packed) c.m = 1;
+  const bool global = p->force_packed == 2 || (packed && sweep_lds_bytes(L, kBits) > p->spin_lds());
+  if (packed) c.m = 1;
   // A word per position (SDWA sign trick) when four replicas share the
   // workgroup and the words fit; results do not depend on the layout.
   // (measured: +2..12 % with four replicas per workgroup, nothing with two)
-  c.wide = !c.packed && !c.nibbles && !descent && p->allow_wide && c.m == 4 && p->ell_col4.ptr != nullptr &&
-           sweep_lds_bytes(L, kWide) <= p->spin_lds();
-  c.layout = c.global ? kGlobal : (c.packed ? kBits : (c.nibbles ? kNibbles : (c.wide ? kWide : kBytes)));
+  const bool wide = !packed && !nibbles && !descent && p->allow_wide && c.m == 4 && p->ell_col4.ptr != nullptr &&
+                    sweep_lds_bytes(L, kWide) <= p->spin_lds();
+  c.layout = global ? kGlobal : (packed ? kBits : (nibbles ? kNibbles : (wide ? kWide : kBytes)));
   return c;
 }
 
-// The plan's part of the sweep arguments (the same for every launch of the plan in the form `c`); the
-// caller adds betas, the start, the outputs, the seed and the sweep / replica counts.
-SweepArgs plan_sweep_args(const asp_sa_plan *p, const ColourLaunch &c) {
+// The plan's part of the sweep arguments (the same for every launch of the plan in `layout`) ...
+SweepArgs plan_sweep_args(const asp_sa_plan *p, int layout) {
   const asp::SaHostLayout &L = p->host;
   SweepArgs plan_args{};
   plan_args.color_block_start = p->color_block_start.ptr;
   plan_args.block_width = p->block_width.ptr;
   plan_args.ell_off = p->ell_off.ptr;
-  plan_args.ell_col = c.wide ? p->ell_col4.ptr : p->ell_col.ptr;
+  plan_args.ell_col = layout == kWide ? p->ell_col4.ptr : p->ell_col.ptr;
   plan_args.ell_val = p->ell_val.ptr;
   plan_args.spin_of_pos = p->spin_of_pos.ptr;
   plan_args.field_pos = p->field_pos.ptr;
   plan_args.scale = std::ldexp(1.0, L.energy_scale_exp);
   plan_args.num_colors = L.num_colors;
   plan_args.num_blocks = L.num_blocks;
-  plan_args.spin_words = c.global ? p->w_spins.ptr : nullptr;
+  plan_args.spin_words = layout == kGlobal ? p->w_spins.ptr : nullptr;
   return plan_args;
+}
+// ... and with the call's: the schedule, the start (nullptr: all spins up, or a segment's own), the outputs,
+// the seed and the sweep / replica counts.  The trace and the field cache stay off: the caller's.
+SweepArgs sweep_args(const asp_sa_plan *p, int layout, const double *betas, const uint64_t *x0_perm,
+                     uint64_t *best_perm, long long *tracked, unsigned long long *accepted, uint64_t seed,
+                     uint32_t num_sweeps, uint32_t replica_first) {
+  SweepArgs args = plan_sweep_args(p, layout);
+  args.betas = betas;
+  args.x0_perm = x0_perm;
+  args.best_perm = best_perm;
+  args.tracked = tracked;
+  args.accepted = accepted;
+  args.seed = seed;
+  args.num_sweeps = num_sweeps;
+  args.replica_first = replica_first;
+  return args;
 }
 
 // Switch the field cache on after a sweep with fewer flips than this: a flip stales ~degree blocks,
@@ -2262,7 +2278,7 @@ int asp_sa_plan_info(asp_sa_plan const *p, asp_sa_info *info) {
 
 int asp_sa_set_launch(asp_sa_plan *p, int replicas_per_group, int threads) {
   if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  if (replicas_per_group != 0 && !sweep_kernel_for(replicas_per_group, false, false)) {
+  if (replicas_per_group != 0 && !colour_form_exists(replicas_per_group, kBytes)) {
     return asp::set_error(ASP_ERR_INVALID, "replicas_per_group must be 0, 1, 2, 4 or 8");
   }
   if (threads != 0 && (threads < 64 || threads > 1024 || threads % 64 != 0)) {
@@ -2329,6 +2345,139 @@ namespace {
 int greedy_relax(asp_sa_plan *p, uint32_t max_sweeps, std::vector<uint64_t> &x, uint64_t *out_x,
                  double *out_e, uint32_t *out_sweeps, bool exact_sweeps);
 
+// One launch on the plan's stream with a workgroup per group of chains: what a closed call (run_chains)
+// and a segment of a handle (chains_advance_colour) do alike.  The caller queues what is its own between
+// these steps — its uploads, the start, ev[0], the pass after the sweeps, ev[3] and its copies.
+struct ColourRun {
+  asp_sa_plan *p;
+  uint32_t repetitions, num_sweeps;
+  int64_t *trace;  // HOST [repetitions][num_sweeps + 1] or nullptr
+  int m = 1, threads = 64, layout = kBytes;
+  size_t lds = 0;
+  uint32_t groups = 0;
+  uint64_t padded = 0;
+  SweepArgs args{};
+
+  int shape(const ColourLaunch &form, size_t lds_bytes) {
+    m = form.m, threads = form.threads, layout = form.layout, lds = lds_bytes;
+    if (lds > p->max_lds) {
+      return asp::set_error(ASP_ERR_TOO_LARGE, "%zu B of LDS needed, %zu B available", lds, p->max_lds);
+    }
+    groups = (repetitions + m - 1) / m;
+    padded = static_cast<uint64_t>(groups) * m;
+    return ASP_OK;
+  }
+  // the work buffers every launch uses; `num_betas` values go up in w_betas
+  int ensure_work(uint64_t num_betas) {
+    if (layout == kGlobal) ASP_TRY(p->w_spins.ensure(static_cast<uint64_t>(groups) * p->host.num_blocks));
+    ASP_TRY(p->w_betas.ensure(num_betas));
+    ASP_TRY(p->w_best.ensure(padded * p->host.num_blocks));
+    ASP_TRY(p->w_tracked.ensure(padded));
+    return p->w_accepted.ensure(padded);
+  }
+  // the arguments, with the trace buffer and the field cache (both the byte and the wide layout)
+  int fill(const double *betas, const uint64_t *x0_perm, uint64_t seed, uint32_t replica_first) {
+    args = sweep_args(p, layout, betas, x0_perm, p->w_best.ptr, p->w_tracked.ptr, p->w_accepted.ptr, seed,
+                      num_sweeps, replica_first);
+    if (trace) {
+      ASP_TRY(p->w_trace.ensure(padded * (static_cast<uint64_t>(num_sweeps) + 1)));
+      args.trace = p->w_trace.ptr;
+    }
+    if (p->use_field_cache && !bit_packed(layout)) attach_field_cache(p, padded, &args);
+    return ASP_OK;
+  }
+  // ev[1], kernel(args, extra...), ev[2]
+  template <typename Kernel, typename... Extra>
+  int launch(Kernel kernel, Extra... extra) {
+    if (!kernel) return asp::set_error(ASP_ERR_INVALID, "no sweep kernel for %d chains per group", m);
+    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(kernel), lds));
+    ASP_HIP_TRY(hipEventRecord(p->ev[1], p->stream));
+    hipLaunchKernelGGL(kernel, dim3(groups), dim3(threads), lds, p->stream, args, extra...);
+    ASP_HIP_TRY(hipGetLastError());
+    ASP_HIP_TRY(hipEventRecord(p->ev[2], p->stream));
+    return ASP_OK;
+  }
+  // the trace rows behind the caller's copies, and the wait for everything queued
+  int collect() {
+    if (trace) {  // rows of the real chains come first
+      ASP_HIP_TRY(hipMemcpyAsync(trace, p->w_trace.ptr,
+                                 static_cast<uint64_t>(repetitions) * (num_sweeps + 1ull) * sizeof(int64_t),
+                                 hipMemcpyDeviceToHost, p->stream));
+    }
+    ASP_HIP_TRY(hipStreamSynchronize(p->stream));
+    return ASP_OK;
+  }
+  // what asp_sa_last_launch / _last_layout / _last_*_ms report; ev[0] .. ev[3]: the caller's
+  int record(int launch_layout) {
+    p->last_m = m;
+    p->last_layout = launch_layout;
+    p->last_spin_layout = layout;
+    p->last_threads = threads;
+    p->last_groups = static_cast<int>(groups);
+    ASP_HIP_TRY(hipEventElapsedTime(&p->last_sweep_ms, p->ev[1], p->ev[2]));
+    ASP_HIP_TRY(hipEventElapsedTime(&p->last_total_ms, p->ev[0], p->ev[3]));
+    return ASP_OK;
+  }
+};
+
+// Two team kernels resident at the same time could each hold CUs the other is waiting for:
+// team launches of one process take turns (from launch to completion).
+std::mutex g_team_launches;
+
+// The launch of a closed call (ev[0] .. ev[2] and the watchdog's read-back) with every chain spread over
+// `team` workgroups; the caller holds g_team_launches.  *refused: the configuration cannot be launched.
+int launch_team(ColourRun &run, uint32_t team, bool descent, bool *refused) {
+  asp_sa_plan *p = run.p;
+  const asp::SaHostLayout &L = p->host;
+  const uint32_t repetitions = run.repetitions;
+  hipStream_t s = p->stream;
+  // wavefronts per member: the widest colour class split over the team, at most 16
+  run.threads = static_cast<int>(std::min<uint32_t>(16u, (widest_color(L) + team - 1) / team)) * 64;
+  if (p->use_field_cache) {
+    // the team's "tracking" of untouched blocks uses the field cache's switch-over threshold
+    run.args.cache_enter_flips = cache_enter_flips_of(L);
+  }
+  TeamArgs ta{};
+  ta.s = run.args;
+  ta.team_size = team;
+  ta.num_teams = repetitions;
+  ta.spin_limit = kTeamSpinLimit;
+  if (const char *env = std::getenv("ASP_TEAM_SPIN_LIMIT")) {  // test hook: provoke the watchdog
+    ta.spin_limit = static_cast<uint32_t>(std::strtoul(env, nullptr, 10));
+  }
+  const size_t head_bytes = static_cast<size_t>(repetitions) * 8 * 7 + 16;
+  const size_t need = head_bytes + static_cast<size_t>(repetitions) * L.num_blocks * 8;
+  if (need > p->team_area_bytes) {
+    if (p->team_area) (void)hipFree(p->team_area);
+    p->team_area = nullptr;
+    p->team_area_bytes = 0;
+    ASP_HIP_TRY(hipExtMallocWithFlags(&p->team_area, need, hipDeviceMallocFinegrained));
+    p->team_area_bytes = need;
+  }
+  ASP_HIP_TRY(hipMemsetAsync(p->team_area, 0, head_bytes, s));
+  uint8_t *area = static_cast<uint8_t *>(p->team_area);
+  ta.arrivals = reinterpret_cast<unsigned long long *>(area);
+  ta.sums = reinterpret_cast<long long *>(area + static_cast<size_t>(repetitions) * 8);
+  ta.abort = reinterpret_cast<uint32_t *>(area + static_cast<size_t>(repetitions) * 8 * 7);
+  ta.flips = reinterpret_cast<uint64_t *>(area + head_bytes);
+  void (*team_kernel)(TeamArgs) = descent ? k_sa_sweep_team<true> : k_sa_sweep_team<false>;
+  ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(team_kernel), run.lds));
+  ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
+  ASP_HIP_TRY(hipEventRecord(p->ev[1], s));
+  // An ORDINARY launch: team * repetitions <= CUs workgroups, each fitting a CU by itself,
+  // are all resident on an otherwise idle device, and the watchdog (with the rerun in run_chains)
+  // covers a device that is not idle.  hipLaunchCooperativeKernel would check the same
+  // occupancy bound, but a process that has used it once dies in the HIP runtime's exit
+  // handler when rocprofv3 is attached (tools/exit_probe.hip: a 40-line program does;
+  // profiles/r02_exit_probe.txt).
+  hipLaunchKernelGGL(team_kernel, dim3(repetitions * team), dim3(run.threads), run.lds, s, ta);
+  *refused = hipGetLastError() != hipSuccess;
+  if (*refused) return ASP_OK;
+  ASP_HIP_TRY(hipEventRecord(p->ev[2], s));
+  ASP_HIP_TRY(hipMemcpyAsync(&p->team_abort_host, ta.abort, sizeof p->team_abort_host, hipMemcpyDeviceToHost, s));
+  return ASP_OK;
+}
+
 // All chains of one call; descent = strict-descent sweeps (greedy relaxation).
 int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_sweeps,
                uint32_t repetitions, uint32_t replica_offset, uint64_t const *x0, bool descent,
@@ -2356,21 +2505,15 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
     for (uint32_t r = 0; r < repetitions; ++r) out_e[r] = 0.0;
     return ASP_OK;
   }
-  const ColourLaunch chosen = choose_colour_launch(p, repetitions, descent, out_trace != nullptr);
-  int m = chosen.m, threads = chosen.threads;
-  const bool packed = chosen.packed, nibbles = chosen.nibbles, global = chosen.global;
+  ColourLaunch form = choose_colour_launch(p, repetitions, descent, out_trace != nullptr);
   // Few chains on a large cluster: spread each chain over a team of workgroups (k_sa_sweep_team).
   uint32_t team = 0;
   {
-    uint32_t widest = 1;
-    for (uint32_t c = 0; c < L.num_colors; ++c) {
-      widest = std::max(widest, L.color_block_start[c + 1] - L.color_block_start[c]);
-    }
-    const size_t team_lds = team_lds_bytes(L);
+    const uint32_t widest = widest_color(L);
     // (one colour class only — a diagonal or field-only J —: the single barrier per sweep would
     // not separate a fast member's next publication from a slow member's read of this one)
-    const bool possible = !out_trace && !global && !nibbles && p->force_packed == 0 && L.num_colors >= 2 &&
-                          p->force_m == 0 && team_lds <= p->max_lds &&
+    const bool possible = !out_trace && form.layout != kGlobal && form.layout != kNibbles && p->force_packed == 0 &&
+                          L.num_colors >= 2 && p->force_m == 0 && team_lds_bytes(L) <= p->max_lds &&
                           static_cast<uint64_t>(repetitions) * 2 <= static_cast<uint64_t>(p->num_cus);
     if (possible && p->team_mode >= 2) {
       team = static_cast<uint32_t>(p->team_mode);  // forced (tests, measurements)
@@ -2382,119 +2525,34 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
     }
     if (team * repetitions > static_cast<uint32_t>(p->num_cus)) team = 0;  // must be co-resident
   }
-  if (team >= 2) m = 1;
-  const int layout = team >= 2 ? kBits : chosen.layout;
-  const size_t lds = team >= 2 ? team_lds_bytes(L) : sweep_lds_bytes(L, layout);
-  if (lds > p->max_lds) {
-    return asp::set_error(ASP_ERR_TOO_LARGE, "%zu B of LDS needed, %zu B available", lds,
-                          p->max_lds);
-  }
-  const uint32_t groups = (repetitions + m - 1) / m;
-  const uint64_t padded = static_cast<uint64_t>(groups) * m;
+  if (team >= 2) form.m = 1, form.layout = kBits;
+  ColourRun run{p, repetitions, num_sweeps, out_trace};
+  ASP_TRY(run.shape(form, team >= 2 ? team_lds_bytes(L) : sweep_lds_bytes(L, form.layout)));
   hipStream_t s = p->stream;
   // every exit below, error or not, first waits for what was queued on the stream: copies into
   // the caller's buffers and kernels using the plan's work buffers never outlive the call
   asp::StreamFence fence(s);
-  if (global) ASP_TRY(p->w_spins.ensure(static_cast<uint64_t>(groups) * L.num_blocks));
-
-  DeviceBuffer<double> &d_betas = p->w_betas, &d_partial = p->w_partial, &d_e = p->w_e;
-  DeviceBuffer<uint64_t> &d_best = p->w_best, &d_x0 = p->w_x0, &d_x0_perm = p->w_x0_perm,
-                         &d_x = p->w_x;
-  DeviceBuffer<long long> &d_tracked = p->w_tracked;
-  DeviceBuffer<unsigned long long> &d_accepted = p->w_accepted;
-  ASP_TRY(d_betas.ensure(num_sweeps));
-  ASP_TRY(d_best.ensure(padded * L.num_blocks));
-  ASP_TRY(d_tracked.ensure(padded));
-  ASP_TRY(d_accepted.ensure(padded));
-  ASP_TRY(d_partial.ensure(static_cast<uint64_t>(repetitions) * L.num_blocks));
-  ASP_TRY(d_e.ensure(repetitions));
-  ASP_TRY(d_x.ensure(static_cast<uint64_t>(repetitions) * words));
-  ASP_TRY(d_betas.upload(betas, num_sweeps, s));
-  ASP_HIP_TRY(hipMemsetAsync(d_accepted.ptr, 0, padded * sizeof(unsigned long long), s));
+  ASP_TRY(run.ensure_work(num_sweeps));
+  ASP_TRY(p->w_partial.ensure(static_cast<uint64_t>(repetitions) * L.num_blocks));
+  ASP_TRY(p->w_e.ensure(repetitions));
+  ASP_TRY(p->w_x.ensure(static_cast<uint64_t>(repetitions) * words));
+  ASP_TRY(p->w_betas.upload(betas, num_sweeps, s));
+  ASP_HIP_TRY(hipMemsetAsync(p->w_accepted.ptr, 0, run.padded * sizeof(unsigned long long), s));
   if (x0) {
-    ASP_TRY(d_x0.ensure(words));
-    ASP_TRY(d_x0_perm.ensure(L.num_blocks));
-    ASP_TRY(d_x0.upload(x0, words, s));
-    hipLaunchKernelGGL(k_permute_bits, dim3((L.num_blocks + 255) / 256), dim3(256), 0, s, d_x0.ptr,
-                       words, p->spin_of_pos.ptr, L.num_blocks, 1u, d_x0_perm.ptr);
+    ASP_TRY(p->w_x0.ensure(words));
+    ASP_TRY(p->w_x0_perm.ensure(L.num_blocks));
+    ASP_TRY(p->w_x0.upload(x0, words, s));
+    ASP_TRY(asp::sa_permute_bits(p, p->w_x0.ptr, 1u, p->w_x0_perm.ptr));
   }
-
-  SweepArgs args = plan_sweep_args(p, chosen);
-  args.betas = d_betas.ptr;
-  args.x0_perm = x0 ? d_x0_perm.ptr : nullptr;
-  args.best_perm = d_best.ptr;
-  args.tracked = d_tracked.ptr;
-  args.accepted = d_accepted.ptr;
-  args.seed = seed;
-  args.num_sweeps = num_sweeps;
-  args.replica_first = replica_offset;
-  const uint64_t trace_elems = padded * (static_cast<uint64_t>(num_sweeps) + 1);
-  if (out_trace) {
-    ASP_TRY(p->w_trace.ensure(trace_elems));
-    args.trace = p->w_trace.ptr;
-  }
-  if (p->use_field_cache && !packed && team < 2) {  // (both the byte and the wide layout)
-    attach_field_cache(p, padded, &args);
-  }
+  ASP_TRY(run.fill(p->w_betas.ptr, x0 ? p->w_x0_perm.ptr : nullptr, seed, replica_offset));
 
   p->team_abort_host = 0;
-  // Two team kernels resident at the same time could each hold CUs the other is waiting for:
-  // team launches of one process take turns (from launch to completion).
-  static std::mutex team_launches;
-  std::unique_lock<std::mutex> team_turn(team_launches, std::defer_lock);
+  std::unique_lock<std::mutex> team_turn(g_team_launches, std::defer_lock);
   if (team >= 2) {
     team_turn.lock();
-    // wavefronts per member: the widest colour class split over the team, at most 16
-    uint32_t widest = 1;
-    for (uint32_t c = 0; c < L.num_colors; ++c) {
-      widest = std::max(widest, L.color_block_start[c + 1] - L.color_block_start[c]);
-    }
-    threads = static_cast<int>(std::min<uint32_t>(16u, (widest + team - 1) / team)) * 64;
-    if (p->use_field_cache) {
-      // the team's "tracking" of untouched blocks uses the field cache's switch-over threshold
-      args.cache_enter_flips = cache_enter_flips_of(L);
-    }
-    TeamArgs ta{};
-    ta.s = args;
-    ta.team_size = team;
-    ta.num_teams = repetitions;
-    ta.spin_limit = kTeamSpinLimit;
-    if (const char *env = std::getenv("ASP_TEAM_SPIN_LIMIT")) {  // test hook: provoke the watchdog
-      ta.spin_limit = static_cast<uint32_t>(std::strtoul(env, nullptr, 10));
-    }
-    const size_t head_bytes = static_cast<size_t>(repetitions) * 8 * 7 + 16;
-    const size_t need = head_bytes + static_cast<size_t>(repetitions) * L.num_blocks * 8;
-    if (need > p->team_area_bytes) {
-      if (p->team_area) (void)hipFree(p->team_area);
-      p->team_area = nullptr;
-      p->team_area_bytes = 0;
-      ASP_HIP_TRY(hipExtMallocWithFlags(&p->team_area, need, hipDeviceMallocFinegrained));
-      p->team_area_bytes = need;
-    }
-    ASP_HIP_TRY(hipMemsetAsync(p->team_area, 0, head_bytes, s));
-    uint8_t *area = static_cast<uint8_t *>(p->team_area);
-    ta.arrivals = reinterpret_cast<unsigned long long *>(area);
-    ta.sums = reinterpret_cast<long long *>(area + static_cast<size_t>(repetitions) * 8);
-    ta.abort = reinterpret_cast<uint32_t *>(area + static_cast<size_t>(repetitions) * 8 * 7);
-    ta.flips = reinterpret_cast<uint64_t *>(area + head_bytes);
-    const void *team_kernel = descent ? reinterpret_cast<const void *>(k_sa_sweep_team<true>)
-                                      : reinterpret_cast<const void *>(k_sa_sweep_team<false>);
-    ASP_TRY(asp::allow_dynamic_lds(team_kernel, lds));
-    ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
-    ASP_HIP_TRY(hipEventRecord(p->ev[1], s));
-    // An ORDINARY launch: team * repetitions <= CUs workgroups, each fitting a CU by itself,
-    // are all resident on an otherwise idle device, and the watchdog (with the rerun below)
-    // covers a device that is not idle.  hipLaunchCooperativeKernel would check the same
-    // occupancy bound, but a process that has used it once dies in the HIP runtime's exit
-    // handler when rocprofv3 is attached (tools/exit_probe.hip: a 40-line program does;
-    // profiles/r02_exit_probe.txt).
-    if (descent) {
-      hipLaunchKernelGGL(k_sa_sweep_team<true>, dim3(repetitions * team), dim3(threads), lds, s, ta);
-    } else {
-      hipLaunchKernelGGL(k_sa_sweep_team<false>, dim3(repetitions * team), dim3(threads), lds, s, ta);
-    }
-    const hipError_t launched = hipGetLastError();
-    if (launched != hipSuccess) {
+    bool refused = false;
+    ASP_TRY(launch_team(run, team, descent, &refused));
+    if (refused) {
       // the configuration cannot be launched: one workgroup per chain instead
       ASP_HIP_TRY(hipStreamSynchronize(s));
       team_turn.unlock();
@@ -2502,40 +2560,26 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
       return run_chains(p, seed, betas, num_sweeps, repetitions, replica_offset, x0, descent, out_x,
                         out_e, out_trace);
     }
-    ASP_HIP_TRY(hipEventRecord(p->ev[2], s));
-    ASP_HIP_TRY(hipMemcpyAsync(&p->team_abort_host, ta.abort, sizeof p->team_abort_host,
-                               hipMemcpyDeviceToHost, s));
   } else {
-    SweepKernel kernel = sweep_kernel_for(m, descent, layout, aligned_replicas(m, replica_offset));
-    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(kernel), lds));
     ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
-    ASP_HIP_TRY(hipEventRecord(p->ev[1], s));
-    hipLaunchKernelGGL(kernel, dim3(groups), dim3(threads), lds, s, args);
-    ASP_HIP_TRY(hipGetLastError());
-    ASP_HIP_TRY(hipEventRecord(p->ev[2], s));
+    ASP_TRY(run.launch(closed_kernel_of(run.m, descent, run.layout, replica_offset)));
   }
   // the first `repetitions` rows of best_perm are the real replicas
   // ... their reported energies and, in the same pass, their configurations in original order
-  ASP_TRY(energies_of_perm(p, d_best.ptr, repetitions, d_partial.ptr, d_e.ptr, d_x.ptr));
+  ASP_TRY(energies_of_perm(p, p->w_best.ptr, repetitions, p->w_partial.ptr, p->w_e.ptr, p->w_x.ptr));
   ASP_HIP_TRY(hipEventRecord(p->ev[3], s));
   // hipMemcpyDefault: out_x / out_e may be host pointers (the usual call) or device pointers
   // (distributed.py hands over RCCL-ready tensors, so a gather needs no host round trip)
-  ASP_HIP_TRY(hipMemcpyAsync(out_x, d_x.ptr, static_cast<uint64_t>(repetitions) * words * sizeof(uint64_t),
+  ASP_HIP_TRY(hipMemcpyAsync(out_x, p->w_x.ptr, static_cast<uint64_t>(repetitions) * words * sizeof(uint64_t),
                              hipMemcpyDefault, s));
-  ASP_HIP_TRY(hipMemcpyAsync(out_e, d_e.ptr, repetitions * sizeof(double), hipMemcpyDefault, s));
+  ASP_HIP_TRY(hipMemcpyAsync(out_e, p->w_e.ptr, repetitions * sizeof(double), hipMemcpyDefault, s));
   p->last_tracked.assign(repetitions, 0);
   p->last_accepted.assign(repetitions, 0);
-  ASP_HIP_TRY(hipMemcpyAsync(p->last_tracked.data(), d_tracked.ptr, repetitions * sizeof(int64_t),
+  ASP_HIP_TRY(hipMemcpyAsync(p->last_tracked.data(), p->w_tracked.ptr, repetitions * sizeof(int64_t),
                              hipMemcpyDeviceToHost, s));
-  ASP_HIP_TRY(hipMemcpyAsync(p->last_accepted.data(), d_accepted.ptr,
+  ASP_HIP_TRY(hipMemcpyAsync(p->last_accepted.data(), p->w_accepted.ptr,
                              repetitions * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  if (out_trace) {  // rows of the real replicas come first
-    ASP_HIP_TRY(hipMemcpyAsync(out_trace, p->w_trace.ptr,
-                               static_cast<uint64_t>(repetitions) * (num_sweeps + 1ull) *
-                                   sizeof(int64_t),
-                               hipMemcpyDeviceToHost, s));
-  }
-  ASP_HIP_TRY(hipStreamSynchronize(s));
+  ASP_TRY(run.collect());
   if (p->team_abort_host != 0) {
     // The members of a team were not resident together (another process or a long kernel holding
     // compute units — the launch mutex only orders this process's team launches): the partial
@@ -2548,75 +2592,32 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
     return run_chains(p, seed, betas, num_sweeps, repetitions, replica_offset, x0, descent, out_x,
                       out_e, out_trace);
   }
-  p->last_m = m;
-  p->last_layout = team >= 2 ? 4 : layout;
-  p->last_spin_layout = layout;
-  p->last_threads = threads;
-  p->last_groups = static_cast<int>(groups);
-  ASP_HIP_TRY(hipEventElapsedTime(&p->last_sweep_ms, p->ev[1], p->ev[2]));
-  ASP_HIP_TRY(hipEventElapsedTime(&p->last_total_ms, p->ev[0], p->ev[3]));
-  return ASP_OK;
+  return run.record(team >= 2 ? 4 : run.layout);
 }
-
-// One segment of a handle in the colour order (below); chain_betas: nullptr, or HOST [repetitions] — a
-// ladder segment, `betas` unused.
-int chains_advance_colour(asp_sa_chains *c, double const *betas, double const *chain_betas, uint32_t num_sweeps,
-                          int64_t *trace);
-
-}  // namespace
-
-namespace asp {
-
-int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace) {
-  return chains_advance_colour(c, betas, nullptr, num_sweeps, trace);
-}
-
-int sa_chains_advance_ladder_colour(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps,
-                                    int64_t *trace) {
-  return chains_advance_colour(c, nullptr, chain_betas, num_sweeps, trace);
-}
-
-}  // namespace asp
-
-namespace {
 
 // One segment of a handle in the colour order: the handle's original-order configurations are
 // permuted into the plan's block order (current and best, every chain its own), k_sa_sweep_resume
 // runs the sweeps from the carried integers with sweep index base c->sweeps_done, and both
 // configurations go back.  The launch is run_chains' minus teams: the same choice of chains per
 // group and spin layout, honouring asp_sa_set_launch / _set_packed / _set_wide; asp_sa_set_team
-// is ignored (a handle runs one workgroup per group of chains).  A ladder segment takes the same form
-// with k_sa_sweep_ladder in place of k_sa_sweep_resume and one beta per (padded) chain in w_betas.
+// is ignored (a handle runs one workgroup per group of chains).  chain_betas: nullptr, or HOST
+// [repetitions] — a ladder segment: `betas` unused, the kernel takes ResumeLadder in place of Resume and
+// one beta per (padded) chain lies in w_betas.
 int chains_advance_colour(asp_sa_chains *c, double const *betas, double const *chain_betas, uint32_t num_sweeps,
                           int64_t *trace) {
   asp_sa_plan *p = c->plan;
   const asp::SaHostLayout &L = p->host;
   const uint64_t K = L.num_spins;
   const uint32_t words = c->words, repetitions = c->repetitions;
-  const ColourLaunch chosen = choose_colour_launch(p, repetitions, false, trace != nullptr);
-  const int m = chosen.m, threads = chosen.threads, layout = chosen.layout;
-  const size_t lds = sweep_lds_bytes(L, layout);
-  if (lds > p->max_lds) {
-    return asp::set_error(ASP_ERR_TOO_LARGE, "%zu B of LDS needed, %zu B available", lds, p->max_lds);
-  }
   const bool ladder = chain_betas != nullptr;
-  ResumeKernel kernel = ladder ? nullptr : resume_kernel_for(m, layout);
-  LadderKernel ladder_kernel = ladder ? ladder_kernel_for(m, layout) : nullptr;
-  if (!kernel && !ladder_kernel) {
-    return asp::set_error(ASP_ERR_INVALID, "no resumable sweep for %d chains per group", m);
-  }
-  const void *kernel_address = ladder ? reinterpret_cast<const void *>(ladder_kernel)
-                                      : reinterpret_cast<const void *>(kernel);
-  const uint32_t groups = (repetitions + m - 1) / m;
-  const uint64_t padded = static_cast<uint64_t>(groups) * m;
+  const ColourLaunch form = choose_colour_launch(p, repetitions, false, trace != nullptr);
+  ColourRun run{p, repetitions, num_sweeps, trace};
+  ASP_TRY(run.shape(form, sweep_lds_bytes(L, form.layout)));
+  const uint64_t padded = run.padded;
   hipStream_t s = p->stream;
   asp::StreamFence fence(s);
-  if (chosen.global) ASP_TRY(p->w_spins.ensure(static_cast<uint64_t>(groups) * L.num_blocks));
-  ASP_TRY(p->w_betas.ensure(ladder ? padded : num_sweeps));
-  ASP_TRY(p->w_best.ensure(padded * L.num_blocks));
+  ASP_TRY(run.ensure_work(ladder ? padded : num_sweeps));
   ASP_TRY(p->w_cur_perm.ensure(padded * L.num_blocks));
-  ASP_TRY(p->w_tracked.ensure(padded));
-  ASP_TRY(p->w_accepted.ensure(padded));
   ASP_TRY(p->w_e_cur.ensure(padded));
   if (ladder) {
     ASP_TRY(p->w_betas.upload(chain_betas, repetitions, s));
@@ -2640,31 +2641,15 @@ int chains_advance_colour(asp_sa_chains *c, double const *betas, double const *c
   ASP_TRY(asp::sa_permute_bits(p, c->x_cur.ptr, repetitions, p->w_cur_perm.ptr));
   ASP_TRY(asp::sa_permute_bits(p, c->x_best.ptr, repetitions, p->w_best.ptr));
 
-  SweepArgs args = plan_sweep_args(p, chosen);
-  args.betas = ladder ? nullptr : p->w_betas.ptr;  // (a ladder segment never reads them)
-  args.x0_perm = nullptr;
-  args.best_perm = p->w_best.ptr;
-  args.tracked = p->w_tracked.ptr;
-  args.accepted = p->w_accepted.ptr;
-  args.seed = c->seed;
-  args.num_sweeps = num_sweeps;
-  args.replica_first = c->replica_offset;
-  if (trace) {
-    ASP_TRY(p->w_trace.ensure(padded * (static_cast<uint64_t>(num_sweeps) + 1)));
-    args.trace = p->w_trace.ptr;
-  }
-  if (p->use_field_cache && !chosen.packed) attach_field_cache(p, padded, &args);
-  ASP_TRY(asp::allow_dynamic_lds(kernel_address, lds));
-  ASP_HIP_TRY(hipEventRecord(p->ev[1], s));
+  // (a ladder segment never reads args.betas)
+  ASP_TRY(run.fill(ladder ? nullptr : p->w_betas.ptr, nullptr, c->seed, c->replica_offset));
   if (ladder) {
-    const ResumeLadder res{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done, p->w_betas.ptr};
-    hipLaunchKernelGGL(ladder_kernel, dim3(groups), dim3(threads), lds, s, args, res);
+    ASP_TRY(run.launch(colour_kernel_of<SegmentFamily<ResumeLadder>>(run.m, run.layout),
+                       ResumeLadder{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done, p->w_betas.ptr}));
   } else {
-    const Resume res{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done};
-    hipLaunchKernelGGL(kernel, dim3(groups), dim3(threads), lds, s, args, res);
+    ASP_TRY(run.launch(colour_kernel_of<SegmentFamily<Resume>>(run.m, run.layout),
+                       Resume{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done}));
   }
-  ASP_HIP_TRY(hipGetLastError());
-  ASP_HIP_TRY(hipEventRecord(p->ev[2], s));
   const dim3 grid((words + 3) / 4, (repetitions + kUnpermuteChains - 1) / kUnpermuteChains);
   hipLaunchKernelGGL(k_unpermute_bits, grid, dim3(256), 0, s, p->w_cur_perm.ptr, L.num_blocks,
                      p->pos_of_spin.ptr, K, words, repetitions, c->x_cur.ptr);
@@ -2676,22 +2661,24 @@ int chains_advance_colour(asp_sa_chains *c, double const *betas, double const *c
   ASP_HIP_TRY(hipMemcpyAsync(c->accepted.ptr, p->w_accepted.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
   ASP_HIP_TRY(hipEventRecord(p->ev[3], s));
   ASP_HIP_TRY(hipMemcpyAsync(c->h_e_cur.data(), p->w_e_cur.ptr, repetitions * 8ull, hipMemcpyDeviceToHost, s));
-  if (trace) {  // rows of the real chains come first
-    ASP_HIP_TRY(hipMemcpyAsync(trace, p->w_trace.ptr,
-                               static_cast<uint64_t>(repetitions) * (num_sweeps + 1ull) * sizeof(int64_t),
-                               hipMemcpyDeviceToHost, s));
-  }
-  ASP_HIP_TRY(hipStreamSynchronize(s));
-  p->last_m = m;
-  p->last_layout = p->last_spin_layout = layout;
-  p->last_threads = threads;
-  p->last_groups = static_cast<int>(groups);
-  ASP_HIP_TRY(hipEventElapsedTime(&p->last_sweep_ms, p->ev[1], p->ev[2]));
-  ASP_HIP_TRY(hipEventElapsedTime(&p->last_total_ms, p->ev[0], p->ev[3]));
-  return ASP_OK;
+  ASP_TRY(run.collect());
+  return run.record(run.layout);
 }
 
 }  // namespace
+
+namespace asp {
+
+int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace) {
+  return chains_advance_colour(c, betas, nullptr, num_sweeps, trace);
+}
+
+int sa_chains_advance_ladder_colour(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps,
+                                    int64_t *trace) {
+  return chains_advance_colour(c, nullptr, chain_betas, num_sweeps, trace);
+}
+
+}  // namespace asp
 
 extern "C" {
 
@@ -2845,10 +2832,7 @@ int asp_sa_energy(asp_sa_plan *p, uint32_t count, uint64_t const *x, double *out
   ASP_TRY(d_partial.alloc(static_cast<uint64_t>(count) * L.num_blocks));
   ASP_TRY(d_e.alloc(count));
   ASP_TRY(d_x.upload(x, static_cast<uint64_t>(count) * words, s));
-  const uint64_t total = static_cast<uint64_t>(count) * L.num_blocks;
-  hipLaunchKernelGGL(k_permute_bits, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0,
-                     s, d_x.ptr, words, p->spin_of_pos.ptr, L.num_blocks, count, d_perm.ptr);
-  ASP_HIP_TRY(hipGetLastError());
+  ASP_TRY(asp::sa_permute_bits(p, d_x.ptr, count, d_perm.ptr));
   ASP_TRY(energies_of_perm(p, d_perm.ptr, count, d_partial.ptr, d_e.ptr));
   ASP_TRY(d_e.download(out_e, count, s));
   ASP_HIP_TRY(hipStreamSynchronize(s));
@@ -2871,14 +2855,6 @@ int asp_sa_energy(asp_sa_plan *p, uint32_t count, uint64_t const *x, double *out
 namespace {
 
 thread_local float g_batch_sweep_ms = 0.0f;
-
-uint32_t widest_color(const asp::SaHostLayout &L) {
-  uint32_t widest = 1;
-  for (uint32_t c = 0; c < L.num_colors; ++c) {
-    widest = std::max(widest, L.color_block_start[c + 1] - L.color_block_start[c]);
-  }
-  return widest;
-}
 
 // What asp_sa_anneal_batch and the batched segments (sa_chains_advance_colour_batch) decide alike, in
 // one place: the wavefront counts of the launch classes, and the layout and wavefronts of a problem
@@ -2922,9 +2898,9 @@ struct ClassLaunch {
   bool used = false;
   hipEvent_t done = nullptr;  // recorded behind its launch
 };
-template <typename Args>  // {problems, slots, slots_per_xcd}
+template <typename Problem>
 struct ClassKernel {
-  void (*kernel)(Args);
+  void (*kernel)(BatchArgs<Problem>);
   uint32_t threads;
 };
 
@@ -2965,9 +2941,9 @@ struct ClassLauncher {
     return events.make(&end, true);
   }
 
-  // Every used class c: kernel_of(c).kernel(Args{problems, its part of the uploaded slot table}) on the
+  // Every used class c: kernel_of(c).kernel({problems, its part of the uploaded slot table}) on the
   // class's stream, between `begin` and `end` on the main stream `s`, which waits for all of them.
-  template <typename Args, typename Problem, typename KernelOf>
+  template <typename Problem, typename KernelOf>
   int run(hipStream_t s, const Problem *problems, const BatchSlot *d_slots, KernelOf kernel_of) {
     const int num_classes = static_cast<int>(launches.size());
     // (classes share kernels and run side by side: a kernel's dynamic-LDS limit is set once, to the
@@ -2989,11 +2965,11 @@ struct ClassLauncher {
       for (int c = 0; c < num_classes; ++c) {
         const ClassLaunch &l = launches[c];
         if (!l.used) continue;
-        const ClassKernel<Args> k = kernel_of(c);
+        const ClassKernel<Problem> k = kernel_of(c);
         hipStream_t cs = streams[c].stream;
         ASP_HIP_TRY(hipStreamWaitEvent(cs, begin, 0));
         hipLaunchKernelGGL(k.kernel, dim3(8u * l.slots_per_xcd), dim3(k.threads), l.lds, cs,
-                           Args{problems, d_slots + l.slot_at, l.slots_per_xcd});
+                           BatchArgs<Problem>{problems, d_slots + l.slot_at, l.slots_per_xcd});
         ASP_HIP_TRY(hipGetLastError());
         ASP_HIP_TRY(hipEventRecord(l.done, cs));
         ASP_HIP_TRY(hipStreamWaitEvent(s, l.done, 0));
@@ -3047,10 +3023,30 @@ int launch_post_batch(const PostProblem *d_post, const BatchSlot *d_chains, unsi
 struct BatchEntry {
   uint32_t item;     // index into the caller's array
   uint32_t waves;    // wavefronts per workgroup this problem wants
-  int layout;        // kWide, kBytes or kBits
+  int layout;        // kWide or kBytes; the closed batch: kNibbles or kBits as well
   double work;       // ~ time of one group: sweeps * ELL slabs
-  uint64_t beta_at;  // offset of its ladder in the concatenated betas
+  uint64_t beta_at;  // offset of its schedule (a ladder segment: its chains' betas) in the concatenated betas
 };
+
+// Chains per workgroup of a batch.  Measured on the production mix (K log-uniform in [1e2, 1e4], 64
+// chains x 5120 sweeps): four replicas per workgroup — the word layout with its one-instruction signs —
+// is fastest from 64 problems (86 G flips/s against 73 with two) over 128 (127 against 101
+// with eight, 95 with two, 62 with one) to 512 (161, the same as eight); fewer replicas per
+// workgroup only when four would leave SIMDs without a wavefront.  Nibble and bit entries count at their
+// fixed group sizes.  chains_of(e.item): the chains of an entry.
+template <typename ChainsOf>
+int batch_chains_per_group(const std::vector<BatchEntry> &entries, int num_cus, ChainsOf chains_of) {
+  for (int cand : {4, 2}) {
+    uint64_t waves = 0;
+    for (const BatchEntry &e : entries) {
+      const uint32_t per_group = e.layout == kBits ? 1 : (e.layout == kNibbles ? 4 : cand);
+      waves += static_cast<uint64_t>((chains_of(e.item) + per_group - 1) / per_group) *
+               kBatchWaves[batch_waves_index(e.waves)];
+    }
+    if (waves >= static_cast<uint64_t>(num_cus) * 4u) return cand;
+  }
+  return 1;
+}
 
 }  // namespace
 
@@ -3197,27 +3193,10 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
   };
   auto waves_of_class = [&](int c) { return kWaves[c / 4]; };
   auto layout_of_class = [&](int c) { return kLayouts[c % 4]; };
-  // ---- replicas per workgroup, per class ----
-  // Measured on the production mix (K log-uniform in [1e2, 1e4], 64 chains x
-  // 5120 sweeps): four replicas per workgroup — the word layout with its one-instruction signs —
-  // is fastest from 64 problems (86 G flips/s against 73 with two) over 128 (127 against 101
-  // with eight, 95 with two, 62 with one) to 512 (161, the same as eight); fewer replicas per
-  // workgroup only when four would leave SIMDs without a wavefront.
+  // ---- replicas per workgroup, per class (batch_chains_per_group) ----
   int m_of_class[kNumClasses];
   {
-    int m = 1;
-    for (int cand : {4, 2}) {
-      uint64_t waves = 0;
-      for (const BatchEntry &e : entries) {
-        const uint32_t reps = items[e.item].repetitions;
-        const int per_group = e.layout == kBits ? 1 : (e.layout == kNibbles ? 4 : cand);
-        waves += static_cast<uint64_t>((reps + per_group - 1) / per_group) * waves_of_class(class_of(e));
-      }
-      if (waves >= static_cast<uint64_t>(num_cus) * 4u) {
-        m = cand;
-        break;
-      }
-    }
+    const int m = batch_chains_per_group(entries, num_cus, [&](uint32_t i) { return items[i].repetitions; });
     for (int c = 0; c < kNumClasses; ++c) m_of_class[c] = m;
     // (fewer replicas per workgroup for the classes of the largest problems, to shorten the
     // batch's longest workgroup, was measured and LOSES: 123 -> 97 G flips/s at 128 problems,
@@ -3301,16 +3280,10 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
     const asp::SaHostLayout &L = p->host;
     const bool packed = entries[k].layout == kBits;
     std::copy(it.betas, it.betas + it.num_sweeps, h_betas.begin() + entries[k].beta_at);
-    ColourLaunch form;
-    form.wide = entries[k].layout == kWide;
-    SweepArgs a = plan_sweep_args(p, form);
-    a.betas = d_betas.ptr + entries[k].beta_at;
-    a.best_perm = d_best.ptr + off[k].best;
-    a.tracked = d_tracked.ptr + off[k].stat;
-    a.accepted = d_accepted.ptr + off[k].stat;
-    a.seed = it.seed;
-    a.num_sweeps = it.num_sweeps;
-    a.replica_first = it.replica_offset;
+    // (of the plan's part only the couplings' columns depend on the layout here: kWide or not)
+    SweepArgs a = sweep_args(p, entries[k].layout, d_betas.ptr + entries[k].beta_at, nullptr, d_best.ptr + off[k].best,
+                             d_tracked.ptr + off[k].stat, d_accepted.ptr + off[k].stat, it.seed, it.num_sweeps,
+                             it.replica_offset);
     // (the bit-packed layout runs without the field cache, as in the single-problem launch)
     a.field_cache = use_cache && !packed ? d_cache.ptr + off[k].cache : nullptr;
     a.cache_enter_flips = packed ? 0u : cache_enter_flips_of(L);
@@ -3339,17 +3312,10 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
   ASP_TRY(d_chains.upload(h_chains.data(), h_chains.size(), s));
   ASP_HIP_TRY(hipMemsetAsync(d_accepted.ptr, 0, n_stat * sizeof(unsigned long long), s));
   // ---- one sweep launch per class ----
-  ASP_TRY(launcher.run<BatchArgs>(s, d_problems.ptr, d_slots.ptr, [&](int c) -> ClassKernel<BatchArgs> {
-    const uint32_t threads = 64u * waves_of_class(c);
-    if (layout_of_class(c) == kWide) return {k_sa_sweep_batch<4, kWide>, threads};
-    if (layout_of_class(c) == kBits) return {k_sa_sweep_batch<1, kBits>, threads};
-    if (layout_of_class(c) == kNibbles) return {k_sa_sweep_batch<4, kNibbles>, threads};
-    switch (m_of_class[c]) {
-      case 1: return {k_sa_sweep_batch<1, kBytes>, threads};
-      case 2: return {k_sa_sweep_batch<2, kBytes>, threads};
-      case 4: return {k_sa_sweep_batch<4, kBytes>, threads};
-      default: return {k_sa_sweep_batch<8, kBytes>, threads};
-    }
+  ASP_TRY(launcher.run(s, d_problems.ptr, d_slots.ptr, [&](int c) {
+    // (a class of words has four chains per workgroup: with another count its problems took bytes)
+    return ClassKernel<SweepArgs>{colour_kernel_of<BatchFamily<SweepArgs>>(m_of_class[c], layout_of_class(c)),
+                                  64u * waves_of_class(c)};
   }));
   // ---- energies and original-order bits of every chain's best configuration ----
   ASP_TRY(launch_post_batch(d_post.ptr, d_chains.ptr, static_cast<unsigned>(h_chains.size()), energy_lds, max_lds,
@@ -3393,7 +3359,7 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
 // ---------------------------------------------------------------------------
 // The launch grouping of asp_sa_anneal_batch — one launch per wavefront count and layout class (a
 // word or a byte per position), four or two chains per workgroup when that still fills the chip —
-// with k_sa_sweep_resume_batch in place of k_sa_sweep_batch, and the handles' state permuted in and
+// with ResumeProblem descriptors in place of SweepArgs, and the handles' state permuted in and
 // out by one launch each way.  Segments that need the bit-packed layouts, plans with a forced
 // geometry or layout, traced segments and a group of one run as sa_chains_advance_colour.
 // Two deliberate differences from the closed batch, whose helpers (kBatchWaves, batch_layout_in_lds,
@@ -3402,9 +3368,9 @@ int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
 // ASP_BATCH_M is not read (chains per workgroup never change a result).
 
 // A batch of LADDER segments (asp_sa_chains_advance_ladder_batch; every segment with chain_betas): the
-// same grouping, class rule, LDS limit and state permute, with LadderProblem descriptors and
-// k_sa_sweep_ladder_batch; the per-chain betas of all handles go up in the one concatenated buffer, every
-// handle's part padded with zeros to whole groups; the segments that run alone take
+// same grouping, class rule, LDS limit and state permute, with LadderProblem descriptors; the per-chain
+// betas of all handles go up in the one concatenated buffer, every handle's part padded with zeros to
+// whole groups; the segments that run alone take
 // sa_chains_advance_ladder_colour.
 
 namespace asp {
@@ -3414,15 +3380,7 @@ namespace {
 template <bool LADDER>
 int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms) {
   using Problem = std::conditional_t<LADDER, LadderProblem, ResumeProblem>;
-  using ProblemBatchArgs = std::conditional_t<LADDER, LadderBatchArgs, ResumeBatchArgs>;
-  struct Entry {
-    uint32_t seg;
-    uint32_t waves;
-    int layout;  // kWide or kBytes
-    double work;
-    uint64_t beta_at;
-  };
-  std::vector<Entry> entries;
+  std::vector<BatchEntry> entries;  // (item: index into segs)
   std::vector<uint32_t> alone;
   for (uint32_t i = 0; i < count; ++i) {
     const asp_sa_plan *p = segs[i].chains->plan;
@@ -3433,15 +3391,15 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
       continue;
     }
     // (layout and wavefronts per workgroup in a shared launch: asp_sa_anneal_batch's, measured there)
-    Entry e{};
-    e.seg = i;
+    BatchEntry e{};
+    e.item = i;
     e.layout = batch_layout_in_lds(p);
     e.waves = batch_waves(L);
     e.work = static_cast<double>(segs[i].num_sweeps) * static_cast<double>(L.ell_off.back() + L.num_blocks);
     entries.push_back(e);
   }
   if (entries.size() == 1) {
-    alone.push_back(entries[0].seg);
+    alone.push_back(entries[0].item);
     entries.clear();
   }
   for (uint32_t i : alone) {
@@ -3456,30 +3414,15 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
   }
   if (entries.empty()) return ASP_OK;
 
-  const asp_sa_plan *first = segs[entries[0].seg].chains->plan;
-  const int num_cus = first->num_cus;
   const auto &kWaves = kBatchWaves;
-  constexpr int kNumWaves = kNumBatchWaves;
-  constexpr int kNumClasses = 2 * kNumWaves;  // class = 2 * (index of the wavefront count) + (bytes ? 1 : 0)
-  auto waves_index = [&](const Entry &e) { return batch_waves_index(e.waves); };
-  // chains per workgroup for the batch: four — the word layout — or two when that still gives every
-  // SIMD a wavefront, else one (asp_sa_anneal_batch's rule)
-  int m = 1;
-  for (int cand : {4, 2}) {
-    uint64_t waves = 0;
-    for (const Entry &e : entries) {
-      const uint32_t reps = segs[e.seg].chains->repetitions;
-      waves += static_cast<uint64_t>((reps + cand - 1) / cand) * kWaves[waves_index(e)];
-    }
-    if (waves >= static_cast<uint64_t>(num_cus) * 4u) {
-      m = cand;
-      break;
-    }
-  }
-  for (Entry &e : entries) {
+  constexpr int kNumClasses = 2 * kNumBatchWaves;  // class = 2 * (index of the wavefront count) + (bytes ? 1 : 0)
+  // chains per workgroup for the batch (asp_sa_anneal_batch's rule)
+  const int m = batch_chains_per_group(entries, segs[entries[0].item].chains->plan->num_cus,
+                                       [&](uint32_t i) { return segs[i].chains->repetitions; });
+  for (BatchEntry &e : entries) {
     if (e.layout == kWide && m != 4) e.layout = kBytes;  // (the word layout exists for four chains)
   }
-  auto class_of = [&](const Entry &e) { return 2 * waves_index(e) + (e.layout == kWide ? 0 : 1); };
+  auto class_of = [&](const BatchEntry &e) { return 2 * batch_waves_index(e.waves) + (e.layout == kWide ? 0 : 1); };
   // ---- per-handle offsets into the launch's buffers ----
   struct Offsets {
     uint64_t perm, stat, cache, groups, padded;
@@ -3488,7 +3431,7 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
   uint64_t n_perm = 0, n_stat = 0, n_cache = 0, n_betas = 0, n_chains = 0;
   bool use_cache = true;
   for (size_t k = 0; k < entries.size(); ++k) {
-    const asp_sa_chains *c = segs[entries[k].seg].chains;
+    const asp_sa_chains *c = segs[entries[k].item].chains;
     const SaHostLayout &L = c->plan->host;
     const uint64_t groups = (c->repetitions + static_cast<uint64_t>(m) - 1) / m, padded = groups * m;
     off[k] = Offsets{n_perm, n_stat, n_cache, groups, padded};
@@ -3497,7 +3440,7 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
     n_cache += padded * L.num_blocks * 64ull;
     n_chains += c->repetitions;
     entries[k].beta_at = n_betas;
-    n_betas += LADDER ? padded : segs[entries[k].seg].num_sweeps;  // (a ladder: one beta per padded chain)
+    n_betas += LADDER ? padded : segs[entries[k].item].num_sweeps;  // (a ladder: one beta per padded chain)
     use_cache = use_cache && c->plan->use_field_cache;
   }
   if (n_cache * sizeof(double) > (32ull << 30)) use_cache = false;
@@ -3533,7 +3476,7 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
   h_chains_in.reserve(n_stat);
   h_chains_out.reserve(n_chains);
   for (size_t k = 0; k < entries.size(); ++k) {
-    const ChainsSegment &seg = segs[entries[k].seg];
+    const ChainsSegment &seg = segs[entries[k].item];
     asp_sa_chains *c = seg.chains;
     const asp_sa_plan *p = c->plan;
     const SaHostLayout &L = p->host;
@@ -3542,21 +3485,13 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
     } else {
       std::copy(seg.betas, seg.betas + seg.num_sweeps, h_betas.begin() + entries[k].beta_at);
     }
-    ColourLaunch form;
-    form.wide = entries[k].layout == kWide;
     Problem rp{};
-    rp.s = plan_sweep_args(p, form);
-    rp.s.betas = LADDER ? nullptr : d_betas.ptr + entries[k].beta_at;  // (a ladder segment never reads them)
-    rp.s.x0_perm = nullptr;
-    rp.s.best_perm = d_best.ptr + off[k].perm;
-    rp.s.tracked = d_tracked.ptr + off[k].stat;
-    rp.s.accepted = d_accepted.ptr + off[k].stat;
-    rp.s.seed = c->seed;
-    rp.s.num_sweeps = seg.num_sweeps;
-    rp.s.replica_first = c->replica_offset;
+    // (a ladder segment never reads s.betas)
+    rp.s = sweep_args(p, entries[k].layout, LADDER ? nullptr : d_betas.ptr + entries[k].beta_at, nullptr,
+                      d_best.ptr + off[k].perm, d_tracked.ptr + off[k].stat, d_accepted.ptr + off[k].stat, c->seed,
+                      seg.num_sweeps, c->replica_offset);
     rp.s.field_cache = use_cache ? d_cache.ptr + off[k].cache : nullptr;
     rp.s.cache_enter_flips = cache_enter_flips_of(L);
-    rp.s.trace = nullptr;
     if constexpr (LADDER) {
       rp.r = ResumeLadder{d_cur.ptr + off[k].perm, d_e_cur.ptr + off[k].stat, c->sweeps_done,
                           d_betas.ptr + entries[k].beta_at};
@@ -3606,25 +3541,9 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
                      d_io.ptr, d_chains_in.ptr);
   ASP_HIP_TRY(hipGetLastError());
   // ---- one sweep launch per class ----
-  using Kernel = void (*)(ProblemBatchArgs);
-  Kernel kernel_of_layout[2] = {nullptr, nullptr};  // [class % 2]
-  if constexpr (LADDER) {
-    kernel_of_layout[0] = k_sa_sweep_ladder_batch<4, kWide>;
-    switch (m) {
-      case 1: kernel_of_layout[1] = k_sa_sweep_ladder_batch<1, kBytes>; break;
-      case 2: kernel_of_layout[1] = k_sa_sweep_ladder_batch<2, kBytes>; break;
-      default: kernel_of_layout[1] = k_sa_sweep_ladder_batch<4, kBytes>; break;
-    }
-  } else {
-    kernel_of_layout[0] = k_sa_sweep_resume_batch<4, kWide>;
-    switch (m) {
-      case 1: kernel_of_layout[1] = k_sa_sweep_resume_batch<1, kBytes>; break;
-      case 2: kernel_of_layout[1] = k_sa_sweep_resume_batch<2, kBytes>; break;
-      default: kernel_of_layout[1] = k_sa_sweep_resume_batch<4, kBytes>; break;
-    }
-  }
-  ASP_TRY(launcher.run<ProblemBatchArgs>(s, d_problems.ptr, d_slots.ptr, [&](int cl) {
-    return ClassKernel<ProblemBatchArgs>{kernel_of_layout[cl % 2], 64u * kWaves[cl / 2]};
+  ASP_TRY(launcher.run(s, d_problems.ptr, d_slots.ptr, [&](int cl) {
+    return ClassKernel<Problem>{colour_kernel_of<BatchFamily<Problem>>(cl % 2 == 0 ? 4 : m, cl % 2 == 0 ? kWide : kBytes),
+                                64u * kWaves[cl / 2]};
   }));
   // ---- the state back into the handles (after the attempt: the colour order has no retry) ----
   hipLaunchKernelGGL(k_chains_unpermute_problems, dim3(static_cast<unsigned>(h_chains_out.size())), dim3(256), 0, s,
@@ -3635,7 +3554,7 @@ int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float
   ASP_HIP_TRY(hipEventElapsedTime(&ms, launcher.begin, launcher.end));
   if (sweep_ms) *sweep_ms += ms;
   for (size_t k = 0; k < entries.size(); ++k) {
-    asp_sa_plan *p = segs[entries[k].seg].chains->plan;
+    asp_sa_plan *p = segs[entries[k].item].chains->plan;
     const int cl = class_of(entries[k]);
     p->last_m = m;
     p->last_layout = p->last_spin_layout = cl % 2 == 0 ? kWide : kBytes;
@@ -3662,7 +3581,7 @@ int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, fl
 // with sa.greedy_solve (Makefile:115-127, experiments/sampled_connected_components.py:696-751).
 // asp_sa_greedy spends one workgroup, ~25 launches and a host round trip every 8 sweeps on each.
 // Here the host trees of all items run on a small thread pool, their signs go up in ONE copy and
-// are permuted by ONE launch, every problem is a workgroup of a few shared k_sa_descent_batch
+// are permuted by ONE launch, every problem is a workgroup of a few shared descent
 // launches (one per wavefront count) that decides on the device when it has converged, and the
 // energies, configurations and sweep counts come back in one copy each.
 
@@ -3854,12 +3773,9 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
               h_x0_shared.begin() + off[k].x);
     DescentProblem d{};
     SweepArgs &a = d.s;
-    a = plan_sweep_args(p, ColourLaunch{});  // (bytes; betas stay null and the seed 0: the descent reads neither)
-    a.x0_perm = d_x0_perm.ptr + off[k].blocks;
-    a.best_perm = d_best.ptr + off[k].blocks;
-    a.tracked = d_tracked.ptr + k;
-    a.accepted = d_accepted.ptr + k;
-    a.num_sweeps = it.max_sweeps;
+    // (betas stay null and the seed 0: the descent reads neither)
+    a = sweep_args(p, kBytes, nullptr, d_x0_perm.ptr + off[k].blocks, d_best.ptr + off[k].blocks, d_tracked.ptr + k,
+                   d_accepted.ptr + k, 0, it.max_sweeps, 0);
     // the field cache and its inert blocks as in the single path: late sweeps flip little
     a.field_cache = use_cache ? d_cache.ptr + off[k].cache : nullptr;
     a.cache_enter_flips = cache_enter_flips_of(L);
@@ -3903,8 +3819,8 @@ int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
                      d_problems.ptr);
   ASP_HIP_TRY(hipGetLastError());
   // ---- one descent launch per class ----
-  ASP_TRY(launcher.run<DescentBatchArgs>(s, d_problems.ptr, d_slots.ptr, [&](int c) {
-    return ClassKernel<DescentBatchArgs>{k_sa_descent_batch<kBytes>, 64u * kBatchWaves[c]};
+  ASP_TRY(launcher.run(s, d_problems.ptr, d_slots.ptr, [&](int c) {
+    return ClassKernel<DescentProblem>{colour_kernel_of<BatchFamily<DescentProblem>>(1, kBytes), 64u * kBatchWaves[c]};
   }));
   // ---- energies and original-order bits of every problem's final configuration ----
   ASP_TRY(launch_post_batch(d_post.ptr, d_chains.ptr, static_cast<unsigned>(n), energy_lds, max_lds, s));

@@ -64,6 +64,7 @@ def test_plan_rejects_bad_matrices_and_oversized_problems():
         sa.anneal(ok, seed=1, number_sweeps=2, repetitions=1, x0=np.zeros(3, np.uint64))
     lib = _lib.load()
     assert lib.asp_sa_set_launch(ok.plan(), 3, 0) == -3
+    assert lib.asp_sa_set_launch(ok.plan(), 16, 0) == -3  # (no form has 16 chains per group)
     assert lib.asp_sa_set_launch(ok.plan(), 0, 100) == -3
     bad_betas = np.array([1.0, -2.0])
     out_x = np.zeros(1, np.uint64)

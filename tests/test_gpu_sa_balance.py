@@ -235,7 +235,7 @@ def test_resumed_segments(ref, wide):
 @pytest.mark.gpu
 @pytest.mark.parametrize("m,wide", [(2, False), (4, False), (4, True)])
 def test_ladder_segment(ref, m, wide):
-    """Every chain at its own inverse temperature (k_sa_sweep_ladder): chain r is the oracle's chain on
+    """Every chain at its own inverse temperature (k_sa_sweep_resume with ResumeLadder): chain r is the oracle's chain on
     the constant schedule beta_r."""
     from annealing_sign_problem_amd import _lib
     from annealing_sign_problem_amd import annealer as sa
@@ -291,7 +291,7 @@ def test_batched_anneal_of_three_sizes():
 
 @pytest.mark.gpu
 def test_batched_greedy_descent_of_three_sizes():
-    """greedy_solve_batch (k_sa_descent_batch) against the oracle's greedy solver."""
+    """greedy_solve_batch (k_sa_sweep_batch over DescentProblem) against the oracle's greedy solver."""
     from annealing_sign_problem_amd import annealer as sa
 
     problems = _three_problems()

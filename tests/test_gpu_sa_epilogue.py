@@ -351,7 +351,7 @@ def test_resume_in_two_segments(ref, wide):
 @pytest.mark.gpu
 @pytest.mark.parametrize("m,wide", [(1, 0), (2, 0), (4, 0), (4, 1), (8, 0)])
 def test_ladder_segment(ref, m, wide):
-    """Every chain at its own inverse temperature (k_sa_sweep_ladder), a frozen, a hot and an infinitely hot
+    """Every chain at its own inverse temperature (k_sa_sweep_resume with ResumeLadder), a frozen, a hot and an infinitely hot
     chain side by side in one group: chain r is the oracle's chain on the constant schedule beta_r."""
     from annealing_sign_problem_amd import annealer as sa
 

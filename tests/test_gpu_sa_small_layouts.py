@@ -681,6 +681,106 @@ def test_colour_order_layouts_through_the_limit():
         _same_as_oracle(forced, forced_stats, want, "colour forced " + NAMES[layout])
 
 
+def _nibble_plan(c):
+    """A plan of its own with four chains per group forced and the limit that runs nibbles: five chains
+    from offset 5 are a full group and a ragged one whose first replica is no multiple of four."""
+    ham = c.fresh()
+    _set_launch(ham, 4)
+    _set_limit(ham, _colour_limits_of(c.name)[NIBBLES])
+    return ham
+
+
+@pytest.mark.parametrize("name", ["mixed", "k65"])
+def test_colour_handle_segments_in_nibbles(name):
+    """The segment kernel in the nibble layout (four chains per group): the case's schedule in segments of
+    5, 1, 0 and the rest of its sweeps, untraced; every segment that runs reports nibbles and groups of
+    four, and the handle ends where the oracle's closed colour-order call for the whole schedule ends."""
+    from annealing_sign_problem_amd import annealer as sa
+
+    c = _case(name)
+    ham = _nibble_plan(c)
+    lengths = (5, 1, 0, len(c.betas) - 6)
+    with sa.Chains(ham, seed=SEED, repetitions=REPS, x0=None, replica_offset=OFFSET) as chains:
+        done = 0
+        for n in lengths:
+            assert chains.advance(c.betas[done:done + n], sweep_order="colour") is None
+            if n:
+                assert (_spin_layout(ham), _last_m(ham)) == (NIBBLES, 4), (n, NAMES[_spin_layout(ham)])
+            done += n
+        (xs, es), state = chains.result(), chains.state()
+    oxs, oes, otracked, oaccepted = _oracle(name, False, False)
+    assert np.array_equal(xs, oxs) and es.tobytes() == oes.tobytes()
+    assert np.array_equal(state["tracked_best"], otracked) and np.array_equal(state["accepted"], oaccepted)
+    assert int(state["sweeps_done"]) == len(c.betas)
+
+
+@pytest.mark.parametrize("name", ["mixed", "k65"])
+def test_colour_ladder_segments_in_nibbles(name):
+    """The ladder-segment kernel in the nibble layout: after a ladder segment chain r is where a one-chain
+    handle at the constant beta[r] and replica offset OFFSET + r is; an exchange and a second ladder segment
+    then equal the same steps at the device's limit, where four chains per group run the word layout."""
+    from annealing_sign_problem_amd import annealer as sa
+
+    c = _case(name)
+    ham = _nibble_plan(c)
+    nibble_limit = _colour_limits_of(name)[NIBBLES]
+    betas = _chain_betas(c.info, REPS)
+    rng = np.random.default_rng(41)
+    x0 = np.stack([sa.signs_to_bits(np.where(rng.random(c.K) < 0.5, 1.0, -1.0)) for _ in range(REPS)])
+
+    def run(limit):
+        _set_limit(ham, limit)
+        with sa.Chains(ham, seed=SEED, repetitions=REPS, x0=x0, replica_offset=OFFSET) as chains:
+            assert chains.advance_ladder(betas, N1, sweep_order="colour") is None
+            ran = [(_spin_layout(ham), _last_m(ham))]
+            state1 = chains.state()
+            swapped = chains.exchange(betas, 0, 3)
+            chains.advance_ladder(betas, N2, sweep_order="colour")
+            ran.append((_spin_layout(ham), _last_m(ham)))
+            return ran, state1, swapped, chains.state(), chains.result()
+
+    ran, state1, swapped, state2, (xs, es) = run(nibble_limit)
+    assert ran == [(NIBBLES, 4)] * 2, ran
+    for r in range(REPS):  # (on the case's own plan: the device's limit, no forced group size)
+        with sa.Chains(c.ham, seed=SEED, repetitions=1, x0=x0[r], replica_offset=OFFSET + r) as alone:
+            alone.advance(np.full(N1, betas[r]), sweep_order="colour")
+            _same_state(state1, alone.state(), rows=slice(r, r + 1))
+    ran0, state10, swapped0, state20, (xs0, es0) = run(0)
+    assert ran0 == [(WORDS, 4)] * 2, ran0
+    _same_state(state1, state10)
+    assert np.array_equal(swapped[0], swapped0[0]) and swapped[1].tobytes() == swapped0[1].tobytes()
+    assert swapped[2] == swapped0[2]
+    assert np.array_equal(xs, xs0) and es.tobytes() == es0.tobytes()
+    _same_state(state2, state20)
+
+
+def test_colour_traced_segment_at_the_nibble_limit_runs_bits():
+    """Nibbles are not taken for a traced run: at the limit where an untraced segment runs nibbles with four
+    chains per group, the traced segment behind it runs bits with one chain per workgroup, and its rows
+    (and the handle) equal the same two segments at the device's limit."""
+    from annealing_sign_problem_amd import annealer as sa
+
+    c = _case("mixed")
+    ham = _nibble_plan(c)
+    nibble_limit = _colour_limits_of("mixed")[NIBBLES]
+
+    def run(limit):
+        _set_limit(ham, limit)
+        with sa.Chains(ham, seed=SEED, repetitions=REPS, x0=c.x0, replica_offset=OFFSET) as chains:
+            chains.advance(c.betas[:1], sweep_order="colour")
+            ran = [(_spin_layout(ham), _last_m(ham))]
+            rows = chains.advance(c.betas[1:9], sweep_order="colour", trace=True)
+            ran.append((_spin_layout(ham), _last_m(ham)))
+            return ran, rows, chains.state()
+
+    ran, rows, state = run(nibble_limit)
+    assert ran == [(NIBBLES, 4), (BITS, 1)], ran
+    ran0, rows0, state0 = run(0)
+    assert ran0 == [(WORDS, 4)] * 2, ran0
+    assert rows.shape == (REPS, 9) and np.array_equal(rows, rows0)
+    _same_state(state, state0)
+
+
 def test_colour_batch_has_a_nibble_class_at_small_sizes():
     """Plans limited to nibbles go into the shared launches of asp_sa_anneal_batch as its nibble class,
     beside one at the device's limit: every item is its single call, "mixed" the oracle's."""
