@@ -1532,3 +1532,63 @@ def test_randomised_shuffled_configurations_match_oracle():
         assert np.array_equal(xs, oxs), label
         assert es.tobytes() == oes.tobytes(), label
         assert np.array_equal(tracked, otr) and np.array_equal(accepted, oacc), label
+
+
+@pytest.mark.parametrize("threads", ["1", None])
+def test_plans_from_the_threaded_general_merge(threads, monkeypatch):
+    """From 20 000 spins on the plan build's general route (transposition with per-part cursors,
+    two-pass merge of J and J^T: csrc/sa_plan.cpp) runs on several host threads; the large tests'
+    planted clusters are exactly symmetric and never take it.  20 011 spins (ragged ranges): plans
+    of a one-sided matrix and of an upper triangle, built on one host thread and on the default
+    four: the same plan either way, both sweep orders equal the oracle bit for bit, the upper
+    triangle gives its symmetric twin's chains, and the energies agree with numpy."""
+    from host_thread_cases import forms
+
+    from annealing_sign_problem_amd import annealer as sa
+
+    n = 20011
+    matrices, field = forms(n)
+    words = (n + 63) // 64
+    rng = np.random.default_rng(7)
+    configurations = rng.integers(0, 2**64, size=(4, words), dtype=np.uint64)
+    configurations[:, -1] &= np.uint64((1 << (n % 64)) - 1)
+    signs = [sa.bits_to_signs(x, n) for x in configurations]
+    results = {}
+    for form in ("one_sided", "upper", "symmetric"):
+        J = matrices[form]
+        infos = []
+        for setting in ((None, "1") if threads == "1" else ("1", None)):  # this test's setting last
+            if setting is None:
+                monkeypatch.delenv("ASP_HOST_THREADS", raising=False)
+            else:
+                monkeypatch.setenv("ASP_HOST_THREADS", setting)
+            ham = sa.Hamiltonian(J, field)
+            infos.append(ham.info())
+            if len(infos) == 1:
+                ham.release()
+        other_info, info = infos
+        for name, _ in info._fields_:
+            assert getattr(info, name) == getattr(other_info, name), (form, name)
+        assert info.num_spins == n and info.num_colors > 1
+        betas = sa.make_schedule(max(info.beta0_auto, 1e-3), min(max(info.beta1_auto, 1.0), 1e6), 3)
+        S = info.energy_scale_exp
+        for shuffled, run in ((False, oracle.sa_anneal), (True, oracle.sa_anneal_shuffled)):
+            xs, es = sa.anneal_raw(ham, 20011, betas, 2, 1, None, shuffled=shuffled)
+            tracked, accepted = _stats(ham, 2)
+            results[form, shuffled] = (xs, es, tracked, accepted)
+            if form == "symmetric":
+                continue                     # the twin: compared with the upper triangle below
+            oxs, oes, otracked, oaccepted = run(J, field, 20011, betas, 2, 1, None, S, num_threads=2)
+            assert np.array_equal(xs, oxs), (form, shuffled)
+            assert es.tobytes() == oes.tobytes(), (form, shuffled)
+            assert np.array_equal(tracked, otracked) and np.array_equal(accepted, oaccepted), (form, shuffled)
+            assert accepted.min() > 0
+        if form != "symmetric":
+            got = ham.energies(configurations)
+            for s, e in zip(signs, got):
+                ref = s @ (J @ s) + field @ s
+                assert abs(e - ref) <= 1e-12 * max(abs(ref), 1e-300), (form, e, ref)
+        ham.release()
+    for shuffled in (False, True):
+        for got, want in zip(results["upper", shuffled], results["symmetric", shuffled]):
+            assert got.tobytes() == want.tobytes(), shuffled
