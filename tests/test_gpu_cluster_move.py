@@ -3,7 +3,11 @@ ASP-ICM-1) against the law as tests/cluster_move_law.py restates it — all five
 Chains.state() and the three outputs, exact — on the shapes where the kernel can go wrong: the tail
 word, a path (one site per search round), a hub (a row the wavefront shares), a component that must
 not cross an equal site, isolated seeds, identical and opposite replicas, many pairs in one launch, the
-bit planes in LDS and in HBM; then the driver against the closed calls."""
+bit planes in LDS and in HBM; then the driver against the closed calls.
+
+What comes out when sweeps, exchange and cluster moves are composed is tested in
+tests/test_gpu_ensemble_law.py against the exact joint law of tests/ensemble_exact_law.py, which is
+independent of the restated law used here."""
 import ctypes
 import os
 

@@ -6,6 +6,10 @@ The references are a one-chain handle run on the constant ladder, the CPU oracle
 sa_anneal_shuffled), Hamiltonian.energies, the law restated in tests/tempering_law.py and numpy
 indexing of an exported state (tests/population_law.gathered) — never the code against itself.
 Problems come from synthetic.planted_cluster, like those of tests/test_gpu_chains.py.
+
+What comes out when sweeps, exchange and cluster moves are composed is tested in
+tests/test_gpu_ensemble_law.py against the exact joint law of tests/ensemble_exact_law.py, which is
+independent of the restated law used here.
 """
 import ctypes
 
