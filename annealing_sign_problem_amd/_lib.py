@@ -250,8 +250,10 @@ SIGNATURES = {
     "asp_sa_set_lds_limit": (c_int, [c_void_p, c_u64]),
     "asp_sa_last_spin_layout": (c_int, [c_void_p]),
     "asp_sa_set_field_cache": (c_int, [c_void_p, c_int]),
+    "asp_sa_set_tail": (c_int, [c_void_p, c_int]),
+    "asp_sa_last_tail": (c_int, [c_void_p, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
     "asp_sa_set_post": (c_int, [c_void_p, c_int]),
-    "asp_sa_anneal": (c_int, [c_void_p, c_u64, c_void_p, c_u32, c_u32, c_u32, c_void_p, c_void_p,
+    "asp_sa_anneal":(c_int, [c_void_p, c_u64, c_void_p, c_u32, c_u32, c_u32, c_void_p, c_void_p,
                               c_void_p]),
     "asp_sa_anneal_trace": (c_int, [c_void_p, c_u64, c_void_p, c_u32, c_u32, c_u32, c_void_p,
                                     c_void_p, c_void_p, c_void_p]),

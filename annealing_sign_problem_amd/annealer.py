@@ -333,6 +333,18 @@ def anneal_raw(hamiltonian: Hamiltonian, seed: int, betas: np.ndarray, repetitio
     return xs[:, :words], es
 
 
+def set_tail(hamiltonian: Hamiltonian, n: int = -1) -> None:
+    """``asp_sa_set_tail``: -1 automatic, 0 no tail sweeps, n > 0 tail sweeps below n flips per sweep."""
+    _lib.check(_lib.load().asp_sa_set_tail(hamiltonian.plan(), int(n)))
+
+
+def last_tail(hamiltonian: Hamiltonian):
+    """``asp_sa_last_tail`` of the last closed colour call: (sweeps_min, sweeps_max, entries_max)."""
+    out = [ctypes.c_uint32(0) for _ in range(3)]
+    _lib.check(_lib.load().asp_sa_last_tail(hamiltonian.plan(), *[ctypes.byref(v) for v in out]))
+    return tuple(int(v.value) for v in out)
+
+
 def anneal_raw_into(hamiltonian: Hamiltonian, seed: int, betas: np.ndarray, repetitions: int,
                     replica_offset: int, x0, out_x_ptr: int, out_e_ptr: int,
                     shuffled: bool = False) -> None:

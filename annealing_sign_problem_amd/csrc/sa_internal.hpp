@@ -95,6 +95,9 @@ struct asp_sa_plan {
   }
   int team_mode = -1;  // asp_sa_set_team: -1 auto, 0 off, G >= 2 forced
   bool use_field_cache = true;
+  int tail_mode = -1;  // asp_sa_set_tail: -1 auto, 0 off, n > 0: tail sweeps below n flips per sweep
+  asp::DeviceBuffer<uint32_t> w_tail;  // [groups][2] tail sweeps run and entries into them (TailArgs::report)
+  std::vector<uint32_t> last_tail;     // its host copy for the last closed call (empty: no tail kernel)
   bool use_post = true;  // asp_sa_set_post: k_sa_post for the pass after a sweep launch
   uint32_t team_abort_host = 0;  // landing place of the watchdog flag's asynchronous read-back
   uint32_t team_watchdog_trips = 0;  // calls of this plan that the team barrier's watchdog cut short (each ~5 s lost)

@@ -358,6 +358,7 @@ int asp_sa_plan_clone(asp_sa_plan const *p, asp_sa_plan **out) {
   c->allow_wide = p->allow_wide;
   c->team_mode = p->team_mode;
   c->use_field_cache = p->use_field_cache;
+  c->tail_mode = p->tail_mode;
   c->use_post = p->use_post;
   c->shuffled_m = p->shuffled_m;
   c->shuffled_waves = p->shuffled_waves;

@@ -479,6 +479,14 @@ struct LadderBetas<M, true> {
   }
 };
 
+// What the TAIL form of the body takes beside SweepArgs (k_sa_sweep_tail; a wrapper would change the
+// descriptor stride of the batched kernels, so it travels as a kernel argument of its own).
+struct TailArgs {
+  uint32_t enter_flips;  // tail sweeps after a sweep with fewer flips of the workgroup than this
+  uint32_t *report;      // [groups][2]: sweeps run as tail sweeps, entries into tail mode
+};
+constexpr uint32_t kTailRing = 128;  // rows a wavefront stages: under 64 waiting plus one block's 64
+
 // DESCENT = true: strict-descent sweeps (accept iff dE < 0, no random numbers, no beta: a.betas is
 // never read), used by the greedy solver's relaxation; the final configuration is snapshotted
 // after every sweep.
@@ -490,10 +498,17 @@ struct LadderBetas<M, true> {
 // keeps a second call path for a group that straddles two calls and selects every replica's word
 // with pick_word (three v_cndmask_b32 on scalar masks per replica).  Same counters, same words:
 // the chains are the generic body's.
+// TAIL (the closed call's M = 4 kernels in bytes and words): once a sweep flips fewer spins than
+// tail.enter_flips the workgroup keeps one `todo` bit per position in LDS and a sweep evaluates only the
+// listed rows, compacted into visits of 64 rows with lane = row.  These
+// instantiations have no field cache and no inert bytes.  Every other one keeps the code it had.
 template <int M, bool DESCENT, int LAYOUT, typename Args, typename Stop = NoEarlyStop,
-          typename Res = NoResume, bool ALIGNED = false>
+          typename Res = NoResume, bool ALIGNED = false, bool TAIL = false>
 __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t group,
-                                              const Stop stop = Stop{}, const Res res = Res{}) {
+                                              const Stop stop = Stop{}, const Res res = Res{},
+                                              const TailArgs tail = TailArgs{}) {
+  static_assert(!TAIL || (M == 4 && !DESCENT && !Res::kEnabled && (LAYOUT == kBytes || LAYOUT == kWide)),
+                "tail sweeps: the closed call of four chains in bytes or words");
   static_assert(DESCENT || !Stop::kEnabled, "only a descent can stop early");
   static_assert(!ALIGNED || (!DESCENT && M == 4), "an aligned group is one whole Philox call");
   static_assert(!DESCENT || !Res::kEnabled, "a descent is never resumed");
@@ -534,7 +549,13 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
   // evaluation every proposal was a certain rejection (beta * dE >= 23 -> expneg = 0, or
   // dE >= 0 in descent mode) and beta has not decreased since, so the visit can be skipped
   uint8_t *inert = dirty + ((a.num_blocks + 15u) & ~15u);
-  const bool cache_available = !PACKED && a.field_cache != nullptr;
+  const bool cache_available = !TAIL && !PACKED && a.field_cache != nullptr;
+  // TAIL: no dirty and inert bytes; behind cache_ctl[4] come [4] the sweeps run as tail sweeps, [5] the
+  // entries into tail mode (cache_ctl[0] counts the flips as above, [1] is 1 while tail sweeps run,
+  // [2] 1 when they were just entered: every todo bit must be set), then one todo word per block (bit l:
+  // row l is evaluated at the next visit of its colour) and kTailRing staged rows per wavefront
+  [[maybe_unused]] uint64_t *todo = reinterpret_cast<uint64_t *>(cache_ctl + 8);
+  [[maybe_unused]] uint32_t *todo32 = reinterpret_cast<uint32_t *>(todo);
 
   // accumulate addresses the spin bytes absolutely: the dynamic LDS block must be the first
   // (this kernel declares no static LDS)
@@ -628,6 +649,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     cache_ctl[1] = 0;
     cache_ctl[2] = 0;
     cache_ctl[3] = 0;  // block tickets drawn so far (colour loop)
+    if constexpr (TAIL) cache_ctl[4] = cache_ctl[5] = 0;
   }
   if constexpr (Res::kEnabled) {
     // (the best configuration so far is in a.best_perm already and stays unless the segment
@@ -680,7 +702,206 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
       n_acc[m] = 0;
     }
 
-    for (uint32_t c = 0; c < a.num_colors; ++c) {
+    // the first colour of the colour loop below: every colour, or none after a tail sweep
+    uint32_t first_hot_colour = 0;
+    if constexpr (TAIL) {
+      // ---- a tail sweep (workgroup-uniform branch): only the rows listed in `todo` ----
+      // Per colour a wavefront takes every waves-th block of the colour, 64 of them at a time (lane i
+      // reads and clears the word of its i-th), and stages the listed rows of the non-empty ones,
+      // block by block, in its ring at their mbcnt ranks.  As soon as 64 rows wait they are one visit
+      // with lane = row: every lane streams its OWN row (its block's first quad, its lane and the quad
+      // in a per-lane buffer offset), accumulates nothing from its own width on, and sums in
+      // ascending k with accumulate() — the block visit's f64 values bit for bit.  The accept phase is
+      // the visit's.  Rows of a colour are independent, the random words are keyed by (spin, sweep,
+      // replica) and the energy sums are integers: which rows share a visit changes no result.
+      if (__builtin_amdgcn_readfirstlane(cache_ctl[1]) != 0) {
+        const uint32_t wave_u = __builtin_amdgcn_readfirstlane(wave);
+        uint32_t *ring = reinterpret_cast<uint32_t *>(todo + a.num_blocks) + wave_u * kTailRing;
+        const BufferRsrc col_rsrc = block_rsrc(a.ell_col), val_rsrc = block_rsrc(a.ell_val);
+        for (uint32_t c = 0; c < a.num_colors; ++c) {
+          const uint32_t b_begin = a.color_block_start[c];
+          const uint32_t nb = a.color_block_start[c + 1] - b_begin;
+          uint32_t fill = 0, drained = 0;  // rows staged and rows visited so far (wave-uniform)
+          uint32_t base = 0, next_base = wave_u;
+          uint64_t w = 0, nonempty = 0;  // the lane's word of the running 64 blocks, and which lanes' are left
+          for (;;) {
+            while (fill - drained < 64u) {
+              if (nonempty == 0ull) {
+                if (next_base >= nb) break;
+                base = next_base;
+                next_base += waves * 64u;
+                const uint32_t i = base + lane * waves;
+                w = 0;
+                if (i < nb) {
+                  // nobody marks a block during its own colour step but the wavefront that took it
+                  w = todo[b_begin + i];
+                  if (w != 0ull) todo[b_begin + i] = 0ull;
+                }
+                nonempty = __ballot(w != 0ull);
+                continue;
+              }
+              const uint32_t src = static_cast<uint32_t>(__builtin_ctzll(nonempty));
+              nonempty &= nonempty - 1ull;
+              const uint32_t w_lo = __builtin_amdgcn_readlane(static_cast<uint32_t>(w), src);
+              const uint32_t w_hi = __builtin_amdgcn_readlane(static_cast<uint32_t>(w >> 32), src);
+              const uint32_t rank = __builtin_amdgcn_mbcnt_hi(w_hi, __builtin_amdgcn_mbcnt_lo(w_lo, 0u));
+              const uint32_t mine = lane < 32u ? w_lo >> lane : w_hi >> (lane - 32u);
+              if (mine & 1u) ring[(fill + rank) & (kTailRing - 1u)] = (b_begin + base + src * waves) * 64u + lane;
+              fill += static_cast<uint32_t>(__builtin_popcount(w_lo) + __builtin_popcount(w_hi));
+            }
+            const uint32_t count = min(64u, fill - drained);
+            if (count == 0u) break;
+            // (LDS operations of one wavefront complete in order; the fence keeps the compiler's order)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            // ---- one visit of `count` rows; the other lanes behave like dummy lanes ----
+            const bool live = lane < count;
+            uint32_t p = 0, row_quads = 0, col_at = 0, val_at = 0;
+            if (live) {
+              p = ring[(drained + lane) & (kTailRing - 1u)];
+              const uint2 info = meta[p >> 6];
+              row_quads = info.y >> 2;
+              // the lane's row in the arrays, from their start (the host launches this form only while
+              // both arrays stay below 4 GiB): columns 1024 B and values 2048 B per quad of a block
+              col_at = (info.x >> 2) * 1024u + (p & 63u) * 16u;
+              val_at = (info.x >> 2) * 2048u + (p & 63u) * 16u;
+            }
+            drained += count;
+            visits += 1;
+            // The row's spin and field: in bytes issued now and consumed behind the row sum, like the
+            // block visit's.  In words they are read behind the k-loop: a lane of this visit holds more
+            // of its own (its position, width and offsets) than a lane of a block visit, and the word
+            // layout has no register left for them (held across the loop they went to scratch).
+            uint32_t spin = kDummySpin;
+            double h = 0.0;
+            if constexpr (!WIDE) {
+              if (live) {
+                spin = a.spin_of_pos[p];
+                h = a.field_pos[p];
+              }
+            }
+            // A lane streams the quads of its OWN row and never the next block's: from its width on it
+            // reads the first 48 bytes of the arrays instead (one cache line for all such lanes) and
+            // accumulates nothing.  Every load is issued unconditionally — a load under a lane mask makes
+            // hipcc drain the queue in front of each accumulate —, so the quad is part of the lane's
+            // offset and the k-loop keeps the block visit's prefetch distance of one.
+            auto load_row_quad = [&](Quad &q, uint32_t quad) {
+              const bool mine = quad < row_quads;
+              const uint32_t c_at = mine ? col_at + quad * 1024u : 0u;
+              const uint32_t v_at = mine ? val_at + quad * 2048u : 0u;
+              q.c = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(col_rsrc, c_at, 0, 0));
+              q.v01 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(val_rsrc, v_at, 0, 0));
+              q.v23 = __builtin_bit_cast(double2,
+                                         __builtin_amdgcn_raw_buffer_load_b128(val_rsrc, v_at + (mine ? 1024u : 16u), 0, 0));
+            };
+            double acc[M];
+#pragma unroll
+            for (int m = 0; m < M; ++m) acc[m] = 0.0;
+            Quad qa, qb;
+            load_row_quad(qa, 0u);
+            for (uint32_t q = 0; __ballot(q < row_quads) != 0ull; q += 2u) {
+              load_row_quad(qb, q + 1u);
+              __builtin_amdgcn_sched_barrier(0);
+              if (q < row_quads) accumulate<M, LAYOUT>(qa, spins, acc, mult);
+              __builtin_amdgcn_sched_barrier(0);
+              load_row_quad(qa, q + 2u);
+              __builtin_amdgcn_sched_barrier(0);
+              if (q + 1u < row_quads) accumulate<M, LAYOUT>(qb, spins, acc, mult);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+            // the accept phase of the visit (below), in its lean form
+            uint32_t own = 0;
+            if (live) {
+              if constexpr (WIDE) {
+                spin = a.spin_of_pos[p];
+                h = a.field_pos[p];
+              }
+              if constexpr (WIDE) {
+                own = reinterpret_cast<const uint32_t *>(spins)[p];
+              } else {
+                own = spins[p];
+              }
+            }
+            const bool valid = spin != kDummySpin;
+            bool open = false, need = false;
+            double de[M];
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+              const double g = __dadd_rn(acc[m], h);
+              const bool negative = (own >> (WIDE ? 8 * m + 7 : replica_bit<M, LAYOUT>(m))) & 1u;  // s = -1
+              de[m] = __dmul_rn(negative ? 2.0 : -2.0, g);
+              const bool maybe = valid && !(__dmul_rn(beta, de[m]) >= 23.0);  // not a certain rejection
+              open = open || maybe;
+              need = need || (maybe && !(de[m] <= 0.0));
+            }
+            uint32_t took[M];
+            if (__ballot(need) != 0ull) {
+              Philox4 rnd{};
+              uint32_t have = 0xFFFFFFFFu;
+#pragma unroll
+              for (int m = 0; m < M; ++m) {
+                uint32_t word;
+                if constexpr (ALIGNED) {
+                  if (m == 0) rnd = philox4x32_10(spin, t_draw, r0 >> 2, 0u, key0, key1);
+                  word = rnd.w[m];
+                } else {
+                  const uint32_t r = r0 + m;
+                  if (m == 0 || (r >> 2) != have) {
+                    have = r >> 2;
+                    rnd = philox4x32_10(spin, t_draw, have, 0u, key0, key1);
+                  }
+                  word = pick_word(rnd, r & 3u);
+                }
+                const bool accept =
+                    valid && (de[m] <= 0.0 || metropolis_accept_word(word, __dmul_rn(beta, de[m])));
+                took[m] = accept ? 0xFFFFFFFFu : 0u;
+              }
+            } else {
+#pragma unroll
+              for (int m = 0; m < M; ++m) took[m] = (valid && de[m] <= 0.0) ? 0xFFFFFFFFu : 0u;
+            }
+            uint32_t flip = 0;
+            double round_bias = 0x1.8p52;
+            asm volatile("" : "+v"(round_bias));
+            const uint32_t scale_hi = static_cast<uint32_t>(__double2hiint(a.scale));
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+              flip |= took[m] & (1u << m);
+              const double scale_m = __hiloint2double(static_cast<int>(scale_hi & took[m]), 0);
+              q_acc[m] += static_cast<unsigned long long>(
+                  __double_as_longlong(__builtin_fma(de[m], scale_m, round_bias)));
+              n_acc[m] -= took[m];  // + 1 when accepted
+            }
+            // the row comes back while a proposal of it is open (an accepted one was); positions of a
+            // visit are distinct: plain stores
+            if (open) atomicOr(&todo32[p >> 5], 1u << (p & 31u));
+            if (flip) {
+              if constexpr (WIDE) {
+                reinterpret_cast<uint32_t *>(spins)[p] = own ^ spread_mask(flip);
+              } else {
+                spins[p] = static_cast<uint8_t>(own ^ encode_replicas<M, LAYOUT>(flip));
+              }
+              // every neighbour's field changed: list it (the neighbours are of other colours; the
+              // row's columns only, its padding entries point at the row itself)
+              const uint4 *cols4 = reinterpret_cast<const uint4 *>(
+                  reinterpret_cast<const uint8_t *>(a.ell_col) + col_at);
+              for (uint32_t q = 0; q < row_quads; ++q) {
+                const uint4 c4 = cols4[q * 64u];
+                const uint32_t cols[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  const uint32_t at = WIDE ? cols[j] >> 2 : cols[j];
+                  if (at != p) atomicOr(&todo32[at >> 5], 1u << (at & 31u));
+                }
+              }
+            }
+          }
+          __syncthreads();
+        }
+        first_hot_colour = a.num_colors;
+      }
+    }
+
+    for (uint32_t c = first_hot_colour; c < a.num_colors; ++c) {
       const uint32_t b_begin = a.color_block_start[c];
       const uint32_t b_end = a.color_block_start[c + 1];
       // The colour's blocks go to the wavefronts in ascending order (widest rows first, the plan
@@ -951,7 +1172,7 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
                 atomicAdd(reinterpret_cast<unsigned long long *>(&delta[m0 + j]), v[j]);
                 atomicAdd(reinterpret_cast<unsigned long long *>(&book[16 + m0 + j]),
                           static_cast<unsigned long long>(n));
-                if (cache_available) atomicAdd(&cache_ctl[0], n);
+                if (TAIL || cache_available) atomicAdd(&cache_ctl[0], n);
               }
             }
           }
@@ -968,6 +1189,22 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
       const bool now = was ? flips < 2u * a.cache_enter_flips : flips < a.cache_enter_flips;
       cache_ctl[1] = now ? 1u : 0u;
       cache_ctl[2] = (now && !was) ? 1u : 0u;  // entering: every block starts stale
+    }
+    if constexpr (TAIL) {
+      if (tid == 0) {
+        // Tail sweeps pay while few rows are listed: enter below `enter_flips` flips per sweep, leave
+        // above twice that, and leave in front of a sweep at a lower beta — a certain rejection is only
+        // certain for non-decreasing beta, and the rows that are not listed rest on it.
+        const uint32_t flips = cache_ctl[0];
+        cache_ctl[0] = 0;
+        const bool was = cache_ctl[1] != 0;
+        bool now = was ? flips <= 2ull * tail.enter_flips : flips < tail.enter_flips;
+        if (t + 1u < a.num_sweeps && a.betas[t + 1u] < beta) now = false;
+        cache_ctl[1] = now ? 1u : 0u;
+        cache_ctl[2] = (now && !was) ? 1u : 0u;  // entering: every row is listed
+        if (was) cache_ctl[4] += 1u;
+        if (now && !was) cache_ctl[5] += 1u;
+      }
     }
     if (tid < M) {
       const long long e = book[tid] + delta[tid];
@@ -999,10 +1236,21 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
     if (cache_available && cache_ctl[2] != 0) {
       for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) dirty[b] = 0xFF;
     }
+    if constexpr (TAIL) {
+      if (cache_ctl[2] != 0) {
+        for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) todo[b] = ~0ull;
+      }
+    }
     __syncthreads();
     if (tid == 0) {
       *improved_flag = 0;  // next write to it is two barriers away
-      if (cache_available) cache_ctl[2] = 0;
+      if (TAIL || cache_available) cache_ctl[2] = 0;
+    }
+  }
+  if constexpr (TAIL) {
+    if (tid == 0) {
+      tail.report[2ull * group] = cache_ctl[4];
+      tail.report[2ull * group + 1u] = cache_ctl[5];
     }
   }
 
@@ -1037,6 +1285,13 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
 template <int M, bool DESCENT, int LAYOUT, bool ALIGNED = false>
 __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep(SweepArgs a) {
   sa_sweep_body<M, DESCENT, LAYOUT, SweepArgs, NoEarlyStop, NoResume, ALIGNED>(a, blockIdx.x);
+}
+
+// The closed call of four chains per group with tail sweeps (the TAIL form of the body), in bytes and words.
+template <int LAYOUT, bool ALIGNED>
+__global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_tail(SweepArgs a, TailArgs tail) {
+  sa_sweep_body<4, false, LAYOUT, SweepArgs, NoEarlyStop, NoResume, ALIGNED, true>(a, blockIdx.x, NoEarlyStop{},
+                                                                                    NoResume{}, tail);
 }
 
 // One segment of an asp_sa_chains handle in the colour order: Res = Resume (asp_sa_chains_advance, order 0)
@@ -1970,6 +2225,44 @@ size_t sweep_lds_bytes(const asp::SaHostLayout &L, int layout) {
          2 * (((static_cast<size_t>(L.num_blocks) + 15) / 16) * 16);
 }
 
+// k_sa_sweep_tail (bytes, words): spins | delta[8] book[24] | flag (16 B) | meta[num_blocks] | cache_ctl[8] |
+// todo[num_blocks] (a u64 each) | kTailRing staged rows per wavefront; no dirty and inert bytes
+size_t tail_lds_bytes(const asp::SaHostLayout &L, int layout, int threads) {
+  const size_t per_block = layout == kWide ? 256 : 64;
+  return static_cast<size_t>(L.num_blocks) * per_block + 34 * sizeof(long long) +
+         static_cast<size_t>(L.num_blocks) * sizeof(uint2) + 32 + static_cast<size_t>(L.num_blocks) * sizeof(uint64_t) +
+         static_cast<size_t>(threads / 64) * kTailRing * sizeof(uint32_t);
+}
+
+// Tail sweeps after a sweep with fewer flips of the workgroup than this (asp_sa_set_tail's automatic
+// value): a flip lists ~degree rows, so c * num_spins / degree flips list the fraction c of all rows at
+// the most.  A listed row costs several times what a row of a block visit costs — its loads touch a cache
+// line per lane where a block visit touches eight per instruction —, so c is small: 0.05 was the fastest
+// of 0.00625 .. 0.4 at K = 3e4 and 1e5 (profiles/tail_timing.txt).  With about one block
+// per wavefront and colour (K = 1e4 on 16 wavefronts) a tail visit replaces one block visit at best: there
+// 0.0125 would be 1 % faster and 0.05 is 0 - 2 % behind the kernel without tail sweeps.
+constexpr double kTailEnterShare = 0.05;
+uint32_t tail_enter_flips_of(const asp::SaHostLayout &L) {
+  const double degree = std::max(1.0, static_cast<double>(L.a_col.size()) / static_cast<double>(L.num_spins));
+  return static_cast<uint32_t>(std::max(1.0, kTailEnterShare * static_cast<double>(L.num_spins) / degree));
+}
+
+// The TAIL kernel of a closed call in `form`, or nullptr: the launch keeps the kernel without tail sweeps
+// of the same form — tail sweeps or the field cache off, another form than four chains in bytes or words,
+// no room in the LDS for the bitmap and the rings, or arrays beyond the 32-bit buffer offsets of a row.
+using TailKernel = void (*)(SweepArgs, TailArgs);
+TailKernel tail_kernel_of(const asp_sa_plan *p, int m, int threads, int layout, bool descent, uint32_t replica_first) {
+  const asp::SaHostLayout &L = p->host;
+  if (p->tail_mode == 0 || !p->use_field_cache || descent || m != 4 || (layout != kBytes && layout != kWide)) {
+    return nullptr;
+  }
+  if (tail_lds_bytes(L, layout, threads) > p->max_lds) return nullptr;
+  if (L.ell_val.size() * sizeof(double) >= (1ull << 32)) return nullptr;
+  const bool aligned = replica_first % 4u == 0;
+  if (layout == kWide) return aligned ? k_sa_sweep_tail<kWide, true> : k_sa_sweep_tail<kWide, false>;
+  return aligned ? k_sa_sweep_tail<kBytes, true> : k_sa_sweep_tail<kBytes, false>;
+}
+
 // k_sa_sweep_team: sign words | book, flags (64 B) | dirty[num_blocks] | inert[num_blocks]
 size_t team_lds_bytes(const asp::SaHostLayout &L) {
   return static_cast<size_t>(L.num_blocks) * 8 + 64 +
@@ -2295,6 +2588,27 @@ int asp_sa_set_field_cache(asp_sa_plan *p, int enable) {
   return ASP_OK;
 }
 
+int asp_sa_set_tail(asp_sa_plan *p, int n) {
+  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
+  if (n < -1) return asp::set_error(ASP_ERR_INVALID, "n must be -1 (auto), 0 (off) or a number of flips");
+  p->tail_mode = n;
+  return ASP_OK;
+}
+
+int asp_sa_last_tail(asp_sa_plan const *p, uint32_t *sweeps_min, uint32_t *sweeps_max, uint32_t *entries_max) {
+  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
+  uint32_t lo = p->last_tail.empty() ? 0u : 0xFFFFFFFFu, hi = 0, entries = 0;
+  for (size_t g = 0; g + 1 < p->last_tail.size(); g += 2) {
+    lo = std::min(lo, p->last_tail[g]);
+    hi = std::max(hi, p->last_tail[g]);
+    entries = std::max(entries, p->last_tail[g + 1]);
+  }
+  if (sweeps_min) *sweeps_min = lo;
+  if (sweeps_max) *sweeps_max = hi;
+  if (entries_max) *entries_max = entries;
+  return ASP_OK;
+}
+
 int asp_sa_set_post(asp_sa_plan *p, int enable) {
   if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
   p->use_post = enable != 0;
@@ -2357,6 +2671,7 @@ struct ColourRun {
   uint32_t groups = 0;
   uint64_t padded = 0;
   SweepArgs args{};
+  bool tail = false;  // a k_sa_sweep_tail launch: no field cache
 
   int shape(const ColourLaunch &form, size_t lds_bytes) {
     m = form.m, threads = form.threads, layout = form.layout, lds = lds_bytes;
@@ -2383,7 +2698,7 @@ struct ColourRun {
       ASP_TRY(p->w_trace.ensure(padded * (static_cast<uint64_t>(num_sweeps) + 1)));
       args.trace = p->w_trace.ptr;
     }
-    if (p->use_field_cache && !bit_packed(layout)) attach_field_cache(p, padded, &args);
+    if (p->use_field_cache && !bit_packed(layout) && !tail) attach_field_cache(p, padded, &args);
     return ASP_OK;
   }
   // ev[1], kernel(args, extra...), ev[2]
@@ -2527,7 +2842,13 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
   }
   if (team >= 2) form.m = 1, form.layout = kBits;
   ColourRun run{p, repetitions, num_sweeps, out_trace};
-  ASP_TRY(run.shape(form, team >= 2 ? team_lds_bytes(L) : sweep_lds_bytes(L, form.layout)));
+  // tail sweeps where the form has them and its LDS has the room: the form itself stays as chosen
+  const TailKernel tail_kernel =
+      team >= 2 ? nullptr : tail_kernel_of(p, form.m, form.threads, form.layout, descent, replica_offset);
+  run.tail = tail_kernel != nullptr;
+  ASP_TRY(run.shape(form, team >= 2 ? team_lds_bytes(L)
+                                    : (run.tail ? tail_lds_bytes(L, form.layout, form.threads)
+                                                : sweep_lds_bytes(L, form.layout))));
   hipStream_t s = p->stream;
   // every exit below, error or not, first waits for what was queued on the stream: copies into
   // the caller's buffers and kernels using the plan's work buffers never outlive the call
@@ -2560,9 +2881,19 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
       return run_chains(p, seed, betas, num_sweeps, repetitions, replica_offset, x0, descent, out_x,
                         out_e, out_trace);
     }
+  } else if (run.tail) {
+    ASP_TRY(p->w_tail.ensure(2ull * run.groups));
+    ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
+    const uint32_t enter = p->tail_mode > 0 ? static_cast<uint32_t>(p->tail_mode) : tail_enter_flips_of(L);
+    ASP_TRY(run.launch(tail_kernel, TailArgs{enter, p->w_tail.ptr}));
   } else {
     ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
     ASP_TRY(run.launch(closed_kernel_of(run.m, descent, run.layout, replica_offset)));
+  }
+  p->last_tail.assign(run.tail ? 2ull * run.groups : 0, 0u);
+  if (run.tail) {
+    ASP_HIP_TRY(hipMemcpyAsync(p->last_tail.data(), p->w_tail.ptr, p->last_tail.size() * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, s));
   }
   // the first `repetitions` rows of best_perm are the real replicas
   // ... their reported energies and, in the same pass, their configurations in original order

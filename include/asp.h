@@ -544,6 +544,23 @@ int asp_sa_team_watchdog_trips(asp_sa_plan const *p, uint32_t *of_plan, uint64_t
  * Pure optimisation of frozen sweeps; results are identical with it on or off. */
 int asp_sa_set_field_cache(asp_sa_plan *p, int enable);
 
+/* Tail sweeps (default automatic): the closed calls with four chains per workgroup in bytes or words
+ * (asp_sa_anneal, asp_sa_anneal_trace) keep one `todo` bit per position once a sweep flips few spins,
+ * and a sweep then evaluates only the listed rows — those with a neighbour that flipped in some chain
+ * since their last evaluation, or with a proposal that was not a certain rejection — compacted into
+ * visits of 64 rows from any blocks of the colour.  These launches run without the field cache.
+ * n = -1: enter below c * num_spins / mean degree flips of the workgroup per sweep (c = 0.05:
+ * DESIGN.md section 6), 0: never (the kernels without tail sweeps, with the field cache), n > 0: enter below
+ * n flips.  Tail sweeps are left above twice the threshold and in front of a sweep whose beta is below
+ * the one before it.  asp_sa_set_field_cache(p, 0) turns them off as well.  Launches whose LDS has
+ * no room for the bitmap keep the kernels without tail sweeps.  Pure optimisation; results are
+ * identical whatever n.  asp_sa_plan_clone copies it. */
+int asp_sa_set_tail(asp_sa_plan *p, int n);
+/* The last closed call of the plan (asp_sa_anneal / _trace): the fewest and the most sweeps one group
+ * of chains ran as tail sweeps, and the most times one group entered them; zeros when the launch took a
+ * kernel without tail sweeps.  Any pointer may be NULL. */
+int asp_sa_last_tail(asp_sa_plan const *p, uint32_t *sweeps_min, uint32_t *sweeps_max, uint32_t *entries_max);
+
 /* The pass after the sweeps (default on): for eight or more configurations whose sign bytes fit the
  * LDS (up to ~1.6e5 spins), the reported energies (and, in asp_sa_anneal / _trace, the unpermuted
  * configurations) come from one kernel that stages four configurations as the sweep's spin bytes
