@@ -4,38 +4,34 @@
 // experiments/full_hilbert_space.py:212-218.
 //
 // Mapping to the machine
-//   * one workgroup = one GROUP of M replicas (M in {1,2,4,8}); the whole anneal
-//     (all sweeps) is ONE launch, the spins never leave LDS;
-//   * LDS: one byte per (padded) spin position, bit 2m (M <= 4) or bit m (M = 8)
-//     = sign bit of replica m (1 means s = -1), so one ds_read_u8 serves all M
-//     replicas of a neighbour (kBytes); a 32-bit word per position for M = 4 on small clusters, where
-//     the sign of a term is one SDWA instruction (kWide); beyond the capacity of
-//     bytes one BIT per position and one replica per workgroup, flips applied
-//     by a wavefront ballot (kBits), and beyond 1.3e6 spins the same bit words
-//     in HBM (kGlobal);
-//   * frozen sweeps: row sums cached in HBM and re-used while no neighbour of a
-//     block flipped (dirty bytes), blocks whose proposals are all certain
-//     rejections skipped outright (inert bytes);
-//   * few chains on a large cluster: k_sa_sweep_team spreads ONE chain over 2-8
-//     workgroups that exchange 64-bit flip words behind a device-scope barrier;
-//   * a wavefront owns a 64-row block of one colour class: lane = spin.  Same
-//     colour means no couplings inside the block, so the 64 x M proposals of a
-//     block are independent and are decided at once;
-//   * couplings stream from the quad-interleaved sliced ELL: per four terms a
-//     lane issues three 16-byte buffer loads (every wavefront instruction covers
-//     1 KiB of contiguous memory; the quad is a scalar offset), shared by M
-//     replicas, one quad prefetched ahead;
-//   * dE is an f64 sum in fixed row order (bit-exact against the oracle), the
-//     acceptance uses a counter-based Philox4x32-10 word per (spin, sweep,
-//     replica) and a fixed-sequence exp reached through a hardware-exp filter,
-//     accepted flips are XOR-ed into LDS;
-//   * the running energy of each replica is tracked exactly in 2^-S fixed point
-//     (integer adds commute, so the parallel reduction is deterministic); the
-//     best configuration is snapshotted to HBM at sweep granularity;
-//   * DESCENT instantiation: strict-descent sweeps without random numbers (the
-//     greedy solver's relaxation); k_sa_sweep_batch<.., DescentProblem> runs the descents of many
-//     problems in one launch, each workgroup stopping after its first sweep
-//     without a flip.
+//   * one workgroup = one GROUP of M replicas (M in {1,2,4,8}); the whole anneal (all sweeps) is ONE
+//     launch, the spins never leave LDS;
+//   * LDS: one byte per (padded) spin position, bit 2m (M <= 4) or bit m (M = 8) = sign bit of replica m
+//     (1 means s = -1), so one ds_read_u8 serves all M replicas of a neighbour (kBytes); a 32-bit word per
+//     position for M = 4 on small clusters, where the sign of a term is one SDWA instruction (kWide);
+//     beyond the capacity of bytes a nibble (kNibbles) or one BIT per position and one replica per
+//     workgroup, flips applied by a wavefront ballot (kBits), and beyond 1.3e6 spins the same bit words in
+//     HBM (kGlobal);
+//   * a wavefront owns a 64-row block of one colour class: lane = spin.  Same colour means no couplings
+//     inside the block, so the 64 x M proposals of a block are independent and are decided at once;
+//   * couplings stream from the quad-interleaved sliced ELL: per four terms a lane issues three 16-byte
+//     buffer loads (every wavefront instruction covers 1 KiB of contiguous memory; the quad is a scalar
+//     offset), shared by M replicas, one quad prefetched ahead;
+//   * dE is an f64 sum in fixed row order (bit-exact against the oracle), the acceptance uses a
+//     counter-based Philox4x32-10 word per (spin, sweep, replica) and a fixed-sequence exp reached through
+//     a hardware-exp filter, accepted flips are XOR-ed into LDS;
+//   * the running energy of each replica is tracked exactly in 2^-S fixed point (integer adds commute, so
+//     the parallel reduction is deterministic); the best configuration is snapshotted to HBM per sweep;
+//   * frozen sweeps: row sums cached in HBM and re-used while no neighbour of a block flipped (dirty
+//     bytes), blocks whose proposals are all certain rejections skipped outright (inert bytes); or (TAIL)
+//     only the rows listed in a bitmap evaluated, compacted into visits of 64;
+//   * DESCENT: strict-descent sweeps without random numbers (the greedy solver's relaxation);
+//   * few chains on a large cluster: k_sa_sweep_team spreads ONE chain over 2-8 workgroups.
+// Every one-workgroup kernel is sa_sweep_body: ColourSweep::start, then per sweep tail_sweep (visit_rows
+// over listed_row_sums) or colour_sweep (visit_block over block_row_sums), reduce and end_of_sweep, then
+// epilogue.  Said once each: where the LDS regions start (SweepLds, CtlSlot), which Philox word replica m
+// gets (for_replica_words), when a proposal needs a draw (ColourSweep::accept, both visits'), when the
+// field cache or tail mode is entered and left (end_of_sweep_mode).
 // f64-VALU- and vector-memory-bound integer+f64 work: no MFMA.
 #include <algorithm>
 #include <atomic>
@@ -329,34 +325,27 @@ __device__ __forceinline__ void accumulate(const Quad &q, const uint8_t *spins, 
   }
 }
 
-// (`Args` is SweepArgs, or SweepArgs in the constant address space: see k_sa_sweep_batch)
+// What snapshot() reads of its arguments, for another target than the best words: the final words of a
+// segment (the resume epilogue).
+struct FinalWords {
+  uint64_t *best_perm;
+  uint32_t num_blocks;
+};
+// (`Args` is SweepArgs, SweepArgs in the constant address space — see k_sa_sweep_batch — or FinalWords)
 template <int M, int LAYOUT, typename Args>
 __device__ __forceinline__ void snapshot(const uint8_t *spins, const Args &a, uint32_t group,
                                          uint32_t mask) {
-  if constexpr (LAYOUT == kWide) {  // a wavefront per block: one ballot per replica
-    const uint32_t *wide = reinterpret_cast<const uint32_t *>(spins);
+  if constexpr (LAYOUT == kWide || LAYOUT == kNibbles) {  // a wavefront per block: one ballot per replica
     const uint32_t lane = threadIdx.x & 63u;
     for (uint32_t b = threadIdx.x >> 6; b < a.num_blocks; b += blockDim.x >> 6) {
-      const uint32_t w = wide[b * 64u + lane];
+      // the position's word (replica m's sign at bit 8m + 7) or nibble (at bit m)
+      const uint32_t own = LAYOUT == kWide
+                               ? reinterpret_cast<const uint32_t *>(spins)[b * 64u + lane]
+                               : static_cast<uint32_t>(spins[b * 32u + (lane >> 1)]) >> ((lane & 1u) << 2);
 #pragma unroll
       for (int m = 0; m < M; ++m) {
         if (!((mask >> m) & 1u)) continue;  // workgroup-uniform
-        const uint64_t word = __ballot((w >> (8 * m + 7)) & 1u);
-        if (lane == 0) {
-          a.best_perm[(static_cast<uint64_t>(group) * M + m) * a.num_blocks + b] = word;
-        }
-      }
-    }
-    return;
-  }
-  if constexpr (LAYOUT == kNibbles) {  // a wavefront per block: one ballot per replica
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t b = threadIdx.x >> 6; b < a.num_blocks; b += blockDim.x >> 6) {
-      const uint32_t nibble = static_cast<uint32_t>(spins[b * 32u + (lane >> 1)]) >> ((lane & 1u) << 2);
-#pragma unroll
-      for (int m = 0; m < M; ++m) {
-        if (!((mask >> m) & 1u)) continue;  // workgroup-uniform
-        const uint64_t word = __ballot((nibble >> m) & 1u);
+        const uint64_t word = __ballot((own >> (LAYOUT == kWide ? 8 * m + 7 : m)) & 1u);
         if (lane == 0) {
           a.best_perm[(static_cast<uint64_t>(group) * M + m) * a.num_blocks + b] = word;
         }
@@ -434,7 +423,7 @@ struct Resume {
 // read, replica m of the group reads chain_betas once before the sweep loop.  The inert bytes stay
 // valid inside the segment — a certain rejection of replica m was certain at replica m's beta, which
 // does not change — and nothing is carried in from the segment before (which may have run colder):
-// cache_ctl, the dirty and the inert bytes live in LDS and are set up by every launch, cached mode is
+// the control words, the dirty and the inert bytes live in LDS and are set up by every launch, cached mode is
 // entered with every block stale, and an inert byte is only read for a block evaluated since.
 struct ResumeLadder {
   static constexpr bool kEnabled = true;
@@ -487,426 +476,595 @@ struct TailArgs {
 };
 constexpr uint32_t kTailRing = 128;  // rows a wavefront stages: under 64 waiting plus one block's 64
 
+// ---- The dynamic LDS of a one-workgroup colour sweep: the byte offset of every region, for the device
+// body's pointers, and the total, for the host (sweep_lds_bytes).  A region is added in this one place. ----
+//   spins | delta[8] | book[24] | flag (16 B) | meta[num_blocks] | ctl ...
+//   bytes, words, nibbles: ... ctl[4] | dirty[num_blocks] | inert[num_blocks]   (each rounded up to 16 B)
+//   TAIL (bytes, words):   ... ctl[8] | todo[num_blocks] | kTailRing staged rows per wavefront
+//   bits, global:          no meta (block metadata comes from HBM by scalar loads, the field cache is
+//                          not available); ctl[4] and 16 B that nobody uses; global: no spins either
+// spins: 64 (a byte per position), 32 (a nibble), 8 (a bit) or 256 (a word) bytes per block: delta is 64-B aligned.
+// Per replica m: delta[m] = energy change of the running sweep, book[m] = current tracked energy,
+//   book[8 + m] = best, book[16 + m] = accepted flips.  flag: bit m = replica m improved in this sweep.
+// meta[b] = {first ELL slab, width} of block b.  ctl: the CtlSlot words below.
+// dirty[b]: bit m = replica m's cached fields of block b are stale.  inert[b], meaningful while the dirty
+//   byte is clear: at the block's last evaluation every proposal was a certain rejection (beta * dE >= 23
+//   -> expneg = 0, or dE >= 0 in descent mode) and beta has not decreased since: the visit can be skipped.
+// todo[b] (a u64): bit l = row l of block b is evaluated at the next visit of its colour.
+struct SweepLds {
+  uint32_t delta = 0, book = 0, flag = 0, meta = 0, ctl = 0, dirty = 0, inert = 0, todo = 0, ring = 0, total = 0;
+  __host__ __device__ constexpr SweepLds(uint32_t num_blocks, int layout, bool tail, uint32_t waves) {
+    const bool packed = layout == kBits || layout == kGlobal;
+    const uint32_t per_block =
+        layout == kGlobal ? 0u : (layout == kBits ? 8u : (layout == kWide ? 256u : (layout == kNibbles ? 32u : 64u)));
+    delta = num_blocks * per_block;
+    book = delta + 8u * 8u;
+    flag = book + 24u * 8u;
+    meta = flag + 16u;
+    ctl = meta + (packed ? 0u : num_blocks * 8u);
+    if (tail) {
+      todo = ctl + 8u * 4u;
+      ring = todo + num_blocks * 8u;
+      total = ring + waves * kTailRing * 4u;
+    } else if (packed) {
+      total = ctl + 32u;
+    } else {
+      const uint32_t bytes16 = (num_blocks + 15u) & ~15u;
+      dirty = ctl + 4u * 4u;
+      inert = dirty + bytes16;
+      total = inert + bytes16;
+    }
+  }
+};
+static_assert(SweepLds(1, kBytes, false, 0).total == 392 && SweepLds(17, kBytes, false, 0).total == 1576 &&
+                  SweepLds(17, kWide, false, 0).total == 4840 && SweepLds(17, kNibbles, false, 0).total == 1032 &&
+                  SweepLds(17, kBits, false, 0).total == 440 && SweepLds(17, kGlobal, false, 0).total == 304 &&
+                  SweepLds(17, kBytes, true, 16).total == 9856 && SweepLds(17, kWide, true, 8).total == 9024,
+              "the LDS totals of the sweep kernels");
+// The words of ctl.  One mode per kernel: the field cache, or (TAIL) tail sweeps.
+enum CtlSlot : uint32_t {
+  kCtlFlips = 0,        // flips of the workgroup in the running sweep
+  kCtlModeOn = 1,       // 1 while the mode is on: cached fields are in use / sweeps run as tail sweeps
+  kCtlModeEntered = 2,  // 1 when the mode was just entered: every dirty byte / todo bit must be set
+  kCtlTicket = 3,       // the ticket counter that hands a colour's blocks to the wavefronts
+  kCtlTailSweeps = 4,   // TAIL: sweeps run as tail sweeps
+  kCtlTailEntries = 5,  // TAIL: entries into tail mode
+};
+
+// ---- Which Philox word replica m gets (RNG contract: DESIGN.md section 4.3) ----
+struct ChainKey {
+  uint32_t r0, key0, key1;  // the group's first replica, the seed's halves
+};
+// use(m, word) for m = 0 .. M - 1: replica r = r0 + m takes word r & 3 of the call with the counter
+// (spin, sweep, r >> 2, 0); sweep = 0xFFFFFFFF is the start configuration.
+// ALIGNED (M = 4 only): the host promises r0 % 4 == 0 (aligned_replicas()), so the group is one whole
+// call and replica m takes word m of it, known at compile time.  Without the promise the first replica's
+// place in its call is a run-time value: a group that straddles two calls makes the second when it
+// reaches it, and every word is selected with pick_word (three v_cndmask_b32 on scalar masks per
+// replica).  Same counters, same words.
+template <int M, bool ALIGNED, typename Use>
+__device__ __forceinline__ void for_replica_words(uint32_t spin, uint32_t sweep, const ChainKey &k, Use &&use) {
+  Philox4 rnd{};
+  if constexpr (ALIGNED) {
+    rnd = philox4x32_10(spin, sweep, k.r0 >> 2, 0u, k.key0, k.key1);
+#pragma unroll
+    for (int m = 0; m < M; ++m) use(m, rnd.w[m]);
+  } else {
+    uint32_t have = 0xFFFFFFFFu;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const uint32_t r = k.r0 + m;
+      if (m == 0 || (r >> 2) != have) {
+        have = r >> 2;
+        rnd = philox4x32_10(spin, sweep, have, 0u, k.key0, k.key1);
+      }
+      use(m, pick_word(rnd, r & 3u));
+    }
+  }
+}
+
+// ---- The row sums of a visit: two k-loops, side by side ----
+// The block visit (lane = row of ONE block): prefetch distance one — the next quad's three 16-byte
+// loads are in flight while the current quad is gathered from LDS and accumulated, in the oracle's
+// order k = 0, 1, 2, ...  Loop control is scalar and the body has no conditional loads (hipcc would
+// otherwise drain the queue with vmcnt(0) at the loop header); sched_barrier keeps each load group
+// ahead of the accumulate it overlaps.  For an even quad count the last load reads one quad past the
+// block — the next block's first slabs or the tail padding the plan appends — and is never consumed.
+template <int M, int LAYOUT>
+__device__ __forceinline__ void block_row_sums(const BlockStream &stream, uint32_t quads, const uint8_t *spins,
+                                               double (&acc)[M], double (&mult)[4]) {
+#pragma unroll
+  for (int m = 0; m < M; ++m) acc[m] = 0.0;
+  Quad qa, qb;
+  load_quad(qa, stream, 0);
+  uint32_t i = 0;
+  for (; i + 2 <= quads; i += 2) {
+    load_quad(qb, stream, i + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    accumulate<M, LAYOUT>(qa, spins, acc, mult);
+    __builtin_amdgcn_sched_barrier(0);
+    load_quad(qa, stream, i + 2);
+    __builtin_amdgcn_sched_barrier(0);
+    accumulate<M, LAYOUT>(qb, spins, acc, mult);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (i < quads) accumulate<M, LAYOUT>(qa, spins, acc, mult);
+}
+// The tail visit (every lane its OWN row of `row_quads` quads, at col_at / val_at bytes from the start of
+// the arrays): a lane streams the quads of its row and never the next block's — from its width on it
+// reads the first 48 bytes of the arrays instead (one cache line for all such lanes) and accumulates
+// nothing.  Every load is issued unconditionally — a load under a lane mask makes hipcc drain the queue
+// in front of each accumulate —, so the quad is part of the lane's offset and the k-loop keeps the block
+// visit's prefetch distance of one.  The sums are accumulate()'s in ascending k: the block visit's f64
+// values bit for bit.
+template <int M, int LAYOUT>
+__device__ __forceinline__ void listed_row_sums(BufferRsrc col_rsrc, BufferRsrc val_rsrc, uint32_t row_quads,
+                                                uint32_t col_at, uint32_t val_at, const uint8_t *spins,
+                                                double (&acc)[M], double (&mult)[4]) {
+  auto load_row_quad = [&](Quad &q, uint32_t quad) {
+    const bool mine = quad < row_quads;
+    const uint32_t c_at = mine ? col_at + quad * 1024u : 0u;
+    const uint32_t v_at = mine ? val_at + quad * 2048u : 0u;
+    q.c = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(col_rsrc, c_at, 0, 0));
+    q.v01 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(val_rsrc, v_at, 0, 0));
+    q.v23 = __builtin_bit_cast(double2,
+                               __builtin_amdgcn_raw_buffer_load_b128(val_rsrc, v_at + (mine ? 1024u : 16u), 0, 0));
+  };
+#pragma unroll
+  for (int m = 0; m < M; ++m) acc[m] = 0.0;
+  Quad qa, qb;
+  load_row_quad(qa, 0u);
+  for (uint32_t q = 0; __ballot(q < row_quads) != 0ull; q += 2u) {
+    load_row_quad(qb, q + 1u);
+    __builtin_amdgcn_sched_barrier(0);
+    if (q < row_quads) accumulate<M, LAYOUT>(qa, spins, acc, mult);
+    __builtin_amdgcn_sched_barrier(0);
+    load_row_quad(qa, q + 2u);
+    __builtin_amdgcn_sched_barrier(0);
+    if (q + 1u < row_quads) accumulate<M, LAYOUT>(qb, spins, acc, mult);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ---- The lane's own spin at position p of block b (block visit: b is wave-uniform), per layout: read in
+// front of the accept phase (ColourSweep::accept), flipped behind it ----
+template <int LAYOUT>
+__device__ __forceinline__ uint32_t load_own(const uint8_t *spins, uint32_t p, uint32_t b) {
+  if constexpr (LAYOUT == kBits || LAYOUT == kGlobal) {
+    return static_cast<uint32_t>(
+        (load_word<LAYOUT == kGlobal>(reinterpret_cast<const uint64_t *>(spins) + b) >> (p & 63u)) & 1ull);
+  } else if constexpr (LAYOUT == kWide) {
+    return reinterpret_cast<const uint32_t *>(spins)[p];
+  } else if constexpr (LAYOUT == kNibbles) {
+    return (static_cast<uint32_t>(spins[p >> 1]) >> ((p & 1u) << 2)) & 15u;
+  } else {
+    return spins[p];
+  }
+}
+
+// What a lane gathers over a sweep.  q[m]: the fixed-point energy changes of its accepted flips, modulo
+// 2^64 (lean bookkeeping: plus 0x4338000000000000 per visit); n[m]: its accepted flips (< 2^32 blocks per
+// sweep); visits: the lean bookkeepings of this wavefront in this sweep (wave-uniform).
+template <int M>
+struct SweepSums {
+  unsigned long long q[M];
+  uint32_t n[M];
+  uint32_t visits;
+};
+
+// The replicas in `flip` change sign.  Every lane of the wavefront calls it.
+template <int M, int LAYOUT>
+__device__ __forceinline__ void store_flip(uint8_t *spins, uint32_t p, uint32_t b, uint32_t own, uint32_t flip) {
+  if constexpr (LAYOUT == kBits || LAYOUT == kGlobal) {
+    // the block's 64 proposals decided: one XOR of the ballot into the block's word
+    const uint64_t flips = __ballot(flip != 0);
+    if ((p & 63u) == 0 && flips != 0) {
+      uint64_t *word = reinterpret_cast<uint64_t *>(spins) + b;
+      store_word<LAYOUT == kGlobal>(word, load_word<LAYOUT == kGlobal>(word) ^ flips);
+    }
+  } else if constexpr (LAYOUT == kWide) {
+    if (flip) reinterpret_cast<uint32_t *>(spins)[p] = own ^ spread_mask(flip);
+  } else if constexpr (LAYOUT == kNibbles) {
+    // the neighbouring lane owns the other nibble of the byte and may flip in the same
+    // instruction: an LDS atomic on the word (eight positions) instead of a byte store
+    if (flip) atomicXor(reinterpret_cast<uint32_t *>(spins) + (p >> 3), flip << ((p & 7u) << 2));
+  } else {
+    // positions of a visit are distinct: plain stores
+    if (flip) spins[p] = static_cast<uint8_t>(own ^ encode_replicas<M, LAYOUT>(flip));
+  }
+}
+
+// ---- When the field cache or tail mode is entered and left (thread 0, end of a sweep) ----
+// Either mode pays while a sweep's flips touch a fraction of the rows only: enter after a sweep with
+// fewer than `enter` flips of the workgroup, leave above twice that — the field cache at 2 * enter
+// itself, tail mode not — or when the caller says so (leave_now: tail mode in front of a sweep at a
+// lower beta).  Resets the flip count; TAIL counts the sweeps run in the mode and the entries.
+template <bool TAIL>
+__device__ __forceinline__ void end_of_sweep_mode(uint32_t *ctl, uint32_t enter, bool leave_now) {
+  const uint32_t flips = ctl[kCtlFlips];
+  ctl[kCtlFlips] = 0;
+  const bool was = ctl[kCtlModeOn] != 0;
+  bool now = was ? (TAIL ? flips <= 2ull * enter : flips < 2u * enter) : flips < enter;
+  if (leave_now) now = false;
+  ctl[kCtlModeOn] = now ? 1u : 0u;
+  ctl[kCtlModeEntered] = (now && !was) ? 1u : 0u;
+  if constexpr (TAIL) {
+    if (was) ctl[kCtlTailSweeps] += 1u;
+    if (now && !was) ctl[kCtlTailEntries] += 1u;
+  }
+}
+// Every block's entry of a per-block LDS array (dirty, inert, todo), by the whole workgroup.
+template <typename T>
+__device__ __forceinline__ void fill_blocks(T *per_block, uint32_t num_blocks, T value) {
+  for (uint32_t b = threadIdx.x; b < num_blocks; b += blockDim.x) per_block[b] = value;
+}
+
+// The whole anneal of one group of M replicas by one workgroup, in the phases sa_sweep_body() below runs in
+// order; `group` = index of the group inside its problem (k_sa_sweep: the workgroup id; k_sa_sweep_batch:
+// looked up in a table).
 // DESCENT = true: strict-descent sweeps (accept iff dE < 0, no random numbers, no beta: a.betas is
 // never read), used by the greedy solver's relaxation; the final configuration is snapshotted
 // after every sweep.
-// The whole anneal of one group of M replicas by one workgroup; `group` = index of the group
-// inside its problem (k_sa_sweep: the workgroup id; k_sa_sweep_batch: looked up in a table).
-// ALIGNED (M = 4 only): the host promises a.replica_first % 4 == 0 (aligned_replicas()), so every
-// group is one whole Philox call, call r0 >> 2, and replica m takes word m of it, known at compile
-// time.  Without the promise the first replica's place in its call is a run-time value, the visit
-// keeps a second call path for a group that straddles two calls and selects every replica's word
-// with pick_word (three v_cndmask_b32 on scalar masks per replica).  Same counters, same words:
-// the chains are the generic body's.
+// ALIGNED (M = 4 only): see for_replica_words.
 // TAIL (the closed call's M = 4 kernels in bytes and words): once a sweep flips fewer spins than
 // tail.enter_flips the workgroup keeps one `todo` bit per position in LDS and a sweep evaluates only the
 // listed rows, compacted into visits of 64 rows with lane = row.  These
-// instantiations have no field cache and no inert bytes.  Every other one keeps the code it had.
-template <int M, bool DESCENT, int LAYOUT, typename Args, typename Stop = NoEarlyStop,
-          typename Res = NoResume, bool ALIGNED = false, bool TAIL = false>
-__device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t group,
-                                              const Stop stop = Stop{}, const Res res = Res{},
-                                              const TailArgs tail = TailArgs{}) {
+// instantiations have no field cache and no inert bytes.
+// (`Args` is SweepArgs, or SweepArgs in the constant address space: see k_sa_sweep_batch)
+template <int M, bool DESCENT, int LAYOUT, typename Args, typename Stop, typename Res, bool ALIGNED, bool TAIL>
+struct ColourSweep {
   static_assert(!TAIL || (M == 4 && !DESCENT && !Res::kEnabled && (LAYOUT == kBytes || LAYOUT == kWide)),
                 "tail sweeps: the closed call of four chains in bytes or words");
   static_assert(DESCENT || !Stop::kEnabled, "only a descent can stop early");
   static_assert(!ALIGNED || (!DESCENT && M == 4), "an aligned group is one whole Philox call");
   static_assert(!DESCENT || !Res::kEnabled, "a descent is never resumed");
-  constexpr bool GLOBAL = LAYOUT == kGlobal;
-  constexpr bool PACKED = LAYOUT == kBits || GLOBAL;  // one bit per position
-  constexpr bool WIDE = LAYOUT == kWide;
-  constexpr bool NIBBLES = LAYOUT == kNibbles;
-  // The lean energy bookkeeping of a visit (see the accept loop) for up to four replicas.  Eight
-  // replicas and the ladder segment of four in words keep the per-flip form: they have no vector
-  // register to spare in the accept phase, and the lean form's two more sent them to scratch
-  // (DESIGN.md section 6).
-  constexpr bool kLeanBook = M <= 4 && !(Res::kLadder && WIDE);
+  static constexpr bool GLOBAL = LAYOUT == kGlobal;
+  static constexpr bool PACKED = LAYOUT == kBits || GLOBAL;  // one bit per position
+  static constexpr bool WIDE = LAYOUT == kWide;
+  static constexpr bool NIBBLES = LAYOUT == kNibbles;
+  static constexpr bool kLeanBook = M <= 4 && !(Res::kLadder && WIDE);  // see accept()
   static_assert(!PACKED || M == 1, "the bit-packed layouts hold one replica");
   static_assert(!NIBBLES || (M <= 4 && !DESCENT), "the nibble layout holds up to four replicas");
   static_assert(!WIDE || (M <= 4 && !DESCENT), "the wide layout holds up to four replicas");
-  extern __shared__ __align__(16) uint8_t lds[];
-  // kGlobal: this workgroup's bit words live in HBM, the LDS holds the bookkeeping only
-  uint8_t *spins = GLOBAL ? reinterpret_cast<uint8_t *>(a.spin_words +
-                                                       static_cast<uint64_t>(group) * a.num_blocks)
-                          : lds;
-  // bytes of the spin area per block: 64 (a byte per position), 32 (a nibble), 8 (a bit) or 256 (a word)
-  const uint32_t P = GLOBAL ? 0u : a.num_blocks * (PACKED ? 8u : (WIDE ? 256u : (NIBBLES ? 32u : 64u)));
-  // P is a multiple of 64.  Per replica m: delta[m] = energy change of the running
-  // sweep, book[m] = current tracked energy, book[8+m] = best, book[16+m] = accepted flips
-  long long *delta = reinterpret_cast<long long *>(lds + P);
-  long long *book = delta + 8;
-  uint32_t *improved_flag = reinterpret_cast<uint32_t *>(book + 24);
-  uint2 *meta = reinterpret_cast<uint2 *>(book + 26);  // per block {first ELL slab, width}
-  // cache control: [0] flips of the running sweep, [1] 1 while the field cache is in use,
-  // [2] 1 when the cache was just switched on (dirty bytes must be set),
-  // [3] the ticket counter that hands a colour's blocks to the wavefronts;
-  // then one dirty byte per block (bit m: replica m's cached fields are stale)
-  // (the bit-packed layout keeps no per-block arrays in LDS besides the spin words: block
-  // metadata is read from HBM with scalar loads, the field cache is not available)
-  uint32_t *cache_ctl = reinterpret_cast<uint32_t *>(meta + (PACKED ? 0u : a.num_blocks));
-  uint8_t *dirty = reinterpret_cast<uint8_t *>(cache_ctl + 4);
-  // one "inert" byte per block, meaningful while the dirty byte is clear: at the block's last
-  // evaluation every proposal was a certain rejection (beta * dE >= 23 -> expneg = 0, or
-  // dE >= 0 in descent mode) and beta has not decreased since, so the visit can be skipped
-  uint8_t *inert = dirty + ((a.num_blocks + 15u) & ~15u);
-  const bool cache_available = !TAIL && !PACKED && a.field_cache != nullptr;
-  // TAIL: no dirty and inert bytes; behind cache_ctl[4] come [4] the sweeps run as tail sweeps, [5] the
-  // entries into tail mode (cache_ctl[0] counts the flips as above, [1] is 1 while tail sweeps run,
-  // [2] 1 when they were just entered: every todo bit must be set), then one todo word per block (bit l:
-  // row l is evaluated at the next visit of its colour) and kTailRing staged rows per wavefront
-  [[maybe_unused]] uint64_t *todo = reinterpret_cast<uint64_t *>(cache_ctl + 8);
-  [[maybe_unused]] uint32_t *todo32 = reinterpret_cast<uint32_t *>(todo);
 
-  // accumulate addresses the spin bytes absolutely: the dynamic LDS block must be the first
-  // (this kernel declares no static LDS)
-  if (reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t *)lds) != 0) {
-    __builtin_trap();
+  const Args &a;
+  const uint32_t group;
+  const Stop stop;  // (what the launch takes beside SweepArgs: see NoEarlyStop, NoResume, TailArgs)
+  const Res res;
+  const TailArgs tail;
+  const uint32_t tid = threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  const ChainKey key;
+  // ResumeLadder: the replicas' own betas (workgroup-uniform: scalar registers)
+  const LadderBetas<M, Res::kLadder> ladder;
+  const bool cache_available;
+  // the LDS regions (SweepLds); kGlobal: this workgroup's bit words live in HBM
+  uint8_t *spins, *dirty, *inert;
+  long long *delta, *book;
+  uint32_t *improved_flag, *ctl, *rings;  // TAIL: wavefront w's ring at rings + w * kTailRing
+  uint2 *meta;
+  uint64_t *todo;
+  double mult[4] = {1.0, 1.0, 1.0, 1.0};  // kWide's multipliers (low words stay 0)
+  uint32_t ticket_base = 0;  // ctl[kCtlTicket] at the start of the running colour (workgroup-uniform)
+  // StopWhenStill: sweeps performed, and the chain's accepted flips before the running sweep
+  uint32_t sweeps_done;
+  long long flips_before = 0;
+
+  __device__ __forceinline__ ColourSweep(const Args &a_, uint32_t group_, const Stop &stop_, const Res &res_,
+                                         const TailArgs &tail_)
+      : a(a_), group(group_), stop(stop_), res(res_), tail(tail_),
+        key{a_.replica_first + group_ * M, static_cast<uint32_t>(a_.seed), static_cast<uint32_t>(a_.seed >> 32)},
+        ladder(res_, group_), cache_available(!TAIL && !PACKED && a_.field_cache != nullptr),
+        sweeps_done(a_.num_sweeps) {
+    extern __shared__ __align__(16) uint8_t lds[];
+    // accumulate addresses the spin bytes absolutely: the dynamic LDS block must be the first
+    // (this kernel declares no static LDS)
+    if (reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t *)lds) != 0) __builtin_trap();
+    const SweepLds at(a.num_blocks, LAYOUT, TAIL, waves);
+    spins = GLOBAL ? reinterpret_cast<uint8_t *>(a.spin_words + static_cast<uint64_t>(group) * a.num_blocks) : lds;
+    delta = reinterpret_cast<long long *>(lds + at.delta);
+    book = reinterpret_cast<long long *>(lds + at.book);
+    improved_flag = reinterpret_cast<uint32_t *>(lds + at.flag);
+    meta = reinterpret_cast<uint2 *>(lds + at.meta);
+    ctl = reinterpret_cast<uint32_t *>(lds + at.ctl);
+    dirty = lds + at.dirty;
+    inert = lds + at.inert;
+    todo = reinterpret_cast<uint64_t *>(lds + at.todo);
+    rings = reinterpret_cast<uint32_t *>(lds + at.ring);
   }
-  const uint32_t tid = threadIdx.x;
-  const uint32_t lane = tid & 63u;
-  const uint32_t wave = tid >> 6;
-  const uint32_t waves = blockDim.x >> 6;
-  const uint32_t r0 = a.replica_first + group * M;
-  const uint32_t key0 = static_cast<uint32_t>(a.seed);
-  const uint32_t key1 = static_cast<uint32_t>(a.seed >> 32);
 
-  // ---- initial configuration ---- (a wavefront initialises whole 64-position blocks)
-  for (uint32_t b0 = tid >> 6; b0 < a.num_blocks; b0 += blockDim.x >> 6) {
-    const uint32_t p = b0 * 64u + (tid & 63u);
-    const uint32_t spin = a.spin_of_pos[p];
-    uint32_t byte = 0;
-    if constexpr (Res::kEnabled) {
-      // every chain's own words (a padding lane's bit is whatever the words hold: never read back)
-      if (spin != kDummySpin) {
+  // ---- Start: the configuration (a wavefront initialises whole 64-position blocks), the books, the
+  // first snapshot ----
+  __device__ __forceinline__ void start() {
+    for (uint32_t b0 = wave; b0 < a.num_blocks; b0 += waves) {
+      const uint32_t p = b0 * 64u + lane;
+      const uint32_t spin = a.spin_of_pos[p];
+      uint32_t byte = 0;  // replica m's sign bit at replica_bit(m)
+      if constexpr (Res::kEnabled) {
+        // every chain's own words (a padding lane's bit is whatever the words hold: never read back)
+        if (spin != kDummySpin) {
 #pragma unroll
-        for (int m = 0; m < M; ++m) {
-          const uint64_t word = res.cur_perm[(static_cast<uint64_t>(group) * M + m) * a.num_blocks + b0];
-          byte |= static_cast<uint32_t>((word >> (tid & 63u)) & 1ull) << replica_bit<M, LAYOUT>(m);
-        }
-      }
-    } else if (spin != kDummySpin) {
-      if (a.x0_perm != nullptr) {
-        byte = ((a.x0_perm[p >> 6] >> (p & 63u)) & 1ull) ? encode_replicas<M, LAYOUT>((1u << M) - 1u)
-                                                         : 0u;  // every replica
-      } else {
-        Philox4 rnd{};
-        uint32_t have = 0xFFFFFFFFu;
-#pragma unroll
-        for (int m = 0; m < M; ++m) {
-          uint32_t word;
-          if constexpr (ALIGNED) {
-            if (m == 0) rnd = philox4x32_10(spin, 0xFFFFFFFFu, r0 >> 2, 0u, key0, key1);
-            word = rnd.w[m];
-          } else {
-            const uint32_t r = r0 + m;
-            if (m == 0 || (r >> 2) != have) {
-              have = r >> 2;
-              rnd = philox4x32_10(spin, 0xFFFFFFFFu, have, 0u, key0, key1);
-            }
-            word = pick_word(rnd, r & 3u);
+          for (int m = 0; m < M; ++m) {
+            const uint64_t word = res.cur_perm[(static_cast<uint64_t>(group) * M + m) * a.num_blocks + b0];
+            byte |= static_cast<uint32_t>((word >> lane) & 1ull) << replica_bit<M, LAYOUT>(m);
           }
-          const uint32_t up = word & 1u;  // 1 -> s = +1 -> sign bit 0
-          byte |= (up ^ 1u) << replica_bit<M, LAYOUT>(m);
+        }
+      } else if (spin != kDummySpin) {
+        if (a.x0_perm != nullptr) {
+          byte = ((a.x0_perm[p >> 6] >> (p & 63u)) & 1ull) ? encode_replicas<M, LAYOUT>((1u << M) - 1u)
+                                                           : 0u;  // every replica
+        } else {
+          for_replica_words<M, ALIGNED>(spin, 0xFFFFFFFFu, key, [&](int m, uint32_t word) {
+            const uint32_t up = word & 1u;  // 1 -> s = +1 -> sign bit 0
+            byte |= (up ^ 1u) << replica_bit<M, LAYOUT>(m);
+          });
         }
       }
+      if constexpr (PACKED) {
+        const uint64_t word = __ballot(byte & 1u);
+        if (lane == 0) store_word<GLOBAL>(reinterpret_cast<uint64_t *>(spins) + b0, word);
+      } else if constexpr (WIDE) {
+        reinterpret_cast<uint32_t *>(spins)[p] = spread_mask(byte);
+      } else if constexpr (NIBBLES) {
+        const uint32_t upper = __shfl_xor(byte, 1);  // the odd lane's nibble, for the even lane
+        if ((tid & 1u) == 0) spins[p >> 1] = static_cast<uint8_t>(byte | (upper << 4));
+      } else {
+        spins[p] = static_cast<uint8_t>(byte);
+      }
     }
-    if constexpr (PACKED) {
-      const uint64_t word = __ballot(byte & 1u);
-      if ((tid & 63u) == 0) store_word<GLOBAL>(reinterpret_cast<uint64_t *>(spins) + b0, word);
-    } else if constexpr (WIDE) {
-      reinterpret_cast<uint32_t *>(spins)[p] = spread_mask(byte);
-    } else if constexpr (NIBBLES) {
-      const uint32_t upper = __shfl_xor(byte, 1);  // the odd lane's nibble, for the even lane
-      if ((tid & 1u) == 0) spins[p >> 1] = static_cast<uint8_t>(byte | (upper << 4));
-    } else {
-      spins[p] = static_cast<uint8_t>(byte);
+    if constexpr (!PACKED) {
+      for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) {
+        meta[b] = make_uint2(static_cast<uint32_t>(a.ell_off[b]), a.block_width[b]);
+      }
     }
-  }
-  if constexpr (!PACKED) {
-    for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) {
-      meta[b] = make_uint2(static_cast<uint32_t>(a.ell_off[b]), a.block_width[b]);
-    }
-  }
-  if constexpr (Res::kEnabled) {
-    // delta[8] | book[24]: every entry is written once, by one lane — 0, or for book[] of a live
-    // chain the carried value (current tracked energy, best, accepted flips)
+    // delta[8] | book[24]: every entry is written once, by one lane — 0, or (a segment) for book[] of a
+    // live chain the carried value (current tracked energy, best, accepted flips)
     if (tid < 32) {
-      const uint32_t which = tid >> 3, m = tid & 7u;
       long long v = 0;
-      if (which >= 1u && m < static_cast<uint32_t>(M)) {
-        const uint64_t chain = static_cast<uint64_t>(group) * M + m;
-        v = which == 1u ? res.e_cur[chain]
-                        : (which == 2u ? a.tracked[chain] : static_cast<long long>(a.accepted[chain]));
+      if constexpr (Res::kEnabled) {
+        const uint32_t which = tid >> 3, m = tid & 7u;
+        if (which >= 1u && m < static_cast<uint32_t>(M)) {
+          const uint64_t chain = static_cast<uint64_t>(group) * M + m;
+          v = which == 1u ? res.e_cur[chain]
+                          : (which == 2u ? a.tracked[chain] : static_cast<long long>(a.accepted[chain]));
+        }
       }
       delta[tid] = v;
     }
-  } else {
-    if (tid < 32) delta[tid] = 0;  // delta[8] + book[24]
-  }
-  if (tid == 0) {
-    *improved_flag = 0;
-    cache_ctl[0] = 0;
-    cache_ctl[1] = 0;
-    cache_ctl[2] = 0;
-    cache_ctl[3] = 0;  // block tickets drawn so far (colour loop)
-    if constexpr (TAIL) cache_ctl[4] = cache_ctl[5] = 0;
-  }
-  if constexpr (Res::kEnabled) {
-    // (the best configuration so far is in a.best_perm already and stays unless the segment
-    // improves on it: no initial snapshot)
+    if (tid == 0) {
+      *improved_flag = 0;
+      ctl[kCtlFlips] = ctl[kCtlModeOn] = ctl[kCtlModeEntered] = ctl[kCtlTicket] = 0;
+      if constexpr (TAIL) ctl[kCtlTailSweeps] = ctl[kCtlTailEntries] = 0;
+    }
     __syncthreads();
-  } else {
-    __syncthreads();
-    snapshot<M, LAYOUT>(spins, a, group, (1u << M) - 1u);
-    __syncthreads();
+    if constexpr (!Res::kEnabled) {
+      // (a segment's best configuration so far is in a.best_perm already and stays unless the segment
+      // improves on it: no initial snapshot)
+      snapshot<M, LAYOUT>(spins, a, group, (1u << M) - 1u);
+      __syncthreads();
+    }
+    if (a.trace != nullptr && tid < M) {
+      long long first = 0;
+      if constexpr (Res::kEnabled) first = book[tid];  // (not reset: relative to the chain's very first state)
+      a.trace[(static_cast<uint64_t>(group) * M + tid) * (a.num_sweeps + 1ull)] = first;
+    }
   }
 
-  if (a.trace != nullptr && tid < M) {
-    long long start = 0;
-    if constexpr (Res::kEnabled) start = book[tid];  // (not reset: relative to the chain's very first state)
-    a.trace[(static_cast<uint64_t>(group) * M + tid) * (a.num_sweeps + 1ull)] = start;
-  }
-  double mult[4] = {1.0, 1.0, 1.0, 1.0};  // kWide's multipliers (low words stay 0)
-  // ResumeLadder: the replicas' own betas (workgroup-uniform: scalar registers)
-  const LadderBetas<M, Res::kLadder> ladder(res, group);
-  // StopWhenStill: sweeps performed, and the chain's accepted flips before the running sweep
-  [[maybe_unused]] uint32_t sweeps_done = a.num_sweeps;
-  [[maybe_unused]] long long flips_before = 0;
-  uint32_t ticket_base = 0;  // cache_ctl[3] at the start of the running colour (workgroup-uniform)
-  for (uint32_t t = 0; t < a.num_sweeps; ++t) {
-    uint32_t t_draw = t;  // the sweep index of the random words: global over the segments of a handle
-    if constexpr (Res::kEnabled) t_draw += res.t0;
-    double beta;
-    if constexpr (DESCENT || Res::kLadder) {
-      beta = 0.0;  // unused by the descent rule: a certain rejection there is dE >= 0 at any beta
-    } else {
-      beta = a.betas[t];
+  // ---- The accept phase of a visit, for the lane's position: propose, decide, book.  Returns the
+  // replicas that flip; open: some proposal of the lane was not a certain rejection.  The positions of a
+  // visit are of one colour, so their proposals are independent and are decided at once. ----
+  __device__ __forceinline__ uint32_t accept(const double (&acc)[M], double h, uint32_t own, uint32_t spin,
+                                             uint32_t t_draw, double beta, SweepSums<M> &sums, bool &open) {
+    const bool valid = spin != kDummySpin;
+    // Propose: de[m] = replica m's energy change of flipping the lane's spin.
+    open = false;
+    bool need = false;  // some proposal of this lane needs a random number
+    double de[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const double g = __dadd_rn(acc[m], h);
+      const bool negative = (own >> (WIDE ? 8 * m + 7 : replica_bit<M, LAYOUT>(m))) & 1u;  // s = -1
+      de[m] = __dmul_rn(negative ? 2.0 : -2.0, g);
+      if constexpr (DESCENT) {
+        open = open || (valid && de[m] < 0.0);
+      } else {
+        const bool maybe = valid && !(__dmul_rn(ladder.of(m, beta), de[m]) >= 23.0);  // not a certain rejection
+        open = open || maybe;
+        need = need || (maybe && !(de[m] <= 0.0));
+      }
     }
+    // Decide.  Random numbers only when some proposal of the wavefront is undecided without one
+    // (dE <= 0 is accepted, beta * dE >= 23 rejected, whatever the draw; a descent accepts dE < 0 and
+    // nothing else): a wave-uniform branch around the 10 Philox rounds and the exp filter.
+    // Counter-based RNG: skipping a draw changes nothing downstream.
+    // The accepted proposals: bit m of accept_mask, or (kLeanBook) all ones in took[m].
+    uint32_t accept_mask = 0;
+    [[maybe_unused]] uint32_t took[M];
+    auto decided = [&](int m, bool accepted) {
+      if constexpr (kLeanBook) {
+        took[m] = accepted ? 0xFFFFFFFFu : 0u;
+      } else {
+        accept_mask |= (accepted ? 1u : 0u) << m;
+      }
+    };
+    if (!DESCENT && __ballot(need) != 0ull) {
+      for_replica_words<M, ALIGNED>(spin, t_draw, key, [&](int m, uint32_t word) {
+        decided(m, valid && (de[m] <= 0.0 || metropolis_accept_word(word, __dmul_rn(ladder.of(m, beta), de[m]))));
+      });
+    } else {
+#pragma unroll
+      for (int m = 0; m < M; ++m) decided(m, valid && (DESCENT ? de[m] < 0.0 : de[m] <= 0.0));
+    }
+    // Book.  rint(dE * 2^S) as int64: |dE * 2^S| < 2^51 by the plan's choice of S, so adding 1.5 * 2^52
+    // leaves the rounded integer in the mantissa (ties to even, = rint): the sum's bit pattern is
+    // 0x4338000000000000 + rint(dE * 2^S).
+    uint32_t flip = 0;
+    if constexpr (kLeanBook) {
+      // Lean (up to four replicas): no branch and no selection.  EVERY replica adds the bit pattern of
+      // dE * scale_m + 1.5 * 2^52, where scale_m is 2^S for an accepted proposal and 0 otherwise (2^S is a
+      // power of two: its low word is 0 and the high word is masked) — dE is finite, so a proposal that
+      // is not accepted adds the bare constant.  The `visits` constants come off once per sweep, in front
+      // of the reduction, modulo 2^64.  One fma is the multiply followed by the add: dE * 2^S is exact —
+      // the fma then rounds the very sum the add rounds — or it underflows, to something below 2^-1022
+      // either way, and both sums round to 1.5 * 2^52.  v_fma_f64 reads one scalar operand, so the
+      // constant is put in vector registers here, after the k-loop: held for the whole launch it costs
+      // every instantiation two registers more.
+      double round_bias = 0x1.8p52;
+      asm volatile("" : "+v"(round_bias));
+      const uint32_t scale_hi = static_cast<uint32_t>(__double2hiint(a.scale));
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        flip |= took[m] & (1u << m);
+        const double scale_m = __hiloint2double(static_cast<int>(scale_hi & took[m]), 0);
+        sums.q[m] += static_cast<unsigned long long>(__double_as_longlong(__builtin_fma(de[m], scale_m, round_bias)));
+        sums.n[m] -= took[m];  // + 1 when accepted
+      }
+      sums.visits += 1;
+    } else {
+      // Per flip: eight replicas and the ladder segment of four in words have no vector register to
+      // spare in the accept phase, and the lean form's two more sent them to scratch.
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        if ((accept_mask >> m) & 1u) {
+          flip |= 1u << m;
+          sums.q[m] += static_cast<unsigned long long>(
+              __double_as_longlong(__dadd_rn(__dmul_rn(de[m], a.scale), 0x1.8p52)) - 0x4338000000000000ll);
+          sums.n[m] += 1;
+        }
+      }
+    }
+    return flip;
+  }
+
+  // ---- A tail sweep (workgroup-uniform: false when tail mode is off): only the rows listed in `todo` ----
+  // Per colour a wavefront takes every waves-th block of the colour, 64 of them at a time (lane i
+  // reads and clears the word of its i-th), and stages the listed rows of the non-empty ones,
+  // block by block, in its ring at their mbcnt ranks.  As soon as 64 rows wait they are one visit
+  // with lane = row (visit_rows).  Rows of a colour are independent, the random words are keyed by
+  // (spin, sweep, replica) and the energy sums are integers: which rows share a visit changes no result.
+  __device__ __forceinline__ bool tail_sweep(uint32_t t_draw, double beta, SweepSums<M> &sums) {
+    if (__builtin_amdgcn_readfirstlane(ctl[kCtlModeOn]) == 0) return false;
+    const uint32_t wave_u = __builtin_amdgcn_readfirstlane(wave);
+    uint32_t *ring = rings + wave_u * kTailRing;
+    const BufferRsrc col_rsrc = block_rsrc(a.ell_col), val_rsrc = block_rsrc(a.ell_val);
+    for (uint32_t c = 0; c < a.num_colors; ++c) {
+      const uint32_t b_begin = a.color_block_start[c];
+      const uint32_t nb = a.color_block_start[c + 1] - b_begin;
+      uint32_t fill = 0, drained = 0;  // rows staged and rows visited so far (wave-uniform)
+      uint32_t base = 0, next_base = wave_u;
+      uint64_t w = 0, nonempty = 0;  // the lane's word of the running 64 blocks, and which lanes' are left
+      for (;;) {
+        while (fill - drained < 64u) {
+          if (nonempty == 0ull) {
+            if (next_base >= nb) break;
+            base = next_base;
+            next_base += waves * 64u;
+            const uint32_t i = base + lane * waves;
+            w = 0;
+            if (i < nb) {
+              // nobody marks a block during its own colour step but the wavefront that took it
+              w = todo[b_begin + i];
+              if (w != 0ull) todo[b_begin + i] = 0ull;
+            }
+            nonempty = __ballot(w != 0ull);
+            continue;
+          }
+          const uint32_t src = static_cast<uint32_t>(__builtin_ctzll(nonempty));
+          nonempty &= nonempty - 1ull;
+          const uint32_t w_lo = __builtin_amdgcn_readlane(static_cast<uint32_t>(w), src);
+          const uint32_t w_hi = __builtin_amdgcn_readlane(static_cast<uint32_t>(w >> 32), src);
+          const uint32_t rank = __builtin_amdgcn_mbcnt_hi(w_hi, __builtin_amdgcn_mbcnt_lo(w_lo, 0u));
+          const uint32_t mine = lane < 32u ? w_lo >> lane : w_hi >> (lane - 32u);
+          if (mine & 1u) ring[(fill + rank) & (kTailRing - 1u)] = (b_begin + base + src * waves) * 64u + lane;
+          fill += static_cast<uint32_t>(__builtin_popcount(w_lo) + __builtin_popcount(w_hi));
+        }
+        const uint32_t count = min(64u, fill - drained);
+        if (count == 0u) break;
+        // (LDS operations of one wavefront complete in order; the fence keeps the compiler's order)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        visit_rows(ring, drained, count, col_rsrc, val_rsrc, t_draw, beta, sums);
+        drained += count;
+      }
+      __syncthreads();
+    }
+    return true;
+  }
+
+  // One visit of the `count` rows staged in the ring from `drained` on; the other lanes behave like
+  // dummy lanes.
+  __device__ __forceinline__ void visit_rows(const uint32_t *ring, uint32_t drained, uint32_t count,
+                                             BufferRsrc col_rsrc, BufferRsrc val_rsrc, uint32_t t_draw,
+                                             double beta, SweepSums<M> &sums) {
+    uint32_t *todo32 = reinterpret_cast<uint32_t *>(todo);
+    const bool live = lane < count;
+    uint32_t p = 0, row_quads = 0, col_at = 0, val_at = 0;
+    if (live) {
+      p = ring[(drained + lane) & (kTailRing - 1u)];
+      const uint2 info = meta[p >> 6];
+      row_quads = info.y >> 2;
+      // the lane's row in the arrays, from their start (the host launches this form only while
+      // both arrays stay below 4 GiB): columns 1024 B and values 2048 B per quad of a block
+      col_at = (info.x >> 2) * 1024u + (p & 63u) * 16u;
+      val_at = (info.x >> 2) * 2048u + (p & 63u) * 16u;
+    }
+    // The row's spin and field: in bytes issued now and consumed behind the row sum, like the
+    // block visit's.  In words they are read behind the k-loop: a lane of this visit holds more
+    // of its own (its position, width and offsets) than a lane of a block visit, and the word
+    // layout has no register left for them (held across the loop they went to scratch).
+    uint32_t spin = kDummySpin;
+    double h = 0.0;
+    if (!WIDE && live) {
+      spin = a.spin_of_pos[p];
+      h = a.field_pos[p];
+    }
+    double acc[M];
+    listed_row_sums<M, LAYOUT>(col_rsrc, val_rsrc, row_quads, col_at, val_at, spins, acc, mult);
+    uint32_t own = 0;
+    if (WIDE && live) {
+      spin = a.spin_of_pos[p];
+      h = a.field_pos[p];
+    }
+    if (live) {
+      own = load_own<LAYOUT>(spins, p, p >> 6);
+    }
+    bool open;
+    const uint32_t flip = accept(acc, h, own, spin, t_draw, beta, sums, open);
+    // the row comes back while a proposal of it is open (an accepted one was)
+    if (open) atomicOr(&todo32[p >> 5], 1u << (p & 31u));
+    if (flip) {
+      store_flip<M, LAYOUT>(spins, p, p >> 6, own, flip);
+      // every neighbour's field changed: list it (the neighbours are of other colours; the
+      // row's columns only, its padding entries point at the row itself)
+      const uint4 *cols4 =
+          reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(a.ell_col) + col_at);
+      for (uint32_t q = 0; q < row_quads; ++q) {
+        const uint4 c4 = cols4[q * 64u];
+        const uint32_t cols[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t at = WIDE ? cols[j] >> 2 : cols[j];
+          if (at != p) atomicOr(&todo32[at >> 5], 1u << (at & 31u));
+        }
+      }
+    }
+  }
+
+  // ---- A full sweep: every colour, every block (but those the field cache calls inert) ----
+  __device__ __forceinline__ void colour_sweep(uint32_t t, uint32_t t_draw, double beta, SweepSums<M> &sums) {
     // wave-uniform: cached fields are in use during this sweep
-    const bool cached = cache_available && __builtin_amdgcn_readfirstlane(cache_ctl[1]) != 0;
+    const bool cached = cache_available && __builtin_amdgcn_readfirstlane(ctl[kCtlModeOn]) != 0;
     if constexpr (!DESCENT && !Res::kLadder) {
       if (cached && t > 0 && beta < a.betas[t - 1]) {
         // certain rejections are only certain for non-decreasing beta (workgroup-uniform branch)
-        for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) inert[b] = 0;
+        fill_blocks(inert, a.num_blocks, uint8_t{0});
         __syncthreads();
       }
     }
-    // q_acc: the fixed-point energy changes of the lane's accepted flips; kLeanBook: plus
-    // 0x4338000000000000 per visit (see the accept loop), arithmetic modulo 2^64
-    unsigned long long q_acc[M];
-    uint32_t n_acc[M];  // accepted flips of this lane in this sweep (< 2^32 blocks per sweep)
-    [[maybe_unused]] uint32_t visits = 0;  // blocks this wavefront evaluated in this sweep (wave-uniform)
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      q_acc[m] = 0;
-      n_acc[m] = 0;
-    }
-
-    // the first colour of the colour loop below: every colour, or none after a tail sweep
-    uint32_t first_hot_colour = 0;
-    if constexpr (TAIL) {
-      // ---- a tail sweep (workgroup-uniform branch): only the rows listed in `todo` ----
-      // Per colour a wavefront takes every waves-th block of the colour, 64 of them at a time (lane i
-      // reads and clears the word of its i-th), and stages the listed rows of the non-empty ones,
-      // block by block, in its ring at their mbcnt ranks.  As soon as 64 rows wait they are one visit
-      // with lane = row: every lane streams its OWN row (its block's first quad, its lane and the quad
-      // in a per-lane buffer offset), accumulates nothing from its own width on, and sums in
-      // ascending k with accumulate() — the block visit's f64 values bit for bit.  The accept phase is
-      // the visit's.  Rows of a colour are independent, the random words are keyed by (spin, sweep,
-      // replica) and the energy sums are integers: which rows share a visit changes no result.
-      if (__builtin_amdgcn_readfirstlane(cache_ctl[1]) != 0) {
-        const uint32_t wave_u = __builtin_amdgcn_readfirstlane(wave);
-        uint32_t *ring = reinterpret_cast<uint32_t *>(todo + a.num_blocks) + wave_u * kTailRing;
-        const BufferRsrc col_rsrc = block_rsrc(a.ell_col), val_rsrc = block_rsrc(a.ell_val);
-        for (uint32_t c = 0; c < a.num_colors; ++c) {
-          const uint32_t b_begin = a.color_block_start[c];
-          const uint32_t nb = a.color_block_start[c + 1] - b_begin;
-          uint32_t fill = 0, drained = 0;  // rows staged and rows visited so far (wave-uniform)
-          uint32_t base = 0, next_base = wave_u;
-          uint64_t w = 0, nonempty = 0;  // the lane's word of the running 64 blocks, and which lanes' are left
-          for (;;) {
-            while (fill - drained < 64u) {
-              if (nonempty == 0ull) {
-                if (next_base >= nb) break;
-                base = next_base;
-                next_base += waves * 64u;
-                const uint32_t i = base + lane * waves;
-                w = 0;
-                if (i < nb) {
-                  // nobody marks a block during its own colour step but the wavefront that took it
-                  w = todo[b_begin + i];
-                  if (w != 0ull) todo[b_begin + i] = 0ull;
-                }
-                nonempty = __ballot(w != 0ull);
-                continue;
-              }
-              const uint32_t src = static_cast<uint32_t>(__builtin_ctzll(nonempty));
-              nonempty &= nonempty - 1ull;
-              const uint32_t w_lo = __builtin_amdgcn_readlane(static_cast<uint32_t>(w), src);
-              const uint32_t w_hi = __builtin_amdgcn_readlane(static_cast<uint32_t>(w >> 32), src);
-              const uint32_t rank = __builtin_amdgcn_mbcnt_hi(w_hi, __builtin_amdgcn_mbcnt_lo(w_lo, 0u));
-              const uint32_t mine = lane < 32u ? w_lo >> lane : w_hi >> (lane - 32u);
-              if (mine & 1u) ring[(fill + rank) & (kTailRing - 1u)] = (b_begin + base + src * waves) * 64u + lane;
-              fill += static_cast<uint32_t>(__builtin_popcount(w_lo) + __builtin_popcount(w_hi));
-            }
-            const uint32_t count = min(64u, fill - drained);
-            if (count == 0u) break;
-            // (LDS operations of one wavefront complete in order; the fence keeps the compiler's order)
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            // ---- one visit of `count` rows; the other lanes behave like dummy lanes ----
-            const bool live = lane < count;
-            uint32_t p = 0, row_quads = 0, col_at = 0, val_at = 0;
-            if (live) {
-              p = ring[(drained + lane) & (kTailRing - 1u)];
-              const uint2 info = meta[p >> 6];
-              row_quads = info.y >> 2;
-              // the lane's row in the arrays, from their start (the host launches this form only while
-              // both arrays stay below 4 GiB): columns 1024 B and values 2048 B per quad of a block
-              col_at = (info.x >> 2) * 1024u + (p & 63u) * 16u;
-              val_at = (info.x >> 2) * 2048u + (p & 63u) * 16u;
-            }
-            drained += count;
-            visits += 1;
-            // The row's spin and field: in bytes issued now and consumed behind the row sum, like the
-            // block visit's.  In words they are read behind the k-loop: a lane of this visit holds more
-            // of its own (its position, width and offsets) than a lane of a block visit, and the word
-            // layout has no register left for them (held across the loop they went to scratch).
-            uint32_t spin = kDummySpin;
-            double h = 0.0;
-            if constexpr (!WIDE) {
-              if (live) {
-                spin = a.spin_of_pos[p];
-                h = a.field_pos[p];
-              }
-            }
-            // A lane streams the quads of its OWN row and never the next block's: from its width on it
-            // reads the first 48 bytes of the arrays instead (one cache line for all such lanes) and
-            // accumulates nothing.  Every load is issued unconditionally — a load under a lane mask makes
-            // hipcc drain the queue in front of each accumulate —, so the quad is part of the lane's
-            // offset and the k-loop keeps the block visit's prefetch distance of one.
-            auto load_row_quad = [&](Quad &q, uint32_t quad) {
-              const bool mine = quad < row_quads;
-              const uint32_t c_at = mine ? col_at + quad * 1024u : 0u;
-              const uint32_t v_at = mine ? val_at + quad * 2048u : 0u;
-              q.c = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(col_rsrc, c_at, 0, 0));
-              q.v01 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(val_rsrc, v_at, 0, 0));
-              q.v23 = __builtin_bit_cast(double2,
-                                         __builtin_amdgcn_raw_buffer_load_b128(val_rsrc, v_at + (mine ? 1024u : 16u), 0, 0));
-            };
-            double acc[M];
-#pragma unroll
-            for (int m = 0; m < M; ++m) acc[m] = 0.0;
-            Quad qa, qb;
-            load_row_quad(qa, 0u);
-            for (uint32_t q = 0; __ballot(q < row_quads) != 0ull; q += 2u) {
-              load_row_quad(qb, q + 1u);
-              __builtin_amdgcn_sched_barrier(0);
-              if (q < row_quads) accumulate<M, LAYOUT>(qa, spins, acc, mult);
-              __builtin_amdgcn_sched_barrier(0);
-              load_row_quad(qa, q + 2u);
-              __builtin_amdgcn_sched_barrier(0);
-              if (q + 1u < row_quads) accumulate<M, LAYOUT>(qb, spins, acc, mult);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-            // the accept phase of the visit (below), in its lean form
-            uint32_t own = 0;
-            if (live) {
-              if constexpr (WIDE) {
-                spin = a.spin_of_pos[p];
-                h = a.field_pos[p];
-              }
-              if constexpr (WIDE) {
-                own = reinterpret_cast<const uint32_t *>(spins)[p];
-              } else {
-                own = spins[p];
-              }
-            }
-            const bool valid = spin != kDummySpin;
-            bool open = false, need = false;
-            double de[M];
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-              const double g = __dadd_rn(acc[m], h);
-              const bool negative = (own >> (WIDE ? 8 * m + 7 : replica_bit<M, LAYOUT>(m))) & 1u;  // s = -1
-              de[m] = __dmul_rn(negative ? 2.0 : -2.0, g);
-              const bool maybe = valid && !(__dmul_rn(beta, de[m]) >= 23.0);  // not a certain rejection
-              open = open || maybe;
-              need = need || (maybe && !(de[m] <= 0.0));
-            }
-            uint32_t took[M];
-            if (__ballot(need) != 0ull) {
-              Philox4 rnd{};
-              uint32_t have = 0xFFFFFFFFu;
-#pragma unroll
-              for (int m = 0; m < M; ++m) {
-                uint32_t word;
-                if constexpr (ALIGNED) {
-                  if (m == 0) rnd = philox4x32_10(spin, t_draw, r0 >> 2, 0u, key0, key1);
-                  word = rnd.w[m];
-                } else {
-                  const uint32_t r = r0 + m;
-                  if (m == 0 || (r >> 2) != have) {
-                    have = r >> 2;
-                    rnd = philox4x32_10(spin, t_draw, have, 0u, key0, key1);
-                  }
-                  word = pick_word(rnd, r & 3u);
-                }
-                const bool accept =
-                    valid && (de[m] <= 0.0 || metropolis_accept_word(word, __dmul_rn(beta, de[m])));
-                took[m] = accept ? 0xFFFFFFFFu : 0u;
-              }
-            } else {
-#pragma unroll
-              for (int m = 0; m < M; ++m) took[m] = (valid && de[m] <= 0.0) ? 0xFFFFFFFFu : 0u;
-            }
-            uint32_t flip = 0;
-            double round_bias = 0x1.8p52;
-            asm volatile("" : "+v"(round_bias));
-            const uint32_t scale_hi = static_cast<uint32_t>(__double2hiint(a.scale));
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-              flip |= took[m] & (1u << m);
-              const double scale_m = __hiloint2double(static_cast<int>(scale_hi & took[m]), 0);
-              q_acc[m] += static_cast<unsigned long long>(
-                  __double_as_longlong(__builtin_fma(de[m], scale_m, round_bias)));
-              n_acc[m] -= took[m];  // + 1 when accepted
-            }
-            // the row comes back while a proposal of it is open (an accepted one was); positions of a
-            // visit are distinct: plain stores
-            if (open) atomicOr(&todo32[p >> 5], 1u << (p & 31u));
-            if (flip) {
-              if constexpr (WIDE) {
-                reinterpret_cast<uint32_t *>(spins)[p] = own ^ spread_mask(flip);
-              } else {
-                spins[p] = static_cast<uint8_t>(own ^ encode_replicas<M, LAYOUT>(flip));
-              }
-              // every neighbour's field changed: list it (the neighbours are of other colours; the
-              // row's columns only, its padding entries point at the row itself)
-              const uint4 *cols4 = reinterpret_cast<const uint4 *>(
-                  reinterpret_cast<const uint8_t *>(a.ell_col) + col_at);
-              for (uint32_t q = 0; q < row_quads; ++q) {
-                const uint4 c4 = cols4[q * 64u];
-                const uint32_t cols[4] = {c4.x, c4.y, c4.z, c4.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                  const uint32_t at = WIDE ? cols[j] >> 2 : cols[j];
-                  if (at != p) atomicOr(&todo32[at >> 5], 1u << (at & 31u));
-                }
-              }
-            }
-          }
-          __syncthreads();
-        }
-        first_hot_colour = a.num_colors;
-      }
-    }
-
-    for (uint32_t c = first_hot_colour; c < a.num_colors; ++c) {
+    for (uint32_t c = 0; c < a.num_colors; ++c) {
       const uint32_t b_begin = a.color_block_start[c];
       const uint32_t b_end = a.color_block_start[c + 1];
       // The colour's blocks go to the wavefronts in ascending order (widest rows first, the plan
       // sorts a colour by descending degree), each to the first wavefront that is free: the first
-      // `waves` blocks one per wavefront, every later one by a ticket drawn from cache_ctl[3].  The
+      // `waves` blocks one per wavefront, every later one by a ticket drawn from ctl[kCtlTicket].  The
       // ticket of the NEXT block is drawn before the visit of this one and read after it, so no
       // visit ends on a wait for the atomic (the visit's first LDS read returns in order behind it
       // and does wait for it); every wavefront that visits a block therefore ends the
@@ -918,293 +1076,136 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
            b = b_begin + waves + (__builtin_amdgcn_readfirstlane(ticket) - ticket_base)) {
         // (atomicInc, not atomicAdd: hipcc rewrites an LDS atomicAdd into a wave reduction and one more
         // dependent wait in front of every visit; measured slower)
-        if (lane == 0) ticket = atomicInc(&cache_ctl[3], 0xFFFFFFFFu);
-        const uint32_t p = b * 64u + lane;
-        bool reuse = false;
-        if (cached) {
-          reuse = (__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(dirty[b])) &
-                   ((1u << M) - 1u)) == 0u;
-          // fields unchanged and every proposal certain to be rejected again: nothing to do
-          if (reuse && __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(inert[b])) != 0u) {
-            continue;
-          }
-        }
-        if constexpr (kLeanBook) visits += 1;
-        // {first slab, width}: one broadcast LDS read (two scalar loads when bit-packed)
-        const uint2 info =
-            PACKED ? make_uint2(static_cast<uint32_t>(a.ell_off[b]), a.block_width[b]) : meta[b];
-        // wave-uniform by construction; readfirstlane makes the loop control scalar
-        const uint32_t quads = __builtin_amdgcn_readfirstlane(info.y) >> 2;
-        // info.x = first slab of the block (a multiple of 4): quad index = slab / 4
-        const uint64_t first_quad = __builtin_amdgcn_readfirstlane(info.x) >> 2;
-        const uint4 *col = reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u;
-        const double2 *val = reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u;
-        const BlockStream stream{col + lane, block_rsrc(col), block_rsrc(val), lane * 16u};
-        // issued now, consumed after the row sum: their latency hides under the k-loop
-        const uint32_t spin = a.spin_of_pos[p];
-        const double h = a.field_pos[p];
-        double acc[M];
-        // Field cache: when the workgroup is in cached mode and no neighbour of this block's
-        // spins has flipped since the block was last evaluated (dirty byte clear), the row
-        // sums are read back from HBM — the very same f64 values the k-loop would produce.
-        double *cache_row = nullptr;
-        if (cached) {
-          cache_row = a.field_cache +
-                      ((static_cast<uint64_t>(group) * a.num_blocks + b) * M) * 64u + lane;
-        }
-        if (reuse) {
-#pragma unroll
-          for (int m = 0; m < M; ++m) acc[m] = cache_row[m * 64];
-        } else {
-#pragma unroll
-          for (int m = 0; m < M; ++m) acc[m] = 0.0;
-          // k-loop, prefetch distance one: the next quad's three 16-byte loads are in flight
-          // while the current quad is gathered from LDS and accumulated, in the oracle's order
-          // k = 0, 1, 2, ...  Loop control is scalar and the body has no conditional loads
-          // (hipcc would otherwise drain the queue with vmcnt(0) at the loop header);
-          // sched_barrier keeps each load group ahead of the accumulate it overlaps.  For an
-          // even quad count the last load reads one quad past the block — the next block's
-          // first slabs or the tail padding the plan appends — and is never consumed.
-          Quad qa, qb;
-          load_quad(qa, stream, 0);
-          uint32_t i = 0;
-          for (; i + 2 <= quads; i += 2) {
-            load_quad(qb, stream, i + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate<M, LAYOUT>(qa, spins, acc, mult);
-            __builtin_amdgcn_sched_barrier(0);
-            load_quad(qa, stream, i + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate<M, LAYOUT>(qb, spins, acc, mult);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          if (i < quads) accumulate<M, LAYOUT>(qa, spins, acc, mult);
-          if (cached) {
-#pragma unroll
-            for (int m = 0; m < M; ++m) cache_row[m * 64] = acc[m];
-            if (lane == 0) dirty[b] = 0;  // nobody marks a block during its own colour step
-          }
-        }
-        const bool valid = spin != kDummySpin;
-        uint32_t own;
-        if constexpr (PACKED) {
-          own = static_cast<uint32_t>(
-              (load_word<GLOBAL>(reinterpret_cast<const uint64_t *>(spins) + b) >> lane) & 1ull);
-        } else if constexpr (WIDE) {
-          own = reinterpret_cast<const uint32_t *>(spins)[p];
-        } else if constexpr (NIBBLES) {
-          own = (static_cast<uint32_t>(spins[p >> 1]) >> ((p & 1u) << 2)) & 15u;
-        } else {
-          own = spins[p];
-        }
-        uint32_t flip = 0;
-        bool open = false;  // some proposal of this lane is not a certain rejection
-        bool need = false;  // some proposal of this lane needs a random number
-        double de[M];
-#pragma unroll
-        for (int m = 0; m < M; ++m) {
-          const double g = __dadd_rn(acc[m], h);
-          const bool negative = (own >> (WIDE ? 8 * m + 7 : replica_bit<M, LAYOUT>(m))) & 1u;  // s = -1
-          de[m] = __dmul_rn(negative ? 2.0 : -2.0, g);
-          if constexpr (DESCENT) {
-            open = open || (valid && de[m] < 0.0);
-          } else {
-            const bool maybe = valid && !(__dmul_rn(ladder.of(m, beta), de[m]) >= 23.0);  // not a certain rejection
-            open = open || maybe;
-            need = need || (maybe && !(de[m] <= 0.0));
-          }
-        }
-        // Random numbers only when some proposal of the block is undecided without one
-        // (dE <= 0 is accepted, beta * dE >= 23 rejected, whatever the draw): a wave-uniform
-        // branch around the 10 Philox rounds and the exp filter.  Counter-based RNG: skipping
-        // a draw changes nothing downstream.
-        const bool draw = !DESCENT && __ballot(need) != 0ull;
-        // the accepted proposals: bit m of accept_mask, or (kLeanBook) all ones in took[m]
-        uint32_t accept_mask = 0;
-        [[maybe_unused]] uint32_t took[M];
-        if (draw) {
-          Philox4 rnd{};
-          uint32_t have = 0xFFFFFFFFu;
-#pragma unroll
-          for (int m = 0; m < M; ++m) {
-            uint32_t word;
-            if constexpr (ALIGNED) {
-              // one call for the four replicas, the word a compile-time pick (no selection)
-              if (m == 0) rnd = philox4x32_10(spin, t_draw, r0 >> 2, 0u, key0, key1);
-              word = rnd.w[m];
-            } else {
-              const uint32_t r = r0 + m;
-              if (m == 0 || (r >> 2) != have) {
-                have = r >> 2;
-                rnd = philox4x32_10(spin, t_draw, have, 0u, key0, key1);
-              }
-              word = pick_word(rnd, r & 3u);
-            }
-            const bool accept =
-                valid && (de[m] <= 0.0 || metropolis_accept_word(word, __dmul_rn(ladder.of(m, beta), de[m])));
-            if constexpr (kLeanBook) {
-              took[m] = accept ? 0xFFFFFFFFu : 0u;
-            } else {
-              accept_mask |= (accept ? 1u : 0u) << m;
-            }
-          }
-        } else {
-#pragma unroll
-          for (int m = 0; m < M; ++m) {
-            // (no draw needed: DESCENT, or every proposal decided)
-            const bool accept = valid && (DESCENT ? de[m] < 0.0 : de[m] <= 0.0);
-            if constexpr (kLeanBook) {
-              took[m] = accept ? 0xFFFFFFFFu : 0u;
-            } else {
-              accept_mask |= (accept ? 1u : 0u) << m;
-            }
-          }
-        }
-        // Energy bookkeeping.  rint(dE * 2^S) as int64: |dE * 2^S| < 2^51 by the plan's choice of
-        // S, so adding 1.5 * 2^52 leaves the rounded integer in the mantissa (ties to even, = rint):
-        // the sum's bit pattern is 0x4338000000000000 + rint(dE * 2^S).
-        if constexpr (kLeanBook) {
-          // No branch and no selection: EVERY replica adds the bit pattern of dE * scale_m +
-          // 1.5 * 2^52, where scale_m is 2^S for an accepted proposal and 0 otherwise (2^S is a
-          // power of two: its low word is 0 and the high word is masked) — dE is finite, so a
-          // proposal that is not accepted adds the bare constant.  The `visits` constants come
-          // off once per sweep, in front of the reduction, modulo 2^64.  One fma is the multiply
-          // followed by the add: dE * 2^S is exact — the fma then rounds the very sum the add
-          // rounds — or it underflows, to something below 2^-1022 either way, and both sums round
-          // to 1.5 * 2^52.  v_fma_f64 reads one scalar operand, so the constant is put in vector
-          // registers here, after the k-loop: held for the whole launch it costs every
-          // instantiation two registers more.
-          double round_bias = 0x1.8p52;
-          asm volatile("" : "+v"(round_bias));
-          const uint32_t scale_hi = static_cast<uint32_t>(__double2hiint(a.scale));
-#pragma unroll
-          for (int m = 0; m < M; ++m) {
-            flip |= took[m] & (1u << m);
-            const double scale_m = __hiloint2double(static_cast<int>(scale_hi & took[m]), 0);
-            q_acc[m] += static_cast<unsigned long long>(
-                __double_as_longlong(__builtin_fma(de[m], scale_m, round_bias)));
-            n_acc[m] -= took[m];  // + 1 when accepted
-          }
-        } else {
-#pragma unroll
-          for (int m = 0; m < M; ++m) {
-            if ((accept_mask >> m) & 1u) {
-              flip |= 1u << m;
-              q_acc[m] += static_cast<unsigned long long>(
-                  __double_as_longlong(__dadd_rn(__dmul_rn(de[m], a.scale), 0x1.8p52)) -
-                  0x4338000000000000ll);
-              n_acc[m] += 1;
-            }
-          }
-        }
-        if constexpr (PACKED) {
-          // the block's 64 proposals decided: one XOR of the ballot into the block's word
-          const uint64_t flips = __ballot(flip != 0);
-          if (lane == 0 && flips != 0) {
-            uint64_t *word = reinterpret_cast<uint64_t *>(spins) + b;
-            store_word<GLOBAL>(word, load_word<GLOBAL>(word) ^ flips);
-          }
-        } else if constexpr (WIDE) {
-          if (flip) reinterpret_cast<uint32_t *>(spins)[p] = own ^ spread_mask(flip);
-        } else if constexpr (NIBBLES) {
-          // the neighbouring lane owns the other nibble of the byte and may flip in the same
-          // instruction: an LDS atomic on the word (eight positions) instead of a byte store
-          if (flip) atomicXor(reinterpret_cast<uint32_t *>(spins) + (p >> 3), flip << ((p & 7u) << 2));
-        } else {
-          if (flip) spins[p] = static_cast<uint8_t>(own ^ encode_replicas<M, LAYOUT>(flip));
-        }
-        if (cached) {
-          const bool none_open = __ballot(open) == 0ull;
-          if (lane == 0) inert[b] = none_open ? 1 : 0;
-        }
-        if (cached && __ballot(flip != 0) != 0ull) {
-          // Every neighbour of a flipped spin sits in a block of ANOTHER colour: mark those
-          // blocks stale for the replicas that flipped.  The row's columns are streamed again
-          // (columns only); in cached mode flips are rare by construction.
-          uint32_t *dirty_words = reinterpret_cast<uint32_t *>(dirty);
-          for (uint32_t q = 0; q < quads; ++q) {
-            const uint4 c4 = stream.cptr[q * 64u];
-            if (flip) {
-              const uint32_t cols[4] = {c4.x, c4.y, c4.z, c4.w};
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                // padding entries point at the lane itself; wide columns are byte addresses
-                if (cols[j] == (WIDE ? p * 4u : p)) continue;
-                const uint32_t blk = cols[j] >> (WIDE ? 8 : 6);
-                atomicOr(&dirty_words[blk >> 2], flip << (8u * (blk & 3u)));
-              }
-            }
-          }
-        }
+        if (lane == 0) ticket = atomicInc(&ctl[kCtlTicket], 0xFFFFFFFFu);
+        visit_block(b, cached, t_draw, beta, sums);
       }
       ticket_base += b_end - b_begin;
       __syncthreads();
     }
+  }
 
-    // ---- exact (integer) reduction of the sweep's energy change ----
-    // Sums between registers with the totals in lane 63, and only in a wavefront some lane of which
-    // accepted a flip in this sweep: in every other one each lane holds 0 flips and an energy
-    // change of 0 (kLeanBook: q_acc = visits * 0x4338000000000000 exactly, a proposal that is not
-    // accepted adds the bare constant), and nothing would be added below.  The flip counts travel two
-    // to a 64-bit sum: a lane accepts at most one flip per block, so the low count's total stays
-    // below 64 * num_blocks < 2^32 and never carries into the high one.
-    {
-      uint32_t any = 0;
+  // One visit of block b: lane = row.
+  __device__ __forceinline__ void visit_block(uint32_t b, bool cached, uint32_t t_draw, double beta,
+                                              SweepSums<M> &sums) {
+    const uint32_t p = b * 64u + lane;
+    bool reuse = false;
+    if (cached) {
+      reuse = (__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(dirty[b])) & ((1u << M) - 1u)) == 0u;
+      // fields unchanged and every proposal certain to be rejected again: nothing to do
+      if (reuse && __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(inert[b])) != 0u) return;
+    }
+    // {first slab, width}: one broadcast LDS read (two scalar loads when bit-packed)
+    const uint2 info = PACKED ? make_uint2(static_cast<uint32_t>(a.ell_off[b]), a.block_width[b]) : meta[b];
+    // wave-uniform by construction; readfirstlane makes the loop control scalar
+    const uint32_t quads = __builtin_amdgcn_readfirstlane(info.y) >> 2;
+    // info.x = first slab of the block (a multiple of 4): quad index = slab / 4
+    const uint64_t first_quad = __builtin_amdgcn_readfirstlane(info.x) >> 2;
+    const uint4 *col = reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u;
+    const double2 *val = reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u;
+    const BlockStream stream{col + lane, block_rsrc(col), block_rsrc(val), lane * 16u};
+    // issued now, consumed after the row sum: their latency hides under the k-loop
+    const uint32_t spin = a.spin_of_pos[p];
+    const double h = a.field_pos[p];
+    double acc[M];
+    // Field cache: when the workgroup is in cached mode and no neighbour of this block's
+    // spins has flipped since the block was last evaluated (dirty byte clear), the row
+    // sums are read back from HBM — the very same f64 values the k-loop would produce.
+    double *cache_row = nullptr;
+    if (cached) {
+      cache_row = a.field_cache + ((static_cast<uint64_t>(group) * a.num_blocks + b) * M) * 64u + lane;
+    }
+    if (reuse) {
 #pragma unroll
-      for (int m = 0; m < M; ++m) any |= n_acc[m];
-      if (__ballot(any != 0) != 0ull) {
+      for (int m = 0; m < M; ++m) acc[m] = cache_row[m * 64];
+    } else {
+      block_row_sums<M, LAYOUT>(stream, quads, spins, acc, mult);
+      if (cached) {
 #pragma unroll
-        for (int m0 = 0; m0 < M; m0 += 2) {
-          unsigned long long v[2] = {0, 0};
+        for (int m = 0; m < M; ++m) cache_row[m * 64] = acc[m];
+        if (lane == 0) dirty[b] = 0;  // nobody marks a block during its own colour step
+      }
+    }
+    const uint32_t own = load_own<LAYOUT>(spins, p, b);
+    bool open;
+    const uint32_t flip = accept(acc, h, own, spin, t_draw, beta, sums, open);
+    store_flip<M, LAYOUT>(spins, p, b, own, flip);
+    if (cached) {
+      const bool none_open = __ballot(open) == 0ull;
+      if (lane == 0) inert[b] = none_open ? 1 : 0;
+    }
+    if (cached && __ballot(flip != 0) != 0ull) {
+      // Every neighbour of a flipped spin sits in a block of ANOTHER colour: mark those
+      // blocks stale for the replicas that flipped.  The row's columns are streamed again
+      // (columns only); in cached mode flips are rare by construction.
+      uint32_t *dirty_words = reinterpret_cast<uint32_t *>(dirty);
+      for (uint32_t q = 0; q < quads; ++q) {
+        const uint4 c4 = stream.cptr[q * 64u];
+        if (flip) {
+          const uint32_t cols[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            // padding entries point at the lane itself; wide columns are byte addresses
+            if (cols[j] == (WIDE ? p * 4u : p)) continue;
+            const uint32_t blk = cols[j] >> (WIDE ? 8 : 6);
+            atomicOr(&dirty_words[blk >> 2], flip << (8u * (blk & 3u)));
+          }
+        }
+      }
+    }
+  }
+
+  // ---- The exact (integer) reduction of the sweep's energy change ----
+  // Sums between registers with the totals in lane 63, and only in a wavefront some lane of which
+  // accepted a flip in this sweep: in every other one each lane holds 0 flips and an energy
+  // change of 0 (kLeanBook: q = visits * 0x4338000000000000 exactly, a proposal that is not
+  // accepted adds the bare constant), and nothing would be added below.  The flip counts travel two
+  // to a 64-bit sum: a lane accepts at most one flip per block, so the low count's total stays
+  // below 64 * num_blocks < 2^32 and never carries into the high one.
+  __device__ __forceinline__ void reduce(const SweepSums<M> &sums) {
+    uint32_t any = 0;
+#pragma unroll
+    for (int m = 0; m < M; ++m) any |= sums.n[m];
+    if (__ballot(any != 0) != 0ull) {
+#pragma unroll
+      for (int m0 = 0; m0 < M; m0 += 2) {
+        unsigned long long v[2] = {0, 0};
+#pragma unroll
+        for (int j = 0; j < 2 && m0 + j < M; ++j) {
+          // kLeanBook: the visits' constants off, modulo 2^64 (the true sum fits: the plan's S)
+          v[j] = wave_sum_lane63_u64(kLeanBook ? sums.q[m0 + j] - sums.visits * 0x4338000000000000ull
+                                               : sums.q[m0 + j]);
+        }
+        const unsigned long long n2 = wave_sum_lane63_u64(
+            sums.n[m0] |
+            (m0 + 1 < M ? static_cast<unsigned long long>(sums.n[m0 + 1 < M ? m0 + 1 : m0]) << 32 : 0ull));
+        if (lane == 63) {
 #pragma unroll
           for (int j = 0; j < 2 && m0 + j < M; ++j) {
-            // kLeanBook: the visits' constants off, modulo 2^64 (the true sum fits: the plan's S)
-            v[j] = wave_sum_lane63_u64(
-                kLeanBook ? q_acc[m0 + j] - visits * 0x4338000000000000ull : q_acc[m0 + j]);
-          }
-          const unsigned long long n2 = wave_sum_lane63_u64(
-              n_acc[m0] | (m0 + 1 < M ? static_cast<unsigned long long>(n_acc[m0 + 1 < M ? m0 + 1 : m0]) << 32 : 0ull));
-          if (lane == 63) {
-#pragma unroll
-            for (int j = 0; j < 2 && m0 + j < M; ++j) {
-              const uint32_t n = static_cast<uint32_t>(n2 >> (32 * j));
-              if (n != 0) {
-                atomicAdd(reinterpret_cast<unsigned long long *>(&delta[m0 + j]), v[j]);
-                atomicAdd(reinterpret_cast<unsigned long long *>(&book[16 + m0 + j]),
-                          static_cast<unsigned long long>(n));
-                if (TAIL || cache_available) atomicAdd(&cache_ctl[0], n);
-              }
+            const uint32_t n = static_cast<uint32_t>(n2 >> (32 * j));
+            if (n != 0) {
+              atomicAdd(reinterpret_cast<unsigned long long *>(&delta[m0 + j]), v[j]);
+              atomicAdd(reinterpret_cast<unsigned long long *>(&book[16 + m0 + j]),
+                        static_cast<unsigned long long>(n));
+              if (TAIL || cache_available) atomicAdd(&ctl[kCtlFlips], n);
             }
           }
         }
       }
     }
     __syncthreads();
-    if (cache_available && tid == 0) {
-      // Cached mode pays when the flips of a sweep dirty only a fraction of the blocks:
-      // enter below `cache_enter_flips` flips per sweep, leave above twice that.
-      const uint32_t flips = cache_ctl[0];
-      cache_ctl[0] = 0;
-      const bool was = cache_ctl[1] != 0;
-      const bool now = was ? flips < 2u * a.cache_enter_flips : flips < a.cache_enter_flips;
-      cache_ctl[1] = now ? 1u : 0u;
-      cache_ctl[2] = (now && !was) ? 1u : 0u;  // entering: every block starts stale
-    }
-    if constexpr (TAIL) {
-      if (tid == 0) {
-        // Tail sweeps pay while few rows are listed: enter below `enter_flips` flips per sweep, leave
-        // above twice that, and leave in front of a sweep at a lower beta — a certain rejection is only
-        // certain for non-decreasing beta, and the rows that are not listed rest on it.
-        const uint32_t flips = cache_ctl[0];
-        cache_ctl[0] = 0;
-        const bool was = cache_ctl[1] != 0;
-        bool now = was ? flips <= 2ull * tail.enter_flips : flips < tail.enter_flips;
-        if (t + 1u < a.num_sweeps && a.betas[t + 1u] < beta) now = false;
-        cache_ctl[1] = now ? 1u : 0u;
-        cache_ctl[2] = (now && !was) ? 1u : 0u;  // entering: every row is listed
-        if (was) cache_ctl[4] += 1u;
-        if (now && !was) cache_ctl[5] += 1u;
+  }
+
+  // ---- End of sweep t: the mode of the next sweep, the books, the snapshot of what improved.  True
+  // when the launch ends here (StopWhenStill). ----
+  __device__ __forceinline__ bool end_of_sweep(uint32_t t, double beta) {
+    if ((TAIL || cache_available) && tid == 0) {
+      bool leave_now = false;
+      if constexpr (TAIL) {
+        // a certain rejection is only certain for non-decreasing beta, and the rows that are not
+        // listed rest on it
+        leave_now = t + 1u < a.num_sweeps && a.betas[t + 1u] < beta;
       }
+      end_of_sweep_mode<TAIL>(ctl, TAIL ? tail.enter_flips : a.cache_enter_flips, leave_now);
     }
     if (tid < M) {
       const long long e = book[tid] + delta[tid];
@@ -1227,59 +1228,69 @@ __device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t grou
       const long long flips = book[16];
       if (flips == flips_before) {
         sweeps_done = t + 1u;
-        break;
+        return true;
       }
       flips_before = flips;
     }
     const uint32_t improved = DESCENT ? ((1u << M) - 1u) : *improved_flag;
     if (improved) snapshot<M, LAYOUT>(spins, a, group, improved);
-    if (cache_available && cache_ctl[2] != 0) {
-      for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) dirty[b] = 0xFF;
-    }
-    if constexpr (TAIL) {
-      if (cache_ctl[2] != 0) {
-        for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) todo[b] = ~0ull;
+    // entering the mode: every block starts stale / every row is listed
+    if ((TAIL || cache_available) && ctl[kCtlModeEntered] != 0) {
+      if constexpr (TAIL) {
+        fill_blocks(todo, a.num_blocks, ~uint64_t{0});
+      } else {
+        fill_blocks(dirty, a.num_blocks, uint8_t{0xFF});
       }
     }
     __syncthreads();
     if (tid == 0) {
       *improved_flag = 0;  // next write to it is two barriers away
-      if (TAIL || cache_available) cache_ctl[2] = 0;
+      if (TAIL || cache_available) ctl[kCtlModeEntered] = 0;
     }
-  }
-  if constexpr (TAIL) {
-    if (tid == 0) {
-      tail.report[2ull * group] = cache_ctl[4];
-      tail.report[2ull * group + 1u] = cache_ctl[5];
-    }
+    return false;
   }
 
-  if (tid < M) {
-    a.tracked[static_cast<uint64_t>(group) * M + tid] = book[8 + tid];
-    a.accepted[static_cast<uint64_t>(group) * M + tid] =
-        static_cast<unsigned long long>(book[16 + tid]);
-  }
-  if constexpr (DESCENT && Stop::kEnabled) {
-    if (tid == 0) *stop.sweeps_done = sweeps_done;
-  }
-  if constexpr (Res::kEnabled) {
-    // the state the next segment starts from (the spins were last written before the final barriers)
-    if (tid < M) res.e_cur[static_cast<uint64_t>(group) * M + tid] = book[tid];
-    if constexpr (std::is_same_v<Args, SweepArgs>) {
-      SweepArgs fin = a;
-      fin.best_perm = res.cur_perm;
-      snapshot<M, LAYOUT>(spins, fin, group, (1u << M) - 1u);
-    } else {
-      // (arguments in the constant address space, k_sa_sweep_batch's segments: what snapshot() reads of
-      // them, with the current words as the target; k_sa_sweep_resume keeps its code)
-      struct FinalWords {
-        uint64_t *best_perm;
-        uint32_t num_blocks;
-      };
-      const FinalWords fin{res.cur_perm, a.num_blocks};
-      snapshot<M, LAYOUT>(spins, fin, group, (1u << M) - 1u);
+  // ---- Epilogue: what the launch reports ----
+  __device__ __forceinline__ void epilogue() {
+    if (TAIL && tid == 0) {
+      tail.report[2ull * group] = ctl[kCtlTailSweeps];
+      tail.report[2ull * group + 1u] = ctl[kCtlTailEntries];
+    }
+    if (tid < M) {
+      a.tracked[static_cast<uint64_t>(group) * M + tid] = book[8 + tid];
+      a.accepted[static_cast<uint64_t>(group) * M + tid] = static_cast<unsigned long long>(book[16 + tid]);
+    }
+    if constexpr (DESCENT && Stop::kEnabled) {
+      if (tid == 0) *stop.sweeps_done = sweeps_done;
+    }
+    if constexpr (Res::kEnabled) {
+      // the state the next segment starts from (the spins were last written before the final barriers)
+      if (tid < M) res.e_cur[static_cast<uint64_t>(group) * M + tid] = book[tid];
+      snapshot<M, LAYOUT>(spins, FinalWords{res.cur_perm, a.num_blocks}, group, (1u << M) - 1u);
     }
   }
+};
+
+template <int M, bool DESCENT, int LAYOUT, typename Args, typename Stop = NoEarlyStop,
+          typename Res = NoResume, bool ALIGNED = false, bool TAIL = false>
+__device__ __forceinline__ void sa_sweep_body(const Args &a, const uint32_t group,
+                                              const Stop stop = Stop{}, const Res res = Res{},
+                                              const TailArgs tail = TailArgs{}) {
+  ColourSweep<M, DESCENT, LAYOUT, Args, Stop, Res, ALIGNED, TAIL> sweep(a, group, stop, res, tail);
+  sweep.start();
+  for (uint32_t t = 0; t < a.num_sweeps; ++t) {
+    uint32_t t_draw = t;  // the sweep index of the random words: global over the segments of a handle
+    if constexpr (Res::kEnabled) t_draw += res.t0;
+    double beta = 0.0;  // (a descent — dE >= 0 is a certain rejection at any beta — and a ladder segment read none)
+    if constexpr (!DESCENT && !Res::kLadder) beta = a.betas[t];
+    SweepSums<M> sums{};
+    bool listed_only = false;
+    if constexpr (TAIL) listed_only = sweep.tail_sweep(t_draw, beta, sums);
+    if (!listed_only) sweep.colour_sweep(t, t_draw, beta, sums);
+    sweep.reduce(sums);
+    if (sweep.end_of_sweep(t, beta)) break;
+  }
+  sweep.epilogue();
 }
 
 template <int M, bool DESCENT, int LAYOUT, bool ALIGNED = false>
@@ -2213,25 +2224,12 @@ ClosedFamily<false, false>::Kernel closed_kernel_of(int m, bool descent, int lay
   return colour_kernel_of<ClosedFamily<false, false>>(m, layout);
 }
 
-size_t sweep_lds_bytes(const asp::SaHostLayout &L, int layout) {
-  // spins | delta[8] book[24] | flag (16 B) | meta[num_blocks]
-  // ... | cache_ctl[4] | dirty[num_blocks] | inert[num_blocks] (each rounded up to 16 B)
-  // bit-packed: spin words | delta book | flag | cache_ctl only
-  if (layout == kGlobal) return 34 * sizeof(long long) + 32;
-  if (layout == kBits) return static_cast<size_t>(L.num_blocks) * 8 + 34 * sizeof(long long) + 32;
-  const size_t per_block = layout == kWide ? 256 : (layout == kNibbles ? 32 : 64);
-  return static_cast<size_t>(L.num_blocks) * per_block + 34 * sizeof(long long) +
-         static_cast<size_t>(L.num_blocks) * sizeof(uint2) + 16 +
-         2 * (((static_cast<size_t>(L.num_blocks) + 15) / 16) * 16);
-}
-
-// k_sa_sweep_tail (bytes, words): spins | delta[8] book[24] | flag (16 B) | meta[num_blocks] | cache_ctl[8] |
-// todo[num_blocks] (a u64 each) | kTailRing staged rows per wavefront; no dirty and inert bytes
-size_t tail_lds_bytes(const asp::SaHostLayout &L, int layout, int threads) {
-  const size_t per_block = layout == kWide ? 256 : 64;
-  return static_cast<size_t>(L.num_blocks) * per_block + 34 * sizeof(long long) +
-         static_cast<size_t>(L.num_blocks) * sizeof(uint2) + 32 + static_cast<size_t>(L.num_blocks) * sizeof(uint64_t) +
-         static_cast<size_t>(threads / 64) * kTailRing * sizeof(uint32_t);
+// The dynamic LDS of a launch (SweepLds::total): a kernel without tail sweeps, or (tail) k_sa_sweep_tail
+// with `threads` threads.  (32-bit offsets: 2^20 blocks are far beyond any LDS in every layout that keeps
+// something per block.)
+size_t sweep_lds_bytes(const asp::SaHostLayout &L, int layout, bool tail = false, int threads = 0) {
+  if (layout != kGlobal && L.num_blocks > (1u << 20)) return SIZE_MAX;
+  return SweepLds(L.num_blocks, layout, tail, static_cast<uint32_t>(threads / 64)).total;
 }
 
 // Tail sweeps after a sweep with fewer flips of the workgroup than this (asp_sa_set_tail's automatic
@@ -2256,7 +2254,7 @@ TailKernel tail_kernel_of(const asp_sa_plan *p, int m, int threads, int layout, 
   if (p->tail_mode == 0 || !p->use_field_cache || descent || m != 4 || (layout != kBytes && layout != kWide)) {
     return nullptr;
   }
-  if (tail_lds_bytes(L, layout, threads) > p->max_lds) return nullptr;
+  if (sweep_lds_bytes(L, layout, true, threads) > p->max_lds) return nullptr;
   if (L.ell_val.size() * sizeof(double) >= (1ull << 32)) return nullptr;
   const bool aligned = replica_first % 4u == 0;
   if (layout == kWide) return aligned ? k_sa_sweep_tail<kWide, true> : k_sa_sweep_tail<kWide, false>;
@@ -2847,8 +2845,7 @@ int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_
       team >= 2 ? nullptr : tail_kernel_of(p, form.m, form.threads, form.layout, descent, replica_offset);
   run.tail = tail_kernel != nullptr;
   ASP_TRY(run.shape(form, team >= 2 ? team_lds_bytes(L)
-                                    : (run.tail ? tail_lds_bytes(L, form.layout, form.threads)
-                                                : sweep_lds_bytes(L, form.layout))));
+                                    : sweep_lds_bytes(L, form.layout, run.tail, form.threads)));
   hipStream_t s = p->stream;
   // every exit below, error or not, first waits for what was queued on the stream: copies into
   // the caller's buffers and kernels using the plan's work buffers never outlive the call
