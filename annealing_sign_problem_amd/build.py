@@ -36,6 +36,7 @@ SOURCES = [
     "key_table.hip",
     "plain_basis.hip",
     "sparsify.hip",
+    "level_segments.hip",
     "bond_stats.hip",
     "sa_plan.cpp",
     "greedy.cpp",

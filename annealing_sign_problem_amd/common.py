@@ -35,6 +35,10 @@ __all__ = [
     "make_hamiltonian_extension",
     "make_hamiltonian_extensions",
     "extension_spins",
+    "extension_spins_segments",
+    "extend_and_sparsify_models",
+    "sparsify_component_segments",
+    "sparsify_models_using_global_cutoff",
     "local_energies",
     "variational_energy",
     "sparsify_using_global_cutoff",
@@ -736,6 +740,126 @@ def sparsify_using_global_cutoff(model: IsingModel, reltol: float, frozen_spins)
     hamiltonian = sa.Hamiltonian.from_canonical_csr(exchange.indptr, exchange.indices, exchange.data, field)
     basis_index = None if model.basis_index is None else model.basis_index[keep]
     return IsingModel(spins, model.quantum_hamiltonian, hamiltonian, sa.signs_to_bits(signs), basis_index)
+
+
+def sparsify_component_segments(offsets, indptr, indices, data, is_frozen, reltol: float, anchors):
+    """:func:`sparsify_component` of many matrices in one device call, specification ASP-SPARSIFY-SEG-1
+    (csrc/level_segments.hip).  The input is laid out as ``DeviceOperator.ising_csr_segments``
+    returns it: ``offsets`` u64[G + 1] cuts the T spins into segments, ``indptr`` is ONE global i64[T + 1]
+    from 0, ``indices`` are local to their segment; ``is_frozen`` bool[T]; ``anchors`` u64[G], local.
+    Returns ``(keep bool[T], kept_offsets u64[G + 1], out_indptr i64[kept + 1], out_indices i32, out_data
+    f64)`` in the same layout over the kept spins; the threshold is ``reltol * max|data|`` of each segment."""
+    lib = _lib.load()
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    frozen = np.ascontiguousarray(is_frozen, dtype=np.uint8)
+    anchors = np.ascontiguousarray(anchors, dtype=np.uint64)
+    if offsets.ndim != 1 or offsets.shape[0] < 1:
+        raise ValueError("offsets should hold one entry more than there are segments")
+    segments = offsets.shape[0] - 1
+    t = int(offsets[-1])
+    if indptr.shape != (t + 1,) or frozen.shape != (t,) or anchors.shape != (segments,):
+        raise ValueError("indptr, is_frozen and anchors should have T + 1, T and G entries")
+    if indices.shape != data.shape or indices.shape[0] < int(indptr[-1]):
+        raise ValueError("indices and data should hold indptr[-1] entries")
+    if t > 0:
+        _lib.require_gpu()
+    keep = np.zeros(max(t, 1), dtype=np.uint8)
+    kept_offsets = np.zeros(segments + 1, dtype=np.uint64)
+    capacity = int(indptr[-1])
+    out_indptr = np.zeros(t + 1, dtype=np.int64)
+    out_indices = np.empty(max(capacity, 1), dtype=np.int32)
+    out_data = np.empty(max(capacity, 1), dtype=np.float64)
+    nnz = ctypes.c_uint64(0)
+    _lib.check(lib.asp_sparsify_component_segments(
+        ctypes.c_uint64(segments), _lib.ptr(offsets), _lib.ptr(indptr), _lib.ptr(indices), _lib.ptr(data),
+        _lib.ptr(frozen), ctypes.c_double(float(reltol)), _lib.ptr(anchors), _lib.ptr(keep), _lib.ptr(kept_offsets),
+        ctypes.c_uint64(capacity), _lib.ptr(out_indptr), _lib.ptr(out_indices), _lib.ptr(out_data),
+        ctypes.byref(nnz)))
+    n, z = int(kept_offsets[-1]), int(nnz.value)
+    return keep[:t].astype(bool), kept_offsets, out_indptr[:n + 1], out_indices[:z], out_data[:z]
+
+
+def sparsify_models_using_global_cutoff(models, reltol: float, frozen_spins_list):
+    """``[sparsify_using_global_cutoff(m, reltol, f) for m, f in zip(models, frozen_spins_list)]`` (not in
+    the reference) with the cutoff, the components and the kept blocks of ALL models from one device call
+    (:func:`sparsify_component_segments`): the same models field by field.  The models' CSR arrays are
+    concatenated as they are — no scipy matrix is built per cluster on the way in."""
+    models = list(models)
+    frozen_spins_list = list(frozen_spins_list)
+    if len(frozen_spins_list) != len(models):
+        raise ValueError("'frozen_spins_list' should hold one array per model")
+    if not models:
+        return []
+    offsets = np.zeros(len(models) + 1, dtype=np.uint64)
+    np.cumsum([m.spins.shape[0] for m in models], out=offsets[1:])
+    total = int(offsets[-1])
+    is_frozen = np.zeros(total, dtype=bool)
+    anchors = np.zeros(len(models), dtype=np.uint64)
+    indptr = np.zeros(total + 1, dtype=np.int64)
+    base = 0
+    for g, (model, frozen_spins) in enumerate(zip(models, frozen_spins_list)):
+        first, last = int(offsets[g]), int(offsets[g + 1])
+        frozen = binary_search(model.spins, frozen_spins)
+        is_frozen[first:last][frozen] = True
+        anchors[g] = int(frozen[0])
+        own = model.ising_hamiltonian.exchange.indptr
+        indptr[first + 1:last + 1] = own[1:].astype(np.int64) + base
+        base += int(own[-1])
+    indices = np.concatenate([m.ising_hamiltonian.exchange.indices for m in models])
+    data = np.concatenate([m.ising_hamiltonian.exchange.data for m in models])
+    keep, kept_offsets, out_indptr, out_indices, out_data = sparsify_component_segments(
+        offsets, indptr, indices, data, is_frozen, reltol, anchors)
+    out = []
+    for g, model in enumerate(models):
+        mask = keep[int(offsets[g]):int(offsets[g + 1])]
+        first, last = int(kept_offsets[g]), int(kept_offsets[g + 1])
+        begin, end = int(out_indptr[first]), int(out_indptr[last])
+        signs = sa.bits_to_signs(model.initial_signs, model.size)[mask]
+        hamiltonian = sa.Hamiltonian.from_canonical_csr(
+            (out_indptr[first:last + 1] - begin).astype(np.int32), out_indices[begin:end].copy(),
+            out_data[begin:end].copy(), model.ising_hamiltonian.field[mask])
+        basis_index = None if model.basis_index is None else model.basis_index[mask]
+        out.append(IsingModel(model.spins[mask], model.quantum_hamiltonian, hamiltonian, sa.signs_to_bits(signs),
+                              basis_index))
+    return out
+
+
+def extension_spins_segments(hamiltonian, spins_list) -> list:
+    """``[extension_spins(hamiltonian, s) for s in spins_list]`` (not in the reference) with the
+    extensions of ALL sets from one device call (``DeviceOperator.extend_segments``, ASP-EXTEND-SEG-1,
+    DESIGN.md §3.10).  Foreign operator objects take that loop."""
+    spins_list = list(spins_list)
+    if not _on_device(hamiltonian) or not spins_list:
+        return [extension_spins(hamiltonian, s) for s in spins_list]
+    parts = [np.ascontiguousarray(s, dtype=np.uint64) for s in spins_list]
+    offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+    np.cumsum([p.shape[0] for p in parts], out=offsets[1:])
+    states, out_offsets = hamiltonian.device().extend_segments(np.concatenate(parts), offsets)
+    return [states[int(out_offsets[g]):int(out_offsets[g + 1])].copy() for g in range(len(parts))]
+
+
+def extend_and_sparsify_models(models, log_psi_fn, reltol: float, frozen_spins_list, external_field: bool = False):
+    """One level of a round in three steps (not in the reference): :func:`extension_spins_segments` ->
+    :func:`make_ising_models` -> :func:`sparsify_models_using_global_cutoff`, each ONE device call for all
+    clusters.  Equals ``[sparsify_using_global_cutoff(make_hamiltonian_extension(m, log_psi_fn,
+    external_field), reltol, f) for m, f in zip(models, frozen_spins_list)]`` field by field; models of
+    different operators take that loop."""
+    models = list(models)
+    frozen_spins_list = list(frozen_spins_list)
+    if len(frozen_spins_list) != len(models):
+        raise ValueError("'frozen_spins_list' should hold one array per model")
+    if not models:
+        return []
+    operator = models[0].quantum_hamiltonian
+    if any(m.quantum_hamiltonian is not operator for m in models):
+        return [sparsify_using_global_cutoff(make_hamiltonian_extension(m, log_psi_fn, external_field), reltol, f)
+                for m, f in zip(models, frozen_spins_list)]
+    extended = extension_spins_segments(operator, [m.spins for m in models])
+    built = make_ising_models(extended, operator, log_psi_fn=log_psi_fn, external_field=external_field)
+    return sparsify_models_using_global_cutoff(built, reltol, frozen_spins_list)
 
 
 def invert_permutation(p) -> np.ndarray:

@@ -871,6 +871,19 @@ int connection_list_queue(const asp_operator *op, uint64_t n, const uint64_t *ke
   return symmetrise_batch(op, n, out->batch, out->d_other.ptr, out->d_coeffs.ptr, sym, false, stream);
 }
 
+int extension_list_queue(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
+                         Symmetrised *sym, hipStream_t stream) {
+  ASP_TRY(count_connections(op, n, keys, &out->batch, stream));
+  ASP_TRY(out->d_other.alloc(out->batch.total));
+  ASP_TRY(out->d_coeffs.alloc(out->batch.total));
+  if (n == 0) return ASP_OK;
+  hipLaunchKernelGGL(k_apply<true>, dim3(grid_for(n, kWaves)), dim3(kThreads), 0, stream,
+                     op->d_bonds.ptr, op->num_bonds, out->batch.d_keys.ptr, n, out->batch.d_offsets.ptr,
+                     nullptr, out->d_other.ptr, out->d_coeffs.ptr);
+  ASP_HIP_TRY(hipGetLastError());
+  return symmetrise_batch(op, n, out->batch, out->d_other.ptr, out->d_coeffs.ptr, sym, true, stream);
+}
+
 int connection_list(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
                     hipStream_t stream) {
   Symmetrised sym;

@@ -103,6 +103,11 @@ int connection_list(const asp_operator *op, uint64_t n, const uint64_t *keys, Co
 // StreamFence declared after `out` and `sym`.
 int connection_list_queue(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
                           Symmetrised *sym, hipStream_t stream);
+// connection_list_queue in EXTENSION mode (asp_operator_extend's): in out->d_other the targets of a
+// symmetry-adapted basis are representatives, and a target of norm 0 is the "no state" value
+// op->symmetry().mask; out->d_coeffs is scratch.  One synchronisation inside (the connection count).
+int extension_list_queue(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
+                         Symmetrised *sym, hipStream_t stream);
 // Clears slots[slots_n] (a power of two >= 2n) and inserts the n device keys.
 int key_hash_build(const uint64_t *d_keys, uint64_t n, unsigned long long *d_slots, uint64_t slots_n,
                    hipStream_t stream);

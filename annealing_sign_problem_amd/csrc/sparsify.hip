@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "asp_common.hpp"
+#include "sparsify_internal.hpp"
 
 namespace {
 
@@ -83,34 +84,8 @@ __device__ __forceinline__ double pruned_transposed(const GraphArgs &a, uint32_t
   return 0.0;
 }
 
-__device__ __forceinline__ uint32_t find_root(uint32_t *parent, uint32_t x) {
-  uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  while (p != x) {
-    const uint32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (g != p) {  // path halving: only ever replaces a parent by one of its ancestors
-      __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    x = p;
-    p = g;
-  }
-  return x;
-}
-
-__device__ __forceinline__ void unite(uint32_t *parent, uint32_t a, uint32_t b) {
-  a = find_root(parent, a);
-  b = find_root(parent, b);
-  while (a != b) {
-    if (a < b) {
-      const uint32_t t = a;
-      a = b;
-      b = t;
-    }  // a > b: hang the larger root under the smaller
-    const uint32_t seen = atomicCAS(&parent[a], a, b);
-    if (seen == a) return;
-    a = find_root(parent, seen);  // somebody re-rooted a meanwhile
-    b = find_root(parent, b);
-  }
-}
+// (find_root / unite: sparsify_internal.hpp, shared with level_segments.hip)
+using asp::unite;
 
 __global__ __launch_bounds__(kThreads) void k_init_parent(uint32_t *parent, uint64_t n) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
@@ -202,6 +177,8 @@ unsigned grid_for(uint64_t items, uint64_t per_block) {
 thread_local float g_last_ms = 0.0f;
 
 }  // namespace
+
+void asp::set_sparsify_last_ms(float ms) { g_last_ms = ms; }
 
 extern "C" float asp_sparsify_last_ms(void) { return g_last_ms; }
 

@@ -613,3 +613,26 @@ class DeviceOperator:
         _lib.check(self._lib.asp_operator_extend(self._handle, n, _lib.ptr(keys), capacity,
                                                  _lib.ptr(out), ctypes.byref(count)))
         return out[:int(count.value)].copy()
+
+    def extend_segments(self, keys, offsets) -> Tuple[np.ndarray, np.ndarray]:
+        """:meth:`extend` of many key sets in one call, specification ASP-EXTEND-SEG-1:
+        ``offsets`` (u64[G + 1], from 0, non-decreasing) cuts ``keys`` into segments, in any order and
+        with repeats.  ``(states u64, out_offsets u64[G + 1])``: ``states[out_offsets[g]:out_offsets[g + 1]]``
+        is ``extend`` of segment ``g``'s keys."""
+        import ctypes
+
+        _lib = self._lib_module
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        t = keys.shape[0]
+        if keys.ndim != 1 or offsets.ndim != 1 or offsets.shape[0] < 1 or int(offsets[-1]) != t:
+            raise ValueError("offsets should run from 0 to the number of keys")
+        segments = offsets.shape[0] - 1
+        capacity = t * self.max_connections
+        out = np.empty(max(capacity, 1), dtype=np.uint64)
+        out_offsets = np.zeros(segments + 1, dtype=np.uint64)
+        count = ctypes.c_uint64(0)
+        _lib.check(self._lib.asp_operator_extend_segments(
+            self._handle, segments, _lib.ptr(offsets), _lib.ptr(keys), capacity, _lib.ptr(out),
+            _lib.ptr(out_offsets), ctypes.byref(count)))
+        return out[:int(count.value)].copy(), out_offsets

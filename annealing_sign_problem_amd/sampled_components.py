@@ -219,7 +219,8 @@ def process_cluster(cluster, hamiltonian, ground_state, noisy_ground_state, nois
 
 def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, noisy_ground_state,
                    noisy_log_coeff_fn, order: int, global_cutoff: float, jobs: int = 1,
-                   greedy_batch: bool = False, external_field: bool = False, build_batch: bool = False):
+                   greedy_batch: bool = False, external_field: bool = False, build_batch: bool = False,
+                   level_batch: bool = False):
     """First half of :func:`process_clusters_batched`: the models of every order of every cluster,
     each with its greedy result — a list of ``(cluster index, model, exact_signs, weights, result
     so far)`` in cluster order.  The models of a cluster do not depend on its solutions (the
@@ -230,7 +231,9 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
     :func:`process_cluster`.  ``build_batch``: the staging runs level by level — for order i all
     clusters are extended (per cluster), the couplings of ALL their models are built in one segmented
     device call (``common.make_ising_models``) and the models are sparsified (per
-    cluster) — instead of cluster by cluster; the models and the results are the same."""
+    cluster) — instead of cluster by cluster; the models and the results are the same.  ``level_batch``
+    (with ``build_batch``): the extension and the sparsification of a level are ONE segmented device call
+    each as well (``common.extend_and_sparsify_models``); the same models again."""
     basis = hamiltonian.basis
     field = {"external_field": True} if external_field else {}
 
@@ -258,7 +261,10 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
         models = common.make_ising_models(clusters, hamiltonian, log_psi_fn=noisy_log_coeff_fn, **field)
         truth = each(lambda c: exact_signs_and_weights(clusters[c], models[c], ground_state, basis), range(count))
         for i in range(order + 1):
-            if i > 0:
+            if i > 0 and level_batch:
+                models = common.extend_and_sparsify_models(models, noisy_log_coeff_fn, global_cutoff, clusters,
+                                                           **field)
+            elif i > 0:
                 models = common.make_hamiltonian_extensions(models, noisy_log_coeff_fn, **field)
                 models = each(lambda c: common.sparsify_using_global_cutoff(models[c], global_cutoff, clusters[c]),
                               range(count))
@@ -311,6 +317,12 @@ def build_batch_of(args) -> dict:
     return {"build_batch": True} if getattr(args, "build_batch", False) else {}
 
 
+def level_batch_of(args) -> dict:
+    """--level-batch as the ``level_batch`` keyword of :func:`stage_clusters` and
+    :func:`process_clusters_batched`; empty without it, so that every call is the one it was."""
+    return {"level_batch": True} if getattr(args, "level_batch", False) else {}
+
+
 def early_stop_of(args) -> dict:
     """--anneal-patience / --anneal-check-every / --anneal-method as the ``early_stop`` keyword of :func:`anneal_staged`
     and :func:`process_clusters_batched`; empty without them, so that every call is the one it was."""
@@ -358,17 +370,19 @@ def process_clusters_batched(clusters: Sequence[np.ndarray], hamiltonian, ground
                              greedy_batch: bool = False,
                              early_stop: Optional[dict] = None,
                              external_field: bool = False,
-                             build_batch: bool = False) -> List[List[OptimizationResult]]:
+                             build_batch: bool = False,
+                             level_batch: bool = False) -> List[List[OptimizationResult]]:
     """``[process_cluster(c, ...) for c in clusters]`` with the annealing of ALL models — every
     cluster at every order — in one batched device call (:func:`stage_clusters`, then
     :func:`anneal_staged`); the results are identical to the per-cluster loop.  ``early_stop``: the
     extra keywords of :func:`common.solve_ising_models` (early stopping or the annealing method), as in
     :func:`anneal_staged`.  ``external_field``: as in :func:`process_cluster`.  ``build_batch``: as in
-    :func:`stage_clusters`."""
+    :func:`stage_clusters`; ``level_batch`` likewise."""
     staged = stage_clusters(clusters, hamiltonian, ground_state, noisy_ground_state, noisy_log_coeff_fn,
                             order, global_cutoff, jobs, **({"greedy_batch": True} if greedy_batch else {}),
                             **({"external_field": True} if external_field else {}),
-                            **({"build_batch": True} if build_batch else {}))
+                            **({"build_batch": True} if build_batch else {}),
+                            **({"level_batch": True} if level_batch else {}))
     return anneal_staged(staged, clusters, annealing, sweep_order, **({"early_stop": early_stop} if early_stop else {}))
 
 
@@ -422,6 +436,11 @@ def parse_command_line(argv=None):
                              "node.  On ONE GPU it does not pay (the device multiplexes processes at "
                              "a higher cost than the interpreter lock: profiles/r03_pipeline_workers.txt)."
                              "  The output does not depend on it")
+    parser.add_argument("--level-batch", default=False, action="store_true",
+                        help="with --build-batch: extend and sparsify a round of clusters with ONE segmented "
+                             "device call each per order (extend_and_sparsify_models: asp_operator_extend_segments, "
+                             "asp_sparsify_component_segments) instead of one call per cluster; the output is the "
+                             "same")
     parser.add_argument("--greedy-batch", default=False, action="store_true",
                         help="solve the greedy models of a round of --batch clusters with ONE batched "
                              "call (greedy_solve_batch) instead of one greedy_solve per model; the "
@@ -458,6 +477,8 @@ def parse_command_line(argv=None):
                          "segments)".format(args.anneal_method))
     if args.build_batch and (args.batch <= 1 or not (args.annealing or args.greedy_batch)):
         parser.error("--build-batch needs --batch > 1 and --annealing or --greedy-batch (it builds a round at once)")
+    if args.level_batch and not args.build_batch:
+        parser.error("--level-batch needs --build-batch (it batches the rest of a level of the round)")
     return args
 
 
@@ -631,7 +652,8 @@ def _worker_chunk(indices):
                                          w["log_coeff_fn"], args.order, args.global_cutoff, args.annealing,
                                          jobs=args.jobs, sweep_order=args.sweep_order,
                                          **({"greedy_batch": True} if args.greedy_batch else {}),
-                                         **early_stop_of(args), **external_field_of(args), **build_batch_of(args))
+                                         **early_stop_of(args), **external_field_of(args), **build_batch_of(args),
+                                         **level_batch_of(args))
         return report([",".join(r.to_csv_str() for r in columns) for columns in chunk])
 
     def work(cluster):
@@ -841,7 +863,8 @@ def _main_in_group(args, asp_dist, created_group, phase):
                                              ground_state, noisy_ground_state, noisy_log_coeff_fn,
                                              args.order, args.global_cutoff, args.annealing,
                                              jobs=args.jobs, sweep_order=args.sweep_order, **greedy_batch,
-                                             **early_stop_of(args), **external_field_of(args), **build_batch_of(args))
+                                             **early_stop_of(args), **external_field_of(args), **build_batch_of(args),
+                                             **level_batch_of(args))
             lines += [",".join(r.to_csv_str() for r in columns) for columns in chunk]
         return lines
 
@@ -872,7 +895,8 @@ def _main_in_group(args, asp_dist, created_group, phase):
             def stage(some):
                 return stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
                                       noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
-                                      **greedy_batch, **external_field_of(args), **build_batch_of(args))
+                                      **greedy_batch, **external_field_of(args), **build_batch_of(args),
+                                      **level_batch_of(args))
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(stage, my_share(0)) if rounds else None
@@ -926,7 +950,8 @@ def _main_in_group(args, asp_dist, created_group, phase):
                 some = list(itertools.islice(clusters, step))
                 return some, stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
                                             noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
-                                            **greedy_batch, **external_field_of(args), **build_batch_of(args))
+                                            **greedy_batch, **external_field_of(args), **build_batch_of(args),
+                                            **level_batch_of(args))
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(next_round)

@@ -321,6 +321,26 @@ int asp_operator_ising_segments(asp_operator const *op, uint64_t num_segments, u
  * key with a higher bit is refused with ASP_ERR_INVALID before any launch (*count = 0). */
 int asp_operator_extend(asp_operator const *op, uint64_t n, uint64_t const *keys,
                         uint64_t capacity, uint64_t *out, uint64_t *count);
+/* The extension of many clusters in one call, specification ASP-EXTEND-SEG-1: keys
+ * [T = offsets[num_segments]] holds num_segments key sets one after the other, and
+ * out[out_offsets[g] : out_offsets[g + 1]] is what asp_operator_extend(op, n_g, keys + offsets[g], ...)
+ * returns — sorted, unique, for symmetry-adapted bases the representatives without the orbits of norm
+ * 0.  A state may sit in any number of segments and comes out in each of them; keys within a segment
+ * need not be sorted or unique; segments may be empty.  out_offsets is u64[num_segments + 1] from 0
+ * and *count its last entry.  capacity == 0 with out == NULL is the sizing call (*count and
+ * out_offsets set); *count > capacity or a missing out is ASP_ERR_INVALID with both set and out not
+ * written.  Before any launch and before any output is written: ASP_ERR_INVALID for a null handle,
+ * a null count or out_offsets, null offsets with num_segments > 0, offsets[0] != 0 or decreasing
+ * offsets, null keys with T > 0 and a key with a bit at or above number_spins (the message names the
+ * segment and the key); ASP_ERR_TOO_LARGE for T >= 2^32 - 1 and for T * max_connections >= 2^32 (the
+ * bound on the connections that is known before a launch; the exact count is checked after the
+ * counting pass as in asp_operator_extend).  A source key of norm 0 in a -1 sector is refused as in
+ * asp_operator_extend.  T == 0 needs no device: *count = 0 and out_offsets all 0.  The number of
+ * launches and of host synchronisations — TWO for the sizing call, THREE for a full call — does not
+ * depend on num_segments. */
+int asp_operator_extend_segments(asp_operator const *op, uint64_t num_segments, uint64_t const *offsets,
+                                 uint64_t const *keys, uint64_t capacity, uint64_t *out,
+                                 uint64_t *out_offsets, uint64_t *count);
 
 /* Boundary field of a cluster, specification ASP-FIELD-1: the miss branch of the
  * reference's coupling build (cbits/build_matrix.c:49) with counts = 1.  keys[num_spins] ascending
@@ -391,7 +411,40 @@ int asp_sparsify_component(uint64_t num_spins, int64_t const *indptr, int32_t co
                            uint64_t anchor, uint8_t *keep, uint64_t *kept_spins,
                            uint64_t capacity, int64_t *out_indptr, int32_t *out_indices,
                            double *out_data, uint64_t *out_nnz);
-/* Device time (ms) of this thread's last asp_sparsify_component call, copies excluded. */
+/* The cutoff of many clusters in one call, specification ASP-SPARSIFY-SEG-1.  The
+ * input conventions are the OUTPUT conventions of asp_operator_ising_segments: num_segments matrices
+ * lie concatenated, segment g holds the spins [offsets[g], offsets[g + 1]) of T = offsets[num_segments];
+ * indptr is ONE global i64[T + 1] starting at 0; indices are SEGMENT-LOCAL; rows sorted and
+ * duplicate-free, stored zeros legal; is_frozen u8[T]; anchors[g] is local to segment g.  The law: for
+ * every segment g with n_g > 0 let (keep_g, kept_g, ip, c, v) be what asp_sparsify_component returns
+ * for the rebased segment with anchors[g]; then keep[offsets[g] : offsets[g + 1]] == keep_g,
+ * kept_offsets[g + 1] - kept_offsets[g] == kept_g with kept_offsets[0] == 0, the rows kept_offsets[g] ...
+ * kept_offsets[g + 1] of out_indptr, rebased, equal ip, their out_indices equal c (columns renumbered
+ * WITHIN the segment's kept spins) and their out_data equal v bit for bit.  The threshold is PER
+ * SEGMENT: reltol * max|data of segment g|, one rounded product (reltol * 0 for a segment without
+ * non-zeros).  Empty segments are legal and their anchor is not read.
+ * capacity == 0 with out_indptr, out_indices and out_data all NULL is the mask-only call: keep,
+ * kept_offsets and *out_nnz are set.  *out_nnz > capacity or a missing output pointer gives
+ * ASP_ERR_INVALID with keep, kept_offsets and *out_nnz set and no out_* written.  A frozen spin outside
+ * its anchor's component gives ASP_ERR_INVALID, the message naming the FIRST such segment and its
+ * number of stray spins; nothing is written to keep, kept_offsets or out_* then.
+ * Before any device work and before any output is written: ASP_ERR_INVALID for a null kept_offsets or
+ * out_nnz, null offsets or anchors with num_segments > 0, offsets[0] != 0 or decreasing offsets, null
+ * indptr / is_frozen / keep with T > 0, indptr[0] != 0 or a non-monotone indptr, a column outside
+ * [0, n_g), a row that is not sorted and duplicate-free (the message names the segment and the row)
+ * and anchors[g] >= n_g with n_g > 0; ASP_ERR_TOO_LARGE for T >= 2^32 - 1.  T == 0 needs no device:
+ * *out_nnz = 0, kept_offsets[0 ... num_segments] = 0 and out_indptr[0] = 0 when out_indptr is given.
+ * Host pointers; out_indptr needs kept_offsets[num_segments] + 1 entries (T + 1 always suffice).  The
+ * number of launches and of host synchronisations — ONE for the mask-only call, TWO for a full call —
+ * does not depend on num_segments. */
+int asp_sparsify_component_segments(uint64_t num_segments, uint64_t const *offsets,
+                                    int64_t const *indptr, int32_t const *indices, double const *data,
+                                    uint8_t const *is_frozen, double reltol, uint64_t const *anchors,
+                                    uint8_t *keep, uint64_t *kept_offsets, uint64_t capacity,
+                                    int64_t *out_indptr, int32_t *out_indices, double *out_data,
+                                    uint64_t *out_nnz);
+/* Device time (ms) of this thread's last asp_sparsify_component or asp_sparsify_component_segments
+ * call, copies excluded. */
 float asp_sparsify_last_ms(void);
 
 /* ------------------------------------------------------------------------- */
