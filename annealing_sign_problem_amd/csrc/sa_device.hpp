@@ -90,6 +90,32 @@ __device__ __forceinline__ uint32_t spread_mask(uint32_t mask) {
   return ((mask & 0xFu) * 0x00204081u & 0x01010101u) << 7;
 }
 
+// The wide word of the COLOUR sweep carries one more bit per replica.  Byte m is 0x80 * s_m + d_m:
+//   bit 8m + 7 = s_m, replica m's sign bit (all the shuffled sweep keeps, and all any reader of the
+//                current configuration looks at);
+//   bit 8m     = d_m, "replica m's spin here differs from replica m's best configuration".
+// The sign instruction of the k-loop ORs the selected byte with 0x3F into the top byte of the +-1.0
+// multiplier, so bits 0..5 of a byte never reach it (checked below for both values of d_m).  A flip
+// toggles both bits, an improvement of replica m clears d_m at every position, and the best
+// configuration is s_m ^ d_m, materialised once per launch: no copy per improving sweep.
+constexpr uint32_t kWideDiffers = 0x01010101u;  // the d bits
+constexpr uint32_t kWideSigns = 0x80808080u;    // the s bits
+static_assert((0x3Fu | 0x00u) == 0x3Fu && (0x3Fu | 0x01u) == 0x3Fu && (0x3Fu | 0x80u) == 0xBFu &&
+                  (0x3Fu | 0x81u) == 0xBFu,
+              "the top byte of the multiplier is that of +1.0 or -1.0 whatever d_m is");
+// Replica mask (bit m) -> the d bits of those replicas: bits 0..3 to bits 0, 8, 16, 24.
+__device__ __forceinline__ uint32_t differs_mask(uint32_t mask) {
+  return (mask & 0xFu) * 0x00204081u & kWideDiffers;
+}
+// Replica mask -> what a flip of those replicas XORs into the word: s_m and d_m (one v_lshl_or_b32
+// where spread_mask has a shift).
+__device__ __forceinline__ uint32_t flip_mask(uint32_t mask) {
+  const uint32_t t = differs_mask(mask);
+  return (t << 7) | t;
+}
+// Bit 8m + 7 of the result = replica m's sign bit in its BEST configuration, s_m ^ d_m.
+__device__ __forceinline__ uint32_t best_signs(uint32_t word) { return word ^ (word << 7); }
+
 // Spins addressed absolutely in LDS: the kernels check in their prologue that the dynamic LDS
 // block starts at address 0, so a byte or word address of the spin area needs no base add.
 using LdsByte = __attribute__((address_space(3))) const uint8_t;
@@ -100,7 +126,8 @@ using LdsWord = __attribute__((address_space(3))) const uint32_t;
 //           replica m at bit 2m for M <= 4);
 //   kBits:  one bit per position, one replica (8x the capacity);
 //   kWide:  one 32-bit word per position, byte m = 0x80 * sign bit of replica m (M <= 4; fits
-//           up to ~4e4 spins): the +-1.0 multiplier of a term is then ONE SDWA instruction.
+//           up to ~4e4 spins): the +-1.0 multiplier of a term is then ONE SDWA instruction (the colour
+//           sweep: plus bit 0 of the byte, above);
 //   kGlobal: the bit words of kBits kept in HBM (one replica): no LDS limit on the size, every
 //           neighbour gather is an L2 access — the slow path for clusters beyond ~1.3e6 spins.
 //   kNibbles: four bits per position — two positions share a byte — for M <= 4 replicas: twice the

@@ -21,7 +21,8 @@
 //     counter-based Philox4x32-10 word per (spin, sweep, replica) and a fixed-sequence exp reached through
 //     a hardware-exp filter, accepted flips are XOR-ed into LDS;
 //   * the running energy of each replica is tracked exactly in 2^-S fixed point (integer adds commute, so
-//     the parallel reduction is deterministic); the best configuration is snapshotted to HBM per sweep;
+//     the parallel reduction is deterministic); the best configuration is snapshotted to HBM per sweep
+//     (kWide: kept as a difference from the current one in a spare bit of the word, written once);
 //   * frozen sweeps: row sums cached in HBM and re-used while no neighbour of a block flipped (dirty
 //     bytes), blocks whose proposals are all certain rejections skipped outright (inert bytes); or (TAIL)
 //     only the rows listed in a bitmap evaluated, compacted into visits of 64;
@@ -387,6 +388,42 @@ __device__ __forceinline__ void snapshot(const uint8_t *spins, const Args &a, ui
   }
 }
 
+// ---- kWide keeps no copy of the best configuration during the launch: bit 8m of a position's word
+// says whether replica m's spin there differs from its best one (sa_device.hpp).  An anneal that cools
+// improves in nearly every sweep, so nearly every snapshot would be overwritten one sweep later. ----
+// The replicas in `improved` (workgroup-uniform) are at their best: their d bits go, at every position.
+// The whole workgroup, a uint4 per thread and iteration; between the barriers snapshot() runs between.
+__device__ __forceinline__ void clear_differs(uint8_t *spins, uint32_t num_blocks, uint32_t improved) {
+  const uint32_t keep = ~differs_mask(improved);
+  uint4 *words = reinterpret_cast<uint4 *>(spins);
+  for (uint32_t i = threadIdx.x; i < num_blocks * 16u; i += blockDim.x) {
+    uint4 w = words[i];
+    w.x &= keep;
+    w.y &= keep;
+    w.z &= keep;
+    w.w &= keep;
+    words[i] = w;
+  }
+}
+// The best configurations of the replicas in `mask` (workgroup-uniform) from the words, once per launch:
+// snapshot()'s wavefront per block and ballot per replica, over s ^ d.
+template <int M, typename Args>
+__device__ __forceinline__ void materialise_best(const uint8_t *spins, const Args &a, uint32_t group,
+                                                 uint32_t mask) {
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint32_t b = threadIdx.x >> 6; b < a.num_blocks; b += blockDim.x >> 6) {
+    const uint32_t best = best_signs(reinterpret_cast<const uint32_t *>(spins)[b * 64u + lane]);
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      if (!((mask >> m) & 1u)) continue;
+      const uint64_t word = __ballot((best >> (8 * m + 7)) & 1u);
+      if (lane == 0) {
+        a.best_perm[(static_cast<uint64_t>(group) * M + m) * a.num_blocks + b] = word;
+      }
+    }
+  }
+}
+
 // How a descent ends (DESCENT only).  NoEarlyStop: all num_sweeps sweeps run (the annealer; the
 // chunks of asp_sa_greedy, whose host looks at the flip count between chunks).  StopWhenStill:
 // the workgroup leaves after the first sweep that flipped nothing and reports the number of
@@ -485,7 +522,8 @@ constexpr uint32_t kTailRing = 128;  // rows a wavefront stages: under 64 waitin
 //                          not available); ctl[4] and 16 B that nobody uses; global: no spins either
 // spins: 64 (a byte per position), 32 (a nibble), 8 (a bit) or 256 (a word) bytes per block: delta is 64-B aligned.
 // Per replica m: delta[m] = energy change of the running sweep, book[m] = current tracked energy,
-//   book[8 + m] = best, book[16 + m] = accepted flips.  flag: bit m = replica m improved in this sweep.
+//   book[8 + m] = best, book[16 + m] = accepted flips.  flag: bit m = replica m improved in this sweep;
+//   its second word (a segment in words): bit m = replica m improved in this launch.
 // meta[b] = {first ELL slab, width} of block b.  ctl: the CtlSlot words below.
 // dirty[b]: bit m = replica m's cached fields of block b are stale.  inert[b], meaningful while the dirty
 //   byte is clear: at the block's last evaluation every proposal was a certain rejection (beta * dE >= 23
@@ -663,7 +701,8 @@ __device__ __forceinline__ void store_flip(uint8_t *spins, uint32_t p, uint32_t 
       store_word<LAYOUT == kGlobal>(word, load_word<LAYOUT == kGlobal>(word) ^ flips);
     }
   } else if constexpr (LAYOUT == kWide) {
-    if (flip) reinterpret_cast<uint32_t *>(spins)[p] = own ^ spread_mask(flip);
+    // sign and "differs from the best" bit alike (sa_device.hpp)
+    if (flip) reinterpret_cast<uint32_t *>(spins)[p] = own ^ flip_mask(flip);
   } else if constexpr (LAYOUT == kNibbles) {
     // the neighbouring lane owns the other nibble of the byte and may flip in the same
     // instruction: an LDS atomic on the word (eight positions) instead of a byte store
@@ -723,6 +762,8 @@ struct ColourSweep {
   static constexpr bool WIDE = LAYOUT == kWide;
   static constexpr bool NIBBLES = LAYOUT == kNibbles;
   static constexpr bool kLeanBook = M <= 4 && !(Res::kLadder && WIDE);  // see accept()
+  // the best configuration lives in the words' d bits until the epilogue (clear_differs, materialise_best)
+  static constexpr bool kLazyBest = WIDE;
   static_assert(!PACKED || M == 1, "the bit-packed layouts hold one replica");
   static_assert(!NIBBLES || (M <= 4 && !DESCENT), "the nibble layout holds up to four replicas");
   static_assert(!WIDE || (M <= 4 && !DESCENT), "the wide layout holds up to four replicas");
@@ -832,13 +873,15 @@ struct ColourSweep {
     }
     if (tid == 0) {
       *improved_flag = 0;
+      if constexpr (kLazyBest && Res::kEnabled) improved_flag[1] = 0;
       ctl[kCtlFlips] = ctl[kCtlModeOn] = ctl[kCtlModeEntered] = ctl[kCtlTicket] = 0;
       if constexpr (TAIL) ctl[kCtlTailSweeps] = ctl[kCtlTailEntries] = 0;
     }
     __syncthreads();
-    if constexpr (!Res::kEnabled) {
+    if constexpr (!Res::kEnabled && !kLazyBest) {
       // (a segment's best configuration so far is in a.best_perm already and stays unless the segment
-      // improves on it: no initial snapshot)
+      // improves on it: no initial snapshot.  kLazyBest: the start has d = 0 for every replica, it IS
+      // the best so far)
       snapshot<M, LAYOUT>(spins, a, group, (1u << M) - 1u);
       __syncthreads();
     }
@@ -1217,6 +1260,8 @@ struct ColourSweep {
       if (e < book[8 + tid]) {
         book[8 + tid] = e;
         atomicOr(improved_flag, 1u << tid);
+        // (a segment's epilogue writes the best of those that improved at least once in the launch)
+        if constexpr (kLazyBest && Res::kEnabled) atomicOr(improved_flag + 1, 1u << tid);
       }
     }
     __syncthreads();
@@ -1232,8 +1277,13 @@ struct ColourSweep {
       }
       flips_before = flips;
     }
-    const uint32_t improved = DESCENT ? ((1u << M) - 1u) : *improved_flag;
-    if (improved) snapshot<M, LAYOUT>(spins, a, group, improved);
+    if constexpr (kLazyBest) {
+      const uint32_t improved = __builtin_amdgcn_readfirstlane(*improved_flag);
+      if (improved) clear_differs(spins, a.num_blocks, improved);
+    } else {
+      const uint32_t improved = DESCENT ? ((1u << M) - 1u) : *improved_flag;
+      if (improved) snapshot<M, LAYOUT>(spins, a, group, improved);
+    }
     // entering the mode: every block starts stale / every row is listed
     if ((TAIL || cache_available) && ctl[kCtlModeEntered] != 0) {
       if constexpr (TAIL) {
@@ -1262,6 +1312,14 @@ struct ColourSweep {
     }
     if constexpr (DESCENT && Stop::kEnabled) {
       if (tid == 0) *stop.sweeps_done = sweeps_done;
+    }
+    if constexpr (kLazyBest) {
+      // The best configurations, from the words (last written before the final barriers).  A closed call
+      // reports every replica's — one that never improved has d = start against current, its start
+      // configuration —; a segment only those it improved on: the others' stand in a.best_perm already.
+      uint32_t mask = (1u << M) - 1u;
+      if constexpr (Res::kEnabled) mask = __builtin_amdgcn_readfirstlane(improved_flag[1]);
+      materialise_best<M>(spins, a, group, mask);
     }
     if constexpr (Res::kEnabled) {
       // the state the next segment starts from (the spins were last written before the final barriers)
