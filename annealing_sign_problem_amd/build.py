@@ -42,6 +42,9 @@ SOURCES = [
     "greedy.cpp",
     "greedy_tree.hip",
     "sa_sweep.hip",
+    "sa_energy.hip",
+    "sa_anneal.hip",
+    "sa_batch.hip",
     "sa_shuffled.hip",
     "sa_chains.hip",
     "sa_population.hip",
@@ -117,7 +120,9 @@ def fingerprint() -> str:
 # builder that lays out what it reads (with the headers they include).  profiles/sweep_counters.json
 # ties every case to the fingerprint of its set, so that a change to an unrelated kernel file (the
 # coupling build, say) does not void the counters of the sweep kernels, and a change to
-# sa_shuffled.hip voids the shuffled cases only.
+# sa_shuffled.hip voids the shuffled cases only.  The colour order's energy pass (sa_energy.hip) and host
+# drivers (sa_anneal.hip, sa_batch.hip) are in neither set: sa_sweep.hip holds the sweep kernels and every
+# launch decision, and its headers (sa_colour.hpp, sa_colour_kloop.hpp) include none of the three.
 KERNEL_SOURCE_SETS = {
     "colour": ["sa_sweep.hip", "sa_plan.cpp"],
     "shuffled": ["sa_shuffled.hip", "sa_plan.cpp"],

@@ -1,7 +1,10 @@
 // Device helpers that BOTH annealing sweeps use (csrc/sa_sweep.hip: colour order;
 // csrc/sa_shuffled.hip: a fresh order every sweep): the Philox stream, the acceptance rule, the
-// wide spin word and the spin layouts.  What only one sweep uses lives in that sweep's file, so
-// a change to one kernel leaves the other's source-set fingerprint alone (build.KERNEL_SOURCE_SETS).
+// wide spin word and the spin layouts.  What only one sweep uses lives in that sweep's files (the
+// colour order: csrc/sa_sweep.hip with sa_colour.hpp and sa_colour_kloop.hpp), so a change to one kernel
+// leaves the other's source-set fingerprint alone (build.KERNEL_SOURCE_SETS) — and so does a change to
+// the colour order's host drivers (csrc/sa_anneal.hip, csrc/sa_batch.hip) or its energy pass
+// (csrc/sa_energy.hip), which are in neither set.
 // Specification: DESIGN.md §4.3-4.5.  gfx950 only.
 #pragma once
 

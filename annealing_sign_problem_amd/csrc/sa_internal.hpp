@@ -1,5 +1,8 @@
 // The plan object behind asp_sa_plan_create and the host helpers the annealing translation
-// units share (csrc/sa_sweep.hip defines them; csrc/sa_shuffled.hip uses them).
+// units share.  The colour order defines them — csrc/sa_anneal.hip (the plan's device setup, a handle's
+// segment), csrc/sa_energy.hip (permute, energies), csrc/sa_batch.hip (batched segments) —, and
+// csrc/sa_shuffled.hip, csrc/sa_chains.hip and the others use them.  What only the colour order's own
+// units share is in sa_colour.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -170,7 +173,7 @@ inline int check_distinct_plans(const std::vector<asp_sa_chains *> &handles) {
 }
 
 // What asp_sa_plan_create does once p->host is filled — stream, events, device limits and the uploads of
-// the layout —, for asp_sa_plan_clone as well (csrc/sa_sweep.hip).  ASP_OK, or the error recorded; the
+// the layout —, for asp_sa_plan_clone as well (csrc/sa_anneal.hip).  ASP_OK, or the error recorded; the
 // caller destroys the plan.
 int sa_plan_device_setup(asp_sa_plan *p);
 
@@ -225,7 +228,8 @@ uint32_t deal_to_xcds(std::vector<uint32_t> members, WorkOf work_of, GroupsOf gr
 }
 
 // perm[c][b] = sign words (bit = 1: s = -1) of configuration c in the plan's block order, from
-// packed original-order configurations x[c][ceil(K/64)] (bit = 1: s = +1); on the plan's stream.
+// packed original-order configurations x[c][ceil(K/64)] (bit = 1: s = +1); on the plan's stream
+// (csrc/sa_energy.hip, as the next).
 int sa_permute_bits(asp_sa_plan *p, const uint64_t *x, uint32_t count, uint64_t *perm);
 
 // Reported energies of `count` configurations given as block-order sign words;
@@ -240,7 +244,7 @@ int sa_shuffled_batch(asp_sa_batch_item const *items, const uint32_t *which, uin
 // One segment of asp_sa_chains_advance (arguments validated, num_sweeps > 0, a plan with spins):
 // sweeps c->sweeps_done .. + num_sweeps - 1 from and into the handle's state; c->sweeps_done is the
 // caller's to advance.  trace: nullptr or HOST [repetitions][num_sweeps + 1], entries 1.. written here.
-// Colour order (csrc/sa_sweep.hip) and shuffled order (csrc/sa_shuffled.hip).
+// Colour order (csrc/sa_anneal.hip; the kernels: csrc/sa_sweep.hip) and shuffled order (csrc/sa_shuffled.hip).
 int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace);
 int sa_chains_advance_shuffled(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace);
 
@@ -265,7 +269,7 @@ struct ChainsSegment {
   int64_t *trace;  // nullptr, or HOST [repetitions][num_sweeps + 1]: the segment runs alone
   double const *chain_betas = nullptr;  // a ladder segment: one inverse temperature per chain
 };
-int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms);
+int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms);  // csrc/sa_batch.hip
 int sa_chains_advance_shuffled_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms);
 
 }  // namespace asp

@@ -3285,7 +3285,7 @@ int segment_alone(asp_sa_chains *c, double const *betas, double const *chain_bet
 
 namespace asp {
 
-// The shuffled items of asp_sa_anneal_batch (csrc/sa_sweep.hip): every item is exactly its own
+// The shuffled items of asp_sa_anneal_batch (csrc/sa_batch.hip): every item is exactly its own
 // asp_sa_anneal_shuffled call.  Items are grouped by their number of sweeps; the problems of a
 // group share launches (run_shuffled_group), a group of one continues as the single-problem call does,
 // with the batch's choices.

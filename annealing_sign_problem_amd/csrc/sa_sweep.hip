@@ -34,57 +34,35 @@
 // gets (for_replica_words), when a proposal needs a draw (ColourSweep::accept, both visits'), when the
 // field cache or tail mode is entered and left (end_of_sweep_mode).
 // f64-VALU- and vector-memory-bound integer+f64 work: no MFMA.
+//
+// This file holds the sweep kernels and, behind them, every decision about which kernel runs in which
+// shape: the form table and the kernel families, the LDS sizes, choose_colour_launch, the team size, the
+// cache and tail thresholds, the class rule of the shared launches and sweep_args — what a profiler
+// counter of k_sa_sweep* can depend on (build.KERNEL_SOURCE_SETS["colour"]).  What only allocates,
+// copies, validates or records is host code elsewhere: csrc/sa_anneal.hip (plan, closed calls, segments),
+// csrc/sa_batch.hip (shared launches); the pass after the sweeps is csrc/sa_energy.hip.  The argument
+// types and the prototypes: sa_colour.hpp.
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cmath>
-#include <cstdlib>
 #include <initializer_list>
-#include <memory>
-#include <mutex>
-#include <numeric>
 #include <type_traits>
 #include <vector>
 
 #include "asp_common.hpp"
-#include "greedy.hpp"
+#include "sa_colour.hpp"
+#include "sa_colour_kloop.hpp"
 #include "sa_device.hpp"
 #include "sa_internal.hpp"
 #include "sa_plan.hpp"
 
 namespace {
 
-using asp::DeviceBuffer;
 using asp::kDummySpin;
-using asp::upload_vector;
 using namespace asp::dev;  // Philox, the accept filter, the spin layouts (sa_device.hpp)
+using namespace asp::colour;  // the kernels' argument types, SweepLds (sa_colour.hpp); the k-loop (sa_colour_kloop.hpp)
 
 constexpr int kMaxThreads = 1024;  // launch bound of the sweep kernel (VGPR budget = 512 / waves per SIMD)
 constexpr int kTeamSleep = 4;  // s_sleep argument between two polls of the team barrier (0/1/4/16/64 scanned)
-
-struct SweepArgs {
-  const uint32_t *color_block_start;  // num_colors + 1
-  const uint32_t *block_width;        // num_blocks
-  const uint64_t *ell_off;            // num_blocks + 1 (slabs)
-  const uint32_t *ell_col;
-  const double *ell_val;
-  const uint32_t *spin_of_pos;  // num_blocks * 64
-  const double *field_pos;      // num_blocks * 64
-  const double *betas;          // num_sweeps
-  const uint64_t *x0_perm;      // num_blocks sign-bit words or nullptr
-  uint64_t *best_perm;          // [groups * M][num_blocks] sign-bit words
-  long long *tracked;           // [groups * M] best tracked energy (fixed point)
-  unsigned long long *accepted;  // [groups * M] accepted flips
-  uint64_t seed;
-  double scale;  // 2^S
-  uint32_t num_colors, num_blocks, num_sweeps, replica_first;
-  // Field cache (nullptr = off): [group][block][m][lane] local fields (the row sums `acc`) of the
-  // last evaluation of every block, valid while the block's dirty byte in LDS is clear.
-  double *field_cache;
-  uint32_t cache_enter_flips;  // switch the cache on after a sweep with fewer flips than this
-  uint64_t *spin_words;        // kGlobal: [groups][num_blocks] sign-bit words in HBM
-  long long *trace;            // nullptr or [groups * M][num_sweeps + 1] tracked energy per sweep
-};
 
 // One 64-spin word of the bit-packed layouts; device-scope accesses when it lives in HBM and
 // other wavefronts of the workgroup read it after the colour barrier.
@@ -103,12 +81,6 @@ __device__ __forceinline__ void store_word(uint64_t *p, uint64_t v) {
   } else {
     *p = v;
   }
-}
-
-// v with its sign flipped when bit 0 of `neg` is set (energy kernel, not hot).
-__device__ __forceinline__ double signed_coupling(double v, uint32_t neg, int m) {
-  const unsigned long long flip = static_cast<unsigned long long>((neg >> m) & 1u) << 63;
-  return __longlong_as_double(__double_as_longlong(v) ^ static_cast<long long>(flip));
 }
 
 __device__ __forceinline__ long long wave_sum_i64(long long v) {
@@ -140,190 +112,10 @@ __device__ __forceinline__ unsigned long long wave_sum_lane63_u64(unsigned long 
   return v;
 }
 
-// Butterfly sum over the 64 lanes; every lane ends with the balanced-tree total
-// ((v0+v1)+(v2+v3))+... (f64 addition commutes, so all lanes agree bitwise).
-__device__ __forceinline__ double wave_tree_sum_f64(double v) {
-#pragma unroll
-  for (int step = 1; step < 64; step <<= 1) v = __dadd_rn(v, __shfl_xor(v, step, 64));
-  return v;
-}
-
 // Collect bit m of each of the four bytes of d into a nibble (byte 0 -> bit 0).
 __device__ __forceinline__ uint32_t gather_bit4(uint32_t d, int m) {
   const uint32_t t = (d >> m) & 0x01010101u;
   return ((t * 0x00204081u) >> 21) & 0xFu;
-}
-
-// kBytes with M <= 4 keeps replica m at bit 2m of the spin byte (the odd bits stay 0); M = 8
-// fills the byte and keeps bit m.  With the even bits the high word of the term's +-1.0 is
-//   (byte << (31 - 2m)) | 0x3FF00000   (one v_lshl_or_b32)
-// for every m: bit 2m lands on bit 31, the higher replica bits leave the word, the lower ones
-// land on bits 29, 27 or 25 (already 1 in 0x3FF00000) and bit 30 receives an odd bit, always 0.
-// With bit m = replica m that shift drags replica m - 1 into bit 30.  Replica MASKS (flip, the
-// dirty and inert bytes, snapshot's `mask`) stay indexed by replica; encode_replicas() turns
-// one into spin-byte bits where it meets the byte.
-template <int M, int LAYOUT>
-constexpr bool kEvenBits = LAYOUT == kBytes && M <= 4;
-
-template <int M, int LAYOUT>
-__device__ __forceinline__ constexpr int replica_bit(int m) {
-  return kEvenBits<M, LAYOUT> ? 2 * m : m;
-}
-
-template <int M, int LAYOUT>
-__device__ __forceinline__ uint32_t encode_replicas(uint32_t mask) {
-  if constexpr (kEvenBits<M, LAYOUT>) {
-    return (mask & 1u) | ((mask & 2u) << 1) | ((mask & 4u) << 2) | ((mask & 8u) << 3);
-  } else {
-    return mask;
-  }
-}
-
-// +-1.0 with the sign taken from replica m's bit of a neighbour's spin byte (1 -> -1.0).
-// acc = fma(v, +-1.0, acc) is bit-identical to acc + (+-v): the product is exact, so the only
-// rounding is the add's; the low dword of the multiplier is a constant zero.
-//   even-bit bytes: one v_lshl_or_b32 (above) that the compiler schedules (plain C++: no inline
-//     asm, so no hazard padding);
-//   bit m (bytes at M = 8, nibbles, bits): replica m's bit to bit 0 with a RIGHT shift — a plain
-//     VOP2, 2.5 SIMD cycles per wave64 on this chip, where every left shift and every VOP3 costs
-//     4.3-4.4 (profiles/r02_issue_rate_probe.txt) — then the m = 0 instruction.
-template <int M, int LAYOUT>
-__device__ __forceinline__ double spin_factor(uint32_t spin_byte, int m) {
-  uint32_t hi;
-  if constexpr (kEvenBits<M, LAYOUT>) {
-    hi = (spin_byte << (31 - 2 * m)) | 0x3FF00000u;
-  } else if (m == 0) {
-    hi = (spin_byte << 31) | 0x3FF00000u;  // v_lshl_or_b32: nothing but bit 0 survives the shift
-  } else {
-    const uint32_t down = spin_byte >> m;
-    asm("v_lshl_or_b32 %0, %1, 31, %2" : "=v"(hi) : "v"(down), "s"(0x3FF00000u));
-  }
-  return __hiloint2double(static_cast<int>(hi), 0);
-}
-
-// kWide: byte m of `word` (0x00 / 0x80) OR 0x3F becomes byte 3 of `hi`, whose lower three bytes
-// keep 0xF00000 — i.e. hi = high word of +1.0 or -1.0 — in one v_or_b32_sdwa (byte select on
-// the source, byte-3 write with the rest preserved).  Two VALU ops per (term, replica)
-// instead of three.
-__device__ __forceinline__ double wide_factor(uint32_t word, int m, uint32_t &hi) {
-  const uint32_t top = 0x3Fu;
-  switch (m) {
-    case 0:
-      asm("v_or_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD "
-          "src1_sel:BYTE_0" : "+v"(hi) : "v"(top), "v"(word));
-      break;
-    case 1:
-      asm("v_or_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD "
-          "src1_sel:BYTE_1" : "+v"(hi) : "v"(top), "v"(word));
-      break;
-    case 2:
-      asm("v_or_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD "
-          "src1_sel:BYTE_2" : "+v"(hi) : "v"(top), "v"(word));
-      break;
-    default:
-      asm("v_or_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD "
-          "src1_sel:BYTE_3" : "+v"(hi) : "v"(top), "v"(word));
-      break;
-  }
-  return __hiloint2double(static_cast<int>(hi), 0);
-}
-
-// The SDWA of wide_factor rewrites the top byte of a multiplier held as a whole f64 whose low
-// word stays 0 for the whole anneal (rebuilt from `hi` and a literal 0, as wide_factor returns
-// it, the pair was re-assembled and low words re-zeroed inside the k-loop).
-__device__ __forceinline__ double wide_factor_held(uint32_t word, int m, double &mult) {
-  uint32_t hi = static_cast<uint32_t>(__double2hiint(mult));
-  wide_factor(word, m, hi);
-  mult = __hiloint2double(static_cast<int>(hi), __double2loint(mult));
-  return mult;
-}
-
-// Four consecutive ELL entries of one lane (one row), k = 4q .. 4q+3.
-struct Quad {
-  uint4 c;
-  double2 v01, v23;
-};
-
-// Three 16-byte loads per lane through pointers (the team kernel); quad index `quad` is relative
-// to the block's first quad.
-__device__ __forceinline__ void load_quad(Quad &q, const uint4 *__restrict__ cptr,
-                                          const double2 *__restrict__ vptr, uint32_t quad) {
-  q.c = cptr[quad * 64u];
-  q.v01 = vptr[quad * 128u];
-  q.v23 = vptr[quad * 128u + 64u];
-}
-
-// The ELL stream of one block through BUFFER loads: the resource's base is the block's first
-// quad (scalar, set up once per visit), the quad is a scalar offset (quad * 1024 B of columns,
-// quad * 2048 B of values) and the lane part a vector offset fixed for the whole kernel, so a
-// quad costs no vector address arithmetic.  Offsets are relative to the block, so any plan size
-// fits the 32-bit offsets.  `cptr`: the lane's columns through a plain pointer, for the dirty
-// marking that re-reads them after a flip.
-using BufferRsrc = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ BufferRsrc block_rsrc(const void *base) {
-  // raw buffer, 4 GiB range, gfx9 DATA_FORMAT word
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0xFFFFFFFF, 0x00020000);
-}
-struct BlockStream {
-  const uint4 *cptr;
-  BufferRsrc col, val;
-  uint32_t lane16;  // lane * 16
-};
-
-__device__ __forceinline__ void load_quad(Quad &q, const BlockStream &s, uint32_t quad) {
-  q.c = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(s.col, s.lane16, quad * 1024u, 0));
-  q.v01 = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(s.val, s.lane16, quad * 2048u, 0));
-  q.v23 = __builtin_bit_cast(double2,
-                             __builtin_amdgcn_raw_buffer_load_b128(s.val, s.lane16 + 1024u, quad * 2048u, 0));
-}
-
-// The row sums of one quad: the four neighbours' spins are gathered, then neighbour-major FMAs
-// (consecutive FMAs go to different accumulators; each acc[m] still receives its terms in
-// ascending k).  `mult`: kWide's held multipliers (wide_factor_held), untouched by the others.
-template <int M, int LAYOUT>
-__device__ __forceinline__ void accumulate(const Quad &q, const uint8_t *spins, double (&acc)[M],
-                                           double (&mult)[4]) {
-  const uint32_t cs[4] = {q.c.x, q.c.y, q.c.z, q.c.w};
-  const double vs[4] = {q.v01.x, q.v01.y, q.v23.x, q.v23.y};
-  uint32_t s[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if constexpr (LAYOUT == kBytes) {
-      // even-bit bytes and bytes at M = 8: the spin bytes start at LDS address 0 (checked in the
-      // kernel prologue), so a position IS its LDS address — no base add in front of every
-      // ds_read_u8
-      s[j] = *reinterpret_cast<LdsByte *>(static_cast<uintptr_t>(cs[j]));
-    } else if constexpr (LAYOUT == kWide) {
-      // columns of the wide plan are LDS byte addresses (position * 4)
-      s[j] = *reinterpret_cast<LdsWord *>(static_cast<uintptr_t>(cs[j]));
-    } else if constexpr (LAYOUT == kNibbles) {
-      // position c: byte c / 2, nibble c % 2; the bits above replica m's are ignored by spin_factor
-      const uint32_t byte = *reinterpret_cast<LdsByte *>(static_cast<uintptr_t>(cs[j] >> 1));
-      s[j] = byte >> ((cs[j] & 1u) << 2);
-    } else if constexpr (LAYOUT == kBits) {
-      const uint32_t *words = reinterpret_cast<const uint32_t *>(spins);
-      s[j] = (words[cs[j] >> 5] >> (cs[j] & 31u)) & 1u;
-    } else {
-      static_assert(LAYOUT == kGlobal, "spins are LDS bytes, words, nibbles or bits, or bits in HBM");
-      // words written by other wavefronts of the workgroup during earlier colour steps: read at
-      // device scope (past the CU's vector L1)
-      const uint32_t *words = reinterpret_cast<const uint32_t *>(spins);
-      const uint32_t w = __hip_atomic_load(words + (cs[j] >> 5), __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-      s[j] = (w >> (cs[j] & 31u)) & 1u;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      if constexpr (LAYOUT == kWide) {
-        acc[m] = __builtin_fma(vs[j], wide_factor_held(s[j], m, mult[m & 3]), acc[m]);
-      } else {
-        acc[m] = __builtin_fma(vs[j], spin_factor<M, LAYOUT>(s[j], m), acc[m]);
-      }
-    }
-  }
 }
 
 // What snapshot() reads of its arguments, for another target than the best words: the final words of a
@@ -436,41 +228,6 @@ struct StopWhenStill {
   uint32_t *sweeps_done;  // this problem's word
 };
 
-// How a launch starts and ends.  NoResume: the closed calls — a fresh chain (one shared x0 or the
-// counter RNG, tracked energy 0, sweep index 0) whose final state is dropped.  Resume: one segment of
-// an asp_sa_chains handle — every chain starts from its OWN sign words, the
-// tracked energy, the best threshold and the flip count start from carried values (a.tracked and
-// a.accepted are read before they are written), sweep t of the launch draws with sweep index t0 + t,
-// and the final configuration and tracked energy are stored beside the best ones.  All of it at the
-// head and the tail of the launch; a template parameter, so the closed calls' instantiations stay
-// what they were.
-struct NoResume {
-  static constexpr bool kEnabled = false;
-  static constexpr bool kLadder = false;
-};
-struct Resume {
-  static constexpr bool kEnabled = true;
-  static constexpr bool kLadder = false;
-  uint64_t *cur_perm;  // [groups * M][num_blocks] sign-bit words: start of every chain in, final state out
-  long long *e_cur;    // [groups * M] current tracked energy, in and out
-  uint32_t t0;         // sweeps the chains have behind them
-};
-// ResumeLadder: a Resume segment in which every chain runs at its OWN inverse temperature, constant
-// over the segment (asp_sa_chains_advance_ladder, DESIGN.md §4.10 "Ladder law"): a.betas is never
-// read, replica m of the group reads chain_betas once before the sweep loop.  The inert bytes stay
-// valid inside the segment — a certain rejection of replica m was certain at replica m's beta, which
-// does not change — and nothing is carried in from the segment before (which may have run colder):
-// the control words, the dirty and the inert bytes live in LDS and are set up by every launch, cached mode is
-// entered with every block stale, and an inert byte is only read for a block evaluated since.
-struct ResumeLadder {
-  static constexpr bool kEnabled = true;
-  static constexpr bool kLadder = true;
-  uint64_t *cur_perm;
-  long long *e_cur;
-  uint32_t t0;
-  const double *chain_betas;  // [groups * M]; the chains padding the last group: 0
-};
-
 // The inverse temperature of replica m: the sweep's shared one, or (ResumeLadder) the replica's own —
 // workgroup-uniform, so scalar registers.  One or two replicas read theirs once before the sweep loop
 // and hold them.  Four and eight read them where they are used, once per visit of a block (scalar loads
@@ -505,60 +262,6 @@ struct LadderBetas<M, true> {
   }
 };
 
-// What the TAIL form of the body takes beside SweepArgs (k_sa_sweep_tail; a wrapper would change the
-// descriptor stride of the batched kernels, so it travels as a kernel argument of its own).
-struct TailArgs {
-  uint32_t enter_flips;  // tail sweeps after a sweep with fewer flips of the workgroup than this
-  uint32_t *report;      // [groups][2]: sweeps run as tail sweeps, entries into tail mode
-};
-constexpr uint32_t kTailRing = 128;  // rows a wavefront stages: under 64 waiting plus one block's 64
-
-// ---- The dynamic LDS of a one-workgroup colour sweep: the byte offset of every region, for the device
-// body's pointers, and the total, for the host (sweep_lds_bytes).  A region is added in this one place. ----
-//   spins | delta[8] | book[24] | flag (16 B) | meta[num_blocks] | ctl ...
-//   bytes, words, nibbles: ... ctl[4] | dirty[num_blocks] | inert[num_blocks]   (each rounded up to 16 B)
-//   TAIL (bytes, words):   ... ctl[8] | todo[num_blocks] | kTailRing staged rows per wavefront
-//   bits, global:          no meta (block metadata comes from HBM by scalar loads, the field cache is
-//                          not available); ctl[4] and 16 B that nobody uses; global: no spins either
-// spins: 64 (a byte per position), 32 (a nibble), 8 (a bit) or 256 (a word) bytes per block: delta is 64-B aligned.
-// Per replica m: delta[m] = energy change of the running sweep, book[m] = current tracked energy,
-//   book[8 + m] = best, book[16 + m] = accepted flips.  flag: bit m = replica m improved in this sweep;
-//   its second word (a segment in words): bit m = replica m improved in this launch.
-// meta[b] = {first ELL slab, width} of block b.  ctl: the CtlSlot words below.
-// dirty[b]: bit m = replica m's cached fields of block b are stale.  inert[b], meaningful while the dirty
-//   byte is clear: at the block's last evaluation every proposal was a certain rejection (beta * dE >= 23
-//   -> expneg = 0, or dE >= 0 in descent mode) and beta has not decreased since: the visit can be skipped.
-// todo[b] (a u64): bit l = row l of block b is evaluated at the next visit of its colour.
-struct SweepLds {
-  uint32_t delta = 0, book = 0, flag = 0, meta = 0, ctl = 0, dirty = 0, inert = 0, todo = 0, ring = 0, total = 0;
-  __host__ __device__ constexpr SweepLds(uint32_t num_blocks, int layout, bool tail, uint32_t waves) {
-    const bool packed = layout == kBits || layout == kGlobal;
-    const uint32_t per_block =
-        layout == kGlobal ? 0u : (layout == kBits ? 8u : (layout == kWide ? 256u : (layout == kNibbles ? 32u : 64u)));
-    delta = num_blocks * per_block;
-    book = delta + 8u * 8u;
-    flag = book + 24u * 8u;
-    meta = flag + 16u;
-    ctl = meta + (packed ? 0u : num_blocks * 8u);
-    if (tail) {
-      todo = ctl + 8u * 4u;
-      ring = todo + num_blocks * 8u;
-      total = ring + waves * kTailRing * 4u;
-    } else if (packed) {
-      total = ctl + 32u;
-    } else {
-      const uint32_t bytes16 = (num_blocks + 15u) & ~15u;
-      dirty = ctl + 4u * 4u;
-      inert = dirty + bytes16;
-      total = inert + bytes16;
-    }
-  }
-};
-static_assert(SweepLds(1, kBytes, false, 0).total == 392 && SweepLds(17, kBytes, false, 0).total == 1576 &&
-                  SweepLds(17, kWide, false, 0).total == 4840 && SweepLds(17, kNibbles, false, 0).total == 1032 &&
-                  SweepLds(17, kBits, false, 0).total == 440 && SweepLds(17, kGlobal, false, 0).total == 304 &&
-                  SweepLds(17, kBytes, true, 16).total == 9856 && SweepLds(17, kWide, true, 8).total == 9024,
-              "the LDS totals of the sweep kernels");
 // The words of ctl.  One mode per kernel: the field cache, or (TAIL) tail sweeps.
 enum CtlSlot : uint32_t {
   kCtlFlips = 0,        // flips of the workgroup in the running sweep
@@ -1370,52 +1073,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_resume(SweepArgs a, Re
   sa_sweep_body<M, false, LAYOUT, SweepArgs, NoEarlyStop, Res>(a, blockIdx.x, NoEarlyStop{}, r);
 }
 
-// Many PROBLEMS in one launch (asp_sa_anneal_batch): workgroup -> (problem, group of M replicas)
-// through a slot table, the problem's SweepArgs through a descriptor table in HBM (scalar
-// loads: the slot is workgroup-uniform).  Slots are laid out per XCD — workgroup i runs on XCD
-// i mod 8 — so that the groups of one problem share that XCD's L2 copy of its couplings, and in
-// descending order of work inside an XCD (longest first, the tail stays short).  Every chain is
-// bit-identical to the one its own single-problem launch produces: the body is the same and
-// results never depend on the launch geometry.
-struct BatchSlot {
-  uint32_t problem;  // 0xFFFFFFFF: padding slot
-  uint32_t group;
-};
-template <typename Problem>  // SweepArgs, or one of the wrappers below
-struct BatchArgs {
-  const Problem *problems;
-  const BatchSlot *slots;  // [8][slots_per_xcd]
-  uint32_t slots_per_xcd;
-};
-
-// What a launch needs beyond SweepArgs lives in a wrapper, so that SweepArgs — shared by every
-// annealing kernel, whose register assignment follows its layout — stays as it is.
-//
-// Many DESCENTS in one launch (asp_sa_greedy_batch): every problem is one chain, so its group is
-// always 0.  Each problem starts from its own configuration (s.x0_perm), runs strict-descent sweeps
-// until one flips nothing or s.num_sweeps (the caller's max_sweeps) are done — decided by the workgroup
-// that owns the whole chain, with no host round trip — and leaves the number of sweeps in its own word.
-struct DescentProblem {
-  SweepArgs s;            // betas: nullptr (never read); num_sweeps: the cap; trace: nullptr
-  const uint64_t *x0;     // the tree's configuration, packed in original order (bit = +1)
-  uint64_t *x0_perm;      // = s.x0_perm, written by k_permute_bits_problems
-  uint32_t *sweeps_done;  // sweeps performed
-};
-// Many SEGMENTS in one launch (asp_sa_chains_advance_batch, order 0): every handle's SweepArgs and its
-// Resume part (its own sign words, tracked energies and sweep index base).  Every chain is the one
-// k_sa_sweep_resume advances: the body is the same.
-struct ResumeProblem {
-  SweepArgs s;  // trace: nullptr (a traced segment runs alone)
-  Resume r;
-};
-// Many LADDER segments in one launch (asp_sa_chains_advance_ladder_batch, order 0): chain_betas points
-// at the handle's [groups * M] values inside the batch's one concatenated buffer (the chains padding a
-// last group: 0).
-struct LadderProblem {
-  SweepArgs s;  // betas: nullptr (never read); trace: nullptr (a traced segment runs alone)
-  ResumeLadder r;
-};
-
+// Many problems in one launch, by descriptor (BatchArgs, sa_colour.hpp).
 template <int M, int LAYOUT, typename Problem>
 __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_batch(BatchArgs<Problem> b) {
   const BatchSlot slot = b.slots[(blockIdx.x & 7u) * b.slots_per_xcd + (blockIdx.x >> 3)];
@@ -1452,26 +1110,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_sa_sweep_batch(BatchArgs<Proble
 // summed over the team through parity-buffered atomics.  All workgroups must be resident together
 // (the launcher keeps the grid within the CU count and serialises team launches); the barrier
 // carries a watchdog so that neither a bug nor a busy device can hang the GPU — on a timeout
-// the call is repeated without teams.  Chains are bit-identical to k_sa_sweep's.
-
-// team launches of the process that the barrier's watchdog cut short (asp_sa_team_watchdog_trips)
-std::atomic<uint64_t> g_team_watchdog_trips{0};
-
-struct TeamArgs {
-  SweepArgs s;
-  uint32_t team_size;            // G
-  uint32_t num_teams;            // = chains of the launch
-  unsigned long long *arrivals;  // [num_teams] barrier counters (monotone)
-  uint64_t *flips;               // [num_teams][num_blocks] flip words of the running colour step
-  long long *sums;               // [num_teams][3 rotating slots][2] {dq, accepted} of a sweep
-  uint32_t *abort;               // set by the watchdog
-  uint32_t spin_limit;           // barrier polls before the watchdog gives up
-};
-
-// Barrier polls before the watchdog gives up and the call is repeated without teams: ~ 5 s (a
-// barrier normally completes in ~ 5 us; members can only be kept waiting by other kernels
-// holding compute units — team launches themselves take turns).
-constexpr uint32_t kTeamSpinLimit = 1u << 22;
+// the call is repeated without teams.  Chains are bit-identical to k_sa_sweep's.  (TeamArgs: sa_colour.hpp.)
 
 __device__ __forceinline__ void team_barrier(const TeamArgs &ta, unsigned long long *counter,
                                              unsigned long long &target) {
@@ -1750,428 +1389,10 @@ __global__ __launch_bounds__(1024) void k_sa_sweep_team(TeamArgs ta) {
   }
 }
 
-// ---------------------------------------------------------------------------
-// Energy of packed configurations: E = D + T, T = radix-64
-// pairwise tree over the blocks of t_p = s_p (A_p . s / 2 + h_p).
-// ---------------------------------------------------------------------------
-
-struct EnergyArgs {
-  const uint32_t *block_width;
-  const uint64_t *ell_off;
-  const uint32_t *ell_col;
-  const double *ell_val;
-  const double *field_pos;
-  const uint64_t *perm_words;  // [count][num_blocks] sign bits
-  double *partial;             // [count][num_blocks]
-  uint32_t num_blocks;
-};
-
-// STAGED: the configuration's sign words are copied to LDS first; otherwise (more blocks than the
-// LDS holds) they are gathered from HBM/L2 directly.
-template <bool STAGED>
-__device__ __forceinline__ void energy_blocks_body(const EnergyArgs &a, const uint32_t r) {
-  extern __shared__ __align__(16) uint8_t lds[];
-  const uint64_t *mine = a.perm_words + static_cast<uint64_t>(r) * a.num_blocks;
-  const uint64_t *bits = mine;
-  if constexpr (STAGED) {
-    uint64_t *staged = reinterpret_cast<uint64_t *>(lds);
-    for (uint32_t w = threadIdx.x; w < a.num_blocks; w += blockDim.x) staged[w] = mine[w];
-    __syncthreads();
-    bits = staged;
-  }
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t waves = blockDim.x >> 6;
-  for (uint32_t b = threadIdx.x >> 6; b < a.num_blocks; b += waves) {
-    const uint32_t quads = a.block_width[b] >> 2;
-    const uint64_t first_quad = a.ell_off[b] >> 2;
-    const uint4 *cptr = reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u + lane;
-    const double2 *vptr = reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u + lane;
-    double acc = 0.0;
-    for (uint32_t q = 0; q < quads; ++q) {
-      const uint4 c = cptr[q * 64u];
-      const double2 v01 = vptr[q * 128u];
-      const double2 v23 = vptr[q * 128u + 64u];
-      const uint32_t cs[4] = {c.x, c.y, c.z, c.w};
-      const double vs[4] = {v01.x, v01.y, v23.x, v23.y};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint32_t neg = static_cast<uint32_t>((bits[cs[j] >> 6] >> (cs[j] & 63u)) & 1ull);
-        acc = __dadd_rn(acc, signed_coupling(vs[j], neg, 0));
-      }
-    }
-    const double g = __dadd_rn(__dmul_rn(0.5, acc), a.field_pos[b * 64u + lane]);
-    const bool negative = (bits[b] >> lane) & 1ull;
-    const double total = wave_tree_sum_f64(negative ? -g : g);
-    if (lane == 0) a.partial[static_cast<uint64_t>(r) * a.num_blocks + b] = total;
-  }
-}
-
-template <bool STAGED>
-__global__ __launch_bounds__(512) void k_sa_energy_blocks(EnergyArgs a) {
-  energy_blocks_body<STAGED>(a, blockIdx.x);
-}
-
-// R configurations per workgroup: every coupling quad is loaded once and applied to the R staged
-// configurations (the chains of one call share the ELL: R times less load traffic than one
-// configuration per workgroup).  Per configuration the arithmetic — and so the bits — are those
-// of energy_blocks_body.
-template <int R>
-__global__ __launch_bounds__(512) void k_sa_energy_blocks_multi(EnergyArgs a, uint32_t count) {
-  extern __shared__ __align__(16) uint8_t lds[];
-  uint64_t *staged = reinterpret_cast<uint64_t *>(lds);  // [R][num_blocks]
-  const uint32_t r0 = blockIdx.x * R;
-  const uint32_t live = count - r0 < static_cast<uint32_t>(R) ? count - r0 : R;
-  const uint64_t *rows = a.perm_words + static_cast<uint64_t>(r0) * a.num_blocks;
-  for (uint32_t w = threadIdx.x; w < live * a.num_blocks; w += blockDim.x) staged[w] = rows[w];
-  __syncthreads();
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t waves = blockDim.x >> 6;
-  for (uint32_t b = threadIdx.x >> 6; b < a.num_blocks; b += waves) {
-    const uint32_t quads = a.block_width[b] >> 2;
-    const uint64_t first_quad = a.ell_off[b] >> 2;
-    const uint4 *cptr = reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u + lane;
-    const double2 *vptr = reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u + lane;
-    double acc[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) acc[k] = 0.0;
-    for (uint32_t q = 0; q < quads; ++q) {
-      const uint4 c = cptr[q * 64u];
-      const double2 v01 = vptr[q * 128u];
-      const double2 v23 = vptr[q * 128u + 64u];
-      const uint32_t cs[4] = {c.x, c.y, c.z, c.w};
-      const double vs[4] = {v01.x, v01.y, v23.x, v23.y};
-      const uint32_t *halves = reinterpret_cast<const uint32_t *>(staged);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint32_t word = cs[j] >> 5, bit = cs[j] & 31u;  // 32-bit halves: ds_read_b32
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-          // (rows beyond `live` hold stale LDS: their sums are computed and never stored)
-          const uint32_t neg = (halves[k * 2u * a.num_blocks + word] >> bit) & 1u;
-          acc[k] = __dadd_rn(acc[k], signed_coupling(vs[j], neg, 0));
-        }
-      }
-    }
-    const double field = a.field_pos[b * 64u + lane];
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      if (static_cast<uint32_t>(k) >= live) break;  // workgroup-uniform
-      const double g = __dadd_rn(__dmul_rn(0.5, acc[k]), field);
-      const bool negative = (staged[k * a.num_blocks + b] >> lane) & 1ull;
-      const double total = wave_tree_sum_f64(negative ? -g : g);
-      if (lane == 0) a.partial[static_cast<uint64_t>(r0 + k) * a.num_blocks + b] = total;
-    }
-  }
-}
-
-// The pass after a sweep launch in one kernel: the block sums of k_sa_energy_blocks_multi<R> and, when
-// `x` is given, the configurations in original order (k_unpermute_bits), from ONE staging of the
-// R sign-word rows.  The rows are staged in the sweep's even-bit byte layout (a byte per position,
-// configuration k at bit 2k), so the row sums run on the sweep's own k-loop: buffer loads with one
-// quad in flight ahead, one ds_read_u8 per term for the R configurations, one v_lshl_or_b32 and one
-// f64 FMA per term and configuration.  fma(J, +-1.0, acc) is acc + (+-J) bit for bit (the product
-// is exact), the terms arrive in ascending k, and everything after the row sum is
-// energy_blocks_body's: the partial sums are the bits of the kernels above.  No quad past the
-// block is loaded.  Block metadata comes from scalar loads (the block index is wave-uniform).
-struct PostArgs {
-  EnergyArgs e;
-  const uint32_t *pos_of_spin;
-  uint64_t *x;  // nullptr, or [count][words] configurations in original order (bit = +1)
-  uint64_t num_spins;
-  uint32_t words;
-};
-
-template <int R>
-__global__ __launch_bounds__(kMaxThreads) void k_sa_post(PostArgs pa, uint32_t count) {
-  static_assert(R <= 4, "the even-bit byte holds four configurations");
-  extern __shared__ __align__(16) uint8_t lds[];  // [num_blocks * 64] spin bytes
-  const EnergyArgs &a = pa.e;
-  // accumulate addresses the spin bytes absolutely: the dynamic LDS block must be the first
-  // (this kernel declares no static LDS)
-  if (reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t *)lds) != 0) {
-    __builtin_trap();
-  }
-  const uint32_t r0 = blockIdx.x * R;
-  const uint32_t live = count - r0 < static_cast<uint32_t>(R) ? count - r0 : R;
-  const uint64_t *rows = a.perm_words + static_cast<uint64_t>(r0) * a.num_blocks;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t waves = blockDim.x >> 6;
-  // a wavefront per block: the R words of the block are scalar loads, the lane's bits one byte
-  // (rows beyond `live` stay 0: their sums are computed and never stored)
-  for (uint32_t b = wave; b < a.num_blocks; b += waves) {
-    uint32_t byte = 0;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      if (static_cast<uint32_t>(k) >= live) break;  // workgroup-uniform
-      const uint64_t word = rows[static_cast<uint64_t>(k) * a.num_blocks + b];
-      byte |= static_cast<uint32_t>((word >> lane) & 1ull) << (2 * k);
-    }
-    lds[b * 64u + lane] = static_cast<uint8_t>(byte);
-  }
-  __syncthreads();  // the bytes are read-only from here on
-  double mult[4] = {1.0, 1.0, 1.0, 1.0};  // (kWide's, unused by bytes)
-  for (uint32_t b = wave; b < a.num_blocks; b += waves) {
-    const uint32_t quads = a.block_width[b] >> 2;
-    const uint64_t first_quad = a.ell_off[b] >> 2;
-    const uint4 *col = reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u;
-    const double2 *val = reinterpret_cast<const double2 *>(a.ell_val) + first_quad * 128u;
-    const BlockStream stream{col + lane, block_rsrc(col), block_rsrc(val), lane * 16u};
-    const uint32_t p = b * 64u + lane;
-    const double field = a.field_pos[p];  // consumed after the row sum
-    double acc[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) acc[k] = 0.0;
-    // prefetch distance one, scalar loop control, no conditional load inside the loop body; the
-    // last one or two quads are an epilogue, so nothing past the block is loaded (an empty
-    // block's first load reads the next block's first quad or the plan's tail slabs, unused)
-    Quad qa, qb;
-    load_quad(qa, stream, 0);
-    uint32_t i = 0;
-    for (; i + 2 < quads; i += 2) {
-      load_quad(qb, stream, i + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      accumulate<R, kBytes>(qa, lds, acc, mult);
-      __builtin_amdgcn_sched_barrier(0);
-      load_quad(qa, stream, i + 2);
-      __builtin_amdgcn_sched_barrier(0);
-      accumulate<R, kBytes>(qb, lds, acc, mult);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (i + 2 == quads) {
-      load_quad(qb, stream, i + 1);
-      accumulate<R, kBytes>(qa, lds, acc, mult);
-      accumulate<R, kBytes>(qb, lds, acc, mult);
-    } else if (i < quads) {
-      accumulate<R, kBytes>(qa, lds, acc, mult);
-    }
-    const uint32_t own = lds[p];
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      if (static_cast<uint32_t>(k) >= live) break;  // workgroup-uniform
-      const double g = __dadd_rn(__dmul_rn(0.5, acc[k]), field);
-      const bool negative = (own >> (2 * k)) & 1u;
-      const double total = wave_tree_sum_f64(negative ? -g : g);
-      if (lane == 0) a.partial[static_cast<uint64_t>(r0 + k) * a.num_blocks + b] = total;
-    }
-  }
-  if (pa.x == nullptr) return;
-  // a wavefront per output word: lane j owns spin 64 w + j, its position is read coalesced, its
-  // byte once, and the word of each live configuration is one ballot
-  for (uint32_t w = wave; w < pa.words; w += waves) {
-    const uint64_t spin = static_cast<uint64_t>(w) * 64u + lane;
-    const bool real = spin < pa.num_spins;
-    const uint32_t byte = real ? static_cast<uint32_t>(lds[pa.pos_of_spin[spin]]) : 0u;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      if (static_cast<uint32_t>(k) >= live) break;  // workgroup-uniform
-      const uint64_t word = __ballot(real && ((byte >> (2 * k)) & 1u) == 0u);
-      if (lane == 0) pa.x[static_cast<uint64_t>(r0 + k) * pa.words + w] = word;
-    }
-  }
-}
-
-// One wavefront per configuration folds its block sums 64 at a time, in place.
-__device__ __forceinline__ void energy_fold_body(double *partial, uint32_t num_blocks,
-                                                 double diag_sum, double *out_e, const uint32_t r) {
-  const uint32_t lane = threadIdx.x;
-  double *level = partial + static_cast<uint64_t>(r) * num_blocks;
-  uint32_t n = num_blocks;
-  while (n > 1) {
-    const uint32_t groups = (n + 63u) / 64u;
-    for (uint32_t g = 0; g < groups; ++g) {
-      const uint32_t i = g * 64u + lane;
-      const double v = i < n ? level[i] : 0.0;
-      const double s = wave_tree_sum_f64(v);
-      if (lane == 0) level[g] = s;
-    }
-    n = groups;
-  }
-  if (lane == 0) out_e[r] = __dadd_rn(diag_sum, num_blocks ? level[0] : 0.0);
-}
-
-__global__ __launch_bounds__(64) void k_sa_energy_fold(double *partial, uint32_t num_blocks,
-                                                      double diag_sum, double *out_e) {
-  energy_fold_body(partial, num_blocks, diag_sum, out_e, blockIdx.x);
-}
-
-// The same three steps for the chains of MANY problems in one launch each (asp_sa_anneal_batch):
-// workgroup -> (problem, chain) through a table, the problem's pointers through a descriptor.
-struct PostProblem {
-  EnergyArgs e;  // perm_words / partial: this problem's rows
-  const uint32_t *pos_of_spin;
-  uint64_t num_spins;
-  uint32_t words;
-  double diag_sum;
-  double *out_e;    // [repetitions]
-  uint64_t *out_x;  // [repetitions][words]
-};
-
-template <bool STAGED>
-__global__ __launch_bounds__(512) void k_sa_energy_blocks_batch(const PostProblem *problems,
-                                                               const BatchSlot *chains) {
-  const BatchSlot c = chains[blockIdx.x];
-  const EnergyArgs a = problems[__builtin_amdgcn_readfirstlane(c.problem)].e;
-  energy_blocks_body<STAGED>(a, __builtin_amdgcn_readfirstlane(c.group));
-}
-
-__global__ __launch_bounds__(64) void k_sa_energy_fold_batch(const PostProblem *problems,
-                                                            const BatchSlot *chains) {
-  const BatchSlot c = chains[blockIdx.x];
-  const PostProblem &pp = problems[c.problem];
-  energy_fold_body(pp.e.partial, pp.e.num_blocks, pp.diag_sum, pp.out_e, c.group);
-}
-
-// Packed original-order configurations (bit = +1) -> permuted sign-bit words.
-__global__ __launch_bounds__(256) void k_permute_bits(const uint64_t *__restrict__ x,
-                                                     uint32_t words,
-                                                     const uint32_t *__restrict__ spin_of_pos,
-                                                     uint32_t num_blocks, uint32_t count,
-                                                     uint64_t *__restrict__ perm_words) {
-  const uint64_t idx = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (idx >= static_cast<uint64_t>(count) * num_blocks) return;
-  const uint32_t r = static_cast<uint32_t>(idx / num_blocks);
-  const uint32_t b = static_cast<uint32_t>(idx % num_blocks);
-  uint64_t word = 0;
-  for (uint32_t l = 0; l < 64; ++l) {
-    const uint32_t spin = spin_of_pos[b * 64u + l];
-    if (spin == kDummySpin) continue;
-    const uint64_t up = (x[static_cast<uint64_t>(r) * words + (spin >> 6)] >> (spin & 63u)) & 1ull;
-    word |= (up ^ 1ull) << l;
-  }
-  perm_words[idx] = word;
-}
-
-// Permuted sign-bit words -> packed original-order configurations (bit = +1).  A wavefront per
-// output word: lane j owns spin 64 w + j, its position is read once (coalesced) and used for
-// kUnpermuteChains configurations; the word of each is one ballot.
-constexpr uint32_t kUnpermuteChains = 32;
-__global__ __launch_bounds__(256) void k_unpermute_bits(const uint64_t *__restrict__ perm_words,
-                                                       uint32_t num_blocks,
-                                                       const uint32_t *__restrict__ pos_of_spin,
-                                                       uint64_t num_spins, uint32_t words,
-                                                       uint32_t count, uint64_t *__restrict__ x) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (w >= words) return;  // whole wavefront
-  const uint64_t spin = static_cast<uint64_t>(w) * 64u + lane;
-  const bool live = spin < num_spins;
-  const uint32_t pos = live ? pos_of_spin[spin] : 0u;
-  const uint32_t first = blockIdx.y * kUnpermuteChains;
-  const uint32_t last = first + kUnpermuteChains < count ? first + kUnpermuteChains : count;
-  for (uint32_t r = first; r < last; ++r) {
-    const uint64_t neg =
-        (perm_words[static_cast<uint64_t>(r) * num_blocks + (pos >> 6)] >> (pos & 63u)) & 1ull;
-    const uint64_t word = __ballot(live && neg == 0ull);
-    if (lane == 0) x[static_cast<uint64_t>(r) * words + w] = word;
-  }
-}
-
-// k_permute_bits for the initial configurations of a batch of descents: a workgroup per problem.
-__global__ __launch_bounds__(256) void k_permute_bits_problems(const DescentProblem *problems) {
-  const DescentProblem &d = problems[blockIdx.x];
-  for (uint32_t b = threadIdx.x; b < d.s.num_blocks; b += blockDim.x) {
-    uint64_t word = 0;
-    for (uint32_t l = 0; l < 64; ++l) {
-      const uint32_t spin = d.s.spin_of_pos[b * 64u + l];
-      if (spin == kDummySpin) continue;
-      const uint64_t up = (d.x0[spin >> 6] >> (spin & 63u)) & 1ull;
-      word |= (up ^ 1ull) << l;
-    }
-    d.x0_perm[b] = word;
-  }
-}
-
-// The handles of a batched segment (asp_sa_chains_advance_batch, order 0) into and out of the form
-// k_sa_sweep_batch runs their segments in: what sa_chains_advance_colour does with two permute launches,
-// two unpermute launches and six copies PER HANDLE, for all handles in one launch each way.
-struct ChainsIo {
-  uint64_t *x_cur, *x_best;  // the handle: [chains][words], original order, bit = +1
-  long long *e_cur, *e_best;
-  unsigned long long *accepted;
-  uint64_t *cur_perm, *best_perm;  // the launch: [padded][num_blocks] sign words (bit = -1)
-  long long *w_e_cur, *w_tracked;  // [padded]
-  unsigned long long *w_accepted;
-  const uint32_t *spin_of_pos, *pos_of_spin;
-  uint64_t num_spins;
-  uint32_t num_blocks, words, chains;
-};
-// in: a workgroup per (handle, chain of the padded groups); the chains padding the last group start
-// with every spin up and integers 0, as in the single segment.
-__global__ __launch_bounds__(256) void k_chains_permute_problems(const ChainsIo *problems,
-                                                                const BatchSlot *chains) {
-  const BatchSlot c = chains[blockIdx.x];
-  const ChainsIo &io = problems[c.problem];
-  const uint64_t r = c.group;
-  const bool live = r < io.chains;
-  for (uint32_t b = threadIdx.x; b < io.num_blocks; b += blockDim.x) {
-    uint64_t cur = 0, best = 0;
-    if (live) {
-      for (uint32_t l = 0; l < 64; ++l) {
-        const uint32_t spin = io.spin_of_pos[b * 64u + l];
-        if (spin == kDummySpin) continue;
-        const uint64_t at = r * io.words + (spin >> 6);
-        cur |= (((io.x_cur[at] >> (spin & 63u)) & 1ull) ^ 1ull) << l;
-        best |= (((io.x_best[at] >> (spin & 63u)) & 1ull) ^ 1ull) << l;
-      }
-    }
-    io.cur_perm[r * io.num_blocks + b] = cur;
-    io.best_perm[r * io.num_blocks + b] = best;
-  }
-  if (threadIdx.x == 0) {
-    io.w_e_cur[r] = live ? io.e_cur[r] : 0ll;
-    io.w_tracked[r] = live ? io.e_best[r] : 0ll;
-    io.w_accepted[r] = live ? io.accepted[r] : 0ull;
-  }
-}
-// out: a workgroup per (handle, chain)
-__global__ __launch_bounds__(256) void k_chains_unpermute_problems(const ChainsIo *problems,
-                                                                  const BatchSlot *chains) {
-  const BatchSlot c = chains[blockIdx.x];
-  const ChainsIo &io = problems[c.problem];
-  const uint64_t r = c.group;
-  const uint64_t *cur = io.cur_perm + r * io.num_blocks, *best = io.best_perm + r * io.num_blocks;
-  for (uint32_t w = threadIdx.x; w < io.words; w += blockDim.x) {
-    uint64_t cur_word = 0, best_word = 0;
-    for (uint32_t j = 0; j < 64; ++j) {
-      const uint64_t spin = static_cast<uint64_t>(w) * 64u + j;
-      if (spin >= io.num_spins) break;
-      const uint32_t pos = io.pos_of_spin[spin];
-      cur_word |= (((cur[pos >> 6] >> (pos & 63u)) & 1ull) ^ 1ull) << j;
-      best_word |= (((best[pos >> 6] >> (pos & 63u)) & 1ull) ^ 1ull) << j;
-    }
-    io.x_cur[r * io.words + w] = cur_word;
-    io.x_best[r * io.words + w] = best_word;
-  }
-  if (threadIdx.x == 0) {
-    io.e_cur[r] = io.w_e_cur[r];
-    io.e_best[r] = io.w_tracked[r];
-    io.accepted[r] = io.w_accepted[r];
-  }
-}
-
-__global__ __launch_bounds__(256) void k_unpermute_bits_batch(const PostProblem *problems,
-                                                             const BatchSlot *chains) {
-  const BatchSlot c = chains[blockIdx.x];
-  const PostProblem &pp = problems[c.problem];
-  const uint64_t *perm = pp.e.perm_words + static_cast<uint64_t>(c.group) * pp.e.num_blocks;
-  for (uint32_t w = threadIdx.x; w < pp.words; w += blockDim.x) {
-    uint64_t word = 0;
-    for (uint32_t j = 0; j < 64; ++j) {
-      const uint64_t spin = static_cast<uint64_t>(w) * 64u + j;
-      if (spin >= pp.num_spins) break;
-      const uint32_t pos = pp.pos_of_spin[spin];
-      const uint64_t neg = (perm[pos >> 6] >> (pos & 63u)) & 1ull;
-      word |= (neg ^ 1ull) << j;
-    }
-    pp.out_x[static_cast<uint64_t>(c.group) * pp.words + w] = word;
-  }
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// Plan object and C ABI
+// Which kernel runs in which shape
 // ---------------------------------------------------------------------------
 
 namespace {
@@ -2276,16 +1497,39 @@ template <typename Family>
 typename Family::Kernel colour_kernel_of(int m, int layout) {
   return colour_kernel_in<Family>(ColourForms{}, m, layout);
 }
-ClosedFamily<false, false>::Kernel closed_kernel_of(int m, bool descent, int layout, uint32_t replica_first) {
+
+}  // namespace
+
+namespace asp {
+namespace colour {
+
+bool colour_form_listed(int m, int layout) { return colour_form_exists(m, layout); }
+
+ClosedKernel closed_kernel_of(int m, bool descent, int layout, uint32_t replica_first) {
   if (descent) return colour_kernel_of<ClosedFamily<true, false>>(m, layout);
   if (aligned_replicas(m, replica_first)) return colour_kernel_of<ClosedFamily<false, true>>(m, layout);
   return colour_kernel_of<ClosedFamily<false, false>>(m, layout);
 }
+template <typename Res>
+SegmentKernel<Res> segment_kernel_of(int m, int layout) {
+  return colour_kernel_of<SegmentFamily<Res>>(m, layout);
+}
+template SegmentKernel<Resume> segment_kernel_of<Resume>(int, int);
+template SegmentKernel<ResumeLadder> segment_kernel_of<ResumeLadder>(int, int);
+template <typename Problem>
+BatchKernel<Problem> batch_kernel_of(int m, int layout) {
+  return colour_kernel_of<BatchFamily<Problem>>(m, layout);
+}
+template BatchKernel<SweepArgs> batch_kernel_of<SweepArgs>(int, int);
+template BatchKernel<DescentProblem> batch_kernel_of<DescentProblem>(int, int);
+template BatchKernel<ResumeProblem> batch_kernel_of<ResumeProblem>(int, int);
+template BatchKernel<LadderProblem> batch_kernel_of<LadderProblem>(int, int);
+TeamKernel team_kernel_of(bool descent) { return descent ? k_sa_sweep_team<true> : k_sa_sweep_team<false>; }
 
 // The dynamic LDS of a launch (SweepLds::total): a kernel without tail sweeps, or (tail) k_sa_sweep_tail
 // with `threads` threads.  (32-bit offsets: 2^20 blocks are far beyond any LDS in every layout that keeps
 // something per block.)
-size_t sweep_lds_bytes(const asp::SaHostLayout &L, int layout, bool tail = false, int threads = 0) {
+size_t sweep_lds_bytes(const asp::SaHostLayout &L, int layout, bool tail, int threads) {
   if (layout != kGlobal && L.num_blocks > (1u << 20)) return SIZE_MAX;
   return SweepLds(L.num_blocks, layout, tail, static_cast<uint32_t>(threads / 64)).total;
 }
@@ -2306,7 +1550,6 @@ uint32_t tail_enter_flips_of(const asp::SaHostLayout &L) {
 // The TAIL kernel of a closed call in `form`, or nullptr: the launch keeps the kernel without tail sweeps
 // of the same form — tail sweeps or the field cache off, another form than four chains in bytes or words,
 // no room in the LDS for the bitmap and the rings, or arrays beyond the 32-bit buffer offsets of a row.
-using TailKernel = void (*)(SweepArgs, TailArgs);
 TailKernel tail_kernel_of(const asp_sa_plan *p, int m, int threads, int layout, bool descent, uint32_t replica_first) {
   const asp::SaHostLayout &L = p->host;
   if (p->tail_mode == 0 || !p->use_field_cache || descent || m != 4 || (layout != kBytes && layout != kWide)) {
@@ -2336,7 +1579,7 @@ uint32_t widest_color(const asp::SaHostLayout &L) {
 
 // Launch geometry: as many replicas per group as still leaves one group per CU,
 // as many wavefronts as a colour class has blocks.
-void choose_launch(const asp_sa_plan *p, uint32_t repetitions, int *m_out, int *threads_out) {
+static void choose_launch(const asp_sa_plan *p, uint32_t repetitions, int *m_out, int *threads_out) {
   const uint32_t widest = widest_color(p->host);
   int m = 1;
   bool two_per_cu = false;
@@ -2371,12 +1614,6 @@ void choose_launch(const asp_sa_plan *p, uint32_t repetitions, int *m_out, int *
   *threads_out = threads;
 }
 
-// Chains per group, threads and spin layout of a launch with one workgroup per group of chains —
-// shared by the closed calls (run_chains, which may then spread a chain over a team instead) and by
-// the segments of a handle (sa_chains_advance_colour), so that both take the same form.
-struct ColourLaunch {
-  int m = 1, threads = 64, layout = kBytes;
-};
 // a bit per position, in LDS or in HBM (forced by asp_sa_set_packed or chosen: the launch is the same)
 bool bit_packed(int layout) { return layout == kBits || layout == kGlobal; }
 ColourLaunch choose_colour_launch(const asp_sa_plan *p, uint32_t repetitions, bool descent, bool traced) {
@@ -2409,8 +1646,30 @@ ColourLaunch choose_colour_launch(const asp_sa_plan *p, uint32_t repetitions, bo
   return c;
 }
 
+// Few chains on a large cluster: spread each chain over a team of workgroups (k_sa_sweep_team).
+uint32_t choose_team(const asp_sa_plan *p, const ColourLaunch &form, uint32_t repetitions, bool traced) {
+  const asp::SaHostLayout &L = p->host;
+  uint32_t team = 0;
+  const uint32_t widest = widest_color(L);
+  // (one colour class only — a diagonal or field-only J —: the single barrier per sweep would
+  // not separate a fast member's next publication from a slow member's read of this one)
+  const bool possible = !traced && form.layout != kGlobal && form.layout != kNibbles && p->force_packed == 0 &&
+                        L.num_colors >= 2 && p->force_m == 0 && team_lds_bytes(L) <= p->max_lds &&
+                        static_cast<uint64_t>(repetitions) * 2 <= static_cast<uint64_t>(p->num_cus);
+  if (possible && p->team_mode >= 2) {
+    team = static_cast<uint32_t>(p->team_mode);  // forced (tests, measurements)
+  } else if (possible && p->team_mode < 0 && widest >= 64) {
+    // auto: as many workgroups per chain as the chip has to spare, up to 8
+    const uint32_t spare = static_cast<uint32_t>(p->num_cus) / repetitions;
+    team = spare >= 8 ? 8u : (spare >= 4 ? 4u : 2u);
+    while (team > 2 && widest < 16u * team) team >>= 1;  // every member needs a full round
+  }
+  if (team * repetitions > static_cast<uint32_t>(p->num_cus)) team = 0;  // must be co-resident
+  return team;
+}
+
 // The plan's part of the sweep arguments (the same for every launch of the plan in `layout`) ...
-SweepArgs plan_sweep_args(const asp_sa_plan *p, int layout) {
+static SweepArgs plan_sweep_args(const asp_sa_plan *p, int layout) {
   const asp::SaHostLayout &L = p->host;
   SweepArgs plan_args{};
   plan_args.color_block_start = p->color_block_start.ptr;
@@ -2450,803 +1709,9 @@ uint32_t cache_enter_flips_of(const asp::SaHostLayout &L) {
   return static_cast<uint32_t>(std::max(1.0, 0.7 * static_cast<double>(L.num_blocks) / degree));
 }
 
-// The field cache of `padded` chains (512 B per block and replica), when it fits comfortably in HBM.
-void attach_field_cache(asp_sa_plan *p, uint64_t padded, SweepArgs *args) {
-  const asp::SaHostLayout &L = p->host;
-  const uint64_t cache_elems = padded * L.num_blocks * 64ull;
-  if (cache_elems * sizeof(double) <= (32ull << 30) && p->w_field_cache.ensure(cache_elems) == ASP_OK) {
-    args->field_cache = p->w_field_cache.ptr;
-    args->cache_enter_flips = cache_enter_flips_of(L);
-  } else {
-    asp_clear_error();  // the cache is an optimisation: run without it
-  }
-}
-
-// out_x: nullptr, or [count][ceil(K/64)] — the configurations in original order (bit = +1) as well:
-// written by k_sa_post where it runs, by k_unpermute_bits behind the older energy kernels.
-int energies_of_perm(asp_sa_plan *p, const uint64_t *perm_words, uint32_t count, double *partial,
-                     double *out_e, uint64_t *out_x = nullptr) {
-  const asp::SaHostLayout &L = p->host;
-  if (count == 0) return ASP_OK;
-  EnergyArgs ea{p->block_width.ptr, p->ell_off.ptr, p->ell_col.ptr, p->ell_val.ptr,
-                p->field_pos.ptr,   perm_words,     partial,        L.num_blocks};
-  const size_t lds = static_cast<size_t>(L.num_blocks) * sizeof(uint64_t);
-  const uint32_t words = static_cast<uint32_t>((L.num_spins + 63) / 64);
-  constexpr int kShare = 4;  // configurations per workgroup sharing the coupling loads
-  const size_t post_lds = static_cast<size_t>(L.num_blocks) * 64;  // a byte per position
-  if (count >= 2 * kShare && p->use_post && post_lds <= p->max_lds) {
-    // (asp_sa_set_post; plans whose bytes do not fit the LDS keep the kernels below)
-    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_sa_post<kShare>), post_lds));
-    const PostArgs pa{ea, p->pos_of_spin.ptr, out_x, L.num_spins, words};
-    const uint32_t waves = std::min<uint32_t>(16u, L.num_blocks);
-    hipLaunchKernelGGL(k_sa_post<kShare>, dim3((count + kShare - 1) / kShare), dim3(64 * waves),
-                       post_lds, p->stream, pa, count);
-    out_x = nullptr;  // done
-  } else if (count >= 2 * kShare && lds * kShare <= p->max_lds) {
-    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_sa_energy_blocks_multi<kShare>), lds * kShare));
-    hipLaunchKernelGGL(k_sa_energy_blocks_multi<kShare>, dim3((count + kShare - 1) / kShare),
-                       dim3(512), lds * kShare, p->stream, ea, count);
-  } else if (lds > p->max_lds) {
-    hipLaunchKernelGGL(k_sa_energy_blocks<false>, dim3(count), dim3(512), 0, p->stream, ea);
-  } else {
-    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_sa_energy_blocks<true>), lds));
-    hipLaunchKernelGGL(k_sa_energy_blocks<true>, dim3(count), dim3(512), lds, p->stream, ea);
-  }
-  hipLaunchKernelGGL(k_sa_energy_fold, dim3(count), dim3(64), 0, p->stream, partial, L.num_blocks,
-                     L.diag_sum, out_e);
-  if (out_x != nullptr) {
-    hipLaunchKernelGGL(k_unpermute_bits,
-                       dim3((words + 3) / 4, (count + kUnpermuteChains - 1) / kUnpermuteChains), dim3(256),
-                       0, p->stream, perm_words, L.num_blocks, p->pos_of_spin.ptr, L.num_spins, words,
-                       count, out_x);
-  }
-  ASP_HIP_TRY(hipGetLastError());
-  return ASP_OK;
-}
-
-}  // namespace
-
-namespace asp {
-
-int sa_plan_device_setup(asp_sa_plan *p) {
-  const SaHostLayout &L = p->host;
-  bool ok = stream_acquire(&p->stream) == ASP_OK;
-  for (auto &e : p->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  if (!ok) set_error(ASP_ERR_HIP, "could not create HIP stream/events");
-  int num_cus = 0;
-  size_t max_lds = 0;
-  if (ok && device_limits(&num_cus, &max_lds) == ASP_OK) {
-    p->num_cus = num_cus;
-    p->max_lds = max_lds;
-  }
-  ok = ok && upload_vector(p->color_block_start, L.color_block_start, p->stream) == ASP_OK &&
-       upload_vector(p->block_width, L.block_width, p->stream) == ASP_OK &&
-       upload_vector(p->ell_off, L.ell_off, p->stream) == ASP_OK &&
-       upload_vector(p->ell_col, L.ell_col, p->stream) == ASP_OK &&
-       upload_vector(p->ell_val, L.ell_val, p->stream) == ASP_OK &&
-       upload_vector(p->spin_of_pos, L.spin_of_pos, p->stream) == ASP_OK &&
-       upload_vector(p->pos_of_spin, L.pos_of_spin, p->stream) == ASP_OK &&
-       upload_vector(p->field_pos, L.field_pos, p->stream) == ASP_OK;
-  if (ok && sweep_lds_bytes(L, kWide) <= p->max_lds) {
-    std::vector<uint32_t> scaled(L.ell_col.size());
-    for (size_t i = 0; i < scaled.size(); ++i) scaled[i] = L.ell_col[i] * 4u;
-    ok = upload_vector(p->ell_col4, scaled, p->stream) == ASP_OK &&
-         hipStreamSynchronize(p->stream) == hipSuccess;  // `scaled` dies with this scope
-  }
-  if (ok && hipStreamSynchronize(p->stream) != hipSuccess) {
-    set_error(ASP_ERR_HIP, "plan upload failed");
-    ok = false;
-  }
-  if (ok) return ASP_OK;
-  if (error_state().code == ASP_OK) set_error(ASP_ERR_HIP, "plan upload failed");
-  return error_state().code;
-}
-
-int sa_permute_bits(asp_sa_plan *p, const uint64_t *x, uint32_t count, uint64_t *perm) {
-  const SaHostLayout &L = p->host;
-  const uint64_t total = static_cast<uint64_t>(count) * L.num_blocks;
-  if (total == 0) return ASP_OK;
-  const uint32_t words = static_cast<uint32_t>((L.num_spins + 63) / 64);
-  hipLaunchKernelGGL(k_permute_bits, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0,
-                     p->stream, x, words, p->spin_of_pos.ptr, L.num_blocks, count, perm);
-  ASP_HIP_TRY(hipGetLastError());
-  return ASP_OK;
-}
-
-int sa_energies_of_perm(asp_sa_plan *p, const uint64_t *perm, uint32_t count, double *partial,
-                        double *out_e) {
-  return energies_of_perm(p, perm, count, partial, out_e);
-}
-
-}  // namespace asp
-
-extern "C" {
-
-asp_sa_plan *asp_sa_plan_create(uint64_t num_spins, int64_t const *indptr, int32_t const *indices,
-                                double const *data, double const *field) {
-  asp_clear_error();
-  if (asp::require_device() != ASP_OK) return nullptr;
-  asp_sa_plan *p = new (std::nothrow) asp_sa_plan();
-  if (!p) {
-    asp::set_error(ASP_ERR_ALLOC, "out of host memory");
-    return nullptr;
-  }
-  if (asp::build_sa_layout(num_spins, indptr, indices, data, field, &p->host) != ASP_OK) {
-    delete p;
-    return nullptr;
-  }
-  p->pattern = std::make_shared<asp::SaPattern>();
-  if (num_spins > 0) {
-    // the pattern, for asp_sa_plan_reweight to compare with (validated above)
-    p->pattern->nnz = static_cast<uint64_t>(indptr[num_spins]);
-    p->pattern->indptr.assign(indptr, indptr + num_spins + 1);
-    p->pattern->indices.assign(indices, indices + p->pattern->nnz);
-  }
-  // ASP_SA_TEAM=0: no team sweeps in this process — several processes share the device (worker
-  // processes or ranks of the pipeline on one GPU), and a team launch needs all its workgroups
-  // resident together, which another process's kernels can prevent (the watchdog then costs
-  // seconds before the rerun without teams)
-  if (const char *env = std::getenv("ASP_SA_TEAM")) {
-    const int team = std::atoi(env);
-    if (team == 0 || team == 2 || team == 4 || team == 8) p->team_mode = team;
-  }
-  if (asp::sa_plan_device_setup(p) != ASP_OK) {
-    asp_sa_plan_destroy(p);
-    return nullptr;
-  }
-  return p;
-}
-
-void asp_sa_plan_destroy(asp_sa_plan *p) {
-  if (!p) return;
-  for (auto &e : p->ev) {
-    if (e) (void)hipEventDestroy(e);
-  }
-  if (p->stream) {
-    (void)hipStreamSynchronize(p->stream);  // idle before it is recycled
-    asp::stream_release(p->stream);
-  }
-  delete p;
-}
-
-int asp_sa_plan_info(asp_sa_plan const *p, asp_sa_info *info) {
-  if (!p || !info) return asp::set_error(ASP_ERR_INVALID, "null argument");
-  const asp::SaHostLayout &L = p->host;
-  info->num_spins = L.num_spins;
-  info->nnz_offdiag = L.a_col.size();
-  info->ell_entries = L.ell_off.back() * 64;
-  info->num_colors = L.num_colors;
-  info->num_blocks = L.num_blocks;
-  info->max_degree = L.max_degree;
-  info->energy_scale_exp = L.energy_scale_exp;
-  info->diag_sum = L.diag_sum;
-  info->beta0_auto = L.beta0_auto;
-  info->beta1_auto = L.beta1_auto;
-  return ASP_OK;
-}
-
-int asp_sa_set_launch(asp_sa_plan *p, int replicas_per_group, int threads) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  if (replicas_per_group != 0 && !colour_form_exists(replicas_per_group, kBytes)) {
-    return asp::set_error(ASP_ERR_INVALID, "replicas_per_group must be 0, 1, 2, 4 or 8");
-  }
-  if (threads != 0 && (threads < 64 || threads > 1024 || threads % 64 != 0)) {
-    return asp::set_error(ASP_ERR_INVALID, "threads must be 0 or a multiple of 64 in [64, 1024]");
-  }
-  p->force_m = replicas_per_group;
-  p->force_threads = threads;
-  return ASP_OK;
-}
-
-int asp_sa_set_field_cache(asp_sa_plan *p, int enable) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  p->use_field_cache = enable != 0;
-  return ASP_OK;
-}
-
-int asp_sa_set_tail(asp_sa_plan *p, int n) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  if (n < -1) return asp::set_error(ASP_ERR_INVALID, "n must be -1 (auto), 0 (off) or a number of flips");
-  p->tail_mode = n;
-  return ASP_OK;
-}
-
-int asp_sa_last_tail(asp_sa_plan const *p, uint32_t *sweeps_min, uint32_t *sweeps_max, uint32_t *entries_max) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  uint32_t lo = p->last_tail.empty() ? 0u : 0xFFFFFFFFu, hi = 0, entries = 0;
-  for (size_t g = 0; g + 1 < p->last_tail.size(); g += 2) {
-    lo = std::min(lo, p->last_tail[g]);
-    hi = std::max(hi, p->last_tail[g]);
-    entries = std::max(entries, p->last_tail[g + 1]);
-  }
-  if (sweeps_min) *sweeps_min = lo;
-  if (sweeps_max) *sweeps_max = hi;
-  if (entries_max) *entries_max = entries;
-  return ASP_OK;
-}
-
-int asp_sa_set_post(asp_sa_plan *p, int enable) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  p->use_post = enable != 0;
-  return ASP_OK;
-}
-
-int asp_sa_team_watchdog_trips(asp_sa_plan const *p, uint32_t *of_plan, uint64_t *of_process) {
-  if (of_plan) *of_plan = p ? p->team_watchdog_trips : 0u;
-  if (of_process) *of_process = g_team_watchdog_trips.load(std::memory_order_relaxed);
-  return ASP_OK;
-}
-
-int asp_sa_set_team(asp_sa_plan *p, int team) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  if (team != -1 && team != 0 && team != 2 && team != 4 && team != 8) {
-    return asp::set_error(ASP_ERR_INVALID, "team must be -1 (auto), 0 (off), 2, 4 or 8");
-  }
-  p->team_mode = team;
-  return ASP_OK;
-}
-
-int asp_sa_set_wide(asp_sa_plan *p, int allow) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  p->allow_wide = allow != 0;
-  return ASP_OK;
-}
-
-int asp_sa_last_layout(asp_sa_plan const *p) { return p ? p->last_layout : -1; }
-
-int asp_sa_last_spin_layout(asp_sa_plan const *p) { return p ? p->last_spin_layout : -1; }
-
-int asp_sa_set_lds_limit(asp_sa_plan *p, uint64_t bytes) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  p->spin_lds_limit = static_cast<size_t>(std::min<uint64_t>(bytes, p->max_lds));  // (0, or >= the device's: the device's)
-  return ASP_OK;
-}
-
-int asp_sa_set_packed(asp_sa_plan *p, int packed) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  p->force_packed = packed < 0 ? 0 : (packed > 2 ? 2 : packed);
-  return ASP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-int greedy_relax(asp_sa_plan *p, uint32_t max_sweeps, std::vector<uint64_t> &x, uint64_t *out_x,
-                 double *out_e, uint32_t *out_sweeps, bool exact_sweeps);
-
-// One launch on the plan's stream with a workgroup per group of chains: what a closed call (run_chains)
-// and a segment of a handle (chains_advance_colour) do alike.  The caller queues what is its own between
-// these steps — its uploads, the start, ev[0], the pass after the sweeps, ev[3] and its copies.
-struct ColourRun {
-  asp_sa_plan *p;
-  uint32_t repetitions, num_sweeps;
-  int64_t *trace;  // HOST [repetitions][num_sweeps + 1] or nullptr
-  int m = 1, threads = 64, layout = kBytes;
-  size_t lds = 0;
-  uint32_t groups = 0;
-  uint64_t padded = 0;
-  SweepArgs args{};
-  bool tail = false;  // a k_sa_sweep_tail launch: no field cache
-
-  int shape(const ColourLaunch &form, size_t lds_bytes) {
-    m = form.m, threads = form.threads, layout = form.layout, lds = lds_bytes;
-    if (lds > p->max_lds) {
-      return asp::set_error(ASP_ERR_TOO_LARGE, "%zu B of LDS needed, %zu B available", lds, p->max_lds);
-    }
-    groups = (repetitions + m - 1) / m;
-    padded = static_cast<uint64_t>(groups) * m;
-    return ASP_OK;
-  }
-  // the work buffers every launch uses; `num_betas` values go up in w_betas
-  int ensure_work(uint64_t num_betas) {
-    if (layout == kGlobal) ASP_TRY(p->w_spins.ensure(static_cast<uint64_t>(groups) * p->host.num_blocks));
-    ASP_TRY(p->w_betas.ensure(num_betas));
-    ASP_TRY(p->w_best.ensure(padded * p->host.num_blocks));
-    ASP_TRY(p->w_tracked.ensure(padded));
-    return p->w_accepted.ensure(padded);
-  }
-  // the arguments, with the trace buffer and the field cache (both the byte and the wide layout)
-  int fill(const double *betas, const uint64_t *x0_perm, uint64_t seed, uint32_t replica_first) {
-    args = sweep_args(p, layout, betas, x0_perm, p->w_best.ptr, p->w_tracked.ptr, p->w_accepted.ptr, seed,
-                      num_sweeps, replica_first);
-    if (trace) {
-      ASP_TRY(p->w_trace.ensure(padded * (static_cast<uint64_t>(num_sweeps) + 1)));
-      args.trace = p->w_trace.ptr;
-    }
-    if (p->use_field_cache && !bit_packed(layout) && !tail) attach_field_cache(p, padded, &args);
-    return ASP_OK;
-  }
-  // ev[1], kernel(args, extra...), ev[2]
-  template <typename Kernel, typename... Extra>
-  int launch(Kernel kernel, Extra... extra) {
-    if (!kernel) return asp::set_error(ASP_ERR_INVALID, "no sweep kernel for %d chains per group", m);
-    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(kernel), lds));
-    ASP_HIP_TRY(hipEventRecord(p->ev[1], p->stream));
-    hipLaunchKernelGGL(kernel, dim3(groups), dim3(threads), lds, p->stream, args, extra...);
-    ASP_HIP_TRY(hipGetLastError());
-    ASP_HIP_TRY(hipEventRecord(p->ev[2], p->stream));
-    return ASP_OK;
-  }
-  // the trace rows behind the caller's copies, and the wait for everything queued
-  int collect() {
-    if (trace) {  // rows of the real chains come first
-      ASP_HIP_TRY(hipMemcpyAsync(trace, p->w_trace.ptr,
-                                 static_cast<uint64_t>(repetitions) * (num_sweeps + 1ull) * sizeof(int64_t),
-                                 hipMemcpyDeviceToHost, p->stream));
-    }
-    ASP_HIP_TRY(hipStreamSynchronize(p->stream));
-    return ASP_OK;
-  }
-  // what asp_sa_last_launch / _last_layout / _last_*_ms report; ev[0] .. ev[3]: the caller's
-  int record(int launch_layout) {
-    p->last_m = m;
-    p->last_layout = launch_layout;
-    p->last_spin_layout = layout;
-    p->last_threads = threads;
-    p->last_groups = static_cast<int>(groups);
-    ASP_HIP_TRY(hipEventElapsedTime(&p->last_sweep_ms, p->ev[1], p->ev[2]));
-    ASP_HIP_TRY(hipEventElapsedTime(&p->last_total_ms, p->ev[0], p->ev[3]));
-    return ASP_OK;
-  }
-};
-
-// Two team kernels resident at the same time could each hold CUs the other is waiting for:
-// team launches of one process take turns (from launch to completion).
-std::mutex g_team_launches;
-
-// The launch of a closed call (ev[0] .. ev[2] and the watchdog's read-back) with every chain spread over
-// `team` workgroups; the caller holds g_team_launches.  *refused: the configuration cannot be launched.
-int launch_team(ColourRun &run, uint32_t team, bool descent, bool *refused) {
-  asp_sa_plan *p = run.p;
-  const asp::SaHostLayout &L = p->host;
-  const uint32_t repetitions = run.repetitions;
-  hipStream_t s = p->stream;
-  // wavefronts per member: the widest colour class split over the team, at most 16
-  run.threads = static_cast<int>(std::min<uint32_t>(16u, (widest_color(L) + team - 1) / team)) * 64;
-  if (p->use_field_cache) {
-    // the team's "tracking" of untouched blocks uses the field cache's switch-over threshold
-    run.args.cache_enter_flips = cache_enter_flips_of(L);
-  }
-  TeamArgs ta{};
-  ta.s = run.args;
-  ta.team_size = team;
-  ta.num_teams = repetitions;
-  ta.spin_limit = kTeamSpinLimit;
-  if (const char *env = std::getenv("ASP_TEAM_SPIN_LIMIT")) {  // test hook: provoke the watchdog
-    ta.spin_limit = static_cast<uint32_t>(std::strtoul(env, nullptr, 10));
-  }
-  const size_t head_bytes = static_cast<size_t>(repetitions) * 8 * 7 + 16;
-  const size_t need = head_bytes + static_cast<size_t>(repetitions) * L.num_blocks * 8;
-  if (need > p->team_area_bytes) {
-    if (p->team_area) (void)hipFree(p->team_area);
-    p->team_area = nullptr;
-    p->team_area_bytes = 0;
-    ASP_HIP_TRY(hipExtMallocWithFlags(&p->team_area, need, hipDeviceMallocFinegrained));
-    p->team_area_bytes = need;
-  }
-  ASP_HIP_TRY(hipMemsetAsync(p->team_area, 0, head_bytes, s));
-  uint8_t *area = static_cast<uint8_t *>(p->team_area);
-  ta.arrivals = reinterpret_cast<unsigned long long *>(area);
-  ta.sums = reinterpret_cast<long long *>(area + static_cast<size_t>(repetitions) * 8);
-  ta.abort = reinterpret_cast<uint32_t *>(area + static_cast<size_t>(repetitions) * 8 * 7);
-  ta.flips = reinterpret_cast<uint64_t *>(area + head_bytes);
-  void (*team_kernel)(TeamArgs) = descent ? k_sa_sweep_team<true> : k_sa_sweep_team<false>;
-  ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(team_kernel), run.lds));
-  ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
-  ASP_HIP_TRY(hipEventRecord(p->ev[1], s));
-  // An ORDINARY launch: team * repetitions <= CUs workgroups, each fitting a CU by itself,
-  // are all resident on an otherwise idle device, and the watchdog (with the rerun in run_chains)
-  // covers a device that is not idle.  hipLaunchCooperativeKernel would check the same
-  // occupancy bound, but a process that has used it once dies in the HIP runtime's exit
-  // handler when rocprofv3 is attached (tools/exit_probe.hip: a 40-line program does;
-  // profiles/r02_exit_probe.txt).
-  hipLaunchKernelGGL(team_kernel, dim3(repetitions * team), dim3(run.threads), run.lds, s, ta);
-  *refused = hipGetLastError() != hipSuccess;
-  if (*refused) return ASP_OK;
-  ASP_HIP_TRY(hipEventRecord(p->ev[2], s));
-  ASP_HIP_TRY(hipMemcpyAsync(&p->team_abort_host, ta.abort, sizeof p->team_abort_host, hipMemcpyDeviceToHost, s));
-  return ASP_OK;
-}
-
-// All chains of one call; descent = strict-descent sweeps (greedy relaxation).
-int run_chains(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_sweeps,
-               uint32_t repetitions, uint32_t replica_offset, uint64_t const *x0, bool descent,
-               uint64_t *out_x, double *out_e, int64_t *out_trace = nullptr) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  ASP_TRY(asp::bind_device());
-  if (repetitions == 0) return ASP_OK;
-  if (!out_x || !out_e || (num_sweeps && !betas)) {
-    return asp::set_error(ASP_ERR_INVALID, "null argument");
-  }
-  if (num_sweeps == 0xFFFFFFFFu) {
-    return asp::set_error(ASP_ERR_INVALID, "num_sweeps 2^32-1 is reserved");
-  }
-  if (static_cast<uint64_t>(replica_offset) + repetitions + 8 > 0xFFFFFFFFull) {
-    return asp::set_error(ASP_ERR_INVALID, "replica ids exceed 32 bits");
-  }
-  for (uint32_t t = 0; t < num_sweeps; ++t) {
-    if (!(betas[t] >= 0.0)) return asp::set_error(ASP_ERR_INVALID, "betas[%u] is not >= 0", t);
-  }
-  const asp::SaHostLayout &L = p->host;
-  const uint64_t K = L.num_spins;
-  const uint32_t words = static_cast<uint32_t>((K + 63) / 64);
-  p->last_sweep_ms = p->last_total_ms = 0.0f;
-  if (K == 0) {
-    for (uint32_t r = 0; r < repetitions; ++r) out_e[r] = 0.0;
-    return ASP_OK;
-  }
-  ColourLaunch form = choose_colour_launch(p, repetitions, descent, out_trace != nullptr);
-  // Few chains on a large cluster: spread each chain over a team of workgroups (k_sa_sweep_team).
-  uint32_t team = 0;
-  {
-    const uint32_t widest = widest_color(L);
-    // (one colour class only — a diagonal or field-only J —: the single barrier per sweep would
-    // not separate a fast member's next publication from a slow member's read of this one)
-    const bool possible = !out_trace && form.layout != kGlobal && form.layout != kNibbles && p->force_packed == 0 &&
-                          L.num_colors >= 2 && p->force_m == 0 && team_lds_bytes(L) <= p->max_lds &&
-                          static_cast<uint64_t>(repetitions) * 2 <= static_cast<uint64_t>(p->num_cus);
-    if (possible && p->team_mode >= 2) {
-      team = static_cast<uint32_t>(p->team_mode);  // forced (tests, measurements)
-    } else if (possible && p->team_mode < 0 && widest >= 64) {
-      // auto: as many workgroups per chain as the chip has to spare, up to 8
-      const uint32_t spare = static_cast<uint32_t>(p->num_cus) / repetitions;
-      team = spare >= 8 ? 8u : (spare >= 4 ? 4u : 2u);
-      while (team > 2 && widest < 16u * team) team >>= 1;  // every member needs a full round
-    }
-    if (team * repetitions > static_cast<uint32_t>(p->num_cus)) team = 0;  // must be co-resident
-  }
-  if (team >= 2) form.m = 1, form.layout = kBits;
-  ColourRun run{p, repetitions, num_sweeps, out_trace};
-  // tail sweeps where the form has them and its LDS has the room: the form itself stays as chosen
-  const TailKernel tail_kernel =
-      team >= 2 ? nullptr : tail_kernel_of(p, form.m, form.threads, form.layout, descent, replica_offset);
-  run.tail = tail_kernel != nullptr;
-  ASP_TRY(run.shape(form, team >= 2 ? team_lds_bytes(L)
-                                    : sweep_lds_bytes(L, form.layout, run.tail, form.threads)));
-  hipStream_t s = p->stream;
-  // every exit below, error or not, first waits for what was queued on the stream: copies into
-  // the caller's buffers and kernels using the plan's work buffers never outlive the call
-  asp::StreamFence fence(s);
-  ASP_TRY(run.ensure_work(num_sweeps));
-  ASP_TRY(p->w_partial.ensure(static_cast<uint64_t>(repetitions) * L.num_blocks));
-  ASP_TRY(p->w_e.ensure(repetitions));
-  ASP_TRY(p->w_x.ensure(static_cast<uint64_t>(repetitions) * words));
-  ASP_TRY(p->w_betas.upload(betas, num_sweeps, s));
-  ASP_HIP_TRY(hipMemsetAsync(p->w_accepted.ptr, 0, run.padded * sizeof(unsigned long long), s));
-  if (x0) {
-    ASP_TRY(p->w_x0.ensure(words));
-    ASP_TRY(p->w_x0_perm.ensure(L.num_blocks));
-    ASP_TRY(p->w_x0.upload(x0, words, s));
-    ASP_TRY(asp::sa_permute_bits(p, p->w_x0.ptr, 1u, p->w_x0_perm.ptr));
-  }
-  ASP_TRY(run.fill(p->w_betas.ptr, x0 ? p->w_x0_perm.ptr : nullptr, seed, replica_offset));
-
-  p->team_abort_host = 0;
-  std::unique_lock<std::mutex> team_turn(g_team_launches, std::defer_lock);
-  if (team >= 2) {
-    team_turn.lock();
-    bool refused = false;
-    ASP_TRY(launch_team(run, team, descent, &refused));
-    if (refused) {
-      // the configuration cannot be launched: one workgroup per chain instead
-      ASP_HIP_TRY(hipStreamSynchronize(s));
-      team_turn.unlock();
-      p->team_mode = 0;
-      return run_chains(p, seed, betas, num_sweeps, repetitions, replica_offset, x0, descent, out_x,
-                        out_e, out_trace);
-    }
-  } else if (run.tail) {
-    ASP_TRY(p->w_tail.ensure(2ull * run.groups));
-    ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
-    const uint32_t enter = p->tail_mode > 0 ? static_cast<uint32_t>(p->tail_mode) : tail_enter_flips_of(L);
-    ASP_TRY(run.launch(tail_kernel, TailArgs{enter, p->w_tail.ptr}));
-  } else {
-    ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
-    ASP_TRY(run.launch(closed_kernel_of(run.m, descent, run.layout, replica_offset)));
-  }
-  p->last_tail.assign(run.tail ? 2ull * run.groups : 0, 0u);
-  if (run.tail) {
-    ASP_HIP_TRY(hipMemcpyAsync(p->last_tail.data(), p->w_tail.ptr, p->last_tail.size() * sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, s));
-  }
-  // the first `repetitions` rows of best_perm are the real replicas
-  // ... their reported energies and, in the same pass, their configurations in original order
-  ASP_TRY(energies_of_perm(p, p->w_best.ptr, repetitions, p->w_partial.ptr, p->w_e.ptr, p->w_x.ptr));
-  ASP_HIP_TRY(hipEventRecord(p->ev[3], s));
-  // hipMemcpyDefault: out_x / out_e may be host pointers (the usual call) or device pointers
-  // (distributed.py hands over RCCL-ready tensors, so a gather needs no host round trip)
-  ASP_HIP_TRY(hipMemcpyAsync(out_x, p->w_x.ptr, static_cast<uint64_t>(repetitions) * words * sizeof(uint64_t),
-                             hipMemcpyDefault, s));
-  ASP_HIP_TRY(hipMemcpyAsync(out_e, p->w_e.ptr, repetitions * sizeof(double), hipMemcpyDefault, s));
-  p->last_tracked.assign(repetitions, 0);
-  p->last_accepted.assign(repetitions, 0);
-  ASP_HIP_TRY(hipMemcpyAsync(p->last_tracked.data(), p->w_tracked.ptr, repetitions * sizeof(int64_t),
-                             hipMemcpyDeviceToHost, s));
-  ASP_HIP_TRY(hipMemcpyAsync(p->last_accepted.data(), p->w_accepted.ptr,
-                             repetitions * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  ASP_TRY(run.collect());
-  if (p->team_abort_host != 0) {
-    // The members of a team were not resident together (another process or a long kernel holding
-    // compute units — the launch mutex only orders this process's team launches): the partial
-    // results are discarded and the call is repeated with one workgroup per chain, the fallback
-    // of a refused launch.  Teams stay off for this plan.
-    if (team_turn.owns_lock()) team_turn.unlock();
-    p->team_mode = 0;
-    p->team_watchdog_trips += 1;
-    g_team_watchdog_trips.fetch_add(1, std::memory_order_relaxed);
-    return run_chains(p, seed, betas, num_sweeps, repetitions, replica_offset, x0, descent, out_x,
-                      out_e, out_trace);
-  }
-  return run.record(team >= 2 ? 4 : run.layout);
-}
-
-// One segment of a handle in the colour order: the handle's original-order configurations are
-// permuted into the plan's block order (current and best, every chain its own), k_sa_sweep_resume
-// runs the sweeps from the carried integers with sweep index base c->sweeps_done, and both
-// configurations go back.  The launch is run_chains' minus teams: the same choice of chains per
-// group and spin layout, honouring asp_sa_set_launch / _set_packed / _set_wide; asp_sa_set_team
-// is ignored (a handle runs one workgroup per group of chains).  chain_betas: nullptr, or HOST
-// [repetitions] — a ladder segment: `betas` unused, the kernel takes ResumeLadder in place of Resume and
-// one beta per (padded) chain lies in w_betas.
-int chains_advance_colour(asp_sa_chains *c, double const *betas, double const *chain_betas, uint32_t num_sweeps,
-                          int64_t *trace) {
-  asp_sa_plan *p = c->plan;
-  const asp::SaHostLayout &L = p->host;
-  const uint64_t K = L.num_spins;
-  const uint32_t words = c->words, repetitions = c->repetitions;
-  const bool ladder = chain_betas != nullptr;
-  const ColourLaunch form = choose_colour_launch(p, repetitions, false, trace != nullptr);
-  ColourRun run{p, repetitions, num_sweeps, trace};
-  ASP_TRY(run.shape(form, sweep_lds_bytes(L, form.layout)));
-  const uint64_t padded = run.padded;
-  hipStream_t s = p->stream;
-  asp::StreamFence fence(s);
-  ASP_TRY(run.ensure_work(ladder ? padded : num_sweeps));
-  ASP_TRY(p->w_cur_perm.ensure(padded * L.num_blocks));
-  ASP_TRY(p->w_e_cur.ensure(padded));
-  if (ladder) {
-    ASP_TRY(p->w_betas.upload(chain_betas, repetitions, s));
-  } else {
-    ASP_TRY(p->w_betas.upload(betas, num_sweeps, s));
-  }
-  // (the chains padding the last group: all spins up, integers 0; their results are never read)
-  if (padded > repetitions) {
-    if (ladder) ASP_HIP_TRY(hipMemsetAsync(p->w_betas.ptr + repetitions, 0, (padded - repetitions) * 8, s));
-    const uint64_t tail = (padded - repetitions) * L.num_blocks * sizeof(uint64_t);
-    ASP_HIP_TRY(hipMemsetAsync(p->w_best.ptr + static_cast<uint64_t>(repetitions) * L.num_blocks, 0, tail, s));
-    ASP_HIP_TRY(hipMemsetAsync(p->w_cur_perm.ptr + static_cast<uint64_t>(repetitions) * L.num_blocks, 0, tail, s));
-    ASP_HIP_TRY(hipMemsetAsync(p->w_tracked.ptr + repetitions, 0, (padded - repetitions) * 8, s));
-    ASP_HIP_TRY(hipMemsetAsync(p->w_accepted.ptr + repetitions, 0, (padded - repetitions) * 8, s));
-    ASP_HIP_TRY(hipMemsetAsync(p->w_e_cur.ptr + repetitions, 0, (padded - repetitions) * 8, s));
-  }
-  ASP_HIP_TRY(hipEventRecord(p->ev[0], s));
-  ASP_HIP_TRY(hipMemcpyAsync(p->w_e_cur.ptr, c->e_cur.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
-  ASP_HIP_TRY(hipMemcpyAsync(p->w_tracked.ptr, c->e_best.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
-  ASP_HIP_TRY(hipMemcpyAsync(p->w_accepted.ptr, c->accepted.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
-  ASP_TRY(asp::sa_permute_bits(p, c->x_cur.ptr, repetitions, p->w_cur_perm.ptr));
-  ASP_TRY(asp::sa_permute_bits(p, c->x_best.ptr, repetitions, p->w_best.ptr));
-
-  // (a ladder segment never reads args.betas)
-  ASP_TRY(run.fill(ladder ? nullptr : p->w_betas.ptr, nullptr, c->seed, c->replica_offset));
-  if (ladder) {
-    ASP_TRY(run.launch(colour_kernel_of<SegmentFamily<ResumeLadder>>(run.m, run.layout),
-                       ResumeLadder{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done, p->w_betas.ptr}));
-  } else {
-    ASP_TRY(run.launch(colour_kernel_of<SegmentFamily<Resume>>(run.m, run.layout),
-                       Resume{p->w_cur_perm.ptr, p->w_e_cur.ptr, c->sweeps_done}));
-  }
-  const dim3 grid((words + 3) / 4, (repetitions + kUnpermuteChains - 1) / kUnpermuteChains);
-  hipLaunchKernelGGL(k_unpermute_bits, grid, dim3(256), 0, s, p->w_cur_perm.ptr, L.num_blocks,
-                     p->pos_of_spin.ptr, K, words, repetitions, c->x_cur.ptr);
-  hipLaunchKernelGGL(k_unpermute_bits, grid, dim3(256), 0, s, p->w_best.ptr, L.num_blocks,
-                     p->pos_of_spin.ptr, K, words, repetitions, c->x_best.ptr);
-  ASP_HIP_TRY(hipGetLastError());
-  ASP_HIP_TRY(hipMemcpyAsync(c->e_cur.ptr, p->w_e_cur.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
-  ASP_HIP_TRY(hipMemcpyAsync(c->e_best.ptr, p->w_tracked.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
-  ASP_HIP_TRY(hipMemcpyAsync(c->accepted.ptr, p->w_accepted.ptr, repetitions * 8ull, hipMemcpyDeviceToDevice, s));
-  ASP_HIP_TRY(hipEventRecord(p->ev[3], s));
-  ASP_HIP_TRY(hipMemcpyAsync(c->h_e_cur.data(), p->w_e_cur.ptr, repetitions * 8ull, hipMemcpyDeviceToHost, s));
-  ASP_TRY(run.collect());
-  return run.record(run.layout);
-}
-
-}  // namespace
-
-namespace asp {
-
-int sa_chains_advance_colour(asp_sa_chains *c, double const *betas, uint32_t num_sweeps, int64_t *trace) {
-  return chains_advance_colour(c, betas, nullptr, num_sweeps, trace);
-}
-
-int sa_chains_advance_ladder_colour(asp_sa_chains *c, double const *chain_betas, uint32_t num_sweeps,
-                                    int64_t *trace) {
-  return chains_advance_colour(c, nullptr, chain_betas, num_sweeps, trace);
-}
-
-}  // namespace asp
-
-extern "C" {
-
-int asp_sa_anneal(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_sweeps,
-                  uint32_t repetitions, uint32_t replica_offset, uint64_t const *x0,
-                  uint64_t *out_x, double *out_e) {
-  asp_clear_error();
-  return run_chains(p, seed, betas, num_sweeps, repetitions, replica_offset, x0, false, out_x,
-                    out_e);
-}
-
-int asp_sa_anneal_trace(asp_sa_plan *p, uint64_t seed, double const *betas, uint32_t num_sweeps,
-                        uint32_t repetitions, uint32_t replica_offset, uint64_t const *x0,
-                        uint64_t *out_x, double *out_e, int64_t *out_trace) {
-  asp_clear_error();
-  if (!out_trace) return asp::set_error(ASP_ERR_INVALID, "null trace pointer");
-  return run_chains(p, seed, betas, num_sweeps, repetitions, replica_offset, x0, false, out_x,
-                    out_e, out_trace);
-}
-
-int asp_sa_greedy(asp_sa_plan *p, uint32_t max_sweeps, uint64_t *out_x, double *out_e,
-                  uint32_t *out_sweeps) {
-  asp_clear_error();
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  if (!out_x || !out_e) return asp::set_error(ASP_ERR_INVALID, "null argument");
-  const asp::SaHostLayout &L = p->host;
-  const uint64_t K = L.num_spins;
-  const uint32_t words = static_cast<uint32_t>((K + 63) / 64);
-  if (out_sweeps) *out_sweeps = 0;
-  if (K == 0) {
-    *out_e = 0.0;
-    return ASP_OK;
-  }
-  // 1. strongest-coupling-first cluster merging: on the host (O(E log E)), or the same tree on the
-  // device (asp_sa_set_greedy_tree, csrc/greedy_tree.hip)
-  std::vector<uint64_t> x(words, 0);
-  if (p->greedy_tree != 0) {
-    ASP_TRY(asp::bind_device());
-    const asp::GreedyTreeTarget target{p, nullptr, x.data()};
-    float split_ms[3] = {0.0f, 0.0f, 0.0f};
-    ASP_TRY(asp::greedy_tree_device(&target, 1, p->stream, split_ms));
-    asp::greedy_tree_record_ms(split_ms, false);
-  } else {
-    ASP_TRY(asp::greedy_tree_signs(L, x.data()));
-  }
-  return greedy_relax(p, max_sweeps, x, out_x, out_e, out_sweeps, false);
-}
-
-}  // extern "C"
-
-namespace {
-
-// The device half of asp_sa_greedy for a plan with K > 0; x: the tree's configuration (consumed).
-// exact_sweeps (asp_sa_greedy_batch's items that run alone): *out_sweeps is t, the index of the
-// first sweep that flipped nothing (or max_sweeps), as the shared launches report it, instead of
-// the whole chunks performed.  The chunks only tell which one flipped last; that chunk is then
-// replayed from its start one sweep at a time until the final configuration appears — a fixed
-// point of the deterministic sweep, so the first sweep after it is the one that flips nothing.
-int greedy_relax(asp_sa_plan *p, uint32_t max_sweeps, std::vector<uint64_t> &x, uint64_t *out_x,
-                 double *out_e, uint32_t *out_sweeps, bool exact_sweeps) {
-  const uint32_t words = static_cast<uint32_t>(x.size());
-  // 2. strict-descent relaxation on the device, in chunks, until a chunk flips nothing
-  constexpr uint32_t kChunk = 8;
-  std::vector<double> zeros(kChunk, 0.0);
-  std::vector<uint64_t> next(words, 0);
-  uint32_t done = 0;
-  double energy = 0.0;
-  if (max_sweeps == 0) {
-    ASP_TRY(asp_sa_energy(p, 1, x.data(), &energy));
-  }
-  const bool replay = exact_sweeps && out_sweeps != nullptr;
-  std::vector<uint64_t> flipped_from;  // start of the last chunk that flipped something
-  uint32_t flipped_at = 0, flipped_len = 0;
-  while (done < max_sweeps) {
-    const uint32_t chunk = std::min(kChunk, max_sweeps - done);
-    ASP_TRY(run_chains(p, 0, zeros.data(), chunk, 1, 0, x.data(), true, next.data(), &energy));
-    const bool still = p->last_accepted.empty() || p->last_accepted[0] == 0;
-    if (replay && !still) {
-      flipped_from = x;
-      flipped_at = done;
-      flipped_len = chunk;
-    }
-    done += chunk;
-    x.swap(next);
-    if (still) break;
-  }
-  std::copy(x.begin(), x.end(), out_x);
-  *out_e = energy;
-  if (out_sweeps) *out_sweeps = done;
-  if (replay && max_sweeps != 0) {
-    uint32_t t = 1;  // no chunk flipped: the tree's configuration is a local minimum
-    if (!flipped_from.empty()) {
-      uint32_t u = 0;
-      double unused = 0.0;
-      while (u < flipped_len) {
-        ASP_TRY(run_chains(p, 0, zeros.data(), 1, 1, 0, flipped_from.data(), true, next.data(), &unused));
-        ++u;
-        if (next == x) break;
-        flipped_from.swap(next);
-      }
-      t = std::min(max_sweeps, flipped_at + u + 1u);
-    }
-    *out_sweeps = t;
-  }
-  return ASP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int asp_sa_last_stats(asp_sa_plan const *p, uint32_t count, int64_t *tracked, uint64_t *accepted) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  if (count != p->last_tracked.size()) {
-    return asp::set_error(ASP_ERR_INVALID, "count does not match the last anneal call");
-  }
-  if (tracked) std::copy(p->last_tracked.begin(), p->last_tracked.end(), tracked);
-  if (accepted) std::copy(p->last_accepted.begin(), p->last_accepted.end(), accepted);
-  return ASP_OK;
-}
-
-int asp_sa_last_launch(asp_sa_plan const *p, int *replicas_per_group, int *threads, int *groups) {
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  if (replicas_per_group) *replicas_per_group = p->last_m;
-  if (threads) *threads = p->last_threads;
-  if (groups) *groups = p->last_groups;
-  return ASP_OK;
-}
-
-float asp_sa_last_sweep_ms(asp_sa_plan const *p) { return p ? p->last_sweep_ms : 0.0f; }
-float asp_sa_last_total_ms(asp_sa_plan const *p) { return p ? p->last_total_ms : 0.0f; }
-
-int asp_sa_energy(asp_sa_plan *p, uint32_t count, uint64_t const *x, double *out_e) {
-  asp_clear_error();
-  if (!p) return asp::set_error(ASP_ERR_INVALID, "null plan");
-  ASP_TRY(asp::bind_device());
-  if (count == 0) return ASP_OK;
-  if (!x || !out_e) return asp::set_error(ASP_ERR_INVALID, "null argument");
-  const asp::SaHostLayout &L = p->host;
-  const uint64_t K = L.num_spins;
-  if (K == 0) {
-    for (uint32_t r = 0; r < count; ++r) out_e[r] = 0.0;
-    return ASP_OK;
-  }
-  const uint32_t words = static_cast<uint32_t>((K + 63) / 64);
-  hipStream_t s = p->stream;
-  DeviceBuffer<uint64_t> d_x, d_perm;
-  DeviceBuffer<double> d_partial, d_e;
-  ASP_TRY(d_x.alloc(static_cast<uint64_t>(count) * words));
-  ASP_TRY(d_perm.alloc(static_cast<uint64_t>(count) * L.num_blocks));
-  ASP_TRY(d_partial.alloc(static_cast<uint64_t>(count) * L.num_blocks));
-  ASP_TRY(d_e.alloc(count));
-  ASP_TRY(d_x.upload(x, static_cast<uint64_t>(count) * words, s));
-  ASP_TRY(asp::sa_permute_bits(p, d_x.ptr, count, d_perm.ptr));
-  ASP_TRY(energies_of_perm(p, d_perm.ptr, count, d_partial.ptr, d_e.ptr));
-  ASP_TRY(d_e.download(out_e, count, s));
-  ASP_HIP_TRY(hipStreamSynchronize(s));
-  return ASP_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Batched anneal: many problems, one launch per size class
-// ---------------------------------------------------------------------------
-// The reference's production job is 50 000 sampled clusters of 50-1000 states, extended twice,
-// each solved with 64 chains x 5120 sweeps (Makefile:9,115-127,
-// experiments/sampled_connected_components.py:764-767, common.py:236-239).  One such problem
-// is 64 workgroups of one or two wavefronts that wait on L2 latency at every colour step: a
-// launch per problem leaves > 90 % of the chip idle.  Here the groups of ALL problems of a batch
-// are the workgroups of a few launches (one per wavefront count), so the chip holds hundreds
-// of problems at once and the latency of one hides behind the others.
-
-namespace {
-
-thread_local float g_batch_sweep_ms = 0.0f;
-
 // What asp_sa_anneal_batch and the batched segments (sa_chains_advance_colour_batch) decide alike, in
 // one place: the wavefront counts of the launch classes, and the layout and wavefronts of a problem
 // that fits a byte per position (the thresholds are measured; see asp_sa_anneal_batch).
-constexpr uint32_t kBatchWaves[] = {1, 2, 3, 4, 6, 8, 12, 16};
-constexpr int kNumBatchWaves = sizeof kBatchWaves / sizeof kBatchWaves[0];
 constexpr uint64_t kBatchWideMax = 10000, kBatchSmallMax = 10000;
 
 int batch_waves_index(uint32_t waves) {
@@ -3265,168 +1730,18 @@ uint32_t batch_waves(const asp::SaHostLayout &L) {
   return std::min<uint32_t>(widest_color(L), L.num_spins <= kBatchSmallMax ? 4u : 16u);
 }
 
-// ---- the shared launches of a batch ----
-// What the three batched entry points below (closed anneals, segments of handles, greedy descents) do
-// alike.  A member — a problem of `groups` workgroups taking about `work` each and `lds` bytes — belongs
-// to a class of workgroup shape; a class is ONE launch of 8 * slots_per_xcd workgroups over its XCD-aware
-// slot table [8][slots_per_xcd] (asp::deal_to_xcds, x-major: the kernels read
-// slots[(b & 7) * slots_per_xcd + (b >> 3)]), on a stream of its own so that the classes share the chip.
-struct ClassMember {
-  int cls;
-  double work;
-  uint32_t groups;
-  size_t lds;
-};
-struct ClassLaunch {
-  uint64_t slot_at = 0;
-  uint32_t slots_per_xcd = 0;
-  size_t lds = 0;  // the largest of its members
-  bool used = false;
-  hipEvent_t done = nullptr;  // recorded behind its launch
-};
-template <typename Problem>
-struct ClassKernel {
-  void (*kernel)(BatchArgs<Problem>);
-  uint32_t threads;
-};
-
-// Declared BEFORE the device buffers of an entry point (h_slots outlives the upload; the streams are
-// waited for and released after the buffers' StreamFence).
-struct ClassLauncher {
-  std::vector<ClassLaunch> launches;
-  std::vector<BatchSlot> h_slots;  // the classes' tables one after the other, for ONE upload
-  // [class]; an array, destroyed in reverse: the streams go back to the pool last acquired first, so
-  // every call leaves the pool — and with it the hardware queues of the next call's streams — as it was
-  std::unique_ptr<asp::ScopedStream[]> streams;
-  asp::EventPool events;
-  hipEvent_t begin = nullptr, end = nullptr;  // on the main stream around the launches, with timing
-
-  // The slot tables, and a stream and an event for every used class.
-  int build(const std::vector<ClassMember> &members, int num_classes) {
-    launches.assign(num_classes, ClassLaunch{});
-    streams.reset(new asp::ScopedStream[num_classes]);
-    for (int c = 0; c < num_classes; ++c) {
-      std::vector<uint32_t> of_class;
-      for (uint32_t k = 0; k < members.size(); ++k) {
-        if (members[k].cls != c) continue;
-        of_class.push_back(k);
-        launches[c].lds = std::max(launches[c].lds, members[k].lds);
-      }
-      if (of_class.empty()) continue;
-      std::vector<BatchSlot> per_xcd[asp::kXcds];
-      launches[c].used = true;
-      launches[c].slot_at = h_slots.size();
-      launches[c].slots_per_xcd = asp::deal_to_xcds(
-          of_class, [&](uint32_t k) { return members[k].work; }, [&](uint32_t k) { return members[k].groups; },
-          per_xcd);
-      for (auto &list : per_xcd) h_slots.insert(h_slots.end(), list.begin(), list.end());
-      ASP_TRY(streams[c].acquire());
-      ASP_TRY(events.make(&launches[c].done));
-    }
-    ASP_TRY(events.make(&begin, true));
-    return events.make(&end, true);
-  }
-
-  // Every used class c: kernel_of(c).kernel({problems, its part of the uploaded slot table}) on the
-  // class's stream, between `begin` and `end` on the main stream `s`, which waits for all of them.
-  template <typename Problem, typename KernelOf>
-  int run(hipStream_t s, const Problem *problems, const BatchSlot *d_slots, KernelOf kernel_of) {
-    const int num_classes = static_cast<int>(launches.size());
-    // (classes share kernels and run side by side: a kernel's dynamic-LDS limit is set once, to the
-    // largest class that uses it, before the first launch)
-    std::vector<std::pair<const void *, size_t>> kernel_lds;
-    for (int c = 0; c < num_classes; ++c) {
-      if (!launches[c].used) continue;
-      const void *address = reinterpret_cast<const void *>(kernel_of(c).kernel);
-      auto seen = std::find_if(kernel_lds.begin(), kernel_lds.end(), [&](auto &k) { return k.first == address; });
-      if (seen == kernel_lds.end()) {
-        kernel_lds.emplace_back(address, launches[c].lds);
-      } else {
-        seen->second = std::max(seen->second, launches[c].lds);
-      }
-    }
-    for (auto &k : kernel_lds) ASP_TRY(asp::allow_dynamic_lds(k.first, k.second));
-    const int rc = [&]() -> int {
-      ASP_HIP_TRY(hipEventRecord(begin, s));
-      for (int c = 0; c < num_classes; ++c) {
-        const ClassLaunch &l = launches[c];
-        if (!l.used) continue;
-        const ClassKernel<Problem> k = kernel_of(c);
-        hipStream_t cs = streams[c].stream;
-        ASP_HIP_TRY(hipStreamWaitEvent(cs, begin, 0));
-        hipLaunchKernelGGL(k.kernel, dim3(8u * l.slots_per_xcd), dim3(k.threads), l.lds, cs,
-                           BatchArgs<Problem>{problems, d_slots + l.slot_at, l.slots_per_xcd});
-        ASP_HIP_TRY(hipGetLastError());
-        ASP_HIP_TRY(hipEventRecord(l.done, cs));
-        ASP_HIP_TRY(hipStreamWaitEvent(s, l.done, 0));
-      }
-      ASP_HIP_TRY(hipEventRecord(end, s));
-      return ASP_OK;
-    }();
-    if (rc != ASP_OK) {
-      // the main stream may not have joined every class: wait for them here, so that the caller's
-      // buffers, fenced on the main stream alone, do not go back to the pool under a running class
-      for (int c = 0; c < num_classes; ++c) {
-        if (launches[c].used) (void)hipStreamSynchronize(streams[c].stream);
-      }
-    }
-    return rc;
-  }
-};
-
-// The pass after the sweeps of a batch — reported energies (the kernels and so the reduction order of
-// energies_of_perm) and original-order bits of every chain's best configuration: a problem's descriptor,
-// and the three launches over (problem, chain) slots.
-PostProblem post_problem_of(const asp_sa_plan *p, const uint64_t *best, double *partial, double *out_e,
-                            uint64_t *out_x) {
-  const asp::SaHostLayout &L = p->host;
-  PostProblem pp{};
-  pp.e = EnergyArgs{p->block_width.ptr, p->ell_off.ptr, p->ell_col.ptr, p->ell_val.ptr,
-                    p->field_pos.ptr,   best,           partial,        L.num_blocks};
-  pp.pos_of_spin = p->pos_of_spin.ptr;
-  pp.num_spins = L.num_spins;
-  pp.words = static_cast<uint32_t>((L.num_spins + 63) / 64);
-  pp.diag_sum = L.diag_sum;
-  pp.out_e = out_e;
-  pp.out_x = out_x;
-  return pp;
-}
-// energy_lds: the sign words of the largest problem (num_blocks * 8 bytes), staged in LDS when they fit
-int launch_post_batch(const PostProblem *d_post, const BatchSlot *d_chains, unsigned chains, size_t energy_lds,
-                      size_t max_lds, hipStream_t s) {
-  if (energy_lds > max_lds) {
-    hipLaunchKernelGGL(k_sa_energy_blocks_batch<false>, dim3(chains), dim3(512), 0, s, d_post, d_chains);
-  } else {
-    ASP_TRY(asp::allow_dynamic_lds(reinterpret_cast<const void *>(k_sa_energy_blocks_batch<true>), energy_lds));
-    hipLaunchKernelGGL(k_sa_energy_blocks_batch<true>, dim3(chains), dim3(512), energy_lds, s, d_post, d_chains);
-  }
-  hipLaunchKernelGGL(k_sa_energy_fold_batch, dim3(chains), dim3(64), 0, s, d_post, d_chains);
-  hipLaunchKernelGGL(k_unpermute_bits_batch, dim3(chains), dim3(256), 0, s, d_post, d_chains);
-  ASP_HIP_TRY(hipGetLastError());
-  return ASP_OK;
-}
-
-struct BatchEntry {
-  uint32_t item;     // index into the caller's array
-  uint32_t waves;    // wavefronts per workgroup this problem wants
-  int layout;        // kWide or kBytes; the closed batch: kNibbles or kBits as well
-  double work;       // ~ time of one group: sweeps * ELL slabs
-  uint64_t beta_at;  // offset of its schedule (a ladder segment: its chains' betas) in the concatenated betas
-};
-
 // Chains per workgroup of a batch.  Measured on the production mix (K log-uniform in [1e2, 1e4], 64
 // chains x 5120 sweeps): four replicas per workgroup — the word layout with its one-instruction signs —
 // is fastest from 64 problems (86 G flips/s against 73 with two) over 128 (127 against 101
 // with eight, 95 with two, 62 with one) to 512 (161, the same as eight); fewer replicas per
 // workgroup only when four would leave SIMDs without a wavefront.  Nibble and bit entries count at their
-// fixed group sizes.  chains_of(e.item): the chains of an entry.
-template <typename ChainsOf>
-int batch_chains_per_group(const std::vector<BatchEntry> &entries, int num_cus, ChainsOf chains_of) {
+// fixed group sizes.
+int batch_chains_per_group(const std::vector<BatchEntry> &entries, int num_cus) {
   for (int cand : {4, 2}) {
     uint64_t waves = 0;
     for (const BatchEntry &e : entries) {
       const uint32_t per_group = e.layout == kBits ? 1 : (e.layout == kNibbles ? 4 : cand);
-      waves += static_cast<uint64_t>((chains_of(e.item) + per_group - 1) / per_group) *
+      waves += static_cast<uint64_t>((e.chains + per_group - 1) / per_group) *
                kBatchWaves[batch_waves_index(e.waves)];
     }
     if (waves >= static_cast<uint64_t>(num_cus) * 4u) return cand;
@@ -3434,805 +1749,5 @@ int batch_chains_per_group(const std::vector<BatchEntry> &entries, int num_cus, 
   return 1;
 }
 
-}  // namespace
-
-extern "C" {
-
-float asp_sa_batch_last_ms(void) { return g_batch_sweep_ms; }
-
-int asp_sa_batch_slots_host(uint32_t count, double const *work, uint32_t const *groups, uint32_t *slots_per_xcd,
-                            uint32_t *slots, uint64_t capacity) {
-  asp_clear_error();
-  if (!slots_per_xcd || (count && (!work || !groups))) return asp::set_error(ASP_ERR_INVALID, "null argument");
-  const auto too_small = [&] {
-    return asp::set_error(ASP_ERR_INVALID, "the table does not fit %llu slots",
-                          static_cast<unsigned long long>(slots ? capacity : 0));
-  };
-  // (the eight lists hold all groups between them: a table that cannot fit is refused before it is built)
-  uint64_t all_groups = 0;
-  for (uint32_t k = 0; k < count; ++k) all_groups += groups[k];
-  if (all_groups > capacity) return too_small();
-  std::vector<uint32_t> members(count);
-  std::iota(members.begin(), members.end(), 0u);
-  std::vector<BatchSlot> per_xcd[asp::kXcds];
-  const uint32_t longest = asp::deal_to_xcds(
-      members, [&](uint32_t k) { return work[k]; }, [&](uint32_t k) { return groups[k]; }, per_xcd);
-  if (uint64_t{asp::kXcds} * longest > capacity || (longest && !slots)) return too_small();
-  *slots_per_xcd = longest;
-  for (const auto &list : per_xcd) {
-    for (const BatchSlot &slot : list) {
-      *slots++ = slot.problem;
-      *slots++ = slot.group;
-    }
-  }
-  return ASP_OK;
-}
-
-int asp_sa_anneal_batch(asp_sa_batch_item const *items, uint32_t count) {
-  asp_clear_error();
-  g_batch_sweep_ms = 0.0f;
-  if (count == 0) return ASP_OK;
-  if (!items) return asp::set_error(ASP_ERR_INVALID, "null items");
-  ASP_TRY(asp::bind_device());
-  // ---- validation (the checks of asp_sa_anneal, for every item before anything runs) ----
-  for (uint32_t i = 0; i < count; ++i) {
-    const asp_sa_batch_item &it = items[i];
-    if (!it.plan) return asp::set_error(ASP_ERR_INVALID, "item %u: null plan", i);
-    if (it.repetitions == 0) continue;
-    if (!it.out_x || !it.out_e || (it.num_sweeps && !it.betas)) {
-      return asp::set_error(ASP_ERR_INVALID, "item %u: null argument", i);
-    }
-    if (it.num_sweeps == 0xFFFFFFFFu) {
-      return asp::set_error(ASP_ERR_INVALID, "item %u: num_sweeps 2^32-1 is reserved", i);
-    }
-    if (it.flags & ~static_cast<uint32_t>(ASP_SA_BATCH_SHUFFLED)) {
-      return asp::set_error(ASP_ERR_INVALID, "item %u: unknown flags 0x%x", i, it.flags);
-    }
-    if (static_cast<uint64_t>(it.replica_offset) + it.repetitions + 8 > 0xFFFFFFFFull) {
-      return asp::set_error(ASP_ERR_INVALID, "item %u: replica ids exceed 32 bits", i);
-    }
-    for (uint32_t t = 0; t < it.num_sweeps; ++t) {
-      if (!(it.betas[t] >= 0.0)) {
-        return asp::set_error(ASP_ERR_INVALID, "item %u: betas[%u] is not >= 0", i, t);
-      }
-    }
-    for (uint32_t j = 0; j < i; ++j) {
-      if (items[j].plan == it.plan && items[j].repetitions) {
-        return asp::set_error(ASP_ERR_INVALID, "items %u and %u share a plan", j, i);
-      }
-    }
-  }
-  // ---- which items go into the shared launches ----
-  // Problems whose spins need the bit-packed layouts, plans with a forced launch geometry
-  // (tests, measurements) and a batch of one keep the single-problem path (team sweep included);
-  // items asking for a fresh visiting order every sweep run concurrently on their plans' own
-  // streams (csrc/sa_shuffled.hip).
-  std::vector<BatchEntry> entries;
-  std::vector<uint32_t> alone, shuffled;
-  bool batch_bits = false, batch_nibbles = true;
-  if (const char *env = std::getenv("ASP_BATCH_BITS")) batch_bits = std::atoi(env) != 0;  // tests, measurements
-  if (const char *env = std::getenv("ASP_BATCH_NIBBLES")) batch_nibbles = std::atoi(env) != 0;
-  for (uint32_t i = 0; i < count; ++i) {
-    const asp_sa_batch_item &it = items[i];
-    if (it.repetitions == 0) continue;
-    if (it.flags & ASP_SA_BATCH_SHUFFLED) {
-      shuffled.push_back(i);
-      continue;
-    }
-    const asp_sa_plan *p = it.plan;
-    const asp::SaHostLayout &L = p->host;
-    // A byte per position must fit the LDS, or (up to ~2.4e5 spins) four bits per position with
-    // four chains per workgroup.  Beyond that a chain would be one workgroup with a bit per
-    // position: as a class of the shared launches it was measured and
-    // LOSES against running those problems one after the other as team sweeps, every chain spread
-    // over four CUs (a round of 64 clusters of the pipeline, largest model 157 706 spins: 5.9 s
-    // against 4.05 s; ASP_BATCH_BITS=1 puts them into the shared launches all the same).
-    const bool bytes_fit = L.num_spins > 0 && sweep_lds_bytes(L, kBytes) <= p->spin_lds();
-    const bool nibbles_fit = L.num_spins > 0 && sweep_lds_bytes(L, kNibbles) <= p->spin_lds() && batch_nibbles;
-    const bool bits_fit = L.num_spins > 0 && sweep_lds_bytes(L, kBits) <= p->spin_lds() && batch_bits;
-    if (!(bytes_fit || nibbles_fit || bits_fit) || p->force_m || p->force_threads || p->force_packed) {
-      alone.push_back(i);
-      continue;
-    }
-    BatchEntry e{};
-    e.item = i;
-    // Layout and wavefronts per workgroup in a shared launch.  Small problems — several
-    // workgroups fit a CU — take the word layout (one-instruction signs) and 4 wavefronts: small
-    // workgroups interleave better than the 16 a lone problem wants (cap 16 / 8 / 4 on clusters of
-    // 1e2..1e4 spins, 128 problems: 109 / 133 / 152 G flips/s, 512: 152 / 200 / 213).  Larger ones keep a byte per spin — the word layout would leave them
-    // one workgroup per CU — and take 16 wavefronts (the sampled-cluster pipeline's order-2 models,
-    // 1e4..2e5 spins, cap 4 / 8 / 16: 150 / 234 / 279 G flips/s; profiles/r03_batch_tune_real.txt).
-    // (kBatchWideMax, kBatchSmallMax: both 10000)
-    e.layout = !bytes_fit ? (nibbles_fit ? kNibbles : kBits) : batch_layout_in_lds(p);
-    e.waves = batch_waves(L);
-    e.work = static_cast<double>(it.num_sweeps) * static_cast<double>(L.ell_off.back() + L.num_blocks);
-    entries.push_back(e);
-  }
-  if (entries.size() == 1) {
-    alone.push_back(entries[0].item);
-    entries.clear();
-  }
-  if (!shuffled.empty()) {
-    ASP_TRY(asp::sa_shuffled_batch(items, shuffled.data(), static_cast<uint32_t>(shuffled.size()),
-                                   &g_batch_sweep_ms));
-  }
-  for (uint32_t i : alone) {
-    const asp_sa_batch_item &it = items[i];
-    ASP_TRY(run_chains(it.plan, it.seed, it.betas, it.num_sweeps, it.repetitions, it.replica_offset,
-                       nullptr, false, it.out_x, it.out_e));
-    g_batch_sweep_ms += it.plan->last_sweep_ms;
-  }
-  if (entries.empty()) return ASP_OK;
-
-  const asp_sa_plan *first = items[entries[0].item].plan;
-  const int num_cus = first->num_cus;
-  const size_t max_lds = first->max_lds;
-  // ---- size classes: workgroups of one launch have one thread count ----
-  // A launch class = (wavefront count, spin layout): kWaves[c / 4] wavefronts, layout c % 4.
-  const auto &kWaves = kBatchWaves;
-  static const int kLayouts[] = {kWide, kBytes, kBits, kNibbles};
-  constexpr int kNumWaves = kNumBatchWaves;
-  constexpr int kNumClasses = 4 * kNumWaves;
-  auto class_of = [&](const BatchEntry &e) {
-    const int w = batch_waves_index(e.waves);
-    return 4 * w + (e.layout == kWide ? 0 : (e.layout == kBytes ? 1 : (e.layout == kBits ? 2 : 3)));
-  };
-  auto waves_of_class = [&](int c) { return kWaves[c / 4]; };
-  auto layout_of_class = [&](int c) { return kLayouts[c % 4]; };
-  // ---- replicas per workgroup, per class (batch_chains_per_group) ----
-  int m_of_class[kNumClasses];
-  {
-    const int m = batch_chains_per_group(entries, num_cus, [&](uint32_t i) { return items[i].repetitions; });
-    for (int c = 0; c < kNumClasses; ++c) m_of_class[c] = m;
-    // (fewer replicas per workgroup for the classes of the largest problems, to shorten the
-    // batch's longest workgroup, was measured and LOSES: 123 -> 97 G flips/s at 128 problems,
-    // 157 -> 120 at 512; the word layout's efficiency outweighs the shorter tail)
-    if (const char *env = std::getenv("ASP_BATCH_M")) {  // tuning aid
-      const int forced = std::atoi(env);
-      if (forced == 1 || forced == 2 || forced == 4 || forced == 8) {
-        for (int c = 0; c < kNumClasses; ++c) m_of_class[c] = forced;
-      }
-    }
-    for (int c = 0; c < kNumClasses; ++c) {
-      if (layout_of_class(c) == kBits) m_of_class[c] = 1;  // a bit per position: one chain per workgroup
-      if (layout_of_class(c) == kNibbles) m_of_class[c] = 4;
-      // the word layout exists for four replicas: with another count its problems take bytes
-    }
-  }
-  auto m_of = [&](const BatchEntry &e) { return m_of_class[class_of(e)]; };
-  for (BatchEntry &e : entries) {
-    if (e.layout == kWide && m_of(e) != 4) e.layout = kBytes;
-  }
-  // ---- per-problem buffer offsets ----
-  struct Offsets {
-    uint64_t best, stat, cache, partial, e, x, groups, padded;
-  };
-  std::vector<Offsets> off(entries.size());
-  uint64_t n_best = 0, n_stat = 0, n_cache = 0, n_partial = 0, n_e = 0, n_x = 0, n_betas = 0;
-  bool use_cache = true;
-  for (size_t k = 0; k < entries.size(); ++k) {
-    const asp_sa_batch_item &it = items[entries[k].item];
-    const asp::SaHostLayout &L = it.plan->host;
-    const uint64_t m = static_cast<uint64_t>(m_of(entries[k]));
-    const uint64_t groups = (it.repetitions + m - 1) / m, padded = groups * m;
-    const uint64_t words = (L.num_spins + 63) / 64;
-    off[k] = Offsets{n_best, n_stat, n_cache, n_partial, n_e, n_x, groups, padded};
-    n_best += padded * L.num_blocks;
-    n_stat += padded;
-    if (entries[k].layout != kBits) n_cache += padded * L.num_blocks * 64ull;
-    n_partial += static_cast<uint64_t>(it.repetitions) * L.num_blocks;
-    n_e += it.repetitions;
-    n_x += static_cast<uint64_t>(it.repetitions) * words;
-    entries[k].beta_at = n_betas;
-    n_betas += it.num_sweeps;
-    use_cache = use_cache && it.plan->use_field_cache;
-  }
-  if (n_cache * sizeof(double) > (32ull << 30)) use_cache = false;
-
-  asp::ScopedStream main_stream;
-  ASP_TRY(main_stream.acquire());
-  hipStream_t s = main_stream.stream;
-  ClassLauncher launcher;
-  DeviceBuffer<double> d_betas, d_partial, d_e, d_cache;
-  DeviceBuffer<uint64_t> d_best, d_x;
-  DeviceBuffer<long long> d_tracked;
-  DeviceBuffer<unsigned long long> d_accepted;
-  DeviceBuffer<SweepArgs> d_problems;
-  DeviceBuffer<PostProblem> d_post;
-  DeviceBuffer<BatchSlot> d_slots, d_chains;
-  asp::StreamFence fence(s);
-  ASP_TRY(d_betas.alloc(n_betas));
-  ASP_TRY(d_best.alloc(n_best));
-  ASP_TRY(d_tracked.alloc(n_stat));
-  ASP_TRY(d_accepted.alloc(n_stat));
-  ASP_TRY(d_partial.alloc(n_partial));
-  ASP_TRY(d_e.alloc(n_e));
-  ASP_TRY(d_x.alloc(n_x));
-  if (use_cache && d_cache.alloc(n_cache) != ASP_OK) {
-    asp_clear_error();  // the cache is an optimisation: run without it
-    use_cache = false;
-  }
-  // ---- descriptors ----
-  std::vector<double> h_betas(n_betas);
-  std::vector<SweepArgs> h_problems(entries.size());
-  std::vector<PostProblem> h_post(entries.size());
-  std::vector<BatchSlot> h_chains;
-  std::vector<ClassMember> members(entries.size());
-  h_chains.reserve(n_e);
-  size_t energy_lds = 0;
-  for (size_t k = 0; k < entries.size(); ++k) {
-    const asp_sa_batch_item &it = items[entries[k].item];
-    const asp_sa_plan *p = it.plan;
-    const asp::SaHostLayout &L = p->host;
-    const bool packed = entries[k].layout == kBits;
-    std::copy(it.betas, it.betas + it.num_sweeps, h_betas.begin() + entries[k].beta_at);
-    // (of the plan's part only the couplings' columns depend on the layout here: kWide or not)
-    SweepArgs a = sweep_args(p, entries[k].layout, d_betas.ptr + entries[k].beta_at, nullptr, d_best.ptr + off[k].best,
-                             d_tracked.ptr + off[k].stat, d_accepted.ptr + off[k].stat, it.seed, it.num_sweeps,
-                             it.replica_offset);
-    // (the bit-packed layout runs without the field cache, as in the single-problem launch)
-    a.field_cache = use_cache && !packed ? d_cache.ptr + off[k].cache : nullptr;
-    a.cache_enter_flips = packed ? 0u : cache_enter_flips_of(L);
-    h_problems[k] = a;
-    h_post[k] = post_problem_of(p, d_best.ptr + off[k].best, d_partial.ptr + off[k].partial, d_e.ptr + off[k].e,
-                                d_x.ptr + off[k].x);
-    for (uint32_t r = 0; r < it.repetitions; ++r) {
-      h_chains.push_back(BatchSlot{static_cast<uint32_t>(k), r});
-    }
-    energy_lds = std::max(energy_lds, static_cast<size_t>(L.num_blocks) * sizeof(uint64_t));
-    const int c = class_of(entries[k]);
-    members[k] = ClassMember{c, entries[k].work, static_cast<uint32_t>(off[k].groups),
-                             sweep_lds_bytes(L, layout_of_class(c))};
-  }
-  // ---- slot tables: per class, problems longest first, dealt to the 8 XCDs ----
-  ASP_TRY(launcher.build(members, kNumClasses));
-  const std::vector<BatchSlot> &h_slots = launcher.h_slots;
-  ASP_TRY(d_problems.alloc(h_problems.size()));
-  ASP_TRY(d_post.alloc(h_post.size()));
-  ASP_TRY(d_slots.alloc(h_slots.size()));
-  ASP_TRY(d_chains.alloc(h_chains.size()));
-  ASP_TRY(d_betas.upload(h_betas.data(), h_betas.size(), s));
-  ASP_TRY(d_problems.upload(h_problems.data(), h_problems.size(), s));
-  ASP_TRY(d_post.upload(h_post.data(), h_post.size(), s));
-  ASP_TRY(d_slots.upload(h_slots.data(), h_slots.size(), s));
-  ASP_TRY(d_chains.upload(h_chains.data(), h_chains.size(), s));
-  ASP_HIP_TRY(hipMemsetAsync(d_accepted.ptr, 0, n_stat * sizeof(unsigned long long), s));
-  // ---- one sweep launch per class ----
-  ASP_TRY(launcher.run(s, d_problems.ptr, d_slots.ptr, [&](int c) {
-    // (a class of words has four chains per workgroup: with another count its problems took bytes)
-    return ClassKernel<SweepArgs>{colour_kernel_of<BatchFamily<SweepArgs>>(m_of_class[c], layout_of_class(c)),
-                                  64u * waves_of_class(c)};
-  }));
-  // ---- energies and original-order bits of every chain's best configuration ----
-  ASP_TRY(launch_post_batch(d_post.ptr, d_chains.ptr, static_cast<unsigned>(h_chains.size()), energy_lds, max_lds,
-                            s));
-  std::vector<uint64_t> h_x(n_x);
-  std::vector<double> h_e(n_e);
-  std::vector<long long> h_tracked(n_stat);
-  std::vector<unsigned long long> h_accepted(n_stat);
-  ASP_TRY(d_x.download(h_x.data(), n_x, s));
-  ASP_TRY(d_e.download(h_e.data(), n_e, s));
-  ASP_TRY(d_tracked.download(h_tracked.data(), n_stat, s));
-  ASP_TRY(d_accepted.download(h_accepted.data(), n_stat, s));
-  ASP_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.0f;
-  ASP_HIP_TRY(hipEventElapsedTime(&ms, launcher.begin, launcher.end));
-  g_batch_sweep_ms += ms;
-  for (size_t k = 0; k < entries.size(); ++k) {
-    const asp_sa_batch_item &it = items[entries[k].item];
-    asp_sa_plan *p = it.plan;
-    const uint64_t words = (p->host.num_spins + 63) / 64;
-    std::copy(h_x.begin() + off[k].x, h_x.begin() + off[k].x + it.repetitions * words, it.out_x);
-    std::copy(h_e.begin() + off[k].e, h_e.begin() + off[k].e + it.repetitions, it.out_e);
-    p->last_tracked.assign(h_tracked.begin() + off[k].stat,
-                           h_tracked.begin() + off[k].stat + it.repetitions);
-    p->last_accepted.assign(h_accepted.begin() + off[k].stat,
-                            h_accepted.begin() + off[k].stat + it.repetitions);
-    const int c = class_of(entries[k]);
-    p->last_m = m_of_class[c];
-    p->last_layout = p->last_spin_layout = layout_of_class(c);
-    p->last_threads = static_cast<int>(64u * waves_of_class(c));
-    p->last_groups = static_cast<int>(off[k].groups);
-    p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_batch_last_ms
-  }
-  return ASP_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Batched segments of resumable chains, colour order (asp_sa_chains_advance_batch)
-// ---------------------------------------------------------------------------
-// The launch grouping of asp_sa_anneal_batch — one launch per wavefront count and layout class (a
-// word or a byte per position), four or two chains per workgroup when that still fills the chip —
-// with ResumeProblem descriptors in place of SweepArgs, and the handles' state permuted in and
-// out by one launch each way.  Segments that need the bit-packed layouts, plans with a forced
-// geometry or layout, traced segments and a group of one run as sa_chains_advance_colour.
-// Two deliberate differences from the closed batch, whose helpers (kBatchWaves, batch_layout_in_lds,
-// batch_waves) this shares: a cluster beyond a byte per position runs alone here even where four bits
-// per position would fit (the nibble class has no resume form), and the closed batch's tuning aid
-// ASP_BATCH_M is not read (chains per workgroup never change a result).
-
-// A batch of LADDER segments (asp_sa_chains_advance_ladder_batch; every segment with chain_betas): the
-// same grouping, class rule, LDS limit and state permute, with LadderProblem descriptors; the per-chain
-// betas of all handles go up in the one concatenated buffer, every handle's part padded with zeros to
-// whole groups; the segments that run alone take
-// sa_chains_advance_ladder_colour.
-
-namespace asp {
-
-namespace {
-
-template <bool LADDER>
-int chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms) {
-  using Problem = std::conditional_t<LADDER, LadderProblem, ResumeProblem>;
-  std::vector<BatchEntry> entries;  // (item: index into segs)
-  std::vector<uint32_t> alone;
-  for (uint32_t i = 0; i < count; ++i) {
-    const asp_sa_plan *p = segs[i].chains->plan;
-    const SaHostLayout &L = p->host;
-    const bool bytes_fit = sweep_lds_bytes(L, kBytes) <= p->spin_lds();
-    if (segs[i].trace || !bytes_fit || p->force_m || p->force_threads || p->force_packed) {
-      alone.push_back(i);
-      continue;
-    }
-    // (layout and wavefronts per workgroup in a shared launch: asp_sa_anneal_batch's, measured there)
-    BatchEntry e{};
-    e.item = i;
-    e.layout = batch_layout_in_lds(p);
-    e.waves = batch_waves(L);
-    e.work = static_cast<double>(segs[i].num_sweeps) * static_cast<double>(L.ell_off.back() + L.num_blocks);
-    entries.push_back(e);
-  }
-  if (entries.size() == 1) {
-    alone.push_back(entries[0].item);
-    entries.clear();
-  }
-  for (uint32_t i : alone) {
-    asp_sa_plan *p = segs[i].chains->plan;
-    p->last_sweep_ms = p->last_total_ms = 0.0f;
-    if constexpr (LADDER) {
-      ASP_TRY(sa_chains_advance_ladder_colour(segs[i].chains, segs[i].chain_betas, segs[i].num_sweeps, segs[i].trace));
-    } else {
-      ASP_TRY(sa_chains_advance_colour(segs[i].chains, segs[i].betas, segs[i].num_sweeps, segs[i].trace));
-    }
-    if (sweep_ms) *sweep_ms += p->last_sweep_ms;
-  }
-  if (entries.empty()) return ASP_OK;
-
-  const auto &kWaves = kBatchWaves;
-  constexpr int kNumClasses = 2 * kNumBatchWaves;  // class = 2 * (index of the wavefront count) + (bytes ? 1 : 0)
-  // chains per workgroup for the batch (asp_sa_anneal_batch's rule)
-  const int m = batch_chains_per_group(entries, segs[entries[0].item].chains->plan->num_cus,
-                                       [&](uint32_t i) { return segs[i].chains->repetitions; });
-  for (BatchEntry &e : entries) {
-    if (e.layout == kWide && m != 4) e.layout = kBytes;  // (the word layout exists for four chains)
-  }
-  auto class_of = [&](const BatchEntry &e) { return 2 * batch_waves_index(e.waves) + (e.layout == kWide ? 0 : 1); };
-  // ---- per-handle offsets into the launch's buffers ----
-  struct Offsets {
-    uint64_t perm, stat, cache, groups, padded;
-  };
-  std::vector<Offsets> off(entries.size());
-  uint64_t n_perm = 0, n_stat = 0, n_cache = 0, n_betas = 0, n_chains = 0;
-  bool use_cache = true;
-  for (size_t k = 0; k < entries.size(); ++k) {
-    const asp_sa_chains *c = segs[entries[k].item].chains;
-    const SaHostLayout &L = c->plan->host;
-    const uint64_t groups = (c->repetitions + static_cast<uint64_t>(m) - 1) / m, padded = groups * m;
-    off[k] = Offsets{n_perm, n_stat, n_cache, groups, padded};
-    n_perm += padded * L.num_blocks;
-    n_stat += padded;
-    n_cache += padded * L.num_blocks * 64ull;
-    n_chains += c->repetitions;
-    entries[k].beta_at = n_betas;
-    n_betas += LADDER ? padded : segs[entries[k].item].num_sweeps;  // (a ladder: one beta per padded chain)
-    use_cache = use_cache && c->plan->use_field_cache;
-  }
-  if (n_cache * sizeof(double) > (32ull << 30)) use_cache = false;
-
-  ScopedStream main_stream;
-  ASP_TRY(main_stream.acquire());
-  hipStream_t s = main_stream.stream;
-  ClassLauncher launcher;
-  DeviceBuffer<double> d_betas, d_cache;
-  DeviceBuffer<uint64_t> d_best, d_cur;
-  DeviceBuffer<long long> d_tracked, d_e_cur;
-  DeviceBuffer<unsigned long long> d_accepted;
-  DeviceBuffer<Problem> d_problems;
-  DeviceBuffer<ChainsIo> d_io;
-  DeviceBuffer<BatchSlot> d_slots, d_chains_in, d_chains_out;
-  StreamFence fence(s);
-  ASP_TRY(d_betas.alloc(n_betas));
-  ASP_TRY(d_best.alloc(n_perm));
-  ASP_TRY(d_cur.alloc(n_perm));
-  ASP_TRY(d_tracked.alloc(n_stat));
-  ASP_TRY(d_e_cur.alloc(n_stat));
-  ASP_TRY(d_accepted.alloc(n_stat));
-  if (use_cache && d_cache.alloc(n_cache) != ASP_OK) {
-    asp_clear_error();  // the cache is an optimisation: run without it
-    use_cache = false;
-  }
-  // ---- descriptors ----
-  std::vector<double> h_betas(n_betas, 0.0);  // (a ladder: the chains padding a last group stay 0)
-  std::vector<Problem> h_problems(entries.size());
-  std::vector<ChainsIo> h_io(entries.size());
-  std::vector<BatchSlot> h_chains_in, h_chains_out;
-  std::vector<ClassMember> members(entries.size());
-  h_chains_in.reserve(n_stat);
-  h_chains_out.reserve(n_chains);
-  for (size_t k = 0; k < entries.size(); ++k) {
-    const ChainsSegment &seg = segs[entries[k].item];
-    asp_sa_chains *c = seg.chains;
-    const asp_sa_plan *p = c->plan;
-    const SaHostLayout &L = p->host;
-    if constexpr (LADDER) {
-      std::copy(seg.chain_betas, seg.chain_betas + c->repetitions, h_betas.begin() + entries[k].beta_at);
-    } else {
-      std::copy(seg.betas, seg.betas + seg.num_sweeps, h_betas.begin() + entries[k].beta_at);
-    }
-    Problem rp{};
-    // (a ladder segment never reads s.betas)
-    rp.s = sweep_args(p, entries[k].layout, LADDER ? nullptr : d_betas.ptr + entries[k].beta_at, nullptr,
-                      d_best.ptr + off[k].perm, d_tracked.ptr + off[k].stat, d_accepted.ptr + off[k].stat, c->seed,
-                      seg.num_sweeps, c->replica_offset);
-    rp.s.field_cache = use_cache ? d_cache.ptr + off[k].cache : nullptr;
-    rp.s.cache_enter_flips = cache_enter_flips_of(L);
-    if constexpr (LADDER) {
-      rp.r = ResumeLadder{d_cur.ptr + off[k].perm, d_e_cur.ptr + off[k].stat, c->sweeps_done,
-                          d_betas.ptr + entries[k].beta_at};
-    } else {
-      rp.r = Resume{d_cur.ptr + off[k].perm, d_e_cur.ptr + off[k].stat, c->sweeps_done};
-    }
-    h_problems[k] = rp;
-    ChainsIo io{};
-    io.x_cur = c->x_cur.ptr;
-    io.x_best = c->x_best.ptr;
-    io.e_cur = c->e_cur.ptr;
-    io.e_best = c->e_best.ptr;
-    io.accepted = c->accepted.ptr;
-    io.cur_perm = rp.r.cur_perm;
-    io.best_perm = rp.s.best_perm;
-    io.w_e_cur = rp.r.e_cur;
-    io.w_tracked = rp.s.tracked;
-    io.w_accepted = rp.s.accepted;
-    io.spin_of_pos = p->spin_of_pos.ptr;
-    io.pos_of_spin = p->pos_of_spin.ptr;
-    io.num_spins = L.num_spins;
-    io.num_blocks = L.num_blocks;
-    io.words = c->words;
-    io.chains = c->repetitions;
-    h_io[k] = io;
-    for (uint32_t r = 0; r < off[k].padded; ++r) h_chains_in.push_back(BatchSlot{static_cast<uint32_t>(k), r});
-    for (uint32_t r = 0; r < c->repetitions; ++r) h_chains_out.push_back(BatchSlot{static_cast<uint32_t>(k), r});
-    const int cl = class_of(entries[k]);
-    members[k] = ClassMember{cl, entries[k].work, static_cast<uint32_t>(off[k].groups),
-                             sweep_lds_bytes(L, cl % 2 == 0 ? kWide : kBytes)};
-  }
-  // ---- slot tables: per class, handles longest first, dealt to the 8 XCDs ----
-  ASP_TRY(launcher.build(members, kNumClasses));
-  const std::vector<BatchSlot> &h_slots = launcher.h_slots;
-  ASP_TRY(d_problems.alloc(h_problems.size()));
-  ASP_TRY(d_io.alloc(h_io.size()));
-  ASP_TRY(d_slots.alloc(h_slots.size()));
-  ASP_TRY(d_chains_in.alloc(h_chains_in.size()));
-  ASP_TRY(d_chains_out.alloc(h_chains_out.size()));
-  ASP_TRY(d_betas.upload(h_betas.data(), h_betas.size(), s));
-  ASP_TRY(d_problems.upload(h_problems.data(), h_problems.size(), s));
-  ASP_TRY(d_io.upload(h_io.data(), h_io.size(), s));
-  ASP_TRY(d_slots.upload(h_slots.data(), h_slots.size(), s));
-  ASP_TRY(d_chains_in.upload(h_chains_in.data(), h_chains_in.size(), s));
-  ASP_TRY(d_chains_out.upload(h_chains_out.data(), h_chains_out.size(), s));
-  hipLaunchKernelGGL(k_chains_permute_problems, dim3(static_cast<unsigned>(h_chains_in.size())), dim3(256), 0, s,
-                     d_io.ptr, d_chains_in.ptr);
-  ASP_HIP_TRY(hipGetLastError());
-  // ---- one sweep launch per class ----
-  ASP_TRY(launcher.run(s, d_problems.ptr, d_slots.ptr, [&](int cl) {
-    return ClassKernel<Problem>{colour_kernel_of<BatchFamily<Problem>>(cl % 2 == 0 ? 4 : m, cl % 2 == 0 ? kWide : kBytes),
-                                64u * kWaves[cl / 2]};
-  }));
-  // ---- the state back into the handles (after the attempt: the colour order has no retry) ----
-  hipLaunchKernelGGL(k_chains_unpermute_problems, dim3(static_cast<unsigned>(h_chains_out.size())), dim3(256), 0, s,
-                     d_io.ptr, d_chains_out.ptr);
-  ASP_HIP_TRY(hipGetLastError());
-  ASP_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.0f;
-  ASP_HIP_TRY(hipEventElapsedTime(&ms, launcher.begin, launcher.end));
-  if (sweep_ms) *sweep_ms += ms;
-  for (size_t k = 0; k < entries.size(); ++k) {
-    asp_sa_plan *p = segs[entries[k].item].chains->plan;
-    const int cl = class_of(entries[k]);
-    p->last_m = m;
-    p->last_layout = p->last_spin_layout = cl % 2 == 0 ? kWide : kBytes;
-    p->last_threads = static_cast<int>(64u * kWaves[cl / 2]);
-    p->last_groups = static_cast<int>(off[k].groups);
-    p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_chains_batch_last_ms
-  }
-  return ASP_OK;
-}
-
-}  // namespace
-
-int sa_chains_advance_colour_batch(const ChainsSegment *segs, uint32_t count, float *sweep_ms) {
-  if (count != 0 && segs[0].chain_betas) return chains_advance_colour_batch<true>(segs, count, sweep_ms);
-  return chains_advance_colour_batch<false>(segs, count, sweep_ms);
-}
-
+}  // namespace colour
 }  // namespace asp
-
-// ---------------------------------------------------------------------------
-// Batched greedy solve: many problems' descents in shared launches
-// ---------------------------------------------------------------------------
-// The reference's production job solves tens of thousands of sampled clusters, three models each,
-// with sa.greedy_solve (Makefile:115-127, experiments/sampled_connected_components.py:696-751).
-// asp_sa_greedy spends one workgroup, ~25 launches and a host round trip every 8 sweeps on each.
-// Here the host trees of all items run on a small thread pool, their signs go up in ONE copy and
-// are permuted by ONE launch, every problem is a workgroup of a few shared descent
-// launches (one per wavefront count) that decides on the device when it has converged, and the
-// energies, configurations and sweep counts come back in one copy each.
-
-namespace {
-
-thread_local float g_greedy_tree_ms = 0.0f, g_greedy_descent_ms = 0.0f;
-
-}  // namespace
-
-extern "C" {
-
-int asp_sa_greedy_batch_last_ms(float *tree_ms, float *descent_ms) {
-  if (tree_ms) *tree_ms = g_greedy_tree_ms;
-  if (descent_ms) *descent_ms = g_greedy_descent_ms;
-  return ASP_OK;
-}
-
-int asp_sa_greedy_batch(asp_sa_greedy_item const *items, uint32_t count) {
-  asp_clear_error();
-  g_greedy_tree_ms = g_greedy_descent_ms = 0.0f;
-  if (count == 0) return ASP_OK;
-  if (!items) return asp::set_error(ASP_ERR_INVALID, "null items");
-  // ---- validation: every item before anything runs or is written ----
-  for (uint32_t i = 0; i < count; ++i) {
-    const asp_sa_greedy_item &it = items[i];
-    if (!it.plan) return asp::set_error(ASP_ERR_INVALID, "item %u: null plan", i);
-    if (!it.out_x || !it.out_e) return asp::set_error(ASP_ERR_INVALID, "item %u: null output", i);
-    if (it.flags != 0) return asp::set_error(ASP_ERR_INVALID, "item %u: unknown flags 0x%x", i, it.flags);
-  }
-  {
-    std::vector<std::pair<const asp_sa_plan *, uint32_t>> plans(count);
-    for (uint32_t i = 0; i < count; ++i) plans[i] = {items[i].plan, i};
-    std::sort(plans.begin(), plans.end());
-    for (uint32_t i = 1; i < count; ++i) {
-      if (plans[i].first == plans[i - 1].first) {
-        return asp::set_error(ASP_ERR_INVALID, "items %u and %u share a plan", plans[i - 1].second,
-                              plans[i].second);
-      }
-    }
-  }
-  ASP_TRY(asp::bind_device());
-  // ---- which items go into the shared launches ----
-  // A byte per position must fit the LDS (up to ~1.3e5 spins); problems beyond that, plans with a
-  // forced launch geometry, layout or team size, and a batch of one take asp_sa_greedy's device
-  // half (team sweep included).  Results never depend on the path.
-  std::vector<uint32_t> live, shared, alone;  // live: K > 0, in item order
-  for (uint32_t i = 0; i < count; ++i) {
-    const asp_sa_greedy_item &it = items[i];
-    const asp_sa_plan *p = it.plan;
-    if (it.out_sweeps) *it.out_sweeps = 0;
-    if (p->host.num_spins == 0) {
-      *it.out_e = 0.0;
-      continue;
-    }
-    live.push_back(i);
-    const bool forced = p->force_m || p->force_threads || p->force_packed || p->team_mode >= 2;
-    if (forced || sweep_lds_bytes(p->host, kBytes) > p->spin_lds()) {
-      alone.push_back(i);
-    } else {
-      shared.push_back(i);
-    }
-  }
-  if (shared.size() == 1) {
-    alone.push_back(shared[0]);
-    shared.clear();
-  }
-  if (live.empty()) return ASP_OK;
-  // ---- the trees: the host trees of the live items that ask for them, on the pool (greedy.cpp); the
-  // device trees (asp_sa_set_greedy_tree, csrc/greedy_tree.hip) of the items that run alone here, and
-  // those of the shared launches below, straight into the buffer the state permute reads ----
-  std::vector<uint64_t> tree_at(count, 0);  // offset of item i's words in h_x0
-  uint64_t n_words = 0;
-  for (uint32_t i : live) {
-    tree_at[i] = n_words;
-    n_words += (items[i].plan->host.num_spins + 63) / 64;
-  }
-  std::vector<uint64_t> h_x0(n_words, 0);
-  {
-    std::vector<const asp::SaHostLayout *> layouts;
-    std::vector<uint64_t *> outs;
-    for (uint32_t i : live) {
-      if (items[i].plan->greedy_tree != 0) continue;
-      layouts.push_back(&items[i].plan->host);
-      outs.push_back(h_x0.data() + tree_at[i]);
-    }
-    if (!layouts.empty()) {
-      const auto t0 = std::chrono::steady_clock::now();
-      asp::greedy_tree_signs_many(layouts.data(), outs.data(), layouts.size());
-      g_greedy_tree_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-  }
-  bool device_trees_ran = false;
-  {
-    std::vector<asp::GreedyTreeTarget> targets;
-    for (uint32_t i : alone) {
-      if (items[i].plan->greedy_tree != 0) {
-        targets.push_back(asp::GreedyTreeTarget{items[i].plan, nullptr, h_x0.data() + tree_at[i]});
-      }
-    }
-    if (!targets.empty()) {
-      asp::ScopedStream tree_stream;
-      ASP_TRY(tree_stream.acquire());
-      float split_ms[3] = {0.0f, 0.0f, 0.0f};
-      ASP_TRY(asp::greedy_tree_device(targets.data(), static_cast<uint32_t>(targets.size()), tree_stream.stream,
-                                      split_ms));
-      asp::greedy_tree_record_ms(split_ms, false);
-      device_trees_ran = true;
-      g_greedy_tree_ms += split_ms[0] + split_ms[1] + split_ms[2];
-    }
-  }
-  for (uint32_t i : alone) {
-    const asp_sa_greedy_item &it = items[i];
-    const uint64_t words = (it.plan->host.num_spins + 63) / 64;
-    std::vector<uint64_t> x(h_x0.begin() + tree_at[i], h_x0.begin() + tree_at[i] + words);
-    ASP_TRY(greedy_relax(it.plan, it.max_sweeps, x, it.out_x, it.out_e, it.out_sweeps, true));
-    g_greedy_descent_ms += it.plan->last_sweep_ms;  // (the last chunk's; see asp_sa_greedy_batch_last_ms)
-  }
-  if (shared.empty()) return ASP_OK;
-
-  // ---- launch classes: workgroups of one launch have one wavefront count (kBatchWaves) ----
-  const size_t n = shared.size();
-  struct Offsets {
-    uint64_t blocks, cache, x;  // best / x0_perm / partial rows; field cache; packed words
-  };
-  std::vector<Offsets> off(n);
-  std::vector<ClassMember> members(n);
-  uint64_t n_blocks = 0, n_cache = 0, n_x = 0;
-  size_t energy_lds = 0;
-  bool use_cache = true;
-  for (size_t k = 0; k < n; ++k) {
-    const asp_sa_plan *p = items[shared[k]].plan;
-    const asp::SaHostLayout &L = p->host;
-    off[k] = Offsets{n_blocks, n_cache, n_x};
-    n_blocks += L.num_blocks;
-    n_cache += static_cast<uint64_t>(L.num_blocks) * 64ull;
-    n_x += (L.num_spins + 63) / 64;
-    // one wavefront per block of the widest colour class, at most 16: the single path's choice
-    const uint32_t waves = std::min<uint32_t>(widest_color(L), 16u);
-    // (every member is one workgroup: the dealing to the XCDs comes out round-robin)
-    members[k] = ClassMember{batch_waves_index(waves), static_cast<double>(L.ell_off.back() + L.num_blocks), 1u,
-                             sweep_lds_bytes(L, kBytes)};
-    energy_lds = std::max(energy_lds, static_cast<size_t>(L.num_blocks) * sizeof(uint64_t));
-    use_cache = use_cache && p->use_field_cache;
-  }
-  if (n_cache * sizeof(double) > (32ull << 30)) use_cache = false;
-  const size_t max_lds = items[shared[0]].plan->max_lds;
-
-  // (host arrays of the asynchronous uploads first, so that they outlive the stream's work)
-  std::vector<uint64_t> h_x0_shared(n_x);
-  std::vector<DescentProblem> h_problems(n);
-  std::vector<PostProblem> h_post(n);
-  std::vector<BatchSlot> h_chains(n);
-  std::vector<uint64_t> h_x(n_x);
-  std::vector<double> h_e(n);
-  std::vector<uint32_t> h_sweeps(n);
-  asp::ScopedStream main_stream;
-  ASP_TRY(main_stream.acquire());
-  hipStream_t s = main_stream.stream;
-  ClassLauncher launcher;
-  DeviceBuffer<uint64_t> d_x0, d_x0_perm, d_best, d_x;
-  DeviceBuffer<double> d_partial, d_e, d_cache;
-  DeviceBuffer<long long> d_tracked;
-  DeviceBuffer<unsigned long long> d_accepted;
-  DeviceBuffer<uint32_t> d_sweeps;
-  DeviceBuffer<DescentProblem> d_problems;
-  DeviceBuffer<PostProblem> d_post;
-  DeviceBuffer<BatchSlot> d_slots, d_chains;
-  asp::StreamFence fence(s);
-  ASP_TRY(d_x0.alloc(n_x));
-  ASP_TRY(d_x0_perm.alloc(n_blocks));
-  ASP_TRY(d_best.alloc(n_blocks));
-  ASP_TRY(d_x.alloc(n_x));
-  ASP_TRY(d_partial.alloc(n_blocks));
-  ASP_TRY(d_e.alloc(n));
-  ASP_TRY(d_tracked.alloc(n));
-  ASP_TRY(d_accepted.alloc(n));
-  ASP_TRY(d_sweeps.alloc(n));
-  if (use_cache && d_cache.alloc(n_cache) != ASP_OK) {
-    asp_clear_error();  // the cache is an optimisation: run without it
-    use_cache = false;
-  }
-  // ---- descriptors ----
-  for (size_t k = 0; k < n; ++k) {
-    const asp_sa_greedy_item &it = items[shared[k]];
-    const asp_sa_plan *p = it.plan;
-    const asp::SaHostLayout &L = p->host;
-    const uint64_t words = (L.num_spins + 63) / 64;
-    std::copy(h_x0.begin() + tree_at[shared[k]], h_x0.begin() + tree_at[shared[k]] + words,
-              h_x0_shared.begin() + off[k].x);
-    DescentProblem d{};
-    SweepArgs &a = d.s;
-    // (betas stay null and the seed 0: the descent reads neither)
-    a = sweep_args(p, kBytes, nullptr, d_x0_perm.ptr + off[k].blocks, d_best.ptr + off[k].blocks, d_tracked.ptr + k,
-                   d_accepted.ptr + k, 0, it.max_sweeps, 0);
-    // the field cache and its inert blocks as in the single path: late sweeps flip little
-    a.field_cache = use_cache ? d_cache.ptr + off[k].cache : nullptr;
-    a.cache_enter_flips = cache_enter_flips_of(L);
-    d.x0 = d_x0.ptr + off[k].x;
-    d.x0_perm = d_x0_perm.ptr + off[k].blocks;
-    d.sweeps_done = d_sweeps.ptr + k;
-    h_problems[k] = d;
-    h_post[k] = post_problem_of(p, d_best.ptr + off[k].blocks, d_partial.ptr + off[k].blocks, d_e.ptr + k,
-                                d_x.ptr + off[k].x);
-    h_chains[k] = BatchSlot{static_cast<uint32_t>(k), 0u};
-  }
-  // ---- slot tables: per class, problems longest first, dealt to the 8 XCDs ----
-  ASP_TRY(launcher.build(members, kNumBatchWaves));
-  const std::vector<BatchSlot> &h_slots = launcher.h_slots;
-  ASP_TRY(d_problems.alloc(n));
-  ASP_TRY(d_post.alloc(n));
-  ASP_TRY(d_slots.alloc(h_slots.size()));
-  ASP_TRY(d_chains.alloc(n));
-  {
-    // host trees go up in one copy; device trees are written where the permute reads them (a batch of
-    // device trees only moves no tree words over PCIe)
-    std::vector<asp::GreedyTreeTarget> targets;
-    for (size_t k = 0; k < n; ++k) {
-      asp_sa_plan *p = items[shared[k]].plan;
-      if (p->greedy_tree != 0) targets.push_back(asp::GreedyTreeTarget{p, d_x0.ptr + off[k].x, nullptr});
-    }
-    if (targets.size() != n) ASP_TRY(d_x0.upload(h_x0_shared.data(), n_x, s));
-    if (!targets.empty()) {
-      float split_ms[3] = {0.0f, 0.0f, 0.0f};
-      ASP_TRY(asp::greedy_tree_device(targets.data(), static_cast<uint32_t>(targets.size()), s, split_ms));
-      asp::greedy_tree_record_ms(split_ms, device_trees_ran);
-      g_greedy_tree_ms += split_ms[0] + split_ms[1] + split_ms[2];
-    }
-  }
-  ASP_TRY(d_problems.upload(h_problems.data(), n, s));
-  ASP_TRY(d_post.upload(h_post.data(), n, s));
-  ASP_TRY(d_slots.upload(h_slots.data(), h_slots.size(), s));
-  ASP_TRY(d_chains.upload(h_chains.data(), n, s));
-  // every problem's tree signs into block order: one launch
-  hipLaunchKernelGGL(k_permute_bits_problems, dim3(static_cast<unsigned>(n)), dim3(256), 0, s,
-                     d_problems.ptr);
-  ASP_HIP_TRY(hipGetLastError());
-  // ---- one descent launch per class ----
-  ASP_TRY(launcher.run(s, d_problems.ptr, d_slots.ptr, [&](int c) {
-    return ClassKernel<DescentProblem>{colour_kernel_of<BatchFamily<DescentProblem>>(1, kBytes), 64u * kBatchWaves[c]};
-  }));
-  // ---- energies and original-order bits of every problem's final configuration ----
-  ASP_TRY(launch_post_batch(d_post.ptr, d_chains.ptr, static_cast<unsigned>(n), energy_lds, max_lds, s));
-  ASP_TRY(d_x.download(h_x.data(), n_x, s));
-  ASP_TRY(d_e.download(h_e.data(), n, s));
-  ASP_TRY(d_sweeps.download(h_sweeps.data(), n, s));
-  ASP_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.0f;
-  ASP_HIP_TRY(hipEventElapsedTime(&ms, launcher.begin, launcher.end));
-  g_greedy_descent_ms += ms;
-  for (size_t k = 0; k < n; ++k) {
-    const asp_sa_greedy_item &it = items[shared[k]];
-    asp_sa_plan *p = it.plan;
-    const uint64_t words = (p->host.num_spins + 63) / 64;
-    std::copy(h_x.begin() + off[k].x, h_x.begin() + off[k].x + words, it.out_x);
-    *it.out_e = h_e[k];
-    if (it.out_sweeps) *it.out_sweeps = h_sweeps[k];
-    p->last_tracked.clear();  // (the shared launches bring no per-chain statistics back)
-    p->last_accepted.clear();
-    p->last_m = 1;
-    p->last_layout = p->last_spin_layout = kBytes;
-    p->last_threads = static_cast<int>(64u * kBatchWaves[members[k].cls]);
-    p->last_groups = 1;
-    p->last_sweep_ms = p->last_total_ms = 0.0f;  // shared launches: see asp_sa_greedy_batch_last_ms
-  }
-  return ASP_OK;
-}
-
-}  // extern "C"

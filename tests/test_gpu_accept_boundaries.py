@@ -114,7 +114,7 @@ def _closed(case, ham, lo=0, count=None, shuffled=False):
 
 
 def _bytes_limit(blocks):
-    """The LDS of the byte layout's sweep (csrc/sa_sweep.hip, sweep_lds_bytes): words do not fit it."""
+    """The LDS of the byte layout's sweep (csrc/sa_sweep.hip, sweep_lds_bytes; SweepLds in csrc/sa_colour.hpp): words do not fit it."""
     return blocks * 64 + 34 * 8 + blocks * 8 + 16 + 2 * ((blocks + 15) // 16 * 16)
 
 

@@ -60,7 +60,7 @@ class _Case:
                                                     self.S, num_threads=8))
 
     def bytes_limit(self):
-        """The LDS of the byte layout's sweep (csrc/sa_sweep.hip, sweep_lds_bytes): words do not fit it."""
+        """The LDS of the byte layout's sweep (csrc/sa_sweep.hip, sweep_lds_bytes; SweepLds in csrc/sa_colour.hpp): words do not fit it."""
         nb = self.blocks
         return nb * 64 + 34 * 8 + nb * 8 + 16 + 2 * ((nb + 15) // 16 * 16)
 

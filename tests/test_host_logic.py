@@ -469,17 +469,30 @@ def test_bench_roofline_refuses_counters_of_other_kernel_sources(tmp_path, monke
 
 def test_build_records_the_fingerprints_of_the_kernel_source_sets():
     """The stamp beside the library names what its sweep kernels were built from; it follows the
-    sources (a change to another kernel file leaves both sets alone)."""
+    sources (a change to another kernel file leaves both sets alone).  An edit to a host driver of the
+    colour order (sa_anneal.hip, sa_batch.hip) or to the pass after the sweeps (sa_energy.hip) cannot
+    void the colour counters: none of them is behind the colour fingerprint, and the drivers own no
+    kernel."""
     from annealing_sign_problem_amd import build
 
     now = build.source_set_fingerprints()
     assert sorted(now) == ["colour", "shuffled"] and now["colour"] != now["shuffled"]
+    import os
+
+    sources = [os.path.join(build.CSRC, s) for s in build.KERNEL_SOURCE_SETS["colour"]]
+    behind = {os.path.basename(f) for s in sources for f in [s] + build._included_headers(s)}
+    assert {"sa_sweep.hip", "sa_plan.cpp", "sa_colour.hpp"} <= behind
+    drivers = {"sa_anneal.hip", "sa_batch.hip", "sa_energy.hip"}
+    assert not (behind & drivers)
+    assert drivers <= set(build.SOURCES)
+    for name in ("sa_anneal.hip", "sa_batch.hip"):
+        with open(os.path.join(build.CSRC, name)) as f:
+            assert "__global__" not in f.read(), name
     built = build.built_source_set_fingerprints()
     if build.built_fingerprint() == build.fingerprint():  # (the library on disk is of these sources)
         assert built == now
     # the committed counters: every case names its set, and a fingerprint if it has one is 64 hex digits
     import json
-    import os
 
     with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                            "sweep_counters.json")) as f:
