@@ -43,7 +43,8 @@ $(OUT)/%.csv:
 
 # `make noise MODEL=...`: influence of amplitude noise on the greedy solver (reference Makefile:37-44:
 # 1000 noise levels x 100 repetitions), every draw on a reweighted clone of one plan, $(BATCH) draws per
-# greedy_solve_batch; then the quartiles per bin of the amplitude overlap (<model>_stats.csv)
+# greedy_solve_batch; then the quartiles per bin of the amplitude overlap (<model>_stats.csv).
+# FROM_AMPLITUDES=1: a round's couplings from a coupling stencil and the new amplitudes alone (the same file)
 NOISE_STEPS ?= 1000
 NOISE_REPETITIONS ?= 100
 BATCH ?= 16
@@ -52,7 +53,8 @@ noise: $(OUT)/noise/$(MODEL).csv
 $(OUT)/noise/%.csv:
 	@mkdir -p $(OUT)/noise
 	$(PYTHON) -m annealing_sign_problem_amd.influence_of_noise --model $* --seed $(SEED) \
-		--output $@.wip --steps $(NOISE_STEPS) --repetitions $(NOISE_REPETITIONS) --batch $(BATCH) && \
+		--output $@.wip --steps $(NOISE_STEPS) --repetitions $(NOISE_REPETITIONS) --batch $(BATCH) \
+		$(if $(FROM_AMPLITUDES),--from-amplitudes) && \
 	mv $@.wip $@
 	$(PYTHON) -c "from annealing_sign_problem_amd.influence_of_noise import postprocess_influence_of_noise as p; p('$@')"
 

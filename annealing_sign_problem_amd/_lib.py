@@ -171,6 +171,31 @@ class BondsSummary(ctypes.Structure):
     ]
 
 
+class IsingStencilCounts(ctypes.Structure):
+    """Mirror of ``asp_ising_stencil_counts`` (include/asp.h)."""
+
+    _fields_ = [
+        ("num_spins", c_u64),
+        ("stored", c_u64),
+        ("connections", c_u64),
+        ("groups", c_u64),
+        ("silent_pairs", c_u64),
+        ("longest_group", c_u64),
+    ]
+
+
+class SaStencilItem(ctypes.Structure):
+    """Mirror of ``asp_sa_stencil_item`` (include/asp.h)."""
+
+    _fields_ = [
+        ("plan", c_void_p),
+        ("psi", c_void_p),
+        ("field", c_void_p),
+        ("data_out", c_void_p),
+        ("status", c_i32),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/asp.h declares
 SIGNATURES = {
     "asp_last_error": (ctypes.c_char_p, []),
@@ -244,6 +269,12 @@ SIGNATURES = {
     "asp_sa_plan_reweight": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "asp_sa_plan_reweight_last_ms": (c_float, [c_void_p]),
     "asp_sa_plan_clone": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
+    "asp_ising_stencil_create": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
+    "asp_ising_stencil_destroy": (None, [c_void_p]),
+    "asp_ising_stencil_info": (c_int, [c_void_p, ctypes.POINTER(IsingStencilCounts)]),
+    "asp_ising_stencil_values": (c_int, [c_void_p, c_u32, c_void_p, c_void_p, c_void_p]),
+    "asp_sa_plan_reweight_stencil_batch": (c_int, [c_void_p, ctypes.POINTER(SaStencilItem), c_u32]),
+    "asp_sa_plan_reweight_stencil_last_ms": (c_float, []),
     "asp_sa_batch_slots_host": (c_int, [c_u32, c_void_p, c_void_p, ctypes.POINTER(c_u32), c_void_p, c_u64]),
     "asp_sa_shuffled_order_host": (c_int, [c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_u32,
                                            c_void_p, c_void_p, ctypes.POINTER(c_u32)]),

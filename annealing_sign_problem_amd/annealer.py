@@ -33,6 +33,7 @@ from . import _lib
 __all__ = [
     "Hamiltonian",
     "PatternMismatch",
+    "reweight_hamiltonians",
     "anneal",
     "anneal_batch",
     "anneal_traces",
@@ -167,7 +168,7 @@ class Hamiltonian:
         key = self._key()
         if self._plan is not None and self._plan_key == key:
             return self._plan
-        self.release()
+        self._release_plan()
         lib = _lib.load()
         _lib.require_gpu()
         indptr, indices, data, field = self._arrays()
@@ -186,7 +187,18 @@ class Hamiltonian:
         return info
 
     def release(self) -> None:
-        """Destroy the device plan now (it is rebuilt on the next use)."""
+        """Destroy the device plan now (it is rebuilt on the next use), and the coupling stencil of the
+        family when this Hamiltonian is the one it was made for."""
+        family = getattr(self, "_family", None)
+        if family and family.get("owner") == id(self):
+            stencil = family.pop("stencil", None)
+            family.pop("owner", None)
+            family.pop("pattern", None)
+            if stencil:
+                stencil.release()
+        self._release_plan()
+
+    def _release_plan(self) -> None:
         if self._plan is not None:
             try:
                 _lib.load().asp_sa_plan_destroy(self._plan)
@@ -254,11 +266,10 @@ class Hamiltonian:
         self._plan_key = self._key()
         return self
 
-    def reweighted(self, data, field=None, indptr=None, indices=None) -> "Hamiltonian":
-        """A NEW Hamiltonian with these numbers on the pattern of this one (which is left alone and
-        gets its plan built if it has none): its plan is a clone of this one's (``asp_sa_plan_clone``:
-        the same structure, own buffers and stream, no preprocessing) reweighted as in
-        :meth:`reweight`.  The two objects can go into one batched call."""
+    def clone(self) -> "Hamiltonian":
+        """A NEW Hamiltonian with the numbers and the structure of this one (which gets its plan built if
+        it has none): its plan is a clone of this one's (``asp_sa_plan_clone``: own buffers and stream, no
+        preprocessing).  It belongs to this one's family (:meth:`family`)."""
         source = self.plan()
         lib = _lib.load()
         handle = ctypes.c_void_p()
@@ -268,7 +279,25 @@ class Hamiltonian:
         other.field = self.field
         other._plan = handle
         other._plan_key = other._key()
+        other._family = self.family()
         _lib.track(other)
+        return other
+
+    def family(self) -> dict:
+        """What a Hamiltonian and its clones share besides the pattern: a dict that
+        ``common.reweight_ising_models`` keeps the coupling stencil in (``"stencil"``, with ``"owner"``,
+        the ``id`` of the Hamiltonian whose :meth:`release` closes it)."""
+        family = getattr(self, "_family", None)
+        if family is None:
+            family = self._family = {}
+        return family
+
+    def reweighted(self, data, field=None, indptr=None, indices=None) -> "Hamiltonian":
+        """A NEW Hamiltonian with these numbers on the pattern of this one (which is left alone and
+        gets its plan built if it has none): its plan is a clone of this one's (``asp_sa_plan_clone``:
+        the same structure, own buffers and stream, no preprocessing) reweighted as in
+        :meth:`reweight`.  The two objects can go into one batched call."""
+        other = self.clone()
         try:
             other.reweight(data, field, indptr, indices)
         except Exception:
@@ -290,6 +319,66 @@ class Hamiltonian:
         _lib.check(_lib.load().asp_sa_energy(self.plan(), ctypes.c_uint32(xs.shape[0]),
                                              _lib.ptr(xs), _lib.ptr(out)))
         return out
+
+
+def reweight_hamiltonians(hamiltonians, stencil, psis, fields=None) -> list:
+    """:meth:`Hamiltonian.reweight` of many Hamiltonians of ONE pattern in one device call
+    (``asp_sa_plan_reweight_stencil_batch``): Hamiltonian ``d`` takes the couplings
+    that ``stencil`` (``operators.IsingStencil`` of that pattern) forms from the amplitudes ``psis[d]``
+    — they never visit the host on their way into the plan — and, with ``fields``, the field
+    ``fields[d]`` (``None``: kept).  In place; returns one bool per Hamiltonian.  ``True``: applied,
+    ``exchange.data`` and ``field`` hold the new numbers (new frozen objects that share the frozen index
+    arrays).  ``False``: that draw's couplings leave the pattern, the Hamiltonian is untouched.  The
+    Hamiltonians must be distinct objects with distinct plans and no live :class:`Chains`; any refusal
+    (``AspError`` with the item's index in the message) leaves all of them as they were."""
+    hamiltonians = list(hamiltonians)
+    count = len(hamiltonians)
+    psis = np.ascontiguousarray(psis, dtype=np.float64)
+    if psis.ndim != 2 or psis.shape[0] != count:
+        raise ValueError("'psis' should hold one row of amplitudes per Hamiltonian")
+    if fields is not None:
+        fields = np.ascontiguousarray(fields, dtype=np.float64)
+        if fields.shape != psis.shape:
+            raise ValueError("'fields' should have the shape of 'psis'")
+    for h in hamiltonians:
+        if h.size != psis.shape[1]:
+            raise ValueError("'psis' should hold {} amplitudes per row".format(h.size))
+    handle = stencil.handle()
+    if count == 0:
+        return []
+    lib = _lib.load()
+    items = (_lib.SaStencilItem * count)()
+    data = [np.empty(stencil.nnz, dtype=np.float64) for _ in range(count)]  # (each adopted by its exchange)
+    for d, h in enumerate(hamiltonians):
+        items[d].plan = h.plan()
+        items[d].psi = psis[d].ctypes.data
+        items[d].field = None if fields is None else fields[d].ctypes.data
+        items[d].data_out = data[d].ctypes.data
+        items[d].status = 0
+    _lib.check(lib.asp_sa_plan_reweight_stencil_batch(handle, items, ctypes.c_uint32(count)))
+    applied = []
+    for d, h in enumerate(hamiltonians):
+        applied.append(items[d].status == 0)
+        if not applied[-1]:
+            continue
+        m = h.exchange
+        values = data[d]
+        values.flags.writeable = False  # (before scipy takes its view of it)
+        matrix = scipy.sparse.csr_matrix((values, m.indices, m.indptr), shape=m.shape, copy=False)
+        matrix.has_sorted_indices = True
+        matrix.has_canonical_format = True
+        h.exchange = matrix
+        if fields is not None:
+            field = fields[d].copy()
+            field.flags.writeable = False
+            h.field = field
+        h._plan_key = h._key()
+    return applied
+
+
+def reweight_hamiltonians_last_ms() -> float:
+    """Device time (ms, HIP events) of this thread's last :func:`reweight_hamiltonians`."""
+    return float(_lib.load().asp_sa_plan_reweight_stencil_last_ms())
 
 
 def resolve_sweep_order(sweep_order: Optional[str]) -> str:

@@ -50,6 +50,7 @@ SOURCES = [
     "sa_population.hip",
     "sa_cluster.hip",
     "sa_reweight.hip",
+    "ising_stencil.hip",
 ]
 
 # -ffp-contract=off: the parity contract needs every multiply/add rounded on its

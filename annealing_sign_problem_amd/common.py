@@ -25,6 +25,7 @@ __all__ = [
     "make_ising_model",
     "make_ising_models",
     "reweight_ising_model",
+    "reweight_ising_models",
     "solve_ising_model",
     "solve_ising_models",
     "dump_ising_model_to_hdf5",
@@ -406,6 +407,128 @@ def reweight_ising_model(
         out.basis_index = basis_index
         return out
     return IsingModel(spins, operator, hamiltonian, x0, basis_index)
+
+
+def _family_stencil(model: IsingModel):
+    """The coupling stencil of ``model``'s states and pattern, created on first use and kept with the
+    family of its Hamiltonian (``Hamiltonian.family``: clones share it, ``release()`` of ``model``'s
+    Hamiltonian closes it); ``None`` when the stencil cannot be made (one-directional matrix elements
+    with duplicates: the per-model route decides what happens then)."""
+    hamiltonian = model.ising_hamiltonian
+    family = hamiltonian.family()
+    stencil = family.get("stencil")
+    exchange = hamiltonian.exchange
+    if stencil is not None and family.get("pattern") is not exchange.indices:
+        # (the Hamiltonian was given another matrix since: reweights keep the frozen index arrays)
+        if stencil:
+            stencil.release()
+        stencil = None
+    if stencil is None:
+        try:
+            stencil = model.quantum_hamiltonian.device().ising_stencil(model.spins, exchange.indptr, exchange.indices)
+        except _lib.AspError as error:
+            if not _takes_host_route(error):
+                raise
+            stencil = False  # (remembered: not tried again for every round)
+        family["stencil"] = stencil
+        family["pattern"] = exchange.indices
+        family["owner"] = id(hamiltonian)
+    return stencil or None
+
+
+def reweight_ising_models(model: IsingModel, log_psis=None, log_psi_fns=None, external_field: bool = False,
+                          outs=None):
+    """``[reweight_ising_model(model, log_psis[d], log_psi_fns[d], external_field, outs[d]) for d in ...]``
+    (not in the reference) — the same states and operator, a round of new amplitudes — with the couplings
+    of ALL draws formed from the stored matrix elements of a coupling stencil (ASP-STENCIL-1, DESIGN.md
+    §4.14.1) and put into the plans in ONE device call (``sa.reweight_hamiltonians``): no operator pass,
+    no key lookups, no comparison of patterns per draw.  Element ``d`` equals the per-model call's bit for
+    bit: ``exchange``, ``field``, ``initial_signs``, every solver result.  ``log_psis`` / ``log_psi_fns``
+    / ``outs``: ``None`` or one element per draw (elements may be ``None``; every draw needs a log_psi or
+    a log_psi_fn).  The stencil is created on first use and kept with the family of ``model``'s
+    Hamiltonian; it goes with ``model.ising_hamiltonian.release()``.  A draw whose couplings leave the
+    pattern gets ``make_ising_model``'s model; an operator without a device action, and a stencil that
+    cannot be made, take the per-model route.  With ``external_field=True`` every draw's field still
+    needs its operator pass (``_boundary_field``)."""
+    lengths = {len(x) for x in (log_psis, log_psi_fns, outs) if x is not None}
+    if len(lengths) > 1:
+        raise ValueError("'log_psis', 'log_psi_fns' and 'outs' should hold one element per draw")
+    count = lengths.pop() if lengths else 0
+    log_psis = [None] * count if log_psis is None else list(log_psis)
+    log_psi_fns = [None] * count if log_psi_fns is None else list(log_psi_fns)
+    outs = [None] * count if outs is None else list(outs)
+    for log_psi, log_psi_fn in zip(log_psis, log_psi_fns):
+        if log_psi is None and log_psi_fn is None:
+            raise ValueError("at least one of log_psi or log_psi_fn should be specified")
+        if external_field and log_psi_fn is None:
+            raise ValueError("log_psi_fn should be specified when external_field=True")
+    if any(a is b for k, a in enumerate(outs) if a is not None for b in outs[:k]):
+        raise ValueError("'outs' holds one model twice")
+    operator, spins = model.quantum_hamiltonian, model.spins
+
+    def single(d):
+        return reweight_ising_model(model, log_psis[d], log_psi_fns[d], external_field, outs[d])
+
+    if count == 0:
+        return []
+    stencil = _family_stencil(model) if _on_device(operator) else None
+    if stencil is None:
+        return [single(d) for d in range(count)]
+    base = model.ising_hamiltonian.exchange
+    results = [None] * count
+    draws = []  # (d, psi, field, basis_index) of the draws that go through the stencil
+    for d in range(count):
+        out = outs[d]
+        if out is not None:
+            pattern = out.ising_hamiltonian.exchange
+            if not (pattern.indices is base.indices or (np.array_equal(pattern.indptr, base.indptr) and
+                                                        np.array_equal(pattern.indices, base.indices))):
+                results[d] = single(d)  # (a model of another pattern: the per-model call's answer)
+                continue
+        basis_index = model.basis_index
+        values = log_psis[d]
+        if values is None:
+            log_psi_fn = log_psi_fns[d]
+            if hasattr(log_psi_fn, "index_of"):
+                if basis_index is None:
+                    basis_index = log_psi_fn.index_of(spins)
+                values = log_psi_fn.at_index(basis_index)
+            else:
+                values = log_psi_fn(spins)
+        psi, field = _cluster_amplitudes_and_field(operator, spins, values, log_psi_fns[d], external_field)
+        draws.append((d, psi, field, basis_index))
+    if not draws:
+        return results
+    cloned = []
+    try:
+        hamiltonians = []
+        for d, _, _, _ in draws:
+            if outs[d] is not None:
+                hamiltonians.append(outs[d].ising_hamiltonian)
+            else:
+                cloned.append(model.ising_hamiltonian.clone())
+                hamiltonians.append(cloned[-1])
+        applied = sa.reweight_hamiltonians(hamiltonians, stencil, np.stack([psi for _, psi, _, _ in draws]),
+                                           np.stack([field for _, _, field, _ in draws]))
+    except Exception:
+        for hamiltonian in cloned:
+            hamiltonian.release()
+        raise
+    for (d, psi, _, basis_index), hamiltonian, ok in zip(draws, hamiltonians, applied):
+        if not ok:
+            if outs[d] is None:
+                hamiltonian.release()
+            results[d] = make_ising_model(spins, operator, log_psi=log_psis[d], log_psi_fn=log_psi_fns[d],
+                                          external_field=external_field)
+            continue
+        x0 = sa.signs_to_bits(np.sign(psi))
+        if outs[d] is not None:
+            outs[d].initial_signs = x0
+            outs[d].basis_index = basis_index
+            results[d] = outs[d]
+        else:
+            results[d] = IsingModel(spins, operator, hamiltonian, x0, basis_index)
+    return results
 
 
 def _boundary_field(hamiltonian, spins, psi, log_psi_fn, cluster_norm: float) -> np.ndarray:

@@ -10,6 +10,10 @@
 // bit for bit.  Only when everything is valid do k_rw_scatter / k_rw_field write the value arrays the
 // plan holds on the device; the lazily uploaded ones are built from the updated host layout as ever.
 //
+// The steps — maps, merge, row statistics, scales, commit — are functions of their own (sa_reweight.hpp):
+// asp_sa_plan_reweight_stencil_batch (csrc/ising_stencil.hip) runs them for a round of plans on couplings
+// that are on the device already.
+//
 // Nothing else of a plan caches a function of the couplings across calls: the field cache
 // (w_field_cache) is switched on inside a launch, from cache_ctl in LDS that every launch zeroes, and
 // filled before it is read; the other w_* buffers are per-call scratch.
@@ -23,6 +27,7 @@
 
 #include "asp_common.hpp"
 #include "sa_internal.hpp"
+#include "sa_reweight.hpp"
 
 namespace {
 
@@ -111,8 +116,12 @@ int64_t find_in_row(const SaPattern &P, uint64_t row, int32_t col) {
   return at != end && *at == col ? P.indptr[row] + (at - begin) : -1;
 }
 
+}  // namespace
+
+namespace asp {
+
 // The maps of SaPattern, from the pattern and the layout of the plan; uploaded on the plan's stream.
-int ensure_maps(asp_sa_plan *p) {
+int rw_ensure_maps(asp_sa_plan *p) {
   SaPattern &P = *p->pattern;
   std::lock_guard<std::mutex> guard(P.build);
   if (P.built) return ASP_OK;
@@ -185,7 +194,72 @@ int ensure_maps(asp_sa_plan *p) {
   return ASP_OK;
 }
 
-}  // namespace
+int rw_queue_merge(const asp_sa_plan *p, const double *d_data, double *d_staged, uint32_t *d_zeros,
+                   hipStream_t s) {
+  const SaPattern &P = *p->pattern;
+  const uint64_t entries = p->host.a_col.size();
+  ASP_HIP_TRY(hipMemsetAsync(d_zeros, 0, sizeof(uint32_t), s));
+  if (entries > 0) {
+    hipLaunchKernelGGL(k_rw_merge, dim3(grid_for(entries)), dim3(kThreads), 0, s, d_data, P.d_src_ij.ptr,
+                       P.d_src_ji.ptr, entries, d_staged, d_zeros);
+  }
+  return ASP_OK;
+}
+
+int rw_queue_row_stats(const asp_sa_plan *p, const double *d_staged, double *d_row_sum, double *d_row_min,
+                       hipStream_t s) {
+  const uint64_t K = p->host.num_spins;
+  hipLaunchKernelGGL(k_rw_row_stats, dim3(grid_for(K)), dim3(kThreads), 0, s, d_staged, p->pattern->d_a_ptr.ptr,
+                     static_cast<uint32_t>(K), d_row_sum, d_row_min);
+  ASP_HIP_TRY(hipGetLastError());
+  return ASP_OK;
+}
+
+bool rw_fold_scales(uint64_t K, const double *row_sum, const double *row_min, const double *field_now,
+                    RwScales *out) {
+  double bound = 0.0, max_delta = 0.0;
+  double min_delta = std::numeric_limits<double>::infinity();
+  for (uint64_t i = 0; i < K; ++i) {
+    const double row = row_sum[i];
+    min_delta = std::min(min_delta, row_min[i]);
+    const double h = std::fabs(field_now[i]);
+    if (h > 0.0) min_delta = std::min(min_delta, 2.0 * h);
+    bound += 0.5 * row + h;
+    max_delta = std::max(max_delta, 2.0 * (row + h));
+  }
+  out->bound = bound;
+  out->max_delta = max_delta;
+  out->min_delta = min_delta;
+  return std::isfinite(bound);
+}
+
+int rw_commit_data(asp_sa_plan *p, const double *d_staged, std::vector<double> *a_val, double diag_sum,
+                   hipStream_t s) {
+  const SaPattern &P = *p->pattern;
+  asp::SaHostLayout &L = p->host;
+  const uint64_t entries = L.a_col.size();
+  if (entries > 0) {
+    hipLaunchKernelGGL(k_rw_scatter, dim3(grid_for(entries)), dim3(kThreads), 0, s, d_staged, P.d_ell_slot.ptr,
+                       P.d_rq_slot.ptr, entries, p->ell_val.ptr, p->rq_ptr.ptr ? p->rq_val.ptr : nullptr,
+                       p->cluster_row_ptr.ptr ? p->cluster_val.ptr : nullptr);
+  }
+  L.diag_sum = diag_sum;
+  for (uint64_t e = 0; e < entries; ++e) L.ell_val[P.ell_slot[e]] = (*a_val)[e];
+  L.a_val.swap(*a_val);
+  return ASP_OK;
+}
+
+int rw_commit_field(asp_sa_plan *p, const double *d_field, const double *field_now, hipStream_t s) {
+  asp::SaHostLayout &L = p->host;
+  const uint64_t K = L.num_spins;
+  hipLaunchKernelGGL(k_rw_field, dim3(grid_for(K)), dim3(kThreads), 0, s, d_field, p->pos_of_spin.ptr,
+                     static_cast<uint32_t>(K), p->field_pos.ptr, p->rq_ptr.ptr ? p->field_dev.ptr : nullptr,
+                     p->cluster_row_ptr.ptr ? p->cluster_field.ptr : nullptr);
+  for (uint64_t i = 0; i < K; ++i) L.field_pos[L.pos_of_spin[i]] = field_now[i];
+  return ASP_OK;
+}
+
+}  // namespace asp
 
 extern "C" {
 
@@ -236,7 +310,7 @@ int asp_sa_plan_reweight(asp_sa_plan *p, uint64_t nnz, int64_t const *indptr, in
     }
   }
   ASP_TRY(asp::bind_device());
-  ASP_TRY(ensure_maps(p));
+  ASP_TRY(asp::rw_ensure_maps(p));
   if (data) {
     for (const auto &pair : P.dropped) {
       const double v = data[pair.first] + (pair.second >= 0 ? data[pair.second] : 0.0);
@@ -268,17 +342,11 @@ int asp_sa_plan_reweight(asp_sa_plan *p, uint64_t nnz, int64_t const *indptr, in
   if (data) {
     ASP_TRY(p->rw_data.ensure(nnz));
     ASP_TRY(p->rw_data.upload(data, nnz, s));
-    ASP_HIP_TRY(hipMemsetAsync(p->rw_zeros.ptr, 0, sizeof(uint32_t), s));
-    if (entries > 0) {
-      hipLaunchKernelGGL(k_rw_merge, dim3(grid_for(entries)), dim3(kThreads), 0, s, p->rw_data.ptr,
-                         P.d_src_ij.ptr, P.d_src_ji.ptr, entries, p->rw_a_val.ptr, p->rw_zeros.ptr);
-    }
+    ASP_TRY(asp::rw_queue_merge(p, p->rw_data.ptr, p->rw_a_val.ptr, p->rw_zeros.ptr, s));
   } else {
     ASP_TRY(p->rw_a_val.upload(L.a_val.data(), entries, s));  // field only: the rows as they are
   }
-  hipLaunchKernelGGL(k_rw_row_stats, dim3(grid_for(K)), dim3(kThreads), 0, s, p->rw_a_val.ptr, P.d_a_ptr.ptr,
-                     static_cast<uint32_t>(K), p->rw_row_sum.ptr, p->rw_row_min.ptr);
-  ASP_HIP_TRY(hipGetLastError());
+  ASP_TRY(asp::rw_queue_row_stats(p, p->rw_a_val.ptr, p->rw_row_sum.ptr, p->rw_row_min.ptr, s));
   ASP_TRY(p->rw_row_sum.download(row_sum.data(), K, s));
   ASP_TRY(p->rw_row_min.download(row_min.data(), K, s));
   if (data) {
@@ -297,41 +365,23 @@ int asp_sa_plan_reweight(asp_sa_plan *p, uint64_t nnz, int64_t const *indptr, in
                           (unsigned long long)row, e < entries ? L.a_col[e] : -1, zeros);
   }
   // the scales, rows in index order (sa_plan.cpp, "energy scale and automatic beta range")
-  double bound = 0.0, max_delta = 0.0;
-  double min_delta = std::numeric_limits<double>::infinity();
-  for (uint64_t i = 0; i < K; ++i) {
-    const double row = row_sum[i];
-    min_delta = std::min(min_delta, row_min[i]);
-    const double h = std::fabs(field_now[i]);
-    if (h > 0.0) min_delta = std::min(min_delta, 2.0 * h);
-    bound += 0.5 * row + h;
-    max_delta = std::max(max_delta, 2.0 * (row + h));
+  asp::RwScales scales;
+  if (!asp::rw_fold_scales(K, row_sum.data(), row_min.data(), field_now.data(), &scales)) {
+    return asp::set_error(ASP_ERR_INVALID, "couplings overflow double range");
   }
-  if (!std::isfinite(bound)) return asp::set_error(ASP_ERR_INVALID, "couplings overflow double range");
   // ---- valid: the plan takes the new numbers ----
   if (data) {
-    if (entries > 0) {
-      hipLaunchKernelGGL(k_rw_scatter, dim3(grid_for(entries)), dim3(kThreads), 0, s, p->rw_a_val.ptr,
-                         P.d_ell_slot.ptr, P.d_rq_slot.ptr, entries, p->ell_val.ptr,
-                         p->rq_ptr.ptr ? p->rq_val.ptr : nullptr,
-                         p->cluster_row_ptr.ptr ? p->cluster_val.ptr : nullptr);
-    }
     double diag = 0.0;  // D in row order
     for (uint64_t i = 0; i < K; ++i) {
       if (P.diag_pos[i] >= 0) diag = diag + data[P.diag_pos[i]];
     }
-    L.diag_sum = diag;
-    for (uint64_t e = 0; e < entries; ++e) L.ell_val[P.ell_slot[e]] = a_val[e];
-    L.a_val.swap(a_val);
+    ASP_TRY(asp::rw_commit_data(p, p->rw_a_val.ptr, &a_val, diag, s));
   }
   if (field) {
     ASP_TRY(p->rw_field.upload(field_now.data(), K, s));
-    hipLaunchKernelGGL(k_rw_field, dim3(grid_for(K)), dim3(kThreads), 0, s, p->rw_field.ptr, p->pos_of_spin.ptr,
-                       static_cast<uint32_t>(K), p->field_pos.ptr, p->rq_ptr.ptr ? p->field_dev.ptr : nullptr,
-                       p->cluster_row_ptr.ptr ? p->cluster_field.ptr : nullptr);
-    for (uint64_t i = 0; i < K; ++i) L.field_pos[L.pos_of_spin[i]] = field_now[i];
+    ASP_TRY(asp::rw_commit_field(p, p->rw_field.ptr, field_now.data(), s));
   }
-  asp::sa_finish_scales(bound, max_delta, min_delta, &L);
+  asp::sa_finish_scales(scales.bound, scales.max_delta, scales.min_delta, &L);
   ASP_HIP_TRY(hipGetLastError());
   ASP_HIP_TRY(hipEventRecord(p->ev[3], s));
   ASP_HIP_TRY(hipStreamSynchronize(s));

@@ -29,8 +29,8 @@ from . import common
 
 
 def influence_of_noise(hamiltonian, ground_state, noise_levels: Iterable[float], repetitions: int,
-                       batch: int = 16, reuse: bool = True,
-                       seed: Optional[int] = None) -> Iterator[Tuple[float, float, float]]:
+                       batch: int = 16, reuse: bool = True, seed: Optional[int] = None,
+                       from_amplitudes: bool = False) -> Iterator[Tuple[float, float, float]]:
     """Rows ``(eps, amplitude_overlap, sign_overlap)``, ``repetitions`` per noise level, in the
     reference's order (common.py:887-903): ``np.random.seed(seed)`` when a seed is given, then one
     ``add_noise_to_amplitudes`` per row from numpy's global legacy stream — the stream and the rows are
@@ -40,7 +40,11 @@ def influence_of_noise(hamiltonian, ground_state, noise_levels: Iterable[float],
     draws reweights a pool of that many clones and is solved by ONE ``greedy_solve_batch``.  A draw
     whose couplings leave the pattern (an amplitude that underflowed to 0) gets a model of its own.
     ``reuse=False``: the reference's loop verbatim, ``make_ising_model`` +
-    ``solve_ising_model(mode="greedy")`` per draw — the comparison leg."""
+    ``solve_ising_model(mode="greedy")`` per draw — the comparison leg.
+    ``from_amplitudes=True`` (opt-in; needs ``reuse``): a round's draws go through ONE
+    ``common.reweight_ising_models`` with the pool as ``outs`` — the couplings come from the stored
+    matrix elements of a coupling stencil and the new amplitudes alone, without the operator pass
+     — and then one ``greedy_solve_batch``.  The rows are the same bytes."""
     batch = int(batch)
     if batch < 1:
         raise ValueError("'batch' must be positive")
@@ -76,7 +80,24 @@ def influence_of_noise(hamiltonian, ground_state, noise_levels: Iterable[float],
         for start in range(0, len(todo), batch):
             round_eps = todo[start:start + batch]
             overlaps, models = [], []
-            for k, eps in enumerate(round_eps):
+            if from_amplitudes:
+                fns = []
+                for eps in round_eps:
+                    amplitude_overlap, log_coeff_fn = draw(eps)
+                    overlaps.append(amplitude_overlap)
+                    fns.append(log_coeff_fn)
+                if base is None:
+                    base = common.make_ising_model(states, hamiltonian, log_psi_fn=fns[0])
+                outs = (pool + [None] * len(fns))[:len(fns)]
+                models = common.reweight_ising_models(base, log_psi_fns=fns, outs=outs)
+                for k, model in enumerate(models):
+                    if outs[k] is None and np.shares_memory(model.ising_hamiltonian.exchange.indices,
+                                                            base.ising_hamiltonian.exchange.indices):
+                        pool.append(model)  # (a new clone; a fallback model shares nothing and is used once)
+                round_eps_todo = []
+            else:
+                round_eps_todo = round_eps
+            for k, eps in enumerate(round_eps_todo):
                 amplitude_overlap, log_coeff_fn = draw(eps)
                 overlaps.append(amplitude_overlap)
                 if base is None:
@@ -181,6 +202,9 @@ def main(argv=None) -> int:
     parser.add_argument("--batch", type=int, default=16, help="draws solved by one greedy_solve_batch")
     parser.add_argument("--no-reuse", action="store_true",
                         help="build every draw's model and plan from scratch (the reference's loop)")
+    parser.add_argument("--from-amplitudes", action="store_true",
+                        help="couplings of a round from stored matrix elements and the new amplitudes alone "
+                             "(coupling stencil); the same rows")
     parser.add_argument("--quality", action="store_true",
                         help="print 'sign accuracy,sign overlap' of the greedy solver on the exact amplitudes")
     args = parser.parse_args(argv)
@@ -200,7 +224,7 @@ def main(argv=None) -> int:
     hamiltonian, ground_state = load_inputs(args.model, args.yaml, args.hdf5)
     noise_levels = np.exp(np.linspace(np.log(args.min_noise), np.log(args.max_noise), args.steps))
     rows = influence_of_noise(hamiltonian, ground_state, noise_levels, args.repetitions, batch=args.batch,
-                              reuse=not args.no_reuse)
+                              reuse=not args.no_reuse, from_amplitudes=args.from_amplitudes)
     pending = []
     for done, row in enumerate(rows, 1):
         pending.append("{},{},{}\n".format(*row))

@@ -491,6 +491,12 @@ class DeviceOperator:
         z = int(nnz.value)
         return indptr, col[:z], val[:z]  # (views: see ising)
 
+    def ising_stencil(self, keys, indptr, indices) -> "IsingStencil":
+        """The coupling stencil (ASP-STENCIL-1) of ``keys`` and the pattern
+        ``(indptr, indices)`` that :meth:`ising_csr` returned for them: all matrix elements among the
+        keys, kept on the device, so that new amplitudes become couplings without the operator pass."""
+        return IsingStencil(self, keys, indptr, indices)
+
     def ising_csr_segments(self, keys, psi, offsets) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """:meth:`ising_csr` of many clusters in one call, specification ASP-ISING-SEG-1 (DESIGN.md
         §3.8): ``offsets`` (u64[S + 1], from 0, non-decreasing) cuts ``keys`` / ``psi`` into segments,
@@ -636,3 +642,86 @@ class DeviceOperator:
             self._handle, segments, _lib.ptr(offsets), _lib.ptr(keys), capacity, _lib.ptr(out),
             _lib.ptr(out_offsets), ctypes.byref(count)))
         return out[:int(count.value)].copy(), out_offsets
+
+
+class IsingStencil:
+    """``asp_ising_stencil`` handle (csrc/ising_stencil.hip; :meth:`DeviceOperator.ising_stencil`): the
+    matrix elements among a fixed set of keys, grouped and resident on the device.  ``values(psis)``
+    gives the couplings of new amplitudes in the order of the pattern; ``annealer.reweight_hamiltonians``
+    puts them into plans of that pattern.  ``close()`` (or leaving the ``with`` block) frees it; a closed
+    stencil refuses every use with ``ValueError``."""
+
+    def __init__(self, operator: DeviceOperator, keys, indptr, indices):
+        import ctypes
+
+        _lib = operator._lib_module
+        self._lib_module = _lib
+        self._lib = operator._lib
+        self._handle = None
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        if keys.ndim != 1 or indptr.shape != (keys.shape[0] + 1,) or indices.ndim != 1:
+            raise ValueError("'indptr' should hold one more element than 'keys'")
+        if int(indptr[-1]) != indices.shape[0]:
+            raise ValueError("'indices' should hold indptr[-1] elements")
+        handle = ctypes.c_void_p()
+        _lib.check(self._lib.asp_ising_stencil_create(operator._handle, keys.shape[0], _lib.ptr(keys),
+                                                      _lib.ptr(indptr), _lib.ptr(indices), ctypes.byref(handle)))
+        self._handle = handle
+        self.num_spins = int(keys.shape[0])
+        self.nnz = int(indices.shape[0])
+        _lib.track(self)
+
+    def handle(self):
+        if not self._handle:
+            raise ValueError("the stencil is closed")
+        return self._handle
+
+    @property
+    def info(self):
+        """``_lib.IsingStencilCounts``: spins, stored entries, in-cluster connections, their groups, silent
+        pairs and the longest group."""
+        import ctypes
+
+        counts = self._lib_module.IsingStencilCounts()
+        self._lib_module.check(self._lib.asp_ising_stencil_info(self.handle(), ctypes.byref(counts)))
+        return counts
+
+    def values(self, psis) -> Tuple[np.ndarray, np.ndarray]:
+        """``(data f64[count, nnz], status i32[count])`` of the draws ``psis[count, K]`` (one draw may be
+        given as a vector): row ``d`` is ``ising_csr(keys, psis[d])[2]`` bit for bit where ``status[d]`` is
+        0; 1 says that draw's couplings leave the pattern (its row is unspecified)."""
+        _lib = self._lib_module
+        handle = self.handle()
+        psis = np.ascontiguousarray(psis, dtype=np.float64)
+        if psis.ndim == 1:
+            psis = psis.reshape(1, -1)
+        if psis.ndim != 2 or psis.shape[1] != self.num_spins:
+            raise ValueError("'psis' should have shape (count, {})".format(self.num_spins))
+        count = psis.shape[0]
+        data = np.empty((count, self.nnz), dtype=np.float64)
+        status = np.zeros(count, dtype=np.int32)
+        _lib.check(self._lib.asp_ising_stencil_values(handle, count, _lib.ptr(psis), _lib.ptr(data),
+                                                      _lib.ptr(status)))
+        return data, status
+
+    def release(self) -> None:
+        handle, self._handle = getattr(self, "_handle", None), None
+        if handle:
+            self._lib.asp_ising_stencil_destroy(handle)
+
+    close = release
+
+    def __enter__(self) -> "IsingStencil":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.release()
+
+    def __del__(self):
+        if getattr(self, "_handle", None) and not self._lib_module.closed():
+            try:
+                self.release()
+            except Exception:
+                pass

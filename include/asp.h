@@ -517,6 +517,76 @@ float asp_sa_plan_reweight_last_ms(asp_sa_plan const *p);
  * to solve several reweighted copies of one model at once: they refuse one plan twice. */
 int asp_sa_plan_clone(asp_sa_plan const *p, asp_sa_plan **out);
 
+/* ---- coupling stencil: the couplings of a fixed set of states from new amplitudes alone ----------
+ * Specification ASP-STENCIL-1.  Inputs: an operator, K sorted unique keys and the
+ * canonical CSR pattern (indptr, indices) of the J that asp_operator_ising_csr(op, K, keys, psi0)
+ * returned for some psi0.  The connections of row i are what asp_operator_apply lists for keys[i], in
+ * its order (the diagonal entry first; representatives and their coefficients for a symmetry-adapted
+ * basis); a connection whose target is not among the keys does not take part.  For finite amplitudes
+ * psi[K], normalised by the caller:
+ *     Mhat_ij = +0.0, then for the connections d of row i that land on j, in connection order,
+ *               Mhat_ij = Mhat_ij + ((c_d * |psi_j|) * |psi_i|)
+ *     J_ij    = 0.5 * (Mhat_ij + Mhat_ji)       (a side without a connection is +0.0)
+ * every operation rounded on its own (__dmul_rn, __dadd_rn, no contraction); the entry exists iff the sum
+ * is non-zero.  Whenever asp_operator_ising_csr(op, K, keys, psi) succeeds with the stencil's pattern,
+ * these values equal the ones it returns bit for bit.  STORED pairs are the entries of the pattern,
+ * SILENT pairs the pairs with at least one connection and no entry (their sum was exactly 0 for psi0).
+ * For new amplitudes the pattern has changed iff a stored pair now sums to exactly 0 or a silent pair no
+ * longer does: that is reported per draw (status 1), and nothing is written for that draw.
+ *
+ * asp_ising_stencil_create runs the action once, resolves the targets among the keys, groups the
+ * connections of every row by target (connection order kept inside a group) and keeps the groups, the
+ * places of every stored pair's forward and mirror group and the silent pairs on the device.
+ * ASP_ERR_INVALID: a null argument, unsorted or duplicate keys, a non-canonical pattern, a pattern entry
+ * that no connection produces, a pattern that holds (i, j) without (j, i), a key outside the sector, and
+ * — for operators whose rows may reach a state twice — a group without its mirror group (one-directional
+ * matrix elements: asp_operator_ising_csr sends the caller to the host route with the same code). */
+typedef struct asp_ising_stencil asp_ising_stencil;
+typedef struct asp_ising_stencil_counts {
+  uint64_t num_spins;     /* K */
+  uint64_t stored;        /* entries of the pattern */
+  uint64_t connections;   /* connections whose target is among the keys */
+  uint64_t groups;        /* (row, target) groups of them */
+  uint64_t silent_pairs;  /* unordered pairs with a connection and no entry */
+  uint64_t longest_group; /* connections of the longest group */
+} asp_ising_stencil_counts;
+int asp_ising_stencil_create(asp_operator const *op, uint64_t num_spins, uint64_t const *keys,
+                             int64_t const *indptr, int32_t const *indices, asp_ising_stencil **out);
+void asp_ising_stencil_destroy(asp_ising_stencil *st);
+int asp_ising_stencil_info(asp_ising_stencil const *st, asp_ising_stencil_counts *out);
+/* data[d][nnz] (pattern order) and status[d] (0 applied, 1 pattern changed: data[d] unspecified) of
+ * `count` draws psi[d][K]: one upload, a fixed number of launches (one fold per group in fixed order, one
+ * 0.5 * (a + b) per stored entry, the zero / non-zero counts per draw), one download of the values (the
+ * 2 * count counters follow in a copy of their own), one synchronisation.  Non-finite
+ * amplitudes fail the call (ASP_ERR_INVALID, the draw's index in the message) before any launch;
+ * count == 0 and K == 0 need no device.  A stencil serves one thread at a time. */
+int asp_ising_stencil_values(asp_ising_stencil *st, uint32_t count, double const *psi, double *data,
+                             int32_t *status);
+/* One draw of asp_sa_plan_reweight_stencil_batch: the plan takes the couplings of `psi` (K amplitudes)
+ * and, unless field == NULL (keep), the field; data_out (nnz doubles, or NULL) receives the couplings;
+ * status: 0 applied, 1 pattern changed (J's, or that of J + J^T) — the plan is exactly as it was. */
+typedef struct asp_sa_stencil_item {
+  asp_sa_plan *plan;
+  double const *psi;
+  double const *field;
+  double *data_out;
+  int32_t status;
+} asp_sa_stencil_item;
+/* asp_sa_plan_reweight(plan, nnz, indptr, indices, data_d, field_d) for every draw d with the values of
+ * asp_ising_stencil_values, which never visit the host on their way into the plans: an applied plan equals
+ * that call's result bit for bit (asp_sa_plan_info, the ELL values, the lazily uploaded row arrays where
+ * they exist, the host mirrors, diag_sum in row order, the scales with rows folded in index order).  One
+ * upload of all amplitudes (and one of the fields); per draw the merged values, row sums, row minima and
+ * diagonal entries come back, and data_out where asked for; the number of host synchronisations does not
+ * grow with count.  Every plan must have been created from, or cloned from a plan of, the stencil's
+ * pattern; the plans are pairwise distinct and have no live asp_sa_chains handle.  ASP_ERR_INVALID for
+ * the whole call, before any plan is touched and with the item's index in the message: a null stencil,
+ * null items with count > 0, a null plan or psi, another pattern, one plan twice, live chains, non-finite
+ * amplitudes or field, couplings that overflow.  A draw with status 1 does not stop the others. */
+int asp_sa_plan_reweight_stencil_batch(asp_ising_stencil *st, asp_sa_stencil_item *items, uint32_t count);
+/* Device time (ms, HIP events) of this thread's last successful asp_sa_plan_reweight_stencil_batch. */
+float asp_sa_plan_reweight_stencil_last_ms(void);
+
 /* Host-only (inspection, CPU tests): where the shared launches of the batched calls (asp_sa_anneal_batch,
  * asp_sa_chains_advance_batch, asp_sa_greedy_batch) place the workgroups of ONE launch class.  Member k
  * < count has groups[k] workgroups of about work[k] each.  The members go in descending work, stable,
