@@ -196,6 +196,24 @@ class SaStencilItem(ctypes.Structure):
     ]
 
 
+class SignScoresItem(ctypes.Structure):
+    """Mirror of ``asp_sign_scores_item`` (include/asp.h)."""
+
+    _fields_ = [
+        ("num_spins", c_u64),
+        ("count", c_u32),
+        ("x", c_void_p),
+        ("x_stride", c_u64),
+        ("num_scored", c_u64),
+        ("select", c_void_p),
+        ("exact", c_void_p),
+        ("weights", c_void_p),
+        ("out_matches", c_void_p),
+        ("out_signed", c_void_p),
+        ("out_total", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/asp.h declares
 SIGNATURES = {
     "asp_last_error": (ctypes.c_char_p, []),
@@ -350,6 +368,12 @@ SIGNATURES = {
     "asp_bonds_destroy": (None, [c_void_p]),
     "asp_bonds_last_ms": (c_float, []),
     "asp_sector_bonds_create": (c_int, [c_u64, c_u32, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
+    "asp_sign_scores": (c_int, [c_u64, c_u32, c_void_p, c_u64, c_u64] + [c_void_p] * 6),
+    "asp_sign_scores_batch": (c_int, [ctypes.POINTER(SignScoresItem), c_u32]),
+    "asp_sign_distances": (c_int, [c_u64, c_u32, c_void_p, c_u64, c_void_p]),
+    "asp_sa_chains_scores": (c_int, [c_void_p, c_u32, c_u64] + [c_void_p] * 6),
+    "asp_sa_chains_distances": (c_int, [c_void_p, c_u32, c_void_p]),
+    "asp_sign_scores_last_ms": (c_float, []),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -804,6 +804,45 @@ class Chains:
             return xs[best].copy(), float(es[best])
         return xs, es
 
+    _WHICH = {"best": 0, "current": 1}
+
+    def scores(self, exact, weights=None, select=None, which: str = "best"):
+        """``scores.sign_scores`` of the handle's configurations WHERE THEY ARE (``asp_sa_chains_scores``,
+        specification ASP-SCORE-1): ``(matches uint64[R], signed float64[R], total)`` of
+        every chain's best (``which="best"``) or current (``"current"``) configuration against ``exact``
+        and ``weights``, position ``i`` taking spin ``select[i]`` (``None``: all spins in order).  Nothing
+        is exported and the chains are not touched: what follows is bit for bit what follows without."""
+        from . import scores as _scores
+
+        if which not in self._WHICH:
+            raise ValueError("'which' must be 'best' or 'current'")
+        item = _scores._Item(None, exact, weights, select, self.hamiltonian.size, resident=True)
+        item._outputs(self.repetitions)
+        _lib.check(_lib.load().asp_sa_chains_scores(self._live(), ctypes.c_uint32(self._WHICH[which]),
+                                                    ctypes.c_uint64(item.scored), _lib.ptr(item.select),
+                                                    _lib.ptr(item.exact), _lib.ptr(item.weights),
+                                                    _lib.ptr(item.matches), _lib.ptr(item.signed),
+                                                    _lib.ptr(item.total)))
+        return item.result()
+
+    def accuracy_and_overlap(self, exact, weights=None, select=None, which: str = "best"):
+        """``(accuracy float64[R], overlap float64[R])`` from :meth:`scores`."""
+        from . import scores as _scores
+
+        matches, signed, total = self.scores(exact, weights, select, which)
+        scored = self.hamiltonian.size if select is None else np.asarray(select).reshape(-1).shape[0]
+        return _scores.accuracy_and_overlap_of(matches, signed, total, scored)
+
+    def distances(self, which: str = "best") -> np.ndarray:
+        """``uint32[R, R]``: the Hamming distances between the chains' best (or current) configurations,
+        computed where they are (``asp_sa_chains_distances``)."""
+        if which not in self._WHICH:
+            raise ValueError("'which' must be 'best' or 'current'")
+        out = np.zeros((self.repetitions, self.repetitions), dtype=np.uint32)
+        _lib.check(_lib.load().asp_sa_chains_distances(self._live(), ctypes.c_uint32(self._WHICH[which]),
+                                                       _lib.ptr(out)))
+        return out
+
     def _export(self, names) -> dict:
         shapes = {"x_current": (self.repetitions, self.words), "x_best": (self.repetitions, self.words),
                   "tracked_current": (self.repetitions,), "tracked_best": (self.repetitions,),
@@ -896,12 +935,17 @@ class Chains:
 def anneal_until(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: int = 5120,
                  beta0: Optional[float] = None, beta1: Optional[float] = None, repetitions: int = 1,
                  only_best: bool = True, sweep_order: Optional[str] = None, check_every: int = 512,
-                 patience: Optional[int] = None):
+                 patience: Optional[int] = None, target=None):
     """``anneal`` that may stop early: the usual geometric ladder of ``number_sweeps`` sweeps is run
     in segments of ``check_every`` sweeps (``Chains``), and the run ends once NO chain's best energy
     has improved for ``patience`` consecutive segments.  Returns ``(x, e, sweeps_run)`` with
     ``(x, e)`` as ``anneal`` returns them.  ``patience=None`` never stops early and returns exactly
-    ``anneal(...)``'s result (the continuation law).  Chains stay on this rank."""
+    ``anneal(...)``'s result (the continuation law).  Chains stay on this rank.
+
+    ``target=(exact, weights, accuracy)``: the run also ends after the first segment at which some
+    chain's best configuration has a sign accuracy (up to a global flip) of at least ``accuracy``
+    against the packed signs ``exact`` — scored on the device, where the chains are (``Chains.scores``;
+    ``weights`` may be ``None``).  ``target=None`` is the run without it."""
     order = resolve_sweep_order(sweep_order)  # (first: a bad order fails without a GPU)
     check_every = int(check_every)
     if check_every < 1:
@@ -910,6 +954,7 @@ def anneal_until(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: in
         raise ValueError("'patience' must be positive or None")
     if not isinstance(hamiltonian, Hamiltonian):
         raise TypeError("'hamiltonian' must be a Hamiltonian")
+    target = _check_target(target)
     if beta0 is None or beta1 is None:
         info = hamiltonian.info()
         beta0 = info.beta0_auto if beta0 is None else beta0
@@ -927,8 +972,27 @@ def anneal_until(hamiltonian: Hamiltonian, x0=None, seed=None, number_sweeps: in
             best = now
             if patience is not None and still >= int(patience):
                 break
+            if target is not None and _target_met(chains, target):
+                break
         x, e = chains.result(only_best=only_best)
     return x, e, done
+
+
+def _check_target(target):
+    if target is None:
+        return None
+    exact, weights, accuracy = target
+    accuracy = float(accuracy)
+    if not 0.0 <= accuracy <= 1.0:
+        raise ValueError("a target's accuracy must lie in [0, 1]")
+    return exact, weights, accuracy
+
+
+def _target_met(chains: "Chains", target) -> bool:
+    """Whether some chain's best configuration reaches the target's accuracy."""
+    exact, weights, wanted = target
+    accuracy, _ = chains.accuracy_and_overlap(exact, weights)
+    return bool(np.any(accuracy >= wanted))
 
 
 def advance_chains(chains, betas, sweep_order=None, progress: bool = False):
@@ -977,12 +1041,14 @@ def advance_chains(chains, betas, sweep_order=None, progress: bool = False):
 def anneal_batch_until(hamiltonians, seed=None, number_sweeps: int = 5120, repetitions: int = 64,
                        only_best: bool = True, beta0: Optional[float] = None, beta1: Optional[float] = None,
                        sweep_order: Optional[str] = None, check_every: int = 512,
-                       patience: Optional[int] = None):
+                       patience: Optional[int] = None, target=None):
     """``[anneal_until(h, seed=seed, number_sweeps=..., repetitions=..., ...) for h in hamiltonians]``
     with every segment of all problems still running in one device call (``advance_chains``): problem
     ``i`` stops once none of its chains improved for ``patience`` consecutive segments and is left out
     of the later calls.  Returns ``[(x, e, sweeps_run), ...]``; with ``patience=None`` nothing stops
-    early and ``(x, e)`` is ``anneal_batch(...)``'s element.  ``seed`` as in ``anneal_batch``."""
+    early and ``(x, e)`` is ``anneal_batch(...)``'s element.  ``seed`` as in ``anneal_batch``.
+    ``target``: ``None``, or one ``(exact, weights, accuracy)`` (or ``None``) per problem as in
+    ``anneal_until``: a problem also stops after the segment at which one of its chains meets it."""
     order = resolve_sweep_order(sweep_order)  # (first: a bad order fails without a GPU)
     check_every = int(check_every)
     if check_every < 1:
@@ -996,6 +1062,9 @@ def anneal_batch_until(hamiltonians, seed=None, number_sweeps: int = 5120, repet
             raise TypeError("'hamiltonians' must hold Hamiltonian objects")
     if len({id(h) for h in hamiltonians}) != n:
         raise ValueError("anneal_batch_until: every problem needs its own Hamiltonian object")
+    targets = [None] * n if target is None else [_check_target(t) for t in target]
+    if len(targets) != n:
+        raise ValueError("anneal_batch_until: %d problems and %d targets" % (n, len(targets)))
     repetitions = int(repetitions)
     if repetitions < 1:
         raise ValueError("'repetitions' must be positive")
@@ -1026,8 +1095,11 @@ def anneal_batch_until(hamiltonians, seed=None, number_sweeps: int = 5120, repet
             for i, (_, improved) in zip(running, told):
                 done[i] = min(done[i] + check_every, schedules[i].shape[0])
                 still[i] = 0 if improved else still[i] + 1
-                if done[i] < schedules[i].shape[0] and not (patience is not None and still[i] >= int(patience)):
-                    later.append(i)
+                if done[i] >= schedules[i].shape[0] or (patience is not None and still[i] >= int(patience)):
+                    continue
+                if targets[i] is not None and _target_met(handles[i], targets[i]):
+                    continue
+                later.append(i)
             running = later
         results = []
         for i, c in enumerate(handles):

@@ -38,6 +38,7 @@ SOURCES = [
     "sparsify.hip",
     "level_segments.hip",
     "bond_stats.hip",
+    "sign_scores.hip",
     "sa_plan.cpp",
     "greedy.cpp",
     "greedy_tree.hip",

@@ -33,6 +33,7 @@ __all__ = [
     "load_ground_state",
     "save_ground_state",
     "compute_accuracy_and_overlap",
+    "compute_accuracies_and_overlaps",
     "make_hamiltonian_extension",
     "make_hamiltonian_extensions",
     "extension_spins",
@@ -571,6 +572,18 @@ def compute_accuracy_and_overlap(
     accuracy = max(accuracy, 1 - accuracy)
     overlap = abs(np.dot(truth * guess, weights / np.sum(weights)))
     return accuracy, overlap
+
+
+def compute_accuracies_and_overlaps(predicted_list, exact_list, weights_list) -> list:
+    """``[compute_accuracy_and_overlap(p, e, w) for p, e, w in zip(...)]`` as ONE device call
+    (``scores.accuracy_and_overlap_each``: ``asp_sign_scores_batch``, specification ASP-SCORE-1,
+    DESIGN.md §3.11): a list of ``(accuracy, overlap)``.  Every accuracy is the host function's bit for
+    bit; every overlap is within ``(K + 64) * 2**-53`` of it (a pairwise tree instead of a dot product
+    with the normalised weights)."""
+    from . import scores
+
+    accuracy, overlap = scores.accuracy_and_overlap_each(list(predicted_list), list(exact_list), list(weights_list))
+    return list(zip(accuracy, overlap))
 
 
 def binary_search(haystack, needles) -> np.ndarray:

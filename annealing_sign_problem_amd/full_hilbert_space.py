@@ -72,24 +72,43 @@ class Simulation:
         # chains can reach exactly is E(sign psi)
         self.energy = e_signs
 
-    def analyze(self, xs: np.ndarray, es: np.ndarray, accuracy_threshold: float = 0.995,
-                overlap_threshold: float = 0.995, residual_threshold: float = 1e-12):
-        """Fractions of chains above the thresholds (experiments/full_hilbert_space.py:164-186)."""
+    def chain_scores(self, xs: np.ndarray, es: np.ndarray, score: str = "host") -> np.ndarray:
+        """``float64[len(xs), 3]``: per chain the sign accuracy, the overlap and the relative energy
+        residual.  ``score="device"``: accuracy and overlap of ALL chains in one device call
+        (``scores.accuracy_and_overlap``) instead of one host call per chain; the
+        accuracies are the same, the overlaps agree to ``(K + 64) * 2**-53``."""
+        if score not in ("host", "device"):
+            raise ValueError("'score' must be 'host' or 'device'")
         results = np.zeros((len(xs), 3), dtype=np.float64)
+        if score == "device" and len(xs):
+            from . import scores
+
+            results[:, 0], results[:, 1] = scores.accuracy_and_overlap(
+                np.asarray(xs), self.exact_model.initial_signs, self.weights)
+            results[:, 2] = np.abs((np.asarray(es, dtype=np.float64) - self.energy) / self.energy)
+            return results
         for i, (x, e) in enumerate(zip(xs, es)):
             accuracy, overlap = common.compute_accuracy_and_overlap(
                 predicted=x, exact=self.exact_model.initial_signs, weights=self.weights)
             results[i] = [accuracy, overlap, abs((e - self.energy) / self.energy)]
+        return results
+
+    def analyze(self, xs: np.ndarray, es: np.ndarray, accuracy_threshold: float = 0.995,
+                overlap_threshold: float = 0.995, residual_threshold: float = 1e-12, score: str = "host"):
+        """Fractions of chains above the thresholds (experiments/full_hilbert_space.py:164-186)."""
+        results = self.chain_scores(xs, es, score)
         return (float(np.mean(results[:, 0] > accuracy_threshold)),
                 float(np.mean(results[:, 1] > overlap_threshold)),
                 float(np.mean(results[:, 2] <= residual_threshold)))
 
-    def run(self, number_sweeps: int, repetitions: int, seed=None, sweep_order: str = None):
-        """One trial (commented block at experiments/full_hilbert_space.py:212-218)."""
+    def run(self, number_sweeps: int, repetitions: int, seed=None, sweep_order: str = None,
+            score: str = "host"):
+        """One trial (commented block at experiments/full_hilbert_space.py:212-218).  ``score``: where
+        the chains are scored, as in :meth:`chain_scores`."""
         xs, es = sa.anneal(self.exact_model.ising_hamiltonian, seed=seed,
                            number_sweeps=number_sweeps, repetitions=repetitions, only_best=False,
                            sweep_order=sweep_order)
-        return self.analyze(xs, es)
+        return self.analyze(xs, es, **({"score": score} if score != "host" else {}))
 
 
 def summarise(number_sweeps: int, results: np.ndarray) -> List:
@@ -102,7 +121,7 @@ def summarise(number_sweeps: int, results: np.ndarray) -> List:
 
 def run_experiment(model: str, sweeps: Sequence[int], repetitions: int, trials: int, seed: int,
                    output: str, log=print, yaml_filename: str = None,
-                   hdf5_filename: str = None, sweep_order: str = None) -> List[List]:
+                   hdf5_filename: str = None, sweep_order: str = None, score: str = "host") -> List[List]:
     if os.path.exists(output):
         raise ValueError("output file '{}' already exists".format(output))
     simulation = Simulation(model, yaml_filename, hdf5_filename)
@@ -116,7 +135,8 @@ def run_experiment(model: str, sweeps: Sequence[int], repetitions: int, trials: 
         for trial in range(trials):
             results[trial] = simulation.run(number_sweeps, repetitions,
                                             seed=seed + 1000003 * trial + number_sweeps,
-                                            sweep_order=sweep_order)
+                                            sweep_order=sweep_order,
+                                            **({"score": score} if score != "host" else {}))
         row = summarise(number_sweeps, results)
         rows.append(row)
         with open(output, "a") as f:
@@ -140,12 +160,17 @@ def main(argv=None):
                         help="'shuffled' (default): a fresh visiting order every sweep, the reference "
                              "annealer's statistics — the published curves (DESIGN.md §6.1); "
                              "'colour': this package's fixed colour order, faster, a different chain")
+    parser.add_argument("--score", type=str, default="host", choices=["host", "device"],
+                        help="where the chains of a trial are scored: 'host' (default: one "
+                             "compute_accuracy_and_overlap call per chain) or 'device' (all chains in one "
+                             "call, scores.accuracy_and_overlap; overlaps agree to rounding)")
     args = parser.parse_args(argv)
     sweeps = [int(s) for s in args.number_sweeps.split(",")]
     if (args.model is None) == (args.yaml is None):
         raise SystemExit("give exactly one of --model and --yaml")
     run_experiment(args.model, sweeps, args.repetitions, args.trials, args.seed, args.output,
-                   yaml_filename=args.yaml, hdf5_filename=args.hdf5, sweep_order=args.sweep_order)
+                   yaml_filename=args.yaml, hdf5_filename=args.hdf5, sweep_order=args.sweep_order,
+                   score=args.score)
 
 
 if __name__ == "__main__":

@@ -220,7 +220,7 @@ def process_cluster(cluster, hamiltonian, ground_state, noisy_ground_state, nois
 def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, noisy_ground_state,
                    noisy_log_coeff_fn, order: int, global_cutoff: float, jobs: int = 1,
                    greedy_batch: bool = False, external_field: bool = False, build_batch: bool = False,
-                   level_batch: bool = False):
+                   level_batch: bool = False, score_batch: bool = False):
     """First half of :func:`process_clusters_batched`: the models of every order of every cluster,
     each with its greedy result — a list of ``(cluster index, model, exact_signs, weights, result
     so far)`` in cluster order.  The models of a cluster do not depend on its solutions (the
@@ -233,7 +233,9 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
     device call (``common.make_ising_models``) and the models are sparsified (per
     cluster) — instead of cluster by cluster; the models and the results are the same.  ``level_batch``
     (with ``build_batch``): the extension and the sparsification of a level are ONE segmented device call
-    each as well (``common.extend_and_sparsify_models``); the same models again."""
+    each as well (``common.extend_and_sparsify_models``); the same models again.
+    ``score_batch`` (with ``greedy_batch``): the greedy solutions of the round are scored by one device
+    call (:func:`score_solutions`); the accuracies are the same, the overlaps agree to rounding."""
     basis = hamiltonian.basis
     field = {"external_field": True} if external_field else {}
 
@@ -292,9 +294,8 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
         if greedy_batch and staged:
             solutions = common.solve_ising_models([m for _, m, _, _, _ in staged],
                                                   [clusters[c] for c, _, _, _, _ in staged], mode="greedy")
-            for (_, _, exact_signs, weights, r), x in zip(staged, solutions):
-                r.greedy_accuracy, r.greedy_overlap = common.compute_accuracy_and_overlap(x, exact_signs,
-                                                                                          weights)
+            for (_, _, _, _, r), scored in zip(staged, score_solutions(staged, solutions, score_batch)):
+                r.greedy_accuracy, r.greedy_overlap = scored
         return staged
 
     if build_batch and len(clusters) > 0:
@@ -323,6 +324,23 @@ def level_batch_of(args) -> dict:
     return {"level_batch": True} if getattr(args, "level_batch", False) else {}
 
 
+def score_batch_of(args) -> dict:
+    """--score-batch as the ``score_batch`` keyword of :func:`stage_clusters`, :func:`anneal_staged` and
+    :func:`process_clusters_batched`; empty without it, so that every call is the one it was."""
+    return {"score_batch": True} if getattr(args, "score_batch", False) else {}
+
+
+def score_solutions(staged, solutions, score_batch: bool = False) -> list:
+    """``(accuracy, overlap)`` of every solution of a round against the exact signs and weights of its
+    staged entry: one host call each, or — ``score_batch`` — ONE device call for all of them
+    (``common.compute_accuracies_and_overlaps``)."""
+    if score_batch:
+        return common.compute_accuracies_and_overlaps(solutions, [e for _, _, e, _, _ in staged],
+                                                      [w for _, _, _, w, _ in staged])
+    return [common.compute_accuracy_and_overlap(x, exact_signs, weights)
+            for (_, _, exact_signs, weights, _), x in zip(staged, solutions)]
+
+
 def early_stop_of(args) -> dict:
     """--anneal-patience / --anneal-check-every / --anneal-method as the ``early_stop`` keyword of :func:`anneal_staged`
     and :func:`process_clusters_batched`; empty without them, so that every call is the one it was."""
@@ -335,13 +353,15 @@ def early_stop_of(args) -> dict:
 
 def anneal_staged(staged, clusters: Sequence[np.ndarray], annealing: bool,
                   sweep_order: Optional[str] = None,
-                  early_stop: Optional[dict] = None) -> List[List[OptimizationResult]]:
+                  early_stop: Optional[dict] = None,
+                  score_batch: bool = False) -> List[List[OptimizationResult]]:
     """Second half: the annealing of ALL staged models — every cluster at every order — in one
     batched device call, scored and sorted back into one list of results per cluster.
     ``early_stop``: despite its name (it began as the early stopping alone) the dict of EVERY extra
     keyword of :func:`common.solve_ising_models` that the command line selects, passed on as it is —
     ``{"patience": N, "check_every": S}`` (--anneal-patience) or ``{"method": "population" |
-    "tempering"}`` (--anneal-method, which selects another algorithm); see :func:`early_stop_of`."""
+    "tempering"}`` (--anneal-method, which selects another algorithm); see :func:`early_stop_of`.
+    ``score_batch``: the solutions are scored by one device call (:func:`score_solutions`)."""
     if annealing and staged:
         started = time.perf_counter()
         solutions = common.solve_ising_models([m for _, m, _, _, _ in staged],
@@ -354,8 +374,8 @@ def anneal_staged(staged, clusters: Sequence[np.ndarray], annealing: bool,
                              "in %.2f s = %.1f G flips/s\n" % (
                                  len(clusters), len(staged), spins, max(m.size for _, m, _, _, _ in staged),
                                  seconds, spins * 64 * 5120 / seconds * 1e-9))
-        for (_, _, exact_signs, weights, r), x in zip(staged, solutions):
-            r.sa_accuracy, r.sa_overlap = common.compute_accuracy_and_overlap(x, exact_signs, weights)
+        for (_, _, _, _, r), scored in zip(staged, score_solutions(staged, solutions, score_batch)):
+            r.sa_accuracy, r.sa_overlap = scored
     results: List[List[OptimizationResult]] = [[] for _ in clusters]
     for index, h, _, _, r in staged:
         results[index].append(r)
@@ -371,19 +391,22 @@ def process_clusters_batched(clusters: Sequence[np.ndarray], hamiltonian, ground
                              early_stop: Optional[dict] = None,
                              external_field: bool = False,
                              build_batch: bool = False,
-                             level_batch: bool = False) -> List[List[OptimizationResult]]:
+                             level_batch: bool = False,
+                             score_batch: bool = False) -> List[List[OptimizationResult]]:
     """``[process_cluster(c, ...) for c in clusters]`` with the annealing of ALL models — every
     cluster at every order — in one batched device call (:func:`stage_clusters`, then
     :func:`anneal_staged`); the results are identical to the per-cluster loop.  ``early_stop``: the
     extra keywords of :func:`common.solve_ising_models` (early stopping or the annealing method), as in
     :func:`anneal_staged`.  ``external_field``: as in :func:`process_cluster`.  ``build_batch``: as in
-    :func:`stage_clusters`; ``level_batch`` likewise."""
+    :func:`stage_clusters`; ``level_batch`` likewise.  ``score_batch``: as in :func:`score_solutions`."""
     staged = stage_clusters(clusters, hamiltonian, ground_state, noisy_ground_state, noisy_log_coeff_fn,
                             order, global_cutoff, jobs, **({"greedy_batch": True} if greedy_batch else {}),
                             **({"external_field": True} if external_field else {}),
                             **({"build_batch": True} if build_batch else {}),
-                            **({"level_batch": True} if level_batch else {}))
-    return anneal_staged(staged, clusters, annealing, sweep_order, **({"early_stop": early_stop} if early_stop else {}))
+                            **({"level_batch": True} if level_batch else {}),
+                            **({"score_batch": True} if score_batch else {}))
+    return anneal_staged(staged, clusters, annealing, sweep_order, **({"early_stop": early_stop} if early_stop else {}),
+                         **({"score_batch": True} if score_batch else {}))
 
 
 def parse_command_line(argv=None):
@@ -450,6 +473,11 @@ def parse_command_line(argv=None):
                              "call per order (make_ising_models, asp_operator_ising_segments) instead of one "
                              "call per cluster; needs --batch > 1 and --annealing or --greedy-batch; the "
                              "output is the same")
+    parser.add_argument("--score-batch", default=False, action="store_true",
+                        help="score all solutions of a round of --batch clusters with ONE device call "
+                             "(compute_accuracies_and_overlaps, asp_sign_scores_batch) instead of one host call "
+                             "per solution; needs --batch > 1; the accuracies are the same, the overlaps agree to "
+                             "rounding")
     parser.add_argument("--greedy-tree", choices=("host", "device"), default=None,
                         help="where the greedy solver builds its strongest-coupling tree (default: "
                              "$ASP_GREEDY_TREE or host); the output is the same")
@@ -477,6 +505,8 @@ def parse_command_line(argv=None):
                          "segments)".format(args.anneal_method))
     if args.build_batch and (args.batch <= 1 or not (args.annealing or args.greedy_batch)):
         parser.error("--build-batch needs --batch > 1 and --annealing or --greedy-batch (it builds a round at once)")
+    if args.score_batch and args.batch <= 1:
+        parser.error("--score-batch needs --batch > 1 (it scores a round at once)")
     if args.level_batch and not args.build_batch:
         parser.error("--level-batch needs --build-batch (it batches the rest of a level of the round)")
     return args
@@ -653,7 +683,7 @@ def _worker_chunk(indices):
                                          jobs=args.jobs, sweep_order=args.sweep_order,
                                          **({"greedy_batch": True} if args.greedy_batch else {}),
                                          **early_stop_of(args), **external_field_of(args), **build_batch_of(args),
-                                         **level_batch_of(args))
+                                         **level_batch_of(args), **score_batch_of(args))
         return report([",".join(r.to_csv_str() for r in columns) for columns in chunk])
 
     def work(cluster):
@@ -864,7 +894,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                                              args.order, args.global_cutoff, args.annealing,
                                              jobs=args.jobs, sweep_order=args.sweep_order, **greedy_batch,
                                              **early_stop_of(args), **external_field_of(args), **build_batch_of(args),
-                                             **level_batch_of(args))
+                                             **level_batch_of(args), **score_batch_of(args))
             lines += [",".join(r.to_csv_str() for r in columns) for columns in chunk]
         return lines
 
@@ -896,7 +926,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                 return stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
                                       noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
                                       **greedy_batch, **external_field_of(args), **build_batch_of(args),
-                                      **level_batch_of(args))
+                                      **level_batch_of(args), **score_batch_of(args))
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(stage, my_share(0)) if rounds else None
@@ -906,7 +936,8 @@ def _main_in_group(args, asp_dist, created_group, phase):
 
                     def solve(some, staged=staged):  # (`some` is this rank's share of the round)
                         return [",".join(x.to_csv_str() for x in columns)
-                                for columns in anneal_staged(staged, some, True, args.sweep_order, **early_stop_of(args))]
+                                for columns in anneal_staged(staged, some, True, args.sweep_order, **early_stop_of(args),
+                                                     **score_batch_of(args))]
 
                     lines = asp_dist.map_sharded_many(rounds[r], solve)
                     if writer:
@@ -951,7 +982,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                 return some, stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
                                             noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
                                             **greedy_batch, **external_field_of(args), **build_batch_of(args),
-                                            **level_batch_of(args))
+                                            **level_batch_of(args), **score_batch_of(args))
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(next_round)
@@ -961,7 +992,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                         break
                     upcoming = builder.submit(next_round)
                     append(lines_of(anneal_staged(staged, some, args.annealing, args.sweep_order,
-                                                  **early_stop_of(args))))
+                                                  **early_stop_of(args), **score_batch_of(args))))
         else:
             while True:
                 some = list(itertools.islice(clusters, step))

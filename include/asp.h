@@ -1250,6 +1250,60 @@ float asp_bonds_last_ms(void);
 int asp_sector_bonds_create(uint64_t n, uint32_t width, uint32_t const *idx_dev, double const *val_dev,
                             double const *psi_dev, asp_bonds **out);
 
+/* ------------------------------------------------------------------------- */
+/* Sign scores (csrc/sign_scores.hip, specification ASP-SCORE-1, DESIGN.md   */
+/* 3.11): common.py:211-229 of the reference for many configurations at once */
+/* ------------------------------------------------------------------------- */
+
+/* Scores of `count` packed configurations x[c * x_stride + word] of one K-spin model (bit i of word
+ * i / 64 set: s_i = +1; W = ceil(K / 64) words each, x_stride >= W; bits at positions >= K are masked)
+ * against exact (K0 = num_scored bits) and weights (K0 doubles, NULL: all 1.0).  Position i < K0 compares
+ * bit select[i] of x with bit i of exact; select == NULL: K0 = K and the identity (num_scored is then
+ * not read).  Per configuration
+ *   matches = #{ i < K0 : g_i == e_i }                                   (out_matches[count], exact)
+ *   signed  = the pairwise tree, strides ASCENDING 1, 2, 4, ..., over t_i = +w_i on a match and -w_i
+ *             otherwise, padded with +0.0 to the next power of two       (out_signed[count])
+ * and once per call total = the same tree over w_i (out_total[1]).  Every add is rounded on its own and
+ * nothing is multiplied, so the bits depend on no launch choice; a zero may carry either sign.  Host
+ * pointers; each output may be NULL.  Checked before any device work and before any output is written —
+ * ASP_ERR_INVALID: a null x (count > 0, K > 0), exact (K0 > 0) or items; x_stride in 1 .. W - 1 (0 is W);
+ * a select entry outside [0, K); a weight that is negative, NaN or infinite; ASP_ERR_TOO_LARGE:
+ * K0 >= 2^31.  count = 0 needs no device and writes nothing; K0 = 0 gives matches 0 and +0.0 twice. */
+int asp_sign_scores(uint64_t num_spins, uint32_t count, uint64_t const *x, uint64_t x_stride,
+                    uint64_t num_scored, int32_t const *select, uint64_t const *exact,
+                    double const *weights, uint64_t *out_matches, double *out_signed, double *out_total);
+typedef struct asp_sign_scores_item {
+  uint64_t num_spins;
+  uint32_t count;
+  uint64_t const *x;
+  uint64_t x_stride;
+  uint64_t num_scored;
+  int32_t const *select;
+  uint64_t const *exact;
+  double const *weights;
+  uint64_t *out_matches;
+  double *out_signed;
+  double *out_total;
+} asp_sign_scores_item;
+/* Many models with their configurations: one upload, launches whose number does not depend on `count`,
+ * one download.  Item i receives the bits of the single call, for any order and composition of the
+ * batch; a refusal names the item's index.  A batch of 0 items needs no device. */
+int asp_sign_scores_batch(asp_sign_scores_item const *items, uint32_t count);
+/* out[a * count + b] = popcount((x_a xor x_b) over bits < K): symmetric, zero diagonal, exact.
+ * ASP_ERR_TOO_LARGE: count > 32768 or K >= 2^32. */
+int asp_sign_distances(uint64_t num_spins, uint32_t count, uint64_t const *x, uint64_t x_stride, uint32_t *out);
+/* The same for the configurations RESIDENT in a chains handle, in original spin order — which = 0: every
+ * chain's best, 1: its current one (ASP_ERR_INVALID above 1) — without exporting them; count is the
+ * handle's repetitions.  Only reads the handle: the chains after the call are bit for bit the chains
+ * without it. */
+int asp_sa_chains_scores(asp_sa_chains *c, uint32_t which, uint64_t num_scored, int32_t const *select,
+                         uint64_t const *exact, double const *weights, uint64_t *out_matches,
+                         double *out_signed, double *out_total);
+int asp_sa_chains_distances(asp_sa_chains *c, uint32_t which, uint32_t *out);
+/* Device time (ms, HIP events) of the kernels of this thread's last call of the five above; copies
+ * between host and device are not in it. */
+float asp_sign_scores_last_ms(void);
+
 #ifdef __cplusplus
 }
 #endif
