@@ -287,6 +287,9 @@ SIGNATURES = {
     "asp_sa_plan_reweight": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "asp_sa_plan_reweight_last_ms": (c_float, [c_void_p]),
     "asp_sa_plan_clone": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
+    "asp_sa_plan_create_segments": (c_int, [c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "asp_sa_plan_segments_last_ms": (c_float, []),
+    "asp_sa_plan_read_array": (c_int, [c_void_p, c_int, c_void_p, c_u64, ctypes.POINTER(c_u64)]),
     "asp_ising_stencil_create": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
     "asp_ising_stencil_destroy": (None, [c_void_p]),
     "asp_ising_stencil_info": (c_int, [c_void_p, ctypes.POINTER(IsingStencilCounts)]),

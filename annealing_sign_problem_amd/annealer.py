@@ -34,6 +34,9 @@ __all__ = [
     "Hamiltonian",
     "PatternMismatch",
     "reweight_hamiltonians",
+    "plan_hamiltonians",
+    "plan_hamiltonians_last_ms",
+    "read_plan_array",
     "anneal",
     "anneal_batch",
     "anneal_traces",
@@ -379,6 +382,75 @@ def reweight_hamiltonians(hamiltonians, stencil, psis, fields=None) -> list:
 def reweight_hamiltonians_last_ms() -> float:
     """Device time (ms, HIP events) of this thread's last :func:`reweight_hamiltonians`."""
     return float(_lib.load().asp_sa_plan_reweight_stencil_last_ms())
+
+
+PLAN_ARRAYS = {  # asp_sa_plan_read_array: name -> (id, dtype)
+    "color_block_start": (0, np.uint32), "block_width": (1, np.uint32), "ell_off": (2, np.uint64),
+    "ell_col": (3, np.uint32), "ell_col4": (4, np.uint32), "ell_val": (5, np.float64),
+    "spin_of_pos": (6, np.uint32), "pos_of_spin": (7, np.uint32), "field_pos": (8, np.float64),
+}
+
+
+def read_plan_array(plan, name: str) -> np.ndarray:
+    """The device array ``name`` (a key of ``PLAN_ARRAYS``) of a plan handle, copied to the host; an
+    empty array where the plan does not hold it (``asp_sa_plan_read_array``)."""
+    which, dtype = PLAN_ARRAYS[name]
+    lib = _lib.load()
+    size = ctypes.c_uint64(0)
+    rc = lib.asp_sa_plan_read_array(plan, which, None, ctypes.c_uint64(0), ctypes.byref(size))
+    if size.value == 0:
+        _lib.check(rc)
+        return np.empty(0, dtype=dtype)
+    out = np.empty(size.value // np.dtype(dtype).itemsize, dtype=dtype)
+    _lib.check(lib.asp_sa_plan_read_array(plan, which, _lib.ptr(out), ctypes.c_uint64(out.nbytes),
+                                          ctypes.byref(size)))
+    return out
+
+
+def plan_hamiltonians(hamiltonians) -> None:
+    """:meth:`Hamiltonian.plan` of many Hamiltonians in ONE device call (``asp_sa_plan_create_segments``,
+    DESIGN.md §4.15): every Hamiltonian without a valid cached plan gets the plan its own ``plan()`` would
+    have made, bit for bit; those with one are left alone.  A refusal (``AspError``, the message naming
+    the first offending Hamiltonian as "segment g" among the ones that were planned) leaves all of them
+    without a plan."""
+    todo, seen = [], set()
+    for h in hamiltonians:
+        if id(h) in seen or (h._plan is not None and h._plan_key == h._key()):
+            continue
+        seen.add(id(h))
+        todo.append(h)
+    if not todo:
+        return
+    lib = _lib.load()
+    _lib.require_gpu()
+    for h in todo:
+        h._release_plan()  # (a stale one)
+    arrays = [h._arrays() for h in todo]
+    offsets = np.zeros(len(todo) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([h.size for h in todo], dtype=np.uint64)
+    entries = np.zeros(len(todo) + 1, dtype=np.int64)
+    entries[1:] = np.cumsum([a[1].size for a in arrays], dtype=np.int64)
+    indptr = np.zeros(int(offsets[-1]) + 1, dtype=np.int64)
+    for g, a in enumerate(arrays):
+        indptr[int(offsets[g]) + 1:int(offsets[g + 1]) + 1] = a[0][1:] + entries[g]
+    indices = np.concatenate([a[1] for a in arrays]) if arrays else np.empty(0, dtype=np.int32)
+    data = np.concatenate([a[2] for a in arrays])
+    field = np.concatenate([a[3] for a in arrays])
+    plans = (ctypes.c_void_p * len(todo))()
+    _lib.check(lib.asp_sa_plan_create_segments(ctypes.c_uint64(len(todo)), _lib.ptr(offsets), _lib.ptr(indptr),
+                                               _lib.ptr(np.ascontiguousarray(indices, dtype=np.int32)),
+                                               _lib.ptr(np.ascontiguousarray(data, dtype=np.float64)),
+                                               _lib.ptr(np.ascontiguousarray(field, dtype=np.float64)), plans))
+    for h, handle in zip(todo, plans):
+        h._plan = ctypes.c_void_p(handle)
+        h._plan_key = h._key()
+        _lib.track(h)
+
+
+def plan_hamiltonians_last_ms() -> float:
+    """Device time (ms, HIP events; copies excluded) of this thread's last :func:`plan_hamiltonians`
+    call that had anything to plan."""
+    return float(_lib.load().asp_sa_plan_segments_last_ms())
 
 
 def resolve_sweep_order(sweep_order: Optional[str]) -> str:

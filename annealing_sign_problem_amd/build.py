@@ -51,6 +51,7 @@ SOURCES = [
     "sa_population.hip",
     "sa_cluster.hip",
     "sa_reweight.hip",
+    "sa_plan_segments.hip",
     "ising_stencil.hip",
 ]
 

@@ -638,7 +638,7 @@ def _project_on_frozen(model: IsingModel, x: np.ndarray, frozen_spins) -> np.nda
 def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_sweeps: int = 5120,
                        repetitions: int = 64, sweep_order: Optional[str] = None, mode: str = "sa",
                        check_every: Optional[int] = None, patience: Optional[int] = None,
-                       method: str = "anneal", tree: Optional[str] = None):
+                       method: str = "anneal", plan_batch: bool = False, tree: Optional[str] = None):
     """``[solve_ising_model(m, mode, f, seed, number_sweeps, repetitions) for m, f in
     zip(models, frozen_spins)]`` with all annealing chains of all models in ONE device call
     (``sa.anneal_batch``): the same result for every model, at the throughput of a full chip
@@ -650,7 +650,10 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
     ``method`` (not in the reference; default ``"anneal"``): ``"population"`` or ``"tempering"`` solve
     every model with ``sa.population_anneal_batch`` / ``sa.parallel_tempering_batch`` instead, in
     ``number_sweeps // 10`` steps / rounds of ten sweeps — the sweep count of the plain call.
-    ``tree`` (``mode="greedy"``): as in :func:`solve_ising_model`."""
+    ``tree`` (``mode="greedy"``): as in :func:`solve_ising_model`.
+    ``plan_batch`` (not in the reference; default off): the sweep plans of all models are made by one
+    segmented device call (``sa.plan_hamiltonians``) before the solve instead of one by one inside it;
+    the results are the same."""
     if method not in ("anneal", "population", "tempering"):
         raise ValueError(
             "invalid method specified: '{}'; expected 'anneal', 'population' or 'tempering'".format(method))
@@ -663,6 +666,11 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
             raise ValueError("method='{}' runs steps of ten sweeps: 'number_sweeps' must be at least 10".format(method))
     models = list(models)
     frozen = [None] * len(models) if frozen_spins is None else list(frozen_spins)
+    if mode not in ("sa", "greedy"):
+        raise ValueError(
+            "invalid mode specified: '{}'; expected either 'sa' or 'greedy'".format(mode))
+    if plan_batch:
+        sa.plan_hamiltonians([m.ising_hamiltonian for m in models])
     if mode == "greedy":
         solved = sa.greedy_solve_batch([m.ising_hamiltonian for m in models], tree=tree)
         return [_project_on_frozen(m, x, f) for m, (x, _), f in zip(models, solved, frozen)]

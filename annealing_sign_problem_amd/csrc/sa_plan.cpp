@@ -61,7 +61,22 @@ unsigned host_threads(uint64_t n) {
 
 std::atomic<uint64_t> g_layout_builds{0};  // asp_sa_layout_build_count
 
+// ASP_PLAN_TIMING=1: stage times of the layout build on stderr (development aid)
+struct StageTimer {
+  const bool timing = std::getenv("ASP_PLAN_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point start = std::chrono::steady_clock::now();
+  void operator()(const char *name) {
+    if (!timing) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "  plan stage %-12s %8.3f ms\n", name,
+                 std::chrono::duration<double, std::milli>(now - start).count());
+    start = now;
+  }
+};
+
 }  // namespace
+
+void sa_layout_count_build() { g_layout_builds.fetch_add(1, std::memory_order_relaxed); }
 
 void sa_finish_scales(double bound, double max_delta, double min_delta, SaHostLayout *out) {
   SaHostLayout &L = *out;
@@ -82,35 +97,13 @@ void sa_finish_scales(double bound, double max_delta, double min_delta, SaHostLa
   }
 }
 
-int build_sa_layout(uint64_t num_spins, const int64_t *indptr, const int32_t *indices,
-                    const double *data, const double *field, SaHostLayout *out) {
-  const uint64_t n = num_spins;
-  g_layout_builds.fetch_add(1, std::memory_order_relaxed);
-  // ASP_PLAN_TIMING=1: stage times of this function on stderr (development aid)
-  const bool timing = std::getenv("ASP_PLAN_TIMING") != nullptr;
-  auto clock_now = [] { return std::chrono::steady_clock::now(); };
-  auto stage_start = clock_now();
-  auto stage = [&](const char *name) {
-    if (!timing) return;
-    const auto now = clock_now();
-    std::fprintf(stderr, "  plan stage %-12s %8.3f ms\n", name,
-                 std::chrono::duration<double, std::milli>(now - stage_start).count());
-    stage_start = now;
-  };
-  if (n >= (1ull << 31)) {
-    return set_error(ASP_ERR_TOO_LARGE, "%llu spins exceed the 2^31 limit", (unsigned long long)n);
-  }
-  if (n > 0 && (!indptr || !field)) return set_error(ASP_ERR_INVALID, "null indptr/field");
+// The FRONT of build_sa_layout (n > 0): validation, the symmetry decision, A = offdiag(J + J^T) in
+// CSR over original indices and the diagonal sum.  asp_sa_plan_create_segments (csrc/sa_plan_segments.hip)
+// does this part on the device for the segments whose stored entries all have stored mirrors.
+static int sa_layout_front(uint64_t n, const int64_t *indptr, const int32_t *indices, const double *data,
+                           const double *field, unsigned parts, SaHostLayout *out) {
+  StageTimer stage;
   SaHostLayout &L = *out;
-  L = SaHostLayout();
-  L.num_spins = n;
-  if (n == 0) {
-    L.a_ptr.assign(1, 0);
-    L.color_block_start.assign(1, 0);
-    L.ell_off.assign(1, 0);
-    L.beta0_auto = L.beta1_auto = 1.0;
-    return ASP_OK;
-  }
   if (indptr[0] != 0) return set_error(ASP_ERR_INVALID, "indptr[0] must be 0");
   const int64_t nnz = indptr[n];
   if (nnz > 0 && (!indices || !data)) return set_error(ASP_ERR_INVALID, "null indices/data");
@@ -176,7 +169,6 @@ int build_sa_layout(uint64_t num_spins, const int64_t *indptr, const int32_t *in
     // test hook: pretend the hashes collided, so that the exact confirmation below decides alone
     if (std::getenv("ASP_PLAN_HASHES_SAY_SYMMETRIC")) symmetric = true;
   }
-  const unsigned parts = host_threads(n);
   if (symmetric) {
     // The hashes are the fast NEGATIVE test; a yes is confirmed exactly before the short cut is
     // taken (a false yes would silently build A = 2 J from the upper rows): every entry above the
@@ -326,9 +318,14 @@ int build_sa_layout(uint64_t num_spins, const int64_t *indptr, const int32_t *in
     if (has_diagonal[i]) diag = diag + diagonal[i];
   }
   L.diag_sum = diag;
-  std::vector<Entry>().swap(t_entries);
-
   stage("merge A");
+  return ASP_OK;
+}
+
+int sa_layout_back(const double *field, unsigned parts, SaHostLayout *out) {
+  StageTimer stage;
+  SaHostLayout &L = *out;
+  const uint64_t n = L.num_spins;
   // ---- DSATUR colouring (Brelaz 1979) --------------------------------
   // Repeatedly colour the uncoloured spin with the most DISTINCT colours among its
   // neighbours (ties: larger degree, then smaller index) with the smallest colour none of
@@ -521,6 +518,12 @@ int build_sa_layout(uint64_t num_spins, const int64_t *indptr, const int32_t *in
   });
 
   stage("ELL fill");
+  return ASP_OK;
+}
+
+static int sa_layout_scales(const double *field, SaHostLayout *out) {
+  SaHostLayout &L = *out;
+  const uint64_t n = L.num_spins;
   // ---- energy scale and automatic beta range ----------------------------------------
   double bound = 0.0;      // B = 1/2 sum|A| + sum|h|  (E - D ranges within +-B)
   double max_delta = 0.0;  // max_i 2 (sum_j |A_ij| + |h_i|)
@@ -539,6 +542,54 @@ int build_sa_layout(uint64_t num_spins, const int64_t *indptr, const int32_t *in
   }
   if (!std::isfinite(bound)) return set_error(ASP_ERR_INVALID, "couplings overflow double range");
   sa_finish_scales(bound, max_delta, min_delta, &L);
+  return ASP_OK;
+}
+
+int sa_layout_scales_from_rows(const double *field, const double *row_sum, const double *row_min,
+                               SaHostLayout *out) {
+  SaHostLayout &L = *out;
+  const uint64_t n = L.num_spins;
+  double bound = 0.0, max_delta = 0.0;
+  double min_delta = std::numeric_limits<double>::infinity();
+  for (uint64_t i = 0; i < n; ++i) {  // the loop above, with the rows' sums and minima given
+    const double row = row_sum[i];
+    min_delta = std::min(min_delta, row_min[i]);
+    const double h = std::fabs(field[i]);
+    if (h > 0.0) min_delta = std::min(min_delta, 2.0 * h);
+    bound += 0.5 * row + h;
+    max_delta = std::max(max_delta, 2.0 * (row + h));
+  }
+  if (!std::isfinite(bound)) return set_error(ASP_ERR_INVALID, "couplings overflow double range");
+  sa_finish_scales(bound, max_delta, min_delta, &L);
+  return ASP_OK;
+}
+
+unsigned sa_layout_host_threads(uint64_t num_spins) { return host_threads(num_spins); }
+
+// Front, then back, then the scales.
+int build_sa_layout(uint64_t num_spins, const int64_t *indptr, const int32_t *indices,
+                    const double *data, const double *field, SaHostLayout *out) {
+  const uint64_t n = num_spins;
+  sa_layout_count_build();
+  if (n >= (1ull << 31)) {
+    return set_error(ASP_ERR_TOO_LARGE, "%llu spins exceed the 2^31 limit", (unsigned long long)n);
+  }
+  if (n > 0 && (!indptr || !field)) return set_error(ASP_ERR_INVALID, "null indptr/field");
+  SaHostLayout &L = *out;
+  L = SaHostLayout();
+  L.num_spins = n;
+  if (n == 0) {
+    L.a_ptr.assign(1, 0);
+    L.color_block_start.assign(1, 0);
+    L.ell_off.assign(1, 0);
+    L.beta0_auto = L.beta1_auto = 1.0;
+    return ASP_OK;
+  }
+  const unsigned parts = host_threads(n);
+  ASP_TRY(sa_layout_front(n, indptr, indices, data, field, parts, &L));
+  ASP_TRY(sa_layout_back(field, parts, &L));
+  StageTimer stage;
+  ASP_TRY(sa_layout_scales(field, &L));
   stage("scales");
   return ASP_OK;
 }

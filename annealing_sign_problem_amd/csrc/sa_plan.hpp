@@ -51,6 +51,20 @@ struct SaHostLayout {
 int build_sa_layout(uint64_t num_spins, const int64_t *indptr, const int32_t *indices,
                     const double *data, const double *field, SaHostLayout *out);
 
+// build_sa_layout is a front (validation, A, the diagonal sum), a back and the scales.  The two below are
+// what asp_sa_plan_create_segments (csrc/sa_plan_segments.hip) runs on the host for a segment whose
+// front ran on the device: num_spins > 0, a_ptr / a_col / a_val and diag_sum of *out are filled.
+// sa_layout_back: DSATUR, permutation, blocks and the host copy of the ELL, the ELL fill on `parts`
+// host threads (the result does not depend on it).  sa_layout_scales_from_rows: build_sa_layout's scale
+// loop with sum_k |A_ik| (added in a_ptr order) and the smallest non-zero 2 |A_ik| (+inf: none) of every
+// row given.  sa_layout_count_build adds one to asp_sa_layout_build_count; sa_layout_host_threads is the
+// `parts` build_sa_layout itself uses.
+int sa_layout_back(const double *field, unsigned parts, SaHostLayout *out);
+int sa_layout_scales_from_rows(const double *field, const double *row_sum, const double *row_min,
+                               SaHostLayout *out);
+void sa_layout_count_build();
+unsigned sa_layout_host_threads(uint64_t num_spins);
+
 // The last step of build_sa_layout, shared with asp_sa_plan_reweight (csrc/sa_reweight.hip): the
 // energy scale and the automatic betas from B = 1/2 sum|A| + sum|h|, max_i 2 (sum_j |A_ij| + |h_i|)
 // and the smallest non-zero 2|A_ij| / 2|h_i| (+inf: none), summed in build_sa_layout's order.

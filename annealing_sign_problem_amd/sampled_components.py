@@ -220,7 +220,7 @@ def process_cluster(cluster, hamiltonian, ground_state, noisy_ground_state, nois
 def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, noisy_ground_state,
                    noisy_log_coeff_fn, order: int, global_cutoff: float, jobs: int = 1,
                    greedy_batch: bool = False, external_field: bool = False, build_batch: bool = False,
-                   level_batch: bool = False, score_batch: bool = False):
+                   level_batch: bool = False, score_batch: bool = False, plan_batch: bool = False):
     """First half of :func:`process_clusters_batched`: the models of every order of every cluster,
     each with its greedy result — a list of ``(cluster index, model, exact_signs, weights, result
     so far)`` in cluster order.  The models of a cluster do not depend on its solutions (the
@@ -235,7 +235,10 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
     (with ``build_batch``): the extension and the sparsification of a level are ONE segmented device call
     each as well (``common.extend_and_sparsify_models``); the same models again.
     ``score_batch`` (with ``greedy_batch``): the greedy solutions of the round are scored by one device
-    call (:func:`score_solutions`); the accuracies are the same, the overlaps agree to rounding."""
+    call (:func:`score_solutions`); the accuracies are the same, the overlaps agree to rounding.
+    ``plan_batch`` (with ``greedy_batch``): the sweep plans of ALL staged models are made by one segmented
+    device call (``sa.plan_hamiltonians``) before the batched greedy solve instead of one
+    ``asp_sa_plan_create`` per model inside it; the plans, and so the results, are the same."""
     basis = hamiltonian.basis
     field = {"external_field": True} if external_field else {}
 
@@ -293,7 +296,8 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
     def solved(staged):
         if greedy_batch and staged:
             solutions = common.solve_ising_models([m for _, m, _, _, _ in staged],
-                                                  [clusters[c] for c, _, _, _, _ in staged], mode="greedy")
+                                                  [clusters[c] for c, _, _, _, _ in staged], mode="greedy",
+                                                  **({"plan_batch": True} if plan_batch else {}))
             for (_, _, _, _, r), scored in zip(staged, score_solutions(staged, solutions, score_batch)):
                 r.greedy_accuracy, r.greedy_overlap = scored
         return staged
@@ -328,6 +332,12 @@ def score_batch_of(args) -> dict:
     """--score-batch as the ``score_batch`` keyword of :func:`stage_clusters`, :func:`anneal_staged` and
     :func:`process_clusters_batched`; empty without it, so that every call is the one it was."""
     return {"score_batch": True} if getattr(args, "score_batch", False) else {}
+
+
+def plan_batch_of(args) -> dict:
+    """--plan-batch as the ``plan_batch`` keyword of :func:`stage_clusters` and
+    :func:`process_clusters_batched`; empty without it, so that every call is the one it was."""
+    return {"plan_batch": True} if getattr(args, "plan_batch", False) else {}
 
 
 def score_solutions(staged, solutions, score_batch: bool = False) -> list:
@@ -392,19 +402,22 @@ def process_clusters_batched(clusters: Sequence[np.ndarray], hamiltonian, ground
                              external_field: bool = False,
                              build_batch: bool = False,
                              level_batch: bool = False,
-                             score_batch: bool = False) -> List[List[OptimizationResult]]:
+                             score_batch: bool = False,
+                             plan_batch: bool = False) -> List[List[OptimizationResult]]:
     """``[process_cluster(c, ...) for c in clusters]`` with the annealing of ALL models — every
     cluster at every order — in one batched device call (:func:`stage_clusters`, then
     :func:`anneal_staged`); the results are identical to the per-cluster loop.  ``early_stop``: the
     extra keywords of :func:`common.solve_ising_models` (early stopping or the annealing method), as in
     :func:`anneal_staged`.  ``external_field``: as in :func:`process_cluster`.  ``build_batch``: as in
-    :func:`stage_clusters`; ``level_batch`` likewise.  ``score_batch``: as in :func:`score_solutions`."""
+    :func:`stage_clusters`; ``level_batch`` and ``plan_batch`` likewise.  ``score_batch``: as in
+    :func:`score_solutions`."""
     staged = stage_clusters(clusters, hamiltonian, ground_state, noisy_ground_state, noisy_log_coeff_fn,
                             order, global_cutoff, jobs, **({"greedy_batch": True} if greedy_batch else {}),
                             **({"external_field": True} if external_field else {}),
                             **({"build_batch": True} if build_batch else {}),
                             **({"level_batch": True} if level_batch else {}),
-                            **({"score_batch": True} if score_batch else {}))
+                            **({"score_batch": True} if score_batch else {}),
+                            **({"plan_batch": True} if plan_batch else {}))
     return anneal_staged(staged, clusters, annealing, sweep_order, **({"early_stop": early_stop} if early_stop else {}),
                          **({"score_batch": True} if score_batch else {}))
 
@@ -478,6 +491,11 @@ def parse_command_line(argv=None):
                              "(compute_accuracies_and_overlaps, asp_sign_scores_batch) instead of one host call "
                              "per solution; needs --batch > 1; the accuracies are the same, the overlaps agree to "
                              "rounding")
+    parser.add_argument("--plan-batch", default=False, action="store_true",
+                        help="make the sweep plans of a round of --batch clusters with ONE segmented device call "
+                             "(plan_hamiltonians, asp_sa_plan_create_segments) before the batched greedy solve "
+                             "instead of one asp_sa_plan_create per model; needs --batch > 1 and --greedy-batch; "
+                             "the output is the same")
     parser.add_argument("--greedy-tree", choices=("host", "device"), default=None,
                         help="where the greedy solver builds its strongest-coupling tree (default: "
                              "$ASP_GREEDY_TREE or host); the output is the same")
@@ -507,6 +525,9 @@ def parse_command_line(argv=None):
         parser.error("--build-batch needs --batch > 1 and --annealing or --greedy-batch (it builds a round at once)")
     if args.score_batch and args.batch <= 1:
         parser.error("--score-batch needs --batch > 1 (it scores a round at once)")
+    if args.plan_batch and (args.batch <= 1 or not args.greedy_batch):
+        parser.error("--plan-batch needs --batch > 1 and --greedy-batch (it plans a round's models at once; "
+                     "without --greedy-batch every model's own greedy solve makes its plan)")
     if args.level_batch and not args.build_batch:
         parser.error("--level-batch needs --build-batch (it batches the rest of a level of the round)")
     return args
@@ -683,7 +704,7 @@ def _worker_chunk(indices):
                                          jobs=args.jobs, sweep_order=args.sweep_order,
                                          **({"greedy_batch": True} if args.greedy_batch else {}),
                                          **early_stop_of(args), **external_field_of(args), **build_batch_of(args),
-                                         **level_batch_of(args), **score_batch_of(args))
+                                         **level_batch_of(args), **score_batch_of(args), **plan_batch_of(args))
         return report([",".join(r.to_csv_str() for r in columns) for columns in chunk])
 
     def work(cluster):
@@ -894,7 +915,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                                              args.order, args.global_cutoff, args.annealing,
                                              jobs=args.jobs, sweep_order=args.sweep_order, **greedy_batch,
                                              **early_stop_of(args), **external_field_of(args), **build_batch_of(args),
-                                             **level_batch_of(args), **score_batch_of(args))
+                                             **level_batch_of(args), **score_batch_of(args), **plan_batch_of(args))
             lines += [",".join(r.to_csv_str() for r in columns) for columns in chunk]
         return lines
 
@@ -926,7 +947,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                 return stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
                                       noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
                                       **greedy_batch, **external_field_of(args), **build_batch_of(args),
-                                      **level_batch_of(args), **score_batch_of(args))
+                                      **level_batch_of(args), **score_batch_of(args), **plan_batch_of(args))
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(stage, my_share(0)) if rounds else None
@@ -982,7 +1003,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
                 return some, stage_clusters(some, hamiltonian, ground_state, noisy_ground_state,
                                             noisy_log_coeff_fn, args.order, args.global_cutoff, args.jobs,
                                             **greedy_batch, **external_field_of(args), **build_batch_of(args),
-                                            **level_batch_of(args), **score_batch_of(args))
+                                            **level_batch_of(args), **score_batch_of(args), **plan_batch_of(args))
 
             with ThreadPoolExecutor(max_workers=1) as builder:
                 upcoming = builder.submit(next_round)

@@ -517,6 +517,54 @@ float asp_sa_plan_reweight_last_ms(asp_sa_plan const *p);
  * to solve several reweighted copies of one model at once: they refuse one plan twice. */
 int asp_sa_plan_clone(asp_sa_plan const *p, asp_sa_plan **out);
 
+/* The plans of a whole round in one call, specification ASP-PLAN-SEG-1.  The input
+ * conventions are the OUTPUT conventions of asp_operator_ising_segments and
+ * asp_sparsify_component_segments, so the three calls chain: segment g holds the spins [offsets[g],
+ * offsets[g + 1]) of T = offsets[num_segments]; indptr is ONE global i64[T + 1] starting at 0; indices
+ * are SEGMENT-LOCAL; rows sorted and duplicate-free, stored zeros and a stored diagonal legal; field is
+ * f64[T].  Host pointers.  The law: after a successful call out_plans[g] is indistinguishable from
+ * asp_sa_plan_create(n_g, rebased indptr, indices, data, field of segment g) — every field of
+ * asp_sa_plan_info, every device array of the plan byte for byte (asp_sa_plan_read_array), the stored
+ * pattern (asp_sa_plan_reweight and asp_sa_plan_clone work), the environment read at creation
+ * (ASP_SA_TEAM), energies, anneals in both orders, chains, the greedy solver with every tree.  An empty
+ * segment yields what asp_sa_plan_create(0, ...) yields.  Every plan is an object of its own, destroyed
+ * with asp_sa_plan_destroy; each segment adds one to asp_sa_layout_build_count.
+ * On failure every out_plans[g] is NULL and nothing leaks.  Before any device work: ASP_ERR_INVALID
+ * for a null out_plans or offsets, offsets[0] != 0 or decreasing offsets, null indptr / field with
+ * T > 0, indptr[0] != 0 or a non-monotone indptr, null indices / data with stored entries;
+ * ASP_ERR_TOO_LARGE for T or the number of stored entries >= 2^32 - 1.  A column out of range, a row
+ * that is not canonical, a non-finite coupling or field and an overflowing bound fail with
+ * asp_sa_plan_create's message behind "segment <g>: ", g the first such segment.  num_segments == 0
+ * needs no device.  The device forms A = offdiag(J + J^T) and the rows' statistics for all segments
+ * at once (a segment with a stored entry whose mirror is not stored takes the host's route instead);
+ * the host colours and orders every segment on at most 16 threads; one kernel then writes every
+ * plan's arrays, the padded ELL from the A that is still on the device.  7 launches, 2 fills, 12
+ * copies and 2 host synchronisations, whatever num_segments. */
+int asp_sa_plan_create_segments(uint64_t num_segments, uint64_t const *offsets, int64_t const *indptr,
+                                int32_t const *indices, double const *data, double const *field,
+                                asp_sa_plan **out_plans);
+/* Device time (ms, HIP events) of this thread's last asp_sa_plan_create_segments call: its kernels,
+ * copies excluded. */
+float asp_sa_plan_segments_last_ms(void);
+
+/* The device arrays of a plan, for asp_sa_plan_read_array. */
+enum {
+  ASP_SA_ARRAY_COLOR_BLOCK_START = 0, /* u32[num_colors + 1]                        */
+  ASP_SA_ARRAY_BLOCK_WIDTH = 1,       /* u32[num_blocks]                            */
+  ASP_SA_ARRAY_ELL_OFF = 2,           /* u64[num_blocks + 1], in 64-entry slabs     */
+  ASP_SA_ARRAY_ELL_COL = 3,           /* u32[ell_entries + tail], quad-interleaved  */
+  ASP_SA_ARRAY_ELL_COL4 = 4,          /* the same as LDS byte addresses, if held    */
+  ASP_SA_ARRAY_ELL_VAL = 5,           /* f64[ell_entries + tail]                    */
+  ASP_SA_ARRAY_SPIN_OF_POS = 6,       /* u32[num_blocks * 64]                       */
+  ASP_SA_ARRAY_POS_OF_SPIN = 7,       /* u32[num_spins]                             */
+  ASP_SA_ARRAY_FIELD_POS = 8          /* f64[num_blocks * 64]                       */
+};
+/* Copies one device array of the plan to dst (host).  *bytes is always set, to the size of the array:
+ * 0 for an array the plan does not hold (ell_col4 where the wide layout does not fit; every ELL array
+ * of a plan without spins).  ASP_ERR_INVALID for a null plan or byte count, an unknown id and a
+ * capacity below *bytes (nothing is copied then). */
+int asp_sa_plan_read_array(asp_sa_plan const *p, int which, void *dst, uint64_t capacity_bytes, uint64_t *bytes);
+
 /* ---- coupling stencil: the couplings of a fixed set of states from new amplitudes alone ----------
  * Specification ASP-STENCIL-1.  Inputs: an operator, K sorted unique keys and the
  * canonical CSR pattern (indptr, indices) of the J that asp_operator_ising_csr(op, K, keys, psi0)
