@@ -156,6 +156,21 @@ class SaChainsExchangeItem(ctypes.Structure):
     ]
 
 
+class SaChainsClusterItem(ctypes.Structure):
+    """Mirror of ``asp_sa_chains_cluster_item`` (include/asp.h)."""
+
+    _fields_ = [
+        ("chains", c_void_p),
+        ("pairs", c_void_p),
+        ("num_pairs", c_u32),
+        ("draw", c_u32),
+        ("flags", c_u32),
+        ("out_differing", c_void_p),
+        ("out_size", c_void_p),
+        ("out_delta", c_void_p),
+    ]
+
+
 class BondsSummary(ctypes.Structure):
     """Mirror of ``asp_bonds_summary`` (include/asp.h)."""
 
@@ -344,6 +359,8 @@ SIGNATURES = {
     "asp_sa_chains_cluster_move": (c_int, [c_void_p, c_void_p, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "asp_sa_chains_cluster_move_last_ms": (c_float, []),
     "asp_sa_chains_set_cluster_planes": (c_int, [c_void_p, c_int]),
+    "asp_sa_chains_cluster_move_batch": (c_int, [ctypes.POINTER(SaChainsClusterItem), c_u32]),
+    "asp_sa_chains_cluster_move_batch_last_ms": (c_float, []),
     "asp_sa_anneal_batch": (c_int, [ctypes.POINTER(SaBatchItem), c_u32]),
     "asp_sa_batch_last_ms": (c_float, []),
     "asp_sa_greedy": (c_int, [c_void_p, c_u32, c_void_p, c_void_p, ctypes.POINTER(c_u32)]),

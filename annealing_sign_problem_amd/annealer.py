@@ -48,8 +48,10 @@ __all__ = [
     "parallel_tempering",
     "parallel_tempering_batch",
     "parallel_tempering_cluster",
+    "parallel_tempering_cluster_batch",
     "advance_ladder_chains",
     "exchange_chains",
+    "cluster_move_chains",
     "greedy_solve",
     "greedy_solve_batch",
     "signs_to_bits",
@@ -841,6 +843,22 @@ class Chains:
         number of differing sites, the size of the flipped cluster and the change of chain ``a``'s tracked
         energy (chain ``b``'s is the opposite).  ``draw`` picks the random words (a Philox counter word),
         for more than one move at one sweep count; the same move again undoes it."""
+        pairs = self._cluster_pairs(pairs)
+        draw = int(draw)
+        if not 0 <= draw < 2**32:
+            raise ValueError("'draw' must fit 32 bits")
+        handle = self._live()
+        count = pairs.shape[0]
+        differing = np.zeros(count, dtype=np.uint32)
+        sizes = np.zeros(count, dtype=np.uint32)
+        deltas = np.zeros(count, dtype=np.int64)
+        _lib.check(_lib.load().asp_sa_chains_cluster_move(handle, _lib.ptr(pairs), ctypes.c_uint32(count),
+                                                          ctypes.c_uint32(draw), _lib.ptr(differing),
+                                                          _lib.ptr(sizes), _lib.ptr(deltas)))
+        return differing, sizes, deltas
+
+    def _cluster_pairs(self, pairs) -> np.ndarray:
+        """``pairs`` of :meth:`cluster_move` checked, as a contiguous ``uint32[P, 2]``."""
         pairs = np.asarray(pairs)
         if pairs.size == 0:
             pairs = np.zeros((0, 2), dtype=np.uint32)
@@ -850,19 +868,7 @@ class Chains:
             raise ValueError("'pairs' must hold chain indices below {}".format(self.repetitions))
         if np.unique(pairs).size != pairs.size:
             raise ValueError("'pairs' names a chain more than once")
-        draw = int(draw)
-        if not 0 <= draw < 2**32:
-            raise ValueError("'draw' must fit 32 bits")
-        handle = self._live()
-        pairs = np.ascontiguousarray(pairs, dtype=np.uint32)
-        count = pairs.shape[0]
-        differing = np.zeros(count, dtype=np.uint32)
-        sizes = np.zeros(count, dtype=np.uint32)
-        deltas = np.zeros(count, dtype=np.int64)
-        _lib.check(_lib.load().asp_sa_chains_cluster_move(handle, _lib.ptr(pairs), ctypes.c_uint32(count),
-                                                          ctypes.c_uint32(draw), _lib.ptr(differing),
-                                                          _lib.ptr(sizes), _lib.ptr(deltas)))
-        return differing, sizes, deltas
+        return np.ascontiguousarray(pairs, dtype=np.uint32)
 
     def result(self, only_best: bool = False):
         """The best configuration so far of every chain and its energy, ``(xs[R, words], es[R])`` —
@@ -1444,6 +1450,114 @@ def exchange_chains(chains, chain_betas, parity, draws=0):
         out.append((source, energies, accepted))
     _lib.check(_lib.load().asp_sa_chains_exchange_batch(items, ctypes.c_uint32(n)))
     return [(source, energies, int(accepted.value)) for source, energies, accepted in out]
+
+
+CLUSTER_NO_PACKED = 1  # ASP_CLUSTER_NO_PACKED (include/asp.h): the workgroup-per-pair form for the handle
+
+
+def cluster_move_chains(chains, pairs, draws=0, flags=0):
+    """``chains[i].cluster_move(pairs[i], draws[i])`` for every ``i`` in ONE device call
+    (``asp_sa_chains_cluster_move_batch``): the same bits, but the pairs of all handles
+    share at most three launches — the pairs of small models (up to 2048 spins) a wavefront each — and every
+    output comes back in one copy.  ``pairs``: one ``(P_i, 2)`` array-like per handle; ``draws``: one value
+    for all or one per handle; ``flags`` (tests and timing; results do not depend on it): likewise,
+    ``CLUSTER_NO_PACKED`` forces the workgroup form.  Returns ``[(differing, sizes, deltas), ...]``."""
+    chains = list(chains)
+    n = len(chains)
+    for c in chains:
+        if not isinstance(c, Chains):
+            raise TypeError("'chains' must hold Chains objects")
+    pairs = list(pairs)
+    if len(pairs) != n:
+        raise ValueError("cluster_move_chains: %d handles, %d arrays of pairs" % (n, len(pairs)))
+    draws = [int(x) for x in _per_handle(draws, n, "cluster_move_chains: 'draws'")]
+    flags = [int(x) for x in _per_handle(flags, n, "cluster_move_chains: 'flags'")]
+    if any(not 0 <= d < 2**32 for d in draws):
+        raise ValueError("'draws' must fit 32 bits")
+    if any(f not in (0, CLUSTER_NO_PACKED) for f in flags):
+        raise ValueError("'flags' must be 0 or CLUSTER_NO_PACKED")
+    checked, known = [], {}  # (a driver hands every handle the same array: checked once per chain count)
+    for c, p in zip(chains, pairs):
+        key = (id(p), c.repetitions)
+        if key not in known:
+            known[key] = c._cluster_pairs(p)
+        checked.append(known[key])
+    items = (_lib.SaChainsClusterItem * max(n, 1))()
+    out = []  # (also keeps the output buffers alive over the call)
+    for i, c in enumerate(chains):
+        count = checked[i].shape[0]
+        differing = np.zeros(count, dtype=np.uint32)
+        sizes = np.zeros(count, dtype=np.uint32)
+        deltas = np.zeros(count, dtype=np.int64)
+        items[i].chains = c._live()
+        items[i].pairs = checked[i].ctypes.data
+        items[i].num_pairs = count
+        items[i].draw = draws[i]
+        items[i].flags = flags[i]
+        items[i].out_differing = differing.ctypes.data
+        items[i].out_size = sizes.ctypes.data
+        items[i].out_delta = deltas.ctypes.data
+        out.append((differing, sizes, deltas))
+    _lib.check(_lib.load().asp_sa_chains_cluster_move_batch(items, ctypes.c_uint32(n)))
+    return out
+
+
+def parallel_tempering_cluster_batch(hamiltonians, seed=None, number_rounds: int = 512, sweeps_per_round: int = 10,
+                                     beta0: Optional[float] = None, beta1: Optional[float] = None,
+                                     repetitions: int = 64, only_best: bool = True,
+                                     sweep_order: Optional[str] = None, exchange: bool = True, cluster_rungs=None):
+    """``[parallel_tempering_cluster(h, seed=seed, ...) for h in hamiltonians]`` with every round of all
+    problems in one ``advance_ladder_chains`` call, one ``cluster_move_chains`` call (on every round, the
+    last included) and — except after the last round — one ``exchange_chains`` call: identical results.
+    ``seed`` as in ``anneal_batch``.  Chains stay on this rank."""
+    order = resolve_sweep_order(sweep_order)  # (first: a bad order fails without a GPU)
+    number_rounds, sweeps_per_round = int(number_rounds), int(sweeps_per_round)
+    if number_rounds < 1 or sweeps_per_round < 1:
+        raise ValueError("'number_rounds' and 'sweeps_per_round' must be positive")
+    hamiltonians = list(hamiltonians)
+    n = len(hamiltonians)
+    for h in hamiltonians:
+        if not isinstance(h, Hamiltonian):
+            raise TypeError("'hamiltonians' must hold Hamiltonian objects")
+    if len({id(h) for h in hamiltonians}) != n:
+        raise ValueError("parallel_tempering_cluster_batch: every problem needs its own Hamiltonian object")
+    repetitions = int(repetitions)
+    if repetitions < 2 or repetitions % 2:
+        raise ValueError("'repetitions' must be even and positive: two chains per rung")
+    rungs = repetitions // 2
+    cluster_rungs = rungs if cluster_rungs is None else int(cluster_rungs)
+    if not 0 <= cluster_rungs <= rungs:
+        raise ValueError("'cluster_rungs' must be between 0 and {}".format(rungs))
+    if seed is None or np.ndim(seed) == 0:
+        seeds = [_resolve_seed(seed) for _ in range(n)] if seed is None else [_resolve_seed(seed)] * n
+    else:
+        seeds = [_resolve_seed(x) for x in seed]
+    hairpins = []
+    for h in hamiltonians:
+        b0, b1 = beta0, beta1
+        if b0 is None or b1 is None:
+            info = h.info()
+            b0 = info.beta0_auto if b0 is None else b0
+            b1 = info.beta1_auto if b1 is None else b1
+        ladder = make_schedule(float(b0), float(b1), rungs)
+        hairpins.append(np.concatenate([ladder, ladder[::-1]]))
+    # (the ladder runs hot to cold: the coldest rungs are the last ones)
+    pairs = np.array([(k, repetitions - 1 - k) for k in range(rungs - cluster_rungs, rungs)],
+                     dtype=np.uint32).reshape(-1, 2)
+    handles = []
+    try:
+        for h, s in zip(hamiltonians, seeds):
+            handles.append(Chains(h, seed=s, repetitions=repetitions))
+        for j in range(number_rounds):
+            advance_ladder_chains(handles, hairpins, sweeps_per_round, sweep_order=order)
+            cluster_move_chains(handles, [pairs] * n, 0)
+            if exchange and j + 1 < number_rounds:
+                exchange_chains(handles, hairpins, j & 1, 0)
+        results = [c.result(only_best=only_best) for c in handles]
+    finally:
+        for c in handles:
+            c.close()
+    return results
 
 
 def parallel_tempering_batch(hamiltonians, seed=None, number_rounds: int = 512, sweeps_per_round: int = 10,

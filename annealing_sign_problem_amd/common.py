@@ -647,16 +647,18 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
     ``patience`` (not in the reference; default off): every model's ladder runs in segments of
     ``check_every`` sweeps (default 512) and stops once none of its chains improved for ``patience``
     consecutive segments (``sa.anneal_batch_until``) — fewer sweeps, results that may differ.
-    ``method`` (not in the reference; default ``"anneal"``): ``"population"`` or ``"tempering"`` solve
-    every model with ``sa.population_anneal_batch`` / ``sa.parallel_tempering_batch`` instead, in
-    ``number_sweeps // 10`` steps / rounds of ten sweeps — the sweep count of the plain call.
+    ``method`` (not in the reference; default ``"anneal"``): ``"population"``, ``"tempering"`` or
+    ``"tempering-cluster"`` solve every model with ``sa.population_anneal_batch`` /
+    ``sa.parallel_tempering_batch`` / ``sa.parallel_tempering_cluster_batch`` (isoenergetic cluster moves
+    in every round; an even ``repetitions``) instead, in ``number_sweeps // 10`` steps / rounds of ten
+    sweeps — the sweep count of the plain call.
     ``tree`` (``mode="greedy"``): as in :func:`solve_ising_model`.
     ``plan_batch`` (not in the reference; default off): the sweep plans of all models are made by one
     segmented device call (``sa.plan_hamiltonians``) before the solve instead of one by one inside it;
     the results are the same."""
-    if method not in ("anneal", "population", "tempering"):
-        raise ValueError(
-            "invalid method specified: '{}'; expected 'anneal', 'population' or 'tempering'".format(method))
+    if method not in ("anneal", "population", "tempering", "tempering-cluster"):
+        raise ValueError("invalid method specified: '{}'; expected 'anneal', 'population', 'tempering' or "
+                         "'tempering-cluster'".format(method))
     if method != "anneal":
         if mode != "sa":
             raise ValueError("'method' selects an annealing method: it needs mode='sa'")
@@ -683,9 +685,13 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
         if method == "population":
             best = sa.population_anneal_batch(hamiltonians, seed=seed, number_steps=steps, sweeps_per_step=10,
                                               repetitions=repetitions, only_best=True, sweep_order=sweep_order)
-        else:
+        elif method == "tempering":
             best = sa.parallel_tempering_batch(hamiltonians, seed=seed, number_rounds=steps, sweeps_per_round=10,
                                                repetitions=repetitions, only_best=True, sweep_order=sweep_order)
+        else:
+            best = sa.parallel_tempering_cluster_batch(hamiltonians, seed=seed, number_rounds=steps,
+                                                       sweeps_per_round=10, repetitions=repetitions, only_best=True,
+                                                       sweep_order=sweep_order)
         return [_project_on_frozen(m, x, f) for m, (x, _), f in zip(models, best, frozen)]
     if patience is not None:
         best = sa.anneal_batch_until([m.ising_hamiltonian for m in models], seed=seed,

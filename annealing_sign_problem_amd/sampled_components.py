@@ -370,7 +370,7 @@ def anneal_staged(staged, clusters: Sequence[np.ndarray], annealing: bool,
     ``early_stop``: despite its name (it began as the early stopping alone) the dict of EVERY extra
     keyword of :func:`common.solve_ising_models` that the command line selects, passed on as it is —
     ``{"patience": N, "check_every": S}`` (--anneal-patience) or ``{"method": "population" |
-    "tempering"}`` (--anneal-method, which selects another algorithm); see :func:`early_stop_of`.
+    "tempering" | "tempering-cluster"}`` (--anneal-method, which selects another algorithm); see :func:`early_stop_of`.
     ``score_batch``: the solutions are scored by one device call (:func:`score_solutions`)."""
     if annealing and staged:
         started = time.perf_counter()
@@ -455,10 +455,13 @@ def parse_command_line(argv=None):
                              "by default: early stopping changes the results")
     parser.add_argument("--anneal-check-every", type=int, default=None, metavar="S",
                         help="sweeps per segment of --anneal-patience (default 512)")
-    parser.add_argument("--anneal-method", type=str, default="anneal", choices=["anneal", "population", "tempering"],
+    parser.add_argument("--anneal-method", type=str, default="anneal",
+                        choices=["anneal", "population", "tempering", "tempering-cluster"],
                         help="how the batched annealing solves a model: 'anneal' (default: the schedule of "
-                             "the reference), 'population' (population annealing, population_anneal_batch) or "
-                             "'tempering' (parallel tempering, parallel_tempering_batch), both in steps of ten "
+                             "the reference), 'population' (population annealing, population_anneal_batch), "
+                             "'tempering' (parallel tempering, parallel_tempering_batch) or 'tempering-cluster' "
+                             "(parallel tempering with isoenergetic cluster moves, "
+                             "parallel_tempering_cluster_batch), all in steps of ten "
                              "sweeps with the same sweep count.  Needs --annealing and --batch > 1, and is not "
                              "combined with --anneal-patience: the other methods change the results")
     parser.add_argument("--sweep-order", type=str, default="shuffled", choices=["colour", "shuffled"],

@@ -1120,6 +1120,36 @@ float asp_sa_chains_cluster_move_last_ms(void);
  * 2 a per-pair slab in HBM.  Results never depend on it. */
 int asp_sa_chains_set_cluster_planes(asp_sa_chains *c, int where);
 
+/* MANY handles' cluster moves in one call ("Batched form"): item i is exactly
+ * asp_sa_chains_cluster_move(chains, pairs, num_pairs, draw, out_*) — steps 1-6 of ASP-ICM-1 unchanged, the
+ * same bits for any composition and order of the batch (every quantity of the law is a set, an integer sum
+ * or a row sum in fixed column order).  One table of rows, one per (item, pair), is uploaded and at most
+ * three kernels run on one stream of the call, ordered after what is pending on the plans' streams: the
+ * pairs of handles of at most 32 words (2048 spins) take a WAVEFRONT each, four to a workgroup, the three
+ * bit planes in 3 x 64 words of LDS; the others a workgroup each as in the single call, with the planes in
+ * LDS or — asp_sa_chains_set_cluster_planes keeps its meaning per handle — in the plan's HBM slab.
+ * n | size, Q and the touched slots' tracked energies of every pair come back in one copy.
+ * flags: ASP_CLUSTER_NO_PACKED forces the workgroup form for the item (tests and timing; no result
+ * depends on it).  Validation as in asp_sa_chains_exchange_batch — every item before any device work and
+ * before any output is written, the item's index in the message: null items with count > 0, unknown
+ * flags, a null handle, null pairs with num_pairs > 0, an entry that is not below repetitions, a slot
+ * named twice within an item, the same handle twice, two handles of one plan.  count = 0 needs no device;
+ * items with num_pairs = 0, handles without chains and plans without spins run nothing (outputs 0).  Any
+ * OTHER error leaves the handles of the batch UNDEFINED. */
+#define ASP_CLUSTER_NO_PACKED 1u
+typedef struct asp_sa_chains_cluster_item {
+  asp_sa_chains *chains;
+  uint32_t const *pairs;     /* HOST u32[2 num_pairs] */
+  uint32_t num_pairs, draw, flags;
+  uint32_t *out_differing;   /* NULL, or HOST [num_pairs] */
+  uint32_t *out_size;        /* NULL, or HOST [num_pairs] */
+  int64_t *out_delta;        /* NULL, or HOST [num_pairs] */
+} asp_sa_chains_cluster_item;
+int asp_sa_chains_cluster_move_batch(asp_sa_chains_cluster_item const *items, uint32_t count);
+/* Device time (ms) of this thread's last asp_sa_chains_cluster_move_batch call: from its first launch to
+ * its last, HIP events on the call's stream; 0 when nothing ran. */
+float asp_sa_chains_cluster_move_batch_last_ms(void);
+
 /* MANY independent problems in one call — the shape of the reference's production job: tens of
  * thousands of sampled clusters, each solved with 64 repetitions x 5120 sweeps
  * (Makefile:9,115-127; experiments/sampled_connected_components.py:764-767; common.py:236-239).
