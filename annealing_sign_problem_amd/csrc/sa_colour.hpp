@@ -107,7 +107,9 @@ constexpr uint32_t kTailRing = 128;  // rows a wavefront stages: under 64 waitin
 // Per replica m: delta[m] = energy change of the running sweep, book[m] = current tracked energy,
 //   book[8 + m] = best, book[16 + m] = accepted flips.  flag: bit m = replica m improved in this sweep;
 //   its second word (a segment in words): bit m = replica m improved in this launch.
-// meta[b] = {first ELL slab, width} of block b.  ctl: the CtlSlot words below.
+// meta[b] = {first ELL slab, EXACT width} of block b: its longest row, which the plan's block_width rounds
+//   up to whole quads (ColourSweep::start derives it): (width + 3) / 4 quads, the last of width % 4 real
+//   terms (0: of four).  ctl: the CtlSlot words below.
 // dirty[b]: bit m = replica m's cached fields of block b are stale.  inert[b], meaningful while the dirty
 //   byte is clear: at the block's last evaluation every proposal was a certain rejection (beta * dE >= 23
 //   -> expneg = 0, or dE >= 0 in descent mode) and beta has not decreased since: the visit can be skipped.

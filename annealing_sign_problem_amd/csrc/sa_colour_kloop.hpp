@@ -141,14 +141,16 @@ __device__ __forceinline__ void load_quad(Quad &q, const BlockStream &s, uint32_
 // The row sums of one quad: the four neighbours' spins are gathered, then neighbour-major FMAs
 // (consecutive FMAs go to different accumulators; each acc[m] still receives its terms in
 // ascending k).  `mult`: kWide's held multipliers (wide_factor_held), untouched by the others.
-template <int M, int LAYOUT>
+// TERMS < 4: the partial form, the quad's first TERMS terms only — gathers and FMAs alike (accumulate_last).
+template <int M, int LAYOUT, int TERMS = 4>
 __device__ __forceinline__ void accumulate(const Quad &q, const uint8_t *spins, double (&acc)[M],
                                            double (&mult)[4]) {
+  static_assert(TERMS >= 1 && TERMS <= 4, "a quad holds four terms");
   const uint32_t cs[4] = {q.c.x, q.c.y, q.c.z, q.c.w};
   const double vs[4] = {q.v01.x, q.v01.y, q.v23.x, q.v23.y};
   uint32_t s[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < TERMS; ++j) {
     if constexpr (LAYOUT == kBytes) {
       // even-bit bytes and bytes at M = 8: the spin bytes start at LDS address 0 (checked in the
       // kernel prologue), so a position IS its LDS address — no base add in front of every
@@ -175,7 +177,7 @@ __device__ __forceinline__ void accumulate(const Quad &q, const uint8_t *spins, 
     }
   }
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < TERMS; ++j) {
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       if constexpr (LAYOUT == kWide) {
@@ -183,6 +185,52 @@ __device__ __forceinline__ void accumulate(const Quad &q, const uint8_t *spins, 
       } else {
         acc[m] = __builtin_fma(vs[j], spin_factor<M, LAYOUT>(s[j], m), acc[m]);
       }
+    }
+  }
+}
+
+// The LAST quad of a block whose longest row ends inside it: `last_terms` = exact width & 3 (1, 2 or 3
+// real terms; 0: all four).  Wave-uniform — a scalar branch, no lane mask — so the terms past the longest
+// row, which are padding in all 64 lanes, cost neither a gather nor an FMA.  The sums keep their bits: a
+// dropped term is fma(+0.0, +-1.0, acc) = acc + (+-0.0) (the plan pads values with +0.0), which is acc for
+// every acc but -0.0, and acc is never -0.0: it starts as +0.0 and a sum rounds to -0.0 only when both of
+// its addends are -0.0 (x + (-x) is +0.0 in round-to-nearest).  The real terms are added in ascending k,
+// as before.
+template <int M, int LAYOUT>
+__device__ __forceinline__ void accumulate_last(const Quad &q, uint32_t last_terms, const uint8_t *spins,
+                                                double (&acc)[M], double (&mult)[4]) {
+  if constexpr (LAYOUT == kWide) {
+    // Words: every term rewrites the held multipliers in place.  As four bodies of their own hipcc copied
+    // the eight registers into each body and out of it again (12 v_mov per visit: what the dropped terms
+    // save); one body with early exits keeps them where they are.  The gathers go first, as in accumulate.
+    const uint32_t cs[4] = {q.c.x, q.c.y, q.c.z, q.c.w};
+    const double vs[4] = {q.v01.x, q.v01.y, q.v23.x, q.v23.y};
+    uint32_t s[4] = {0u, 0u, 0u, 0u};
+    s[0] = *reinterpret_cast<LdsWord *>(static_cast<uintptr_t>(cs[0]));
+    if (last_terms != 1u) {
+      s[1] = *reinterpret_cast<LdsWord *>(static_cast<uintptr_t>(cs[1]));
+      if (last_terms != 2u) {
+        s[2] = *reinterpret_cast<LdsWord *>(static_cast<uintptr_t>(cs[2]));
+        if (last_terms != 3u) s[3] = *reinterpret_cast<LdsWord *>(static_cast<uintptr_t>(cs[3]));
+      }
+    }
+    auto term = [&](int j) {
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[m] = __builtin_fma(vs[j], wide_factor_held(s[j], m, mult[m & 3]), acc[m]);
+    };
+    term(0);
+    if (last_terms == 1u) return;
+    term(1);
+    if (last_terms == 2u) return;
+    term(2);
+    if (last_terms == 3u) return;
+    term(3);
+  } else {
+    switch (last_terms) {
+      case 1: accumulate<M, LAYOUT, 1>(q, spins, acc, mult); break;
+      case 2: accumulate<M, LAYOUT, 2>(q, spins, acc, mult); break;
+      case 3: accumulate<M, LAYOUT, 3>(q, spins, acc, mult); break;
+      default: accumulate<M, LAYOUT, 4>(q, spins, acc, mult); break;
     }
   }
 }

@@ -309,27 +309,69 @@ __device__ __forceinline__ void for_replica_words(uint32_t spin, uint32_t sweep,
 // loads are in flight while the current quad is gathered from LDS and accumulated, in the oracle's
 // order k = 0, 1, 2, ...  Loop control is scalar and the body has no conditional loads (hipcc would
 // otherwise drain the queue with vmcnt(0) at the loop header); sched_barrier keeps each load group
-// ahead of the accumulate it overlaps.  For an even quad count the last load reads one quad past the
-// block — the next block's first slabs or the tail padding the plan appends — and is never consumed.
-template <int M, int LAYOUT>
-__device__ __forceinline__ void block_row_sums(const BlockStream &stream, uint32_t quads, const uint8_t *spins,
+// ahead of the accumulate it overlaps.  `width`: the block's EXACT width, its longest row (meta[b].y;
+// the rounded width where a kernel has no meta): (width + 3) / 4 quads, the last of width & 3 real terms
+// (0: of four).
+//   EXACT (exact_kloop() below says which kernels): the loop runs only while both of its loads lie inside
+//     the block, and the block's last quad goes through accumulate_last, which stops at the longest row's
+//     last term.  No load is issued for a quad the block does not have, nothing for a block of width 0.
+//     The parity of the quad count is settled in FRONT of the loop — an even count loads quads 0 and 1 and
+//     accumulates quad 0 first —, so that the last quad is in qa whatever the count: with the last one or
+//     two quads behind the loop hipcc merged the two accumulate_last and copied a quad (+10 VGPRs, scratch
+//     in words).
+//   otherwise the loop every kernel had: every quad in full, and for an even quad count (and for none)
+//     a last load that reads one quad past the block — the next block's first slabs or the tail padding
+//     the plan appends — and is never consumed.
+// Either way acc[m] receives the row's real terms in ascending k, and the same bits (accumulate_last).
+template <int M, int LAYOUT, bool EXACT>
+__device__ __forceinline__ void block_row_sums(const BlockStream &stream, uint32_t width, const uint8_t *spins,
                                                double (&acc)[M], double (&mult)[4]) {
+  const uint32_t quads = (width + 3u) >> 2;
 #pragma unroll
   for (int m = 0; m < M; ++m) acc[m] = 0.0;
   Quad qa, qb;
-  load_quad(qa, stream, 0);
-  uint32_t i = 0;
-  for (; i + 2 <= quads; i += 2) {
-    load_quad(qb, stream, i + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    accumulate<M, LAYOUT>(qa, spins, acc, mult);
-    __builtin_amdgcn_sched_barrier(0);
-    load_quad(qa, stream, i + 2);
-    __builtin_amdgcn_sched_barrier(0);
-    accumulate<M, LAYOUT>(qb, spins, acc, mult);
-    __builtin_amdgcn_sched_barrier(0);
+  if constexpr (EXACT) {
+    if (quads == 0u) return;
+    uint32_t i = 0;  // qa holds quad i, and quads - i is odd
+    if (quads & 1u) {
+      load_quad(qa, stream, 0);
+    } else {
+      // (the barrier in front keeps hipcc from merging this load of quad 0 with the other branch's: it
+      // then copied quad 1 into qa behind a vmcnt(0))
+      __builtin_amdgcn_sched_barrier(0);
+      load_quad(qb, stream, 0);
+      load_quad(qa, stream, 1);
+      __builtin_amdgcn_sched_barrier(0);
+      accumulate<M, LAYOUT>(qb, spins, acc, mult);
+      __builtin_amdgcn_sched_barrier(0);
+      i = 1;
+    }
+    for (; i + 2 < quads; i += 2) {
+      load_quad(qb, stream, i + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      accumulate<M, LAYOUT>(qa, spins, acc, mult);
+      __builtin_amdgcn_sched_barrier(0);
+      load_quad(qa, stream, i + 2);
+      __builtin_amdgcn_sched_barrier(0);
+      accumulate<M, LAYOUT>(qb, spins, acc, mult);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    accumulate_last<M, LAYOUT>(qa, width & 3u, spins, acc, mult);
+  } else {
+    load_quad(qa, stream, 0);
+    uint32_t i = 0;
+    for (; i + 2 <= quads; i += 2) {
+      load_quad(qb, stream, i + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      accumulate<M, LAYOUT>(qa, spins, acc, mult);
+      __builtin_amdgcn_sched_barrier(0);
+      load_quad(qa, stream, i + 2);
+      __builtin_amdgcn_sched_barrier(0);
+      accumulate<M, LAYOUT>(qb, spins, acc, mult);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (i < quads) accumulate<M, LAYOUT>(qa, spins, acc, mult);
   }
-  if (i < quads) accumulate<M, LAYOUT>(qa, spins, acc, mult);
 }
 // The tail visit (every lane its OWN row of `row_quads` quads, at col_at / val_at bytes from the start of
 // the arrays): a lane streams the quads of its row and never the next block's — from its width on it
@@ -441,6 +483,17 @@ __device__ __forceinline__ void fill_blocks(T *per_block, uint32_t num_blocks, T
   for (uint32_t b = threadIdx.x; b < num_blocks; b += blockDim.x) per_block[b] = value;
 }
 
+// ---- Which kernels' block visit takes the k-loop that ends on the block's last real term (block_row_sums,
+// EXACT) ----
+// The forms of four chains per group in bytes, words and nibbles.  Every other kernel keeps the loop it had:
+// the switch at the loop's end is code a visit has to hold registers across (DESIGN.md section 6 has the
+// resource table of both loops).  Every kernel reads the exact width from meta[] all the same.
+template <int M, bool DESCENT, int LAYOUT, typename Args, typename Res>
+constexpr bool exact_kloop() {
+  if (M != 4 || DESCENT) return false;
+  return LAYOUT == kBytes || LAYOUT == kWide || LAYOUT == kNibbles;
+}
+
 // The whole anneal of one group of M replicas by one workgroup, in the phases sa_sweep_body() below runs in
 // order; `group` = index of the group inside its problem (k_sa_sweep: the workgroup id; k_sa_sweep_batch:
 // looked up in a table).
@@ -467,6 +520,8 @@ struct ColourSweep {
   static constexpr bool kLeanBook = M <= 4 && !(Res::kLadder && WIDE);  // see accept()
   // the best configuration lives in the words' d bits until the epilogue (clear_differs, materialise_best)
   static constexpr bool kLazyBest = WIDE;
+  // the block visit's k-loop ends on the block's last real term (block_row_sums)
+  static constexpr bool kExactLoop = exact_kloop<M, DESCENT, LAYOUT, Args, Res>();
   static_assert(!PACKED || M == 1, "the bit-packed layouts hold one replica");
   static_assert(!NIBBLES || (M <= 4 && !DESCENT), "the nibble layout holds up to four replicas");
   static_assert(!WIDE || (M <= 4 && !DESCENT), "the wide layout holds up to four replicas");
@@ -554,10 +609,24 @@ struct ColourSweep {
       } else {
         spins[p] = static_cast<uint8_t>(byte);
       }
-    }
-    if constexpr (!PACKED) {
-      for (uint32_t b = tid; b < a.num_blocks; b += blockDim.x) {
-        meta[b] = make_uint2(static_cast<uint32_t>(a.ell_off[b]), a.block_width[b]);
+      if constexpr (!PACKED) {
+        // meta[b0] = {first slab, EXACT width}.  The plan rounds a block's width up to whole quads and
+        // pads every row with entries that point at the row's own position (A has no diagonal: no real
+        // entry does), so the padding the 64 rows share is, in the block's last quad, the smallest count
+        // of trailing own-position columns over the lanes (a dummy lane is all padding: it never lowers
+        // it).  Once per launch and block; the plan's arrays stay what they are.
+        const uint32_t first_slab = static_cast<uint32_t>(a.ell_off[b0]);
+        const uint32_t rounded = a.block_width[b0];  // wave-uniform
+        uint32_t shared = 0;
+        if (rounded != 0u) {
+          const uint64_t last_quad = static_cast<uint64_t>((first_slab >> 2) + (rounded >> 2) - 1u);
+          const uint4 c4 = reinterpret_cast<const uint4 *>(a.ell_col)[last_quad * 64u + lane];
+          const uint32_t own = WIDE ? p * 4u : p;  // (wide columns are byte addresses)
+          const bool pad3 = c4.w == own, pad2 = pad3 && c4.z == own, pad1 = pad2 && c4.y == own;
+          shared = (__ballot(pad3) == ~0ull ? 1u : 0u) + (__ballot(pad2) == ~0ull ? 1u : 0u) +
+                   (__ballot(pad1) == ~0ull ? 1u : 0u);
+        }
+        if (lane == 0) meta[b0] = make_uint2(first_slab, rounded - shared);
       }
     }
     // delta[8] | book[24]: every entry is written once, by one lane — 0, or (a segment) for book[] of a
@@ -746,7 +815,7 @@ struct ColourSweep {
     if (live) {
       p = ring[(drained + lane) & (kTailRing - 1u)];
       const uint2 info = meta[p >> 6];
-      row_quads = info.y >> 2;
+      row_quads = (info.y + 3u) >> 2;  // (info.y: the exact width)
       // the lane's row in the arrays, from their start (the host launches this form only while
       // both arrays stay below 4 GiB): columns 1024 B and values 2048 B per quad of a block
       col_at = (info.x >> 2) * 1024u + (p & 63u) * 16u;
@@ -840,10 +909,11 @@ struct ColourSweep {
       // fields unchanged and every proposal certain to be rejected again: nothing to do
       if (reuse && __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(inert[b])) != 0u) return;
     }
-    // {first slab, width}: one broadcast LDS read (two scalar loads when bit-packed)
+    // {first slab, exact width}: one broadcast LDS read (bit-packed: two scalar loads, the rounded width)
     const uint2 info = PACKED ? make_uint2(static_cast<uint32_t>(a.ell_off[b]), a.block_width[b]) : meta[b];
     // wave-uniform by construction; readfirstlane makes the loop control scalar
-    const uint32_t quads = __builtin_amdgcn_readfirstlane(info.y) >> 2;
+    const uint32_t width = __builtin_amdgcn_readfirstlane(info.y);
+    const uint32_t quads = (width + 3u) >> 2;
     // info.x = first slab of the block (a multiple of 4): quad index = slab / 4
     const uint64_t first_quad = __builtin_amdgcn_readfirstlane(info.x) >> 2;
     const uint4 *col = reinterpret_cast<const uint4 *>(a.ell_col) + first_quad * 64u;
@@ -864,7 +934,7 @@ struct ColourSweep {
 #pragma unroll
       for (int m = 0; m < M; ++m) acc[m] = cache_row[m * 64];
     } else {
-      block_row_sums<M, LAYOUT>(stream, quads, spins, acc, mult);
+      block_row_sums<M, LAYOUT, kExactLoop>(stream, width, spins, acc, mult);
       if (cached) {
 #pragma unroll
         for (int m = 0; m < M; ++m) cache_row[m * 64] = acc[m];
