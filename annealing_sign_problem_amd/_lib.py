@@ -229,6 +229,42 @@ class SignScoresItem(ctypes.Structure):
     ]
 
 
+_VOTE_TAIL = [
+    ("weights", c_void_p),
+    ("ref", c_void_p),
+    ("anchor", c_u32),
+    ("align", c_u32),
+    ("rounds", c_u32),
+    ("out_distance", c_void_p),
+    ("out_flipped", c_void_p),
+    ("out_ones", c_void_p),
+    ("out_plus", c_void_p),
+    ("out_minus", c_void_p),
+    ("out_consensus", c_void_p),
+    ("out_changed", c_void_p),
+]
+
+
+class SignVoteItem(ctypes.Structure):
+    """Mirror of ``asp_sign_vote_item`` (include/asp.h)."""
+
+    _fields_ = [
+        ("num_spins", c_u64),
+        ("count", c_u32),
+        ("x", c_void_p),
+        ("x_stride", c_u64),
+    ] + _VOTE_TAIL
+
+
+class SaChainsVoteItem(ctypes.Structure):
+    """Mirror of ``asp_sa_chains_vote_item`` (include/asp.h)."""
+
+    _fields_ = [
+        ("chains", c_void_p),
+        ("which", c_u32),
+    ] + _VOTE_TAIL
+
+
 # name -> (restype, argtypes); every symbol include/asp.h declares
 SIGNATURES = {
     "asp_last_error": (ctypes.c_char_p, []),
@@ -394,6 +430,9 @@ SIGNATURES = {
     "asp_sa_chains_scores": (c_int, [c_void_p, c_u32, c_u64] + [c_void_p] * 6),
     "asp_sa_chains_distances": (c_int, [c_void_p, c_u32, c_void_p]),
     "asp_sign_scores_last_ms": (c_float, []),
+    "asp_sign_vote_batch": (c_int, [ctypes.POINTER(SignVoteItem), c_u32]),
+    "asp_sa_chains_vote_batch": (c_int, [ctypes.POINTER(SaChainsVoteItem), c_u32]),
+    "asp_sign_vote_last_ms": (c_float, []),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -52,6 +52,7 @@ __all__ = [
     "advance_ladder_chains",
     "exchange_chains",
     "cluster_move_chains",
+    "consensus_chains",
     "greedy_solve",
     "greedy_solve_batch",
     "signs_to_bits",
@@ -921,8 +922,17 @@ class Chains:
                                                        _lib.ptr(out)))
         return out
 
+    def consensus(self, weights=None, which: str = "best", anchor=None, align=None, rounds: int = 1):
+        """``scores.consensus`` of the handle's configurations WHERE THEY ARE (``asp_sa_chains_vote_batch``,
+        law ASP-VOTE-1): the chains' best (or current) configurations aligned up to the
+        global flip and voted per site, as a ``scores.Consensus`` that also carries the ``energy`` of the
+        consensus.  ``anchor=None``: the first chain of lowest energy, as ``result(only_best=True)`` picks
+        it (that takes the energies through ``result()``; an explicit ``anchor`` exports nothing);
+        ``align=None``: ``True`` exactly when the model has no field.  The chains are not touched."""
+        return consensus_chains([self], weights=[weights], which=which, anchor=anchor, align=align, rounds=rounds)[0]
+
     def _export(self, names) -> dict:
-        shapes = {"x_current": (self.repetitions, self.words), "x_best": (self.repetitions, self.words),
+        shapes ={"x_current": (self.repetitions, self.words), "x_best": (self.repetitions, self.words),
                   "tracked_current": (self.repetitions,), "tracked_best": (self.repetitions,),
                   "accepted": (self.repetitions,)}
         out = {name: np.zeros(shapes[name], dtype=np.int64 if name.startswith("tracked") else np.uint64)
@@ -1499,6 +1509,50 @@ def cluster_move_chains(chains, pairs, draws=0, flags=0):
         items[i].out_delta = deltas.ctypes.data
         out.append((differing, sizes, deltas))
     _lib.check(_lib.load().asp_sa_chains_cluster_move_batch(items, ctypes.c_uint32(n)))
+    return out
+
+
+def consensus_chains(chains, weights=None, which="best", anchor=None, align=None, rounds=1) -> list:
+    """``chains[i].consensus(weights[i], which[i], anchor[i], align[i], rounds[i])`` for every ``i`` in ONE
+    device call (``asp_sa_chains_vote_batch``): the same bits, but the handles share two
+    launches a round and every output comes back in one copy.  ``weights``: ``None`` (all 1 everywhere)
+    or one entry per handle (an array or ``None``); the others: one value for all or one per handle.  The
+    call only reads, so a handle may be named more than once."""
+    from . import scores as _scores
+
+    chains = list(chains)
+    n = len(chains)
+    for c in chains:
+        if not isinstance(c, Chains):
+            raise TypeError("'chains' must hold Chains objects")
+    weights = [None] * n if weights is None else list(weights)
+    if len(weights) != n:
+        raise ValueError("consensus_chains: %d handles, %d arrays of weights" % (n, len(weights)))
+    whiches = _per_handle(which, n, "consensus_chains: 'which'")
+    if any(w not in Chains._WHICH for w in whiches):
+        raise ValueError("'which' must be 'best' or 'current'")
+    anchors = _per_handle(anchor, n, "consensus_chains: 'anchor'")
+    aligns = _per_handle(align, n, "consensus_chains: 'align'")
+    all_rounds = _per_handle(rounds, n, "consensus_chains: 'rounds'")
+    items = (_lib.SaChainsVoteItem * max(n, 1))()
+    votes = []
+    for i, c in enumerate(chains):
+        handle = c._live()
+        if anchors[i] is None:
+            anchors[i] = int(np.argmin(c.result()[1]))  # first minimum, as result(only_best=True)
+        if aligns[i] is None:
+            aligns[i] = not np.any(c.hamiltonian.field)
+        vote = _scores._Vote(c.hamiltonian.size, c.repetitions, weights[i], None, anchors[i], aligns[i], all_rounds[i])
+        vote.fill(items[i])
+        items[i].chains = handle
+        items[i].which = Chains._WHICH[whiches[i]]
+        votes.append(vote)
+    _lib.check(_lib.load().asp_sa_chains_vote_batch(items, ctypes.c_uint32(n)))
+    out = []
+    for c, vote in zip(chains, votes):
+        result = vote.result()
+        result.energy = float(c.hamiltonian.energy(result.x))
+        out.append(result)
     return out
 
 

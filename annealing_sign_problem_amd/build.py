@@ -39,6 +39,7 @@ SOURCES = [
     "level_segments.hip",
     "bond_stats.hip",
     "sign_scores.hip",
+    "sign_vote.hip",
     "sa_plan.cpp",
     "greedy.cpp",
     "greedy_tree.hip",

@@ -606,6 +606,7 @@ def solve_ising_model(
     repetitions: int = 64,
     only_best: bool = True,
     sweep_order: Optional[str] = None,
+    select: str = "best",
     tree: Optional[str] = None,
 ) -> np.ndarray:
     """Optimise the signs of ``model`` and project them onto ``frozen_spins``
@@ -614,8 +615,15 @@ def solve_ising_model(
     the reference's law —, or ``"colour"``, this package's fixed colour order (faster, a different
     chain; ``sa.anneal``); ``None`` = ``$ASP_SWEEP_ORDER`` or shuffled.
     ``tree`` (not in the reference; ``mode="greedy"``): ``"host"`` or ``"device"``, where the greedy
-    solver's strongest-coupling tree is built; ``None`` = ``$ASP_GREEDY_TREE`` or host.  The same signs."""
-    if mode == "sa":
+    solver's strongest-coupling tree is built; ``None`` = ``$ASP_GREEDY_TREE`` or host.  The same signs.
+    ``select`` (not in the reference; ``mode="sa"``): ``"best"``, the chain of lowest energy, or
+    ``"consensus"``, the vote of all chains (:func:`_consensus_of_chains`)."""
+    _check_select(select, mode, "anneal", None)
+    if mode == "sa" and select == "consensus":
+        xs, es = sa.anneal(model.ising_hamiltonian, seed=seed, number_sweeps=number_sweeps,
+                           repetitions=repetitions, only_best=False, sweep_order=sweep_order)
+        x = _consensus_of_chains([model], [(xs, es)])[0]
+    elif mode == "sa":
         x, _ = sa.anneal(model.ising_hamiltonian, seed=seed, number_sweeps=number_sweeps,
                          repetitions=repetitions, only_best=only_best, sweep_order=sweep_order)
     elif mode == "greedy":
@@ -624,6 +632,26 @@ def solve_ising_model(
         raise ValueError(
             "invalid mode specified: '{}'; expected either 'sa' or 'greedy'".format(mode))
     return _project_on_frozen(model, x, frozen_spins)
+
+
+def _check_select(select: str, mode: str, method: str, patience) -> None:
+    if select not in ("best", "consensus"):
+        raise ValueError("invalid select specified: '{}'; expected 'best' or 'consensus'".format(select))
+    if select == "consensus" and (mode != "sa" or method != "anneal" or patience is not None):
+        raise ValueError("select='consensus' votes over the chains of a plain anneal: it needs mode='sa' and "
+                         "method='anneal', without 'patience'")
+
+
+def _consensus_of_chains(models, chains) -> list:
+    """The consensus configuration of every model's chains ``(xs[R, words], es[R])`` — the uniform vote
+    of law ASP-VOTE-1, anchored on the first chain of lowest energy and aligned up to
+    the global flip exactly when the model has no field — for ALL models in one device call
+    (``scores.consensus_batch``)."""
+    from . import scores
+
+    items = [dict(xs=xs, number_spins=m.ising_hamiltonian.size, anchor=int(np.argmin(es)),
+                  align=not np.any(m.ising_hamiltonian.field)) for m, (xs, es) in zip(models, chains)]
+    return [c.x for c in scores.consensus_batch(items)]
 
 
 def _project_on_frozen(model: IsingModel, x: np.ndarray, frozen_spins) -> np.ndarray:
@@ -638,7 +666,8 @@ def _project_on_frozen(model: IsingModel, x: np.ndarray, frozen_spins) -> np.nda
 def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_sweeps: int = 5120,
                        repetitions: int = 64, sweep_order: Optional[str] = None, mode: str = "sa",
                        check_every: Optional[int] = None, patience: Optional[int] = None,
-                       method: str = "anneal", plan_batch: bool = False, tree: Optional[str] = None):
+                       method: str = "anneal", plan_batch: bool = False, select: str = "best",
+                       tree: Optional[str] = None):
     """``[solve_ising_model(m, mode, f, seed, number_sweeps, repetitions) for m, f in
     zip(models, frozen_spins)]`` with all annealing chains of all models in ONE device call
     (``sa.anneal_batch``): the same result for every model, at the throughput of a full chip
@@ -655,7 +684,11 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
     ``tree`` (``mode="greedy"``): as in :func:`solve_ising_model`.
     ``plan_batch`` (not in the reference; default off): the sweep plans of all models are made by one
     segmented device call (``sa.plan_hamiltonians``) before the solve instead of one by one inside it;
-    the results are the same."""
+    the results are the same.
+    ``select`` (not in the reference; default ``"best"``): ``"consensus"`` returns, instead of every
+    model's chain of lowest energy, the vote of all its chains — uniform weights, anchored on that
+    chain, aligned up to the global flip where the model has no field (law ASP-VOTE-1, DESIGN.md
+    §3.12) —, all models in one ``scores.consensus_batch`` call; plain anneals only."""
     if method not in ("anneal", "population", "tempering", "tempering-cluster"):
         raise ValueError("invalid method specified: '{}'; expected 'anneal', 'population', 'tempering' or "
                          "'tempering-cluster'".format(method))
@@ -666,6 +699,7 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
             raise ValueError("method='{}' cannot be combined with 'patience'".format(method))
         if int(number_sweeps) < 10:
             raise ValueError("method='{}' runs steps of ten sweeps: 'number_sweeps' must be at least 10".format(method))
+    _check_select(select, mode, method, patience)
     models = list(models)
     frozen = [None] * len(models) if frozen_spins is None else list(frozen_spins)
     if mode not in ("sa", "greedy"):
@@ -699,6 +733,11 @@ def solve_ising_models(models, frozen_spins=None, seed: int = 12345, number_swee
                                      sweep_order=sweep_order, patience=patience,
                                      check_every=512 if check_every is None else check_every)
         return [_project_on_frozen(m, x, f) for m, (x, _, _), f in zip(models, best, frozen)]
+    if select == "consensus":
+        chains = sa.anneal_batch([m.ising_hamiltonian for m in models], seed=seed, number_sweeps=number_sweeps,
+                                 repetitions=repetitions, only_best=False, sweep_order=sweep_order)
+        voted = _consensus_of_chains(models, chains)
+        return [_project_on_frozen(m, x, f) for m, x, f in zip(models, voted, frozen)]
     best = sa.anneal_batch([m.ising_hamiltonian for m in models], seed=seed,
                            number_sweeps=number_sweeps, repetitions=repetitions, only_best=True,
                            sweep_order=sweep_order)

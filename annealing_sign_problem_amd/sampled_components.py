@@ -353,7 +353,10 @@ def score_solutions(staged, solutions, score_batch: bool = False) -> list:
 
 def early_stop_of(args) -> dict:
     """--anneal-patience / --anneal-check-every / --anneal-method as the ``early_stop`` keyword of :func:`anneal_staged`
-    and :func:`process_clusters_batched`; empty without them, so that every call is the one it was."""
+    and :func:`process_clusters_batched`; empty without them, so that every call is the one it was.
+    --anneal-select consensus (plain anneals only) is ``{"select": "consensus"}``."""
+    if getattr(args, "anneal_select", "best") != "best":  # (never together with the two below)
+        return {"early_stop": {"select": args.anneal_select}}
     if getattr(args, "anneal_method", "anneal") != "anneal":  # (never together with --anneal-patience)
         return {"early_stop": {"method": args.anneal_method}}
     if getattr(args, "anneal_patience", None) is None:
@@ -464,6 +467,13 @@ def parse_command_line(argv=None):
                              "parallel_tempering_cluster_batch), all in steps of ten "
                              "sweeps with the same sweep count.  Needs --annealing and --batch > 1, and is not "
                              "combined with --anneal-patience: the other methods change the results")
+    parser.add_argument("--anneal-select", type=str, default="best", choices=["best", "consensus"],
+                        help="which configuration of a model's annealing chains is scored: 'best' (default: the "
+                             "chain of lowest energy, as the reference) or 'consensus' (the chains aligned up to "
+                             "the global flip and voted per site, all models of a round in one device call: "
+                             "consensus_batch, asp_sign_vote_batch).  Needs --annealing and --batch > 1 and the "
+                             "plain --anneal-method without --anneal-patience; the SA columns then score the "
+                             "consensus")
     parser.add_argument("--sweep-order", type=str, default="shuffled", choices=["colour", "shuffled"],
                         help="visiting order of the annealing sweeps: 'shuffled' (default: a fresh "
                              "random order every sweep, the reference annealer's statistics) or "
@@ -524,6 +534,13 @@ def parse_command_line(argv=None):
         if not args.annealing or args.batch <= 1:
             parser.error("--anneal-method {} needs --annealing and --batch > 1 (it runs batched "
                          "segments)".format(args.anneal_method))
+    if args.anneal_select != "best":
+        if args.anneal_patience is not None or args.anneal_method != "anneal":
+            parser.error("--anneal-select {} votes over the chains of a plain anneal: not with --anneal-patience "
+                         "or another --anneal-method".format(args.anneal_select))
+        if not args.annealing or args.batch <= 1:
+            parser.error("--anneal-select {} needs --annealing and --batch > 1 (it votes a round at "
+                         "once)".format(args.anneal_select))
     if args.build_batch and (args.batch <= 1 or not (args.annealing or args.greedy_batch)):
         parser.error("--build-batch needs --batch > 1 and --annealing or --greedy-batch (it builds a round at once)")
     if args.score_batch and args.batch <= 1:

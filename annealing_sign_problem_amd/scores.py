@@ -8,19 +8,26 @@ configurations resident in a chains handle.
 Signs are packed as everywhere else (``annealer.signs_to_bits``: bit ``i`` of word ``i // 64`` set means
 ``s_i = +1``).  ``matches`` is an exact integer; ``signed`` and ``total`` are the pairwise tree of the
 specification (``tree_sum`` in tests/score_cases.py restates it in numpy), bit for bit, whatever the launch.
+
+Consensus signs (csrc/sign_vote.hip, law ASP-VOTE-1 in DESIGN.md §3.12; not in the reference): the
+configurations of a model aligned up to the global flip and a weighted vote per site — :func:`consensus`,
+:func:`consensus_batch` for many models in one call, ``annealer.Chains.consensus`` and
+``annealer.consensus_chains`` for resident chains; tests/vote_cases.py restates the law in numpy.
 No CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Sequence, Tuple
+import dataclasses
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
 
 __all__ = ["sign_scores", "sign_scores_batch", "accuracy_and_overlap", "accuracy_and_overlap_batch",
-           "accuracy_and_overlap_each", "sign_distances", "accuracy_and_overlap_of", "last_ms"]
+           "accuracy_and_overlap_each", "sign_distances", "accuracy_and_overlap_of", "last_ms", "Consensus",
+           "consensus", "consensus_batch", "vote_weights", "vote_last_ms"]
 
 # asp_sign_scores_item as a numpy record (checked against the ctypes mirror where it is used)
 _ITEM_RECORD = np.dtype([("num_spins", "<u8"), ("count", "<u4"), ("_pad", "<u4"), ("x", "<u8"), ("x_stride", "<u8"),
@@ -248,3 +255,137 @@ def sign_distances(xs, number_spins: int) -> np.ndarray:
 def last_ms() -> float:
     """Device time (ms) of the kernels of this thread's last scoring or distance call, copies excluded."""
     return float(_lib.load().asp_sign_scores_last_ms())
+
+
+# ---- consensus signs (csrc/sign_vote.hip, law ASP-VOTE-1, DESIGN.md §3.12) ----
+
+@dataclasses.dataclass
+class Consensus:
+    """What a vote returns (law ASP-VOTE-1): the consensus configuration ``x`` (``uint64[W]``, tail bits 0),
+    per site ``ones`` (``uint32[K]``: the aligned configurations with the bit set), ``plus`` / ``minus``
+    (``float64[K]``: their weights and the others', summed in ascending order of the configurations) and
+    ``margin = (plus - minus) / (plus + minus)`` (computed on the host; 0 where nothing has weight), per
+    configuration ``flipped`` (``bool[R]``) and ``distance`` (``uint32[R]``, to the last round's reference,
+    before the flip), and ``changed``: the sites on which ``x`` differs from the last round's reference
+    (0: a fixed point).  ``energy``: the Ising energy of ``x``, where a Hamiltonian was at hand."""
+    x: np.ndarray
+    ones: np.ndarray
+    plus: np.ndarray
+    minus: np.ndarray
+    margin: np.ndarray
+    flipped: np.ndarray
+    distance: np.ndarray
+    changed: int
+    energy: Optional[float] = None
+
+
+class _Vote:
+    """The checked inputs and the outputs of one item of a vote (kept alive over the call)."""
+
+    def __init__(self, number_spins, count, weights=None, ref=None, anchor=0, align=True, rounds=1, xs=None):
+        self.number_spins, self.count = int(number_spins), int(count)
+        if self.number_spins < 0:
+            raise ValueError("'number_spins' must not be negative")
+        self.words = (self.number_spins + 63) // 64
+        self.stride = 0
+        self.xs = None
+        if xs is not None:
+            xs = np.ascontiguousarray(xs, dtype=np.uint64)
+            if xs.ndim != 2:
+                raise ValueError("'xs' must be packed configurations [count, words]")
+            if xs.shape[1] < self.words:
+                raise ValueError("'xs' holds fewer than {} spins per configuration".format(self.number_spins))
+            self.count, self.stride = xs.shape[0], xs.shape[1]
+            self.xs = xs if xs.size else np.zeros(1, dtype=np.uint64)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if weights.shape[0] != self.count:
+                raise ValueError("'weights' must hold {} values, one per configuration".format(self.count))
+            if weights.shape[0] == 0:
+                weights = None
+        if ref is not None:
+            ref = np.ascontiguousarray(ref, dtype=np.uint64).reshape(-1)
+            if ref.shape[0] < self.words:
+                raise ValueError("'ref' holds fewer than {} spins".format(self.number_spins))
+            if ref.shape[0] == 0:
+                ref = np.zeros(1, dtype=np.uint64)  # (never read; NULL would mean x[anchor])
+        anchor, rounds = int(anchor), int(rounds)
+        if not (0 <= anchor < 2**32 and 0 <= rounds < 2**32):
+            raise ValueError("'anchor' and 'rounds' must fit 32 bits")
+        self.weights, self.ref, self.anchor, self.align, self.rounds = weights, ref, anchor, bool(align), rounds
+        self.distance = np.zeros(self.count, dtype=np.uint32)
+        self.flipped = np.zeros(self.count, dtype=np.uint8)
+        self.ones = np.zeros(self.number_spins, dtype=np.uint32)
+        self.plus = np.zeros(self.number_spins, dtype=np.float64)
+        self.minus = np.zeros(self.number_spins, dtype=np.float64)
+        self.x = np.zeros(self.words, dtype=np.uint64)
+        self.changed = np.zeros(1, dtype=np.uint32)
+
+    def fill(self, item) -> None:
+        """The fields that asp_sign_vote_item and asp_sa_chains_vote_item share, and x where there is one."""
+        if self.xs is not None:
+            item.num_spins = self.number_spins
+            item.count = self.count
+            item.x = _address(self.xs)
+            item.x_stride = self.stride
+        item.weights = None if self.weights is None else _address(self.weights)
+        item.ref = None if self.ref is None else _address(self.ref)
+        item.anchor, item.align, item.rounds = self.anchor, int(self.align), self.rounds
+        item.out_distance = _address(self.distance) if self.count else None
+        item.out_flipped = _address(self.flipped) if self.count else None
+        item.out_ones = _address(self.ones) if self.number_spins else None
+        item.out_plus = _address(self.plus) if self.number_spins else None
+        item.out_minus = _address(self.minus) if self.number_spins else None
+        item.out_consensus = _address(self.x) if self.words else None
+        item.out_changed = _address(self.changed)
+
+    def result(self) -> Consensus:
+        total = self.plus + self.minus
+        margin = np.zeros_like(total)
+        np.divide(self.plus - self.minus, total, out=margin, where=total != 0)
+        return Consensus(self.x, self.ones, self.plus, self.minus, margin, self.flipped.astype(bool), self.distance,
+                         int(self.changed[0]))
+
+
+def _as_vote(entry) -> _Vote:
+    if isinstance(entry, dict):
+        entry = dict(entry)
+        return _Vote(entry.pop("number_spins"), 0, xs=entry.pop("xs"), **entry)
+    xs, number_spins, *rest = entry
+    return _Vote(number_spins, 0, *rest, xs=xs)
+
+
+def consensus_batch(items) -> list:
+    """``[consensus(*item) for item in items]`` in ONE device call (``asp_sign_vote_batch``: one upload, two
+    launches a round whatever the number of items, one download), the same bits.  An item is the tuple of
+    :func:`consensus`' arguments, or a dict of them."""
+    votes = [_as_vote(entry) for entry in items]
+    raw = (_lib.SignVoteItem * max(len(votes), 1))()
+    for slot, vote in zip(raw, votes):
+        vote.fill(slot)
+    _lib.check(_lib.load().asp_sign_vote_batch(raw, ctypes.c_uint32(len(votes))))
+    return [vote.result() for vote in votes]
+
+
+def consensus(xs, number_spins, weights=None, ref=None, anchor=0, align=True, rounds=1) -> Consensus:
+    """The vote of law ASP-VOTE-1 over the configurations ``xs[R, words]`` of a
+    ``number_spins``-spin model, on the device: every configuration is aligned with the reference (``ref``,
+    packed, or ``xs[anchor]``) up to the global flip — flipped when it differs from it on more than half
+    of the sites; ``align=False``: never, for models with a field — and every site takes the sign that the
+    larger weight votes for (``weights``: one per configuration, ``None``: all 1; a tie takes the
+    reference's).  ``rounds > 1`` repeats the vote with the consensus as the reference."""
+    return consensus_batch([(xs, number_spins, weights, ref, anchor, align, rounds)])[0]
+
+
+def vote_weights(energies, beta=None) -> np.ndarray:
+    """Weights of a vote from the configurations' energies: ones (``beta=None``), or the Boltzmann factors
+    ``exp(-beta * (E - E.min()))``."""
+    energies = np.asarray(energies, dtype=np.float64).reshape(-1)
+    if beta is None or energies.shape[0] == 0:
+        return np.ones(energies.shape[0], dtype=np.float64)
+    return np.exp(-float(beta) * (energies - energies.min()))
+
+
+def vote_last_ms() -> float:
+    """Device time (ms) of the kernels of this thread's last vote, copies excluded."""
+    return float(_lib.load().asp_sign_vote_last_ms())

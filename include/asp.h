@@ -1382,6 +1382,81 @@ int asp_sa_chains_distances(asp_sa_chains *c, uint32_t which, uint32_t *out);
  * between host and device are not in it. */
 float asp_sign_scores_last_ms(void);
 
+/* ------------------------------------------------------------------------- */
+/* Consensus signs (csrc/sign_vote.hip, law ASP-VOTE-1): not */
+/* in the reference, which keeps the chain of lowest energy and nothing else */
+/* ------------------------------------------------------------------------- */
+
+/* One model of a vote: `count` = R packed configurations x[r * x_stride + word] of a K-spin model (the
+ * bits of the scores above: W = ceil(K / 64) words each, x_stride >= W, 0 is W; bits at positions >= K
+ * are ignored), weights (R doubles, NULL: all 1.0), a reference ref (W words; NULL: x[anchor]), the flag
+ * align and the number of rounds.  One round with reference ref:
+ *   d_r     = popcount((x_r xor ref) over bits < K)                        (out_distance[R])
+ *   flip_r  = align && 2 d_r > K          (a tie does not flip)            (out_flipped[R], 0 or 1)
+ *   a_ri    = bit i of x_r, xor flip_r
+ *   ones_i  = #{ r : a_ri = 1 }                                            (out_ones[K], exact)
+ *   plus_i  = the sum of w_r over the r with a_ri = 1, ASCENDING r from +0.0  (out_plus[K])
+ *   minus_i = the same over the r with a_ri = 0                            (out_minus[K])
+ *   c_i     = 1 if plus_i > minus_i, 0 if plus_i < minus_i, bit i of ref on equality (all weights
+ *             zero included); the tail bits of c's last word are 0        (out_consensus[W])
+ *   changed = #{ i : c_i != ref_i }                                        (out_changed[1])
+ * Round t + 1 takes c of round t for ref; the outputs are those of the last round, and changed = 0 says
+ * that c is a fixed point.  Every add is rounded on its own and nothing is multiplied, so the bits
+ * depend on no launch choice.  align = 0 is for models with a field, where the global flip is no
+ * symmetry.  Host pointers; each output may be NULL. */
+typedef struct asp_sign_vote_item {
+  uint64_t num_spins;
+  uint32_t count;
+  uint64_t const *x;
+  uint64_t x_stride;
+  double const *weights;
+  uint64_t const *ref;
+  uint32_t anchor;
+  uint32_t align;
+  uint32_t rounds;
+  uint32_t *out_distance;
+  uint8_t *out_flipped;
+  uint32_t *out_ones;
+  double *out_plus;
+  double *out_minus;
+  uint64_t *out_consensus;
+  uint32_t *out_changed;
+} asp_sign_vote_item;
+/* Many models: one upload, two launches a round of the item with the most rounds (their number does not
+ * depend on `count`), one download; the rounds follow one another on the device.  Item i receives the
+ * bits of a batch of that item alone, for any order and composition of the batch.  Checked before any
+ * device work and before any output is written, a refusal naming the item's index — ASP_ERR_TOO_LARGE:
+ * K >= 2^31, count > 2^20; ASP_ERR_INVALID: null items; a null x (count > 0, K > 0); x_stride in
+ * 1 .. W - 1; a weight that is negative, NaN or infinite; ref == NULL with anchor >= count (count > 0);
+ * rounds outside 1 .. 16.  A batch of 0 items and an item with count = 0 need no device and write
+ * nothing; K = 0 writes zeros to out_distance and out_flipped and changed = 0. */
+int asp_sign_vote_batch(asp_sign_vote_item const *items, uint32_t count);
+/* The same for the configurations RESIDENT in chains handles, in original spin order — which = 0: every
+ * chain's best, 1: its current one (ASP_ERR_INVALID above 1, and for a null handle) — without exporting
+ * them; K and count are the handle's spins and repetitions.  Many handles share the launches; one handle
+ * is a batch of one and then runs on its plan's stream.  Only reads the handles, so the same handle may
+ * appear twice, and the chains after the call are bit for bit the chains without it. */
+typedef struct asp_sa_chains_vote_item {
+  asp_sa_chains *chains;
+  uint32_t which;
+  double const *weights;
+  uint64_t const *ref;
+  uint32_t anchor;
+  uint32_t align;
+  uint32_t rounds;
+  uint32_t *out_distance;
+  uint8_t *out_flipped;
+  uint32_t *out_ones;
+  double *out_plus;
+  double *out_minus;
+  uint64_t *out_consensus;
+  uint32_t *out_changed;
+} asp_sa_chains_vote_item;
+int asp_sa_chains_vote_batch(asp_sa_chains_vote_item const *items, uint32_t count);
+/* Device time (ms, HIP events) of the kernels of this thread's last call of the two above; copies
+ * between host and device are not in it. */
+float asp_sign_vote_last_ms(void);
+
 #ifdef __cplusplus
 }
 #endif
