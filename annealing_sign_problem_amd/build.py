@@ -37,6 +37,7 @@ SOURCES = [
     "plain_basis.hip",
     "sparsify.hip",
     "level_segments.hip",
+    "cluster_grow.hip",
     "bond_stats.hip",
     "sign_scores.hip",
     "sign_vote.hip",

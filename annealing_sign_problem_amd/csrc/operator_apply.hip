@@ -670,13 +670,9 @@ unsigned grid_for(uint64_t items, uint64_t per_block) {
 
 namespace {
 
-int count_connections(const asp_operator *op, uint64_t n, const uint64_t *keys, ApplyBatch *w,
-                      hipStream_t stream) {
-  ASP_TRY(w->d_keys.alloc(n));
-  ASP_TRY(w->d_counts.alloc(n));
-  ASP_TRY(w->d_offsets.alloc(n + 1));
-  ASP_TRY(w->d_scratch.alloc(asp::scan_scratch_elems(n)));
-  ASP_TRY(w->d_keys.upload(keys, n, stream));
+// The counting pass over the n keys that are resident in w->d_keys (its other buffers allocated): the
+// connection offsets and, after ONE synchronisation, their total.
+int count_resident(const asp_operator *op, uint64_t n, ApplyBatch *w, hipStream_t stream) {
   if (n > 0) {
     hipLaunchKernelGGL(k_apply<false>, dim3(grid_for(n, kWaves)), dim3(kThreads), 0, stream,
                        op->d_bonds.ptr, op->num_bonds, w->d_keys.ptr, n, nullptr, w->d_counts.ptr,
@@ -690,6 +686,16 @@ int count_connections(const asp_operator *op, uint64_t n, const uint64_t *keys, 
   ASP_HIP_TRY(hipStreamSynchronize(stream));
   w->total = static_cast<uint64_t>(total);
   return ASP_OK;
+}
+
+int count_connections(const asp_operator *op, uint64_t n, const uint64_t *keys, ApplyBatch *w,
+                      hipStream_t stream) {
+  ASP_TRY(w->d_keys.alloc(n));
+  ASP_TRY(w->d_counts.alloc(n));
+  ASP_TRY(w->d_offsets.alloc(n + 1));
+  ASP_TRY(w->d_scratch.alloc(asp::scan_scratch_elems(n)));
+  ASP_TRY(w->d_keys.upload(keys, n, stream));
+  return count_resident(op, n, w, stream);
 }
 
 // After k_apply<true>: representatives and rescaled coefficients for a symmetry-adapted basis;
@@ -871,17 +877,36 @@ int connection_list_queue(const asp_operator *op, uint64_t n, const uint64_t *ke
   return symmetrise_batch(op, n, out->batch, out->d_other.ptr, out->d_coeffs.ptr, sym, false, stream);
 }
 
-int extension_list_queue(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
-                         Symmetrised *sym, hipStream_t stream) {
-  ASP_TRY(count_connections(op, n, keys, &out->batch, stream));
-  ASP_TRY(out->d_other.alloc(out->batch.total));
-  ASP_TRY(out->d_coeffs.alloc(out->batch.total));
+// The emitting pass and the symmetrise pass in extension mode, once the connections are counted.
+static int emit_extension(const asp_operator *op, uint64_t n, ConnectionList *out, Symmetrised *sym,
+                          hipStream_t stream) {
   if (n == 0) return ASP_OK;
   hipLaunchKernelGGL(k_apply<true>, dim3(grid_for(n, kWaves)), dim3(kThreads), 0, stream,
                      op->d_bonds.ptr, op->num_bonds, out->batch.d_keys.ptr, n, out->batch.d_offsets.ptr,
                      nullptr, out->d_other.ptr, out->d_coeffs.ptr);
   ASP_HIP_TRY(hipGetLastError());
   return symmetrise_batch(op, n, out->batch, out->d_other.ptr, out->d_coeffs.ptr, sym, true, stream);
+}
+
+int extension_list_queue(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
+                         Symmetrised *sym, hipStream_t stream) {
+  ASP_TRY(count_connections(op, n, keys, &out->batch, stream));
+  ASP_TRY(out->d_other.alloc(out->batch.total));
+  ASP_TRY(out->d_coeffs.alloc(out->batch.total));
+  return emit_extension(op, n, out, sym, stream);
+}
+
+int extension_list_queue_device(const asp_operator *op, uint64_t n, ConnectionList *out, Symmetrised *sym,
+                                hipStream_t stream) {
+  // (grow-only: a caller that comes back pass after pass keeps its buffers; whatever is replaced here was
+  // last used before the caller's previous synchronisation)
+  ASP_TRY(out->batch.d_counts.ensure(n));
+  ASP_TRY(out->batch.d_offsets.ensure(n + 1));
+  ASP_TRY(out->batch.d_scratch.ensure(asp::scan_scratch_elems(n)));
+  ASP_TRY(count_resident(op, n, &out->batch, stream));
+  ASP_TRY(out->d_other.ensure(out->batch.total));
+  ASP_TRY(out->d_coeffs.ensure(out->batch.total));
+  return emit_extension(op, n, out, sym, stream);
 }
 
 int connection_list(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,

@@ -108,6 +108,12 @@ int connection_list_queue(const asp_operator *op, uint64_t n, const uint64_t *ke
 // op->symmetry().mask; out->d_coeffs is scratch.  One synchronisation inside (the connection count).
 int extension_list_queue(const asp_operator *op, uint64_t n, const uint64_t *keys, ConnectionList *out,
                          Symmetrised *sym, hipStream_t stream);
+// extension_list_queue for n keys that are ALREADY on the device: the caller has allocated out->batch.d_keys and
+// queued on `stream` whatever fills its first n entries; no upload.  The other buffers of `out` only grow, so a
+// caller that comes back pass after pass (asp_operator_grow_segments) keeps them; call it when nothing queued
+// earlier on `stream` still reads them.  One synchronisation inside (the connection count).
+int extension_list_queue_device(const asp_operator *op, uint64_t n, ConnectionList *out, Symmetrised *sym,
+                                hipStream_t stream);
 // Clears slots[slots_n] (a power of two >= 2n) and inserts the n device keys.
 int key_hash_build(const uint64_t *d_keys, uint64_t n, unsigned long long *d_slots, uint64_t slots_n,
                    hipStream_t stream);

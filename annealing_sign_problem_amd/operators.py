@@ -643,6 +643,32 @@ class DeviceOperator:
             _lib.ptr(out_offsets), ctypes.byref(count)))
         return out[:int(count.value)].copy(), out_offsets
 
+    def grow_segments(self, seeds, sizes, keep_probability: float, seed: int, ids=None):
+        """Grows one cluster per seed state in one call, specification ASP-GROW-1: cluster
+        ``g`` has at most ``sizes[g]`` states, and its draws are the Philox stream ``ids[g]`` (default
+        ``0 ... G - 1``) of the 64-bit ``seed``, so it does not depend on what else is in the call.
+        ``(clusters, passes)``: a list of sorted ``uint64`` arrays and ``uint32[G]``."""
+        import ctypes
+
+        _lib = self._lib_module
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+        sizes = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+        g = seeds.shape[0]
+        ids = np.arange(g, dtype=np.uint32) if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if sizes.shape[0] != g or ids.shape[0] != g:
+            raise ValueError("one size and one id per seed")
+        capacity = int(sizes.sum(dtype=np.uint64)) if g else 0
+        out = np.empty(max(capacity, 1), dtype=np.uint64)
+        out_offsets = np.zeros(g + 1, dtype=np.uint64)
+        passes = np.zeros(max(g, 1), dtype=np.uint32)
+        count = ctypes.c_uint64(0)
+        _lib.check(self._lib.asp_operator_grow_segments(
+            self._handle, g, _lib.ptr(seeds), _lib.ptr(sizes), _lib.ptr(ids), float(keep_probability),
+            int(seed) & (2 ** 64 - 1), capacity, _lib.ptr(out), _lib.ptr(out_offsets), ctypes.byref(count),
+            _lib.ptr(passes)))
+        bounds = out_offsets.astype(np.int64)
+        return [out[bounds[j]:bounds[j + 1]].copy() for j in range(g)], passes[:g]
+
 
 class IsingStencil:
     """``asp_ising_stencil`` handle (csrc/ising_stencil.hip; :meth:`DeviceOperator.ising_stencil`): the

@@ -112,12 +112,67 @@ def random_cluster_size(min_size: float, max_size: float) -> int:
     return int(round(np.exp(np.log(min_size) + (np.log(max_size) - np.log(min_size)) * u)))
 
 
+GROW_CONNECTIONS_PER_CALL = 2 ** 32 - 1
+
+
+def grow_clusters(hamiltonian, seeds, sizes, keep_probability: float, seed: int, first_id: int = 0,
+                  max_connections_per_call: int = GROW_CONNECTIONS_PER_CALL) -> List[np.ndarray]:
+    """One cluster per seed state, grown on the device by specification ASP-GROW-1 (DESIGN.md §3.13;
+    ``DeviceOperator.grow_segments``, asp_operator_grow_segments): the law of
+    :func:`create_small_cluster_around_point` with the frontier visited in ascending order and one Philox draw
+    per candidate, so these are DIFFERENT clusters of the same law.  Cluster ``j`` draws from stream
+    ``first_id + j`` of ``seed``.  A long list is cut into calls whose bound on the connections of a pass,
+    (sum of the sizes) * max_connections, stays at or below ``max_connections_per_call``; the cut changes no
+    cluster.  No host fallback: an operator without a device action is an error."""
+    if not common._on_device(hamiltonian):
+        raise TypeError("grow_clusters needs this package's operator with real matrices: {} has no device "
+                        "action".format(type(hamiltonian).__name__))
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    if sizes.shape[0] != seeds.shape[0]:
+        raise ValueError("one size per seed")
+    device = hamiltonian.device()
+    room = max(int(max_connections_per_call) // max(device.max_connections, 1), 1)  # states per call
+    clusters: List[np.ndarray] = []
+    start, n = 0, seeds.shape[0]
+    while start < n:
+        stop, states = start, 0
+        while stop < n and (stop == start or states + int(sizes[stop]) <= room):
+            states += int(sizes[stop])
+            stop += 1
+        ids = (np.arange(start, stop, dtype=np.uint64) + np.uint64(first_id)).astype(np.uint32)
+        grown, _ = device.grow_segments(seeds[start:stop], sizes[start:stop], keep_probability, seed, ids=ids)
+        clusters.extend(grown)
+        start = stop
+    return clusters
+
+
 def iter_clusters(hamiltonian, ground_state, number_samples: int, sampled_power: float,
-                  min_cluster_size: int, max_cluster_size: int, keep_probability: float):
+                  min_cluster_size: int, max_cluster_size: int, keep_probability: float,
+                  grow: str = "host", batch: int = 256):
     """driver :652-669, one cluster at a time (all draws from numpy's global stream, in the
-    reference's order: the seeds first, then size and growth of one cluster after the other)."""
+    reference's order: the seeds first, then size and growth of one cluster after the other).
+
+    ``grow="device"`` (not in the reference): the seeds as before, then ALL sizes in cluster order and ONE
+    ``np.random.randint`` draw for the Philox seed from the same stream, then the clusters in rounds of
+    ``batch`` from :func:`grow_clusters` — different clusters of the same law."""
+    if grow not in ("host", "device"):
+        raise ValueError("grow should be 'host' or 'device'")
     seeds = common.monte_carlo_sampling(hamiltonian.basis.states, ground_state,
                                         number_samples=number_samples, sampled_power=sampled_power)
+    if grow == "device":
+        if not common._on_device(hamiltonian):
+            raise TypeError("grow='device' needs this package's operator with real matrices: {} has no device "
+                            "action".format(type(hamiltonian).__name__))
+        spins = np.ascontiguousarray(np.asarray(seeds.spins, dtype=np.uint64).reshape(len(seeds.spins), -1)[:, 0])
+        sizes = np.array([random_cluster_size(min_cluster_size, max_cluster_size) for _ in range(spins.shape[0])],
+                         dtype=np.uint64)
+        philox_seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64))
+        step = max(int(batch), 1)
+        for start in range(0, spins.shape[0], step):
+            yield from grow_clusters(hamiltonian, spins[start:start + step], sizes[start:start + step],
+                                     keep_probability, philox_seed, first_id=start)
+        return
     for s in seeds.spins:
         size = random_cluster_size(min_cluster_size, max_cluster_size)
         cluster = create_small_cluster_around_point(s, hamiltonian, required_size=size,
@@ -127,10 +182,21 @@ def iter_clusters(hamiltonian, ground_state, number_samples: int, sampled_power:
 
 def generate_clusters(hamiltonian, ground_state, number_samples: int, sampled_power: float,
                       min_cluster_size: int, max_cluster_size: int,
-                      keep_probability: float) -> List[np.ndarray]:
-    """driver :652-669."""
+                      keep_probability: float, grow: str = "host", batch: int = 256) -> List[np.ndarray]:
+    """driver :652-669; ``grow="device"``: see :func:`iter_clusters`."""
+    if grow == "host":
+        return list(iter_clusters(hamiltonian, ground_state, number_samples, sampled_power,
+                                  min_cluster_size, max_cluster_size, keep_probability))
     return list(iter_clusters(hamiltonian, ground_state, number_samples, sampled_power,
-                              min_cluster_size, max_cluster_size, keep_probability))
+                              min_cluster_size, max_cluster_size, keep_probability, grow=grow, batch=batch))
+
+
+def grow_of(args) -> dict:
+    """The keyword arguments of :func:`iter_clusters` / :func:`generate_clusters` for ``--grow`` (none for the
+    default, the host growth)."""
+    if getattr(args, "grow", "host") == "host":
+        return {}
+    return {"grow": args.grow, "batch": args.batch}
 
 
 @dataclass
@@ -517,6 +583,12 @@ def parse_command_line(argv=None):
                              "(make_ising_model(..., external_field=True)): the amplitudes of the states "
                              "one hop outside the model act on it with their signs.  --global-cutoff still "
                              "only selects spins: a spin it drops is not moved into the environment")
+    parser.add_argument("--grow", choices=("host", "device"), default="host",
+                        help="where the clusters are grown: 'host' (default: the reference's growth, one "
+                             "sequential chain of numpy draws) or 'device' (grow_clusters, "
+                             "asp_operator_grow_segments: rounds of --batch clusters in one segmented device "
+                             "call each, specification ASP-GROW-1 — different clusters of the same law, so "
+                             "another file; needs this package's operator, there is no fallback)")
     parser.add_argument("--jobs", type=int, default=1,
                         help="host threads building / solving clusters concurrently (independent "
                              "plans and HIP streams on one GPU; the output does not depend on it)")
@@ -615,7 +687,7 @@ def _generate_in_child(conn, hamiltonian, ground_state, args):
     any HIP state and can fork its workers afterwards."""
     try:
         clusters = generate_clusters(hamiltonian, ground_state, args.number_samples, args.sampled_power,
-                                     args.min_cluster_size, args.max_cluster_size, args.keep_probability)
+                                     args.min_cluster_size, args.max_cluster_size, args.keep_probability, **grow_of(args))
         conn.send(("ok", clusters))
     except BaseException as error:  # noqa: BLE001 - reported to the parent
         conn.send(("error", "%s: %s" % (type(error).__name__, error)))
@@ -629,7 +701,7 @@ def _stream_from_child(conn, hamiltonian, ground_state, args):
     try:
         pending = []
         for cluster in iter_clusters(hamiltonian, ground_state, args.number_samples, args.sampled_power,
-                                     args.min_cluster_size, args.max_cluster_size, args.keep_probability):
+                                     args.min_cluster_size, args.max_cluster_size, args.keep_probability, **grow_of(args)):
             pending.append(cluster)
             if len(pending) >= 16:
                 conn.send(("clusters", pending))
@@ -660,7 +732,7 @@ def clusters_from_child(hamiltonian, ground_state, args):
                 or os.environ.get("ASP_GROW_IN_PLACE") == "1")
     if in_place:
         yield from iter_clusters(hamiltonian, ground_state, args.number_samples, args.sampled_power,
-                                 args.min_cluster_size, args.max_cluster_size, args.keep_probability)
+                                 args.min_cluster_size, args.max_cluster_size, args.keep_probability, **grow_of(args))
         return
     ctx = multiprocessing.get_context("fork")
     receiver, sender = ctx.Pipe(False)
@@ -895,7 +967,7 @@ def _main_in_group(args, asp_dist, created_group, phase):
         if writer:
             clusters = generate_clusters(hamiltonian, ground_state, args.number_samples,
                                          args.sampled_power, args.min_cluster_size,
-                                         args.max_cluster_size, args.keep_probability)
+                                         args.max_cluster_size, args.keep_probability, **grow_of(args))
         clusters = asp_dist.broadcast_object(clusters)
         phase("clusters grown")
     else:

@@ -341,6 +341,31 @@ int asp_operator_extend(asp_operator const *op, uint64_t n, uint64_t const *keys
 int asp_operator_extend_segments(asp_operator const *op, uint64_t num_segments, uint64_t const *offsets,
                                  uint64_t const *keys, uint64_t capacity, uint64_t *out,
                                  uint64_t *out_offsets, uint64_t *count);
+/* The growth of many sampled clusters in one call, specification ASP-GROW-1.  Segment g
+ * grows a cluster of at most sizes[g] >= 1 states around the basis state seeds[g] (for a symmetry-adapted
+ * basis a representative of non-zero norm) by breadth-first passes t = 0, 1, ...: the frontier F_t
+ * (F_0 = [seed]) is visited in ascending order; its states are added to the cluster until the size is
+ * reached — then the segment ends after this pass —; the states before that one are applied
+ * (asp_operator_apply's row order, own state first, in a symmetry-adapted basis the representatives
+ * without the orbits of norm 0), and the k-th entry of the i-th source's row, if it is neither in the
+ * cluster before the pass nor at a position <= i of F_t, is kept iff word 0 of Philox4x32-10(counter
+ * (i, k, t, ids[g]), key (rng_seed low, high)) < floor(keep_probability * 2^32); F_{t+1} is the sorted set of
+ * the kept ones.  A segment's result depends on (operator, seed, size, id, keep_probability, rng_seed) only.
+ * out[out_offsets[g] : out_offsets[g + 1]] are segment g's states, ascending; out_offsets is
+ * u64[num_segments + 1] from 0, *count its last entry, passes[g] (NULL: not wanted) the number of passes
+ * in which segment g had a frontier.  The caller allocates capacity >= sum of sizes: an upper bound, so
+ * there is no sizing call.  Before any launch and before any output is written: ASP_ERR_INVALID for a null
+ * handle, a null count or out_offsets, null seeds, sizes or ids with num_segments > 0, a
+ * keep_probability outside [0, 1] (or NaN), a size of 0, capacity below the sum of the sizes, a null out
+ * and a seed with a bit at or above number_spins; ASP_ERR_TOO_LARGE for 2^32 - 1 or more segments or
+ * states.  A pass whose applied sources times max_connections reach 2^32 is ASP_ERR_TOO_LARGE before that
+ * pass's launches; a seed of norm 0 in a -1 sector is ASP_ERR_INVALID; in both cases no output is
+ * written.  num_segments == 0 needs no device.  Per pass the number of launches and of host
+ * synchronisations (two) does not depend on num_segments.  asp_operator_last_ms reports the duration. */
+int asp_operator_grow_segments(asp_operator const *op, uint64_t num_segments, uint64_t const *seeds,
+                               uint64_t const *sizes, uint32_t const *ids, double keep_probability,
+                               uint64_t rng_seed, uint64_t capacity, uint64_t *out, uint64_t *out_offsets,
+                               uint64_t *count, uint32_t *passes /* [num_segments] or NULL */);
 
 /* Boundary field of a cluster, specification ASP-FIELD-1: the miss branch of the
  * reference's coupling build (cbits/build_matrix.c:49) with counts = 1.  keys[num_spins] ascending
