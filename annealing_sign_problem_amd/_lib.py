@@ -321,6 +321,8 @@ SIGNATURES = {
                                            c_u64, c_void_p, c_void_p, ctypes.POINTER(c_u64), c_void_p]),
     "asp_operator_field": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_u64, c_void_p, c_void_p,
                                    ctypes.c_double, c_void_p, ctypes.POINTER(c_u64)]),
+    "asp_operator_field_segments": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, ctypes.c_double, c_void_p, c_void_p]),
     "asp_operator_local_energy": (c_int, [c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_u64, c_void_p,
                                           c_void_p, c_void_p, c_void_p]),
     "asp_operator_last_ms": (c_float, []),

@@ -30,6 +30,7 @@ SOURCES = [
     "ising_elements.hip",
     "operator_apply.hip",
     "operator_field.hip",
+    "operator_field_segments.hip",
     "operator_local_energy.hip",
     "operator_ising_segments.hip",
     "sector_basis.hip",

@@ -250,8 +250,11 @@ def make_ising_models(clusters, quantum_hamiltonian, log_psis=None, log_psi_fn=N
     ASP-ISING-SEG-1): the same models field by field — ``spins``, the exchange's CSR
     arrays as bits, ``field``, ``initial_signs``, ``basis_index``.  Everything else is done per cluster
     as there: sort and unique, the amplitudes and their normalisation, the ``index_of`` / ``at_index``
-    shortcut of the ground-state closure and, with ``external_field=True``, the boundary field.
-    ``log_psis``: one array per cluster, or ``None``.  Foreign operator objects, and operators whose
+    shortcut of the ground-state closure.  With ``external_field=True`` the boundary fields of ALL
+    clusters come from one extension call and one field call (``_boundary_fields``, ASP-FIELD-SEG-1,
+    DESIGN.md §3.5.1): ``log_psi_fn`` is asked for the environments cluster by cluster, in order, AFTER
+    the states of all clusters instead of in turns with them, so a pure ``log_psi_fn`` gives identical
+    models.  ``log_psis``: one array per cluster, or ``None``.  Foreign operator objects, and operators whose
     segmented call is refused with ASP_ERR_INVALID (one-directional matrix elements with duplicates),
     take the loop."""
     clusters = list(clusters)
@@ -269,11 +272,16 @@ def make_ising_models(clusters, quantum_hamiltonian, log_psis=None, log_psi_fn=N
         raise ValueError("at least one of log_psi or log_psi_fn should be specified")
     if external_field and log_psi_fn is None:
         raise ValueError("log_psi_fn should be specified when external_field=True")
-    prepared = []
+    states = []
     for spins, log_psi in zip(clusters, log_psis):
         spins, log_psi, basis_index = _cluster_states(spins, log_psi, log_psi_fn)
-        psi, field = _cluster_amplitudes_and_field(quantum_hamiltonian, spins, log_psi, log_psi_fn, external_field)
-        prepared.append((spins, basis_index, psi, field))
+        psi, cluster_norm = _cluster_amplitudes(log_psi)
+        states.append((spins, basis_index, psi, cluster_norm))
+    if external_field:
+        fields = _boundary_fields(quantum_hamiltonian, [(spins, psi, c) for spins, _, psi, c in states], log_psi_fn)
+    else:
+        fields = [np.zeros(spins.shape[0]) for spins, _, _, _ in states]
+    prepared = [(spins, basis_index, psi, field) for (spins, basis_index, psi, _), field in zip(states, fields)]
     offsets = np.zeros(len(prepared) + 1, dtype=np.uint64)
     np.cumsum([p[0].shape[0] for p in prepared], out=offsets[1:])
     try:
@@ -297,8 +305,8 @@ def make_ising_models(clusters, quantum_hamiltonian, log_psis=None, log_psi_fn=N
 
 def make_hamiltonian_extensions(models, log_psi_fn, external_field: bool = False):
     """``[make_hamiltonian_extension(m, log_psi_fn, external_field) for m in models]`` (not in the
-    reference) with the couplings of all extensions built in one device call
-    (:func:`make_ising_models`); the models share one operator."""
+    reference) with the couplings of all extensions — and, with ``external_field``, their boundary
+    fields — built in one device call each (:func:`make_ising_models`); the models share one operator."""
     models = list(models)
     if not models:
         return []
@@ -339,15 +347,22 @@ def _cluster_amplitudes_and_field(hamiltonian, spins, log_psi, log_psi_fn, exter
     amplitudes L2-normalised over the cluster (common.py:211-216) and the zero or boundary field.
     One place for :func:`make_ising_model` and :func:`reweight_ising_model`, whose models must agree
     bit for bit."""
+    psi, cluster_norm = _cluster_amplitudes(log_psi)
+    field = np.zeros(spins.shape[0]) if not external_field else _boundary_field(
+        hamiltonian, spins, psi, log_psi_fn, cluster_norm)
+    return psi, field
+
+
+def _cluster_amplitudes(log_psi):
+    """``(psi, cluster_norm)``: the real amplitudes of a cluster's states, L2-normalised over the cluster
+    (common.py:211-216), and the norm they were divided by."""
     psi = np.exp(log_psi, dtype=np.complex128)
     if not np.allclose(psi.imag, 0, atol=1e-6):
         raise ValueError("expected all wavefunction coefficients to be real")
     psi = np.ascontiguousarray(psi.real)
     cluster_norm = norm2(psi)
     psi /= cluster_norm
-    field = np.zeros(spins.shape[0]) if not external_field else _boundary_field(
-        hamiltonian, spins, psi, log_psi_fn, cluster_norm)
-    return psi, field
+    return psi, cluster_norm
 
 
 def reweight_ising_model(
@@ -449,8 +464,11 @@ def reweight_ising_models(model: IsingModel, log_psis=None, log_psi_fns=None, ex
     a log_psi_fn).  The stencil is created on first use and kept with the family of ``model``'s
     Hamiltonian; it goes with ``model.ising_hamiltonian.release()``.  A draw whose couplings leave the
     pattern gets ``make_ising_model``'s model; an operator without a device action, and a stencil that
-    cannot be made, take the per-model route.  With ``external_field=True`` every draw's field still
-    needs its operator pass (``_boundary_field``)."""
+    cannot be made, take the per-model route.  With ``external_field=True`` the fields of all stencil
+    draws come from ONE device call (``_boundary_fields``, ASP-FIELD-SEG-1): one
+    segment per draw, the same states and the same environment — computed once —, each with its own
+    amplitudes and norm; every ``log_psi_fn`` is asked for the environment after the amplitudes of all
+    draws are known, in draw order."""
     lengths = {len(x) for x in (log_psis, log_psi_fns, outs) if x is not None}
     if len(lengths) > 1:
         raise ValueError("'log_psis', 'log_psi_fns' and 'outs' should hold one element per draw")
@@ -496,10 +514,17 @@ def reweight_ising_models(model: IsingModel, log_psis=None, log_psi_fns=None, ex
                 values = log_psi_fn.at_index(basis_index)
             else:
                 values = log_psi_fn(spins)
-        psi, field = _cluster_amplitudes_and_field(operator, spins, values, log_psi_fns[d], external_field)
-        draws.append((d, psi, field, basis_index))
+        psi, cluster_norm = _cluster_amplitudes(values)
+        draws.append((d, psi, cluster_norm, basis_index))
     if not draws:
         return results
+    if external_field:
+        # D segments of the same states and (computed once) the same environment, amplitudes per draw
+        fields = _boundary_fields(operator, [(spins, psi, c) for _, psi, c, _ in draws],
+                                  [log_psi_fns[d] for d, _, _, _ in draws])
+    else:
+        fields = [np.zeros(spins.shape[0]) for _ in draws]
+    draws = [(d, psi, field, basis_index) for (d, psi, _, basis_index), field in zip(draws, fields)]
     cloned = []
     try:
         hamiltonians = []
@@ -550,6 +575,72 @@ def _boundary_field(hamiltonian, spins, psi, log_psi_fn, cluster_norm: float) ->
     if unresolved > 0:
         raise ValueError("{} connections leave the cluster for states outside its environment".format(unresolved))
     return field
+
+
+def _boundary_fields(hamiltonian, clusters, log_psi_fns) -> list:
+    """``[_boundary_field(hamiltonian, spins, psi, log_psi_fn, cluster_norm) for spins, psi, cluster_norm in
+    clusters]`` for prepared clusters of ONE device operator, with all environments from one
+    :func:`extension_spins_segments` call and all fields from one ``DeviceOperator.field_segments`` call
+    (ASP-FIELD-SEG-1): the same fields bit for bit.  ``log_psi_fns``: one callable for
+    all clusters, or one per cluster.  Clusters that share their ``spins`` array (the draws of a noise
+    study) share one environment, which is computed once.  The amplitude lookups are the loop's — per
+    cluster, in cluster order, with the arguments the loop passes —; only their interleaving with whatever
+    the caller does between the clusters changes, so a pure ``log_psi_fn`` gives identical fields.  The
+    ``ValueError`` for connections that leave a cluster's environment is that of the FIRST such cluster,
+    the one the loop raises.  A call refused for its size (ASP_ERR_TOO_LARGE), or in a way after which
+    the host route does the job, takes the loop."""
+    clusters = list(clusters)
+    if not clusters:
+        return []
+    if callable(log_psi_fns):
+        log_psi_fns = [log_psi_fns] * len(clusters)
+
+    def loop():
+        return [_boundary_field(hamiltonian, spins, psi, fn, cluster_norm)
+                for (spins, psi, cluster_norm), fn in zip(clusters, log_psi_fns)]
+
+    distinct, key_sets = {}, []  # id(spins) -> position among the distinct key sets
+    for spins, _, _ in clusters:
+        if id(spins) not in distinct:
+            distinct[id(spins)] = len(key_sets)
+            key_sets.append(spins)
+    try:
+        extended = extension_spins_segments(hamiltonian, key_sets)
+    except _lib.AspError as error:
+        if not (error.code == -4 or _takes_host_route(error)):
+            raise
+        return loop()
+    environments = []
+    for (spins, _, cluster_norm), log_psi_fn in zip(clusters, log_psi_fns):
+        env_keys = extended[distinct[id(spins)]]
+        if hasattr(log_psi_fn, "index_of"):  # (ground_state_to_log_coeff_fn's closure)
+            env_log_psi = log_psi_fn.at_index(log_psi_fn.index_of(env_keys))
+        else:
+            env_log_psi = log_psi_fn(env_keys)
+        env_psi = np.exp(env_log_psi, dtype=np.complex128)
+        if not np.allclose(env_psi.imag, 0, atol=1e-6):
+            raise ValueError("expected all wavefunction coefficients to be real")
+        env_psi = np.ascontiguousarray(env_psi.real)
+        env_psi /= cluster_norm
+        environments.append((env_keys, env_psi))
+    offsets = np.zeros(len(clusters) + 1, dtype=np.uint64)
+    np.cumsum([spins.shape[0] for spins, _, _ in clusters], out=offsets[1:])
+    env_offsets = np.zeros(len(clusters) + 1, dtype=np.uint64)
+    np.cumsum([env_keys.shape[0] for env_keys, _ in environments], out=env_offsets[1:])
+    try:
+        field, unresolved = hamiltonian.device().field_segments(
+            np.concatenate([spins for spins, _, _ in clusters]), np.concatenate([psi for _, psi, _ in clusters]),
+            offsets, np.concatenate([env_keys for env_keys, _ in environments]),
+            np.concatenate([env_psi for _, env_psi in environments]), env_offsets, scale=2.0)
+    except _lib.AspError as error:
+        if not (error.code == -4 or _takes_host_route(error)):
+            raise
+        return loop()
+    lost = np.flatnonzero(unresolved)
+    if lost.size:
+        raise ValueError("{} connections leave the cluster for states outside its environment".format(
+            int(unresolved[lost[0]])))
+    return [field[int(offsets[g]):int(offsets[g + 1])].copy() for g in range(len(clusters))]
 
 
 def compute_accuracy_and_overlap(

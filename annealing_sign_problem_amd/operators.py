@@ -563,6 +563,43 @@ class DeviceOperator:
                                                 _lib.ptr(out), ctypes.byref(unresolved)))
         return out[:k], int(unresolved.value)
 
+    def field_segments(self, keys, psi, offsets, env_keys, env_psi, env_offsets,
+                       scale: float = 2.0) -> Tuple[np.ndarray, np.ndarray]:
+        """:meth:`field` of many clusters in one call, specification ASP-FIELD-SEG-1:
+        ``offsets`` (u64[S + 1], from 0, non-decreasing) cuts ``keys`` / ``psi`` into clusters and
+        ``env_offsets`` cuts ``env_keys`` / ``env_psi`` into their environments, each segment ascending
+        and unique.  ``(field f64[T], unresolved u64[S])``: ``field[offsets[g]:offsets[g + 1]]`` and
+        ``unresolved[g]`` are ``field`` of cluster ``g`` in environment ``g`` alone, bit for bit.
+        ``env_keys=None``: every environment is empty."""
+        _lib = self._lib_module
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        psi = np.ascontiguousarray(psi, dtype=np.float64)
+        if keys.ndim != 1 or psi.shape != keys.shape:
+            raise ValueError("psi and keys differ in length")
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        t = keys.shape[0]
+        if offsets.ndim != 1 or offsets.shape[0] < 1 or int(offsets[-1]) != t:
+            raise ValueError("offsets should run from 0 to the number of keys")
+        segments = offsets.shape[0] - 1
+        if env_keys is None:
+            env_keys = env_psi = None
+            env_offsets = np.zeros(segments + 1, dtype=np.uint64)
+        else:
+            env_keys = np.ascontiguousarray(env_keys, dtype=np.uint64)
+            env_psi = np.ascontiguousarray(env_psi, dtype=np.float64)
+            if env_keys.ndim != 1 or env_psi.shape != env_keys.shape:
+                raise ValueError("env_psi and env_keys differ in length")
+            env_offsets = np.ascontiguousarray(env_offsets, dtype=np.uint64)
+            if env_offsets.shape != offsets.shape or int(env_offsets[-1]) != env_keys.shape[0]:
+                raise ValueError("env_offsets should run from 0 to the number of environment keys, one entry "
+                                 "per entry of offsets")
+        out = np.zeros(max(t, 1), dtype=np.float64)
+        unresolved = np.zeros(max(segments, 1), dtype=np.uint64)
+        _lib.check(self._lib.asp_operator_field_segments(
+            self._handle, segments, _lib.ptr(offsets), _lib.ptr(keys), _lib.ptr(psi), _lib.ptr(env_offsets),
+            _lib.ptr(env_keys), _lib.ptr(env_psi), float(scale), _lib.ptr(out), _lib.ptr(unresolved)))
+        return out[:t], unresolved[:segments]
+
     def local_energy(self, keys, phi, offsets=None, rows=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Local energies of the signed amplitudes ``phi`` (any normalisation) over the table
         ``keys``, specification ASP-ELOC-1: ``(hphi f64[N], eloc f64[N],

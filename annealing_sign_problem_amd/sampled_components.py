@@ -296,7 +296,8 @@ def stage_clusters(clusters: Sequence[np.ndarray], hamiltonian, ground_state, no
     of one ``greedy_solve`` each; the results are the same.  ``external_field``: as in
     :func:`process_cluster`.  ``build_batch``: the staging runs level by level — for order i all
     clusters are extended (per cluster), the couplings of ALL their models are built in one segmented
-    device call (``common.make_ising_models``) and the models are sparsified (per
+    device call (``common.make_ising_models``; with ``external_field`` their boundary
+    fields in one more) and the models are sparsified (per
     cluster) — instead of cluster by cluster; the models and the results are the same.  ``level_batch``
     (with ``build_batch``): the extension and the sparsification of a level are ONE segmented device call
     each as well (``common.extend_and_sparsify_models``); the same models again.

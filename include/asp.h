@@ -388,6 +388,40 @@ int asp_operator_grow_segments(asp_operator const *op, uint64_t num_segments, ui
 int asp_operator_field(asp_operator const *op, uint64_t num_spins, uint64_t const *keys, double const *psi,
                        uint64_t num_env, uint64_t const *env_keys, double const *env_psi, double scale,
                        double *field, uint64_t *unresolved /* may be NULL */);
+/* The boundary fields of many clusters in one call, specification ASP-FIELD-SEG-1.
+ * num_segments clusters lie concatenated in keys / psi [T = offsets[num_segments]] and their
+ * environments in env_keys / env_psi [E = env_offsets[num_segments]]: cluster g is
+ * [offsets[g], offsets[g + 1]), its environment [env_offsets[g], env_offsets[g + 1]), each ascending
+ * and unique, the amplitudes in the cluster's normalisation.  Segments of either kind may be empty; a
+ * state may sit in any number of segments of either kind, and may be a cluster key of one segment and
+ * an environment key of another; a row of segment g sees segment g's cluster and segment g's
+ * environment only.  The law: for every segment g with n_g keys and e_g environment keys,
+ * field[offsets[g] : offsets[g + 1]] and unresolved[g] are what
+ *     asp_operator_field(op, n_g, keys + offsets[g], psi + offsets[g], e_g, env_keys + env_offsets[g],
+ *                        env_psi + env_offsets[g], scale, ...)
+ * returns: the field bit for bit (the sign of scale * +0.0 included), the count exactly.  With
+ * n_g = 0 nothing is written for g and unresolved[g] = 0; with e_g = 0, field = scale * +0.0.  Both
+ * variants of asp_operator_field are covered: lanes over the bonds for
+ * asp_operator_unique_targets(op) == 1, the device connection list otherwise.  Host pointers;
+ * unresolved (u64[num_segments]) may be NULL.
+ * Before any device work and before any output is written: ASP_ERR_INVALID for a null handle, null
+ * offsets or env_offsets with num_segments > 0, an offsets array that does not start at 0 or
+ * decreases, null keys / psi / field with T > 0, null env_keys / env_psi with E > 0, and a cluster or
+ * environment segment that is not ascending and unique (the message names the segment and the index
+ * within it); ASP_ERR_TOO_LARGE for T >= 2^32 - 1 or E >= 2^32 - 1 (the hashes store index + 1 in 32
+ * bits) and, in the connection-list variant, for T * max_connections >= 2^32.  A key of norm 0 in a
+ * -1 sector gives ASP_ERR_INVALID as in asp_operator_field, the message naming the first such
+ * segment, and no output is written.  T == 0 needs no device: unresolved is zeroed.  The number of
+ * launches and of host synchronisations — ONE (the download), or TWO in the connection-list variant
+ * (the size of the list, and the download) — does not depend on num_segments.  asp_operator_last_ms
+ * reports the device time. */
+int asp_operator_field_segments(asp_operator const *op, uint64_t num_segments,
+                                uint64_t const *offsets,      /* u64[S+1] over keys / psi, T = offsets[S] */
+                                uint64_t const *keys, double const *psi,
+                                uint64_t const *env_offsets,  /* u64[S+1] over env_keys / env_psi, E = env_offsets[S] */
+                                uint64_t const *env_keys, double const *env_psi,
+                                double scale, double *field /* f64[T] */,
+                                uint64_t *unresolved /* u64[S] or NULL */);
 
 /* Local energies of signed amplitudes, specification ASP-ELOC-1:
  *     E_loc(s) = sum_s' H_ss' phi_s' / phi_s
@@ -415,7 +449,8 @@ int asp_operator_local_energy(asp_operator const *op, uint64_t num_segments, uin
                               uint64_t const *rows, double *hphi, double *eloc, uint32_t *missing);
 
 /* Device time (ms, HIP events, no host<->HBM copies) of this thread's last
- * asp_operator_apply / _ising / _ising_segments / _extend / _field / _local_energy call. */
+ * asp_operator_apply / _ising / _ising_segments / _extend / _field / _field_segments / _local_energy
+ * call. */
 float asp_operator_last_ms(void);
 
 /* ------------------------------------------------------------------------- */
